@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- GAN train steps/sec of the HIP path on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one iteration of the reference's train_gan.py loop body (train_gan.py:159-203:
@@ -15,11 +15,19 @@ N > 1 is weak scaling: every rank trains its own 64-trajectory shard of a global
 steps: N * iterations/s.
 
 Timing: W warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize on both sides,
-maximum over ranks.  When K steps take less than ~50 ms the bracket is repeated R times back to
-back and the MEDIAN repetition is reported (`config.repeats`, all repetitions in
-`config.repeat_ms_per_step`): a 20-step run is 1.9 ms of GPU time, one sample of which says little.
+maximum over ranks; `ms_per_step` is that bracket over K.  A plain run does nothing else: set-up,
+warm-up, the K timed steps, the outputs (--dump-outputs), the JSON line.
 
-Rank 0 prints one JSON line (contract in the task statement) with extra objects:
+--dump-outputs DIR writes what a caller of the timed path holds after its last timed step, as float32
+.npy files: action_hat (G's actions of that step, [M, 4]), losses (D, G, NDiv), g_params, d_params
+(the flat parameters after its Adam updates).  Inputs and device noise are seeded, so two runs with
+the same arguments compute on the same data.
+
+--full adds everything that is not the headline figure.  When K steps take less than ~50 ms the
+bracket is repeated R times back to back and the MEDIAN repetition is reported (`config.repeats`,
+all repetitions in `config.repeat_ms_per_step`): a 20-step run is 1.9 ms of GPU time, one sample of
+which says little.  Rank 0's JSON line then also holds the step-0 parity figure against the oracle
+(`parity_step0`, N = 1) and these objects (--no-extras: roofline only; --no-cpu-baseline: no CPU runs):
   roofline     the dominant kernel of the step vs the fp32-MFMA peak (157.3 TFLOP/s):
                algorithmic FLOPs of that kernel per launch / its average duration, measured
                with HIP events on the launch stream (ndp_timing_*), plus every kernel's share;
@@ -110,13 +118,17 @@ def parse_args():
     ap.add_argument("--no-graph", action="store_true", help="launch kernels eagerly instead of replaying a HIP graph")
     ap.add_argument("--steps-per-launch", type=int, default=16,
                     help="iterations captured per HIP graph (each iteration has its own input slot)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs after its last step to DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the repeated bracket, step-0 parity, roofline, CPU baselines and the other workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="--full with headline + roofline only (profiling runs)")
     ap.add_argument("--force-dp", action="store_true",
                     help="run the data-parallel code path (non-fused Adam + RCCL all-reduce) even with one rank")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="repeat the K-step bracket until about this much GPU time has been sampled; report the median")
+                    help="--full: repeat the K-step bracket until about this much GPU time has been sampled; report the median")
     return ap.parse_args()
 
 
@@ -259,15 +271,15 @@ class Bench:
         for _ in range(n - done):
             tr.step()                  # device noise, resident inputs
 
-    def timed(self, tr, steps, warmup, stepper=None):
-        """Warm up, then R x (barrier, EXACTLY `steps` steps, barrier), maximum over ranks per repetition;
-        returns (median seconds per repetition, [seconds per repetition])."""
+    def timed(self, tr, steps, warmup, stepper=None, repeat=True):
+        """Warm up, then R x (barrier, EXACTLY `steps` steps, barrier), maximum over ranks per repetition
+        (repeat=False: R = 1); returns (median seconds per repetition, [seconds per repetition])."""
         self.barrier()
         self.run_steps(tr, max(warmup, 1), stepper)
         self.run_steps(tr, tr.nslots + 1, stepper)                        # both graphs exist before timing
         self.barrier()
         reps, total = [], 1
-        want = self.args.min_timed_ms * 1e-3
+        want = self.args.min_timed_ms * 1e-3 if repeat else 0.0
         while True:
             self.barrier()
             t0 = time.perf_counter()
@@ -281,6 +293,20 @@ class Bench:
             if len(reps) >= total:
                 break
         return statistics.median(reps), reps
+
+
+def step_outputs(tr, m):
+    """Host copies of what a caller of GanTrainer holds after the last step: G's actions for the M rows, the three
+    losses, the flat parameters after both Adam updates (copied now: --full steps the trainer again afterwards)."""
+    dev = {"action_hat": tr.action_hat[:m], "losses": tr.losses_dev[:3], "g_params": tr.g_flat, "d_params": tr.d_flat}
+    return {name: t.detach().to("cpu", torch.float32).clone() for name, t in dev.items()}
+
+
+def write_outputs(outputs, out_dir):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
 
 
 def step_flops(m):
@@ -700,10 +726,10 @@ def main():
         spl = args.steps          # a short bracket that is not a multiple of the default: one graph of exactly K steps
     tr = b.make_trainer(batch, k, flat * world, spl, b.p2p, b.reduce_fn, use_graph=graph_ok)
 
-    # step-0 parity figure (outside the timed region): NDiv / losses vs the oracle on rank 0's shard
+    # step-0 parity figure (--full, outside the timed region): NDiv / losses vs the oracle on rank 0's shard
     parity = None
     codes, actions, noise = O.synthetic_batch(1000 + rank, batch, k, NZ, steps=1)
-    if world == 1:
+    if world == 1 and args.full:
         ref = O.StepMath({n_: v.clone() for n_, v in b.g0.items()}, {n_: v.clone() for n_, v in b.d0.items()})
         out = ref.step(codes, actions, noise[0])
         tr.step(codes.to(dev), actions.to(dev), noise[0].to(dev))
@@ -737,10 +763,11 @@ def main():
 
     p2p_note = None
     while True:
-        elapsed, reps = b.timed(tr, args.steps, args.warmup)
+        elapsed, reps = b.timed(tr, args.steps, args.warmup, repeat=args.full)
+        outputs = step_outputs(tr, m) if args.dump_outputs else None
         losses = tr.losses()
         hip_graph = bool(tr.use_graph)
-        kernels = kernel_table(b, tr, m, k)
+        kernels = kernel_table(b, tr, m, k) if args.full else None
         replicas_identical = replicas_in_lockstep(tr) if world > 1 else None
         if b.p2p is None:
             break
@@ -774,7 +801,7 @@ def main():
         except Exception as exc:                                           # noqa: BLE001
             extra_errors[name] = repr(exc)[:300]
             b.log("extra %s failed: %r" % (name, exc))
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         if world > 1:
             nsteps = min(args.steps, 400)
 
@@ -878,10 +905,6 @@ def main():
 
     iters_per_s = args.steps / elapsed
     value = iters_per_s * world
-    table = kernel_macs(k)[0]
-    dom = max((n_ for n_ in kernels if table.get(n_)), key=lambda n_: kernels[n_]["avg_us"] * kernels[n_]["launches_per_step"])
-    dom_flops = 2.0 * table[dom] * m                     # what the kernel executes per launch
-    achieved = dom_flops / (kernels[dom]["avg_us"] * 1e-6) / 1e12
     result = {
         "metric": "gan_train_steps_per_sec_traj8_batch64", "value": round(value, 2), "unit": "steps/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -898,34 +921,42 @@ def main():
                    "gradient_exchange": b.exchange, "all_reduce_us": dict(b.dp.last_exchange_report) or None,
                    "replicas_bit_identical": replicas_identical, "exchange_note": p2p_note,
                    "last_losses": {"D": losses[0], "G": losses[1], "ndiv": losses[2]}},
-        "roofline": {"bound": "mfma", "kernel": dom, "achieved": round(achieved, 3), "peak": MFMA_F32_PEAK_TFLOPS,
-                     "unit": "TFLOP/s", "frac": round(achieved / MFMA_F32_PEAK_TFLOPS, 4),
-                     # the same launch priced at the reference's work (D's real pass on all M rows, as round 1 counted it
-                     # before the real pass was deduplicated): comparable across rounds
-                     "achieved_reference_equivalent": round(achieved * kernel_macs(1)[0][dom] / table[dom], 3),
-                     "frac_reference_equivalent": round(achieved * kernel_macs(1)[0][dom] / table[dom] / MFMA_F32_PEAK_TFLOPS, 4),
-                     "traffic": PMC_HBM_BYTES_DEFAULT.get(dom) if (batch, k) == (64, 6) else None,
-                     "traffic_source": PMC_SOURCE,
-                     "mfma_busy_counter": PMC_MFMA_BUSY_DEFAULT.get(dom) if (batch, k) == (64, 6) else None,
-                     "mfma_busy_source": PMC_MFMA_SOURCE,
-                     "algorithmic_flops_per_launch": dom_flops,
-                     "flops_note": "per-kernel figures count the MACs executed: D's real pass runs on the FLAT distinct "
-                                   "rows (1/K of what the reference feeds through D, train_gan.py:140-156)",
-                     "whole_step": {"flops": step_flops(m),
-                                    "tflops": round(step_flops(m) * iters_per_s / 1e12, 3),
-                                    "frac": round(step_flops(m) * iters_per_s / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
-                                    "flops_executed": step_flops_executed(m, k),
-                                    "frac_executed": round(step_flops_executed(m, k) * iters_per_s / 1e12 / MFMA_F32_PEAK_TFLOPS, 4)},
-                     "kernels": kernels},
     }
+    if kernels is not None:
+        table = kernel_macs(k)[0]
+        dom = max((n_ for n_ in kernels if table.get(n_)), key=lambda n_: kernels[n_]["avg_us"] * kernels[n_]["launches_per_step"])
+        dom_flops = 2.0 * table[dom] * m                     # what the kernel executes per launch
+        achieved = dom_flops / (kernels[dom]["avg_us"] * 1e-6) / 1e12
+        result["roofline"] = {
+            "bound": "mfma", "kernel": dom, "achieved": round(achieved, 3), "peak": MFMA_F32_PEAK_TFLOPS,
+            "unit": "TFLOP/s", "frac": round(achieved / MFMA_F32_PEAK_TFLOPS, 4),
+            # the same launch priced at the reference's work (D's real pass on all M rows, as round 1 counted it
+            # before the real pass was deduplicated): comparable across rounds
+            "achieved_reference_equivalent": round(achieved * kernel_macs(1)[0][dom] / table[dom], 3),
+            "frac_reference_equivalent": round(achieved * kernel_macs(1)[0][dom] / table[dom] / MFMA_F32_PEAK_TFLOPS, 4),
+            "traffic": PMC_HBM_BYTES_DEFAULT.get(dom) if (batch, k) == (64, 6) else None,
+            "traffic_source": PMC_SOURCE,
+            "mfma_busy_counter": PMC_MFMA_BUSY_DEFAULT.get(dom) if (batch, k) == (64, 6) else None,
+            "mfma_busy_source": PMC_MFMA_SOURCE,
+            "algorithmic_flops_per_launch": dom_flops,
+            "flops_note": "per-kernel figures count the MACs executed: D's real pass runs on the FLAT distinct "
+                          "rows (1/K of what the reference feeds through D, train_gan.py:140-156)",
+            "whole_step": {"flops": step_flops(m),
+                           "tflops": round(step_flops(m) * iters_per_s / 1e12, 3),
+                           "frac": round(step_flops(m) * iters_per_s / 1e12 / MFMA_F32_PEAK_TFLOPS, 4),
+                           "flops_executed": step_flops_executed(m, k),
+                           "frac_executed": round(step_flops_executed(m, k) * iters_per_s / 1e12 / MFMA_F32_PEAK_TFLOPS, 4)},
+            "kernels": kernels}
     if parity is not None:
         result["parity_step0"] = {k_: float("%.3e" % v) for k_, v in parity.items()}
     result.update(extras)
     if extra_errors:
         result["extras_failed"] = extra_errors
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(batch, k, NZ, args.cpu_seconds)
         result["cpu_baseline"]["gpu_over_cpu"] = round(value / result["cpu_baseline"]["value"], 1)
+    if outputs is not None:
+        write_outputs(outputs, args.dump_outputs)
     print(json.dumps(result))
     if dist.is_initialized():
         dist.destroy_process_group()
