@@ -86,20 +86,6 @@ struct KTimer {
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 static inline int64_t pad_rows(int64_t rows) { return (rows + NDP_ROW_PAD - 1) / NDP_ROW_PAD * NDP_ROW_PAD; }
 
-// rows per tile = 16*RT.  Measured (bench.py --batch 192..2048, K = 6 and 32): 16-row tiles win
-// at every size -- their LDS footprint lets 2+ workgroups share a CU, which hides more latency
-// than the halved weight traffic of 32-row tiles buys.  NDP_RT=2 selects 32-row tiles for
-// experiments.
-static int pick_rt(int64_t m) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("NDP_RT");
-    forced = (e && (e[0] == '1' || e[0] == '2')) ? e[0] - '0' : 0;
-  }
-  (void)m;
-  return forced ? forced : 1;
-}
-
 template <typename K>
 static void allow_lds(K kernel, int bytes) {
   // dynamic LDS above 64 KiB must be opted into once per kernel
@@ -119,29 +105,25 @@ static_assert(phase_a_lds_floats() * 4 * 3 <= 160 * 1024, "phase A: three workgr
 
 static void set_attrs() {
   std::call_once(device_once(g_attr_once), [] {
-#define NDP_ATTR_GFWD(RT, WA) \
-    allow_lds(k_g_fwd<RT, WA, false>, g_fwd_lds_floats<RT>() * 4); \
-    allow_lds(k_g_fwd<RT, WA, true>, g_fwd_lds_floats<RT>() * 4);
-    NDP_ATTR_GFWD(1, 1) NDP_ATTR_GFWD(1, 2) NDP_ATTR_GFWD(1, 4)
-    NDP_ATTR_GFWD(2, 1) NDP_ATTR_GFWD(2, 2) NDP_ATTR_GFWD(2, 4)
+#define NDP_ATTR_GFWD(WA) \
+    allow_lds(k_g_fwd<WA, false>, g_fwd_lds_floats() * 4); \
+    allow_lds(k_g_fwd<WA, true>, g_fwd_lds_floats() * 4);
+    NDP_ATTR_GFWD(1) NDP_ATTR_GFWD(2) NDP_ATTR_GFWD(4)
 #undef NDP_ATTR_GFWD
-#define NDP_ATTR_D(RT, NP) \
-    allow_lds(k_d<RT, NP, false>, (d_lds_floats<RT, NP>() * 4)); \
-    allow_lds(k_d<RT, NP, true>, (d_lds_floats<RT, NP>() * 4));
-    NDP_ATTR_D(1, 1) NDP_ATTR_D(2, 1) NDP_ATTR_D(1, 2)
+#define NDP_ATTR_D(NP) \
+    allow_lds(k_d<NP, false>, (d_lds_floats<NP>() * 4)); \
+    allow_lds(k_d<NP, true>, (d_lds_floats<NP>() * 4));
+    NDP_ATTR_D(1) NDP_ATTR_D(2)
 #undef NDP_ATTR_D
-    allow_lds(k_g_bwd<1, false>, g_bwd_lds_floats<1>() * 4);
-    allow_lds(k_g_bwd<1, true>, g_bwd_lds_floats<1>() * 4);
-    allow_lds(k_g_bwd<2, false>, g_bwd_lds_floats<2>() * 4);
-    allow_lds(k_g_bwd<2, true>, g_bwd_lds_floats<2>() * 4);
+    allow_lds(k_g_bwd<false>, g_bwd_lds_floats() * 4);
+    allow_lds(k_g_bwd<true>, g_bwd_lds_floats() * 4);
     allow_lds(k_wgrad, wgrad_lds_floats() * 4);
     allow_lds(k_wgrad_wide, wgrad_wide_launch_lds_floats() * 4);
 #define NDP_ALLOW_A(RG, NR) allow_lds((k_phase_a<true, RG, NR>), phase_a_lds_floats() * 4)
 #define NDP_ALLOW_B(RG, PRE, NR) allow_lds((k_phase_b<true, RG, PRE, NR>), phase_b_lds_floats(PRE) * 4)
     NDP_ALLOW_A(96, 0);
-    NDP_ALLOW_A(NDP_PHASE_A_SMALL_RING, 0); NDP_ALLOW_A(NDP_PHASE_A_SMALL_RING, 1); NDP_ALLOW_A(NDP_PHASE_A_SMALL_RING, 4);
+    NDP_ALLOW_A(kPhaseASmallRing, 0); NDP_ALLOW_A(kPhaseASmallRing, 1); NDP_ALLOW_A(kPhaseASmallRing, 4);
     NDP_ALLOW_B(96, true, 0);
-    NDP_ALLOW_B(96, false, 0);
     NDP_ALLOW_B(32, false, 0); NDP_ALLOW_B(32, false, 1); NDP_ALLOW_B(32, false, 4);
 #undef NDP_ALLOW_A
 #undef NDP_ALLOW_B
@@ -261,12 +243,6 @@ static GActs g_acts(float* base, int64_t mpad) {
 }
 // split-K chunking of the weight-gradient rows
 static int wgrad_chunks(int njobs, int64_t rows) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("NDP_WGRAD_CHUNKS");
-    forced = e ? atoi(e) : 0;
-  }
-  if (forced > 0) return forced > 64 ? 64 : forced;
   int64_t want = 512 / njobs;                          // jobs*chunks <= 512 = 2 workgroups per CU (64 KiB LDS each): one resident round
   if (want >= 8) want = want / 8 * 8;                  // whole chunks per XCD (k_wgrad deals chunk c to XCD c % 8)
   // With many rows the light jobs (K-deduplicated fc1 columns, the 1- and 4-wide layers) retire
@@ -284,67 +260,35 @@ constexpr int kGJobs = 26, kDJobs = 19;
 // fc2 / fc3 of D), `light` for the K-deduplicated fc1 blocks and the 1..4-wide operands, which finish in half the
 // time (stamps): at small M giving the heavy jobs more, shorter chunks and the light ones fewer keeps the launch
 // within one resident round (<= 512 workgroups) and shortens its critical path.  heavy >= light; heavy is the slab
-// count.  NDP_WGRAD_CHUNKS forces a uniform count, NDP_WGRAD_HD / LD / HG / LG the two of D and of G.
-static int wgrad_wide_chunks(int64_t rows, bool is_g = false);
+// count.  From 16,384 rows, or where the heavy count would leave a chunk fewer than 64 rows, both are wgrad_chunks.
 static void wgrad_plan(bool is_g, int64_t rows, int* heavy, int* light) {
-  static int fh[2] = {-1, -1}, fl[2] = {-1, -1}, forced_uniform = -1;
-  if (forced_uniform < 0) {
-    const char* e = getenv("NDP_WGRAD_HD"); fh[0] = e ? atoi(e) : 0;
-    e = getenv("NDP_WGRAD_LD"); fl[0] = e ? atoi(e) : 0;
-    e = getenv("NDP_WGRAD_HG"); fh[1] = e ? atoi(e) : 0;
-    e = getenv("NDP_WGRAD_LG"); fl[1] = e ? atoi(e) : 0;
-    forced_uniform = getenv("NDP_WGRAD_CHUNKS") != nullptr;
-  }
-  const int uniform = wgrad_chunks(is_g ? kGJobs : kDJobs, rows);
   // measured: G 24 at config 2; D (whose real pass is deduplicated: FLAT + M rows) 8 up to 4,096 rows -- 152 workgroups
   // and 8 slabs, 79.0 vs 80.3 us per step at B = 64, 75.2 vs 76.8 at B = 32 -- and 32 above (B = 128, 192)
   // (G's light jobs: 12 chunks, 12,788 vs 12,742 steps/s with 8 at config 2, three alternating runs each)
-  int h = fh[is_g] > 0 ? fh[is_g] : (is_g ? 24 : (rows <= 4096 ? 8 : 32)), l = fl[is_g] > 0 ? fl[is_g] : (is_g ? 12 : 8);
-  if (forced_uniform || rows >= 16384 || rows / 64 < h || l > h) { *heavy = *light = uniform; return; }
+  const int h = is_g ? 24 : (rows <= 4096 ? 8 : 32), l = is_g ? 12 : 8;
+  if (rows >= 16384 || rows / 64 < h) { *heavy = *light = wgrad_chunks(is_g ? kGJobs : kDJobs, rows); return; }
   *heavy = h; *light = l;
 }
-// Large M: the 256 x 128 layer (D.fc3, G.fc4) as ONE LDS-staged job per row chunk (k_wgrad, WG_WIDE) instead of eight
-// 64 x 64 jobs; its workgroups carry 8 x the work of a 64 x 64 job per row, so it gets its own, larger chunk count (and
-// as many slabs: that layer's parameters are a region of the slab sum).  0: not used.  NDP_WGRAD_WIDE=0 turns it off,
-// =N forces N chunks (a multiple of 8).
-// 1: the layer as one 256 x 128 job per chunk; 2: as two 128 x 128 jobs (NDP_WGRAD_WIDE_SPLIT)
-static int wgrad_wide_split() {
-  static int v = 0;
-  if (v == 0) {
-    const char* e = getenv("NDP_WGRAD_WIDE_SPLIT");
-    v = (e && e[0] == '1') ? 1 : 2;
-  }
-  return v;
-}
-static int wgrad_wide_chunks(int64_t rows, bool is_g) {
-  static int forced = -2;
-  if (forced == -2) {
-    const char* e = getenv("NDP_WGRAD_WIDE");
-    forced = e ? atoi(e) : -1;
-  }
-  if (forced == 0) return 0;
-  if (rows < 16384) return 0;
+// Large M: the 256 x 128 layer (D.fc3, G.fc4) as two LDS-staged 128 x 128 jobs per row chunk (k_wgrad_wide, WG_WIDE)
+// instead of eight 64 x 64 jobs; their workgroups carry 4 x the work of a 64 x 64 job per row, so they get their own,
+// larger chunk count (and as many slabs: that layer's parameters are a region of the slab sum).  0: not used.
+static int wgrad_wide_chunks(int64_t rows) {
   // from 28,000 rows (below, the 64 x 64 jobs win: B = 512 / K = 6, 25,088 / 21,504 rows, 0.2869 vs 0.2929 ms; B = 384 / K = 6
   // 0.2254 vs 0.2347), a multiple of 32 chunks (56 chunks were 6 us slower than 64 at 28,672 rows),
-  if (rows < 28000 && forced <= 0) return 0;
+  if (rows < 28000) return 0;
   // about 480 rows per chunk (two 128 x 128 jobs per chunk: ~30 slabs of 16 rows per workgroup).  Measured with the layer
-  // split in two jobs (scripts/probe/gpu_session_r3q.sh): B = 128 / K = 32 (29,568 / 28,672 rows) 64 chunks 0.3191 ms per
+  // split in two jobs (commit 2abfcda): B = 128 / K = 32 (29,568 / 28,672 rows) 64 chunks 0.3191 ms per
   // step (48: 0.3326, 80: 0.3212, 96: 0.3263, 128: 0.3542; without the WIDE jobs 0.3290), B = 1024 / K = 6 (50,176 rows)
   // 96 chunks 0.4963 (64: 0.5084; without 0.5158).  As ONE 256 x 128 job per chunk the layer needed 128-160 chunks
   // and the slab sums grew by 4 us each: 0.3247 / 0.5027.
-  (void)is_g;
-  int64_t want = forced > 0 ? forced : (rows / 480 + 16) / 32 * 32;
-  if (forced <= 0 && want < 64) want = 64;
-  const int64_t maxc = rows / 64;
-  if (want > maxc) want = maxc;
-  want = want / 8 * 8;
-  return (int)(want < 8 ? 0 : want);
+  const int64_t want = (rows / 480 + 16) / 32 * 32;
+  return (int)(want < 64 ? 64 : want);
 }
 // slabs a launch may write: the 64 x 64 jobs' chunk count or the WIDE job's, whichever is larger
 static int wgrad_slabs(bool is_g, int64_t rows) {
   int h, l;
   wgrad_plan(is_g, rows, &h, &l);
-  const int w = wgrad_wide_chunks(rows, is_g);
+  const int w = wgrad_wide_chunks(rows);
   return h > w ? h : w;
 }
 // G backward scratch: dy1 | dy2 | dy3 | dy4 | dy5 | slabs
@@ -399,60 +343,47 @@ static int launch_g_fwd(const GNet& net, const float* code, int64_t ld_code, int
   a.h3 = acts ? acts->h3 : nullptr; a.h4 = acts ? acts->h4 : nullptr;
   a.action_hat = action_hat;
   a.noise_out = gen ? gen->out : nullptr; a.noise_seed = gen ? gen->seed : 0; a.noise_step = gen ? gen->step : nullptr;
-  const int rt = pick_rt(m);
-  const int64_t mpad = pad_rows(m);
   const int walign = (net.ld1 % 4 == 0) ? 4 : (net.ld1 % 2 == 0 ? 2 : 1);
-  const dim3 grid((unsigned)(mpad / (16 * rt)));
+  const dim3 grid((unsigned)(pad_rows(m) / 16));
   const bool pk = net.pf1 != nullptr;
-#define NDP_LAUNCH_GFWD(RT, WA) \
+#define NDP_LAUNCH_GFWD(WA) \
   do { \
-    if (pk) hipLaunchKernelGGL((k_g_fwd<RT, WA, true>), grid, dim3(kThreads), g_fwd_lds_floats<RT>() * 4, st, a); \
-    else hipLaunchKernelGGL((k_g_fwd<RT, WA, false>), grid, dim3(kThreads), g_fwd_lds_floats<RT>() * 4, st, a); \
+    if (pk) hipLaunchKernelGGL((k_g_fwd<WA, true>), grid, dim3(kThreads), g_fwd_lds_floats() * 4, st, a); \
+    else hipLaunchKernelGGL((k_g_fwd<WA, false>), grid, dim3(kThreads), g_fwd_lds_floats() * 4, st, a); \
   } while (0)
   KTimer kt("k_g_fwd", st);
-  if (rt == 1) {
-    if (walign == 4) NDP_LAUNCH_GFWD(1, 4); else if (walign == 2) NDP_LAUNCH_GFWD(1, 2); else NDP_LAUNCH_GFWD(1, 1);
-  } else {
-    if (walign == 4) NDP_LAUNCH_GFWD(2, 4); else if (walign == 2) NDP_LAUNCH_GFWD(2, 2); else NDP_LAUNCH_GFWD(2, 1);
-  }
+  if (walign == 4) NDP_LAUNCH_GFWD(4); else if (walign == 2) NDP_LAUNCH_GFWD(2); else NDP_LAUNCH_GFWD(1);
 #undef NDP_LAUNCH_GFWD
   return check_launch("k_g_fwd");
 }
 
-// rows per pass per workgroup: the 2-pass D step always stacks 16 real + 16 fake rows
-static int d_rt(int64_t m, int npass) { return npass == 2 ? 1 : pick_rt(m); }
-static int d_ntiles(int64_t m, int npass) { return (int)(pad_rows(m) / (16 * d_rt(m, npass))); }
-
+// Every kernel of the step works on 16-row tiles; the 2-pass D step stacks 16 real + 16 fake rows per workgroup.
+// Measured (bench.py --batch 192..2048, K = 6 and 32): 16-row tiles win at every size -- their LDS footprint lets 2+
+// workgroups share a CU, which hides more latency than the halved weight traffic of 32-row tiles bought.
 static int launch_d(DArgs& a, int npass, int nd_blocks, hipStream_t st) {
   set_attrs();
-  const int rt = d_rt(a.m, npass);
-  a.ntiles = (int)(a.mpad / (16 * rt));
+  a.ntiles = (int)(a.mpad / 16);
   if (nd_blocks == 0) a.nd.n = 0;
   const dim3 grid((unsigned)(a.ntiles + nd_blocks));
   KTimer kt(a.do_backward ? (npass == 2 ? "k_d[2 pass fwd+bwd]" : "k_d[fwd+bwd]") : "k_d[fwd]", st);
   const bool pk = a.net.pf1 != nullptr;
-#define NDP_LAUNCH_D(RT, NP) \
+#define NDP_LAUNCH_D(NP) \
   do { \
-    if (pk) hipLaunchKernelGGL((k_d<RT, NP, true>), grid, dim3(kThreads), (d_lds_floats<RT, NP>() * 4), st, a); \
-    else hipLaunchKernelGGL((k_d<RT, NP, false>), grid, dim3(kThreads), (d_lds_floats<RT, NP>() * 4), st, a); \
+    if (pk) hipLaunchKernelGGL((k_d<NP, true>), grid, dim3(kThreads), (d_lds_floats<NP>() * 4), st, a); \
+    else hipLaunchKernelGGL((k_d<NP, false>), grid, dim3(kThreads), (d_lds_floats<NP>() * 4), st, a); \
   } while (0)
-  if (npass == 2) NDP_LAUNCH_D(1, 2);
-  else if (rt == 1) NDP_LAUNCH_D(1, 1);
-  else NDP_LAUNCH_D(2, 1);
+  if (npass == 2) NDP_LAUNCH_D(2);
+  else NDP_LAUNCH_D(1);
 #undef NDP_LAUNCH_D
   return check_launch("k_d");
 }
 
 static int launch_g_bwd(GBwdArgs& a, hipStream_t st) {
   set_attrs();
-  const int rt = pick_rt(a.m);
-  const dim3 grid((unsigned)(pad_rows(a.m) / (16 * rt)));
+  const dim3 grid((unsigned)(pad_rows(a.m) / 16));
   KTimer kt("k_g_bwd", st);
-  const bool pk = a.net.pg2 != nullptr;
-  if (rt == 1 && pk) hipLaunchKernelGGL((k_g_bwd<1, true>), grid, dim3(kThreads), g_bwd_lds_floats<1>() * 4, st, a);
-  else if (rt == 1) hipLaunchKernelGGL((k_g_bwd<1, false>), grid, dim3(kThreads), g_bwd_lds_floats<1>() * 4, st, a);
-  else if (pk) hipLaunchKernelGGL((k_g_bwd<2, true>), grid, dim3(kThreads), g_bwd_lds_floats<2>() * 4, st, a);
-  else hipLaunchKernelGGL((k_g_bwd<2, false>), grid, dim3(kThreads), g_bwd_lds_floats<2>() * 4, st, a);
+  if (a.net.pg2 != nullptr) hipLaunchKernelGGL((k_g_bwd<true>), grid, dim3(kThreads), g_bwd_lds_floats() * 4, st, a);
+  else hipLaunchKernelGGL((k_g_bwd<false>), grid, dim3(kThreads), g_bwd_lds_floats() * 4, st, a);
   return check_launch("k_g_bwd");
 }
 
@@ -501,7 +432,7 @@ static void build_g_jobs(WgradArgs& w, int nz, const GBwdWs& ws, const GActs& ac
   for (int jb = 0; jb < 2; ++jb)                         // fc3: [128 x 64]
     w.job[n++] = make_job(ws.dy3 + jb * 64, 128, 64, acts.h2, 64, 64, L.w3 + (int64_t)jb * 64 * 64, 64,
                           L.b3 + jb * 64, WG_FULL);
-  const int wide = wgrad_wide_chunks(pad_rows(m), true);
+  const int wide = wgrad_wide_chunks(pad_rows(m));
   if (!wide)
     for (int jb = 0; jb < 4; ++jb)                       // fc4: [256 x 128]
       for (int kb = 0; kb < 2; ++kb)
@@ -514,11 +445,9 @@ static void build_g_jobs(WgradArgs& w, int nz, const GBwdWs& ws, const GActs& ac
   w.nwide = 0; w.wide_chunks = 0;
   w.wide_begin = w.wide_end = 0;
   if (wide) {                                            // fc4 as LDS-staged jobs per row chunk (large M)
-    w.nwide = wgrad_wide_split();
-    for (int h = 0; h < w.nwide; ++h) {
-      const int aw = 256 / w.nwide;
-      w.job[n + h] = make_job(ws.dy4 + h * aw, 256, aw, acts.h3, 128, 128, L.w4 + (int64_t)h * aw * 128, 128, L.b4 + h * aw, WG_WIDE);
-    }
+    w.nwide = 2;
+    for (int h = 0; h < 2; ++h)
+      w.job[n + h] = make_job(ws.dy4 + h * 128, 256, 128, acts.h3, 128, 128, L.w4 + (int64_t)h * 128 * 128, 128, L.b4 + h * 128, WG_WIDE);
     w.wide_chunks = wide;
     w.wide_begin = (int)L.w4; w.wide_end = (int)L.b4 + 256;
   }
@@ -564,11 +493,9 @@ static void build_d_jobs(WgradArgs& w, const DBwdWs& ws, const float* code, int6
   w.nwide = 0; w.wide_chunks = 0;
   w.wide_begin = w.wide_end = 0;
   if (wide) {                                            // fc3 as LDS-staged jobs per row chunk (large M)
-    w.nwide = wgrad_wide_split();
-    for (int h = 0; h < w.nwide; ++h) {
-      const int aw = 256 / w.nwide;
-      w.job[n + h] = make_job(ws.dy3 + h * aw, 256, aw, ws.h2, 128, 128, L.w3 + (int64_t)h * aw * 128, 128, L.b3 + h * aw, WG_WIDE);
-    }
+    w.nwide = 2;
+    for (int h = 0; h < 2; ++h)
+      w.job[n + h] = make_job(ws.dy3 + h * 128, 256, 128, ws.h2, 128, 128, L.w3 + (int64_t)h * 128 * 128, 128, L.b3 + h * 128, WG_WIDE);
     w.wide_chunks = wide;
     w.wide_begin = (int)L.w3; w.wide_end = (int)L.b3 + 256;
   }
@@ -838,37 +765,10 @@ struct StepWs {
   float* g_packed; float* d_packed;
   float* d_seg; float* g_seg;    // segment sums of dY1 for the K-deduplicated fc1 weight gradients
 };
-static bool phase_a_small_ring(int64_t workgroups) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("NDP_PHASE_A_RING");
-    forced = e ? (e[0] == 's' ? 1 : 2) : 0;        // "small" / "large" override for experiments
-  }
-  if (forced) return forced == 1;
-  return workgroups > 256;                         // more workgroups than CUs: several per CU, small rings
-}
-
-// phase B fetches G's activations at kernel start into LDS of their own (one workgroup per CU: nothing else hides
-// the mid-kernel round trip)
-static bool phase_b_prefetch(int ntiles) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("NDP_PHASE_B_PREFETCH");
-    forced = e ? (e[0] == '1' ? 1 : 2) : 0;
-  }
-  if (forced) return forced == 1;
-  return ntiles <= 256;
-}
-
-static bool phase_b_small_ring(int64_t ntiles) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("NDP_PHASE_B_RING");
-    forced = e ? (e[0] == 's' ? 1 : 2) : 0;
-  }
-  if (forced) return forced == 1;
-  return ntiles > 256;                             // more tiles than CUs
-}
+// More workgroups than CUs: several per CU, small weight rings.  Up to 256 workgroups each sits alone on a CU with
+// 96-register rings; phase B's then also fetches G's activations at kernel start into LDS of their own (nothing else
+// hides the mid-kernel round trip).
+static bool several_per_cu(int64_t workgroups) { return workgroups > 256; }
 
 // The K samples of a flat row share its code: a 16-row tile holds 1 distinct code row when K % 16 == 0 and at most 4
 // when K >= 6 -- fc1's code columns become that many dot-product rows per tile on the VALU (code_rows_dot in
@@ -876,14 +776,9 @@ static bool phase_b_small_ring(int64_t ntiles) {
 // It pays only where the matrix pipe is the bound -- several workgroups per CU, the small-ring variants: B = 1024 / K = 6
 // 0.529 -> 0.518 ms, B = 128 / K = 32 0.351 -> 0.334 ms.  With one workgroup per CU the MFMA k-loop of fc1 runs while the
 // next layers' weights stream in, and the VALU + LDS work that would replace it is longer (measured: config 2 with four
-// rows, phase A 27.0 -> 30.4 us; B = 8 / K = 32 with one row, 27.3 -> 28.2 us).  NDP_STEP_CODE_ROWS=0 switches it off.
+// rows, phase A 27.0 -> 30.4 us; B = 8 / K = 32 with one row, 27.3 -> 28.2 us).
 static int step_code_rows(int K, bool several_per_cu) {
-  static int enabled = -1;
-  if (enabled < 0) {
-    const char* e = getenv("NDP_STEP_CODE_ROWS");
-    enabled = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!enabled || !several_per_cu) return 0;
+  if (!several_per_cu) return 0;
   return K % 16 == 0 ? 1 : (K >= 6 ? 4 : 0);
 }
 
@@ -1064,7 +959,7 @@ int ndp_step_d_grads(const ndp_step_config* c, const ndp_step_buffers* b, const 
   NdivArgs nd;
   if (fused_ndiv)   // NDiv loss + gradient (train_gan.py:193-199; gradient pre-scaled by pairwise_div_factor)
     nd = ndiv_args(b->action_hat, ADIM, noise, nz, c->flat, K, c->pairwise_div_factor, ws.nd_grad, ws.nd_part, kThreads);
-  int loss_count = d_ntiles(m, 2);                 // workgroups that wrote a BCE partial
+  int loss_count = (int)(mpad / 16);            // workgroups that wrote a BCE partial
   if (run_g_forward) {
     // G forward + D(real) + D(fake) + BCE + D's backward data path in one launch
     set_attrs();
@@ -1087,12 +982,13 @@ int ndp_step_d_grads(const ndp_step_config* c, const ndp_step_buffers* b, const 
     // one workgroup per fake tile (G + D) and one per tile of distinct real rows; up to 256 of them sit alone on a CU
     // each with deep weight rings, more share CUs (three per CU by LDS) with small ones
     loss_count = (int)(mpad / 16 + rpad / 16);
-    const int nr = step_code_rows(K, phase_a_small_ring(loss_count));
+    const bool small = several_per_cu(loss_count);
+    const int nr = step_code_rows(K, small);
 #define NDP_LAUNCH_A(RG, NR) hipLaunchKernelGGL((k_phase_a<true, RG, NR>), dim3((unsigned)loss_count), dim3(kThreads), phase_a_lds_floats() * 4, st, pa)
-    if (phase_a_small_ring(loss_count)) {
-      if (nr == 1) NDP_LAUNCH_A(NDP_PHASE_A_SMALL_RING, 1);
-      else if (nr == 4) NDP_LAUNCH_A(NDP_PHASE_A_SMALL_RING, 4);
-      else NDP_LAUNCH_A(NDP_PHASE_A_SMALL_RING, 0);
+    if (small) {
+      if (nr == 1) NDP_LAUNCH_A(kPhaseASmallRing, 1);
+      else if (nr == 4) NDP_LAUNCH_A(kPhaseASmallRing, 4);
+      else NDP_LAUNCH_A(kPhaseASmallRing, 0);
     } else {
       NDP_LAUNCH_A(96, 0);
     }
@@ -1172,13 +1068,16 @@ int ndp_step_g_grads(const ndp_step_config* c, const ndp_step_buffers* b, const 
   {
     KTimer kt("k_phase_b", st);
     const int nt = (int)(mpad / 16);
-    const int nr = step_code_rows(K, phase_b_small_ring(nt));
+    const bool small = several_per_cu(nt);
+    const int nr = step_code_rows(K, small);
 #define NDP_LAUNCH_B(RG, PRE, NR) hipLaunchKernelGGL((k_phase_b<true, RG, PRE, NR>), dim3((unsigned)nt), dim3(kThreads), phase_b_lds_floats(PRE) * 4, st, pb)
-#define NDP_LAUNCH_B3(RG, PRE) do { if (nr == 1) NDP_LAUNCH_B(RG, PRE, 1); else if (nr == 4) NDP_LAUNCH_B(RG, PRE, 4); else NDP_LAUNCH_B(RG, PRE, 0); } while (0)
-    if (phase_b_small_ring(nt)) NDP_LAUNCH_B3(32, false);
-    else if (phase_b_prefetch(nt)) NDP_LAUNCH_B(96, true, 0);
-    else NDP_LAUNCH_B(96, false, 0);
-#undef NDP_LAUNCH_B3
+    if (small) {
+      if (nr == 1) NDP_LAUNCH_B(32, false, 1);
+      else if (nr == 4) NDP_LAUNCH_B(32, false, 4);
+      else NDP_LAUNCH_B(32, false, 0);
+    } else {
+      NDP_LAUNCH_B(96, true, 0);
+    }
 #undef NDP_LAUNCH_B
   }
   rc = check_launch("k_phase_b");

@@ -2082,6 +2082,10 @@ static FmStatFin fm_fin(int slot, int what, int64_t P, const FmWs& ws) {
   return f;
 }
 
+// Workgroups a K-split launch aims for: one per CU (a target of 512 -- two per CU -- measured 2 % slower at batch 8 and
+// 32: the partial sums cost more than the second workgroup hides).
+constexpr int kFmSplitTarget = 256;
+
 // out = act(bias + gather-GEMM) [+ out]; see k_fm_gemm for the modes.  GH = grid of rows per image (square maps).
 // rq: statistics of the finished output, from this launch's epilogue or -- with a K split -- from the split sums'.
 static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int SH, int ss, const float* w, const float* bias,
@@ -2096,20 +2100,13 @@ static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int 
   a.mode = mode; a.KH = a.KW = KH; a.pad = pad; a.act = act; a.accumulate = accumulate; a.zero_to = zero_to;
   if (mode == 3 && a.M <= 64 && C <= kFmRowsMaxC && C % 32 == 0 && N % 16 == 0 && zero_to == 0) {
     // a few images: one wave per (class, 16 columns), weights straight into MFMA operands (k_fm_rows_cls)
-    static int rows_on = -1;
-    if (rows_on < 0) {
-      const char* e = getenv("NDP_FM_ROWS");                           // experiments
-      rows_on = e ? atoi(e) : 1;
-    }
-    if (rows_on) {
-      const FmEpReq none0 = fm_ep_none();
-      fm_ep_fill(a.ep, rq ? *rq : none0, ws);
-      a.nsplit = 1;
-      const unsigned blocks = (unsigned)((16 * (N / 16) + kWaves - 1) / kWaves);
-      KTimer kt(label, st);
-      hipLaunchKernelGGL(k_fm_rows_cls, dim3(blocks), dim3(kThreads), 0, st, a);
-      return check_launch("k_fm_rows_cls");
-    }
+    const FmEpReq none0 = fm_ep_none();
+    fm_ep_fill(a.ep, rq ? *rq : none0, ws);
+    a.nsplit = 1;
+    const unsigned blocks = (unsigned)((16 * (N / 16) + kWaves - 1) / kWaves);
+    KTimer kt(label, st);
+    hipLaunchKernelGGL(k_fm_rows_cls, dim3(blocks), dim3(kThreads), 0, st, a);
+    return check_launch("k_fm_rows_cls");
   }
   const int ncls = mode == 0 ? 1 : (mode == 3 ? 16 : 4);
   const int maxtaps = mode == 0 ? KH * KH : (mode == 3 ? 1 : 4);
@@ -2117,32 +2114,21 @@ static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int 
   const int bn = N >= 128 ? 128 : 32;
   a.mtiles = (a.M + kFmBM - 1) / kFmBM; a.ntiles = (N + bn - 1) / bn;
   const int64_t gx = a.mtiles >= 8 ? (int64_t)8 * ((a.mtiles + 7) / 8) * a.ntiles : (int64_t)a.mtiles * a.ntiles;
-  // K split: the deep layers have few output tiles at small batches (deconv2 at 8 images: 16): one workgroup per CU,
-  // each with at least 8 K steps (a target of 512 -- two per CU -- measured 2 % slower at batch 8 and 32: the partial
-  // sums cost more than the second workgroup hides)
+  // K split: the deep layers have few output tiles at small batches (deconv2 at 8 images: 16): one workgroup per CU
+  // (kFmSplitTarget), each with at least 8 K steps
   const int64_t tiles = (int64_t)a.mtiles * a.ntiles * ncls;
   int nsplit = 1;
-  static int target = 0;
-  if (target == 0) {
-    const char* e = getenv("NDP_FM_SPLIT_TARGET");                   // experiments
-    target = e ? atoi(e) : 256;
-  }
-  while (zero_to == 0 && tiles * nsplit < target && nsplit * 8 <= ksteps && nsplit < 128 &&
+  while (zero_to == 0 && tiles * nsplit < kFmSplitTarget && nsplit * 8 <= ksteps && nsplit < 128 &&
          (int64_t)ncls * nsplit * 2 * a.M * N <= kFmPartCap) nsplit *= 2;
   a.steps_per_split = (ksteps + nsplit - 1) / nsplit;
   a.nsplit = (ksteps + a.steps_per_split - 1) / a.steps_per_split;
   // mode 2 where the K loop is split anyway: nine equal K units per tile instead of four unequal classes (fm_unit_first).
   // (Measured at 32 images: conv4 / conv5 85 -> 80 us each; conv3, unsplit before, 100 -> 70 us + 16 us of reduce launch
   // + 38 MB of partial sums: step unchanged, so a layer that needs no split keeps its one launch.)
-  static int units_on = -1;
-  if (units_on < 0) {
-    const char* e = getenv("NDP_FM_CLASS_UNITS");                      // experiments
-    units_on = e ? atoi(e) : 1;
-  }
   const int tap_steps = C / kFmBK;
-  if (units_on && mode == 2 && a.nsplit > 1 && tap_steps >= 8 && tiles <= target && (int64_t)9 * a.M * N <= kFmPartCap) {
+  if (mode == 2 && a.nsplit > 1 && tap_steps >= 8 && tiles <= kFmSplitTarget && (int64_t)9 * a.M * N <= kFmPartCap) {
     int s = 1;
-    while ((int64_t)a.mtiles * a.ntiles * 9 * s < target && tap_steps / (2 * s) >= 8 && tap_steps % (2 * s) == 0 &&
+    while ((int64_t)a.mtiles * a.ntiles * 9 * s < kFmSplitTarget && tap_steps / (2 * s) >= 8 && tap_steps % (2 * s) == 0 &&
            (int64_t)9 * 2 * s * a.M * N <= kFmPartCap) s *= 2;
     a.cls_units = s;
     a.steps_per_split = tap_steps / s;
@@ -2462,26 +2448,11 @@ static int fm_forward(hipStream_t st, const float* params, float* running, const
   FM_TRY(fm_bn_fwd(st, 5, {t[FMT_RAWU3], 256}, n * 256, {t[FMT_CAT4], 512}, P, running, training, ws));
   FM_TRY(fm_gemm(st, "k_fm_gemm[deconv4]", 1, {t[FMT_CAT4], 512}, 16, 1, W2(9), B(9), {t[FMT_RAWU4], 128}, 32, 16, n, 512, 128, 2, 0, 0, 0, ws, 0, EP(6)));
   FM_TRY(fm_bn_fwd(st, 6, {t[FMT_RAWU4], 128}, n * 1024, {t[FMT_CAT5], 256}, P, running, training, ws));
-  {
-    static int fused5 = -1;
-    if (fused5 < 0) {
-      const char* e = getenv("NDP_FM_DECONV5_FUSED");                  // experiments
-      fused5 = e ? atoi(e) : 1;
-    }
-    if (fused5 && n * 1024 / kFmBM * 2 >= 256)                         // (two halves of 32 channels: enough tiles from 16 images)
-      FM_TRY(fm_deconv32(st, "k_fm_gemm[deconv5]", {t[FMT_CAT5], 256}, 32, W2(10), B(10), {t[FMT_RAWU5], 64}, n, 256, 64, *EP(7), ws));
-    else FM_TRY(fm_gemm(st, "k_fm_gemm[deconv5]", 1, {t[FMT_CAT5], 256}, 32, 1, W2(10), B(10), {t[FMT_RAWU5], 64}, 64, 32, n, 256, 64, 2, 0, 0, 0, ws, 0, EP(7)));
-  }
+  if (n * 1024 / kFmBM * 2 >= 256)                                     // (two halves of 32 channels: enough tiles from 16 images)
+    FM_TRY(fm_deconv32(st, "k_fm_gemm[deconv5]", {t[FMT_CAT5], 256}, 32, W2(10), B(10), {t[FMT_RAWU5], 64}, n, 256, 64, *EP(7), ws));
+  else FM_TRY(fm_gemm(st, "k_fm_gemm[deconv5]", 1, {t[FMT_CAT5], 256}, 32, 1, W2(10), B(10), {t[FMT_RAWU5], 64}, 64, 32, n, 256, 64, 2, 0, 0, 0, ws, 0, EP(7)));
   FM_TRY(fm_bn_fwd(st, 7, {t[FMT_RAWU5], 64}, n * 4096, {t[FMT_CAT6], 128}, P, running, training, ws));
-  {
-    static int fused = -1;
-    if (fused < 0) {
-      const char* e = getenv("NDP_FM_DECONV6_FUSED");                  // experiments
-      fused = e ? atoi(e) : 1;
-    }
-    if (fused) FM_TRY(fm_deconv32(st, "k_fm_gemm[deconv6]", {t[FMT_CAT6], 128}, 64, W2(11), B(11), {t[FMT_RAWU6], 32}, n, 128, 32, *EP(8), ws));
-    else FM_TRY(fm_gemm(st, "k_fm_gemm[deconv6]", 1, {t[FMT_CAT6], 128}, 64, 1, W2(11), B(11), {t[FMT_RAWU6], 32}, 128, 64, n, 128, 32, 2, 0, 0, 0, ws, 0, EP(8)));
-  }
+  FM_TRY(fm_deconv32(st, "k_fm_gemm[deconv6]", {t[FMT_CAT6], 128}, 64, W2(11), B(11), {t[FMT_RAWU6], 32}, n, 128, 32, *EP(8), ws));
   FM_TRY(fm_bn_fwd(st, 8, {t[FMT_RAWU6], 32}, npix, {t[FMT_UP6], 32}, P, running, training, ws));
   FM_TRY(fm_r1(st, "k_fm_gemm[refine1]", false, t[FMT_UP6], W1(12), B(12), t[FMT_RAWR1], n, *EP(9), ws));
   FM_TRY(fm_bn_fwd(st, 9, {t[FMT_RAWR1], kFmR1LD}, npix, {t[FMT_R1], kFmR1LD}, P, running, training, ws));
@@ -2528,16 +2499,12 @@ static int fm_loss(hipStream_t st, const void* cur, const void* fut, bool u8, in
 // weight gradients run on a second stream (one per device, created on first use) beside the chain data gradient ->
 // BatchNorm backward -> next layer, whose many short launches they fill in around.  Fork: the side stream waits for an
 // event recorded where d(raw) is complete; join: the launch stream waits for the side stream before the slab sums.
-// NDP_FM_SIDE_STREAM=0 keeps everything on the launch stream.
+// ndp_fm_side_stream(0) keeps everything on the launch stream.
 struct FmSide { hipStream_t stream; hipEvent_t fork, join; bool ok; };
 static FmSide g_fm_side[kMaxDevices];
 static std::once_flag g_fm_side_once[kMaxDevices];
-static int g_fm_side_enabled = -1;                                  // -1: NDP_FM_SIDE_STREAM decides (default on)
+static int g_fm_side_enabled = 1;                                   // ndp_fm_side_stream
 static FmSide* fm_side() {
-  if (g_fm_side_enabled < 0) {
-    const char* e = getenv("NDP_FM_SIDE_STREAM");
-    g_fm_side_enabled = (e && e[0] == '0') ? 0 : 1;
-  }
   if (!g_fm_side_enabled) return nullptr;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
@@ -2545,8 +2512,6 @@ static FmSide* fm_side() {
   std::call_once(g_fm_side_once[dev], [sd] {
     int lo = 0, hi = 0;                                             // lowest priority: the chain's launches go first
     if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) lo = 0;
-    const char* pe = getenv("NDP_FM_SIDE_PRIORITY");                // experiments: "normal" = default priority
-    if (pe && pe[0] == 'n') lo = 0;
     sd->ok = hipStreamCreateWithPriority(&sd->stream, hipStreamNonBlocking, lo) == hipSuccess &&
              hipEventCreateWithFlags(&sd->fork, hipEventDisableTiming) == hipSuccess &&
              hipEventCreateWithFlags(&sd->join, hipEventDisableTiming) == hipSuccess;
@@ -2880,7 +2845,7 @@ int ndp_fm_bucket_wait(int bucket, void* stream) {
 int ndp_fm_side_stream(int on) {
   const int before = ndp::g_fm_side_enabled;
   ndp::g_fm_side_enabled = on ? 1 : 0;
-  return before < 0 ? 1 : before;
+  return before;
 }
 
 int ndp_fm_backward(const float* params, const float* d_resid, int64_t n_images, float* grad, float* workspace, void* stream) {

@@ -1,6 +1,6 @@
 // ndp_kernels.hip -- gfx950 kernels of the GAN train step (see include/ndp.h).
 //
-//   k_g_fwd      Decoder.forward, one workgroup per 16*RT-row tile, all five layers fused
+//   k_g_fwd      Decoder.forward, one workgroup per 16-row tile, all five layers fused
 //   k_d          Discriminator forward (+ BCE + backward data path), fused per row tile
 //   k_g_bwd      backward data path of the Decoder per row tile
 //   k_wgrad      all weight/bias gradients of one network: dW = dY^T X as MFMA blocks,
@@ -48,12 +48,6 @@ __device__ int g_stamp_kernel = 0;   // which kernel flushes: 1 k_g_fwd, 2 k_d, 
 #define NDP_STAMP_FLUSH(n, id) do { } while (0)
 #endif
 
-// -DNDP_PLAIN_KERNARGS: ablation of load_kernargs (ndp_device.h) in the phase kernels (27.5 vs 27.9 us for phase A)
-#ifdef NDP_PLAIN_KERNARGS
-constexpr bool kFastKernargs = false;
-#else
-constexpr bool kFastKernargs = true;
-#endif
 constexpr int CODE = 256;
 constexpr int ADIM = 4;
 constexpr int TAILLD = 16;   // LDS row stride of the narrow "tail" inputs (noise / action)
@@ -147,12 +141,11 @@ struct GFwdArgs {
   float* noise_out; uint64_t noise_seed; const int32_t* noise_step;
 };
 
-template <int RT>
-constexpr int g_fwd_lds_floats() { return 16 * RT * (260 + TAILLD + 132 + 68 + 132 + 260 + 4); }
+constexpr int g_fwd_lds_floats() { return 16 * (260 + TAILLD + 132 + 68 + 132 + 260 + 4); }
 
-template <int RT, int W1ALIGN, bool PK>
+template <int W1ALIGN, bool PK>
 __global__ __launch_bounds__(kThreads) void k_g_fwd(GFwdArgs a) {
-  constexpr int R = 16 * RT;
+  constexpr int R = 16;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* Xc = smem;                 // R x 260
   float* Xt = Xc + R * 260;         // R x 16   noise
@@ -169,7 +162,7 @@ __global__ __launch_bounds__(kThreads) void k_g_fwd(GFwdArgs a) {
   // each layer's first weight loads are issued one stage early (they fly across the barrier)
   FwdW<256, 128, W1ALIGN, PK> w1;
   w1.preload(PK ? n.pf1 : n.w1, n.ld1, n.b1, n.w1 + CODE, n.nz);
-  load_code_tile<RT>(Xc, 260, a.code, a.ld_code, a.code_rep, row0, a.m, a.code_vec4 != 0);
+  load_code_tile<1>(Xc, 260, a.code, a.ld_code, a.code_rep, row0, a.m, a.code_vec4 != 0);
   for (int idx = threadIdx.x; idx < R * TAILLD; idx += kThreads) {
     const int i = idx / TAILLD, t = idx % TAILLD;
     const int64_t row = row0 + i;
@@ -189,30 +182,30 @@ __global__ __launch_bounds__(kThreads) void k_g_fwd(GFwdArgs a) {
   // every layer's first weight fragments are issued inside the previous layer's k-loop (FwdW::preload_slice)
   FwdW<128, 64, 4, PK> w2;
   w2.bind(PK ? n.pf2 : n.w2, 128, n.b2, nullptr, 0);
-  layer_fwd_run<RT, 256, 128, ACT_RELU, W1ALIGN, PK>(w1, Xc, 260, H1, 132, Xt, TAILLD, w2);
+  layer_fwd_run<1, 256, 128, ACT_RELU, W1ALIGN, PK>(w1, Xc, 260, H1, 132, Xt, TAILLD, w2);
   __syncthreads();
   NDP_STAMP(2);
   FwdW<64, 128, 4, PK> w3;
   w3.bind(PK ? n.pf3 : n.w3, 64, n.b3, nullptr, 0);
-  layer_fwd_run<RT, 128, 64, ACT_RELU, 4, PK>(w2, H1, 132, H2, 68, nullptr, 0, w3);
+  layer_fwd_run<1, 128, 64, ACT_RELU, 4, PK>(w2, H1, 132, H2, 68, nullptr, 0, w3);
   __syncthreads();
   NDP_STAMP(3);
   FwdW<128, 256, 4, PK> w4;
   w4.bind(PK ? n.pf4 : n.w4, 128, n.b4, nullptr, 0);
-  layer_fwd_run<RT, 64, 128, ACT_RELU, 4, PK>(w3, H2, 68, H3, 132, nullptr, 0, w4);
+  layer_fwd_run<1, 64, 128, ACT_RELU, 4, PK>(w3, H2, 68, H3, 132, nullptr, 0, w4);
   __syncthreads();
   NDP_STAMP(4);
-  layer_fwd_run<RT, 128, 256, ACT_RELU, 4, PK>(w4, H3, 132, H4, 260, nullptr, 0);
+  layer_fwd_run<1, 128, 256, ACT_RELU, 4, PK>(w4, H3, 132, H4, 260, nullptr, 0);
   __syncthreads();
   NDP_STAMP(5);
-  layer_fwd_narrow<RT, 256, 4>(H4, 260, n.w5, n.b5, A, 4);
+  layer_fwd_narrow<1, 256, 4>(H4, 260, n.w5, n.b5, A, 4);
   __syncthreads();
   NDP_STAMP(6);
   if (a.h1 != nullptr) {
-    store_tile<RT, 128>(a.h1 + row0 * 128, 128, H1, 132);
-    store_tile<RT, 64>(a.h2 + row0 * 64, 64, H2, 68);
-    store_tile<RT, 128>(a.h3 + row0 * 128, 128, H3, 132);
-    store_tile<RT, 256>(a.h4 + row0 * 256, 256, H4, 260);
+    store_tile<1, 128>(a.h1 + row0 * 128, 128, H1, 132);
+    store_tile<1, 64>(a.h2 + row0 * 64, 64, H2, 68);
+    store_tile<1, 128>(a.h3 + row0 * 128, 128, H3, 132);
+    store_tile<1, 256>(a.h4 + row0 * 256, 256, H4, 260);
   }
   if (threadIdx.x < R) {
     const int64_t row = row0 + threadIdx.x;
@@ -332,8 +325,8 @@ __global__ __launch_bounds__(kThreads) void k_ndiv(NdivArgs a) {
 }
 
 // ================================================================ D forward / backward
-// One workgroup = the same 16*RT rows of NP passes (NP = 2: the real and the fake batch of the
-// D step), stacked in LDS as 16*RT*NP rows, so both passes share ONE stream of D's weights
+// One workgroup = the same 16 rows of NP passes (NP = 2: the real and the fake batch of the
+// D step), stacked in LDS as 16*NP rows, so both passes share ONE stream of D's weights
 // (the per-CU L2->L1 rate, not the MFMA rate, bounds these kernels at small M).
 // Workgroups with blockIdx.x >= ntiles (if any) are NDiv blocks riding in the same launch:
 // the NDiv loss/gradient needs only action_hat and the noise, so it runs on otherwise idle
@@ -359,14 +352,13 @@ struct DArgs {
   NdivArgs nd;                // blocks ntiles.. : NDiv (cx <= 4, cz <= 2), nd.n == 0 -> none
 };
 
-template <int RT, int NP>
-constexpr int d_lds_floats() { return 16 * RT * NP * (260 + TAILLD + 68 + 132 + 260 + 2) + 8; }
+template <int NP>
+constexpr int d_lds_floats() { return 16 * NP * (260 + TAILLD + 68 + 132 + 260 + 2) + 8; }
 
-template <int RT, int NP, bool PK>
+template <int NP, bool PK>
 __global__ __launch_bounds__(kThreads) void k_d(DArgs a) {
-  constexpr int R = 16 * RT;        // rows per pass
-  constexpr int RR = R * NP;        // LDS rows
-  constexpr int RTT = RT * NP;      // 16-row tiles the layer functions see
+  constexpr int R = 16;             // rows per pass
+  constexpr int RR = R * NP;        // LDS rows: the layer functions see NP 16-row tiles
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if ((int)blockIdx.x >= a.ntiles) {
     ndiv_block<4, 2>(a.nd, (int)blockIdx.x - a.ntiles, smem);
@@ -416,18 +408,18 @@ __global__ __launch_bounds__(kThreads) void k_d(DArgs a) {
   NDP_STAMP(1);
   FwdW<64, 128, 4, PK> w2;
   w2.bind(PK ? n.pf2 : n.w2, 64, n.b2, nullptr, 0);
-  layer_fwd_run<RTT, 256, 64, ACT_LRELU, 4, PK>(w1, Xc, 260, H1, 68, Xt, TAILLD, w2);
+  layer_fwd_run<NP, 256, 64, ACT_LRELU, 4, PK>(w1, Xc, 260, H1, 68, Xt, TAILLD, w2);
   __syncthreads();
   NDP_STAMP(2);
   FwdW<128, 256, 4, PK> w3;
   w3.bind(PK ? n.pf3 : n.w3, 128, n.b3, nullptr, 0);
-  layer_fwd_run<RTT, 64, 128, ACT_LRELU, 4, PK>(w2, H1, 68, H2, 132, nullptr, 0, w3);
+  layer_fwd_run<NP, 64, 128, ACT_LRELU, 4, PK>(w2, H1, 68, H2, 132, nullptr, 0, w3);
   __syncthreads();
   NDP_STAMP(3);
-  layer_fwd_run<RTT, 128, 256, ACT_LRELU, 4, PK>(w3, H2, 132, H3, 260, nullptr, 0);
+  layer_fwd_run<NP, 128, 256, ACT_LRELU, 4, PK>(w3, H2, 132, H3, 260, nullptr, 0);
   __syncthreads();
   NDP_STAMP(4);
-  layer_fwd_narrow<RTT, 256, 1>(H3, 260, n.w4, n.b4, L, 1);
+  layer_fwd_narrow<NP, 256, 1>(H3, 260, n.w4, n.b4, L, 1);
   __syncthreads();
   NDP_STAMP(5);
 
@@ -462,9 +454,9 @@ __global__ __launch_bounds__(kThreads) void k_d(DArgs a) {
 #pragma unroll
     for (int ps = 0; ps < NP; ++ps) {
       const int64_t g0 = (int64_t)ps * a.mpad + row0;
-      store_tile<RT, 64>(a.h1 + g0 * 64, 64, H1 + ps * R * 68, 68);
-      store_tile<RT, 128>(a.h2 + g0 * 128, 128, H2 + ps * R * 132, 132);
-      store_tile<RT, 256>(a.h3 + g0 * 256, 256, H3 + ps * R * 260, 260);
+      store_tile<1, 64>(a.h1 + g0 * 64, 64, H1 + ps * R * 68, 68);
+      store_tile<1, 128>(a.h2 + g0 * 128, 128, H2 + ps * R * 132, 132);
+      store_tile<1, 256>(a.h3 + g0 * 256, 256, H3 + ps * R * 260, 260);
     }
     if (threadIdx.x < RR) {
       const int ps = threadIdx.x / R;
@@ -476,24 +468,24 @@ __global__ __launch_bounds__(kThreads) void k_d(DArgs a) {
   NDP_STAMP(7);
   DgW<128, 256, PK> g3;
   g3.preload(PK ? n.pg3 : n.w3, 128);
-  layer_dgrad_narrow<RTT, 256, 1, ACT_LRELU>(DL, 1, n.w4, H3, 260);          // H3 := dY3
+  layer_dgrad_narrow<NP, 256, 1, ACT_LRELU>(DL, 1, n.w4, H3, 260);          // H3 := dY3
   __syncthreads();
   NDP_STAMP(8);
   DgW<64, 128, PK> g2;
   g2.bind(PK ? n.pg2 : n.w2, 64);
-  layer_dgrad_run<RTT, 128, 256, ACT_LRELU, PK>(g3, H3, 260, H2, 132, g2);   // H2 := dY2
+  layer_dgrad_run<NP, 128, 256, ACT_LRELU, PK>(g3, H3, 260, H2, 132, g2);   // H2 := dY2
   __syncthreads();
   NDP_STAMP(9);
-  layer_dgrad_run<RTT, 64, 128, ACT_LRELU, PK>(g2, H2, 132, H1, 68);         // H1 := dY1
+  layer_dgrad_run<NP, 64, 128, ACT_LRELU, PK>(g2, H2, 132, H1, 68);         // H1 := dY1
   __syncthreads();
   NDP_STAMP(10);
   if (a.dy1 != nullptr) {
 #pragma unroll
     for (int ps = 0; ps < NP; ++ps) {
       const int64_t g0 = (int64_t)ps * a.mpad + row0;
-      store_tile<RT, 64>(a.dy1 + g0 * 64, 64, H1 + ps * R * 68, 68);
-      store_tile<RT, 128>(a.dy2 + g0 * 128, 128, H2 + ps * R * 132, 132);
-      store_tile<RT, 256>(a.dy3 + g0 * 256, 256, H3 + ps * R * 260, 260);
+      store_tile<1, 64>(a.dy1 + g0 * 64, 64, H1 + ps * R * 68, 68);
+      store_tile<1, 128>(a.dy2 + g0 * 128, 128, H2 + ps * R * 132, 132);
+      store_tile<1, 256>(a.dy3 + g0 * 256, 256, H3 + ps * R * 260, 260);
     }
   }
   if (a.d_action != nullptr && threadIdx.x < R * ADIM) {
@@ -519,12 +511,11 @@ struct GBwdArgs {
   float *dy1, *dy2, *dy3, *dy4, *dy5;   // [mpad x 128/64/128/256/4]
 };
 
-template <int RT>
-constexpr int g_bwd_lds_floats() { return 16 * RT * (132 + 68 + 132 + 260 + 4); }
+constexpr int g_bwd_lds_floats() { return 16 * (132 + 68 + 132 + 260 + 4); }
 
-template <int RT, bool PK>
+template <bool PK>
 __global__ __launch_bounds__(kThreads) void k_g_bwd(GBwdArgs a) {
-  constexpr int R = 16 * RT;
+  constexpr int R = 16;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* H1 = smem;               // R x 132
   float* H2 = H1 + R * 132;       // R x 68
@@ -536,10 +527,10 @@ __global__ __launch_bounds__(kThreads) void k_g_bwd(GBwdArgs a) {
 
   DgW<128, 256, PK> g4;
   g4.preload(PK ? n.pg4 : n.w4, 128);
-  load_tile<RT, 128>(H1, 132, a.h1 + row0 * 128, 128);
-  load_tile<RT, 64>(H2, 68, a.h2 + row0 * 64, 64);
-  load_tile<RT, 128>(H3, 132, a.h3 + row0 * 128, 128);
-  load_tile<RT, 256>(H4, 260, a.h4 + row0 * 256, 256);
+  load_tile<1, 128>(H1, 132, a.h1 + row0 * 128, 128);
+  load_tile<1, 64>(H2, 68, a.h2 + row0 * 64, 64);
+  load_tile<1, 128>(H3, 132, a.h3 + row0 * 128, 128);
+  load_tile<1, 256>(H4, 260, a.h4 + row0 * 256, 256);
   if (threadIdx.x < R) {
     const int64_t row = row0 + threadIdx.x;
     f32x4 g = {0.f, 0.f, 0.f, 0.f};
@@ -551,22 +542,22 @@ __global__ __launch_bounds__(kThreads) void k_g_bwd(GBwdArgs a) {
     *reinterpret_cast<f32x4*>(a.dy5 + row * 4) = g;
   }
   __syncthreads();
-  layer_dgrad_narrow<RT, 256, 4, ACT_RELU>(DA, 4, n.w5, H4, 260);                // H4 := dY4
+  layer_dgrad_narrow<1, 256, 4, ACT_RELU>(DA, 4, n.w5, H4, 260);                // H4 := dY4
   __syncthreads();
   DgW<64, 128, PK> g3;
   g3.bind(PK ? n.pg3 : n.w3, 64);
-  layer_dgrad_run<RT, 128, 256, ACT_RELU, PK>(g4, H4, 260, H3, 132, g3);         // H3 := dY3
+  layer_dgrad_run<1, 128, 256, ACT_RELU, PK>(g4, H4, 260, H3, 132, g3);         // H3 := dY3
   __syncthreads();
   DgW<128, 64, PK> g2;
   g2.bind(PK ? n.pg2 : n.w2, 128);
-  layer_dgrad_run<RT, 64, 128, ACT_RELU, PK>(g3, H3, 132, H2, 68, g2);           // H2 := dY2
+  layer_dgrad_run<1, 64, 128, ACT_RELU, PK>(g3, H3, 132, H2, 68, g2);           // H2 := dY2
   __syncthreads();
-  layer_dgrad_run<RT, 128, 64, ACT_RELU, PK>(g2, H2, 68, H1, 132);               // H1 := dY1
+  layer_dgrad_run<1, 128, 64, ACT_RELU, PK>(g2, H2, 68, H1, 132);               // H1 := dY1
   __syncthreads();
-  store_tile<RT, 128>(a.dy1 + row0 * 128, 128, H1, 132);
-  store_tile<RT, 64>(a.dy2 + row0 * 64, 64, H2, 68);
-  store_tile<RT, 128>(a.dy3 + row0 * 128, 128, H3, 132);
-  store_tile<RT, 256>(a.dy4 + row0 * 256, 256, H4, 260);
+  store_tile<1, 128>(a.dy1 + row0 * 128, 128, H1, 132);
+  store_tile<1, 64>(a.dy2 + row0 * 64, 64, H2, 68);
+  store_tile<1, 128>(a.dy3 + row0 * 128, 128, H3, 132);
+  store_tile<1, 256>(a.dy4 + row0 * 256, 256, H4, 260);
 }
 
 // Per-tile segment sums of a pre-activation gradient tile for the K-deduplicated fc1 weight
@@ -802,9 +793,9 @@ __device__ __forceinline__ void phase_a_d_part(const PhaseAArgs& a, bool real, i
   store_tile<1, 256>(a.dy3 + g0 * 256, 256, XC, 260);
 }
 
-#ifndef NDP_PHASE_A_SMALL_RING
-#define NDP_PHASE_A_SMALL_RING 24     // 32 needs 36 bytes of scratch per lane under the 168-VGPR cap of three workgroups per CU;
-#endif                                // 24: none, and 0.7 - 1 % of the large-M step (B = 1024 / K = 6: 0.5325 -> 0.5288 ms)
+// 32 needs 36 bytes of scratch per lane under the 168-VGPR cap of three workgroups per CU;
+// 24: none, and 0.7 - 1 % of the large-M step (B = 1024 / K = 6: 0.5325 -> 0.5288 ms)
+constexpr int kPhaseASmallRing = 24;
 // RG = VGPR budget of each weight prefetch ring: 96 keeps a lone workgroup per CU streaming (grids of up to 256
 // workgroups); a small one (phase A 24, phase B 32) with a tighter register cap lets several workgroups share a CU at large M.
 template <bool PK, int RG, int NR>
@@ -813,7 +804,7 @@ __global__ __launch_bounds__(kThreads, (RG >= 96 ? 1 : 3)) void k_phase_a(PhaseA
   constexpr int NRR = NR > 0 ? NR : 1;
   // one workgroup per CU (RG = 96): nothing hides the argument loads, read them in one round trip (load_kernargs);
   // with several workgroups per CU the registers that costs are worth more
-  const PhaseAArgs a = (RG >= 96 && kFastKernargs) ? load_kernargs<PhaseAArgs>() : a_segment;
+  const PhaseAArgs a = RG >= 96 ? load_kernargs<PhaseAArgs>() : a_segment;
   constexpr int R = 16;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* XC = smem;                  // 16 x 260
@@ -1011,7 +1002,7 @@ template <bool PK, int RG, bool PRE, int NR>
 __global__ __launch_bounds__(kThreads, (RG >= 96 ? 2 : 3)) void k_phase_b(PhaseBArgs a_segment) {
   constexpr bool DD = NR > 0;
   constexpr int NRR = NR > 0 ? NR : 1;
-  const PhaseBArgs a = (RG >= 96 && kFastKernargs) ? load_kernargs<PhaseBArgs>() : a_segment;   // see k_phase_a
+  const PhaseBArgs a = RG >= 96 ? load_kernargs<PhaseBArgs>() : a_segment;   // see k_phase_a
   constexpr int R = 16;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float* XC = smem;                  // 16 x 260: code tile -> D.h3 / dY3 -> G.h4 / dY4
@@ -1222,9 +1213,7 @@ __device__ __forceinline__ void adam_advance(int32_t* state, float lr, float b1,
 // accumulate in registers, then add their four results through LDS and store one slab.
 //   WIDE      256 j x 128 k: a whole layer's dW (D.fc3, G.fc4) per workgroup, operands staged through LDS (large M)
 enum { WG_FULL = 0, WG_SKINNY_B = 1, WG_SKINNY_A = 2, WG_WIDE = 3 };
-#ifndef NDP_WGRAD_PFG
-#define NDP_WGRAD_PFG 8     // 4-row steps in the operand prefetch ring
-#endif
+constexpr int kWgradPrefetch = 8;   // 4-row steps in the operand prefetch ring
 
 struct WgradJob {
   const float* A;      // dY block: A[row*lda + j]
@@ -1290,7 +1279,7 @@ __device__ __forceinline__ void wgrad_block(const WgradJob& jb, int rbeg, int re
   // Every load is UNconditional (rows past the end are clamped to a valid row and simply never
   // consumed; narrow operands are loaded from a clamped column and zeroed by a select): a
   // branch around a load makes hipcc fall back to s_waitcnt vmcnt(0) inside the loop.
-  constexpr int PF = NDP_WGRAD_PFG;
+  constexpr int PF = kWgradPrefetch;
   const bool seg_b = jb.seg != 0;
   const bool plain_b = !seg_b && jb.b_rowdiv == 1 && jb.b_rowmod == 0x7fffffff;         // uniform per workgroup
   const float b_inv = 1.0f / (float)(seg_b ? jb.seg_k : jb.b_rowdiv);
@@ -1431,60 +1420,47 @@ __device__ __forceinline__ void wgrad_block(const WgradJob& jb, int rbeg, int re
   }
 }
 
-// WIDE job: dW [256 x 128] = sum over the chunk's rows of dY[row][0..256) x X[row][0..128), one workgroup, every wave
-// over ALL rows: wave w owns the 64 j of tile w and all 128 k (32 accumulator tiles = 128 registers).  The register-fed
-// 64 x 64 blocks above fetch 2 KB per 16 MFMAs and wave -- 16 B/clk per CU from L2, which is what the memory pipe gives
-// beyond L1 (counters at B = 128 / K = 32: matrix pipe 28 % busy, L2 hit rate 48 %, the eight jobs of this layer read
-// every activation byte 2.7 times).  Here slabs of 16 rows (24 KB: 16 x 256 floats of dY, 16 x 128 of X) go global ->
-// LDS by LDS-DMA (global_load_lds_dwordx4: no register round trip), three buffers, TWO slabs in flight while one is
-// multiplied (a slab is 128 MFMAs per wave, ~4,100 cycles; an HBM miss under load is longer than that): a counted
-// s_waitcnt leaves the next slab's loads pending across the one raw barrier per slab.  6 B/clk per CU from L2.
-// Chunks are whole slabs (rows are padded to 32 and chunk bounds to 16), so no row needs masking.
-// JW = 64-row tiles of dW per workgroup: 4 -- the whole 256 x 128 layer, wave w owns tile w and both 64-column halves (32
-// accumulator tiles); 2 -- half of it (128 x 128: two jobs per layer), wave w owns tile w >> 1 and column half w & 1 (16
-// accumulator tiles, three workgroups per CU): at the same workgroup duration the layer then needs half the row chunks,
-// i.e. half the slabs for k_reduce_adam to add.
+// WIDE job: half of a 256 x 128 layer (D.fc3, G.fc4; two jobs per layer), dW [128 x 128] = sum over the chunk's rows of
+// dY[row][128 h..128 h + 128) x X[row][0..128), one workgroup, every wave over ALL rows: wave w owns 64-row tile w >> 1 of
+// dW and column half w & 1 (16 accumulator tiles).  The register-fed 64 x 64 blocks above fetch 2 KB per 16 MFMAs and
+// wave -- 16 B/clk per CU from L2, which is what the memory pipe gives beyond L1 (counters at B = 128 / K = 32: matrix
+// pipe 28 % busy, L2 hit rate 48 %, the eight jobs of this layer read every activation byte 2.7 times).  Here slabs of
+// 16 rows (16 KB: 16 x 128 floats of dY, 16 x 128 of X) go global -> LDS by LDS-DMA (global_load_lds_dwordx4: no
+// register round trip), three buffers, TWO slabs in flight while one is multiplied (an HBM miss under load is longer
+// than a slab's MFMAs): a counted s_waitcnt leaves the next slab's loads pending across the one raw barrier per slab.
+// Chunks are whole slabs (rows are padded to 32 and chunk bounds to 16), so no row needs masking.  The whole layer as
+// ONE job per workgroup (32 accumulator tiles per wave, 24 KB slabs) needed twice the row chunks at the same workgroup
+// duration, i.e. twice the slabs for k_reduce_adam to add (measured and dropped, see wgrad_wide_chunks).
 constexpr int kWideR = 16;
-template <int JW> constexpr int wide_slab_floats() { return kWideR * (64 * JW + 128); }
-constexpr int wgrad_wide_lds_floats() { return 3 * wide_slab_floats<4>(); }
-template <int JW>
+constexpr int wide_slab_floats() { return kWideR * (128 + 128); }
+constexpr int wgrad_wide_lds_floats() { return 3 * wide_slab_floats(); }
 __device__ __forceinline__ void wgrad_wide(const WgradJob& jb, int rbeg, int rend, float* slab, float* smem) {
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   typedef const __attribute__((address_space(1))) void* glb_ptr_t;
-  constexpr int AW = 64 * JW;                       // dY columns of this job
-  constexpr int NK = JW == 4 ? 2 : 1;               // 64-column halves of X per wave
-  constexpr int SLAB = wide_slab_floats<JW>();
+  constexpr int AW = 128;                           // dY columns of this job
+  constexpr int SLAB = wide_slab_floats();
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int c = lane & 15, q = lane >> 4;
-  const int jt = JW == 4 ? wave : (wave >> 1), kt0 = JW == 4 ? 0 : (wave & 1);
-  f32x4 acc[4][4 * NK];
+  const int jt = wave >> 1, kt0 = wave & 1;
+  f32x4 acc[4][4];
   float bs[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     bs[u] = 0.f;
 #pragma unroll
-    for (int v = 0; v < 4 * NK; ++v) acc[u][v] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int v = 0; v < 4; ++v) acc[u][v] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   const int nslabs = rend > rbeg ? (rend - rbeg) / kWideR : 0;
-  // one wave-instruction writes 1 KB of LDS, lane i at base + 16 i: a whole 256-float dY row (JW = 4; wave w: rows w, w +
-  // 4, w + 8, w + 12) or two 128-float rows (dY at JW = 2, X always; wave w: row pairs w and w + 4, lanes 0..31 the first
-  // row of the pair)
+  // one wave-instruction writes 1 KB of LDS, lane i at base + 16 i: two 128-float rows of dY or of X (wave w: row pairs w
+  // and w + 4, lanes 0..31 the first row of the pair)
   auto fetch = [&](int s) {
     float* buf = smem + (s % 3) * SLAB;
     const size_t r0 = (size_t)rbeg + (size_t)s * kWideR;
-    if (JW == 4) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = wave + 4 * i;
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)(jb.A + (r0 + row) * jb.lda + 4 * lane), (lds_ptr_t)(buf + row * AW), 16, 0, 0);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int pair = wave + 4 * i;
-        __builtin_amdgcn_global_load_lds((glb_ptr_t)(jb.A + (r0 + 2 * pair + (lane >> 5)) * jb.lda + 4 * (lane & 31)),
-                                         (lds_ptr_t)(buf + pair * 256), 16, 0, 0);
-      }
+    for (int i = 0; i < 2; ++i) {
+      const int pair = wave + 4 * i;
+      __builtin_amdgcn_global_load_lds((glb_ptr_t)(jb.A + (r0 + 2 * pair + (lane >> 5)) * jb.lda + 4 * (lane & 31)),
+                                       (lds_ptr_t)(buf + pair * 256), 16, 0, 0);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -1498,12 +1474,8 @@ __device__ __forceinline__ void wgrad_wide(const WgradJob& jb, int rbeg, int ren
   for (int s = 0; s < nslabs; ++s) {
     // slab s has landed (this wave's share: all but the loads of slab s + 1, if any), for every wave: barrier.  The
     // barrier also says every wave is done reading the buffer of slab s - 1, which slab s + 2 then overwrites.
-    if (s + 1 < nslabs) {
-      if (JW == 4) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    if (s + 1 < nslabs) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (s + 2 < nslabs) fetch(s + 2);
     const float* As = smem + (s % 3) * SLAB + 64 * jt + 4 * c;
@@ -1511,28 +1483,22 @@ __device__ __forceinline__ void wgrad_wide(const WgradJob& jb, int rbeg, int ren
 #pragma unroll
     for (int st = 0; st < kWideR / 4; ++st) {
       const f32x4 va = *reinterpret_cast<const f32x4*>(As + (4 * st + q) * AW);
-      f32x4 vb[NK];
-#pragma unroll
-      for (int k = 0; k < NK; ++k) vb[k] = *reinterpret_cast<const f32x4*>(Bs + (4 * st + q) * 128 + 64 * k);
+      const f32x4 vb = *reinterpret_cast<const f32x4*>(Bs + (4 * st + q) * 128);
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         if (kt0 == 0) bs[u] += va[u];
 #pragma unroll
-        for (int k = 0; k < NK; ++k)
-#pragma unroll
-          for (int v = 0; v < 4; ++v) acc[u][4 * k + v] = mfma16(va[u], vb[k][v], acc[u][4 * k + v]);
+        for (int v = 0; v < 4; ++v) acc[u][v] = mfma16(va[u], vb[v], acc[u][v]);
       }
     }
   }
-  // C tile (u, v) of column half k: the lane holds dW row j = 64 jt + 4 (4 q + i) + u, columns 64 (kt0 + k) + 4 c + v
+  // C tile (u, v): the lane holds dW row j = 64 jt + 4 (4 q + i) + u, columns 64 kt0 + 4 c + v
 #pragma unroll
   for (int u = 0; u < 4; ++u)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       float* d = slab + jb.dst_off + (size_t)(64 * jt + 4 * (4 * q + i) + u) * jb.dst_ld + 64 * kt0 + 4 * c;
-#pragma unroll
-      for (int k = 0; k < NK; ++k)
-        *reinterpret_cast<f32x4*>(d + 64 * k) = f32x4{acc[u][4 * k][i], acc[u][4 * k + 1][i], acc[u][4 * k + 2][i], acc[u][4 * k + 3][i]};
+      *reinterpret_cast<f32x4*>(d) = f32x4{acc[u][0][i], acc[u][1][i], acc[u][2][i], acc[u][3][i]};
     }
   if (jb.bias_off >= 0 && kt0 == 0) {
 #pragma unroll
@@ -1581,8 +1547,7 @@ __device__ __forceinline__ void wgrad_fetch_args(WgradHead& a, WgradJob& jb, int
     __builtin_memcpy(&jb, (kbytes_t)v + joff, sizeof(WgradJob));
 }
 
-// WIDE: the instantiation that can run WG_WIDE jobs (large M: its 128 accumulator registers leave one workgroup per CU;
-// the other keeps two)
+// WIDE: the instantiation that can run WG_WIDE jobs (large M)
 template <bool WIDE>
 __device__ __forceinline__ void wgrad_body(float* smem) {
   WgradHead a;
@@ -1618,8 +1583,7 @@ __device__ __forceinline__ void wgrad_body(float* smem) {
 #else
   unsigned long long* wst = nullptr;
 #endif
-  if (WIDE && kind == WG_WIDE && jb.a_cols == 256) wgrad_wide<4>(jb, rbeg, rend, slab, smem);
-  else if (WIDE && kind == WG_WIDE) wgrad_wide<2>(jb, rbeg, rend, slab, smem);
+  if (WIDE && kind == WG_WIDE) wgrad_wide(jb, rbeg, rend, slab, smem);
   else if (kind == WG_FULL) wgrad_block<4, 4, WG_FULL>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
   else if (kind == WG_SKINNY_B) wgrad_block<4, 1, WG_SKINNY_B>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
   else wgrad_block<1, 4, WG_SKINNY_A>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
@@ -1635,7 +1599,7 @@ __global__ __launch_bounds__(kThreads) void k_wgrad(WgradArgs a_segment) {
   (void)a_segment;
   wgrad_body<false>(smem);
 }
-// (two workgroups per CU: at most 256 registers per lane, 128 of them the WIDE job's accumulators)
+// (two workgroups per CU: at most 256 registers per lane, 64 of them the WIDE job's accumulators)
 __global__ __launch_bounds__(kThreads, 2) void k_wgrad_wide(WgradArgs a_segment) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   (void)a_segment;

@@ -33,5 +33,5 @@ for _ in range(20):
             with torch.cuda.stream(st):
                 torch.zeros(1024, device=dev).add_(1.0)
 torch.cuda.synchronize()
-print("extra streams %d, side priority %s, GPU_MAX_HW_QUEUES %s: %.3f ms/step" % (
-    extra, os.environ.get("NDP_FM_SIDE_PRIORITY", "low"), os.environ.get("GPU_MAX_HW_QUEUES", "default"), (time.perf_counter() - t0) / 20 * 1e3))
+print("extra streams %d, GPU_MAX_HW_QUEUES %s: %.3f ms/step" % (
+    extra, os.environ.get("GPU_MAX_HW_QUEUES", "default"), (time.perf_counter() - t0) / 20 * 1e3))
