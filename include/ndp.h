@@ -401,6 +401,38 @@ int ndp_fm_apply_adam(float *params, const float *grad, float *exp_avg, float *e
                       int32_t *step_count, float lr, float beta1, float beta2, float eps,
                       float *workspace, void *stream);
 
+/* ------------------------------------------------------- image autoencoder ---
+ * models.image_autoencoder.Encoder + Decoder (image_autoencoder.py:14-87) and one iteration of their training loop
+ * (train_autoencoder.py:79-90).  Additive to the forward-model family above, same conventions:
+ *   ndp_ae_train_grads  replaces  recon = decoder(encoder(x)); loss = mse(recon, x); zero_grad(); loss.backward()
+ *                       images [n,3,128,128] NCHW; training-mode BatchNorm (batch statistics; the running statistics
+ *                       move when running_stats != NULL); loss[0] = the MSE, *loss_sum += it (NULL: not kept);
+ *                       grad = every gradient; recon_out (NULL or [n,3,128,128]) = the reconstruction
+ *   ndp_ae_apply_adam   replaces  optimizer.step() (:90) for the flat parameter vector and rebuilds the second weight
+ *                       order in the workspace (step_count: the Adam state word of ndp_adam_step)
+ * Parameters: ONE flat fp32 vector of ndp_ae_param_floats() floats, per layer (conv1..6, deconv1..6) the weight then
+ * the bias, then per BatchNorm in use (conv1..3_bn, deconv1..5_bn) weight then bias; weights as in the forward model
+ * (Conv2d [cout_pad][kh][kw][cin_pad], ConvTranspose2d [cin_pad][kh][kw][cout_pad]; conv1's cin 3 -> 32, deconv6's
+ * cout 3 -> 4).  ndp_ae_layout: as ndp_fm_layout (what 0..5) over this vector and the running_stats vector of
+ * ndp_ae_stat_floats() floats.  conv4_bn / conv5_bn are never applied (image_autoencoder.py:42-45) and are not part of
+ * the vectors.  workspace: ndp_ae_workspace_floats(n) floats, the same pointer for every call; its head holds the
+ * second weight order, which ndp_ae_pack_params (after the parameters were written from outside) and
+ * ndp_ae_apply_adam rebuild.  1 <= n_images <= 8192 (larger: NDP_E_ARG; ndp_ae_workspace_floats returns 0).
+ * ndp_ae_workspace_offset(n, t): where intermediate map t (order of AeTensor in csrc/ndp_autoencoder.inc) lives, for
+ * tests; -1 for a bad query. */
+int64_t ndp_ae_param_floats(void);
+int64_t ndp_ae_stat_floats(void);
+int64_t ndp_ae_workspace_floats(int64_t n_images);
+int64_t ndp_ae_workspace_offset(int64_t n_images, int tensor);
+int ndp_ae_layout(int what, int index, int64_t *offset, int64_t *dims /* [6] */);
+int ndp_ae_pack_params(const float *params, float *workspace, void *stream);
+int ndp_ae_train_grads(const float *params, float *running_stats, const float *images, int64_t n_images,
+                       float *grad, float *loss, float *loss_sum, float *recon_out, float *workspace,
+                       void *stream);
+int ndp_ae_apply_adam(float *params, const float *grad, float *exp_avg, float *exp_avg_sq,
+                      int32_t *step_count, float lr, float beta1, float beta2, float eps,
+                      float *workspace, void *stream);
+
 /* ------------------------------------------------------------ measurement ---
  * Per-kernel timing for bench.py: while enabled (per host thread) every kernel
  * this library launches is bracketed by hipEvents recorded on the stream it is

@@ -119,6 +119,16 @@ SIGNATURES = {
     "ndp_fm_backward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "ndp_fm_apply_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                   c_void_p, c_void_p]),
+    "ndp_ae_param_floats": (c_int64, []),
+    "ndp_ae_stat_floats": (c_int64, []),
+    "ndp_ae_workspace_floats": (c_int64, [c_int64]),
+    "ndp_ae_workspace_offset": (c_int64, [c_int64, c_int]),
+    "ndp_ae_layout": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "ndp_ae_pack_params": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "ndp_ae_train_grads": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
+    "ndp_ae_apply_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
+                                  c_void_p, c_void_p]),
     "ndp_timing_enable": (c_int, [c_int]),
     "ndp_timing_collect": (c_int, [ctypes.c_char_p, c_int, POINTER(c_float), POINTER(c_int32), c_int]),
 }

@@ -1,0 +1,110 @@
+"""One iteration of the reference's autoencoder training loop (train_autoencoder.py:79-90) as gfx950 kernels:
+
+    z = encoder(state_cur); state_cur_hat = decoder(z)              ->  ndp_ae_train_grads   (forward, training-mode
+    recon_loss = mse(state_cur_hat, state_cur)                            BatchNorm, MSE, backward: every gradient)
+    optimizer.zero_grad(); recon_loss.backward()
+    optimizer.step()                                                 ->  ndp_ae_apply_adam
+
+The trainer owns the flat parameter vector the kernels read (include/ndp.h: image autoencoder), its gradient, the Adam
+moments (one Adam over both modules, as the reference's two parameter groups with the same settings) and the running
+BatchNorm statistics; `sync_to_modules()` writes them back into the `Encoder` and `Decoder` (the reference saves the whole
+modules: train_autoencoder.py:92-97).  There is no CPU path."""
+import torch
+
+from . import _capi
+from .models import image_autoencoder as IA
+
+
+class AutoencoderTrainer:
+    def __init__(self, encoder: IA.Encoder, decoder: IA.Decoder, batch: int, lr: float = 2e-4, betas=(0.5, 0.999),
+                 eps: float = 1e-8, keep_reconstruction: bool = False):
+        self.lib = _capi.load()
+        self.encoder, self.decoder = encoder, decoder
+        dev = next(encoder.parameters()).device
+        if dev.type != "cuda" or next(decoder.parameters()).device != dev:
+            raise _capi.NdpError("AutoencoderTrainer needs both modules on one ROCm GPU (got %s, %s); there is no CPU path"
+                                 % (dev, next(decoder.parameters()).device))
+        self.device, self.batch = dev, int(batch)
+        if self.batch < 1 or self.lib.ndp_ae_workspace_floats(self.batch) <= 0:
+            raise _capi.NdpError("AutoencoderTrainer: unsupported batch of %d images" % self.batch)
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.params, self.stats = IA.pack_autoencoder(encoder, decoder, dev)
+        self.grad = torch.zeros_like(self.params)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.step_word = torch.zeros(4, dtype=torch.int32, device=dev)      # Adam state word (include/ndp.h)
+        self.loss = torch.zeros(1, **f32)
+        self.loss_sum = torch.zeros(1, **f32)
+        self.recon = torch.zeros(self.batch, 3, 128, 128, **f32) if keep_reconstruction else None
+        self.workspace = torch.empty(self.lib.ndp_ae_workspace_floats(self.batch), **f32)
+        self.steps = 0                                                       # Adam steps
+        self.forwards = 0                                                    # training-mode forwards (num_batches_tracked)
+        self._batches0 = int(encoder.conv1_bn.num_batches_tracked.item())
+        self._pack()
+
+    def _pack(self):
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.ndp_ae_pack_params(_capi.ptr(self.params), _capi.ptr(self.workspace),
+                                                    _capi.stream_ptr(self.device)), "ndp_ae_pack_params")
+
+    def grads(self, images):
+        """forward + loss + backward on images [n,3,128,128] (n <= batch): fills .grad, .loss (device scalar, the
+        reference's `recon_loss`), adds it to .loss_sum, moves the running statistics."""
+        n = int(images.shape[0]) if images.dim() == 4 else 0
+        if not 1 <= n <= self.batch:
+            raise _capi.NdpError("batch of %d images with a trainer built for at most %d" % (n, self.batch))
+        if (images.device != self.device or images.dtype != torch.float32 or tuple(images.shape) != (n, 3, 128, 128)
+                or not images.is_contiguous()):
+            raise _capi.NdpError("images: expected a contiguous float32 [%d, 3, 128, 128] tensor on %s, got %s %s on %s"
+                                 % (n, self.device, images.dtype, list(images.shape), images.device))
+        p = _capi.ptr
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.ndp_ae_train_grads(p(self.params), p(self.stats), p(images), n, p(self.grad), p(self.loss),
+                                                    p(self.loss_sum), p(self.recon) if self.recon is not None else None,
+                                                    p(self.workspace), _capi.stream_ptr(self.device)), "ndp_ae_train_grads")
+        self.forwards += 1
+        return self.loss
+
+    def apply(self):
+        """optimizer.step()"""
+        p = _capi.ptr
+        with torch.cuda.device(self.device):
+            _capi.check(self.lib.ndp_ae_apply_adam(p(self.params), p(self.grad), p(self.exp_avg), p(self.exp_avg_sq),
+                                                   p(self.step_word), self.lr, self.betas[0], self.betas[1], self.eps,
+                                                   p(self.workspace), _capi.stream_ptr(self.device)), "ndp_ae_apply_adam")
+        self.steps += 1
+
+    def step(self, images):
+        """The loop body of train_autoencoder.py:79-90 for one image batch; returns the loss (device scalar)."""
+        self.grads(images)
+        self.apply()
+        return self.loss
+
+    def load_from_modules(self):
+        """Take parameters and running statistics from the modules again (after they were changed from outside)."""
+        self.params, self.stats = IA.pack_autoencoder(self.encoder, self.decoder, self.device)
+        self._batches0 = int(self.encoder.conv1_bn.num_batches_tracked.item())
+        self.forwards = 0
+        self._pack()
+
+    def sync_to_modules(self):
+        IA.unpack_into_autoencoder(self.encoder, self.decoder, self.params, self.stats,
+                                   batches_tracked=self._batches0 + self.forwards)
+        return self.encoder, self.decoder
+
+    # post-ReLU maps of the last grads() call (tests, inspection): name -> (workspace tensor index, side, channels)
+    _MAPS = {"feat1": (2, 64, 64), "feat2": (4, 32, 128), "feat3": (6, 16, 256), "feat4": (7, 8, 512), "feat5": (8, 4, 1024),
+             "up1": (11, 4, 1024), "up2": (13, 8, 512), "up3": (15, 16, 256), "up4": (17, 32, 128), "up5": (19, 64, 64)}
+
+    def activation(self, name, n):
+        """Post-ReLU map `name` (feat1..5, up1..5) of the last call on n images, NCHW."""
+        idx, side, ch = self._MAPS[name]
+        off = self.lib.ndp_ae_workspace_offset(n, idx)
+        return self.workspace[off:off + n * side * side * ch].view(n, side, side, ch).permute(0, 3, 1, 2).contiguous()
+
+    def named_gradients(self):
+        """'encoder.conv1.weight' ... -> gradient in the modules' own tensor shapes (tests, inspection)."""
+        return IA.unpack_autoencoder_vector(self.grad, self.encoder, self.decoder)
+
+    def named_parameters(self):
+        return IA.unpack_autoencoder_vector(self.params, self.encoder, self.decoder)

@@ -1,0 +1,626 @@
+// ndp_autoencoder.inc -- one training iteration of the reference's image autoencoder (train_autoencoder.py:79-94):
+//   models/image_autoencoder.py:14-49   Encoder: conv1..5 (3x3 s2 p1, 3 -> 64 -> 128 -> 256 -> 512 -> 1024), BatchNorm after
+//                                       conv1..3 only (conv4_bn / conv5_bn are constructed and never applied), ReLU; conv6
+//                                       (4x4 on the 4x4 map) -> 128-d code
+//   :53-87    Decoder: deconv1 (128 -> 1024, 4x4 on the 1x1 code), deconv2..5 (ConvTranspose2d(c, c/2, 4, 2, 1)), each +
+//             BatchNorm + ReLU; deconv6 (64 -> 3, 4x4 s2 p1) + tanh
+//   train_autoencoder.py:84-90          loss = mse(decoder(encoder(x)), x); zero_grad; backward; Adam step
+// Included at the end of ndp_kernels.hip, after ndp_forward_model.inc.
+//
+// The network is the forward model without its skip connections and refinement head, so every layer but the output
+// layer runs on the forward model's kernels and host helpers (k_fm_gemm, k_fm_deconv32, k_fm_rows_cls, k_fm_wgrad,
+// k_fm_splitk_reduce, k_fm_slab_sum, the epilogue statistics, k_fm_bn_apply / k_fm_bn_bwd_apply, k_fm_pack /
+// k_fm_adam_pack).  Its maps are NHWC with the channel count as the pixel stride (nothing is concatenated).  Its eight
+// BatchNorms have the channel counts of the forward model's first eight (conv1..3_bn, deconv1..5_bn), so they use those
+// BatchNorm indices, statistics slots and scratch; where their tensors live comes from FmBnAt.
+//
+// New here: deconv6, 64 -> 3 channels at 128 x 128.  As a GEMM its three output channels would be padded to 32 (ten
+// times the MACs, a 32-wide output map); instead three small VALU kernels sized to what they move, as k_fm_r2_*:
+//   k_ae_out_fwd_loss  y = tanh(b + deconv6(up5)), the squared error against the image, g = d loss / d (pre-tanh) into
+//                      g6 [pixel][4], the per-block sums of the squared error and of g (the bias gradient)
+//   k_ae_out_dgrad     d up5 [pixel][64] from g6, and in its epilogue deconv5_bn's backward sums (epilogue mode 2)
+//   k_ae_out_wgrad     d W6 [64][16][4] per block of input pixels into slabs, summed in block order by k_fm_slab_sum
+//
+// Limits: the forward model's argument structs carry pixel counts as int (FmGemmArgs::M, FmEltArgs::P, FmStatFin::P; the
+// largest map is n x 4,096 pixels: conv1's output and up5); the new kernels index in 64 bits.  ndp_ae_* accept
+// 1 <= n <= kAeMaxImages = 8192 (n x 4,096 < 2^31 with a wide margin; the fixed-point statistics of the largest map stay
+// far inside their 2^50 range), as the ndp_fm_* calls do.
+
+namespace ndp {
+
+constexpr int kAeLayers = 12;
+static const FmLayer kAe[kAeLayers] = {
+    {FM_CONV, 3, 64, 128, 64, 3, 2, 1, 32, 64},        // 0  encoder.conv1
+    {FM_CONV, 64, 128, 64, 32, 3, 2, 1, 64, 128},      // 1  encoder.conv2
+    {FM_CONV, 128, 256, 32, 16, 3, 2, 1, 128, 256},    // 2  encoder.conv3
+    {FM_CONV, 256, 512, 16, 8, 3, 2, 1, 256, 512},     // 3  encoder.conv4
+    {FM_CONV, 512, 1024, 8, 4, 3, 2, 1, 512, 1024},    // 4  encoder.conv5
+    {FM_CONV, 1024, 128, 4, 1, 4, 1, 0, 1024, 128},    // 5  encoder.conv6
+    {FM_DECONV, 128, 1024, 1, 4, 4, 1, 0, 128, 1024},  // 6  decoder.deconv1
+    {FM_DECONV, 1024, 512, 4, 8, 4, 2, 1, 1024, 512},  // 7  decoder.deconv2
+    {FM_DECONV, 512, 256, 8, 16, 4, 2, 1, 512, 256},   // 8  decoder.deconv3
+    {FM_DECONV, 256, 128, 16, 32, 4, 2, 1, 256, 128},  // 9  decoder.deconv4
+    {FM_DECONV, 128, 64, 32, 64, 4, 2, 1, 128, 64},    // 10 decoder.deconv5
+    {FM_DECONV, 64, 3, 64, 128, 4, 2, 1, 64, 4},       // 11 decoder.deconv6
+};
+// BatchNorms in use: conv1..3_bn, deconv1..5_bn = the forward model's BatchNorms 0..7 (kFmBnC, kFmBnLayer: same channels,
+// same layer indices)
+constexpr int kAeBns = 8;
+constexpr int64_t kAeMaxImages = 8192;
+
+static int64_t ae_w_rows(int l) { return kAe[l].kind == FM_CONV ? kAe[l].cout_pad : kAe[l].cin_pad; }
+static int64_t ae_w_cols(int l) { return kAe[l].kind == FM_CONV ? kAe[l].cin_pad : kAe[l].cout_pad; }
+static int64_t ae_w_floats(int l) { return ae_w_rows(l) * kAe[l].ksz * kAe[l].ksz * ae_w_cols(l); }
+// flat parameter buffer: per layer [W (P1)][bias (cout_pad)], then per BatchNorm [weight][bias]
+static int64_t ae_param_offset(int l, bool bias) {
+  int64_t o = 0;
+  for (int i = 0; i < l; ++i) o += ae_w_floats(i) + kAe[i].cout_pad;
+  return o + (bias ? ae_w_floats(l) : 0);
+}
+static int64_t ae_bn_offset(int b, bool bias) {
+  int64_t o = ae_param_offset(kAeLayers, false);
+  for (int i = 0; i < b; ++i) o += 2 * kFmBnC[i];
+  return o + (bias ? kFmBnC[b] : 0);
+}
+static int64_t ae_param_floats() { return ae_bn_offset(kAeBns, false); }
+// running statistics: per BatchNorm [running_mean][running_var] (the forward model's first eight entries)
+static int64_t ae_stat_floats() { return fm_stat_offset(kAeBns, false); }
+// P2 (second operand order, the forward model's kinds): conv1's column form, conv2..deconv5; deconv6 reads P1
+static int64_t ae_p2_floats(int l) {
+  if (l == 0) return (int64_t)64 * 32;
+  if (l == 11) return 0;
+  return ae_w_floats(l);
+}
+static int64_t ae_p2_offset(int l) {
+  int64_t o = 0;
+  for (int i = 0; i < l; ++i) o += ae_p2_floats(i);
+  return o;
+}
+static int ae_pack_kind(int l) {
+  if (l == 0) return 5;
+  if (l == 5) return 2;
+  if (l == 6) return 4;
+  return kAe[l].kind == FM_CONV ? 0 : 3;
+}
+
+// ------------------------------------------------------------------------------------------ deconv6 (64 -> 3, 4x4 s2 p1)
+// Output pixel (oy, ox) of image i takes the taps ky = ((oy + 1) & 1) + 2 a (a = 0, 1) at source row iy = (oy + 1 - ky) / 2,
+// the same in x: four taps per pixel, 4 x 64 x 3 MACs.  W: P1 [ci 64][ky * 4 + kx][co 4] (co = 3 is zero padding),
+// staged in LDS (16 KB).  up5 [pixel][64] (n x 64 x 64), g6 [pixel][4] (n x 128 x 128).
+constexpr int kAeOutW = 64 * 16 * 4;
+struct AeOutArgs {
+  const float* up5; const float* w; const float* bias; const float* img;   // img: [n][3][128][128]
+  float* g6; float* recon; float* partial;                                 // recon: NCHW output (nullable); partial [block][4]
+  float* du5; float* slabs;
+  int64_t npix;                     // k_ae_out_fwd_loss: output pixels n x 16,384; dgrad / wgrad: input pixels n x 4,096
+  int64_t rows_per_block;           // dgrad / wgrad: input pixels per workgroup
+  FmStatEp ep;                      // dgrad: deconv5_bn's backward sums (mode 2; x = raw deconv5 output, y = up5)
+};
+__device__ __forceinline__ void ae_out_stage_weights(float* Ws, const float* __restrict__ w) {
+  for (int i = threadIdx.x; i < kAeOutW / 4; i += kThreads)
+    reinterpret_cast<f32x4*>(Ws)[i] = reinterpret_cast<const f32x4*>(w)[i];
+  __syncthreads();
+}
+
+// one thread per output pixel
+__global__ __launch_bounds__(kThreads) void k_ae_out_fwd_loss(AeOutArgs a) {
+  __shared__ __attribute__((aligned(16))) float Ws[kAeOutW];
+  __shared__ float red[4];
+  ae_out_stage_weights(Ws, a.w);
+  const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  float sq = 0.f;
+  f32x4 g = {0.f, 0.f, 0.f, 0.f};
+  if (p < a.npix) {
+    const int64_t img = p >> 14;
+    const int oy = (int)(p >> 7) & 127, ox = (int)p & 127;
+    float acc[3] = {a.bias[0], a.bias[1], a.bias[2]};
+#pragma unroll
+    for (int ay = 0; ay < 2; ++ay) {
+      const int ky = ((oy + 1) & 1) + 2 * ay, iy = (oy + 1 - ky) >> 1;
+      if ((unsigned)iy >= 64u) continue;
+#pragma unroll
+      for (int ax = 0; ax < 2; ++ax) {
+        const int kx = ((ox + 1) & 1) + 2 * ax, ix = (ox + 1 - kx) >> 1;
+        if ((unsigned)ix >= 64u) continue;
+        const float* src = a.up5 + ((img << 12) + iy * 64 + ix) * 64;
+        const float* wt = Ws + (ky * 4 + kx) * 4;
+#pragma unroll 4
+        for (int c4 = 0; c4 < 16; ++c4) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * c4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(wt + (4 * c4 + e) * 64);
+            acc[0] = fmaf(v[e], wv[0], acc[0]);
+            acc[1] = fmaf(v[e], wv[1], acc[1]);
+            acc[2] = fmaf(v[e], wv[2], acc[2]);
+          }
+        }
+      }
+    }
+    const float scale = 2.0f / (3.0f * (float)a.npix);
+    const int64_t base = img * 3 * 16384 + (p & 16383);
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+      const float y = tanhf(acc[e]);
+      const float d = y - a.img[base + e * 16384];
+      sq += d * d;
+      g[e] = scale * d * (1.f - y * y);
+      if (a.recon != nullptr) a.recon[base + e * 16384] = y;
+    }
+    *reinterpret_cast<f32x4*>(a.g6 + p * 4) = g;
+  }
+  sq = block_sum(sq, red);
+  const float g0 = block_sum(g[0], red), g1 = block_sum(g[1], red), g2 = block_sum(g[2], red);
+  if (threadIdx.x == 0) *reinterpret_cast<f32x4*>(a.partial + 4 * (size_t)blockIdx.x) = f32x4{sq, g0, g1, g2};
+}
+
+// d up5 [i][ci] = sum over the 16 taps (ky, kx) and co < 3 of g6[(2 iy - 1 + ky, 2 ix - 1 + kx)][co] * W[ci][ky kx][co].
+// Wave w owns channels 16 w .. 16 w + 15 of the workgroup's pixels, a lane one pixel per pass (weights: wave-uniform LDS
+// reads).  Epilogue: deconv5_bn's backward sums over the workgroup's pixels, lanes by shuffles in a fixed order.
+constexpr int kAeDgradRows = 256;                          // input pixels per workgroup (4 passes of 64)
+__global__ __launch_bounds__(kThreads) void k_ae_out_dgrad(AeOutArgs a) {
+  __shared__ __attribute__((aligned(16))) float Ws[kAeOutW];
+  __shared__ __attribute__((aligned(16))) float sums[2 * 64];
+  ae_out_stage_weights(Ws, a.w);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ch0 = wave * 16;
+  const bool stat = a.ep.mode != 0;
+  f32x4 s1[4], s2[4], mu[4], is[4];
+#pragma unroll
+  for (int c4 = 0; c4 < 4; ++c4) {
+    s1[c4] = s2[c4] = mu[c4] = is[c4] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (stat) {
+      mu[c4] = *reinterpret_cast<const f32x4*>(a.ep.mean + ch0 + 4 * c4);
+      is[c4] = *reinterpret_cast<const f32x4*>(a.ep.invstd + ch0 + 4 * c4);
+    }
+  }
+  const int64_t r0 = (int64_t)blockIdx.x * kAeDgradRows;
+  for (int pass = 0; pass < kAeDgradRows / 64; ++pass) {
+    const int64_t i = r0 + pass * 64 + lane;
+    if (i >= a.npix) break;                                // (the tail: the remaining lanes idle, no barrier below)
+    const int64_t img = i >> 12;
+    const int iy = (int)(i >> 6) & 63, ix = (int)i & 63;
+    f32x4 xv[4], yv[4];
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {                       // operands of the statistics: in flight during the sums
+      xv[c4] = yv[c4] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (stat) {
+        xv[c4] = *reinterpret_cast<const f32x4*>(a.ep.x + i * a.ep.x_ld + ch0 + 4 * c4);
+        yv[c4] = *reinterpret_cast<const f32x4*>(a.ep.y + i * a.ep.y_ld + ch0 + 4 * c4);
+      }
+    }
+    f32x4 acc[4];
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) acc[c4] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ky = 0; ky < 4; ++ky) {
+      const int oy = 2 * iy - 1 + ky;
+      if ((unsigned)oy >= 128u) continue;
+#pragma unroll
+      for (int kx = 0; kx < 4; ++kx) {
+        const int ox = 2 * ix - 1 + kx;
+        if ((unsigned)ox >= 128u) continue;
+        const f32x4 d = *reinterpret_cast<const f32x4*>(a.g6 + ((img << 14) + oy * 128 + ox) * 4);
+#pragma unroll
+        for (int c4 = 0; c4 < 4; ++c4)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const f32x4 wv = *reinterpret_cast<const f32x4*>(Ws + ((ch0 + 4 * c4 + e) * 16 + ky * 4 + kx) * 4);
+            acc[c4][e] = fmaf(d[0], wv[0], acc[c4][e]);
+            acc[c4][e] = fmaf(d[1], wv[1], acc[c4][e]);
+            acc[c4][e] = fmaf(d[2], wv[2], acc[c4][e]);
+          }
+      }
+    }
+    float* o = a.du5 + i * 64 + ch0;
+#pragma unroll
+    for (int c4 = 0; c4 < 4; ++c4) {
+      *reinterpret_cast<f32x4*>(o + 4 * c4) = acc[c4];
+      if (stat) fm_stat_terms(a.ep.mode, acc[c4], yv[c4], xv[c4], mu[c4], is[c4], s1[c4], s2[c4]);
+    }
+  }
+  if (!stat) return;
+#pragma unroll
+  for (int c4 = 0; c4 < 4; ++c4)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float v1 = wave_sum(s1[c4][e]), v2 = wave_sum(s2[c4][e]);
+      if (lane == 0) {
+        sums[ch0 + 4 * c4 + e] = v1;
+        sums[64 + ch0 + 4 * c4 + e] = v2;
+      }
+    }
+  __syncthreads();
+  fm_stat_publish(a.ep, (int)blockIdx.x, 0, 64, sums);
+}
+
+// d W[ci][ky kx][co] = sum over input pixels i of up5[i][ci] * g6[(2 iy - 1 + ky, 2 ix - 1 + kx)][co].  Thread = (ci: lane,
+// ky: wave), the four kx and three co in registers; a workgroup walks its block of input pixels in order (four in
+// flight), and writes its [64][16][4] sums to its slab.
+__global__ __launch_bounds__(kThreads) void k_ae_out_wgrad(AeOutArgs a) {
+  const int ci = threadIdx.x & 63, ky = threadIdx.x >> 6;
+  const int64_t p0 = (int64_t)blockIdx.x * a.rows_per_block;
+  const int64_t p1 = p0 + a.rows_per_block < a.npix ? p0 + a.rows_per_block : a.npix;
+  f32x4 acc[4];
+#pragma unroll
+  for (int kx = 0; kx < 4; ++kx) acc[kx] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int64_t pb = p0; pb < p1; pb += 4) {
+    float u[4];
+    f32x4 d[4][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t i = pb + q;
+      const bool live = i < p1;
+      const int64_t ic = live ? i : p0;
+      const int64_t img = ic >> 12;
+      const int iy = (int)(ic >> 6) & 63, ix = (int)ic & 63;
+      const int oy = 2 * iy - 1 + ky;
+      u[q] = live ? a.up5[ic * 64 + ci] : 0.f;
+#pragma unroll
+      for (int kx = 0; kx < 4; ++kx) {
+        const int ox = 2 * ix - 1 + kx;
+        const bool ok = (unsigned)oy < 128u && (unsigned)ox < 128u;
+        d[q][kx] = *reinterpret_cast<const f32x4*>(a.g6 + ((img << 14) + (ok ? oy * 128 + ox : 0)) * 4);
+        if (!ok) d[q][kx] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int kx = 0; kx < 4; ++kx) acc[kx] += d[q][kx] * u[q];
+  }
+  float* slab = a.slabs + (size_t)blockIdx.x * kAeOutW + ci * 64 + ky * 16;
+#pragma unroll
+  for (int kx = 0; kx < 4; ++kx) {
+    f32x4 v = acc[kx];
+    v[3] = 0.f;                                            // (the padded output channel)
+    *reinterpret_cast<f32x4*>(slab + 4 * kx) = v;
+  }
+}
+
+// ------------------------------------------------------------------------------------------ host side
+// Workspace (floats): [P2 weights][BatchNorm scratch + statistics accumulators (the forward model's)][per-image maps x n]
+// [loss partial sums][split-K partial sums][weight-gradient slabs]
+enum AeTensor {
+  AET_COLS = 0, AET_RAW1, AET_A1, AET_RAW2, AET_A2, AET_RAW3, AET_A3, AET_A4, AET_A5, AET_Z,
+  AET_RAWU1, AET_U1, AET_RAWU2, AET_U2, AET_RAWU3, AET_U3, AET_RAWU4, AET_U4, AET_RAWU5, AET_U5, AET_G6,
+  AET_DU5, AET_DU4, AET_DU3, AET_DU2, AET_DU1, AET_DZ, AET_DA5, AET_DA4, AET_DA3, AET_DA2, AET_DA1, AET_COUNT
+};
+static const int64_t kAeTensorFloats[AET_COUNT] = {          // per image
+    4096 * 32, 4096 * 64, 4096 * 64, 1024 * 128, 1024 * 128, 256 * 256, 256 * 256, 64 * 512, 16 * 1024, 128,
+    16 * 1024, 16 * 1024, 64 * 512, 64 * 512, 256 * 256, 256 * 256, 1024 * 128, 1024 * 128, 4096 * 64, 4096 * 64, 16384 * 4,
+    4096 * 64, 1024 * 128, 256 * 256, 64 * 512, 16 * 1024, 128, 16 * 1024, 64 * 512, 256 * 256, 1024 * 128, 4096 * 64};
+static int64_t ae_fixed_floats() {
+  return ae_p2_offset(kAeLayers) + 3 * 2480 + 2 * fm_stat_offset_words(kFmStatSlots);
+}
+static int64_t ae_tensor_offset(int64_t n, int t) {
+  int64_t o = ae_fixed_floats();
+  for (int i = 0; i < t; ++i) o += fm_round4(n * kAeTensorFloats[i]);
+  return o;
+}
+static int64_t ae_ws_floats(int64_t n) {
+  return ae_tensor_offset(n, AET_COUNT) + fm_round4(n * 256) /* loss partial sums */ + kFmPartCap + kFmSlabCap;
+}
+struct AeWs { FmWs fm; float* t[AET_COUNT]; };
+static AeWs ae_ws(float* ws, int64_t n) {
+  AeWs w;
+  memset(&w, 0, sizeof(w));
+  w.fm.p2 = ws;
+  w.fm.bn_mean = ws + ae_p2_offset(kAeLayers);
+  w.fm.bn_invstd = w.fm.bn_mean + 2480;
+  w.fm.bn_meanres = w.fm.bn_invstd + 2480;
+  w.fm.stat_acc = reinterpret_cast<long long*>(w.fm.bn_meanres + 2480);   // 16-byte aligned: every size before it is a multiple of 4 floats
+  w.fm.stat_acc_local = nullptr;                                          // (no cross-rank statistics)
+  for (int i = 0; i < AET_COUNT; ++i) w.t[i] = ws + ae_tensor_offset(n, i);
+  w.fm.loss_partial = ws + ae_tensor_offset(n, AET_COUNT);
+  w.fm.part = w.fm.loss_partial + fm_round4(n * 256);
+  w.fm.slabs = w.fm.part + kFmPartCap;
+  return w;
+}
+static FmBnAt ae_bn_at(int b, const float* params, float* running, float* grad) {
+  FmBnAt at;
+  at.gamma = params + ae_bn_offset(b, false); at.beta = params + ae_bn_offset(b, true);
+  at.running_mean = running ? running + fm_stat_offset(b, false) : nullptr;
+  at.running_var = running ? running + fm_stat_offset(b, true) : nullptr;
+  at.d_gamma = grad ? grad + ae_bn_offset(b, false) : nullptr;
+  at.d_beta = grad ? grad + ae_bn_offset(b, true) : nullptr;
+  at.d_conv_bias = grad ? grad + ae_param_offset(kFmBnLayer[b], true) : nullptr;
+  at.cross_rank = false;                                                  // (the reference trains this model on one device)
+  return at;
+}
+
+// P1 -> P2 of conv1 .. deconv5, one launch (k_fm_pack)
+static int ae_pack(hipStream_t st, const float* params, const FmWs& ws) {
+  FmPackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.params = params; a.p2_base = ws.p2; a.nseg = 0; a.block_begin[0] = 0;
+  int blocks = 0;
+  for (int l = 0; l < 11; ++l) {
+    const FmLayer& L = kAe[l];
+    const int i = a.nseg;
+    a.p1_off[i] = ae_param_offset(l, false); a.p2_off[i] = ae_p2_offset(l); a.count[i] = ae_p2_floats(l);
+    a.cin_[i] = L.cin; a.cout_[i] = L.cout; a.cin_pad_[i] = L.cin_pad; a.cout_pad_[i] = L.cout_pad;
+    a.kind[i] = ae_pack_kind(l);
+    blocks += (int)((a.count[i] + 1023) / 1024);
+    a.block_begin[++a.nseg] = blocks;
+  }
+  KTimer kt("k_fm_pack", st);
+  hipLaunchKernelGGL(k_fm_pack, dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
+  return check_launch("k_fm_pack");
+}
+
+// Adam over the flat vector + the P2 rebuild in one launch (k_fm_adam_pack with this network's segments)
+static int ae_adam_pack(hipStream_t st, float* params, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* step,
+                        float beta1, float beta2, float eps, const FmWs& ws) {
+  FmAdamPackArgs a;
+  memset(&a, 0, sizeof(a));
+  a.params = params; a.grad = grad; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.step = step;
+  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  a.pk.params = params; a.pk.p2_base = ws.p2; a.pk.nseg = 0; a.pk.block_begin[0] = 0;
+  int blocks = 0;
+  int64_t covered = 0;
+  auto plain = [&](int64_t off, int64_t count) {
+    if (count <= 0) return;
+    const int i = a.nplain;
+    a.plain_off[i] = off; a.plain_count[i] = count;
+    a.plain_begin[i + 1] = a.plain_begin[i] + (int)((count + 1023) / 1024);
+    ++a.nplain;
+  };
+  for (int l = 1; l < 11; ++l) {                                       // conv2 .. deconv5: transposing segments
+    const FmLayer& L = kAe[l];
+    const int i = a.pk.nseg;
+    a.pk.p1_off[i] = ae_param_offset(l, false); a.pk.p2_off[i] = ae_p2_offset(l); a.pk.count[i] = ae_p2_floats(l);
+    a.pk.cin_[i] = L.cin; a.pk.cout_[i] = L.cout; a.pk.cin_pad_[i] = L.cin_pad; a.pk.cout_pad_[i] = L.cout_pad;
+    a.pk.kind[i] = ae_pack_kind(l);
+    blocks += (int)(a.pk.count[i] / 1024);                             // (whole 32 x 32 tiles)
+    a.pk.block_begin[++a.pk.nseg] = blocks;
+    plain(covered, ae_param_offset(l, false) - covered);               // what lies before this layer's weights
+    covered = ae_param_offset(l, true);
+  }
+  plain(covered, ae_param_floats() - covered);                         // deconv5's bias, deconv6, BatchNorm
+  a.tile_blocks = blocks;
+  a.r_count[0] = a.r_count[1] = 0;                                     // (no refinement layers)
+  a.r_cin_pad[0] = a.r_cin_pad[1] = 1;
+  a.c1_count = ae_w_floats(0); a.c1_p2 = ae_p2_offset(0);
+  KTimer kt("k_fm_adam_pack", st);
+  hipLaunchKernelGGL(k_fm_adam_pack, dim3((unsigned)(blocks + a.plain_begin[a.nplain])), dim3(kThreads), 0, st, a);
+  return check_launch("k_fm_adam_pack");
+}
+
+// forward pass, training mode, through the loss: g6 = d loss / d (pre-tanh output), loss partial sums
+static int ae_forward_loss(hipStream_t st, const float* params, float* running, const float* images, int64_t n, float* recon,
+                           const AeWs& aw) {
+  fm_attrs();
+  const FmWs& ws = aw.fm;
+  const float* P = params;
+  auto W1 = [&](int l) { return P + ae_param_offset(l, false); };
+  auto B = [&](int l) { return P + ae_param_offset(l, true); };
+  auto W2 = [&](int l) { return (const float*)(ws.p2 + ae_p2_offset(l)); };
+  auto BN = [&](int b) { return ae_bn_at(b, params, running, nullptr); };
+  float* const* t = aw.t;
+  int rc;
+#define AE_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+  {
+    // conv1's columns, and every statistics accumulator of the step zeroed (k_fm_image_cols without actions)
+    KTimer kt("k_fm_image_cols", st);
+    const int64_t opix = n * 4096;
+    const int64_t zero_words = fm_stat_offset_words(kFmStatSlots);
+    const unsigned blocks = (unsigned)((opix + kThreads - 1) / kThreads + (zero_words / 2 + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(k_fm_image_cols<false>, dim3(blocks), dim3(kThreads), 0, st, (const void*)images, opix, t[AET_COLS],
+                       (const float*)nullptr, (int64_t)0, (float*)nullptr, ws.stat_acc, zero_words);
+  }
+  AE_TRY(check_launch("k_fm_image_cols"));
+  FmEpReq eps_[kAeBns];
+  for (int b = 0; b < kAeBns; ++b) eps_[b] = fm_ep_bn_fwd(b);
+  auto EP = [&](int b) { return (const FmEpReq*)&eps_[b]; };
+  // ---- encoder (image_autoencoder.py:36-49)
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv1]", 0, {t[AET_COLS], 32}, 64, 1, W2(0), B(0), {t[AET_RAW1], 64}, 64, 64, n, 32, 64, 1, 0, 0, 0, ws, 0, EP(0)));
+  AE_TRY(fm_bn_fwd_at(st, 0, {t[AET_RAW1], 64}, n * 4096, {t[AET_A1], 64}, BN(0), 1, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv2]", 0, {t[AET_A1], 64}, 64, 2, W1(1), B(1), {t[AET_RAW2], 128}, 32, 32, n, 64, 128, 3, 1, 0, 0, ws, 0, EP(1)));
+  AE_TRY(fm_bn_fwd_at(st, 1, {t[AET_RAW2], 128}, n * 1024, {t[AET_A2], 128}, BN(1), 1, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv3]", 0, {t[AET_A2], 128}, 32, 2, W1(2), B(2), {t[AET_RAW3], 256}, 16, 16, n, 128, 256, 3, 1, 0, 0, ws, 0, EP(2)));
+  AE_TRY(fm_bn_fwd_at(st, 2, {t[AET_RAW3], 256}, n * 256, {t[AET_A3], 256}, BN(2), 1, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv4]", 0, {t[AET_A3], 256}, 16, 2, W1(3), B(3), {t[AET_A4], 512}, 8, 8, n, 256, 512, 3, 1, 1, 0, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv5]", 0, {t[AET_A4], 512}, 8, 2, W1(4), B(4), {t[AET_A5], 1024}, 4, 4, n, 512, 1024, 3, 1, 1, 0, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv6]", 0, {t[AET_A5], 1024}, 4, 1, W1(5), B(5), {t[AET_Z], 128}, 1, 1, n, 1024, 128, 4, 0, 0, 0, ws));
+  // ---- decoder (image_autoencoder.py:80-87)
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv1]", 3, {t[AET_Z], 128}, 1, 1, W2(6), B(6), {t[AET_RAWU1], 1024}, 4, 1, n, 128, 1024, 1, 0, 0, 0, ws, 0, EP(3)));
+  AE_TRY(fm_bn_fwd_at(st, 3, {t[AET_RAWU1], 1024}, n * 16, {t[AET_U1], 1024}, BN(3), 1, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv2]", 1, {t[AET_U1], 1024}, 4, 1, W2(7), B(7), {t[AET_RAWU2], 512}, 8, 4, n, 1024, 512, 2, 0, 0, 0, ws, 0, EP(4)));
+  AE_TRY(fm_bn_fwd_at(st, 4, {t[AET_RAWU2], 512}, n * 64, {t[AET_U2], 512}, BN(4), 1, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv3]", 1, {t[AET_U2], 512}, 8, 1, W2(8), B(8), {t[AET_RAWU3], 256}, 16, 8, n, 512, 256, 2, 0, 0, 0, ws, 0, EP(5)));
+  AE_TRY(fm_bn_fwd_at(st, 5, {t[AET_RAWU3], 256}, n * 256, {t[AET_U3], 256}, BN(5), 1, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv4]", 1, {t[AET_U3], 256}, 16, 1, W2(9), B(9), {t[AET_RAWU4], 128}, 32, 16, n, 256, 128, 2, 0, 0, 0, ws, 0, EP(6)));
+  AE_TRY(fm_bn_fwd_at(st, 6, {t[AET_RAWU4], 128}, n * 1024, {t[AET_U4], 128}, BN(6), 1, ws));
+  if (n * 1024 / kFmBM * 2 >= 256)                                     // (the four parity classes per workgroup: enough tiles from 16 images)
+    AE_TRY(fm_deconv32(st, "k_fm_gemm[ae.deconv5]", {t[AET_U4], 128}, 32, W2(10), B(10), {t[AET_RAWU5], 64}, n, 128, 64, *EP(7), ws));
+  else AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv5]", 1, {t[AET_U4], 128}, 32, 1, W2(10), B(10), {t[AET_RAWU5], 64}, 64, 32, n, 128, 64, 2, 0, 0, 0, ws, 0, EP(7)));
+  AE_TRY(fm_bn_fwd_at(st, 7, {t[AET_RAWU5], 64}, n * 4096, {t[AET_U5], 64}, BN(7), 1, ws));
+  {
+    AeOutArgs o;
+    memset(&o, 0, sizeof(o));
+    o.up5 = t[AET_U5]; o.w = W1(11); o.bias = B(11); o.img = images; o.g6 = t[AET_G6]; o.recon = recon;
+    o.partial = ws.loss_partial; o.npix = n * 16384;
+    KTimer kt("k_ae_out_fwd_loss", st);
+    hipLaunchKernelGGL(k_ae_out_fwd_loss, dim3((unsigned)((o.npix + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, o);
+  }
+  return check_launch("k_ae_out_fwd_loss");
+}
+
+// backward pass: from g6 to every gradient in `grad` (the bias gradient of deconv6 comes from the loss' partial sums)
+static int ae_backward(hipStream_t st, const float* params, int64_t n, float* grad, const AeWs& aw) {
+  const FmWs& ws = aw.fm;
+  const float* P = params;
+  auto W1 = [&](int l) { return P + ae_param_offset(l, false); };
+  auto W2 = [&](int l) { return (const float*)(ws.p2 + ae_p2_offset(l)); };
+  auto GW = [&](int l) { return grad + ae_param_offset(l, false); };
+  auto BN = [&](int b) { return ae_bn_at(b, params, nullptr, grad); };
+  float* const* t = aw.t;
+  int rc;
+  FmSlabPlan plan;
+  memset(&plan, 0, sizeof(plan));
+  plan.a.remap_seg = -1;
+  auto bias_finish = [&](int i) -> int {                               // conv6 / conv5 / conv4 (statistics slot 20 + i)
+    const int layer[3] = {5, 4, 3};
+    FmBiasFinishArgs bf;
+    memset(&bf, 0, sizeof(bf));
+    bf.fin = fm_fin(20 + i, 1, 1, ws, false);
+    bf.fin.out1 = grad + ae_param_offset(layer[i], true);
+    bf.cols = fm_stat_cols(20 + i);
+    KTimer kt("k_fm_bias_finish", st);
+    hipLaunchKernelGGL(k_fm_bias_finish, dim3(1), dim3(kThreads), 0, st, bf);
+    return check_launch("k_fm_bias_finish");
+  };
+  const int64_t in_pix = n * 4096;
+  {
+    // deconv6's weight gradient: one slab per block of input pixels (at most 1,024 blocks), summed with the others' slabs
+    AeOutArgs o;
+    memset(&o, 0, sizeof(o));
+    int64_t nblk = 1024;
+    if (nblk > kFmSlabCap / kAeOutW) nblk = kFmSlabCap / kAeOutW;
+    o.rows_per_block = (in_pix + nblk - 1) / nblk;
+    nblk = (in_pix + o.rows_per_block - 1) / o.rows_per_block;
+    o.up5 = t[AET_U5]; o.g6 = t[AET_G6]; o.slabs = ws.slabs; o.npix = in_pix;
+    FmSlabSumArgs& ps = plan.a;
+    ps.slabs[ps.nseg] = o.slabs; ps.grad[ps.nseg] = GW(11); ps.nchunks[ps.nseg] = (int)nblk; ps.n4[ps.nseg] = kAeOutW / 4;
+    ps.block_begin[ps.nseg] = plan.blocks;
+    plan.blocks += (kAeOutW / 4 + kThreads - 1) / kThreads;
+    ps.block_begin[++ps.nseg] = plan.blocks;
+    plan.used += nblk * kAeOutW;
+    KTimer kt("k_ae_out_wgrad", st);
+    hipLaunchKernelGGL(k_ae_out_wgrad, dim3((unsigned)nblk), dim3(kThreads), 0, st, o);
+  }
+  AE_TRY(check_launch("k_ae_out_wgrad"));
+  {
+    // deconv6's data gradient + the BatchNorm-backward sums of deconv5_bn over it
+    AeOutArgs o;
+    memset(&o, 0, sizeof(o));
+    o.w = W1(11); o.g6 = t[AET_G6]; o.du5 = t[AET_DU5]; o.npix = in_pix;
+    const FmEpReq rq = fm_ep_bn_bwd(7, {t[AET_RAWU5], 64}, {t[AET_U5], 64}, ws);
+    fm_ep_fill(o.ep, rq, ws);
+    KTimer kt("k_ae_out_dgrad", st);
+    hipLaunchKernelGGL(k_ae_out_dgrad, dim3((unsigned)((in_pix + kAeDgradRows - 1) / kAeDgradRows)), dim3(kThreads), 0, st, o);
+  }
+  AE_TRY(check_launch("k_ae_out_dgrad"));
+  // deconv5 .. deconv2: dense = the layer's input map, gathered = d(raw output) at the 4x4 stride-2 taps; every data
+  // gradient leaves the sums the next BatchNorm backward needs
+  AE_TRY(fm_bn_bwd_at(st, 7, {t[AET_RAWU5], 64}, {t[AET_U5], 64}, {t[AET_DU5], 64}, n * 4096, BN(7), ws));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv5]", {t[AET_U4], 128}, 32, 128, {t[AET_RAWU5], 64}, 64, 2, 4, 1, 64, n, GW(10), ws, plan));
+  FmEpReq rq = fm_ep_bn_bwd(6, {t[AET_RAWU4], 128}, {t[AET_U4], 128}, ws);
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv5]", 0, {t[AET_RAWU5], 64}, 64, 2, W1(10), nullptr, {t[AET_DU4], 128}, 32, 32, n, 64, 128, 4, 1, 0, 0, ws, 0, &rq));
+  AE_TRY(fm_bn_bwd_at(st, 6, {t[AET_RAWU4], 128}, {t[AET_U4], 128}, {t[AET_DU4], 128}, n * 1024, BN(6), ws));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv4]", {t[AET_U3], 256}, 16, 256, {t[AET_RAWU4], 128}, 32, 2, 4, 1, 128, n, GW(9), ws, plan));
+  rq = fm_ep_bn_bwd(5, {t[AET_RAWU3], 256}, {t[AET_U3], 256}, ws);
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv4]", 0, {t[AET_RAWU4], 128}, 32, 2, W1(9), nullptr, {t[AET_DU3], 256}, 16, 16, n, 128, 256, 4, 1, 0, 0, ws, 0, &rq));
+  AE_TRY(fm_bn_bwd_at(st, 5, {t[AET_RAWU3], 256}, {t[AET_U3], 256}, {t[AET_DU3], 256}, n * 256, BN(5), ws));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv3]", {t[AET_U2], 512}, 8, 512, {t[AET_RAWU3], 256}, 16, 2, 4, 1, 256, n, GW(8), ws, plan));
+  rq = fm_ep_bn_bwd(4, {t[AET_RAWU2], 512}, {t[AET_U2], 512}, ws);
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv3]", 0, {t[AET_RAWU3], 256}, 16, 2, W1(8), nullptr, {t[AET_DU2], 512}, 8, 8, n, 256, 512, 4, 1, 0, 0, ws, 0, &rq));
+  AE_TRY(fm_bn_bwd_at(st, 4, {t[AET_RAWU2], 512}, {t[AET_U2], 512}, {t[AET_DU2], 512}, n * 64, BN(4), ws));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv2]", {t[AET_U1], 1024}, 4, 1024, {t[AET_RAWU2], 512}, 8, 2, 4, 1, 512, n, GW(7), ws, plan));
+  rq = fm_ep_bn_bwd(3, {t[AET_RAWU1], 1024}, {t[AET_U1], 1024}, ws);
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv2]", 0, {t[AET_RAWU2], 512}, 8, 2, W1(7), nullptr, {t[AET_DU1], 1024}, 4, 4, n, 512, 1024, 4, 1, 0, 0, ws, 0, &rq));
+  // deconv1: a 4x4 "image" of d(raw) per code
+  AE_TRY(fm_bn_bwd_at(st, 3, {t[AET_RAWU1], 1024}, {t[AET_U1], 1024}, {t[AET_DU1], 1024}, n * 16, BN(3), ws));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv1]", {t[AET_Z], 128}, 1, 128, {t[AET_RAWU1], 1024}, 4, 1, 4, 0, 1024, n, GW(6), ws, plan));
+  // conv6: d code, whose column sums are conv6's bias gradient
+  rq = fm_ep_bias(4, 20, {nullptr, 0});
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv1]", 0, {t[AET_RAWU1], 1024}, 4, 1, W1(6), nullptr, {t[AET_DZ], 128}, 1, 1, n, 1024, 128, 4, 0, 0, 0, ws, 0, &rq));
+  AE_TRY(bias_finish(0));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv6]", {t[AET_DZ], 128}, 1, 128, {t[AET_A5], 1024}, 4, 1, 4, 0, 1024, n, GW(5), ws, plan));
+  // conv5, conv4 (ReLU, no BatchNorm): the ReLU's backward is applied as the finished gradient is written
+  rq = fm_ep_bias(3, 21, {t[AET_A5], 1024});
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv6]", 3, {t[AET_DZ], 128}, 1, 1, W2(5), nullptr, {t[AET_DA5], 1024}, 4, 1, n, 128, 1024, 1, 0, 0, 0, ws, 0, &rq));
+  AE_TRY(bias_finish(1));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv5]", {t[AET_DA5], 1024}, 4, 1024, {t[AET_A4], 512}, 8, 2, 3, 1, 512, n, GW(4), ws, plan));
+  rq = fm_ep_bias(3, 22, {t[AET_A4], 512});
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv5]", 2, {t[AET_DA5], 1024}, 4, 1, W2(4), nullptr, {t[AET_DA4], 512}, 8, 4, n, 1024, 512, 2, 0, 0, 0, ws, 0, &rq));
+  AE_TRY(bias_finish(2));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv4]", {t[AET_DA4], 512}, 8, 512, {t[AET_A3], 256}, 16, 2, 3, 1, 256, n, GW(3), ws, plan));
+  rq = fm_ep_bn_bwd(2, {t[AET_RAW3], 256}, {t[AET_A3], 256}, ws);
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv4]", 2, {t[AET_DA4], 512}, 8, 1, W2(3), nullptr, {t[AET_DA3], 256}, 16, 8, n, 512, 256, 2, 0, 0, 0, ws, 0, &rq));
+  // conv3 .. conv1 (the images need no gradient: conv1's data gradient is skipped)
+  AE_TRY(fm_bn_bwd_at(st, 2, {t[AET_RAW3], 256}, {t[AET_A3], 256}, {t[AET_DA3], 256}, n * 256, BN(2), ws));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv3]", {t[AET_RAW3], 256}, 16, 256, {t[AET_A2], 128}, 32, 2, 3, 1, 128, n, GW(2), ws, plan));
+  rq = fm_ep_bn_bwd(1, {t[AET_RAW2], 128}, {t[AET_A2], 128}, ws);
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv3]", 2, {t[AET_RAW3], 256}, 16, 1, W2(2), nullptr, {t[AET_DA2], 128}, 32, 16, n, 256, 128, 2, 0, 0, 0, ws, 0, &rq));
+  AE_TRY(fm_bn_bwd_at(st, 1, {t[AET_RAW2], 128}, {t[AET_A2], 128}, {t[AET_DA2], 128}, n * 1024, BN(1), ws));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv2]", {t[AET_RAW2], 128}, 32, 128, {t[AET_A1], 64}, 64, 2, 3, 1, 64, n, GW(1), ws, plan));
+  rq = fm_ep_bn_bwd(0, {t[AET_RAW1], 64}, {t[AET_A1], 64}, ws);
+  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv2]", 2, {t[AET_RAW2], 128}, 32, 1, W2(1), nullptr, {t[AET_DA1], 64}, 64, 32, n, 128, 64, 2, 0, 0, 0, ws, 0, &rq));
+  AE_TRY(fm_bn_bwd_at(st, 0, {t[AET_RAW1], 64}, {t[AET_A1], 64}, {t[AET_DA1], 64}, n * 4096, BN(0), ws));
+  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv1]", {t[AET_RAW1], 64}, 64, 64, {t[AET_COLS], 32}, 64, 1, 1, 0, 32, n, GW(0), ws, plan, true));   // (columns)
+  return fm_slab_sums(st, plan);
+#undef AE_TRY
+}
+
+}  // namespace ndp
+
+extern "C" {
+
+int64_t ndp_ae_param_floats(void) { return ndp::ae_param_floats(); }
+int64_t ndp_ae_stat_floats(void) { return ndp::ae_stat_floats(); }
+int64_t ndp_ae_workspace_floats(int64_t n_images) {
+  return n_images < 1 || n_images > ndp::kAeMaxImages ? 0 : ndp::ae_ws_floats(n_images);
+}
+
+int64_t ndp_ae_workspace_offset(int64_t n_images, int tensor) {
+  if (n_images < 1 || n_images > ndp::kAeMaxImages || tensor < 0 || tensor >= ndp::AET_COUNT) return -1;
+  return ndp::ae_tensor_offset(n_images, tensor);
+}
+
+int ndp_ae_layout(int what, int index, int64_t* offset, int64_t* dims) {
+  using namespace ndp;
+  NDP_CHECK_ARG(offset && dims, "ndp_ae_layout: null pointer");
+  if (what == 0 || what == 1) {
+    NDP_CHECK_ARG(index >= 0 && index < kAeLayers, "ndp_ae_layout: layer index out of range");
+    const FmLayer& L = kAe[index];
+    *offset = ae_param_offset(index, what == 1);
+    dims[0] = what == 0 ? ae_w_rows(index) : L.cout_pad; dims[1] = what == 0 ? L.ksz * L.ksz : 1;
+    dims[2] = what == 0 ? ae_w_cols(index) : 1; dims[3] = L.kind; dims[4] = L.cin; dims[5] = L.cout;
+    return NDP_OK;
+  }
+  NDP_CHECK_ARG(what >= 2 && what <= 5 && index >= 0 && index < kAeBns, "ndp_ae_layout: bad BatchNorm query");
+  *offset = what < 4 ? ae_bn_offset(index, what == 3) : fm_stat_offset(index, what == 5);
+  dims[0] = kFmBnC[index]; dims[1] = dims[2] = 1; dims[3] = kFmBnLayer[index]; dims[4] = dims[5] = kFmBnC[index];
+  return NDP_OK;
+}
+
+int ndp_ae_pack_params(const float* params, float* workspace, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(params && workspace && aligned16(params) && aligned16(workspace), "ndp_ae_pack_params: bad arguments");
+  return ae_pack((hipStream_t)stream, params, ae_ws(workspace, 1).fm);
+}
+
+int ndp_ae_train_grads(const float* params, float* running_stats, const float* images, int64_t n_images, float* grad,
+                       float* loss, float* loss_sum, float* recon_out, float* workspace, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(params && images && grad && loss && workspace && n_images >= 1, "ndp_ae_train_grads: bad arguments");
+  NDP_CHECK_ARG(n_images <= kAeMaxImages, "ndp_ae_train_grads: more than %d images per call", (int)kAeMaxImages);
+  NDP_CHECK_ARG(aligned16(params) && aligned16(images) && aligned16(grad) && aligned16(workspace) &&
+                (!running_stats || aligned16(running_stats)) && (!recon_out || aligned16(recon_out)),
+                "ndp_ae_train_grads: buffers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const AeWs ws = ae_ws(workspace, n_images);
+  int rc = ae_forward_loss(st, params, running_stats, images, n_images, recon_out, ws);
+  if (rc) return rc;
+  const int nblocks = (int)(n_images * 64);
+  hipLaunchKernelGGL(k_fm_loss_final, dim3(1), dim3(kThreads), 0, st, (const float*)ws.fm.loss_partial, nblocks,
+                     1.0 / (3.0 * (double)(n_images * 16384)), loss, loss_sum, grad + ae_param_offset(11, true));
+  rc = check_launch("k_fm_loss_final");
+  if (rc) return rc;
+  return ae_backward(st, params, n_images, grad, ws);
+}
+
+int ndp_ae_apply_adam(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int32_t* step_count, float lr,
+                      float beta1, float beta2, float eps, float* workspace, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(params && grad && exp_avg && exp_avg_sq && step_count && workspace, "ndp_ae_apply_adam: null pointer");
+  NDP_CHECK_ARG(aligned16(params) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq) && aligned16(workspace),
+                "ndp_ae_apply_adam: buffers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(1), 0, st, step_count, lr, beta1, beta2);
+  return ae_adam_pack(st, params, grad, exp_avg, exp_avg_sq, step_count, beta1, beta2, eps, ae_ws(workspace, 1).fm);
+}
+
+}  // extern "C"

@@ -2070,12 +2070,13 @@ static int fm_stat_sync(hipStream_t st, const FmWs& ws, int slot) {
   return NDP_OK;
 }
 // ... and what the consumer makes of the accumulator of `slot` (FmStatFin); P = this rank's pixels summed over
-static FmStatFin fm_fin(int slot, int what, int64_t P, const FmWs& ws) {
+// (cross_rank false: this rank's sums only, whatever ndp_fm_set_stat_sync installed -- ndp_autoencoder.inc)
+static FmStatFin fm_fin(int slot, int what, int64_t P, const FmWs& ws, bool cross_rank = true) {
   FmStatFin f;
   memset(&f, 0, sizeof(f));
   f.acc = ws.stat_acc + fm_stat_offset_words(slot); f.replicas = fm_stat_replicas(fm_stat_cols(slot));
   f.what = what; f.P = (int)P; f.eps = kFmBnEps; f.momentum = kFmBnMomentum;
-  if (g_fm_sync.fn != nullptr && g_fm_sync.world > 1 && slot < 20) {
+  if (cross_rank && g_fm_sync.fn != nullptr && g_fm_sync.world > 1 && slot < 20) {
     f.P = (int)(P * g_fm_sync.world);
     if (slot >= 10) f.acc_local = ws.stat_acc_local + fm_stat_offset_words(slot);
   }
@@ -2245,11 +2246,31 @@ static FmEpReq fm_ep_bias(int mode, int slot, FmView y) {
   return r;
 }
 
+// Where BatchNorm b's tensors live: the forward model's flat vectors (fm_bn_at), or those of another network whose
+// BatchNorms are the first ones of kFmBnC (ndp_autoencoder.inc).  cross_rank: the statistics go through the
+// ndp_fm_set_stat_sync hook.
+struct FmBnAt {
+  const float* gamma; const float* beta; float* running_mean; float* running_var;
+  float* d_gamma; float* d_beta; float* d_conv_bias;     // backward outputs (d_conv_bias: the bias of the layer in front)
+  bool cross_rank;
+};
+static FmBnAt fm_bn_at(int b, const float* params, float* running, float* grad) {
+  FmBnAt at;
+  at.gamma = params + fm_bn_offset(b, false); at.beta = params + fm_bn_offset(b, true);
+  at.running_mean = running ? running + fm_stat_offset(b, false) : nullptr;
+  at.running_var = running ? running + fm_stat_offset(b, true) : nullptr;
+  at.d_gamma = grad ? grad + fm_bn_offset(b, false) : nullptr;
+  at.d_beta = grad ? grad + fm_bn_offset(b, true) : nullptr;
+  at.d_conv_bias = grad ? grad + fm_param_offset(kFmBnLayer[b], true) : nullptr;
+  at.cross_rank = true;
+  return at;
+}
+
 // BatchNorm b (+ ReLU) forward: raw [P][C] -> dest.  Training mode: batch statistics from the sums the launch that produced
 // `raw` accumulated (mean / invstd / running statistics are written for the backward pass and the caller); eval mode: from
 // the running statistics.
-static int fm_bn_fwd(hipStream_t st, int b, FmView raw, int64_t P, FmView dest, const float* params, float* running,
-                     int training, const FmWs& ws) {
+static int fm_bn_fwd_at(hipStream_t st, int b, FmView raw, int64_t P, FmView dest, const FmBnAt& at, int training,
+                        const FmWs& ws) {
   const int C = kFmBnC[b];
   float* mean = ws.bn_mean + fm_bn_stat_index(b);
   float* invstd = ws.bn_invstd + fm_bn_stat_index(b);
@@ -2257,44 +2278,50 @@ static int fm_bn_fwd(hipStream_t st, int b, FmView raw, int64_t P, FmView dest, 
   FmEltArgs e;
   memset(&e, 0, sizeof(e));
   if (training) {
-    rc = fm_stat_sync(st, ws, b);
-    if (rc) return rc;
-    e.fin = fm_fin(b, 0, P, ws);
+    if (at.cross_rank) {
+      rc = fm_stat_sync(st, ws, b);
+      if (rc) return rc;
+    }
+    e.fin = fm_fin(b, 0, P, ws, at.cross_rank);
     e.fin.out1 = mean; e.fin.out2 = invstd; e.fin.meanres = ws.bn_meanres + fm_bn_stat_index(b);
-    e.fin.running_mean = running ? running + fm_stat_offset(b, false) : nullptr;
-    e.fin.running_var = running ? running + fm_stat_offset(b, true) : nullptr;
+    e.fin.running_mean = at.running_mean;
+    e.fin.running_var = at.running_var;
   } else {
     hipLaunchKernelGGL(k_fm_bn_eval_stats, dim3((unsigned)((C + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                       (const float*)(running + fm_stat_offset(b, false)), (const float*)(running + fm_stat_offset(b, true)),
-                       C, kFmBnEps, mean, invstd);
+                       (const float*)at.running_mean, (const float*)at.running_var, C, kFmBnEps, mean, invstd);
     rc = check_launch("k_fm_bn_eval_stats");
     if (rc) return rc;
   }
   e.x = raw.p; e.x_ld = raw.ld; e.out = dest.p; e.out_ld = dest.ld; e.mean = mean; e.invstd = invstd;
-  e.gamma = params + fm_bn_offset(b, false); e.beta = params + fm_bn_offset(b, true); e.C = C; e.P = (int)P;
+  e.gamma = at.gamma; e.beta = at.beta; e.C = C; e.P = (int)P;
   e.zero_to = 0;                                                     // (no padded map is left: conv_refine_1's 16 channels are stored as 16, kFmR1LD)
   e.iters = fm_elt_iters(P, e.zero_to > C ? e.zero_to : C);
   KTimer kt("k_fm_bn_apply", st);
   hipLaunchKernelGGL(k_fm_bn_apply, fm_elt_grid(P, e.zero_to > C ? e.zero_to : C), dim3(kThreads), 0, st, e);
   return check_launch("k_fm_bn_apply");
 }
+static int fm_bn_fwd(hipStream_t st, int b, FmView raw, int64_t P, FmView dest, const float* params, float* running,
+                     int training, const FmWs& ws) {
+  return fm_bn_fwd_at(st, b, raw, P, dest, fm_bn_at(b, params, running, nullptr), training, ws);
+}
 // BatchNorm b + ReLU backward: raw (x) := d loss / d x, from the sums the launch that produced dy accumulated; writes the
 // BatchNorm weight / bias gradients and the gradient of the convolution bias in front of it (layer l: the column sum of
 // dx -- zero but for rounding, as in the reference)
-static int fm_bn_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int64_t P, const float* params, float* grad,
-                     const FmWs& ws) {
+static int fm_bn_bwd_at(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int64_t P, const FmBnAt& at, const FmWs& ws) {
   const int C = kFmBnC[b];
   FmEltArgs e;
   memset(&e, 0, sizeof(e));
   e.x = raw.p; e.x_ld = raw.ld; e.y = y.p; e.y_ld = y.ld; e.dy = dy.p; e.dy_ld = dy.ld; e.out = raw.p; e.out_ld = raw.ld;
   e.mean = ws.bn_mean + fm_bn_stat_index(b); e.invstd = ws.bn_invstd + fm_bn_stat_index(b);
-  e.gamma = params + fm_bn_offset(b, false);
+  e.gamma = at.gamma;
   e.C = C; e.P = (int)P;
-  int rc = fm_stat_sync(st, ws, 10 + b);
-  if (rc) return rc;
-  e.fin = fm_fin(10 + b, 2, P, ws);
-  e.fin.out1 = grad + fm_bn_offset(b, true); e.fin.out2 = grad + fm_bn_offset(b, false);
-  e.fin.out3 = grad + fm_param_offset(kFmBnLayer[b], true);
+  if (at.cross_rank) {
+    int rc = fm_stat_sync(st, ws, 10 + b);
+    if (rc) return rc;
+  }
+  e.fin = fm_fin(10 + b, 2, P, ws, at.cross_rank);
+  e.fin.out1 = at.d_beta; e.fin.out2 = at.d_gamma;
+  e.fin.out3 = at.d_conv_bias;
   e.fin.meanres = ws.bn_meanres + fm_bn_stat_index(b); e.fin.gamma = e.gamma; e.fin.invstd = e.invstd;
   e.iters = fm_elt_iters(P, C);
   {
@@ -2302,6 +2329,10 @@ static int fm_bn_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int
     hipLaunchKernelGGL(k_fm_bn_bwd_apply, fm_elt_grid(P, C), dim3(kThreads), 0, st, e);
   }
   return check_launch("k_fm_bn_bwd_apply");
+}
+static int fm_bn_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int64_t P, const float* params, float* grad,
+                     const FmWs& ws) {
+  return fm_bn_bwd_at(st, b, raw, y, dy, P, fm_bn_at(b, params, nullptr, grad), ws);
 }
 
 // deconv6's forward pass, the four parity classes per workgroup (k_fm_deconv32)

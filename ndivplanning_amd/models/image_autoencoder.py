@@ -1,15 +1,17 @@
-"""Frozen image encoder that produces the GAN's condition codes -- mirror of the reference's
-`models/image_autoencoder.py::Encoder` (image_autoencoder.py:14-49): 5 x conv3x3 stride 2
-(BatchNorm only after the first three; conv4_bn / conv5_bn exist as attributes but are not
-applied) + a 4x4 conv to 128 channels; 3x128x128 -> 128x1x1.
+"""Image autoencoder -- mirror of the reference's `models/image_autoencoder.py` (image_autoencoder.py:14-87).
 
-On the GAN path it runs in eval mode ahead of the step and its output is detached (train_gan.py:75-76,
-152-153): that case -- CUDA input, eval mode, input without grad -- goes through the gfx950
-kernels of `csrc/ndp_encoder.inc` (`ndp_encoder_forward`: implicit-GEMM convolutions on the fp32
-matrix pipe, BatchNorm folded into the weights).  Training the autoencoder itself
-(train_autoencoder.py) is outside this repository's scope; a forward in training mode or with
-gradients keeps PyTorch's operators so that the class still behaves like an nn.Module there.
-The class also exists so that the reference's whole-module encoder pickles load."""
+`Encoder`: 5 x conv3x3 stride 2 (BatchNorm only after the first three; conv4_bn / conv5_bn exist as attributes but are
+not applied) + a 4x4 conv to 128 channels; 3x128x128 -> 128x1x1.  `Decoder`: deconv1 (128 -> 1024, 4x4 on the 1x1 code),
+deconv2..5 (ConvTranspose2d(c, c/2, 4, 2, 1)), each + BatchNorm + ReLU, deconv6 (64 -> 3) + tanh.  Same attribute names,
+state_dict keys and `weight_init` as the reference, so that its whole-module pickles load.
+
+On the GAN path the encoder runs in eval mode ahead of the step and its output is detached (train_gan.py:75-76,
+152-153): that case -- CUDA input, eval mode, input without grad -- goes through the gfx950 kernels of
+`csrc/ndp_encoder.inc` (`ndp_encoder_forward`: implicit-GEMM convolutions on the fp32 matrix pipe, BatchNorm folded into
+the weights).  Training both modules (train_autoencoder.py) goes through `ndivplanning_amd.autoencoder_trainer`
+(`ndp_ae_train_grads` / `ndp_ae_apply_adam`, csrc/ndp_autoencoder.inc), which owns the flat vectors `pack_autoencoder`
+builds.  A forward in training mode or with gradients, and every `Decoder.forward`, keep PyTorch's operators so that the
+classes still behave like nn.Modules there."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -73,6 +75,126 @@ class Encoder(nn.Module):
         x = F.relu(self.conv4(x))
         x = F.relu(self.conv5(x))
         return self.conv6(x)
+
+
+class Decoder(nn.Module):
+    _CHANNELS = (1024, 512, 256, 128, 64)
+
+    def __init__(self, d=128):
+        super().__init__()
+        ch = self._CHANNELS
+        self.deconv1 = nn.ConvTranspose2d(128, ch[0], 4, 1, 0)
+        self.deconv1_bn = nn.BatchNorm2d(ch[0])
+        for i in range(1, 5):
+            setattr(self, "deconv%d" % (i + 1), nn.ConvTranspose2d(ch[i - 1], ch[i], 4, 2, 1))
+            setattr(self, "deconv%d_bn" % (i + 1), nn.BatchNorm2d(ch[i]))
+        self.deconv6 = nn.ConvTranspose2d(ch[4], 3, 4, 2, 1)
+
+    def weight_init(self, mean, std):
+        for name in self._modules:
+            normal_init(self._modules[name], mean, std)
+
+    def forward(self, z):
+        for i in range(1, 6):
+            z = F.relu(getattr(self, "deconv%d_bn" % i)(getattr(self, "deconv%d" % i)(z)))
+        return torch.tanh(self.deconv6(z))
+
+
+# ---------------------------------------------------------------- flat vectors of ndp_ae_* <-> modules
+AE_LAYERS = (("encoder", "conv1"), ("encoder", "conv2"), ("encoder", "conv3"), ("encoder", "conv4"), ("encoder", "conv5"),
+             ("encoder", "conv6"), ("decoder", "deconv1"), ("decoder", "deconv2"), ("decoder", "deconv3"),
+             ("decoder", "deconv4"), ("decoder", "deconv5"), ("decoder", "deconv6"))
+AE_BNS = (("encoder", "conv1_bn"), ("encoder", "conv2_bn"), ("encoder", "conv3_bn"), ("decoder", "deconv1_bn"),
+          ("decoder", "deconv2_bn"), ("decoder", "deconv3_bn"), ("decoder", "deconv4_bn"), ("decoder", "deconv5_bn"))
+
+
+def ae_layout(lib, what, index):
+    import ctypes
+    from .. import _capi
+    off, dims = ctypes.c_int64(), (ctypes.c_int64 * 6)()
+    _capi.check(lib.ndp_ae_layout(what, index, ctypes.byref(off), dims), "ndp_ae_layout")
+    return off.value, list(dims)
+
+
+def _to_kernel_layout(weight, rows, cols):
+    w = weight.detach().float().permute(0, 2, 3, 1)                    # [dim0][kh][kw][dim1]
+    out = torch.zeros(rows, w.shape[1], w.shape[2], cols, dtype=torch.float32, device=w.device)
+    out[: w.shape[0], :, :, : w.shape[3]] = w
+    return out
+
+
+def _from_kernel_layout(flat_w, rows, taps, cols, shape):
+    k = int(round(taps ** 0.5))
+    w = flat_w.view(rows, k, k, cols)[: shape[0], :, :, : shape[1]]
+    return w.permute(0, 3, 1, 2).contiguous()
+
+
+def pack_autoencoder(encoder, decoder, device=None):
+    """(params, running_stats): the flat vectors ndp_ae_train_grads reads, from an Encoder and a Decoder (layout:
+    include/ndp.h, image autoencoder).  conv4_bn / conv5_bn are not part of them."""
+    from .. import _capi
+    lib = _capi.load()
+    mods = {"encoder": encoder, "decoder": decoder}
+    device = device if device is not None else next(encoder.parameters()).device
+    params = torch.zeros(lib.ndp_ae_param_floats(), dtype=torch.float32, device=device)
+    stats = torch.zeros(lib.ndp_ae_stat_floats(), dtype=torch.float32, device=device)
+    with torch.no_grad():
+        for i, (m, name) in enumerate(AE_LAYERS):
+            mod = getattr(mods[m], name)
+            off, d = ae_layout(lib, 0, i)
+            params[off:off + d[0] * d[1] * d[2]] = _to_kernel_layout(mod.weight, d[0], d[2]).to(device).reshape(-1)
+            boff, _ = ae_layout(lib, 1, i)
+            params[boff:boff + mod.bias.numel()] = mod.bias.detach().float().to(device)
+        for i, (m, name) in enumerate(AE_BNS):
+            bn = getattr(mods[m], name)
+            c = bn.weight.numel()
+            params[ae_layout(lib, 2, i)[0]:][:c] = bn.weight.detach().float().to(device)
+            params[ae_layout(lib, 3, i)[0]:][:c] = bn.bias.detach().float().to(device)
+            stats[ae_layout(lib, 4, i)[0]:][:c] = bn.running_mean.detach().float().to(device)
+            stats[ae_layout(lib, 5, i)[0]:][:c] = bn.running_var.detach().float().to(device)
+    return params, stats
+
+
+def unpack_autoencoder_vector(vec, encoder=None, decoder=None):
+    """'encoder.conv1.weight' ... -> tensor in the modules' own shapes, from a flat vector in the parameters' layout
+    (parameters, gradients or Adam moments)."""
+    from .. import _capi
+    lib = _capi.load()
+    mods = {"encoder": encoder if encoder is not None else Encoder(), "decoder": decoder if decoder is not None else Decoder()}
+    out = {}
+    for i, (m, name) in enumerate(AE_LAYERS):
+        shape = tuple(getattr(mods[m], name).weight.shape)
+        off, d = ae_layout(lib, 0, i)
+        out["%s.%s.weight" % (m, name)] = _from_kernel_layout(vec[off:off + d[0] * d[1] * d[2]], d[0], d[1], d[2], shape)
+        boff, _ = ae_layout(lib, 1, i)
+        out["%s.%s.bias" % (m, name)] = vec[boff:boff + d[5]].clone()
+    for i, (m, name) in enumerate(AE_BNS):
+        off, d = ae_layout(lib, 2, i)
+        out["%s.%s.weight" % (m, name)] = vec[off:off + d[0]].clone()
+        off, d = ae_layout(lib, 3, i)
+        out["%s.%s.bias" % (m, name)] = vec[off:off + d[0]].clone()
+    return out
+
+
+def unpack_into_autoencoder(encoder, decoder, params, stats=None, batches_tracked=None):
+    """Write the flat vectors back into the modules (after HIP training).  conv4_bn / conv5_bn -- no gradient, as torch's
+    Adam leaves a parameter whose .grad is None -- keep their parameters, running statistics and counters."""
+    mods = {"encoder": encoder, "decoder": decoder}
+    from .. import _capi
+    lib = _capi.load()
+    tensors = unpack_autoencoder_vector(params, encoder, decoder)
+    with torch.no_grad():
+        for key, value in tensors.items():
+            m, name, attr = key.split(".")
+            getattr(getattr(mods[m], name), attr).copy_(value)
+        if stats is not None:
+            for i, (m, name) in enumerate(AE_BNS):
+                bn = getattr(mods[m], name)
+                c = bn.weight.numel()
+                bn.running_mean.copy_(stats[ae_layout(lib, 4, i)[0]:][:c])
+                bn.running_var.copy_(stats[ae_layout(lib, 5, i)[0]:][:c])
+                if batches_tracked is not None:
+                    bn.num_batches_tracked.fill_(int(batches_tracked))
 
 
 def pack_encoder_params(enc):

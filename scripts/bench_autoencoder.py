@@ -1,0 +1,93 @@
+"""Time one autoencoder training step (train_autoencoder.py:79-90) on the GPU box: the HIP trainer (ndp_ae_train_grads +
+ndp_ae_apply_adam) vs the reference loop unchanged on PyTorch-ROCm / MIOpen (module forward, mse, backward,
+torch.optim.Adam).  Median ms/step over STEPS timed steps after WARMUP, fraction of the fp32 MFMA peak, per-kernel split
+of the HIP step.  Usage: python scripts/bench_autoencoder.py [N ...]   (default: 240 16)"""
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from ndivplanning_amd import _capi  # noqa: E402
+from ndivplanning_amd.autoencoder_trainer import AutoencoderTrainer  # noqa: E402
+from ndivplanning_amd.models.image_autoencoder import Decoder, Encoder  # noqa: E402
+
+DEV = "cuda:0"
+PEAK = 157.3e12                                      # fp32 MFMA, MI355X
+STEPS, WARMUP = int(os.environ.get("STEPS", 20)), int(os.environ.get("WARMUP", 5))
+
+
+def macs_per_image():
+    """Forward multiply-adds of Encoder + Decoder per 128 x 128 image, from the module shapes."""
+    total = 0
+    hw = 128
+    for cin, cout in ((3, 64), (64, 128), (128, 256), (256, 512), (512, 1024)):
+        hw //= 2
+        total += hw * hw * cout * cin * 9
+    total += 1024 * 128 * 16                        # conv6
+    total += 16 * 1024 * 128                        # deconv1 (4 x 4 outputs, one tap each)
+    hw = 4
+    for cin, cout in ((1024, 512), (512, 256), (256, 128), (128, 64), (64, 3)):
+        hw *= 2
+        total += hw * hw * cout * cin * 4           # stride 2, 4 x 4 kernel: 4 taps per output pixel
+    return total
+
+
+def models():
+    torch.manual_seed(1)
+    enc, dec = Encoder(), Decoder()
+    dec.weight_init(0.0, 0.02)
+    enc.weight_init(0.0, 0.02)
+    return enc.to(DEV).train(), dec.to(DEV).train()
+
+
+def median_ms(fn):
+    for _ in range(WARMUP):
+        fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(STEPS):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    ts.sort()
+    return 1e3 * ts[len(ts) // 2]
+
+
+def main(sizes):
+    flop_img = 2.0 * 3 * macs_per_image()            # forward + data gradients + weight gradients
+    print("forward MACs per image %.1f M; %.2f GFLOP per training image" % (macs_per_image() / 1e6, flop_img / 1e9))
+    for n in sizes:
+        x = torch.rand(n, 3, 128, 128, device=DEV) * 2 - 1
+        enc, dec = models()
+        tr = AutoencoderTrainer(enc, dec, batch=n)
+        t_hip = median_ms(lambda: tr.step(x))
+        enc, dec = models()
+        mse = torch.nn.MSELoss()
+        opt = torch.optim.Adam([{"params": dec.parameters()}, {"params": enc.parameters()}], lr=2e-4, betas=(0.5, 0.999))
+
+        def ref_step():
+            loss = mse(dec(enc._forward_torch(x)), x)
+            opt.zero_grad()
+            loss.backward()
+            opt.step()
+        t_ref = median_ms(ref_step)
+        flop = flop_img * n
+        print("n=%d  hip %.3f ms/step = %.1f TFLOP/s (%.1f %% of peak)   pytorch-rocm %.3f ms/step = %.1f TFLOP/s "
+              "(%.1f %%)   speed-up %.2fx" % (n, t_hip, flop / t_hip / 1e9, 100 * flop / (t_hip * 1e-3) / PEAK, t_ref,
+                                             flop / t_ref / 1e9, 100 * flop / (t_ref * 1e-3) / PEAK, t_ref / t_hip))
+        _capi.timing_enable(True)
+        tr.step(x)
+        torch.cuda.synchronize()
+        split = sorted(_capi.timing_collect().items(), key=lambda kv: -kv[1][0])
+        _capi.timing_enable(False)
+        total = sum(v[0] for _, v in split)
+        for name, (ms, cnt) in split[:16]:
+            print("   %-26s %8.3f ms (%2d launches) %5.1f %%" % (name, ms, cnt, 100 * ms / total))
+
+
+if __name__ == "__main__":
+    main([int(a) for a in sys.argv[1:]] or [240, 16])
