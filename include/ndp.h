@@ -432,6 +432,23 @@ int ndp_ae_train_grads(const float *params, float *running_stats, const float *i
 int ndp_ae_apply_adam(float *params, const float *grad, float *exp_avg, float *exp_avg_sq,
                       int32_t *step_count, float lr, float beta1, float beta2, float eps,
                       float *workspace, void *stream);
+/* Data parallel: ndp_ae_train_grads for one rank's share of a global batch, with
+ *   - cross-rank BatchNorm statistics through the function given with THIS call (ndp_fm_stat_sync_fn: same contract as
+ *     ndp_fm_set_stat_sync's, which this call never uses): the 8 BatchNorms call stat_sync(acc, words, stream, stat_ctx)
+ *     between the launch that fills an accumulator and the launch that reads it, 8 forward + 8 backward calls; the
+ *     running statistics and dx come from the sums over the ranks, d gamma / d beta from this rank's own.
+ *     stat_sync == NULL or world == 1: this rank's statistics only (1 <= world <= 4096);
+ *   - gradient buckets: ndp_ae_grad_buckets writes the 6 ranges (offset, count: floats of the flat gradient) in the
+ *     order the backward pass completes them -- deconv3..6, deconv2, deconv1 + conv6, conv5, conv1..4, the BatchNorm
+ *     weights and biases; they cover the vector exactly once -- and the count through n_buckets (NDP_OK, or an error
+ *     code and nothing written).  Every ndp_ae_train_grads_dp call records one event per bucket where its last byte is
+ *     written; ndp_ae_bucket_wait(b, stream) makes `stream` wait for bucket b of the most recent such call on the current
+ *     device (NDP_E_ARG before the first one).  The gradient bits are those of ndp_ae_train_grads. */
+int ndp_ae_train_grads_dp(const float *params, float *running_stats, const float *images, int64_t n_images,
+                          float *grad, float *loss, float *loss_sum, float *recon_out, float *workspace,
+                          void *stream, ndp_fm_stat_sync_fn stat_sync, void *stat_ctx, int world);
+int ndp_ae_grad_buckets(int64_t *offsets, int64_t *counts, int capacity, int *n_buckets);
+int ndp_ae_bucket_wait(int bucket, void *stream);
 
 /* ------------------------------------------------------------- evaluation ---
  * The glue of the evaluation scripts (control_evaluation.py, complete_eval.py, mpc_eval.py) between the encoder, the

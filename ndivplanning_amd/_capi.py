@@ -129,6 +129,10 @@ SIGNATURES = {
                                    c_void_p]),
     "ndp_ae_apply_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                   c_void_p, c_void_p]),
+    "ndp_ae_train_grads_dp": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "ndp_ae_grad_buckets": (c_int, [POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_int)]),
+    "ndp_ae_bucket_wait": (c_int, [c_int, c_void_p]),
     "ndp_eval_score_select": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ndp_eval_mse_ws_floats": (c_int64, [c_int64]),
@@ -244,6 +248,16 @@ def fm_grad_buckets():
         msg = lib.ndp_last_error()
         raise NdpError("ndp_fm_grad_buckets failed: %s" % (msg.decode() if msg else "?"))
     return [(int(off[i]), int(cnt[i])) for i in range(n)]
+
+
+def ae_grad_buckets():
+    """[(offset, count)]: the ranges of the autoencoder's flat gradient in completion order (ndp_ae_grad_buckets)."""
+    lib = load()
+    off = (ctypes.c_int64 * 16)()
+    cnt = (ctypes.c_int64 * 16)()
+    n = ctypes.c_int(0)
+    check(lib.ndp_ae_grad_buckets(off, cnt, 16, ctypes.byref(n)), "ndp_ae_grad_buckets")
+    return [(int(off[i]), int(cnt[i])) for i in range(n.value)]
 
 
 STAT_SYNC_FN = ctypes.CFUNCTYPE(None, c_void_p, c_int64, c_void_p, c_void_p)    # ndp_fm_stat_sync_fn (include/ndp.h)

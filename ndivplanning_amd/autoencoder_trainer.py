@@ -8,7 +8,15 @@
 The trainer owns the flat parameter vector the kernels read (include/ndp.h: image autoencoder), its gradient, the Adam
 moments (one Adam over both modules, as the reference's two parameter groups with the same settings) and the running
 BatchNorm statistics; `sync_to_modules()` writes them back into the `Encoder` and `Decoder` (the reference saves the whole
-modules: train_autoencoder.py:92-97).  There is no CPU path."""
+modules: train_autoencoder.py:92-97).  There is no CPU path.
+
+Data parallel (one rank's share of a global batch), as ForwardModelTrainer: `reduce_fn(grad)` all-reduces the gradient
+between the two library calls, or `bucket_reduce` (dp.BucketedMeanAllReduce over ndp_ae_grad_buckets /
+ndp_ae_bucket_wait) does it per gradient bucket beside the rest of the backward pass; `sync_batchnorm_world` > 1 sums
+the BatchNorm statistics over the ranks (`stat_group`: their process group) through a callback passed with every
+ndp_ae_train_grads_dp call, so that W ranks with B / W images each train the step of one process with B images."""
+import ctypes
+
 import torch
 
 from . import _capi
@@ -17,7 +25,8 @@ from .models import image_autoencoder as IA
 
 class AutoencoderTrainer:
     def __init__(self, encoder: IA.Encoder, decoder: IA.Decoder, batch: int, lr: float = 2e-4, betas=(0.5, 0.999),
-                 eps: float = 1e-8, keep_reconstruction: bool = False):
+                 eps: float = 1e-8, keep_reconstruction: bool = False, reduce_fn=None, bucket_reduce=None,
+                 sync_batchnorm_world: int = 1, stat_group=None):
         self.lib = _capi.load()
         self.encoder, self.decoder = encoder, decoder
         dev = next(encoder.parameters()).device
@@ -27,6 +36,12 @@ class AutoencoderTrainer:
         self.device, self.batch = dev, int(batch)
         if self.batch < 1 or self.lib.ndp_ae_workspace_floats(self.batch) <= 0:
             raise _capi.NdpError("AutoencoderTrainer: unsupported batch of %d images" % self.batch)
+        if reduce_fn is not None and bucket_reduce is not None:
+            raise ValueError("give either reduce_fn (one collective) or bucket_reduce (per-bucket, overlapped)")
+        if int(sync_batchnorm_world) < 1:
+            raise ValueError("sync_batchnorm_world must be >= 1, got %r" % (sync_batchnorm_world,))
+        self.reduce_fn, self.bucket_reduce = reduce_fn, bucket_reduce
+        self.sync_world = int(sync_batchnorm_world)
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         f32 = dict(dtype=torch.float32, device=dev)
         self.params, self.stats = IA.pack_autoencoder(encoder, decoder, dev)
@@ -40,6 +55,12 @@ class AutoencoderTrainer:
         self.steps = 0                                                       # Adam steps
         self.forwards = 0                                                    # training-mode forwards (num_batches_tracked)
         self._batches0 = int(encoder.conv1_bn.num_batches_tracked.item())
+        # cross-rank statistics: the callback and the ctypes thunk the library calls, alive until close()
+        self.stat_sync, self._stat_cb = None, None
+        if self.sync_world > 1:
+            from . import dp
+            self.stat_sync = dp.StatAllReduce(self.workspace, group=stat_group)
+            self._stat_cb = _capi.STAT_SYNC_FN(self.stat_sync)
         self._pack()
 
     def _pack(self):
@@ -58,10 +79,22 @@ class AutoencoderTrainer:
             raise _capi.NdpError("images: expected a contiguous float32 [%d, 3, 128, 128] tensor on %s, got %s %s on %s"
                                  % (n, self.device, images.dtype, list(images.shape), images.device))
         p = _capi.ptr
+        recon = p(self.recon) if self.recon is not None else None
         with torch.cuda.device(self.device):
-            _capi.check(self.lib.ndp_ae_train_grads(p(self.params), p(self.stats), p(images), n, p(self.grad), p(self.loss),
-                                                    p(self.loss_sum), p(self.recon) if self.recon is not None else None,
-                                                    p(self.workspace), _capi.stream_ptr(self.device)), "ndp_ae_train_grads")
+            if self.sync_world == 1 and self.bucket_reduce is None:
+                _capi.check(self.lib.ndp_ae_train_grads(p(self.params), p(self.stats), p(images), n, p(self.grad),
+                                                        p(self.loss), p(self.loss_sum), recon, p(self.workspace),
+                                                        _capi.stream_ptr(self.device)), "ndp_ae_train_grads")
+            else:
+                if self.sync_world > 1 and self._stat_cb is None:
+                    raise _capi.NdpError("AutoencoderTrainer: closed (its cross-rank statistics callback is released)")
+                fn = ctypes.cast(self._stat_cb, ctypes.c_void_p) if self._stat_cb is not None else None
+                _capi.check(self.lib.ndp_ae_train_grads_dp(p(self.params), p(self.stats), p(images), n, p(self.grad),
+                                                           p(self.loss), p(self.loss_sum), recon, p(self.workspace),
+                                                           _capi.stream_ptr(self.device), fn, None, self.sync_world),
+                            "ndp_ae_train_grads_dp")
+        if self.stat_sync is not None:
+            self.stat_sync.check()
         self.forwards += 1
         return self.loss
 
@@ -75,10 +108,23 @@ class AutoencoderTrainer:
         self.steps += 1
 
     def step(self, images):
-        """The loop body of train_autoencoder.py:79-90 for one image batch; returns the loss (device scalar)."""
+        """The loop body of train_autoencoder.py:79-90 for one image batch; returns the loss (device scalar: this rank's,
+        the mean over its own images)."""
         self.grads(images)
+        if self.bucket_reduce is not None:
+            self.bucket_reduce(self.grad, self.device)
+        elif self.reduce_fn is not None:
+            self.reduce_fn(self.grad)
         self.apply()
         return self.loss
+
+    def close(self):
+        """Release the cross-rank statistics callback (if any); a closed data-parallel trainer refuses grads()."""
+        self.stat_sync, self._stat_cb = None, None
+
+    def gradient_buckets(self):
+        """[(offset, count)] of the flat gradient, in the order the backward pass completes them."""
+        return _capi.ae_grad_buckets()
 
     def load_from_modules(self):
         """Take parameters and running statistics from the modules again (after they were changed from outside)."""

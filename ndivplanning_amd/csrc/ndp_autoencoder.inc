@@ -25,6 +25,12 @@
 // largest map is n x 4,096 pixels: conv1's output and up5); the new kernels index in 64 bits.  ndp_ae_* accept
 // 1 <= n <= kAeMaxImages = 8192 (n x 4,096 < 2^31 with a wide margin; the fixed-point statistics of the largest map stay
 // far inside their 2^50 range), as the ndp_fm_* calls do.
+//
+// Data parallel (ndp_ae_train_grads_dp): the same pass, with the BatchNorm statistics summed over the ranks through the
+// caller's per-call function (fm_stat_sync; 8 forward + 8 backward calls) and one event per gradient bucket, recorded
+// where the backward pass has written the bucket's last byte (ae_backward's close_bucket; ndp_ae_bucket_wait).
+
+#include <atomic>
 
 namespace ndp {
 
@@ -280,7 +286,8 @@ __global__ __launch_bounds__(kThreads) void k_ae_out_wgrad(AeOutArgs a) {
 
 // ------------------------------------------------------------------------------------------ host side
 // Workspace (floats): [P2 weights][BatchNorm scratch + statistics accumulators (the forward model's)][per-image maps x n]
-// [loss partial sums][split-K partial sums][weight-gradient slabs]
+// [loss partial sums][split-K partial sums][weight-gradient slabs][this rank's copy of the accumulators (cross-rank
+// statistics: FmWs::stat_acc_local)]
 enum AeTensor {
   AET_COLS = 0, AET_RAW1, AET_A1, AET_RAW2, AET_A2, AET_RAW3, AET_A3, AET_A4, AET_A5, AET_Z,
   AET_RAWU1, AET_U1, AET_RAWU2, AET_U2, AET_RAWU3, AET_U3, AET_RAWU4, AET_U4, AET_RAWU5, AET_U5, AET_G6,
@@ -299,7 +306,8 @@ static int64_t ae_tensor_offset(int64_t n, int t) {
   return o;
 }
 static int64_t ae_ws_floats(int64_t n) {
-  return ae_tensor_offset(n, AET_COUNT) + fm_round4(n * 256) /* loss partial sums */ + kFmPartCap + kFmSlabCap;
+  return ae_tensor_offset(n, AET_COUNT) + fm_round4(n * 256) /* loss partial sums */ + kFmPartCap + kFmSlabCap +
+         2 * fm_stat_offset_words(kFmStatSlots);
 }
 struct AeWs { FmWs fm; float* t[AET_COUNT]; };
 static AeWs ae_ws(float* ws, int64_t n) {
@@ -310,14 +318,15 @@ static AeWs ae_ws(float* ws, int64_t n) {
   w.fm.bn_invstd = w.fm.bn_mean + 2480;
   w.fm.bn_meanres = w.fm.bn_invstd + 2480;
   w.fm.stat_acc = reinterpret_cast<long long*>(w.fm.bn_meanres + 2480);   // 16-byte aligned: every size before it is a multiple of 4 floats
-  w.fm.stat_acc_local = nullptr;                                          // (no cross-rank statistics)
   for (int i = 0; i < AET_COUNT; ++i) w.t[i] = ws + ae_tensor_offset(n, i);
   w.fm.loss_partial = ws + ae_tensor_offset(n, AET_COUNT);
   w.fm.part = w.fm.loss_partial + fm_round4(n * 256);
   w.fm.slabs = w.fm.part + kFmPartCap;
+  w.fm.stat_acc_local = reinterpret_cast<long long*>(w.fm.slabs + kFmSlabCap);
   return w;
 }
-static FmBnAt ae_bn_at(int b, const float* params, float* running, float* grad) {
+// sync: the caller's cross-rank statistics (ndp_ae_train_grads_dp) or null (this rank's own)
+static FmBnAt ae_bn_at(int b, const float* params, float* running, float* grad, const FmStatSync* sync) {
   FmBnAt at;
   at.gamma = params + ae_bn_offset(b, false); at.beta = params + ae_bn_offset(b, true);
   at.running_mean = running ? running + fm_stat_offset(b, false) : nullptr;
@@ -325,8 +334,41 @@ static FmBnAt ae_bn_at(int b, const float* params, float* running, float* grad) 
   at.d_gamma = grad ? grad + ae_bn_offset(b, false) : nullptr;
   at.d_beta = grad ? grad + ae_bn_offset(b, true) : nullptr;
   at.d_conv_bias = grad ? grad + ae_param_offset(kFmBnLayer[b], true) : nullptr;
-  at.cross_rank = false;                                                  // (the reference trains this model on one device)
+  at.sync = sync;                                                         // (never the forward model's ndp_fm_set_stat_sync)
   return at;
+}
+
+// Gradient buckets of ndp_ae_train_grads_dp: ranges of the flat gradient in the order ae_backward completes them (weight
+// gradients last layer first; a layer's bias gradient is final before its weight gradient starts).  Each is closed as
+// fm_backward closes its buckets: the row-chunk slabs of its layers are summed, then its event is recorded.
+//   bucket 0  layers 8..11 (deconv3..6)        3  layer 4 (conv5)
+//          1  layer 7 (deconv2: 8.4 M floats)  4  layers 0..3 (conv1..4)
+//          2  layers 5, 6 (conv6, deconv1)     5  the BatchNorm weights and biases (final after conv1_bn's backward)
+constexpr int kAeBuckets = 6;
+static const int kAeBucketFirst[kAeBuckets] = {8, 7, 5, 4, 0, -1};    // first layer of the range (-1: BatchNorm parameters)
+static const int kAeBucketEnd[kAeBuckets] = {12, 8, 7, 5, 4, -1};     // one past its last layer
+static void ae_bucket_range(int b, int64_t* offset, int64_t* count) {
+  if (kAeBucketFirst[b] < 0) {
+    *offset = ae_bn_offset(0, false);
+    *count = ae_param_floats() - *offset;
+  } else {
+    *offset = ae_param_offset(kAeBucketFirst[b], false);
+    *count = ae_param_offset(kAeBucketEnd[b], false) - *offset;
+  }
+}
+// per device; `recorded` once a ndp_ae_train_grads_dp call has recorded all of them (ndp_ae_bucket_wait refuses before)
+struct AeBucketEvents { hipEvent_t ev[kAeBuckets]; bool ok; std::atomic<bool> recorded; };
+static AeBucketEvents g_ae_buckets[kMaxDevices];
+static std::once_flag g_ae_buckets_once[kMaxDevices];
+static AeBucketEvents* ae_bucket_events() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
+  AeBucketEvents* be = &g_ae_buckets[dev];
+  std::call_once(g_ae_buckets_once[dev], [be] {
+    be->ok = true;
+    for (int i = 0; i < kAeBuckets; ++i) be->ok = be->ok && hipEventCreateWithFlags(&be->ev[i], hipEventDisableTiming) == hipSuccess;
+  });
+  return be->ok ? be : nullptr;
 }
 
 // P1 -> P2 of conv1 .. deconv5, one launch (k_fm_pack)
@@ -389,14 +431,14 @@ static int ae_adam_pack(hipStream_t st, float* params, const float* grad, float*
 
 // forward pass, training mode, through the loss: g6 = d loss / d (pre-tanh output), loss partial sums
 static int ae_forward_loss(hipStream_t st, const float* params, float* running, const float* images, int64_t n, float* recon,
-                           const AeWs& aw) {
+                           const AeWs& aw, const FmStatSync* sync) {
   fm_attrs();
   const FmWs& ws = aw.fm;
   const float* P = params;
   auto W1 = [&](int l) { return P + ae_param_offset(l, false); };
   auto B = [&](int l) { return P + ae_param_offset(l, true); };
   auto W2 = [&](int l) { return (const float*)(ws.p2 + ae_p2_offset(l)); };
-  auto BN = [&](int b) { return ae_bn_at(b, params, running, nullptr); };
+  auto BN = [&](int b) { return ae_bn_at(b, params, running, nullptr, sync); };
   float* const* t = aw.t;
   int rc;
 #define AE_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
@@ -447,24 +489,36 @@ static int ae_forward_loss(hipStream_t st, const float* params, float* running, 
   return check_launch("k_ae_out_fwd_loss");
 }
 
-// backward pass: from g6 to every gradient in `grad` (the bias gradient of deconv6 comes from the loss' partial sums)
-static int ae_backward(hipStream_t st, const float* params, int64_t n, float* grad, const AeWs& aw) {
+// backward pass: from g6 to every gradient in `grad` (the bias gradient of deconv6 comes from the loss' partial sums).
+// buckets: record the gradient buckets' events (ndp_ae_train_grads_dp); null: one slab-sum launch at the end
+static int ae_backward(hipStream_t st, const float* params, int64_t n, float* grad, const AeWs& aw, const FmStatSync* sync,
+                       AeBucketEvents* buckets) {
   const FmWs& ws = aw.fm;
   const float* P = params;
   auto W1 = [&](int l) { return P + ae_param_offset(l, false); };
   auto W2 = [&](int l) { return (const float*)(ws.p2 + ae_p2_offset(l)); };
   auto GW = [&](int l) { return grad + ae_param_offset(l, false); };
-  auto BN = [&](int b) { return ae_bn_at(b, params, nullptr, grad); };
+  auto BN = [&](int b) { return ae_bn_at(b, params, nullptr, grad, sync); };
   float* const* t = aw.t;
   int rc;
   FmSlabPlan plan;
   memset(&plan, 0, sizeof(plan));
   plan.a.remap_seg = -1;
+  // bucket b is complete behind everything launched so far but the row-chunk slabs of its layers: sum them now, then
+  // record its event
+  auto close_bucket = [&](int b) -> int {
+    if (buckets == nullptr) return NDP_OK;
+    const int r = fm_slab_sums(st, plan);
+    plan.a.nseg = 0; plan.a.remap_seg = -1; plan.a.block_begin[0] = 0; plan.blocks = 0;   // (slab memory is not reused: plan.used keeps growing)
+    if (r != NDP_OK) return r;
+    if (hipEventRecord(buckets->ev[b], st) != hipSuccess) return fail(NDP_E_LAUNCH, "autoencoder: hipEventRecord failed");
+    return NDP_OK;
+  };
   auto bias_finish = [&](int i) -> int {                               // conv6 / conv5 / conv4 (statistics slot 20 + i)
     const int layer[3] = {5, 4, 3};
     FmBiasFinishArgs bf;
     memset(&bf, 0, sizeof(bf));
-    bf.fin = fm_fin(20 + i, 1, 1, ws, false);
+    bf.fin = fm_fin(20 + i, 1, 1, ws);
     bf.fin.out1 = grad + ae_param_offset(layer[i], true);
     bf.cols = fm_stat_cols(20 + i);
     KTimer kt("k_fm_bias_finish", st);
@@ -514,10 +568,12 @@ static int ae_backward(hipStream_t st, const float* params, int64_t n, float* gr
   AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv4]", 0, {t[AET_RAWU4], 128}, 32, 2, W1(9), nullptr, {t[AET_DU3], 256}, 16, 16, n, 128, 256, 4, 1, 0, 0, ws, 0, &rq));
   AE_TRY(fm_bn_bwd_at(st, 5, {t[AET_RAWU3], 256}, {t[AET_U3], 256}, {t[AET_DU3], 256}, n * 256, BN(5), ws));
   AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv3]", {t[AET_U2], 512}, 8, 512, {t[AET_RAWU3], 256}, 16, 2, 4, 1, 256, n, GW(8), ws, plan));
+  AE_TRY(close_bucket(0));
   rq = fm_ep_bn_bwd(4, {t[AET_RAWU2], 512}, {t[AET_U2], 512}, ws);
   AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv3]", 0, {t[AET_RAWU3], 256}, 16, 2, W1(8), nullptr, {t[AET_DU2], 512}, 8, 8, n, 256, 512, 4, 1, 0, 0, ws, 0, &rq));
   AE_TRY(fm_bn_bwd_at(st, 4, {t[AET_RAWU2], 512}, {t[AET_U2], 512}, {t[AET_DU2], 512}, n * 64, BN(4), ws));
   AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv2]", {t[AET_U1], 1024}, 4, 1024, {t[AET_RAWU2], 512}, 8, 2, 4, 1, 512, n, GW(7), ws, plan));
+  AE_TRY(close_bucket(1));
   rq = fm_ep_bn_bwd(3, {t[AET_RAWU1], 1024}, {t[AET_U1], 1024}, ws);
   AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv2]", 0, {t[AET_RAWU2], 512}, 8, 2, W1(7), nullptr, {t[AET_DU1], 1024}, 4, 4, n, 512, 1024, 4, 1, 0, 0, ws, 0, &rq));
   // deconv1: a 4x4 "image" of d(raw) per code
@@ -528,11 +584,13 @@ static int ae_backward(hipStream_t st, const float* params, int64_t n, float* gr
   AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv1]", 0, {t[AET_RAWU1], 1024}, 4, 1, W1(6), nullptr, {t[AET_DZ], 128}, 1, 1, n, 1024, 128, 4, 0, 0, 0, ws, 0, &rq));
   AE_TRY(bias_finish(0));
   AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv6]", {t[AET_DZ], 128}, 1, 128, {t[AET_A5], 1024}, 4, 1, 4, 0, 1024, n, GW(5), ws, plan));
+  AE_TRY(close_bucket(2));
   // conv5, conv4 (ReLU, no BatchNorm): the ReLU's backward is applied as the finished gradient is written
   rq = fm_ep_bias(3, 21, {t[AET_A5], 1024});
   AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv6]", 3, {t[AET_DZ], 128}, 1, 1, W2(5), nullptr, {t[AET_DA5], 1024}, 4, 1, n, 128, 1024, 1, 0, 0, 0, ws, 0, &rq));
   AE_TRY(bias_finish(1));
   AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv5]", {t[AET_DA5], 1024}, 4, 1024, {t[AET_A4], 512}, 8, 2, 3, 1, 512, n, GW(4), ws, plan));
+  AE_TRY(close_bucket(3));
   rq = fm_ep_bias(3, 22, {t[AET_A4], 512});
   AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv5]", 2, {t[AET_DA5], 1024}, 4, 1, W2(4), nullptr, {t[AET_DA4], 512}, 8, 4, n, 1024, 512, 2, 0, 0, 0, ws, 0, &rq));
   AE_TRY(bias_finish(2));
@@ -550,8 +608,31 @@ static int ae_backward(hipStream_t st, const float* params, int64_t n, float* gr
   AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv2]", 2, {t[AET_RAW2], 128}, 32, 1, W2(1), nullptr, {t[AET_DA1], 64}, 64, 32, n, 128, 64, 2, 0, 0, 0, ws, 0, &rq));
   AE_TRY(fm_bn_bwd_at(st, 0, {t[AET_RAW1], 64}, {t[AET_A1], 64}, {t[AET_DA1], 64}, n * 4096, BN(0), ws));
   AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv1]", {t[AET_RAW1], 64}, 64, 64, {t[AET_COLS], 32}, 64, 1, 1, 0, 32, n, GW(0), ws, plan, true));   // (columns)
-  return fm_slab_sums(st, plan);
+  if (buckets == nullptr) return fm_slab_sums(st, plan);
+  AE_TRY(close_bucket(4));
+  return close_bucket(5);                                              // (nothing left to sum: the BatchNorm parameters)
 #undef AE_TRY
+}
+
+// one training iteration's gradients: ndp_ae_train_grads (sync, buckets null) and ndp_ae_train_grads_dp
+static int ae_train_grads(const char* name, const float* params, float* running_stats, const float* images, int64_t n_images,
+                          float* grad, float* loss, float* loss_sum, float* recon_out, float* workspace, void* stream,
+                          const FmStatSync* sync, AeBucketEvents* buckets) {
+  NDP_CHECK_ARG(params && images && grad && loss && workspace && n_images >= 1, "%s: bad arguments", name);
+  NDP_CHECK_ARG(n_images <= kAeMaxImages, "%s: more than %d images per call", name, (int)kAeMaxImages);
+  NDP_CHECK_ARG(aligned16(params) && aligned16(images) && aligned16(grad) && aligned16(workspace) &&
+                (!running_stats || aligned16(running_stats)) && (!recon_out || aligned16(recon_out)),
+                "%s: buffers must be 16-byte aligned", name);
+  hipStream_t st = (hipStream_t)stream;
+  const AeWs ws = ae_ws(workspace, n_images);
+  int rc = ae_forward_loss(st, params, running_stats, images, n_images, recon_out, ws, sync);
+  if (rc) return rc;
+  const int nblocks = (int)(n_images * 64);
+  hipLaunchKernelGGL(k_fm_loss_final, dim3(1), dim3(kThreads), 0, st, (const float*)ws.fm.loss_partial, nblocks,
+                     1.0 / (3.0 * (double)(n_images * 16384)), loss, loss_sum, grad + ae_param_offset(11, true));
+  rc = check_launch("k_fm_loss_final");
+  if (rc) return rc;
+  return ae_backward(st, params, n_images, grad, ws, sync, buckets);
 }
 
 }  // namespace ndp
@@ -594,22 +675,45 @@ int ndp_ae_pack_params(const float* params, float* workspace, void* stream) {
 
 int ndp_ae_train_grads(const float* params, float* running_stats, const float* images, int64_t n_images, float* grad,
                        float* loss, float* loss_sum, float* recon_out, float* workspace, void* stream) {
+  return ndp::ae_train_grads("ndp_ae_train_grads", params, running_stats, images, n_images, grad, loss, loss_sum, recon_out,
+                             workspace, stream, nullptr, nullptr);
+}
+
+int ndp_ae_train_grads_dp(const float* params, float* running_stats, const float* images, int64_t n_images, float* grad,
+                          float* loss, float* loss_sum, float* recon_out, float* workspace, void* stream,
+                          ndp_fm_stat_sync_fn stat_sync, void* stat_ctx, int world) {
   using namespace ndp;
-  NDP_CHECK_ARG(params && images && grad && loss && workspace && n_images >= 1, "ndp_ae_train_grads: bad arguments");
-  NDP_CHECK_ARG(n_images <= kAeMaxImages, "ndp_ae_train_grads: more than %d images per call", (int)kAeMaxImages);
-  NDP_CHECK_ARG(aligned16(params) && aligned16(images) && aligned16(grad) && aligned16(workspace) &&
-                (!running_stats || aligned16(running_stats)) && (!recon_out || aligned16(recon_out)),
-                "ndp_ae_train_grads: buffers must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  const AeWs ws = ae_ws(workspace, n_images);
-  int rc = ae_forward_loss(st, params, running_stats, images, n_images, recon_out, ws);
-  if (rc) return rc;
-  const int nblocks = (int)(n_images * 64);
-  hipLaunchKernelGGL(k_fm_loss_final, dim3(1), dim3(kThreads), 0, st, (const float*)ws.fm.loss_partial, nblocks,
-                     1.0 / (3.0 * (double)(n_images * 16384)), loss, loss_sum, grad + ae_param_offset(11, true));
-  rc = check_launch("k_fm_loss_final");
-  if (rc) return rc;
-  return ae_backward(st, params, n_images, grad, ws);
+  NDP_CHECK_ARG(world >= 1 && world <= 4096, "ndp_ae_train_grads_dp: bad world size");
+  NDP_CHECK_ARG(params && images && grad && loss && workspace && n_images >= 1 && n_images <= kAeMaxImages,
+                "ndp_ae_train_grads_dp: bad arguments");
+  AeBucketEvents* buckets = ae_bucket_events();
+  if (buckets == nullptr) return fail(NDP_E_LAUNCH, "ndp_ae_train_grads_dp: could not create the bucket events");
+  const FmStatSync sync = {stat_sync, stat_ctx, world};
+  const int rc = ae_train_grads("ndp_ae_train_grads_dp", params, running_stats, images, n_images, grad, loss, loss_sum,
+                                recon_out, workspace, stream, fm_sync_on(&sync) ? &sync : nullptr, buckets);
+  if (rc == NDP_OK) buckets->recorded.store(true);
+  return rc;
+}
+
+int ndp_ae_grad_buckets(int64_t* offsets, int64_t* counts, int capacity, int* n_buckets) {
+  using namespace ndp;
+  NDP_CHECK_ARG(offsets && counts && n_buckets, "ndp_ae_grad_buckets: null pointer");
+  NDP_CHECK_ARG(capacity >= kAeBuckets, "ndp_ae_grad_buckets: need room for %d buckets", kAeBuckets);
+  for (int b = 0; b < kAeBuckets; ++b) ae_bucket_range(b, offsets + b, counts + b);
+  *n_buckets = kAeBuckets;
+  return NDP_OK;
+}
+
+int ndp_ae_bucket_wait(int bucket, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(bucket >= 0 && bucket < kAeBuckets, "ndp_ae_bucket_wait: bucket out of range");
+  int dev = -1;
+  NDP_CHECK_ARG(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices, "ndp_ae_bucket_wait: no current device");
+  AeBucketEvents& be = g_ae_buckets[dev];
+  NDP_CHECK_ARG(be.recorded.load(), "ndp_ae_bucket_wait: no ndp_ae_train_grads_dp call has recorded the events on this device");
+  if (hipStreamWaitEvent((hipStream_t)stream, be.ev[bucket], 0) != hipSuccess)
+    return fail(NDP_E_LAUNCH, "ndp_ae_bucket_wait: hipStreamWaitEvent failed");
+  return NDP_OK;
 }
 
 int ndp_ae_apply_adam(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int32_t* step_count, float lr,

@@ -2057,27 +2057,29 @@ static void fm_ep_fill(FmStatEp& ep, const FmEpReq& rq, const FmWs& ws) {
 // exactly as one process with B images does (SyncBatchNorm's semantics; the reference trains on one device).  The
 // backward sums are copied first: d beta / d gamma are written from this rank's own sums (the gradient all-reduce adds
 // the ranks' up), dx is computed with the global ones.
+// The descriptor travels with the call (FmBnAt::sync): the ndp_fm_* entry points pass the process-wide g_fm_sync, the
+// autoencoder's data-parallel entry point its own per-call one (ndp_autoencoder.inc); null: this rank's sums only.
 struct FmStatSync { ndp_fm_stat_sync_fn fn; void* ctx; int world; };
 static FmStatSync g_fm_sync = {nullptr, nullptr, 1};
-static int fm_stat_sync(hipStream_t st, const FmWs& ws, int slot) {
-  if (g_fm_sync.fn == nullptr || g_fm_sync.world <= 1) return NDP_OK;
+static bool fm_sync_on(const FmStatSync* s) { return s != nullptr && s->fn != nullptr && s->world > 1; }
+static int fm_stat_sync(hipStream_t st, const FmWs& ws, int slot, const FmStatSync* sync) {
+  if (!fm_sync_on(sync)) return NDP_OK;
   long long* acc = ws.stat_acc + fm_stat_offset_words(slot);
   const int64_t words = fm_stat_words(slot);
   if (slot >= 10 && hipMemcpyAsync(ws.stat_acc_local + fm_stat_offset_words(slot), acc, sizeof(long long) * (size_t)words,
                                    hipMemcpyDeviceToDevice, st) != hipSuccess)
     return fail(NDP_E_LAUNCH, "forward model: hipMemcpyAsync of the statistics failed");
-  g_fm_sync.fn(acc, words, (void*)st, g_fm_sync.ctx);
+  sync->fn(acc, words, (void*)st, sync->ctx);
   return NDP_OK;
 }
 // ... and what the consumer makes of the accumulator of `slot` (FmStatFin); P = this rank's pixels summed over
-// (cross_rank false: this rank's sums only, whatever ndp_fm_set_stat_sync installed -- ndp_autoencoder.inc)
-static FmStatFin fm_fin(int slot, int what, int64_t P, const FmWs& ws, bool cross_rank = true) {
+static FmStatFin fm_fin(int slot, int what, int64_t P, const FmWs& ws, const FmStatSync* sync = nullptr) {
   FmStatFin f;
   memset(&f, 0, sizeof(f));
   f.acc = ws.stat_acc + fm_stat_offset_words(slot); f.replicas = fm_stat_replicas(fm_stat_cols(slot));
   f.what = what; f.P = (int)P; f.eps = kFmBnEps; f.momentum = kFmBnMomentum;
-  if (cross_rank && g_fm_sync.fn != nullptr && g_fm_sync.world > 1 && slot < 20) {
-    f.P = (int)(P * g_fm_sync.world);
+  if (fm_sync_on(sync) && slot < 20) {
+    f.P = (int)(P * sync->world);
     if (slot >= 10) f.acc_local = ws.stat_acc_local + fm_stat_offset_words(slot);
   }
   return f;
@@ -2247,12 +2249,12 @@ static FmEpReq fm_ep_bias(int mode, int slot, FmView y) {
 }
 
 // Where BatchNorm b's tensors live: the forward model's flat vectors (fm_bn_at), or those of another network whose
-// BatchNorms are the first ones of kFmBnC (ndp_autoencoder.inc).  cross_rank: the statistics go through the
-// ndp_fm_set_stat_sync hook.
+// BatchNorms are the first ones of kFmBnC (ndp_autoencoder.inc).  sync: where the statistics are summed over the ranks
+// (fm_stat_sync; null: this rank's own).
 struct FmBnAt {
   const float* gamma; const float* beta; float* running_mean; float* running_var;
   float* d_gamma; float* d_beta; float* d_conv_bias;     // backward outputs (d_conv_bias: the bias of the layer in front)
-  bool cross_rank;
+  const FmStatSync* sync;
 };
 static FmBnAt fm_bn_at(int b, const float* params, float* running, float* grad) {
   FmBnAt at;
@@ -2262,7 +2264,7 @@ static FmBnAt fm_bn_at(int b, const float* params, float* running, float* grad) 
   at.d_gamma = grad ? grad + fm_bn_offset(b, false) : nullptr;
   at.d_beta = grad ? grad + fm_bn_offset(b, true) : nullptr;
   at.d_conv_bias = grad ? grad + fm_param_offset(kFmBnLayer[b], true) : nullptr;
-  at.cross_rank = true;
+  at.sync = &g_fm_sync;                                   // (ndp_fm_set_stat_sync)
   return at;
 }
 
@@ -2278,11 +2280,9 @@ static int fm_bn_fwd_at(hipStream_t st, int b, FmView raw, int64_t P, FmView des
   FmEltArgs e;
   memset(&e, 0, sizeof(e));
   if (training) {
-    if (at.cross_rank) {
-      rc = fm_stat_sync(st, ws, b);
-      if (rc) return rc;
-    }
-    e.fin = fm_fin(b, 0, P, ws, at.cross_rank);
+    rc = fm_stat_sync(st, ws, b, at.sync);
+    if (rc) return rc;
+    e.fin = fm_fin(b, 0, P, ws, at.sync);
     e.fin.out1 = mean; e.fin.out2 = invstd; e.fin.meanres = ws.bn_meanres + fm_bn_stat_index(b);
     e.fin.running_mean = at.running_mean;
     e.fin.running_var = at.running_var;
@@ -2315,11 +2315,9 @@ static int fm_bn_bwd_at(hipStream_t st, int b, FmView raw, FmView y, FmView dy, 
   e.mean = ws.bn_mean + fm_bn_stat_index(b); e.invstd = ws.bn_invstd + fm_bn_stat_index(b);
   e.gamma = at.gamma;
   e.C = C; e.P = (int)P;
-  if (at.cross_rank) {
-    int rc = fm_stat_sync(st, ws, 10 + b);
-    if (rc) return rc;
-  }
-  e.fin = fm_fin(10 + b, 2, P, ws, at.cross_rank);
+  const int rc = fm_stat_sync(st, ws, 10 + b, at.sync);
+  if (rc) return rc;
+  e.fin = fm_fin(10 + b, 2, P, ws, at.sync);
   e.fin.out1 = at.d_beta; e.fin.out2 = at.d_gamma;
   e.fin.out3 = at.d_conv_bias;
   e.fin.meanres = ws.bn_meanres + fm_bn_stat_index(b); e.fin.gamma = e.gamma; e.fin.invstd = e.invstd;

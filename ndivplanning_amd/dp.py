@@ -112,34 +112,69 @@ class BucketedMeanAllReduce:
     the replicas still agree with each other bit for bit.
 
     With a backend that stages CUDA tensors through the host (gloo, the one-GPU rehearsals) each collective blocks the
-    host until its bucket is complete: correct, but not overlapped."""
+    host until its bucket is complete: correct, but not overlapped.
 
-    def __init__(self, world, group=None):
+    `bucket_ranges` / `wait`: another network's buckets -- a function returning the [(offset, count)] list and the name
+    of the library's wait entry point (the autoencoder: _capi.ae_grad_buckets, "ndp_ae_bucket_wait"); by default the
+    forward model's."""
+
+    def __init__(self, world, group=None, bucket_ranges=None, wait="ndp_fm_bucket_wait"):
         self.world, self.group = int(world), group
         self.stream = None
         self.buckets = None
+        self.bucket_ranges, self.wait = bucket_ranges, wait
 
     def __call__(self, flat_grad, device):
         from . import _capi
         lib = _capi.load()
         if self.buckets is None:
-            self.buckets = _capi.fm_grad_buckets()
+            self.buckets = (self.bucket_ranges or _capi.fm_grad_buckets)()
             if sum(c for _, c in self.buckets) != flat_grad.numel():
                 raise _capi.NdpError("gradient buckets do not cover the flat gradient")
         if self.stream is None:
             self.stream = torch.cuda.Stream(device)
         main = torch.cuda.current_stream(device)
         scale = 1.0 / self.world
+        wait = getattr(lib, self.wait)
         with torch.cuda.device(device), torch.cuda.stream(self.stream):
             for b, (off, cnt) in enumerate(self.buckets):
-                _capi.check(lib.ndp_fm_bucket_wait(b, _capi.stream_ptr(device)), "ndp_fm_bucket_wait")
+                _capi.check(wait(b, _capi.stream_ptr(device)), self.wait)
                 piece = flat_grad[off:off + cnt]
                 dist.all_reduce(piece, op=dist.ReduceOp.SUM, group=self.group)
                 piece.mul_(scale)
         main.wait_stream(self.stream)
 
 
-class CrossRankBatchNorm:
+class StatAllReduce:
+    """The body of a cross-rank statistics callback (include/ndp.h, ndp_fm_stat_sync_fn): called as
+    fn(acc, words, stream, ctx) through a ctypes thunk (_capi.STAT_SYNC_FN(instance)), it all-reduces (SUM, int64: exact,
+    order-free) the `words` accumulator values at `acc` -- inside `workspace`, the trainer's workspace tensor -- in place.
+    Counts its calls; an exception inside a callback is kept and re-raised by `check()`."""
+
+    def __init__(self, workspace, group=None):
+        self.workspace, self.group = workspace, group
+        self.error = None
+        self.calls = 0
+
+    def __call__(self, acc, words, stream, ctx):
+        try:
+            off = (int(acc) - self.workspace.data_ptr()) // 4
+            if off < 0 or off + 2 * int(words) > self.workspace.numel() or (int(acc) - self.workspace.data_ptr()) % 8:
+                raise RuntimeError("statistics accumulator outside the workspace")
+            view = self.workspace[off:off + 2 * int(words)].view(torch.int64)
+            dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group)
+            self.calls += 1
+        except Exception as exc:                               # noqa: BLE001 - must not propagate through the C frame
+            if self.error is None:
+                self.error = exc
+
+    def check(self):
+        if self.error is not None:
+            err, self.error = self.error, None
+            raise RuntimeError("cross-rank BatchNorm statistics: %r" % (err,))
+
+
+class CrossRankBatchNorm(StatAllReduce):
     """Forward-model BatchNorm statistics over ALL ranks' images (include/ndp.h, ndp_fm_set_stat_sync): the library calls
     back between the launch that fills a BatchNorm's fixed-point accumulator and the launch that reads it, and this
     all-reduces (SUM, int64: exact, order-free) the accumulator in place on the launch stream.  W ranks with B / W images
@@ -151,31 +186,13 @@ class CrossRankBatchNorm:
 
     def __init__(self, workspace, world, group=None):
         from . import _capi
+        super().__init__(workspace, group)
         self._capi, self.lib = _capi, _capi.load()
-        self.workspace, self.world, self.group = workspace, int(world), group
-        self.error = None
-        self.calls = 0
-
-        def sync(acc, words, stream, ctx):
-            try:
-                off = (int(acc) - self.workspace.data_ptr()) // 4
-                if off < 0 or off + 2 * int(words) > self.workspace.numel() or (int(acc) - self.workspace.data_ptr()) % 8:
-                    raise RuntimeError("statistics accumulator outside the workspace")
-                view = self.workspace[off:off + 2 * int(words)].view(torch.int64)
-                dist.all_reduce(view, op=dist.ReduceOp.SUM, group=self.group)
-                self.calls += 1
-            except Exception as exc:                           # noqa: BLE001 - must not propagate through the C frame
-                if self.error is None:
-                    self.error = exc
-        self._cb = _capi.STAT_SYNC_FN(sync)                    # keep the thunk alive as long as it is installed
+        self.world = int(world)
+        self._cb = _capi.STAT_SYNC_FN(self)                    # keep the thunk alive as long as it is installed
         import ctypes
         _capi.check(self.lib.ndp_fm_set_stat_sync(ctypes.cast(self._cb, ctypes.c_void_p), None, self.world),
                     "ndp_fm_set_stat_sync")
-
-    def check(self):
-        if self.error is not None:
-            err, self.error = self.error, None
-            raise RuntimeError("cross-rank BatchNorm statistics: %r" % (err,))
 
     def close(self):
         if self._cb is not None:

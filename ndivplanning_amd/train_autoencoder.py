@@ -9,14 +9,24 @@ What differs from the reference, on purpose:
     utils/trajectory_loader.py);
   * visdom is optional: with it importable (and `visdom=True`) the loss is plotted every `report_freq` steps.
 The whole modules are saved as models/encoder_{epoch}.pt / models/decoder_{epoch}.pt when epoch % 10 == 1
-(train_autoencoder.py:92-97), after the trainer's flat vectors are written back into them."""
+(train_autoencoder.py:92-97), after the trainer's flat vectors are written back into them.
+
+More than one process (torch.distributed.run) trains data-parallel: `batch_size` is the GLOBAL trajectory count, every
+rank takes batch_size / world_size trajectories of each (identically shuffled) batch, one GPU per local rank
+(NDP_BENCH_ONE_GPU=1: all on cuda:0).  BatchNorm normalises over all ranks' images (`sync_batchnorm`, default on) and the
+gradient is averaged bucket by bucket beside the backward pass (`grad_exchange="bucketed"`; "single": one collective
+between backward and Adam), so W ranks train what one process trains on the whole batch.  A final batch that does not
+split evenly is skipped; the per-step loss is the mean of the ranks' losses; rank 0 prints, plots and saves."""
 import os
+import warnings
 from argparse import ArgumentParser
 
 import numpy as np
 import torch
+import torch.distributed as dist
 from torch.utils import data
 
+from . import _capi, dp
 from .autoencoder_trainer import AutoencoderTrainer
 from .models.image_autoencoder import Decoder, Encoder
 from .utils.trajectory_loader import PushDataset, SyntheticPushDataset
@@ -56,8 +66,21 @@ def build_models(device):
 
 
 def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS, lr=LR_RATE, betas=(0.5, 0.999),
-          device="cuda", save_dir="models", report_freq=REPORT_FREQ, visdom=False, log=print):
-    """The reference's loop; returns (encoder, decoder, per-step losses)."""
+          device="cuda", save_dir="models", report_freq=REPORT_FREQ, visdom=False, log=print, sync_batchnorm=True,
+          grad_exchange="bucketed"):
+    """The reference's loop; returns (encoder, decoder, per-step losses).  Under torch.distributed.run: data parallel
+    (module docstring); `device` is then the local rank's GPU, every rank returns the same losses."""
+    if grad_exchange not in ("bucketed", "single"):
+        raise ValueError("grad_exchange must be 'bucketed' or 'single', got %r" % (grad_exchange,))
+    rank, world, local_rank = dp.env_world()
+    if batch_size % world != 0:                                        # (before any process group or GPU is touched)
+        raise ValueError("batch_size=%d trajectories must be a multiple of the %d ranks" % (batch_size, world))
+    own_group = False
+    if world > 1:
+        device = torch.device("cuda", 0 if os.environ.get("NDP_BENCH_ONE_GPU") == "1" else local_rank)
+        torch.cuda.set_device(device)
+        own_group = not dist.is_initialized()
+        dp.init_process_group(device)
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -67,48 +90,101 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
     dataset = make_dataset(data_path)
     loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True)
     encoder, decoder = build_models(device)
-    trainer = AutoencoderTrainer(encoder.train(), decoder.train(), batch=batch_size * 15, lr=lr, betas=betas)   # (15 frames)
-    display = None
-    if visdom:
-        try:
-            from .vis_tools import visualizer
-            display = visualizer(port=8082)
-        except Exception as e:  # pragma: no cover - visdom is optional
-            log("visdom unavailable (%s): no plots" % e)
-    losses = []
-    step = 0
-    for epoch in range(num_epochs):
-        for i, inputs in enumerate(loader):
-            images, _, _, _ = inputs
-            images = images.to(device)
-            state_cur = images.view(-1, *(images.size()[2:])).contiguous()
-            recon_loss = trainer.step(state_cur)
-            step += 1
-            recon_loss_np = recon_loss.cpu().data.numpy()
-            losses.append(float(recon_loss_np[0]))
-            log(epoch, step, "recon_loss_np: ", recon_loss_np)
-            if display is not None and step % report_freq == 0:
-                display.plot("recon_loss", "train", "autoencoder", step, float(recon_loss_np[0]))
-        if epoch % 10 == 1:
-            os.makedirs(save_dir, exist_ok=True)
-            trainer.sync_to_modules()
-            torch.save(encoder, os.path.join(save_dir, "encoder_" + str(epoch) + ".pt"))
-            torch.save(decoder, os.path.join(save_dir, "decoder_" + str(epoch) + ".pt"))
-    trainer.sync_to_modules()
+    trainer, bucket_group = None, None
+    try:
+        dp_kw = {}
+        if world > 1:
+            for t in [*encoder.parameters(), *encoder.buffers(), *decoder.parameters(), *decoder.buffers()]:
+                dist.broadcast(t.data, src=0)                          # one set of initial weights: rank 0's
+            if grad_exchange == "single":
+                dp_kw["reduce_fn"] = dp.mean_all_reduce(world)
+            else:
+                # with cross-rank statistics the buckets get a communicator of their own: on the statistics' one they
+                # would queue behind the 8 backward statistics syncs, i.e. behind nearly the whole backward pass
+                bucket_group = dist.new_group(list(range(world))) if sync_batchnorm else None
+                dp_kw["bucket_reduce"] = dp.BucketedMeanAllReduce(world, group=bucket_group,
+                                                                  bucket_ranges=_capi.ae_grad_buckets,
+                                                                  wait="ndp_ae_bucket_wait")
+            dp_kw["sync_batchnorm_world"] = world if sync_batchnorm else 1
+        trainer = AutoencoderTrainer(encoder.train(), decoder.train(), batch=batch_size // world * 15, lr=lr, betas=betas,
+                                     **dp_kw)                          # (15 frames)
+        display = None
+        if visdom and rank == 0:
+            try:
+                from .vis_tools import visualizer
+                display = visualizer(port=8082)
+            except Exception as e:  # pragma: no cover - visdom is optional
+                log("visdom unavailable (%s): no plots" % e)
+        losses = []
+        step = 0
+        warned = False
+        for epoch in range(num_epochs):
+            for i, inputs in enumerate(loader):
+                images, _, _, _ = inputs
+                if world > 1:
+                    if images.shape[0] != batch_size:                  # ragged final batch: skipped on every rank
+                        if rank == 0 and not warned:
+                            warnings.warn("train_autoencoder: a final batch of %d trajectories does not split over %d "
+                                          "ranks; skipped" % (images.shape[0], world))
+                        warned = True
+                        continue
+                    lo, hi = dp.shard_bounds(batch_size, rank, world)
+                    images = images[lo:hi]
+                images = images.to(device)
+                state_cur = images.view(-1, *(images.size()[2:])).contiguous()
+                recon_loss = trainer.step(state_cur)
+                step += 1
+                if world > 1:                                          # the global batch's loss: the mean of the ranks'
+                    mean = dp.reduce_loss_shares([recon_loss.item() / world], device=device)[0]
+                    recon_loss = torch.tensor([mean], dtype=torch.float32)
+                    if step == 1:
+                        dp.assert_replicas_identical([trainer.params], grad_exchange, "after the first step")
+                recon_loss_np = recon_loss.cpu().data.numpy()
+                losses.append(float(recon_loss_np[0]))
+                if rank == 0:
+                    log(epoch, step, "recon_loss_np: ", recon_loss_np)
+                if display is not None and step % report_freq == 0:
+                    display.plot("recon_loss", "train", "autoencoder", step, float(recon_loss_np[0]))
+            if world > 1:
+                dp.assert_replicas_identical([trainer.params], grad_exchange, "end of epoch %d" % epoch)
+            if epoch % 10 == 1 and rank == 0:
+                os.makedirs(save_dir, exist_ok=True)
+                trainer.sync_to_modules()
+                torch.save(encoder, os.path.join(save_dir, "encoder_" + str(epoch) + ".pt"))
+                torch.save(decoder, os.path.join(save_dir, "decoder_" + str(epoch) + ".pt"))
+        trainer.sync_to_modules()
+    finally:
+        if trainer is not None:
+            trainer.close()
+        if bucket_group is not None:
+            dist.destroy_process_group(bucket_group)
+        if own_group and dist.is_initialized():
+            dist.destroy_process_group()
+    train.last_trainer = trainer                                       # tests: the replica's flat vectors
     return encoder, decoder, losses
 
 
-def main(argv=None):
+def make_parser():
     parser = ArgumentParser(description="Train the image autoencoder (train_autoencoder.py)")
     parser.add_argument("--data", default="128_128_data", help="trajectory directory, or synthetic:<N>:images")
-    parser.add_argument("--batch-size", type=int, default=BATCH_SIZE, help="trajectories per step")
+    parser.add_argument("--batch-size", type=int, default=BATCH_SIZE,
+                        help="trajectories per step (under torch.distributed.run: over all ranks)")
     parser.add_argument("--epochs", type=int, default=NUM_EPOCHS)
     parser.add_argument("--lr", type=float, default=LR_RATE)
     parser.add_argument("--save-dir", default="models")
     parser.add_argument("--visdom", action="store_true", help="plot the loss through visdom")
-    args = parser.parse_args(argv)
+    parser.add_argument("--no-sync-batchnorm", dest="sync_batchnorm", action="store_false",
+                        help="data parallel: BatchNorm statistics per rank instead of over all ranks' images")
+    parser.add_argument("--grad-exchange", choices=("bucketed", "single"), default="bucketed",
+                        help="data parallel: average the gradient per bucket beside the backward pass, or in one "
+                             "collective after it")
+    return parser
+
+
+def main(argv=None):
+    args = make_parser().parse_args(argv)
     return train(args.data, batch_size=args.batch_size, num_epochs=args.epochs, lr=args.lr, save_dir=args.save_dir,
-                 visdom=args.visdom)
+                 visdom=args.visdom, sync_batchnorm=args.sync_batchnorm, grad_exchange=args.grad_exchange)
 
 
 if __name__ == "__main__":

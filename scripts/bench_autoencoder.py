@@ -1,7 +1,12 @@
 """Time one autoencoder training step (train_autoencoder.py:79-90) on the GPU box: the HIP trainer (ndp_ae_train_grads +
 ndp_ae_apply_adam) vs the reference loop unchanged on PyTorch-ROCm / MIOpen (module forward, mse, backward,
 torch.optim.Adam).  Median ms/step over STEPS timed steps after WARMUP, fraction of the fp32 MFMA peak, per-kernel split
-of the HIP step.  Usage: python scripts/bench_autoencoder.py [N ...]   (default: 240 16)"""
+of the HIP step.  Usage: python scripts/bench_autoencoder.py [N ...]   (default: 240 16)
+
+python scripts/bench_autoencoder.py --shards [N ...]   (default: 240 120 60 30, the per-rank share of the reference's 240
+images at 1, 2, 4, 8 ranks): per-rank compute time of one step at each shard size, through ndp_ae_train_grads and through
+ndp_ae_train_grads_dp at world 1 (no statistics callback, no collective: the bucket events recorded and the weight-gradient
+slabs summed per bucket) -- what bucketing costs on the compute path.  The two are timed alternately, median of STEPS."""
 import os
 import sys
 import time
@@ -89,5 +94,39 @@ def main(sizes):
             print("   %-26s %8.3f ms (%2d launches) %5.1f %%" % (name, ms, cnt, 100 * ms / total))
 
 
+def shards(sizes):
+    lib = _capi.load()
+    p = _capi.ptr
+    print("per-rank step (forward + backward + Adam), median of %d after %d warm-up; dp = ndp_ae_train_grads_dp at world 1"
+          % (STEPS, WARMUP))
+    for n in sizes:
+        x = torch.rand(n, 3, 128, 128, device=DEV) * 2 - 1
+        tr = AutoencoderTrainer(*models(), batch=n)
+
+        def dp_step():
+            _capi.check(lib.ndp_ae_train_grads_dp(p(tr.params), p(tr.stats), p(x), n, p(tr.grad), p(tr.loss),
+                                                  p(tr.loss_sum), None, p(tr.workspace), _capi.stream_ptr(DEV), None, None,
+                                                  1), "ndp_ae_train_grads_dp")
+            tr.apply()
+        for _ in range(WARMUP):
+            tr.step(x)
+            dp_step()
+        torch.cuda.synchronize()
+        ts = {"plain": [], "dp": []}
+        for _ in range(STEPS):
+            for name, fn in (("plain", lambda: tr.step(x)), ("dp", dp_step)):
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts[name].append(time.perf_counter() - t0)
+        med = {k: 1e3 * sorted(v)[len(v) // 2] for k, v in ts.items()}
+        print("n=%d (%d ranks of 240)  ndp_ae_train_grads %.3f ms   ndp_ae_train_grads_dp %.3f ms   bucketing %+.3f ms "
+              "(%+.1f %%)" % (n, 240 // n if 240 % n == 0 else 0, med["plain"], med["dp"], med["dp"] - med["plain"],
+                              100 * (med["dp"] - med["plain"]) / med["plain"]))
+
+
 if __name__ == "__main__":
-    main([int(a) for a in sys.argv[1:]] or [240, 16])
+    if sys.argv[1:2] == ["--shards"]:
+        shards([int(a) for a in sys.argv[2:]] or [240, 120, 60, 30])
+    else:
+        main([int(a) for a in sys.argv[1:]] or [240, 16])
