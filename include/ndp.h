@@ -492,6 +492,32 @@ int ndp_eval_g_input(const float *state_code, int64_t n_state, int state_rep, co
                      int goal_rep, int64_t rows, float *out, void *stream);
 int ndp_eval_frames_u8(const uint8_t *frames_hwc, int64_t n_images, float *images, void *stream);
 
+/* ------------------------------------------------------------- JPEG decode ---
+ * The frames of the reference's trajectory bundles are JPEG streams (generate_trajectories.py:113-122: PIL, quality 95);
+ * ndp_jpeg_decode_u8 turns a batch of them into the [n][128][128][3] bytes that the *_u8 entry points take, bit-identical
+ * to PIL (libjpeg-turbo: integer islow IDCT, "fancy" h2v2 chroma upsampling, fixed-point YCbCr -> RGB).
+ * Supported: baseline / extended sequential DCT (SOF0 / SOF1), 8-bit, Huffman, one interleaved scan, 3 components
+ * sampled 4:2:0 (Y 2x2, Cb 1x1, Cr 1x1) with Cb and Cr sharing their Huffman tables, 128x128; any DQT / DHT tables;
+ * 0xFF00 stuffing, fill bytes, APPn / COM segments.  Anything else is not decoded and gets a status:
+ *   streams     device bytes; frame i is streams[offsets[i] .. offsets[i+1]) (offsets: n+1 device int64, non-decreasing);
+ *               nothing outside that range is read for frame i
+ *   frames_hwc  [n][128][128][3] bytes; a frame whose status is not NDP_JPEG_OK is all zero
+ *   status      [n] int32, one of NDP_JPEG_*
+ *   workspace   ndp_jpeg_workspace_bytes(n, stream_bytes) bytes, 256-byte aligned, where stream_bytes >=
+ *               offsets[n] - offsets[0]; a frame that does not fit a smaller workspace gets NDP_JPEG_WORKSPACE.
+ * No host synchronisation: the host never reads the streams or the offsets.  1 <= n_images <= 65536;
+ * ndp_jpeg_workspace_bytes returns 0 for a bad request. */
+#define NDP_JPEG_OK          0
+#define NDP_JPEG_UNSUPPORTED 1   /* progressive, arithmetic, 12-bit, restart intervals, not 3 components at 4:2:0, ... */
+#define NDP_JPEG_SIZE        2   /* not 128x128 */
+#define NDP_JPEG_CORRUPT     3   /* corrupt or truncated stream (bad marker, segment past the end, bad Huffman code,
+                                    entropy data shorter than the 384 blocks, no EOI) */
+#define NDP_JPEG_WORKSPACE   4   /* the stream does not fit the workspace's stream area */
+int64_t ndp_jpeg_workspace_bytes(int64_t n_images, int64_t stream_bytes);
+int ndp_jpeg_decode_u8(const uint8_t *streams, const int64_t *offsets /* [n+1], device */, int64_t n_images,
+                       uint8_t *frames_hwc /* [n][128][128][3] */, int32_t *status /* [n], device */, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------ measurement ---
  * Per-kernel timing for bench.py: while enabled (per host thread) every kernel
  * this library launches is bracketed by hipEvents recorded on the stream it is

@@ -140,6 +140,8 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_void_p]),
     "ndp_eval_g_input": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
     "ndp_eval_frames_u8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
+    "ndp_jpeg_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "ndp_jpeg_decode_u8": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ndp_timing_enable": (c_int, [c_int]),
     "ndp_timing_collect": (c_int, [ctypes.c_char_p, c_int, POINTER(c_float), POINTER(c_int32), c_int]),
 }

@@ -25,7 +25,7 @@ def fetch(kind, image_encoder, fwd_model_autoencoder, generator, dataset, config
     t1 = int(dataset.seq_length) - 1
     torch.manual_seed(seed)
     np.random.seed(seed)
-    loader = data.DataLoader(dataset, batch_size=bs, shuffle=False)
+    loader = data.DataLoader(dataset, batch_size=bs, shuffle=False, **E.jpeg.loader_kwargs(dataset))
     shapes = E.noise_piece_shapes(kind, bs, dataset.seq_length, k, nz, r, th)
     action_error_sum = torch.zeros(1, dtype=torch.float32, device=models.device)
     image_error_sum = None
@@ -49,6 +49,7 @@ def fetch(kind, image_encoder, fwd_model_autoencoder, generator, dataset, config
             print(action_error_sum[0])                     # one host sync per batch, as the reference's print
     if image_error_sum is None:
         raise ValueError("the evaluation dataset is empty")
+    models.finish_jpeg()
     avg_action_error = action_error_sum[0] / (t1 * len(loader))
     avg_image_loss = image_error_sum / (t1 * len(loader))
     return avg_action_error.item(), avg_image_loss.item()

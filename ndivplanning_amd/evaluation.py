@@ -19,7 +19,7 @@ What the loops deduplicate against the reference, with the same arithmetic per i
 """
 import torch
 
-from . import _capi
+from . import _capi, jpeg
 from .models.forward_encoder import pack_module
 from .models.image_autoencoder import pack_encoder_params
 
@@ -110,6 +110,18 @@ class EvalModels:
                                                   int(goal_code.shape[0]), int(goal_rep), int(rows), _ptr(out),
                                                   self._stream()), "ndp_eval_g_input")
         return out
+
+    def jpeg_decoder(self):
+        """The device's JPEG decoder (made on first use): failed frames raise at the next batch's decode or at
+        finish_jpeg()."""
+        if getattr(self, "_jpeg", None) is None:
+            self._jpeg = jpeg.JpegDecoder(self.device, check="deferred")
+        return self._jpeg
+
+    def finish_jpeg(self):
+        """Raise for JPEG frames of the last batch that did not decode (nothing to do without a decoder)."""
+        if getattr(self, "_jpeg", None) is not None:
+            self._jpeg.finish()
 
     def images(self, frames):
         """[n,3,128,128] fp32 from float NCHW images or byte frames [n,128,128,3] (normalised as the loader would)."""
@@ -205,8 +217,11 @@ def reference_noise_schedule(kind, random_seed, num_batches, batch, seq_length, 
 
 # ---------------------------------------------------------------------- the three loops
 def _frames(models, frames):
-    """[B,T,...] float NCHW or bytes HWC -> fp32 [B*T,3,128,128] on the device, once per trajectory batch."""
+    """[B,T,...] float NCHW, bytes HWC or JPEG streams (jpeg.JpegFrames) -> fp32 [B*T,3,128,128] on the device, once per
+    trajectory batch."""
     b, t = int(frames.shape[0]), int(frames.shape[1])
+    if isinstance(frames, jpeg.JpegFrames):
+        frames = models.jpeg_decoder().decode_frames(frames)
     return models.images(frames.reshape(b * t, *frames.shape[2:])), b, t
 
 
@@ -445,11 +460,15 @@ def make_eval_dataset(config):
     if path.startswith("synthetic:") or "/synthetic:" in path:
         spec = path[path.index("synthetic:"):].split(":")
         mode = spec[2] if len(spec) > 2 else "images"
-        if mode not in ("images", "frames_u8"):
-            raise ValueError("evaluation needs images: use synthetic:<N>:images or synthetic:<N>:frames_u8")
+        if mode not in ("images", "frames_u8", "jpeg"):
+            raise ValueError("evaluation needs images: use synthetic:<N>:images, synthetic:<N>:frames_u8 or "
+                             "synthetic:<N>:jpeg")
         return SyntheticPushDataset(int(spec[1]), seq_length=int(config.trajectory_length), mode=mode,
                                     seed=int(config.random_seed))
-    # decoded frames stay bytes (normalised by ndp_eval_frames_u8); `raw_uint8: false` gives the reference's floats
+    # decoded frames stay bytes (normalised by ndp_eval_frames_u8); `raw_uint8: false` gives the reference's floats;
+    # `raw_jpeg: true` yields the JPEG streams, decoded on the device
+    if bool(config.get("raw_jpeg", False)):
+        return PushDataset(config.evaluation_data_path, seq_length=int(config.trajectory_length), raw_jpeg=True)
     return PushDataset(config.evaluation_data_path, seq_length=int(config.trajectory_length),
                        raw_uint8=bool(config.get("raw_uint8", True)))
 

@@ -27,6 +27,7 @@ import torch.distributed as dist
 from torch.utils import data
 
 from . import _capi, dp
+from . import jpeg as jpeg_frames
 from .autoencoder_trainer import AutoencoderTrainer
 from .models.image_autoencoder import Decoder, Encoder
 from .utils.trajectory_loader import PushDataset, SyntheticPushDataset
@@ -45,15 +46,16 @@ def norm(image):
     return (image / 255.0 - 0.5) * 2.0
 
 
-def make_dataset(path, seed=1):
+def make_dataset(path, seed=1, raw_jpeg=False):
+    """synthetic:<N>:images|jpeg, or the HDF5 directory (raw_jpeg: its JPEG streams, decoded on the device)."""
     path = str(path)
     if path.startswith("synthetic:"):
         spec = path.split(":")
         mode = spec[2] if len(spec) > 2 else "images"
-        if mode != "images":
-            raise ValueError("the autoencoder trains on images: use synthetic:<N>:images")
-        return SyntheticPushDataset(int(spec[1]), seq_length=15, mode="images", seed=seed)
-    return PushDataset(path)
+        if mode not in ("images", "jpeg"):
+            raise ValueError("the autoencoder trains on images: use synthetic:<N>:images or synthetic:<N>:jpeg")
+        return SyntheticPushDataset(int(spec[1]), seq_length=15, mode=mode, seed=seed)
+    return PushDataset(path, raw_jpeg=raw_jpeg) if raw_jpeg else PushDataset(path)
 
 
 def build_models(device):
@@ -67,7 +69,7 @@ def build_models(device):
 
 def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS, lr=LR_RATE, betas=(0.5, 0.999),
           device="cuda", save_dir="models", report_freq=REPORT_FREQ, visdom=False, log=print, sync_batchnorm=True,
-          grad_exchange="bucketed"):
+          grad_exchange="bucketed", raw_jpeg=False):
     """The reference's loop; returns (encoder, decoder, per-step losses).  Under torch.distributed.run: data parallel
     (module docstring); `device` is then the local rank's GPU, every rank returns the same losses."""
     if grad_exchange not in ("bucketed", "single"):
@@ -87,8 +89,10 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
     # seeds first, then the dataset and the modules, as the reference's module-level code runs
     torch.manual_seed(1)
     np.random.seed(1)
-    dataset = make_dataset(data_path)
-    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True)
+    dataset = make_dataset(data_path, raw_jpeg=raw_jpeg)
+    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True, **jpeg_frames.loader_kwargs(dataset))
+    # JPEG frames are decoded on the device, then normalised by ndp_eval_frames_u8; failures raise one batch later
+    jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
     encoder, decoder = build_models(device)
     trainer, bucket_group = None, None
     try:
@@ -130,6 +134,8 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
                         continue
                     lo, hi = dp.shard_bounds(batch_size, rank, world)
                     images = images[lo:hi]
+                if jpeg_decoder is not None:
+                    images = jpeg_decoder.decode_images(images)
                 images = images.to(device)
                 state_cur = images.view(-1, *(images.size()[2:])).contiguous()
                 recon_loss = trainer.step(state_cur)
@@ -145,6 +151,8 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
                     log(epoch, step, "recon_loss_np: ", recon_loss_np)
                 if display is not None and step % report_freq == 0:
                     display.plot("recon_loss", "train", "autoencoder", step, float(recon_loss_np[0]))
+            if jpeg_decoder is not None:
+                jpeg_decoder.finish()
             if world > 1:
                 dp.assert_replicas_identical([trainer.params], grad_exchange, "end of epoch %d" % epoch)
             if epoch % 10 == 1 and rank == 0:
@@ -166,7 +174,9 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
 
 def make_parser():
     parser = ArgumentParser(description="Train the image autoencoder (train_autoencoder.py)")
-    parser.add_argument("--data", default="128_128_data", help="trajectory directory, or synthetic:<N>:images")
+    parser.add_argument("--data", default="128_128_data", help="trajectory directory, or synthetic:<N>:images|jpeg")
+    parser.add_argument("--raw-jpeg", action="store_true",
+                        help="read the directory's JPEG streams as they are and decode them on the GPU")
     parser.add_argument("--batch-size", type=int, default=BATCH_SIZE,
                         help="trajectories per step (under torch.distributed.run: over all ranks)")
     parser.add_argument("--epochs", type=int, default=NUM_EPOCHS)
@@ -184,7 +194,8 @@ def make_parser():
 def main(argv=None):
     args = make_parser().parse_args(argv)
     return train(args.data, batch_size=args.batch_size, num_epochs=args.epochs, lr=args.lr, save_dir=args.save_dir,
-                 visdom=args.visdom, sync_batchnorm=args.sync_batchnorm, grad_exchange=args.grad_exchange)
+                 visdom=args.visdom, sync_batchnorm=args.sync_batchnorm, grad_exchange=args.grad_exchange,
+                 raw_jpeg=args.raw_jpeg)
 
 
 if __name__ == "__main__":

@@ -26,6 +26,7 @@ import torch
 from torch.utils import data
 
 from . import dp
+from . import jpeg as jpeg_frames
 from .forward_trainer import ForwardModelTrainer
 from .models.forward_encoder import Decoder, Encoder, ForwardAutoencoder
 from .train_gan import _get, denorm, make_dataset, norm  # noqa: F401
@@ -99,9 +100,11 @@ def train(config):
         display = None
 
     dataset = make_dataset(config)
-    if getattr(dataset, "mode", "images") not in ("images", "frames_u8"):
+    if getattr(dataset, "mode", "images") not in ("images", "frames_u8", "jpeg"):
         raise ValueError("the forward model trains on images: use `synthetic:<N>:images` or an HDF5 directory")
-    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True)
+    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True, **jpeg_frames.loader_kwargs(dataset))
+    # JPEG frames (`synthetic:<N>:jpeg`, `raw_jpeg: true`) are decoded on the device; failures raise one batch later
+    jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
 
     model = ForwardAutoencoder().to(device)                          # train_forward_model.py:67-70
     model.decoder.weight_init(mean=0.0, std=0.02)
@@ -139,6 +142,8 @@ def train(config):
                     continue
                 lo, hi = dp.shard_bounds(batch_size, rank, world)
                 images, actions = images[lo:hi], actions[lo:hi]
+            if jpeg_decoder is not None:
+                images = jpeg_decoder.decode_frames(images)
             images = images.to(device, non_blocking=True)
             if images.dtype != torch.uint8:                          # byte frames [B,T,128,128,3]: normalised by the kernels
                 images = images.float()
@@ -148,6 +153,8 @@ def train(config):
                              actions[:, image_num].contiguous())
                 step += 1
                 pairs += 1
+        if jpeg_decoder is not None:
+            jpeg_decoder.finish()
         avg_loss = float(trainer.loss_sum.item()) / max(pairs, 1)    # (seq_length - 1) * len(loader) terms
         if world > 1:
             avg_loss = dp.reduce_loss_shares([avg_loss / world], device=device)[0]

@@ -18,7 +18,7 @@ What differs from the reference, on purpose:
   * the forward-model checkpoints the reference loads and never uses (train_gan.py:79-86) are
     not loaded; visdom plotting is attempted only if visdom is importable.
 
-Extra YAML keys (all optional): `train_data_path: synthetic:<N>[:codes|images|frames_u8]` for seeded
+Extra YAML keys (all optional): `train_data_path: synthetic:<N>[:codes|images|frames_u8|jpeg]` for seeded
 synthetic trajectories, `training.gan.noise_source`, `training.gan.use_graph`,
 `training.gan.steps_per_launch` (iterations per HIP-graph launch, default 16; the batches of one
 launch are staged into separate input slots, the arithmetic is unchanged),
@@ -40,6 +40,7 @@ import torch  # noqa: E402
 from torch.utils import data  # noqa: E402
 
 from . import dp  # noqa: E402
+from . import jpeg as jpeg_frames  # noqa: E402
 from .models.gan import Decoder, Discriminator  # noqa: E402
 from .models.image_autoencoder import Encoder  # noqa: E402
 from .trainer import GanTrainer  # noqa: E402
@@ -93,8 +94,10 @@ def make_dataset(config):
         mode = spec[2] if len(spec) > 2 else "codes"
         return SyntheticPushDataset(n, seq_length=config.trajectory_length, mode=mode, seed=int(config.random_seed))
     # decoded frames stay bytes until the first convolution reads them (ndp_encoder_forward_u8 / ndp_fm_*_u8):
-    # `raw_uint8: false` restores the reference's host-side float tensors
-    return PushDataset(config.train_data_path, seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)))
+    # `raw_uint8: false` restores the reference's host-side float tensors; `raw_jpeg: true` yields the stored JPEG
+    # streams, decoded on the device (ndivplanning_amd.jpeg)
+    return PushDataset(config.train_data_path, seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)),
+                       raw_jpeg=bool(_get(config, "raw_jpeg", False)))
 
 
 def load_encoder(config, device):
@@ -178,7 +181,9 @@ def train(config):
     if n_batches == 0:
         raise ValueError("dataset of %d trajectories is smaller than one batch of %d" % (len(dataset), batch_size))
     seq_length = int(dataset.seq_length)
-    image_mode = getattr(dataset, "mode", "images") in ("images", "frames_u8")
+    image_mode = getattr(dataset, "mode", "images") in ("images", "frames_u8", "jpeg")
+    # JPEG frames (`synthetic:<N>:jpeg`, `raw_jpeg: true`) are decoded on the device; failures raise one batch later
+    jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
     encoder = load_encoder(config, device) if image_mode else None
 
     decoder = Decoder(noise_dim=noise_dim)
@@ -242,7 +247,8 @@ def train(config):
                 check_lockstep("after the first launch")
 
         all_cached = cached is not None and bool(cached.all())
-        loader = None if all_cached else iter(data.DataLoader(dataset, batch_sampler=[b.tolist() for b in batches]))
+        loader = None if all_cached else iter(data.DataLoader(dataset, batch_sampler=[b.tolist() for b in batches],
+                                                              **jpeg_frames.loader_kwargs(dataset)))
         for idx in batches:
             if all_cached:
                 mine = idx[lo:hi].to(device)
@@ -250,6 +256,8 @@ def train(config):
             else:
                 frames, _states, actions, _goal = next(loader)
                 frames = frames[lo:hi]
+                if jpeg_decoder is not None:
+                    frames = jpeg_decoder.decode_frames(frames)
                 if frames.dtype != torch.uint8:                      # byte frames [B,T,128,128,3] are uploaded as they are
                     frames = frames.float()
                 frames = frames.to(device, non_blocking=True)
@@ -277,6 +285,8 @@ def train(config):
             if len(pending) == group:
                 flush()
         flush()
+        if jpeg_decoder is not None:
+            jpeg_decoder.finish()
         check_lockstep("end of epoch %d" % epoch)
         sums = dp.reduce_loss_shares(trainer.pop_loss_sums(), device=device)
         d_avg, g_avg, div_avg = (v / n_batches for v in sums)                   # train_gan.py:209-211
