@@ -26,6 +26,7 @@ namespace ndp {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 256;
 constexpr int kWaves = 4;
@@ -527,8 +528,27 @@ __device__ __forceinline__ void layer_dgrad_narrow(const float* dY, int ldd,
   }
 }
 
-// Copy an LDS tile [R x W] (stride ld) to global rows (stride gld), float4 coalesced.
-template <int RT, int W>
+// Write-through (sc1) 16-byte store of hand-off data -- what the NEXT kernel reads -- at base[off .. off + 3]; `base` is
+// wave-uniform.  The bytes leave the XCD's L2 while the kernel still computes, so the end-of-kernel release finds no
+// dirty lines to write back on the critical path; a 16-byte sc1 store issues like a plain one.  The buffer form is the
+// compiler-visible one: hipcc's counted s_waitcnt vmcnt(N) of the weight rings keeps seeing these stores (loads and
+// stores share the counter), which it would not with an asm store.  Only for 16-byte stores: narrower write-through
+// stores are one fabric write each and cost 3-6x per byte.
+__device__ __forceinline__ void stg4_wt(float* base, uint32_t off, f32x4 v) {
+  // (the descriptor is four scalar registers: built next to its use, not kept live.  Arguments copied by
+  // load_kernargs may sit in vector registers: readfirstlane tells hipcc the base is uniform -- without it every
+  // store becomes a loop over the distinct bases it cannot rule out)
+  const uint64_t ub = reinterpret_cast<uint64_t>(base);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(ub >> 32));   // (the builtin returns int:
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ub);  // widen as unsigned)
+  const uint64_t sb = ((uint64_t)hi << 32) | (uint64_t)lo;
+  const __amdgpu_buffer_rsrc_t rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(sb), 0, 0x7fffffff, 0x00020000);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rsrc, (int)(off * 4u), 0, 16 /* sc1 */);
+}
+
+// Copy an LDS tile [R x W] (stride ld) to global rows (stride gld), float4 coalesced.  WT: see stg4_wt.
+template <int RT, int W, bool WT = false>
 __device__ __forceinline__ void store_tile(float* __restrict__ dst, size_t gld,
                                            const float* src, int ld) {
   constexpr int R = 16 * RT;
@@ -538,8 +558,9 @@ __device__ __forceinline__ void store_tile(float* __restrict__ dst, size_t gld,
 #endif
   for (int idx = threadIdx.x; idx < NV; idx += kThreads) {
     const int row = idx / (W / 4), k = 4 * (idx % (W / 4));
-    *reinterpret_cast<f32x4*>(dst + (size_t)row * gld + k) =
-        *reinterpret_cast<const f32x4*>(src + row * ld + k);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(src + row * ld + k);
+    if constexpr (WT) stg4_wt(dst, (uint32_t)(row * (int)gld + k), v);
+    else *reinterpret_cast<f32x4*>(dst + (size_t)row * gld + k) = v;
   }
 }
 

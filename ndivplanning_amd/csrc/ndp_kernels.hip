@@ -708,6 +708,16 @@ __device__ __forceinline__ void fc1_from_code_rows(const float* part, const floa
   }
 }
 
+// Store policy of the data that crosses a kernel boundary of the fused step (stg4_wt in ndp_device.h): which of the
+// 16-byte hand-off stores are write-through.  Decided per instantiation, each by its own A/B:
+// the one-workgroup-per-CU phase kernels of the small configurations (RG = 96) and the large-M ones, the slabs of
+// k_wgrad and of k_wgrad_wide.  4-byte and scattered stores always stay plain.
+constexpr bool kWtTilesCu1 = true;      // config 2: k_phase_a -1.4 us, k_phase_b -0.7 us per step
+constexpr bool kWtTilesLargeM = false;  // B = 1024 / K = 6 and B = 128 / K = 32: inside the run-to-run spread
+constexpr bool kWtSlabs = true;         // config 2: k_wgrad -0.2 us per launch, +0.6 % steps/s
+constexpr bool kWtSlabsWide = false;    // large M: no difference outside the run-to-run spread
+constexpr bool wt_tiles(int RG) { return RG >= 96 ? kWtTilesCu1 : kWtTilesLargeM; }
+
 // D forward + BCE + D backward data path on one 16-row tile whose inputs are in XC (codes) and XT (actions) and whose
 // fc1 weights `dw1` are already in flight.  real: the tile holds distinct real rows (weight real_scale each, stored
 // at row offset 0); otherwise fake rows (stored behind the rpad real rows).
@@ -720,6 +730,7 @@ __device__ __forceinline__ void phase_a_d_part(const PhaseAArgs& a, bool real, i
                                                float* B2, float* L, float* DL, const float* W4S,
                                                unsigned long long* stamp_lds_) {
   constexpr int R = 16;
+  constexpr bool WT = wt_tiles(RG);
   const DNet& d = a.d;
   (void)stamp_lds_;
   const int64_t row0 = (int64_t)tile * R;
@@ -768,11 +779,12 @@ __device__ __forceinline__ void phase_a_d_part(const PhaseAArgs& a, bool real, i
     if (threadIdx.x == 0) a.loss_partials[blockIdx.x] = tot;
   }
   NDP_STAMP(5);
-  store_tile<1, 64>(a.h1 + g0 * 64, 64, B2, 68);
-  store_tile<1, 128>(a.h2 + g0 * 128, 128, B1, 132);
-  store_tile<1, 256>(a.h3 + g0 * 256, 256, XC, 260);
+  store_tile<1, 64, WT>(a.h1 + g0 * 64, 64, B2, 68);
+  store_tile<1, 128, WT>(a.h2 + g0 * 128, 128, B1, 132);
+  store_tile<1, 256, WT>(a.h3 + g0 * 256, 256, XC, 260);
   if (threadIdx.x < R)
-    *reinterpret_cast<f32x4*>(a.xa + (g0 + threadIdx.x) * 4) = *reinterpret_cast<const f32x4*>(XT + threadIdx.x * TAILLD);
+    if constexpr (WT) stg4_wt(a.xa + g0 * 4, 4 * threadIdx.x, *reinterpret_cast<const f32x4*>(XT + threadIdx.x * TAILLD));
+    else *reinterpret_cast<f32x4*>(a.xa + (g0 + threadIdx.x) * 4) = *reinterpret_cast<const f32x4*>(XT + threadIdx.x * TAILLD);
   __syncthreads();
   NDP_STAMP(6);
   layer_dgrad_narrow<1, 256, 1, ACT_LRELU>(DL, 1, W4S, XC, 260);                       // XC := dY3
@@ -786,11 +798,11 @@ __device__ __forceinline__ void phase_a_d_part(const PhaseAArgs& a, bool real, i
   __syncthreads();
   // fc1's code-column weight gradient runs K-deduplicated: the fake rows of a tile that share a FLAT row (same code)
   // are pre-summed here; a real row is its FLAT row
-  if (real) store_tile<1, 64>(a.dy1seg + ((size_t)a.seg_entries + row0) * 64, 64, B2, 68);
+  if (real) store_tile<1, 64, WT>(a.dy1seg + ((size_t)a.seg_entries + row0) * 64, 64, B2, 68);
   else store_segment_sums<64, 1>(B2, 68, a.dy1seg, row0, a.code_rep, a.seg_s, a.seg_entries, tile, ntiles);
-  store_tile<1, 64>(a.dy1 + g0 * 64, 64, B2, 68);
-  store_tile<1, 128>(a.dy2 + g0 * 128, 128, B1, 132);
-  store_tile<1, 256>(a.dy3 + g0 * 256, 256, XC, 260);
+  store_tile<1, 64, WT>(a.dy1 + g0 * 64, 64, B2, 68);
+  store_tile<1, 128, WT>(a.dy2 + g0 * 128, 128, B1, 132);
+  store_tile<1, 256, WT>(a.dy3 + g0 * 256, 256, XC, 260);
 }
 
 // 32 needs 36 bytes of scratch per lane under the 168-VGPR cap of three workgroups per CU;
@@ -802,6 +814,7 @@ template <bool PK, int RG, int NR>
 __global__ __launch_bounds__(kThreads, (RG >= 96 ? 1 : 3)) void k_phase_a(PhaseAArgs a_segment) {
   constexpr bool DD = NR > 0;
   constexpr int NRR = NR > 0 ? NR : 1;
+  constexpr bool WT = wt_tiles(RG);
   // one workgroup per CU (RG = 96): nothing hides the argument loads, read them in one round trip (load_kernargs);
   // with several workgroups per CU the registers that costs are worth more
   const PhaseAArgs a = RG >= 96 ? load_kernargs<PhaseAArgs>() : a_segment;
@@ -902,14 +915,14 @@ __global__ __launch_bounds__(kThreads, (RG >= 96 ? 1 : 3)) void k_phase_a(PhaseA
     NDP_STAMP(12);
     FwdW<64, 128, 4, PK, RG> gw3;
     gw3.bind(PK ? g.pf3 : g.w3, 64, g.b3, nullptr, 0);
-    store_tile<1, 128>(a.gh1 + row0 * 128, 128, B1, 132);
+    store_tile<1, 128, WT>(a.gh1 + row0 * 128, 128, B1, 132);
     layer_fwd_run<1, 128, 64, ACT_RELU, 4, PK>(gw2, B1, 132, B2, 68, nullptr, 0, gw3);   // h2 -> B2
     __syncthreads();
     NDP_STAMP(13);
     FwdW<128, 256, 4, PK, RG> gw4;
     gw4.bind(PK ? g.pf4 : g.w4, 128, g.b4, nullptr, 0);
     NDP_STAMP(16);
-    store_tile<1, 64>(a.gh2 + row0 * 64, 64, B2, 68);
+    store_tile<1, 64, WT>(a.gh2 + row0 * 64, 64, B2, 68);
     NDP_STAMP(17);
     layer_fwd_run<1, 64, 128, ACT_RELU, 4, PK>(gw3, B2, 68, B1, 132, nullptr, 0, gw4);   // h3 -> B1 (h1 is stored)
     NDP_STAMP(18);
@@ -918,14 +931,14 @@ __global__ __launch_bounds__(kThreads, (RG >= 96 ? 1 : 3)) void k_phase_a(PhaseA
     if (DD) dw2.bind(PK ? d.pf2 : d.w2, 64, d.b2, nullptr, 0);                            // D's first MFMA layer flies during G fc4
     else dw1.bind(PK ? d.pf1 : d.w1 + ADIM, 260, d.b1, d.w1, ADIM);
     NDP_STAMP(19);
-    store_tile<1, 128>(a.gh3 + row0 * 128, 128, B1, 132);
+    store_tile<1, 128, WT>(a.gh3 + row0 * 128, 128, B1, 132);
     NDP_STAMP(20);
     if (DD) layer_fwd_run<1, 128, 256, ACT_RELU, 4, PK>(gw4, B1, 132, B3, 260, nullptr, 0, dw2);
     else layer_fwd_run<1, 128, 256, ACT_RELU, 4, PK>(gw4, B1, 132, B3, 260, nullptr, 0, dw1); // h4 -> B3
     NDP_STAMP(21);
     __syncthreads();
     NDP_STAMP(15);
-    store_tile<1, 256>(a.gh4 + row0 * 256, 256, B3, 260);
+    store_tile<1, 256, WT>(a.gh4 + row0 * 256, 256, B3, 260);
     NDP_STAMP(22);
     layer_fwd_narrow<1, 256, 4>(B3, 260, W5S, W5S + 1024, A, 4);                          // action_hat -> A
     NDP_STAMP(23);
@@ -939,7 +952,8 @@ __global__ __launch_bounds__(kThreads, (RG >= 96 ? 1 : 3)) void k_phase_a(PhaseA
     if (threadIdx.x < R) {
       const int64_t row = row0 + threadIdx.x;
       if (row < a.m)
-        *reinterpret_cast<f32x4*>(a.action_hat + row * 4) = *reinterpret_cast<const f32x4*>(A + threadIdx.x * 4);
+        if constexpr (WT) stg4_wt(a.action_hat + row0 * 4, 4 * threadIdx.x, *reinterpret_cast<const f32x4*>(A + threadIdx.x * 4));
+        else *reinterpret_cast<f32x4*>(a.action_hat + row * 4) = *reinterpret_cast<const f32x4*>(A + threadIdx.x * 4);
     }
     __syncthreads();
     NDP_STAMP(9);
@@ -1002,6 +1016,7 @@ template <bool PK, int RG, bool PRE, int NR>
 __global__ __launch_bounds__(kThreads, (RG >= 96 ? 2 : 3)) void k_phase_b(PhaseBArgs a_segment) {
   constexpr bool DD = NR > 0;
   constexpr int NRR = NR > 0 ? NR : 1;
+  constexpr bool WT = wt_tiles(RG);
   const PhaseBArgs a = RG >= 96 ? load_kernargs<PhaseBArgs>() : a_segment;   // see k_phase_a
   constexpr int R = 16;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1177,16 +1192,16 @@ __global__ __launch_bounds__(kThreads, (RG >= 96 ? 2 : 3)) void k_phase_b(PhaseB
   NDP_STAMP(8);
   DgW<128, 64, PK, RG> gg2;
   gg2.bind(PK ? g.pg2 : g.w2, 128);
-  store_tile<1, 256>(a.dy4 + row0 * 256, 256, G4, 260);
+  store_tile<1, 256, WT>(a.dy4 + row0 * 256, 256, G4, 260);
   layer_dgrad_run<1, 64, 128, ACT_RELU, PK>(gg3, G3, 132, G2, 68, gg2);                 // G2 := G.dY2
   __syncthreads();
   NDP_STAMP(9);
-  store_tile<1, 128>(a.dy3 + row0 * 128, 128, G3, 132);
+  store_tile<1, 128, WT>(a.dy3 + row0 * 128, 128, G3, 132);
   layer_dgrad_run<1, 128, 64, ACT_RELU, PK>(gg2, G2, 68, H1, 132);                      // H1 := G.dY1
   __syncthreads();
   NDP_STAMP(10);
-  store_tile<1, 64>(a.dy2 + row0 * 64, 64, G2, 68);
-  store_tile<1, 128>(a.dy1 + row0 * 128, 128, H1, 132);
+  store_tile<1, 64, WT>(a.dy2 + row0 * 64, 64, G2, 68);
+  store_tile<1, 128, WT>(a.dy1 + row0 * 128, 128, H1, 132);
   store_segment_sums<128, 1>(H1, 132, a.dy1seg, row0, a.code_rep, a.seg_s, a.seg_entries, (int)blockIdx.x, (int)gridDim.x);
   NDP_STAMP(11);
   NDP_STAMP_FLUSH(12, 6);
@@ -1260,7 +1275,7 @@ struct WgradArgs : WgradHead {
 #define NDP_WSTAMP(i) do { } while (0)
 #endif
 
-template <int MT, int NT, int KIND>
+template <int MT, int NT, int KIND, bool WT>
 __device__ __forceinline__ void wgrad_block(const WgradJob& jb, int rbeg, int rend, int row_last,
                                             float* slab, float* smem, unsigned long long* wst) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1406,7 +1421,8 @@ __device__ __forceinline__ void wgrad_block(const WgradJob& jb, int rbeg, int re
     if (j < jn) {
       float* d = slab + jb.dst_off + (size_t)j * jb.dst_ld + k;
       if (KIND != WG_SKINNY_B && ((jb.dst_ld | jb.dst_off) & 3) == 0) {
-        *reinterpret_cast<f32x4*>(d) = s;
+        if constexpr (WT) stg4_wt(slab + jb.dst_off, (uint32_t)(j * jb.dst_ld + k), s);
+        else *reinterpret_cast<f32x4*>(d) = s;
       } else {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
@@ -1434,6 +1450,7 @@ __device__ __forceinline__ void wgrad_block(const WgradJob& jb, int rbeg, int re
 constexpr int kWideR = 16;
 constexpr int wide_slab_floats() { return kWideR * (128 + 128); }
 constexpr int wgrad_wide_lds_floats() { return 3 * wide_slab_floats(); }
+template <bool WT>
 __device__ __forceinline__ void wgrad_wide(const WgradJob& jb, int rbeg, int rend, float* slab, float* smem) {
   typedef __attribute__((address_space(3))) void* lds_ptr_t;
   typedef const __attribute__((address_space(1))) void* glb_ptr_t;
@@ -1497,8 +1514,13 @@ __device__ __forceinline__ void wgrad_wide(const WgradJob& jb, int rbeg, int ren
   for (int u = 0; u < 4; ++u)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      float* d = slab + jb.dst_off + (size_t)(64 * jt + 4 * (4 * q + i) + u) * jb.dst_ld + 64 * kt0 + 4 * c;
-      *reinterpret_cast<f32x4*>(d) = f32x4{acc[u][0][i], acc[u][1][i], acc[u][2][i], acc[u][3][i]};
+      const f32x4 o = {acc[u][0][i], acc[u][1][i], acc[u][2][i], acc[u][3][i]};
+      if constexpr (WT) {
+        stg4_wt(slab + jb.dst_off, (uint32_t)((64 * jt + 4 * (4 * q + i) + u) * jb.dst_ld + 64 * kt0 + 4 * c), o);
+      } else {
+        float* d = slab + jb.dst_off + (size_t)(64 * jt + 4 * (4 * q + i) + u) * jb.dst_ld + 64 * kt0 + 4 * c;
+        *reinterpret_cast<f32x4*>(d) = o;
+      }
     }
   if (jb.bias_off >= 0 && kt0 == 0) {
 #pragma unroll
@@ -1583,10 +1605,11 @@ __device__ __forceinline__ void wgrad_body(float* smem) {
 #else
   unsigned long long* wst = nullptr;
 #endif
-  if (WIDE && kind == WG_WIDE) wgrad_wide(jb, rbeg, rend, slab, smem);
-  else if (kind == WG_FULL) wgrad_block<4, 4, WG_FULL>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
-  else if (kind == WG_SKINNY_B) wgrad_block<4, 1, WG_SKINNY_B>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
-  else wgrad_block<1, 4, WG_SKINNY_A>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
+  constexpr bool WT = WIDE ? kWtSlabsWide : kWtSlabs;       // the slabs k_reduce_adam reads next
+  if (WIDE && kind == WG_WIDE) wgrad_wide<WT>(jb, rbeg, rend, slab, smem);
+  else if (kind == WG_FULL) wgrad_block<4, 4, WG_FULL, WT>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
+  else if (kind == WG_SKINNY_B) wgrad_block<4, 1, WG_SKINNY_B, WT>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
+  else wgrad_block<1, 4, WG_SKINNY_A, WT>(jb, rbeg, rend, jrows - 1, slab, smem, wst);
 #ifdef NDP_STAMPS
   NDP_WSTAMP(4);
   if (threadIdx.x == 0 && NDP_STAMP_ON(4))
