@@ -20,10 +20,14 @@ import ctypes
 import torch
 
 from . import _capi
+from .forward_trainer import FlatTrainer
 from .models import image_autoencoder as IA
 
 
-class AutoencoderTrainer:
+class AutoencoderTrainer(FlatTrainer):
+    _WORKSPACE_FN, _APPLY_FN = "ndp_ae_workspace_floats", "ndp_ae_apply_adam"
+    _grad_buckets = staticmethod(_capi.ae_grad_buckets)
+
     def __init__(self, encoder: IA.Encoder, decoder: IA.Decoder, batch: int, lr: float = 2e-4, betas=(0.5, 0.999),
                  eps: float = 1e-8, keep_reconstruction: bool = False, reduce_fn=None, bucket_reduce=None,
                  sync_batchnorm_world: int = 1, stat_group=None):
@@ -42,17 +46,8 @@ class AutoencoderTrainer:
             raise ValueError("sync_batchnorm_world must be >= 1, got %r" % (sync_batchnorm_world,))
         self.reduce_fn, self.bucket_reduce = reduce_fn, bucket_reduce
         self.sync_world = int(sync_batchnorm_world)
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.params, self.stats = IA.pack_autoencoder(encoder, decoder, dev)
-        self.grad = torch.zeros_like(self.params)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.step_word = torch.zeros(4, dtype=torch.int32, device=dev)      # Adam state word (include/ndp.h)
-        self.loss = torch.zeros(1, **f32)
-        self.loss_sum = torch.zeros(1, **f32)
-        self.recon = torch.zeros(self.batch, 3, 128, 128, **f32) if keep_reconstruction else None
-        self.workspace = torch.empty(self.lib.ndp_ae_workspace_floats(self.batch), **f32)
-        self.steps = 0                                                       # Adam steps
+        self._allocate(IA.pack_autoencoder(encoder, decoder, dev), lr, betas, eps)
+        self.recon = torch.zeros(self.batch, 3, 128, 128, dtype=torch.float32, device=dev) if keep_reconstruction else None
         self.forwards = 0                                                    # training-mode forwards (num_batches_tracked)
         self._batches0 = int(encoder.conv1_bn.num_batches_tracked.item())
         # cross-rank statistics: the callback and the ctypes thunk the library calls, alive until close()
@@ -98,33 +93,15 @@ class AutoencoderTrainer:
         self.forwards += 1
         return self.loss
 
-    def apply(self):
-        """optimizer.step()"""
-        p = _capi.ptr
-        with torch.cuda.device(self.device):
-            _capi.check(self.lib.ndp_ae_apply_adam(p(self.params), p(self.grad), p(self.exp_avg), p(self.exp_avg_sq),
-                                                   p(self.step_word), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                   p(self.workspace), _capi.stream_ptr(self.device)), "ndp_ae_apply_adam")
-        self.steps += 1
-
     def step(self, images):
         """The loop body of train_autoencoder.py:79-90 for one image batch; returns the loss (device scalar: this rank's,
         the mean over its own images)."""
         self.grads(images)
-        if self.bucket_reduce is not None:
-            self.bucket_reduce(self.grad, self.device)
-        elif self.reduce_fn is not None:
-            self.reduce_fn(self.grad)
-        self.apply()
-        return self.loss
+        return self._reduce_and_apply()
 
     def close(self):
         """Release the cross-rank statistics callback (if any); a closed data-parallel trainer refuses grads()."""
         self.stat_sync, self._stat_cb = None, None
-
-    def gradient_buckets(self):
-        """[(offset, count)] of the flat gradient, in the order the backward pass completes them."""
-        return _capi.ae_grad_buckets()
 
     def load_from_modules(self):
         """Take parameters and running statistics from the modules again (after they were changed from outside)."""
@@ -148,9 +125,5 @@ class AutoencoderTrainer:
         off = self.lib.ndp_ae_workspace_offset(n, idx)
         return self.workspace[off:off + n * side * side * ch].view(n, side, side, ch).permute(0, 3, 1, 2).contiguous()
 
-    def named_gradients(self):
-        """'encoder.conv1.weight' ... -> gradient in the modules' own tensor shapes (tests, inspection)."""
-        return IA.unpack_autoencoder_vector(self.grad, self.encoder, self.decoder)
-
-    def named_parameters(self):
-        return IA.unpack_autoencoder_vector(self.params, self.encoder, self.decoder)
+    def _unpack(self, vec):
+        return IA.unpack_autoencoder_vector(vec, self.encoder, self.decoder)

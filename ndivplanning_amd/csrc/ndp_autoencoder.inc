@@ -12,7 +12,10 @@
 // k_fm_splitk_reduce, k_fm_slab_sum, the epilogue statistics, k_fm_bn_apply / k_fm_bn_bwd_apply, k_fm_pack /
 // k_fm_adam_pack).  Its maps are NHWC with the channel count as the pixel stride (nothing is concatenated).  Its eight
 // BatchNorms have the channel counts of the forward model's first eight (conv1..3_bn, deconv1..5_bn), so they use those
-// BatchNorm indices, statistics slots and scratch; where their tensors live comes from FmBnAt.
+// BatchNorm indices, statistics slots and scratch; where their tensors live comes from FmBnAt.  What this file says about
+// the network is its table (kAeNet: layers, BatchNorm count, gradient buckets), its workspace tensors, the output layer's
+// kernels and the two launch sequences; every size, offset, pack and optimizer segment comes from the table through the
+// helpers of ndp_forward_model.inc, which is also how a further network of the family would be added.
 //
 // New here: deconv6, 64 -> 3 channels at 128 x 128.  As a GEMM its three output channels would be padded to 32 (ten
 // times the MACs, a 32-wide output map); instead three small VALU kernels sized to what they move, as k_fm_r2_*:
@@ -30,64 +33,41 @@
 // caller's per-call function (fm_stat_sync; 8 forward + 8 backward calls) and one event per gradient bucket, recorded
 // where the backward pass has written the bucket's last byte (ae_backward's close_bucket; ndp_ae_bucket_wait).
 
-#include <atomic>
-
 namespace ndp {
 
 constexpr int kAeLayers = 12;
 static const FmLayer kAe[kAeLayers] = {
-    {FM_CONV, 3, 64, 128, 64, 3, 2, 1, 32, 64},        // 0  encoder.conv1
-    {FM_CONV, 64, 128, 64, 32, 3, 2, 1, 64, 128},      // 1  encoder.conv2
-    {FM_CONV, 128, 256, 32, 16, 3, 2, 1, 128, 256},    // 2  encoder.conv3
-    {FM_CONV, 256, 512, 16, 8, 3, 2, 1, 256, 512},     // 3  encoder.conv4
-    {FM_CONV, 512, 1024, 8, 4, 3, 2, 1, 512, 1024},    // 4  encoder.conv5
-    {FM_CONV, 1024, 128, 4, 1, 4, 1, 0, 1024, 128},    // 5  encoder.conv6
-    {FM_DECONV, 128, 1024, 1, 4, 4, 1, 0, 128, 1024},  // 6  decoder.deconv1
-    {FM_DECONV, 1024, 512, 4, 8, 4, 2, 1, 1024, 512},  // 7  decoder.deconv2
-    {FM_DECONV, 512, 256, 8, 16, 4, 2, 1, 512, 256},   // 8  decoder.deconv3
-    {FM_DECONV, 256, 128, 16, 32, 4, 2, 1, 256, 128},  // 9  decoder.deconv4
-    {FM_DECONV, 128, 64, 32, 64, 4, 2, 1, 128, 64},    // 10 decoder.deconv5
-    {FM_DECONV, 64, 3, 64, 128, 4, 2, 1, 64, 4},       // 11 decoder.deconv6
+    {FM_CONV, 3, 64, 128, 64, 3, 2, 1, 32, 64, FM_P2_COLUMNS},          // 0  encoder.conv1
+    {FM_CONV, 64, 128, 64, 32, 3, 2, 1, 64, 128, FM_P2_CONV_S2},        // 1  encoder.conv2
+    {FM_CONV, 128, 256, 32, 16, 3, 2, 1, 128, 256, FM_P2_CONV_S2},      // 2  encoder.conv3
+    {FM_CONV, 256, 512, 16, 8, 3, 2, 1, 256, 512, FM_P2_CONV_S2},       // 3  encoder.conv4
+    {FM_CONV, 512, 1024, 8, 4, 3, 2, 1, 512, 1024, FM_P2_CONV_S2},      // 4  encoder.conv5
+    {FM_CONV, 1024, 128, 4, 1, 4, 1, 0, 1024, 128, FM_P2_CONV6},        // 5  encoder.conv6
+    {FM_DECONV, 128, 1024, 1, 4, 4, 1, 0, 128, 1024, FM_P2_DECONV1},    // 6  decoder.deconv1
+    {FM_DECONV, 1024, 512, 4, 8, 4, 2, 1, 1024, 512, FM_P2_DECONV_S2},  // 7  decoder.deconv2
+    {FM_DECONV, 512, 256, 8, 16, 4, 2, 1, 512, 256, FM_P2_DECONV_S2},   // 8  decoder.deconv3
+    {FM_DECONV, 256, 128, 16, 32, 4, 2, 1, 256, 128, FM_P2_DECONV_S2},  // 9  decoder.deconv4
+    {FM_DECONV, 128, 64, 32, 64, 4, 2, 1, 128, 64, FM_P2_DECONV_S2},    // 10 decoder.deconv5
+    {FM_DECONV, 64, 3, 64, 128, 4, 2, 1, 64, 4, FM_P2_NONE},            // 11 decoder.deconv6
 };
 // BatchNorms in use: conv1..3_bn, deconv1..5_bn = the forward model's BatchNorms 0..7 (kFmBnC, kFmBnLayer: same channels,
 // same layer indices)
 constexpr int kAeBns = 8;
 constexpr int64_t kAeMaxImages = 8192;
-
-static int64_t ae_w_rows(int l) { return kAe[l].kind == FM_CONV ? kAe[l].cout_pad : kAe[l].cin_pad; }
-static int64_t ae_w_cols(int l) { return kAe[l].kind == FM_CONV ? kAe[l].cin_pad : kAe[l].cout_pad; }
-static int64_t ae_w_floats(int l) { return ae_w_rows(l) * kAe[l].ksz * kAe[l].ksz * ae_w_cols(l); }
-// flat parameter buffer: per layer [W (P1)][bias (cout_pad)], then per BatchNorm [weight][bias]
-static int64_t ae_param_offset(int l, bool bias) {
-  int64_t o = 0;
-  for (int i = 0; i < l; ++i) o += ae_w_floats(i) + kAe[i].cout_pad;
-  return o + (bias ? ae_w_floats(l) : 0);
-}
-static int64_t ae_bn_offset(int b, bool bias) {
-  int64_t o = ae_param_offset(kAeLayers, false);
-  for (int i = 0; i < b; ++i) o += 2 * kFmBnC[i];
-  return o + (bias ? kFmBnC[b] : 0);
-}
-static int64_t ae_param_floats() { return ae_bn_offset(kAeBns, false); }
-// running statistics: per BatchNorm [running_mean][running_var] (the forward model's first eight entries)
-static int64_t ae_stat_floats() { return fm_stat_offset(kAeBns, false); }
-// P2 (second operand order, the forward model's kinds): conv1's column form, conv2..deconv5; deconv6 reads P1
-static int64_t ae_p2_floats(int l) {
-  if (l == 0) return (int64_t)64 * 32;
-  if (l == 11) return 0;
-  return ae_w_floats(l);
-}
-static int64_t ae_p2_offset(int l) {
-  int64_t o = 0;
-  for (int i = 0; i < l; ++i) o += ae_p2_floats(i);
-  return o;
-}
-static int ae_pack_kind(int l) {
-  if (l == 0) return 5;
-  if (l == 5) return 2;
-  if (l == 6) return 4;
-  return kAe[l].kind == FM_CONV ? 0 : 3;
-}
+// Gradient buckets of ndp_ae_train_grads_dp: ranges of the flat gradient in the order ae_backward completes them (weight
+// gradients last layer first; a layer's bias gradient is final before its weight gradient starts).  Each is closed as
+// fm_backward closes its buckets: the row-chunk slabs of its layers are summed, then its event is recorded.
+//   bucket 0  layers 8..11 (deconv3..6)        3  layer 4 (conv5)
+//          1  layer 7 (deconv2: 8.4 M floats)  4  layers 0..3 (conv1..4)
+//          2  layers 5, 6 (conv6, deconv1)     5  the BatchNorm weights and biases (final after conv1_bn's backward)
+constexpr int kAeBuckets = 6;
+static const int kAeBucketFirst[kAeBuckets] = {8, 7, 5, 4, 0, -1};
+static const int kAeBucketEnd[kAeBuckets] = {12, 8, 7, 5, 4, -1};
+// the table every host helper of ndp_forward_model.inc reads (sizes, offsets, fm_pack, fm_adam_pack, fm_layout, buckets);
+// deconv6 has no second weight order (FM_P2_NONE): the kernels below read P1
+static const FmNet kAeNet = {kAe, kAeLayers, kAeBns, kAeBucketFirst, kAeBucketEnd, kAeBuckets};
+static_assert(kAeBuckets <= kFmMaxBuckets, "FmBucketEvents::ev");
+static FmBucketEventSet g_ae_buckets;
 
 // ------------------------------------------------------------------------------------------ deconv6 (64 -> 3, 4x4 s2 p1)
 // Output pixel (oy, ox) of image i takes the taps ky = ((oy + 1) & 1) + 2 a (a = 0, 1) at source row iy = (oy + 1 - ky) / 2,
@@ -298,7 +278,7 @@ static const int64_t kAeTensorFloats[AET_COUNT] = {          // per image
     16 * 1024, 16 * 1024, 64 * 512, 64 * 512, 256 * 256, 256 * 256, 1024 * 128, 1024 * 128, 4096 * 64, 4096 * 64, 16384 * 4,
     4096 * 64, 1024 * 128, 256 * 256, 64 * 512, 16 * 1024, 128, 16 * 1024, 64 * 512, 256 * 256, 1024 * 128, 4096 * 64};
 static int64_t ae_fixed_floats() {
-  return ae_p2_offset(kAeLayers) + 3 * 2480 + 2 * fm_stat_offset_words(kFmStatSlots);
+  return fm_p2_offset(kAeNet, kAeLayers) + 3 * kFmBnChannels + 2 * fm_stat_offset_words(kFmStatSlots);
 }
 static int64_t ae_tensor_offset(int64_t n, int t) {
   int64_t o = ae_fixed_floats();
@@ -313,120 +293,13 @@ struct AeWs { FmWs fm; float* t[AET_COUNT]; };
 static AeWs ae_ws(float* ws, int64_t n) {
   AeWs w;
   memset(&w, 0, sizeof(w));
-  w.fm.p2 = ws;
-  w.fm.bn_mean = ws + ae_p2_offset(kAeLayers);
-  w.fm.bn_invstd = w.fm.bn_mean + 2480;
-  w.fm.bn_meanres = w.fm.bn_invstd + 2480;
-  w.fm.stat_acc = reinterpret_cast<long long*>(w.fm.bn_meanres + 2480);   // 16-byte aligned: every size before it is a multiple of 4 floats
+  fm_ws_head(w.fm, ws, kAeNet);
   for (int i = 0; i < AET_COUNT; ++i) w.t[i] = ws + ae_tensor_offset(n, i);
   w.fm.loss_partial = ws + ae_tensor_offset(n, AET_COUNT);
   w.fm.part = w.fm.loss_partial + fm_round4(n * 256);
   w.fm.slabs = w.fm.part + kFmPartCap;
   w.fm.stat_acc_local = reinterpret_cast<long long*>(w.fm.slabs + kFmSlabCap);
   return w;
-}
-// sync: the caller's cross-rank statistics (ndp_ae_train_grads_dp) or null (this rank's own)
-static FmBnAt ae_bn_at(int b, const float* params, float* running, float* grad, const FmStatSync* sync) {
-  FmBnAt at;
-  at.gamma = params + ae_bn_offset(b, false); at.beta = params + ae_bn_offset(b, true);
-  at.running_mean = running ? running + fm_stat_offset(b, false) : nullptr;
-  at.running_var = running ? running + fm_stat_offset(b, true) : nullptr;
-  at.d_gamma = grad ? grad + ae_bn_offset(b, false) : nullptr;
-  at.d_beta = grad ? grad + ae_bn_offset(b, true) : nullptr;
-  at.d_conv_bias = grad ? grad + ae_param_offset(kFmBnLayer[b], true) : nullptr;
-  at.sync = sync;                                                         // (never the forward model's ndp_fm_set_stat_sync)
-  return at;
-}
-
-// Gradient buckets of ndp_ae_train_grads_dp: ranges of the flat gradient in the order ae_backward completes them (weight
-// gradients last layer first; a layer's bias gradient is final before its weight gradient starts).  Each is closed as
-// fm_backward closes its buckets: the row-chunk slabs of its layers are summed, then its event is recorded.
-//   bucket 0  layers 8..11 (deconv3..6)        3  layer 4 (conv5)
-//          1  layer 7 (deconv2: 8.4 M floats)  4  layers 0..3 (conv1..4)
-//          2  layers 5, 6 (conv6, deconv1)     5  the BatchNorm weights and biases (final after conv1_bn's backward)
-constexpr int kAeBuckets = 6;
-static const int kAeBucketFirst[kAeBuckets] = {8, 7, 5, 4, 0, -1};    // first layer of the range (-1: BatchNorm parameters)
-static const int kAeBucketEnd[kAeBuckets] = {12, 8, 7, 5, 4, -1};     // one past its last layer
-static void ae_bucket_range(int b, int64_t* offset, int64_t* count) {
-  if (kAeBucketFirst[b] < 0) {
-    *offset = ae_bn_offset(0, false);
-    *count = ae_param_floats() - *offset;
-  } else {
-    *offset = ae_param_offset(kAeBucketFirst[b], false);
-    *count = ae_param_offset(kAeBucketEnd[b], false) - *offset;
-  }
-}
-// per device; `recorded` once a ndp_ae_train_grads_dp call has recorded all of them (ndp_ae_bucket_wait refuses before)
-struct AeBucketEvents { hipEvent_t ev[kAeBuckets]; bool ok; std::atomic<bool> recorded; };
-static AeBucketEvents g_ae_buckets[kMaxDevices];
-static std::once_flag g_ae_buckets_once[kMaxDevices];
-static AeBucketEvents* ae_bucket_events() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
-  AeBucketEvents* be = &g_ae_buckets[dev];
-  std::call_once(g_ae_buckets_once[dev], [be] {
-    be->ok = true;
-    for (int i = 0; i < kAeBuckets; ++i) be->ok = be->ok && hipEventCreateWithFlags(&be->ev[i], hipEventDisableTiming) == hipSuccess;
-  });
-  return be->ok ? be : nullptr;
-}
-
-// P1 -> P2 of conv1 .. deconv5, one launch (k_fm_pack)
-static int ae_pack(hipStream_t st, const float* params, const FmWs& ws) {
-  FmPackArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = params; a.p2_base = ws.p2; a.nseg = 0; a.block_begin[0] = 0;
-  int blocks = 0;
-  for (int l = 0; l < 11; ++l) {
-    const FmLayer& L = kAe[l];
-    const int i = a.nseg;
-    a.p1_off[i] = ae_param_offset(l, false); a.p2_off[i] = ae_p2_offset(l); a.count[i] = ae_p2_floats(l);
-    a.cin_[i] = L.cin; a.cout_[i] = L.cout; a.cin_pad_[i] = L.cin_pad; a.cout_pad_[i] = L.cout_pad;
-    a.kind[i] = ae_pack_kind(l);
-    blocks += (int)((a.count[i] + 1023) / 1024);
-    a.block_begin[++a.nseg] = blocks;
-  }
-  KTimer kt("k_fm_pack", st);
-  hipLaunchKernelGGL(k_fm_pack, dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
-  return check_launch("k_fm_pack");
-}
-
-// Adam over the flat vector + the P2 rebuild in one launch (k_fm_adam_pack with this network's segments)
-static int ae_adam_pack(hipStream_t st, float* params, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* step,
-                        float beta1, float beta2, float eps, const FmWs& ws) {
-  FmAdamPackArgs a;
-  memset(&a, 0, sizeof(a));
-  a.params = params; a.grad = grad; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.step = step;
-  a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.pk.params = params; a.pk.p2_base = ws.p2; a.pk.nseg = 0; a.pk.block_begin[0] = 0;
-  int blocks = 0;
-  int64_t covered = 0;
-  auto plain = [&](int64_t off, int64_t count) {
-    if (count <= 0) return;
-    const int i = a.nplain;
-    a.plain_off[i] = off; a.plain_count[i] = count;
-    a.plain_begin[i + 1] = a.plain_begin[i] + (int)((count + 1023) / 1024);
-    ++a.nplain;
-  };
-  for (int l = 1; l < 11; ++l) {                                       // conv2 .. deconv5: transposing segments
-    const FmLayer& L = kAe[l];
-    const int i = a.pk.nseg;
-    a.pk.p1_off[i] = ae_param_offset(l, false); a.pk.p2_off[i] = ae_p2_offset(l); a.pk.count[i] = ae_p2_floats(l);
-    a.pk.cin_[i] = L.cin; a.pk.cout_[i] = L.cout; a.pk.cin_pad_[i] = L.cin_pad; a.pk.cout_pad_[i] = L.cout_pad;
-    a.pk.kind[i] = ae_pack_kind(l);
-    blocks += (int)(a.pk.count[i] / 1024);                             // (whole 32 x 32 tiles)
-    a.pk.block_begin[++a.pk.nseg] = blocks;
-    plain(covered, ae_param_offset(l, false) - covered);               // what lies before this layer's weights
-    covered = ae_param_offset(l, true);
-  }
-  plain(covered, ae_param_floats() - covered);                         // deconv5's bias, deconv6, BatchNorm
-  a.tile_blocks = blocks;
-  a.r_count[0] = a.r_count[1] = 0;                                     // (no refinement layers)
-  a.r_cin_pad[0] = a.r_cin_pad[1] = 1;
-  a.c1_count = ae_w_floats(0); a.c1_p2 = ae_p2_offset(0);
-  KTimer kt("k_fm_adam_pack", st);
-  hipLaunchKernelGGL(k_fm_adam_pack, dim3((unsigned)(blocks + a.plain_begin[a.nplain])), dim3(kThreads), 0, st, a);
-  return check_launch("k_fm_adam_pack");
 }
 
 // forward pass, training mode, through the loss: g6 = d loss / d (pre-tanh output), loss partial sums
@@ -435,10 +308,10 @@ static int ae_forward_loss(hipStream_t st, const float* params, float* running, 
   fm_attrs();
   const FmWs& ws = aw.fm;
   const float* P = params;
-  auto W1 = [&](int l) { return P + ae_param_offset(l, false); };
-  auto B = [&](int l) { return P + ae_param_offset(l, true); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + ae_p2_offset(l)); };
-  auto BN = [&](int b) { return ae_bn_at(b, params, running, nullptr, sync); };
+  auto W1 = [&](int l) { return P + fm_param_offset(kAeNet, l, false); };
+  auto B = [&](int l) { return P + fm_param_offset(kAeNet, l, true); };
+  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kAeNet, l)); };
+  auto BN = [&](int b) { return fm_bn_at(kAeNet, b, params, running, nullptr, sync); };   // (sync: the caller's, never ndp_fm_set_stat_sync's)
   float* const* t = aw.t;
   int rc;
 #define AE_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
@@ -492,13 +365,13 @@ static int ae_forward_loss(hipStream_t st, const float* params, float* running, 
 // backward pass: from g6 to every gradient in `grad` (the bias gradient of deconv6 comes from the loss' partial sums).
 // buckets: record the gradient buckets' events (ndp_ae_train_grads_dp); null: one slab-sum launch at the end
 static int ae_backward(hipStream_t st, const float* params, int64_t n, float* grad, const AeWs& aw, const FmStatSync* sync,
-                       AeBucketEvents* buckets) {
+                       FmBucketEvents* buckets) {
   const FmWs& ws = aw.fm;
   const float* P = params;
-  auto W1 = [&](int l) { return P + ae_param_offset(l, false); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + ae_p2_offset(l)); };
-  auto GW = [&](int l) { return grad + ae_param_offset(l, false); };
-  auto BN = [&](int b) { return ae_bn_at(b, params, nullptr, grad, sync); };
+  auto W1 = [&](int l) { return P + fm_param_offset(kAeNet, l, false); };
+  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kAeNet, l)); };
+  auto GW = [&](int l) { return grad + fm_param_offset(kAeNet, l, false); };
+  auto BN = [&](int b) { return fm_bn_at(kAeNet, b, params, nullptr, grad, sync); };
   float* const* t = aw.t;
   int rc;
   FmSlabPlan plan;
@@ -519,7 +392,7 @@ static int ae_backward(hipStream_t st, const float* params, int64_t n, float* gr
     FmBiasFinishArgs bf;
     memset(&bf, 0, sizeof(bf));
     bf.fin = fm_fin(20 + i, 1, 1, ws);
-    bf.fin.out1 = grad + ae_param_offset(layer[i], true);
+    bf.fin.out1 = grad + fm_param_offset(kAeNet, layer[i], true);
     bf.cols = fm_stat_cols(20 + i);
     KTimer kt("k_fm_bias_finish", st);
     hipLaunchKernelGGL(k_fm_bias_finish, dim3(1), dim3(kThreads), 0, st, bf);
@@ -617,7 +490,7 @@ static int ae_backward(hipStream_t st, const float* params, int64_t n, float* gr
 // one training iteration's gradients: ndp_ae_train_grads (sync, buckets null) and ndp_ae_train_grads_dp
 static int ae_train_grads(const char* name, const float* params, float* running_stats, const float* images, int64_t n_images,
                           float* grad, float* loss, float* loss_sum, float* recon_out, float* workspace, void* stream,
-                          const FmStatSync* sync, AeBucketEvents* buckets) {
+                          const FmStatSync* sync, FmBucketEvents* buckets) {
   NDP_CHECK_ARG(params && images && grad && loss && workspace && n_images >= 1, "%s: bad arguments", name);
   NDP_CHECK_ARG(n_images <= kAeMaxImages, "%s: more than %d images per call", name, (int)kAeMaxImages);
   NDP_CHECK_ARG(aligned16(params) && aligned16(images) && aligned16(grad) && aligned16(workspace) &&
@@ -629,7 +502,7 @@ static int ae_train_grads(const char* name, const float* params, float* running_
   if (rc) return rc;
   const int nblocks = (int)(n_images * 64);
   hipLaunchKernelGGL(k_fm_loss_final, dim3(1), dim3(kThreads), 0, st, (const float*)ws.fm.loss_partial, nblocks,
-                     1.0 / (3.0 * (double)(n_images * 16384)), loss, loss_sum, grad + ae_param_offset(11, true));
+                     1.0 / (3.0 * (double)(n_images * 16384)), loss, loss_sum, grad + fm_param_offset(kAeNet, 11, true));
   rc = check_launch("k_fm_loss_final");
   if (rc) return rc;
   return ae_backward(st, params, n_images, grad, ws, sync, buckets);
@@ -639,8 +512,8 @@ static int ae_train_grads(const char* name, const float* params, float* running_
 
 extern "C" {
 
-int64_t ndp_ae_param_floats(void) { return ndp::ae_param_floats(); }
-int64_t ndp_ae_stat_floats(void) { return ndp::ae_stat_floats(); }
+int64_t ndp_ae_param_floats(void) { return ndp::fm_param_floats(ndp::kAeNet); }
+int64_t ndp_ae_stat_floats(void) { return ndp::fm_stat_offset(ndp::kAeBns, false); }
 int64_t ndp_ae_workspace_floats(int64_t n_images) {
   return n_images < 1 || n_images > ndp::kAeMaxImages ? 0 : ndp::ae_ws_floats(n_images);
 }
@@ -651,26 +524,13 @@ int64_t ndp_ae_workspace_offset(int64_t n_images, int tensor) {
 }
 
 int ndp_ae_layout(int what, int index, int64_t* offset, int64_t* dims) {
-  using namespace ndp;
-  NDP_CHECK_ARG(offset && dims, "ndp_ae_layout: null pointer");
-  if (what == 0 || what == 1) {
-    NDP_CHECK_ARG(index >= 0 && index < kAeLayers, "ndp_ae_layout: layer index out of range");
-    const FmLayer& L = kAe[index];
-    *offset = ae_param_offset(index, what == 1);
-    dims[0] = what == 0 ? ae_w_rows(index) : L.cout_pad; dims[1] = what == 0 ? L.ksz * L.ksz : 1;
-    dims[2] = what == 0 ? ae_w_cols(index) : 1; dims[3] = L.kind; dims[4] = L.cin; dims[5] = L.cout;
-    return NDP_OK;
-  }
-  NDP_CHECK_ARG(what >= 2 && what <= 5 && index >= 0 && index < kAeBns, "ndp_ae_layout: bad BatchNorm query");
-  *offset = what < 4 ? ae_bn_offset(index, what == 3) : fm_stat_offset(index, what == 5);
-  dims[0] = kFmBnC[index]; dims[1] = dims[2] = 1; dims[3] = kFmBnLayer[index]; dims[4] = dims[5] = kFmBnC[index];
-  return NDP_OK;
+  return ndp::fm_layout(ndp::kAeNet, "ndp_ae_layout", what, index, offset, dims);
 }
 
 int ndp_ae_pack_params(const float* params, float* workspace, void* stream) {
   using namespace ndp;
   NDP_CHECK_ARG(params && workspace && aligned16(params) && aligned16(workspace), "ndp_ae_pack_params: bad arguments");
-  return ae_pack((hipStream_t)stream, params, ae_ws(workspace, 1).fm);
+  return fm_pack((hipStream_t)stream, kAeNet, params, ae_ws(workspace, 1).fm);
 }
 
 int ndp_ae_train_grads(const float* params, float* running_stats, const float* images, int64_t n_images, float* grad,
@@ -686,7 +546,7 @@ int ndp_ae_train_grads_dp(const float* params, float* running_stats, const float
   NDP_CHECK_ARG(world >= 1 && world <= 4096, "ndp_ae_train_grads_dp: bad world size");
   NDP_CHECK_ARG(params && images && grad && loss && workspace && n_images >= 1 && n_images <= kAeMaxImages,
                 "ndp_ae_train_grads_dp: bad arguments");
-  AeBucketEvents* buckets = ae_bucket_events();
+  FmBucketEvents* buckets = fm_bucket_events(g_ae_buckets, kAeNet);
   if (buckets == nullptr) return fail(NDP_E_LAUNCH, "ndp_ae_train_grads_dp: could not create the bucket events");
   const FmStatSync sync = {stat_sync, stat_ctx, world};
   const int rc = ae_train_grads("ndp_ae_train_grads_dp", params, running_stats, images, n_images, grad, loss, loss_sum,
@@ -699,7 +559,7 @@ int ndp_ae_grad_buckets(int64_t* offsets, int64_t* counts, int capacity, int* n_
   using namespace ndp;
   NDP_CHECK_ARG(offsets && counts && n_buckets, "ndp_ae_grad_buckets: null pointer");
   NDP_CHECK_ARG(capacity >= kAeBuckets, "ndp_ae_grad_buckets: need room for %d buckets", kAeBuckets);
-  for (int b = 0; b < kAeBuckets; ++b) ae_bucket_range(b, offsets + b, counts + b);
+  for (int b = 0; b < kAeBuckets; ++b) fm_bucket_range(kAeNet, b, offsets + b, counts + b);
   *n_buckets = kAeBuckets;
   return NDP_OK;
 }
@@ -709,7 +569,7 @@ int ndp_ae_bucket_wait(int bucket, void* stream) {
   NDP_CHECK_ARG(bucket >= 0 && bucket < kAeBuckets, "ndp_ae_bucket_wait: bucket out of range");
   int dev = -1;
   NDP_CHECK_ARG(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices, "ndp_ae_bucket_wait: no current device");
-  AeBucketEvents& be = g_ae_buckets[dev];
+  FmBucketEvents& be = g_ae_buckets.dev[dev];
   NDP_CHECK_ARG(be.recorded.load(), "ndp_ae_bucket_wait: no ndp_ae_train_grads_dp call has recorded the events on this device");
   if (hipStreamWaitEvent((hipStream_t)stream, be.ev[bucket], 0) != hipSuccess)
     return fail(NDP_E_LAUNCH, "ndp_ae_bucket_wait: hipStreamWaitEvent failed");
@@ -724,7 +584,7 @@ int ndp_ae_apply_adam(float* params, const float* grad, float* exp_avg, float* e
                 "ndp_ae_apply_adam: buffers must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(1), 0, st, step_count, lr, beta1, beta2);
-  return ae_adam_pack(st, params, grad, exp_avg, exp_avg_sq, step_count, beta1, beta2, eps, ae_ws(workspace, 1).fm);
+  return fm_adam_pack(st, kAeNet, params, grad, exp_avg, exp_avg_sq, step_count, beta1, beta2, eps, ae_ws(workspace, 1).fm);
 }
 
 }  // extern "C"

@@ -27,66 +27,100 @@
 // Reductions are fixed-order (split-K partial sums, row-chunk slabs, per-block column partials): a step is
 // bit-reproducible.
 
+#include <atomic>
+
 namespace ndp {
 
-// ------------------------------------------------------------------------------------------ layer tables
+// ------------------------------------------------------------------------------------------ network tables
+// A network of this family is an FmNet: its layers, how many of the BatchNorms below it uses, and its gradient buckets.
+// Every size, offset and pack / optimizer segment on the host side is derived from that table (the helpers below,
+// fm_pack, fm_adam_pack, fm_layout, fm_bucket_range); the instances are kFmNet here and kAeNet in ndp_autoencoder.inc.
+// A further network adds its table, its workspace tensors and its own forward / backward launch sequence -- nothing else.
 enum { FM_CONV = 0, FM_DECONV = 1 };
-struct FmLayer { int kind, cin, cout, hin, hout, ksz, stride, pad, cin_pad, cout_pad; };
+// p2: how the layer's second weight order is made from P1 -- a k_fm_pack kind (see there), or none (the layer reads P1 only)
+enum { FM_P2_NONE = -1, FM_P2_CONV_S2 = 0, FM_P2_REFINE = 1, FM_P2_CONV6 = 2, FM_P2_DECONV_S2 = 3, FM_P2_DECONV1 = 4, FM_P2_COLUMNS = 5 };
+struct FmLayer { int kind, cin, cout, hin, hout, ksz, stride, pad, cin_pad, cout_pad, p2; };
+struct FmNet {
+  const FmLayer* layer; int layers;
+  int bns;                                              // it uses the first `bns` of kFmBnC / kFmBnLayer
+  const int* bucket_first; const int* bucket_end; int buckets;   // layer ranges [first, end); first -1: the BatchNorm parameters
+};
 constexpr int kFmLayers = 14;
 static const FmLayer kFm[kFmLayers] = {
-    {FM_CONV, 3, 64, 128, 64, 3, 2, 1, 32, 64},        // 0  encoder.conv1
-    {FM_CONV, 64, 128, 64, 32, 3, 2, 1, 64, 128},      // 1  encoder.conv2
-    {FM_CONV, 128, 256, 32, 16, 3, 2, 1, 128, 256},    // 2  encoder.conv3
-    {FM_CONV, 256, 512, 16, 8, 3, 2, 1, 256, 512},     // 3  encoder.conv4
-    {FM_CONV, 512, 1024, 8, 4, 3, 2, 1, 512, 1024},    // 4  encoder.conv5
-    {FM_CONV, 1024, 128, 4, 1, 4, 1, 0, 1024, 128},    // 5  encoder.conv6
-    {FM_DECONV, 132, 1024, 1, 4, 4, 1, 0, 160, 1024},  // 6  decoder.deconv1
-    {FM_DECONV, 2048, 512, 4, 8, 4, 2, 1, 2048, 512},  // 7  decoder.deconv2
-    {FM_DECONV, 1024, 256, 8, 16, 4, 2, 1, 1024, 256}, // 8  decoder.deconv3
-    {FM_DECONV, 512, 128, 16, 32, 4, 2, 1, 512, 128},  // 9  decoder.deconv4
-    {FM_DECONV, 256, 64, 32, 64, 4, 2, 1, 256, 64},    // 10 decoder.deconv5
-    {FM_DECONV, 128, 32, 64, 128, 4, 2, 1, 128, 32},   // 11 decoder.deconv6
-    {FM_CONV, 32, 16, 128, 128, 3, 1, 1, 32, 16},      // 12 decoder.conv_refine_1
-    {FM_CONV, 16, 3, 128, 128, 3, 1, 1, 32, 4},        // 13 decoder.conv_refine_2
+    {FM_CONV, 3, 64, 128, 64, 3, 2, 1, 32, 64, FM_P2_COLUMNS},          // 0  encoder.conv1
+    {FM_CONV, 64, 128, 64, 32, 3, 2, 1, 64, 128, FM_P2_CONV_S2},        // 1  encoder.conv2
+    {FM_CONV, 128, 256, 32, 16, 3, 2, 1, 128, 256, FM_P2_CONV_S2},      // 2  encoder.conv3
+    {FM_CONV, 256, 512, 16, 8, 3, 2, 1, 256, 512, FM_P2_CONV_S2},       // 3  encoder.conv4
+    {FM_CONV, 512, 1024, 8, 4, 3, 2, 1, 512, 1024, FM_P2_CONV_S2},      // 4  encoder.conv5
+    {FM_CONV, 1024, 128, 4, 1, 4, 1, 0, 1024, 128, FM_P2_CONV6},        // 5  encoder.conv6
+    {FM_DECONV, 132, 1024, 1, 4, 4, 1, 0, 160, 1024, FM_P2_DECONV1},    // 6  decoder.deconv1
+    {FM_DECONV, 2048, 512, 4, 8, 4, 2, 1, 2048, 512, FM_P2_DECONV_S2},  // 7  decoder.deconv2
+    {FM_DECONV, 1024, 256, 8, 16, 4, 2, 1, 1024, 256, FM_P2_DECONV_S2}, // 8  decoder.deconv3
+    {FM_DECONV, 512, 128, 16, 32, 4, 2, 1, 512, 128, FM_P2_DECONV_S2},  // 9  decoder.deconv4
+    {FM_DECONV, 256, 64, 32, 64, 4, 2, 1, 256, 64, FM_P2_DECONV_S2},    // 10 decoder.deconv5
+    {FM_DECONV, 128, 32, 64, 128, 4, 2, 1, 128, 32, FM_P2_DECONV_S2},   // 11 decoder.deconv6
+    {FM_CONV, 32, 16, 128, 128, 3, 1, 1, 32, 16, FM_P2_REFINE},         // 12 decoder.conv_refine_1
+    {FM_CONV, 16, 3, 128, 128, 3, 1, 1, 32, 4, FM_P2_REFINE},           // 13 decoder.conv_refine_2
 };
+// Gradient buckets for a data-parallel driver (SURVEY.md section 8e / 8f-4: "RCCL all-reduce ... overlapped with backward"):
+// ranges of the flat gradient in the order in which the backward pass completes them.  The weight gradients are produced
+// last layer first, so the range of layers 9..13 is final while the data-gradient chain is still at deconv3; one event per
+// bucket is recorded on the stream that wrote its last byte, and ndp_fm_bucket_wait makes the caller's communication
+// stream wait for it: the all-reduce of a bucket runs beside the rest of the backward pass.
+//   bucket 0  layers 9..13 (deconv4..6, refinement)      4  layer 4 (conv5)
+//          1  layer 8 (deconv3)                          5  layers 0..3 (conv1..4)
+//          2  layer 7 (deconv2: half of all parameters)  6  the BatchNorm weights and biases
+//          3  layers 5, 6 (conv6, deconv1)
+constexpr int kFmBuckets = 7;
+static const int kFmBucketFirst[kFmBuckets] = {9, 8, 7, 5, 4, 0, -1};
+static const int kFmBucketEnd[kFmBuckets] = {14, 9, 8, 7, 5, 4, -1};
 // BatchNorms in use (conv4_bn / conv5_bn are constructed by the reference and never applied: forward_encoder.py:51-54)
 constexpr int kFmBns = 10;
-static const int kFmBnC[kFmBns] = {64, 128, 256, 1024, 512, 256, 128, 64, 32, 16};   // conv1..3, deconv1..6, conv_refine_1
+constexpr int kFmBnC[kFmBns] = {64, 128, 256, 1024, 512, 256, 128, 64, 32, 16};   // conv1..3, deconv1..6, conv_refine_1
 static const int kFmBnLayer[kFmBns] = {0, 1, 2, 6, 7, 8, 9, 10, 11, 12};
 constexpr float kFmBnEps = 1e-5f, kFmBnMomentum = 0.1f;
+static const FmNet kFmNet = {kFm, kFmLayers, kFmBns, kFmBucketFirst, kFmBucketEnd, kFmBuckets};
+// channels of the BatchNorms before b: where b's batch mean / invstd / mean residual start in their scratch vectors
+constexpr int fm_bn_stat_index(int b) {
+  int o = 0;
+  for (int i = 0; i < b; ++i) o += kFmBnC[i];
+  return o;
+}
+constexpr int kFmBnChannels = fm_bn_stat_index(kFmBns);    // 2,480: the length of each scratch vector, in every network's workspace
 
 // P1 weight floats of layer l: rows x taps x columns
-static int64_t fm_w_rows(int l) { return kFm[l].kind == FM_CONV ? kFm[l].cout_pad : kFm[l].cin_pad; }
-static int64_t fm_w_cols(int l) { return kFm[l].kind == FM_CONV ? kFm[l].cin_pad : kFm[l].cout_pad; }
-static int64_t fm_w_floats(int l) { return fm_w_rows(l) * kFm[l].ksz * kFm[l].ksz * fm_w_cols(l); }
+static int64_t fm_w_rows(const FmNet& net, int l) { return net.layer[l].kind == FM_CONV ? net.layer[l].cout_pad : net.layer[l].cin_pad; }
+static int64_t fm_w_cols(const FmNet& net, int l) { return net.layer[l].kind == FM_CONV ? net.layer[l].cin_pad : net.layer[l].cout_pad; }
+static int64_t fm_w_floats(const FmNet& net, int l) { return fm_w_rows(net, l) * net.layer[l].ksz * net.layer[l].ksz * fm_w_cols(net, l); }
 // flat parameter buffer: per layer [W (P1)][bias (cout_pad)], then per BatchNorm [weight][bias]
-static int64_t fm_param_offset(int l, bool bias) {
+static int64_t fm_param_offset(const FmNet& net, int l, bool bias) {
   int64_t o = 0;
-  for (int i = 0; i < l; ++i) o += fm_w_floats(i) + kFm[i].cout_pad;
-  return o + (bias ? fm_w_floats(l) : 0);
+  for (int i = 0; i < l; ++i) o += fm_w_floats(net, i) + net.layer[i].cout_pad;
+  return o + (bias ? fm_w_floats(net, l) : 0);
 }
-static int64_t fm_bn_offset(int b, bool bias) {
-  int64_t o = fm_param_offset(kFmLayers, false);
+static int64_t fm_bn_offset(const FmNet& net, int b, bool bias) {
+  int64_t o = fm_param_offset(net, net.layers, false);
   for (int i = 0; i < b; ++i) o += 2 * kFmBnC[i];
   return o + (bias ? kFmBnC[b] : 0);
 }
-static int64_t fm_param_floats() { return fm_bn_offset(kFmBns, false); }
-// running statistics: per BatchNorm [running_mean][running_var]
+static int64_t fm_param_floats(const FmNet& net) { return fm_bn_offset(net, net.bns, false); }
+// running statistics: per BatchNorm [running_mean][running_var] (the same for every network: each uses the first ones)
 static int64_t fm_stat_offset(int b, bool var) {
   int64_t o = 0;
   for (int i = 0; i < b; ++i) o += 2 * kFmBnC[i];
   return o + (var ? kFmBnC[b] : 0);
 }
-// P2 (second operand order): which layers have one, and its size
-static int64_t fm_p2_floats(int l) {
-  if (l == 0) return (int64_t)64 * 32;                                    // conv1: [co][k = tap * 3 + ci, 27 -> 32] for the column form
-  if (l == 12) return (int64_t)32 * 9 * 32;                               // [ci 32][tap][co 16 -> 32]
-  if (l == 13) return (int64_t)16 * 9 * 32;                               // [ci 16][tap][co 3 -> 32]
-  return fm_w_floats(l);
+// P2 (second operand order): its size follows from the layer's kind
+static int64_t fm_p2_floats(const FmNet& net, int l) {
+  const FmLayer& L = net.layer[l];
+  if (L.p2 == FM_P2_NONE) return 0;
+  if (L.p2 == FM_P2_COLUMNS) return (int64_t)64 * 32;                     // conv1: [co][k = tap * 3 + ci, 27 -> 32] for the column form
+  if (L.p2 == FM_P2_REFINE) return (int64_t)L.cin * 9 * 32;               // [ci (unpadded: 32 / 16)][tap][co -> 32]
+  return fm_w_floats(net, l);
 }
-static int64_t fm_p2_offset(int l) {
+static int64_t fm_p2_offset(const FmNet& net, int l) {
   int64_t o = 0;
-  for (int i = 0; i < l; ++i) o += fm_p2_floats(i);
+  for (int i = 0; i < l; ++i) o += fm_p2_floats(net, i);
   return o;
 }
 
@@ -1981,8 +2015,8 @@ static int64_t fm_stat_offset_words(int slot) {
   return o;
 }
 static int64_t fm_fixed_floats() {
-  return fm_p2_offset(kFmLayers)                       // P2
-         + 3 * 2480                                    // BatchNorm batch mean / invstd / mean residual (sum of kFmBnC = 2480)
+  return fm_p2_offset(kFmNet, kFmLayers)               // P2
+         + 3 * kFmBnChannels                           // BatchNorm batch mean / invstd / mean residual
          + 4 * fm_stat_offset_words(kFmStatSlots);     // statistics accumulators (64-bit words) + their per-rank copies
 }
 static int64_t fm_tensor_offset(int64_t n, int t) {
@@ -1998,13 +2032,17 @@ struct FmWs {
   float* t[FMT_COUNT];
   float* loss_partial; float* part; float* slabs;
 };
+// the start of every network's workspace: [P2][batch mean][invstd][mean residual][statistics accumulators]
+static void fm_ws_head(FmWs& w, float* ws, const FmNet& net) {
+  w.p2 = ws;
+  w.bn_mean = ws + fm_p2_offset(net, net.layers);
+  w.bn_invstd = w.bn_mean + kFmBnChannels;
+  w.bn_meanres = w.bn_invstd + kFmBnChannels;
+  w.stat_acc = reinterpret_cast<long long*>(w.bn_meanres + kFmBnChannels);   // 16-byte aligned: every size before it is a multiple of 4 floats
+}
 static FmWs fm_ws(float* ws, int64_t n) {
   FmWs w;
-  w.p2 = ws;
-  w.bn_mean = ws + fm_p2_offset(kFmLayers);
-  w.bn_invstd = w.bn_mean + 2480;
-  w.bn_meanres = w.bn_invstd + 2480;
-  w.stat_acc = reinterpret_cast<long long*>(w.bn_meanres + 2480);       // 16-byte aligned: every size before it is a multiple of 4 floats
+  fm_ws_head(w, ws, kFmNet);
   w.stat_acc_local = w.stat_acc + fm_stat_offset_words(kFmStatSlots);
   for (int i = 0; i < FMT_COUNT; ++i) w.t[i] = ws + fm_tensor_offset(n, i);
   w.loss_partial = ws + fm_tensor_offset(n, FMT_COUNT);
@@ -2019,11 +2057,6 @@ static int fm_stat_clear(hipStream_t st, const FmWs& ws, int first, int last) {
                      sizeof(long long) * (size_t)(fm_stat_offset_words(last) - fm_stat_offset_words(first)), st) != hipSuccess)
     return fail(NDP_E_LAUNCH, "forward model: hipMemsetAsync failed");
   return NDP_OK;
-}
-static int fm_bn_stat_index(int b) {
-  int o = 0;
-  for (int i = 0; i < b; ++i) o += kFmBnC[i];
-  return o;
 }
 
 struct FmView { float* p; int ld; };
@@ -2248,23 +2281,22 @@ static FmEpReq fm_ep_bias(int mode, int slot, FmView y) {
   return r;
 }
 
-// Where BatchNorm b's tensors live: the forward model's flat vectors (fm_bn_at), or those of another network whose
-// BatchNorms are the first ones of kFmBnC (ndp_autoencoder.inc).  sync: where the statistics are summed over the ranks
-// (fm_stat_sync; null: this rank's own).
+// Where BatchNorm b's tensors live in a network's flat vectors.  sync: where the statistics are summed over the ranks
+// (fm_stat_sync; null: this rank's own) -- the forward model's process-wide hook, the autoencoder's per-call one.
 struct FmBnAt {
   const float* gamma; const float* beta; float* running_mean; float* running_var;
   float* d_gamma; float* d_beta; float* d_conv_bias;     // backward outputs (d_conv_bias: the bias of the layer in front)
   const FmStatSync* sync;
 };
-static FmBnAt fm_bn_at(int b, const float* params, float* running, float* grad) {
+static FmBnAt fm_bn_at(const FmNet& net, int b, const float* params, float* running, float* grad, const FmStatSync* sync) {
   FmBnAt at;
-  at.gamma = params + fm_bn_offset(b, false); at.beta = params + fm_bn_offset(b, true);
+  at.gamma = params + fm_bn_offset(net, b, false); at.beta = params + fm_bn_offset(net, b, true);
   at.running_mean = running ? running + fm_stat_offset(b, false) : nullptr;
   at.running_var = running ? running + fm_stat_offset(b, true) : nullptr;
-  at.d_gamma = grad ? grad + fm_bn_offset(b, false) : nullptr;
-  at.d_beta = grad ? grad + fm_bn_offset(b, true) : nullptr;
-  at.d_conv_bias = grad ? grad + fm_param_offset(kFmBnLayer[b], true) : nullptr;
-  at.sync = &g_fm_sync;                                   // (ndp_fm_set_stat_sync)
+  at.d_gamma = grad ? grad + fm_bn_offset(net, b, false) : nullptr;
+  at.d_beta = grad ? grad + fm_bn_offset(net, b, true) : nullptr;
+  at.d_conv_bias = grad ? grad + fm_param_offset(net, kFmBnLayer[b], true) : nullptr;
+  at.sync = sync;
   return at;
 }
 
@@ -2302,7 +2334,7 @@ static int fm_bn_fwd_at(hipStream_t st, int b, FmView raw, int64_t P, FmView des
 }
 static int fm_bn_fwd(hipStream_t st, int b, FmView raw, int64_t P, FmView dest, const float* params, float* running,
                      int training, const FmWs& ws) {
-  return fm_bn_fwd_at(st, b, raw, P, dest, fm_bn_at(b, params, running, nullptr), training, ws);
+  return fm_bn_fwd_at(st, b, raw, P, dest, fm_bn_at(kFmNet, b, params, running, nullptr, &g_fm_sync), training, ws);
 }
 // BatchNorm b + ReLU backward: raw (x) := d loss / d x, from the sums the launch that produced dy accumulated; writes the
 // BatchNorm weight / bias gradients and the gradient of the convolution bias in front of it (layer l: the column sum of
@@ -2330,7 +2362,7 @@ static int fm_bn_bwd_at(hipStream_t st, int b, FmView raw, FmView y, FmView dy, 
 }
 static int fm_bn_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int64_t P, const float* params, float* grad,
                      const FmWs& ws) {
-  return fm_bn_bwd_at(st, b, raw, y, dy, P, fm_bn_at(b, params, nullptr, grad), ws);
+  return fm_bn_bwd_at(st, b, raw, y, dy, P, fm_bn_at(kFmNet, b, params, nullptr, grad, &g_fm_sync), ws);
 }
 
 // deconv6's forward pass, the four parity classes per workgroup (k_fm_deconv32)
@@ -2363,37 +2395,42 @@ static int fm_r1(hipStream_t st, const char* label, bool dgrad, const float* src
   return check_launch(label);
 }
 
-static int fm_pack(hipStream_t st, const float* params, const FmWs& ws) {
+// layer l of `net` becomes the next segment of a k_fm_pack / k_fm_adam_pack launch: a 32 x 32 tile (or 1,024 elements) per workgroup
+static void fm_pack_segment(FmPackArgs& a, const FmNet& net, int l) {
+  const FmLayer& L = net.layer[l];
+  const int i = a.nseg++;
+  a.p1_off[i] = fm_param_offset(net, l, false); a.p2_off[i] = fm_p2_offset(net, l); a.count[i] = fm_p2_floats(net, l);
+  a.cin_[i] = L.cin; a.cout_[i] = L.cout; a.cin_pad_[i] = L.cin_pad; a.cout_pad_[i] = L.cout_pad;
+  a.kind[i] = L.p2;
+  a.block_begin[i + 1] = a.block_begin[i] + (int)((a.count[i] + 1023) / 1024);
+}
+static bool fm_p2_transposes(int p2) {
+  return p2 == FM_P2_CONV_S2 || p2 == FM_P2_CONV6 || p2 == FM_P2_DECONV_S2 || p2 == FM_P2_DECONV1;
+}
+
+// P1 -> P2 of every layer that has a P2, one launch (k_fm_pack)
+static int fm_pack(hipStream_t st, const FmNet& net, const float* params, const FmWs& ws) {
   FmPackArgs a;
-  a.params = params; a.p2_base = ws.p2; a.nseg = 0; a.block_begin[0] = 0;
-  int blocks = 0;
-  for (int l = 0; l < kFmLayers; ++l) {
-    const FmLayer& L = kFm[l];
-    const int i = a.nseg;
-    a.p1_off[i] = fm_param_offset(l, false); a.p2_off[i] = fm_p2_offset(l); a.count[i] = fm_p2_floats(l);
-    a.cin_[i] = L.cin; a.cout_[i] = L.cout; a.cin_pad_[i] = L.cin_pad; a.cout_pad_[i] = L.cout_pad;
-    if (l == 0) a.kind[i] = 5;
-    else if (l == 5) a.kind[i] = 2;
-    else if (l == 6) a.kind[i] = 4;
-    else if (l >= 12) { a.kind[i] = 1; a.cin_[i] = l == 12 ? 32 : 16; }
-    else a.kind[i] = L.kind == FM_CONV ? 0 : 3;
-    blocks += (int)((a.count[i] + 1023) / 1024);                      // a 32 x 32 tile (or 1024 elements) per workgroup
-    a.block_begin[++a.nseg] = blocks;
-  }
+  memset(&a, 0, sizeof(a));
+  a.params = params; a.p2_base = ws.p2;
+  for (int l = 0; l < net.layers; ++l)
+    if (net.layer[l].p2 != FM_P2_NONE) fm_pack_segment(a, net, l);
   KTimer kt("k_fm_pack", st);
-  hipLaunchKernelGGL(k_fm_pack, dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(k_fm_pack, dim3((unsigned)a.block_begin[a.nseg]), dim3(kThreads), 0, st, a);
   return check_launch("k_fm_pack");
 }
 
-// Adam over the flat parameter buffer + the P2 rebuild, one launch (k_fm_adam_pack); `step` was advanced by the caller
-static int fm_adam_pack(hipStream_t st, float* params, const float* grad, float* exp_avg, float* exp_avg_sq, const int32_t* step,
-                        float beta1, float beta2, float eps, const FmWs& ws) {
+// Adam over the flat parameter buffer + the P2 rebuild, one launch (k_fm_adam_pack); `step` was advanced by the caller.
+// Tiles: the transposing layers.  Plain elements: everything between and after their weights -- among them the refinement
+// layers' weights (FM_P2_REFINE: at most the kernel's two) and conv1's (FM_P2_COLUMNS), which store their P2 position too.
+static int fm_adam_pack(hipStream_t st, const FmNet& net, float* params, const float* grad, float* exp_avg, float* exp_avg_sq,
+                        const int32_t* step, float beta1, float beta2, float eps, const FmWs& ws) {
   FmAdamPackArgs a;
   memset(&a, 0, sizeof(a));
   a.params = params; a.grad = grad; a.exp_avg = exp_avg; a.exp_avg_sq = exp_avg_sq; a.step = step;
   a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.pk.params = params; a.pk.p2_base = ws.p2; a.pk.nseg = 0; a.pk.block_begin[0] = 0;
-  int blocks = 0;
+  a.pk.params = params; a.pk.p2_base = ws.p2;
+  a.r_cin_pad[0] = a.r_cin_pad[1] = 1;                                 // (an unused refinement slot: count 0, divisor 1)
   int64_t covered = 0;                                                 // end of the parameters handled so far
   auto plain = [&](int64_t off, int64_t count) {
     if (count <= 0) return;
@@ -2402,27 +2439,25 @@ static int fm_adam_pack(hipStream_t st, float* params, const float* grad, float*
     a.plain_begin[i + 1] = a.plain_begin[i] + (int)((count + 1023) / 1024);
     ++a.nplain;
   };
-  for (int l = 1; l < 12; ++l) {                                       // conv2 .. deconv6: transposing segments
-    const FmLayer& L = kFm[l];
-    const int i = a.pk.nseg;
-    a.pk.p1_off[i] = fm_param_offset(l, false); a.pk.p2_off[i] = fm_p2_offset(l); a.pk.count[i] = fm_p2_floats(l);
-    a.pk.cin_[i] = L.cin; a.pk.cout_[i] = L.cout; a.pk.cin_pad_[i] = L.cin_pad; a.pk.cout_pad_[i] = L.cout_pad;
-    a.pk.kind[i] = l == 5 ? 2 : (l == 6 ? 4 : (L.kind == FM_CONV ? 0 : 3));
-    blocks += (int)(a.pk.count[i] / 1024);                             // (fm_p2_floats == fm_w_floats, a multiple of 1,024)
-    a.pk.block_begin[++a.pk.nseg] = blocks;
-    plain(covered, fm_param_offset(l, false) - covered);               // what lies before this layer's weights
-    covered = fm_param_offset(l, true);
+  int r = 0;
+  for (int l = 0; l < net.layers; ++l) {
+    const FmLayer& L = net.layer[l];
+    if (fm_p2_transposes(L.p2)) {                                      // (whole tiles: its P2 is its P1 size, a multiple of 1,024)
+      fm_pack_segment(a.pk, net, l);
+      plain(covered, fm_param_offset(net, l, false) - covered);        // what lies before this layer's weights
+      covered = fm_param_offset(net, l, true);
+    } else if (L.p2 == FM_P2_REFINE) {
+      a.r_off[r] = fm_param_offset(net, l, false); a.r_count[r] = fm_w_floats(net, l); a.r_p2[r] = fm_p2_offset(net, l);
+      a.r_cin_pad[r] = L.cin_pad; a.r_cin[r] = L.cin;
+      ++r;
+    } else if (L.p2 == FM_P2_COLUMNS) {                                // (conv1, layer 0: the kernel takes its P1 offset as 0)
+      a.c1_count = fm_w_floats(net, l); a.c1_p2 = fm_p2_offset(net, l);
+    }
   }
-  plain(covered, fm_param_floats() - covered);                         // deconv6's bias, the refinement layers, BatchNorm
-  a.tile_blocks = blocks;
-  for (int r = 0; r < 2; ++r) {
-    const int l = 12 + r;
-    a.r_off[r] = fm_param_offset(l, false); a.r_count[r] = fm_w_floats(l); a.r_p2[r] = fm_p2_offset(l);
-    a.r_cin_pad[r] = kFm[l].cin_pad; a.r_cin[r] = l == 12 ? 32 : 16;
-  }
-  a.c1_count = fm_w_floats(0); a.c1_p2 = fm_p2_offset(0);              // (fm_param_offset(0, false) == 0)
+  plain(covered, fm_param_floats(net) - covered);                      // the last bias, the layers without tiles, BatchNorm
+  a.tile_blocks = a.pk.block_begin[a.pk.nseg];
   KTimer kt("k_fm_adam_pack", st);
-  hipLaunchKernelGGL(k_fm_adam_pack, dim3((unsigned)(blocks + a.plain_begin[a.nplain])), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(k_fm_adam_pack, dim3((unsigned)(a.tile_blocks + a.plain_begin[a.nplain])), dim3(kThreads), 0, st, a);
   return check_launch("k_fm_adam_pack");
 }
 
@@ -2431,9 +2466,9 @@ static int fm_forward(hipStream_t st, const float* params, float* running, const
                       int64_t n, int training, const FmWs& ws, bool clear_backward_too = false, const FmLossArgs* with_loss = nullptr) {
   fm_attrs();
   const float* P = params;
-  auto W1 = [&](int l) { return P + fm_param_offset(l, false); };
-  auto B = [&](int l) { return P + fm_param_offset(l, true); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(l)); };
+  auto W1 = [&](int l) { return P + fm_param_offset(kFmNet, l, false); };
+  auto B = [&](int l) { return P + fm_param_offset(kFmNet, l, true); };
+  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kFmNet, l)); };
   float* const* t = ws.t;
   const int64_t npix = n * 16384;
   // (padded channels must hold finite values where they meet zero weights: k_fm_gemm's zero_to; the refinement stage's
@@ -2520,7 +2555,7 @@ static int fm_loss(hipStream_t st, const void* cur, const void* fut, bool u8, in
   if (rc || (training != 1 && training != 3)) return rc;
   hipLaunchKernelGGL(k_fm_loss_final, dim3(1), dim3(kThreads), 0, st, (const float*)ws.loss_partial, nblocks,
                      1.0 / (3.0 * (double)a.npix), training == 1 ? loss : (float*)nullptr,
-                     training == 1 ? loss_sum : (float*)nullptr, grad + fm_param_offset(13, true));
+                     training == 1 ? loss_sum : (float*)nullptr, grad + fm_param_offset(kFmNet, 13, true));
   return check_launch("k_fm_loss_final");
 }
 
@@ -2548,37 +2583,31 @@ static FmSide* fm_side() {
   return sd->ok ? sd : nullptr;
 }
 
-// Gradient buckets for a data-parallel driver (SURVEY.md section 8e / 8f-4: "RCCL all-reduce ... overlapped with backward"):
-// ranges of the flat gradient in the order in which the backward pass completes them.  The weight gradients are produced
-// last layer first, so the range of layers 9..13 is final while the data-gradient chain is still at deconv3; one event per
-// bucket is recorded on the stream that wrote its last byte, and ndp_fm_bucket_wait makes the caller's communication
-// stream wait for it: the all-reduce of a bucket runs beside the rest of the backward pass.
-//   bucket 0  layers 9..13 (deconv4..6, refinement)      4  layer 4 (conv5)
-//          1  layer 8 (deconv3)                          5  layers 0..3 (conv1..4)
-//          2  layer 7 (deconv2: half of all parameters)  6  the BatchNorm weights and biases
-//          3  layers 5, 6 (conv6, deconv1)
-constexpr int kFmBuckets = 7;
-static const int kFmBucketFirst[kFmBuckets] = {9, 8, 7, 5, 4, 0, -1};   // first layer of the range (-1: BatchNorm parameters)
-static const int kFmBucketEnd[kFmBuckets] = {14, 9, 8, 7, 5, 4, -1};    // one past its last layer
-static void fm_bucket_range(int b, int64_t* offset, int64_t* count) {
-  if (kFmBucketFirst[b] < 0) {
-    *offset = fm_bn_offset(0, false);
-    *count = fm_param_floats() - *offset;
+// Gradient bucket b of a network (the tables: beside its layers) as a range of the flat gradient
+static void fm_bucket_range(const FmNet& net, int b, int64_t* offset, int64_t* count) {
+  if (net.bucket_first[b] < 0) {
+    *offset = fm_bn_offset(net, 0, false);
+    *count = fm_param_floats(net) - *offset;
   } else {
-    *offset = fm_param_offset(kFmBucketFirst[b], false);
-    *count = fm_param_offset(kFmBucketEnd[b], false) - *offset;
+    *offset = fm_param_offset(net, net.bucket_first[b], false);
+    *count = fm_param_offset(net, net.bucket_end[b], false) - *offset;
   }
 }
-struct FmBucketEvents { hipEvent_t ev[kFmBuckets]; bool ok; };
-static FmBucketEvents g_fm_buckets[kMaxDevices];
-static std::once_flag g_fm_buckets_once[kMaxDevices];
-static FmBucketEvents* fm_bucket_events() {
+// One event per bucket, per device and network, created on first use.  `recorded`: set once a call has recorded all of
+// them (the autoencoder's ndp_ae_bucket_wait refuses before; the forward model does not look at it).
+constexpr int kFmMaxBuckets = 8;
+struct FmBucketEvents { hipEvent_t ev[kFmMaxBuckets]; bool ok; std::atomic<bool> recorded; };
+struct FmBucketEventSet { FmBucketEvents dev[kMaxDevices]; std::once_flag once[kMaxDevices]; };
+static FmBucketEventSet g_fm_buckets;
+static FmBucketEvents* fm_bucket_events(FmBucketEventSet& set, const FmNet& net) {
+  static_assert(kFmBuckets <= kFmMaxBuckets, "FmBucketEvents::ev");
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-  FmBucketEvents* be = &g_fm_buckets[dev];
-  std::call_once(g_fm_buckets_once[dev], [be] {
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
+  FmBucketEvents* be = &set.dev[dev];
+  const int n = net.buckets;
+  std::call_once(set.once[dev], [be, n] {
     be->ok = true;
-    for (int i = 0; i < kFmBuckets; ++i) be->ok = be->ok && hipEventCreateWithFlags(&be->ev[i], hipEventDisableTiming) == hipSuccess;
+    for (int i = 0; i < n; ++i) be->ok = be->ok && hipEventCreateWithFlags(&be->ev[i], hipEventDisableTiming) == hipSuccess;
   });
   return be->ok ? be : nullptr;
 }
@@ -2587,7 +2616,7 @@ static FmBucketEvents* fm_bucket_events() {
 static int fm_backward(hipStream_t st, const float* params, int64_t n, float* grad, const FmWs& ws, bool cleared = false) {
   FmSide* side = fm_side();
   hipStream_t sw = side ? side->stream : st;                        // where the weight gradients go
-  FmBucketEvents* buckets = fm_bucket_events();
+  FmBucketEvents* buckets = fm_bucket_events(g_fm_buckets, kFmNet);
   // everything launched on `st` so far is complete for what the side stream launches after this
   auto fork = [&]() {
     if (side) {
@@ -2596,9 +2625,9 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
     }
   };
   const float* P = params;
-  auto W1 = [&](int l) { return P + fm_param_offset(l, false); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(l)); };
-  auto GW = [&](int l) { return grad + fm_param_offset(l, false); };
+  auto W1 = [&](int l) { return P + fm_param_offset(kFmNet, l, false); };
+  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kFmNet, l)); };
+  auto GW = [&](int l) { return grad + fm_param_offset(kFmNet, l, false); };
   float* const* t = ws.t;
   const int64_t npix = n * 16384;
   int rc;
@@ -2618,7 +2647,7 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
     FmBiasFinishArgs bf;
     memset(&bf, 0, sizeof(bf));
     bf.fin = fm_fin(20 + i, 1, 1, ws);
-    bf.fin.out1 = grad + fm_param_offset(layer[i], true);
+    bf.fin.out1 = grad + fm_param_offset(kFmNet, layer[i], true);
     bf.cols = fm_stat_cols(20 + i);
     KTimer kt("k_fm_bias_finish", sw);
     hipLaunchKernelGGL(k_fm_bias_finish, dim3(1), dim3(kThreads), 0, sw, bf);
@@ -2749,29 +2778,33 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
 #undef FM_TRY
 }
 
+// the body of ndp_fm_layout / ndp_ae_layout (include/ndp.h); `who`: the entry point, for its error strings
+static int fm_layout(const FmNet& net, const char* who, int what, int index, int64_t* offset, int64_t* dims) {
+  NDP_CHECK_ARG(offset && dims, "%s: null pointer", who);
+  if (what == 0 || what == 1) {
+    NDP_CHECK_ARG(index >= 0 && index < net.layers, "%s: layer index out of range", who);
+    const FmLayer& L = net.layer[index];
+    *offset = fm_param_offset(net, index, what == 1);
+    dims[0] = what == 0 ? fm_w_rows(net, index) : L.cout_pad; dims[1] = what == 0 ? L.ksz * L.ksz : 1;
+    dims[2] = what == 0 ? fm_w_cols(net, index) : 1; dims[3] = L.kind; dims[4] = L.cin; dims[5] = L.cout;
+    return NDP_OK;
+  }
+  NDP_CHECK_ARG(what >= 2 && what <= 5 && index >= 0 && index < net.bns, "%s: bad BatchNorm query", who);
+  *offset = what < 4 ? fm_bn_offset(net, index, what == 3) : fm_stat_offset(index, what == 5);
+  dims[0] = kFmBnC[index]; dims[1] = dims[2] = 1; dims[3] = kFmBnLayer[index]; dims[4] = dims[5] = kFmBnC[index];
+  return NDP_OK;
+}
+
 }  // namespace ndp
 
 extern "C" {
 
-int64_t ndp_fm_param_floats(void) { return ndp::fm_param_floats(); }
+int64_t ndp_fm_param_floats(void) { return ndp::fm_param_floats(ndp::kFmNet); }
 int64_t ndp_fm_stat_floats(void) { return ndp::fm_stat_offset(ndp::kFmBns, false); }
 int64_t ndp_fm_workspace_floats(int64_t n_images) { return n_images < 1 ? 0 : ndp::fm_ws_floats(n_images); }
 
 int ndp_fm_layout(int what, int index, int64_t* offset, int64_t* dims) {
-  using namespace ndp;
-  NDP_CHECK_ARG(offset && dims, "ndp_fm_layout: null pointer");
-  if (what == 0 || what == 1) {
-    NDP_CHECK_ARG(index >= 0 && index < kFmLayers, "ndp_fm_layout: layer index out of range");
-    const FmLayer& L = kFm[index];
-    *offset = fm_param_offset(index, what == 1);
-    dims[0] = what == 0 ? fm_w_rows(index) : L.cout_pad; dims[1] = what == 0 ? L.ksz * L.ksz : 1;
-    dims[2] = what == 0 ? fm_w_cols(index) : 1; dims[3] = L.kind; dims[4] = L.cin; dims[5] = L.cout;
-    return NDP_OK;
-  }
-  NDP_CHECK_ARG(what >= 2 && what <= 5 && index >= 0 && index < kFmBns, "ndp_fm_layout: bad BatchNorm query");
-  *offset = what < 4 ? fm_bn_offset(index, what == 3) : fm_stat_offset(index, what == 5);
-  dims[0] = kFmBnC[index]; dims[1] = dims[2] = 1; dims[3] = kFmBnLayer[index]; dims[4] = dims[5] = kFmBnC[index];
-  return NDP_OK;
+  return ndp::fm_layout(ndp::kFmNet, "ndp_fm_layout", what, index, offset, dims);
 }
 
 int64_t ndp_fm_workspace_offset(int64_t n_images, int tensor) {
@@ -2782,7 +2815,7 @@ int64_t ndp_fm_workspace_offset(int64_t n_images, int tensor) {
 int ndp_fm_pack_params(const float* params, float* workspace, void* stream) {
   using namespace ndp;
   NDP_CHECK_ARG(params && workspace && aligned16(params) && aligned16(workspace), "ndp_fm_pack_params: bad arguments");
-  return fm_pack((hipStream_t)stream, params, fm_ws(workspace, 1));
+  return fm_pack((hipStream_t)stream, kFmNet, params, fm_ws(workspace, 1));
 }
 
 static int fm_forward_any(const float* params, float* running_stats, const void* state_cur, bool u8, const float* actions,
@@ -2857,14 +2890,14 @@ int ndp_fm_set_stat_sync(ndp_fm_stat_sync_fn fn, void* ctx, int world) {
 int ndp_fm_grad_buckets(int64_t* offsets, int64_t* counts, int capacity) {
   using namespace ndp;
   NDP_CHECK_ARG(offsets && counts && capacity >= kFmBuckets, "ndp_fm_grad_buckets: need room for 7 buckets");
-  for (int b = 0; b < kFmBuckets; ++b) fm_bucket_range(b, offsets + b, counts + b);
+  for (int b = 0; b < kFmBuckets; ++b) fm_bucket_range(kFmNet, b, offsets + b, counts + b);
   return kFmBuckets;
 }
 
 int ndp_fm_bucket_wait(int bucket, void* stream) {
   using namespace ndp;
   NDP_CHECK_ARG(bucket >= 0 && bucket < kFmBuckets, "ndp_fm_bucket_wait: bucket out of range");
-  FmBucketEvents* be = fm_bucket_events();
+  FmBucketEvents* be = fm_bucket_events(g_fm_buckets, kFmNet);
   if (!be) return fail(NDP_E_LAUNCH, "ndp_fm_bucket_wait: could not create the bucket events");
   if (hipStreamWaitEvent((hipStream_t)stream, be->ev[bucket], 0) != hipSuccess)
     return fail(NDP_E_LAUNCH, "ndp_fm_bucket_wait: hipStreamWaitEvent failed");
@@ -2897,7 +2930,7 @@ int ndp_fm_apply_adam(float* params, const float* grad, float* exp_avg, float* e
                 "ndp_fm_apply_adam: buffers must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_adam_advance, dim3(1), dim3(1), 0, st, step_count, lr, beta1, beta2);
-  return fm_adam_pack(st, params, grad, exp_avg, exp_avg_sq, step_count, beta1, beta2, eps, fm_ws(workspace, 1));
+  return fm_adam_pack(st, kFmNet, params, grad, exp_avg, exp_avg_sq, step_count, beta1, beta2, eps, fm_ws(workspace, 1));
 }
 
 }  // extern "C"

@@ -18,7 +18,60 @@ from . import _capi
 from .models import forward_encoder as FE
 
 
-class ForwardModelTrainer:
+class FlatTrainer:
+    """What the trainers of this family share: the flat vectors the kernels read and write, the Adam call, the
+    reduce-then-apply tail of a step and the named views.  A subclass names its entry points, packs its modules,
+    checks its inputs and calls its own `grads()`."""
+    _WORKSPACE_FN = _APPLY_FN = None                     # "ndp_fm_workspace_floats", "ndp_fm_apply_adam"
+    _grad_buckets = None                                 # _capi.fm_grad_buckets
+
+    def _allocate(self, packed, lr, betas, eps):
+        """Buffers of a trainer on self.device for at most self.batch images; packed: (params, running_stats)."""
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.params, self.stats = packed
+        self.grad = torch.zeros_like(self.params)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
+        self.step_word = torch.zeros(4, dtype=torch.int32, device=self.device)      # Adam state word (include/ndp.h)
+        self.loss = torch.zeros(1, **f32)
+        self.loss_sum = torch.zeros(1, **f32)
+        self.workspace = torch.empty(getattr(self.lib, self._WORKSPACE_FN)(self.batch), **f32)
+        self.steps = 0                                                               # Adam steps
+
+    def apply(self):
+        """optimizer.step()"""
+        p = _capi.ptr
+        with torch.cuda.device(self.device):
+            _capi.check(getattr(self.lib, self._APPLY_FN)(p(self.params), p(self.grad), p(self.exp_avg), p(self.exp_avg_sq),
+                                                          p(self.step_word), self.lr, self.betas[0], self.betas[1], self.eps,
+                                                          p(self.workspace), _capi.stream_ptr(self.device)), self._APPLY_FN)
+        self.steps += 1
+
+    def _reduce_and_apply(self):
+        """The rest of a step after grads(): the data-parallel reduction of the gradient (if any), then Adam."""
+        if self.bucket_reduce is not None:
+            self.bucket_reduce(self.grad, self.device)
+        elif self.reduce_fn is not None:
+            self.reduce_fn(self.grad)
+        self.apply()
+        return self.loss
+
+    def gradient_buckets(self):
+        """[(offset, count)] of the flat gradient, in the order the backward pass completes them."""
+        return self._grad_buckets()
+
+    def named_gradients(self):
+        """'encoder.conv1.weight' ... -> gradient in the modules' own tensor shapes (tests, inspection)."""
+        return self._unpack(self.grad)
+
+    def named_parameters(self):
+        return self._unpack(self.params)
+
+
+class ForwardModelTrainer(FlatTrainer):
+    _WORKSPACE_FN, _APPLY_FN = "ndp_fm_workspace_floats", "ndp_fm_apply_adam"
+    _grad_buckets = staticmethod(_capi.fm_grad_buckets)
+
     def __init__(self, model: FE.ForwardAutoencoder, batch: int, lr: float = 2e-4, betas=(0.5, 0.999), eps: float = 1e-8,
                  reduce_fn=None, keep_residual: bool = False, bucket_reduce=None, sync_batchnorm_world: int = 1):
         self.lib = _capi.load()
@@ -27,20 +80,11 @@ class ForwardModelTrainer:
         if dev.type != "cuda":
             raise _capi.NdpError("ForwardModelTrainer needs the model on a ROCm GPU (got %s); there is no CPU path" % dev)
         self.device, self.batch = dev, int(batch)
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         if reduce_fn is not None and bucket_reduce is not None:
             raise ValueError("give either reduce_fn (one collective) or bucket_reduce (per-bucket, overlapped)")
         self.reduce_fn, self.bucket_reduce = reduce_fn, bucket_reduce
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.params, self.stats = FE.pack_module(model, dev)
-        self.grad = torch.zeros_like(self.params)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.step_word = torch.zeros(4, dtype=torch.int32, device=dev)      # Adam state word (include/ndp.h)
-        self.loss = torch.zeros(1, **f32)
-        self.loss_sum = torch.zeros(1, **f32)
-        self.resid = torch.zeros(self.batch, 3, 128, 128, **f32) if keep_residual else None
-        self.workspace = torch.empty(self.lib.ndp_fm_workspace_floats(self.batch), **f32)
-        self.steps = 0
+        self._allocate(FE.pack_module(model, dev), lr, betas, eps)
+        self.resid = torch.zeros(self.batch, 3, 128, 128, dtype=torch.float32, device=dev) if keep_residual else None
         # BatchNorm statistics over all ranks' images (dp.CrossRankBatchNorm): W ranks x B / W images = one process x B
         self.stat_sync = None
         if int(sync_batchnorm_world) > 1:
@@ -78,34 +122,16 @@ class ForwardModelTrainer:
             self.stat_sync.check()
         return self.loss
 
-    def apply(self):
-        """optimizer.step()"""
-        p = _capi.ptr
-        with torch.cuda.device(self.device):
-            _capi.check(self.lib.ndp_fm_apply_adam(p(self.params), p(self.grad), p(self.exp_avg), p(self.exp_avg_sq),
-                                                   p(self.step_word), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                   p(self.workspace), _capi.stream_ptr(self.device)), "ndp_fm_apply_adam")
-        self.steps += 1
-
     def step(self, state_cur, state_fut, actions):
         """The loop body of train_forward_model.py:98-112 for one frame pair; returns the loss (device scalar)."""
         self.grads(state_cur, state_fut, actions)
-        if self.bucket_reduce is not None:
-            self.bucket_reduce(self.grad, self.device)
-        elif self.reduce_fn is not None:
-            self.reduce_fn(self.grad)
-        self.apply()
-        return self.loss
+        return self._reduce_and_apply()
 
     def close(self):
         """Remove the process-wide cross-rank statistics hook this trainer installed (if any)."""
         if self.stat_sync is not None:
             self.stat_sync.close()
             self.stat_sync = None
-
-    def gradient_buckets(self):
-        """[(offset, count)] of the flat gradient, in the order the backward pass completes them."""
-        return _capi.fm_grad_buckets()
 
     # intermediate maps of the last grads() call (tests, inspection): name -> (workspace tensor index, side, channels kept)
     _MAPS = {"feat1": (1, 64, 128, 64, 128), "up5": (1, 64, 128, 0, 64), "feat2": (2, 32, 256, 128, 256), "up4": (2, 32, 256, 0, 128),
@@ -131,9 +157,5 @@ class ForwardModelTrainer:
         FE.unpack_into_module(self.model, self.params, self.stats, batches_tracked=self.steps)
         return self.model
 
-    def named_gradients(self):
-        """name -> gradient in the module's own tensor shapes (tests, inspection)."""
-        return FE.unpack_vector(self.grad, self.model)
-
-    def named_parameters(self):
-        return FE.unpack_vector(self.params, self.model)
+    def _unpack(self, vec):
+        return FE.unpack_vector(vec, self.model)

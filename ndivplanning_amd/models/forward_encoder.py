@@ -18,13 +18,13 @@ train is `ndivplanning_amd.forward_trainer.ForwardModelTrainer`, which owns the 
 and runs forward, loss, backward and Adam in HIP without repacking.  There is no CPU path and no gradient with respect
 to the images or actions (the reference never asks for one): both raise.  `Encoder` / `Decoder` called on their own
 (nobody in the reference does) keep PyTorch's operators."""
-import ctypes
+from functools import partial
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import _capi
+from .. import _capi, flat_params
 
 ENC_CHANNELS = (3, 64, 128, 256, 512, 1024)
 LAYER_NAMES = ("encoder.conv1", "encoder.conv2", "encoder.conv3", "encoder.conv4", "encoder.conv5", "encoder.conv6",
@@ -97,98 +97,30 @@ class Decoder(nn.Module):
         return torch.tanh(self.conv_refine_2(up))
 
 
-# ---------------------------------------------------------------- flat parameter vector <-> module
+# ---------------------------------------------------------------- flat parameter vector <-> module (flat_params.py)
+_FLAT = flat_params.FlatParams("ndp_fm_layout", "ndp_fm_param_floats", "ndp_fm_stat_floats", LAYER_NAMES, BN_NAMES)
+to_kernel_layout, from_kernel_layout = flat_params.to_kernel_layout, flat_params.from_kernel_layout
+_module_tensor = flat_params.module_at
+
+
 def _layout(lib, what, index):
-    off, dims = ctypes.c_int64(), (ctypes.c_int64 * 6)()
-    _capi.check(lib.ndp_fm_layout(what, index, ctypes.byref(off), dims), "ndp_fm_layout")
-    return off.value, list(dims)
-
-
-def _module_tensor(model, dotted):
-    obj = model
-    for part in dotted.split("."):
-        obj = getattr(obj, part)
-    return obj
-
-
-def to_kernel_layout(weight, rows, cols):
-    """Conv2d [co][ci][kh][kw] / ConvTranspose2d [ci][co][kh][kw] -> [dim0 padded to rows][kh][kw][dim1 padded to cols]
-    (include/ndp.h)."""
-    w = weight.detach().float().permute(0, 2, 3, 1)
-    out = torch.zeros(rows, w.shape[1], w.shape[2], cols, dtype=torch.float32, device=w.device)
-    out[: w.shape[0], :, :, : w.shape[3]] = w
-    return out
-
-
-def from_kernel_layout(flat_w, rows, taps, cols, shape):
-    """Inverse of to_kernel_layout: back to the module's weight shape."""
-    k = int(round(taps ** 0.5))
-    w = flat_w.view(rows, k, k, cols)[: shape[0], :, :, : shape[1]]
-    return w.permute(0, 3, 1, 2).contiguous()
+    return _FLAT.layout(what, index)
 
 
 def pack_module(model, device=None):
     """(params, running_stats): the flat vectors the kernels read, from a ForwardAutoencoder (layout: include/ndp.h)."""
-    lib = _capi.load()
-    device = device if device is not None else next(model.parameters()).device
-    params = torch.zeros(lib.ndp_fm_param_floats(), dtype=torch.float32, device=device)
-    stats = torch.zeros(lib.ndp_fm_stat_floats(), dtype=torch.float32, device=device)
-    with torch.no_grad():
-        for i, name in enumerate(LAYER_NAMES):
-            mod = _module_tensor(model, name)
-            off, d = _layout(lib, 0, i)
-            n = d[0] * d[1] * d[2]
-            params[off:off + n] = to_kernel_layout(mod.weight, d[0], d[2]).to(device).reshape(-1)
-            boff, bd = _layout(lib, 1, i)
-            params[boff:boff + mod.bias.numel()] = mod.bias.detach().float().to(device)
-        for i, name in enumerate(BN_NAMES):
-            bn = _module_tensor(model, name)
-            c = bn.weight.numel()
-            params[_layout(lib, 2, i)[0]:][:c] = bn.weight.detach().float().to(device)
-            params[_layout(lib, 3, i)[0]:][:c] = bn.bias.detach().float().to(device)
-            stats[_layout(lib, 4, i)[0]:][:c] = bn.running_mean.detach().float().to(device)
-            stats[_layout(lib, 5, i)[0]:][:c] = bn.running_var.detach().float().to(device)
-    return params, stats
+    return _FLAT.pack(partial(_module_tensor, model), device if device is not None else next(model.parameters()).device)
 
 
 def unpack_vector(vec, model=None):
     """name -> tensor in the module's own shapes, from a flat vector in the parameters' layout (parameters, gradients or
     Adam moments)."""
-    lib = _capi.load()
-    out = {}
-    shapes = {}
-    ref = model if model is not None else ForwardAutoencoder()
-    for name in LAYER_NAMES:
-        shapes[name] = tuple(_module_tensor(ref, name).weight.shape)
-    for i, name in enumerate(LAYER_NAMES):
-        off, d = _layout(lib, 0, i)
-        n = d[0] * d[1] * d[2]
-        out[name + ".weight"] = from_kernel_layout(vec[off:off + n], d[0], d[1], d[2], shapes[name])
-        boff, _ = _layout(lib, 1, i)
-        out[name + ".bias"] = vec[boff:boff + d[5]].clone()
-    for i, name in enumerate(BN_NAMES):
-        off, d = _layout(lib, 2, i)
-        out[name + ".weight"] = vec[off:off + d[0]].clone()
-        off, d = _layout(lib, 3, i)
-        out[name + ".bias"] = vec[off:off + d[0]].clone()
-    return out
+    return _FLAT.unpack_vector(vec, partial(_module_tensor, model if model is not None else ForwardAutoencoder()))
 
 
 def unpack_into_module(model, params, stats=None, batches_tracked=None):
     """Write the flat vectors back into the module's parameters and buffers (after HIP training)."""
-    lib = _capi.load()
-    tensors = unpack_vector(params, model)
-    with torch.no_grad():
-        for key, value in tensors.items():
-            _module_tensor(model, key).copy_(value)
-        if stats is not None:
-            for i, name in enumerate(BN_NAMES):
-                bn = _module_tensor(model, name)
-                c = bn.weight.numel()
-                bn.running_mean.copy_(stats[_layout(lib, 4, i)[0]:][:c])
-                bn.running_var.copy_(stats[_layout(lib, 5, i)[0]:][:c])
-                if batches_tracked is not None:
-                    bn.num_batches_tracked.fill_(int(batches_tracked))
+    _FLAT.unpack_into(partial(_module_tensor, model), params, stats, batches_tracked)
 
 
 class _TrainingForward(torch.autograd.Function):

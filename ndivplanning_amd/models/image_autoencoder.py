@@ -12,9 +12,14 @@ the weights).  Training both modules (train_autoencoder.py) goes through `ndivpl
 (`ndp_ae_train_grads` / `ndp_ae_apply_adam`, csrc/ndp_autoencoder.inc), which owns the flat vectors `pack_autoencoder`
 builds.  A forward in training mode or with gradients, and every `Decoder.forward`, keep PyTorch's operators so that the
 classes still behave like nn.Modules there."""
+from functools import partial
+from types import SimpleNamespace
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+from .. import flat_params
 
 
 def normal_init(m, mean, std):
@@ -108,93 +113,35 @@ AE_BNS = (("encoder", "conv1_bn"), ("encoder", "conv2_bn"), ("encoder", "conv3_b
           ("decoder", "deconv2_bn"), ("decoder", "deconv3_bn"), ("decoder", "deconv4_bn"), ("decoder", "deconv5_bn"))
 
 
+_FLAT = flat_params.FlatParams("ndp_ae_layout", "ndp_ae_param_floats", "ndp_ae_stat_floats",
+                               [".".join(x) for x in AE_LAYERS], [".".join(x) for x in AE_BNS])
+
+
+def _resolve(encoder, decoder):
+    return partial(flat_params.module_at, SimpleNamespace(encoder=encoder, decoder=decoder))
+
+
 def ae_layout(lib, what, index):
-    import ctypes
-    from .. import _capi
-    off, dims = ctypes.c_int64(), (ctypes.c_int64 * 6)()
-    _capi.check(lib.ndp_ae_layout(what, index, ctypes.byref(off), dims), "ndp_ae_layout")
-    return off.value, list(dims)
-
-
-def _to_kernel_layout(weight, rows, cols):
-    w = weight.detach().float().permute(0, 2, 3, 1)                    # [dim0][kh][kw][dim1]
-    out = torch.zeros(rows, w.shape[1], w.shape[2], cols, dtype=torch.float32, device=w.device)
-    out[: w.shape[0], :, :, : w.shape[3]] = w
-    return out
-
-
-def _from_kernel_layout(flat_w, rows, taps, cols, shape):
-    k = int(round(taps ** 0.5))
-    w = flat_w.view(rows, k, k, cols)[: shape[0], :, :, : shape[1]]
-    return w.permute(0, 3, 1, 2).contiguous()
+    return _FLAT.layout(what, index)
 
 
 def pack_autoencoder(encoder, decoder, device=None):
     """(params, running_stats): the flat vectors ndp_ae_train_grads reads, from an Encoder and a Decoder (layout:
     include/ndp.h, image autoencoder).  conv4_bn / conv5_bn are not part of them."""
-    from .. import _capi
-    lib = _capi.load()
-    mods = {"encoder": encoder, "decoder": decoder}
-    device = device if device is not None else next(encoder.parameters()).device
-    params = torch.zeros(lib.ndp_ae_param_floats(), dtype=torch.float32, device=device)
-    stats = torch.zeros(lib.ndp_ae_stat_floats(), dtype=torch.float32, device=device)
-    with torch.no_grad():
-        for i, (m, name) in enumerate(AE_LAYERS):
-            mod = getattr(mods[m], name)
-            off, d = ae_layout(lib, 0, i)
-            params[off:off + d[0] * d[1] * d[2]] = _to_kernel_layout(mod.weight, d[0], d[2]).to(device).reshape(-1)
-            boff, _ = ae_layout(lib, 1, i)
-            params[boff:boff + mod.bias.numel()] = mod.bias.detach().float().to(device)
-        for i, (m, name) in enumerate(AE_BNS):
-            bn = getattr(mods[m], name)
-            c = bn.weight.numel()
-            params[ae_layout(lib, 2, i)[0]:][:c] = bn.weight.detach().float().to(device)
-            params[ae_layout(lib, 3, i)[0]:][:c] = bn.bias.detach().float().to(device)
-            stats[ae_layout(lib, 4, i)[0]:][:c] = bn.running_mean.detach().float().to(device)
-            stats[ae_layout(lib, 5, i)[0]:][:c] = bn.running_var.detach().float().to(device)
-    return params, stats
+    return _FLAT.pack(_resolve(encoder, decoder), device if device is not None else next(encoder.parameters()).device)
 
 
 def unpack_autoencoder_vector(vec, encoder=None, decoder=None):
     """'encoder.conv1.weight' ... -> tensor in the modules' own shapes, from a flat vector in the parameters' layout
     (parameters, gradients or Adam moments)."""
-    from .. import _capi
-    lib = _capi.load()
-    mods = {"encoder": encoder if encoder is not None else Encoder(), "decoder": decoder if decoder is not None else Decoder()}
-    out = {}
-    for i, (m, name) in enumerate(AE_LAYERS):
-        shape = tuple(getattr(mods[m], name).weight.shape)
-        off, d = ae_layout(lib, 0, i)
-        out["%s.%s.weight" % (m, name)] = _from_kernel_layout(vec[off:off + d[0] * d[1] * d[2]], d[0], d[1], d[2], shape)
-        boff, _ = ae_layout(lib, 1, i)
-        out["%s.%s.bias" % (m, name)] = vec[boff:boff + d[5]].clone()
-    for i, (m, name) in enumerate(AE_BNS):
-        off, d = ae_layout(lib, 2, i)
-        out["%s.%s.weight" % (m, name)] = vec[off:off + d[0]].clone()
-        off, d = ae_layout(lib, 3, i)
-        out["%s.%s.bias" % (m, name)] = vec[off:off + d[0]].clone()
-    return out
+    return _FLAT.unpack_vector(vec, _resolve(encoder if encoder is not None else Encoder(),
+                                             decoder if decoder is not None else Decoder()))
 
 
 def unpack_into_autoencoder(encoder, decoder, params, stats=None, batches_tracked=None):
     """Write the flat vectors back into the modules (after HIP training).  conv4_bn / conv5_bn -- no gradient, as torch's
     Adam leaves a parameter whose .grad is None -- keep their parameters, running statistics and counters."""
-    mods = {"encoder": encoder, "decoder": decoder}
-    from .. import _capi
-    lib = _capi.load()
-    tensors = unpack_autoencoder_vector(params, encoder, decoder)
-    with torch.no_grad():
-        for key, value in tensors.items():
-            m, name, attr = key.split(".")
-            getattr(getattr(mods[m], name), attr).copy_(value)
-        if stats is not None:
-            for i, (m, name) in enumerate(AE_BNS):
-                bn = getattr(mods[m], name)
-                c = bn.weight.numel()
-                bn.running_mean.copy_(stats[ae_layout(lib, 4, i)[0]:][:c])
-                bn.running_var.copy_(stats[ae_layout(lib, 5, i)[0]:][:c])
-                if batches_tracked is not None:
-                    bn.num_batches_tracked.fill_(int(batches_tracked))
+    _FLAT.unpack_into(_resolve(encoder, decoder), params, stats, batches_tracked)
 
 
 def pack_encoder_params(enc):

@@ -1,7 +1,11 @@
 """CPU: the flat parameter vector of the forward-model kernels (include/ndp.h, ndp_fm_layout) against the module's own
 tensors -- packing and unpacking are inverse, padded entries are zero, every float of the vector belongs to exactly one
-tensor -- and the host-side refusals that need no GPU."""
+tensor -- the pin of both networks' host-side numbers (tests/golden/flat_layout_pin.json), and the host-side refusals
+that need no GPU."""
 import ctypes
+import importlib.util
+import json
+import os
 
 import pytest
 import torch
@@ -54,6 +58,38 @@ def test_layout_tiles_the_vector_and_round_trips(lib):
     assert torch.equal(clone.decoder.deconv6.weight, model.decoder.deconv6.weight)
     assert torch.equal(clone.decoder.conv_refine_1_bn.running_var, model.decoder.conv_refine_1_bn.running_var)
     assert int(clone.encoder.conv2_bn.num_batches_tracked) == 3
+
+
+def test_sizes_layouts_workspaces_and_buckets_are_the_pinned_ones(lib):
+    """Every number the host side derives from the two network tables -- vector sizes, ndp_*_layout of every valid query,
+    workspace sizes and tensor offsets, gradient buckets -- against the file written before the two networks' host code
+    was merged (tests/golden/make_flat_layout_pin.py): entry by entry."""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    with open(os.path.join(golden, "flat_layout_pin.json")) as f:
+        pin = json.load(f)
+    spec = importlib.util.spec_from_file_location("make_flat_layout_pin", os.path.join(golden, "make_flat_layout_pin.py"))
+    maker = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(maker)
+    now = json.loads(json.dumps(maker.collect()))                        # (tuples -> lists, integer keys -> strings)
+    assert sorted(now) == sorted(pin) == ["ae", "fm"]
+    for tag in pin:
+        assert sorted(now[tag]) == sorted(pin[tag])
+        for key, want in pin[tag].items():
+            if isinstance(want, dict):
+                assert sorted(now[tag][key]) == sorted(want), (tag, key)
+                for sub, value in want.items():
+                    assert now[tag][key][sub] == value, (tag, key, sub)
+            else:
+                assert now[tag][key] == want, (tag, key)
+    # the figures the refactoring was pinned on
+    assert (pin["fm"]["param_floats"], pin["fm"]["stat_floats"]) == (33366548, 4960)
+    assert (pin["ae"]["param_floats"], pin["ae"]["stat_floats"]) == (21633796, 4864)
+    assert pin["fm"]["workspace_floats"]["3"] == 100110800 and pin["ae"]["workspace_floats"]["3"] == 77552400
+    assert pin["ae"]["workspace_floats"]["8193"] == 0
+    assert pin["fm"]["workspace_offset"]["3"][27] == 52399824 and pin["ae"]["workspace_offset"]["3"][31] == 30519312
+    assert len(pin["fm"]["layout"]) == 2 * 14 + 4 * 10 and len(pin["ae"]["layout"]) == 2 * 12 + 4 * 8
+    assert pin["fm"]["buckets"][0] == [31979328, 1382260] and pin["fm"]["buckets"][-1] == [33361588, 4960]
+    assert pin["ae"]["buckets"][0] == [18871872, 2757060] and pin["ae"]["buckets"][-1] == [21628932, 4864]
 
 
 def test_host_side_refusals(lib):

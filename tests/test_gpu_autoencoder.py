@@ -165,6 +165,30 @@ def test_step_is_bit_reproducible_and_runs_smaller_batches():
         tr.grads(_images(241, 0).to(DEV))
 
 
+def test_the_optimizer_launch_leaves_the_second_weight_order_a_full_repack_would():
+    """ndp_ae_apply_adam writes the new weights in both orders in one launch (k_fm_adam_pack with this network's segments:
+    32 x 32 tiles of conv2 .. deconv5 transposed through LDS, conv1's compact [64][32] copy element by element, no
+    refinement segment, deconv6 without a second order).  ndp_ae_pack_params rebuilds the second order from the parameters
+    alone: after a training step it must change nothing.  The second order does not depend on the batch: one image."""
+    from ndivplanning_amd import _capi
+    from ndivplanning_amd.autoencoder_trainer import AutoencoderTrainer
+    from ndivplanning_amd.models import image_autoencoder as IA
+    enc, dec = _models(3)
+    tr = AutoencoderTrainer(enc.to(DEV).train(), dec.to(DEV).train(), batch=1)
+    tr.step(_images(1, 5).to(DEV))
+    torch.cuda.synchronize()
+    # the second-order region, from the layout: conv1 as [rows][27 -> 32 columns], conv2 .. deconv5 at their full size
+    sizes = [IA.ae_layout(tr.lib, 0, l)[1][:3] for l in range(len(IA.AE_LAYERS) - 1)]
+    p2 = sizes[0][0] * 32 + sum(r * t * c for r, t, c in sizes[1:])
+    assert 18_000_000 < p2 < tr.lib.ndp_ae_workspace_offset(1, 0)  # (most of the 21.6 M parameters; ahead of the first map)
+    before = tr.workspace[:p2].clone()
+    assert int((before != 0).sum()) > p2 // 2                       # (it is in use)
+    _capi.check(tr.lib.ndp_ae_pack_params(_capi.ptr(tr.params), _capi.ptr(tr.workspace), _capi.stream_ptr(DEV)),
+                "ndp_ae_pack_params")
+    torch.cuda.synchronize()
+    assert torch.equal(before.view(torch.int32), tr.workspace[:p2].view(torch.int32))
+
+
 def test_training_script_and_gan_handoff(tmp_path):
     """python train_autoencoder.py on synthetic images for one epoch in a fresh interpreter; pickles with the reference
     class paths; the loss sequence equals a CPU replay of the same loop; the saved encoder feeds ndp_encoder_forward."""
