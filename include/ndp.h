@@ -97,14 +97,26 @@ int ndp_g_forward(const float *g_params, int noise_dim,
  * and the activations saved by ndp_g_forward, writes
  *   grad [ndp_g_param_count]  dLoss/d params (written, not accumulated)
  *   ws   scratch of ndp_g_bwd_ws_floats(m, noise_dim) floats
- * No gradient is produced for the network input (the reference detaches the
- * codes and never differentiates the noise: train_gan.py:152-153, 44). */
+ * No gradient is produced for the network input here (the reference detaches the
+ * codes and never differentiates the noise: train_gan.py:152-153, 44); that is
+ * ndp_g_input_grad, below. */
 int64_t ndp_g_bwd_ws_floats(int64_t m, int noise_dim);
 int ndp_g_backward(const float *g_params, int noise_dim,
                    const float *code, int64_t ld_code, int code_rep,
                    const float *noise, int64_t ld_noise, int64_t m,
                    const float *acts, const float *d_action,
                    float *grad, float *ws, void *stream);
+
+/* Gradient with respect to the network input z [m, 256+noise_dim] (row stride ld_z;
+ * the plain form of ndp_g_forward's input: code_rep == 1):
+ *   d_z [m, 256+noise_dim] (row stride ld_dz) = dY1 . fc1.weight, written.
+ * d_action != NULL: the data path of the backward pass runs first (acts: what
+ * ndp_g_forward saved) -- no parameter gradient is computed.  d_action == NULL: ws
+ * is the workspace an ndp_g_backward call with the same arguments has just filled
+ * (one more launch on top of it).  ws: ndp_g_bwd_ws_floats(m, noise_dim) floats. */
+int ndp_g_input_grad(const float *g_params, int noise_dim, const float *z, int64_t ld_z,
+                     int64_t m, const float *acts, const float *d_action,
+                     float *d_z, int64_t ld_dz, float *ws, void *stream);
 
 /* ------------------------------------------------------ Discriminator D ---
  * Discriminator.forward (models/gan.py:104-110): logits = fc4(lrelu(fc3(lrelu(
@@ -118,7 +130,8 @@ int ndp_d_forward(const float *d_params,
                   float *logits, void *stream);
 
 /* Backward of Discriminator.forward given d_logits [m] = dLoss/d logits
- * (recomputes the forward inside the kernel; nothing needs to be saved):
+ * (recomputes the forward inside the kernel; nothing needs to be saved; the gradient
+ * with respect to the code is ndp_d_input_grad's):
  *   grad     [ndp_d_param_count] or NULL   dLoss/d params (written)
  *   d_action [m,4] or NULL                 dLoss/d action (written; needs action_rep==1)
  *   ws       scratch of ndp_d_bwd_ws_floats(m) floats (only used when grad != NULL) */
@@ -128,6 +141,13 @@ int ndp_d_backward(const float *d_params,
                    const float *code, int64_t ld_code, int code_rep, int64_t m,
                    const float *d_logits, float *grad, float *d_action,
                    float *ws, void *stream);
+/* ndp_d_backward that also writes d_code [m,256] (row stride ld_dcode) = dLoss/d code,
+ * in the same launch; needs code_rep == 1.  grad and d_action as above (may be NULL). */
+int ndp_d_input_grad(const float *d_params,
+                     const float *action, int action_rep,
+                     const float *code, int64_t ld_code, int code_rep, int64_t m,
+                     const float *d_logits, float *grad, float *d_action,
+                     float *d_code, int64_t ld_dcode, float *ws, void *stream);
 
 /* ----------------------------------------------------------------- Adam ---
  * torch.optim.Adam.step for one flat parameter vector (train_gan.py:98-104,
@@ -400,6 +420,14 @@ int ndp_fm_backward(const float *params, const float *d_resid, int64_t n_images,
 int ndp_fm_apply_adam(float *params, const float *grad, float *exp_avg, float *exp_avg_sq,
                       int32_t *step_count, float lr, float beta1, float beta2, float eps,
                       float *workspace, void *stream);
+/* Input gradients of the EVAL-mode forward pass (out = state_cur + residual, BatchNorm with the running statistics):
+ * d_out [n,3,128,128] = d loss / d out  ->  d_state_cur [n,3,128,128] (or NULL) and d_actions [n,4] (or NULL; not both).
+ * Must follow ndp_fm_forward / ndp_fm_forward_u8 (training == 0) on the same n images with the same workspace and no
+ * other ndp_fm_* call on that workspace in between; it consumes the activations, so a second call (or one without such
+ * a forward pass) returns NDP_E_UNSUPPORTED and launches nothing.  Only the data-gradient chain runs -- no parameter
+ * gradient is written anywhere -- and with d_state_cur == NULL it stops at the decoder's first layer. */
+int ndp_fm_input_grads(const float *params, const float *d_out, int64_t n_images,
+                       float *d_state_cur, float *d_actions, float *workspace, void *stream);
 
 /* ------------------------------------------------------- image autoencoder ---
  * models.image_autoencoder.Encoder + Decoder (image_autoencoder.py:14-87) and one iteration of their training loop

@@ -70,10 +70,14 @@ SIGNATURES = {
     "ndp_g_bwd_ws_floats": (c_int64, [c_int64, c_int]),
     "ndp_g_backward": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_int64, c_int64,
                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ndp_g_input_grad": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
+                                 c_void_p, c_void_p]),
     "ndp_d_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
     "ndp_d_bwd_ws_floats": (c_int64, [c_int64]),
     "ndp_d_backward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p,
                                c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ndp_d_input_grad": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     "ndp_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                               c_float, c_float, c_float, c_float, c_void_p]),
     "ndp_step_workspace_floats": (c_int64, [POINTER(StepConfig)]),
@@ -117,6 +121,7 @@ SIGNATURES = {
     "ndp_fm_set_stat_sync": (c_int, [c_void_p, c_void_p, c_int]),
     "ndp_fm_bucket_wait": (c_int, [c_int, c_void_p]),
     "ndp_fm_backward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ndp_fm_input_grads": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ndp_fm_apply_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                   c_void_p, c_void_p]),
     "ndp_ae_param_floats": (c_int64, []),

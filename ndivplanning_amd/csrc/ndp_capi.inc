@@ -677,6 +677,37 @@ int ndp_g_backward(const float* g_params, int noise_dim, const float* code, int6
                          nullptr, ws, red, nullptr, AdamHyper{0.f, 0.f, 0.f}, (hipStream_t)stream);
 }
 
+int ndp_g_input_grad(const float* g_params, int noise_dim, const float* z, int64_t ld_z, int64_t m, const float* acts,
+                     const float* d_action, float* d_z, int64_t ld_dz, float* ws, void* stream) {
+  int rc = check_g_common("ndp_g_input_grad", g_params, noise_dim, z, ld_z, 1, z, ld_z, m);
+  if (rc) return rc;
+  NDP_CHECK_ARG(ld_z >= NDP_CODE_DIM + noise_dim && ld_dz >= NDP_CODE_DIM + noise_dim, "ndp_g_input_grad: bad strides");
+  NDP_CHECK_ARG(d_z && ws && aligned16(ws), "ndp_g_input_grad: d_z / ws null or ws not 16-byte aligned");
+  NDP_CHECK_ARG(!d_action || (acts && aligned16(acts) && aligned16(d_action)),
+                "ndp_g_input_grad: d_action needs the 16-byte aligned activations of ndp_g_forward");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t mpad = pad_rows(m);
+  const GNet net = g_net(g_params, noise_dim);
+  const GBwdWs w = g_bwd_ws(ws, mpad, noise_dim);
+  if (d_action != nullptr) {          // null: dy1 is what the ndp_g_backward call just before left in ws
+    const GActs a = g_acts(const_cast<float*>(acts), mpad);
+    GBwdArgs b;
+    b.net = net;
+    b.m = m;
+    b.h1 = a.h1; b.h2 = a.h2; b.h3 = a.h3; b.h4 = a.h4;
+    b.d_action = d_action; b.d_action2 = nullptr;
+    b.dy1 = w.dy1; b.dy2 = w.dy2; b.dy3 = w.dy3; b.dy4 = w.dy4; b.dy5 = w.dy5;
+    rc = launch_g_bwd(b, st);
+    if (rc) return rc;
+  }
+  GInGradArgs g;
+  g.w1 = net.w1; g.ld1 = net.ld1; g.nz = noise_dim;
+  g.dy1 = w.dy1; g.d_z = d_z; g.ld_dz = ld_dz; g.m = m;
+  KTimer kt("k_g_in_dgrad", st);
+  hipLaunchKernelGGL(k_g_in_dgrad, dim3((unsigned)(mpad / 16)), dim3(kThreads), 0, st, g);
+  return check_launch("k_g_in_dgrad");
+}
+
 static int check_d_common(const char* fn, const float* d_params, const float* action, int action_rep,
                           const float* code, int64_t ld_code, int code_rep, int64_t m) {
   NDP_CHECK_ARG(d_params && action && code, "%s: null pointer", fn);
@@ -709,14 +740,15 @@ int ndp_d_forward(const float* d_params, const float* action, int action_rep, co
 
 int64_t ndp_d_bwd_ws_floats(int64_t m) { return d_bwd_floats(pad_rows(m), 1); }
 
-int ndp_d_backward(const float* d_params, const float* action, int action_rep, const float* code, int64_t ld_code,
-                   int code_rep, int64_t m, const float* d_logits, float* grad, float* d_action, float* ws,
-                   void* stream) {
-  int rc = check_d_common("ndp_d_backward", d_params, action, action_rep, code, ld_code, code_rep, m);
+static int d_backward_impl(const char* fn, const float* d_params, const float* action, int action_rep, const float* code,
+                           int64_t ld_code, int code_rep, int64_t m, const float* d_logits, float* grad, float* d_action,
+                           float* d_code, int64_t ld_dcode, float* ws, void* stream) {
+  int rc = check_d_common(fn, d_params, action, action_rep, code, ld_code, code_rep, m);
   if (rc) return rc;
-  NDP_CHECK_ARG(d_logits, "ndp_d_backward: null d_logits");
-  NDP_CHECK_ARG(!grad || (ws && aligned16(ws)), "ndp_d_backward: grad needs a 16-byte aligned workspace");
-  NDP_CHECK_ARG(!d_action || action_rep == 1, "ndp_d_backward: d_action needs action_rep == 1");
+  NDP_CHECK_ARG(d_logits, "%s: null d_logits", fn);
+  NDP_CHECK_ARG(!grad || (ws && aligned16(ws)), "%s: grad needs a 16-byte aligned workspace", fn);
+  NDP_CHECK_ARG(!d_action || action_rep == 1, "%s: d_action needs action_rep == 1", fn);
+  NDP_CHECK_ARG(!d_code || (code_rep == 1 && ld_dcode >= NDP_CODE_DIM), "%s: d_code needs code_rep == 1 and ld_dcode >= 256", fn);
   hipStream_t st = (hipStream_t)stream;
   DArgs a;
   d_args_init(a, d_params, code, ld_code, code_rep, m);
@@ -724,6 +756,7 @@ int ndp_d_backward(const float* d_params, const float* action, int action_rep, c
   a.ext_dlogit = d_logits;
   a.do_backward = 1;
   a.d_action = d_action;
+  a.d_code = d_code; a.ld_dcode = ld_dcode;
   DBwdWs w;
   if (grad) {
     w = d_bwd_ws(ws, a.mpad, 1);
@@ -741,6 +774,21 @@ int ndp_d_backward(const float* d_params, const float* action, int action_rep, c
   set_red_regions(red, wa, w.light);
   red.grad = grad;
   return launch_reduce(red, st);
+}
+
+int ndp_d_backward(const float* d_params, const float* action, int action_rep, const float* code, int64_t ld_code,
+                   int code_rep, int64_t m, const float* d_logits, float* grad, float* d_action, float* ws,
+                   void* stream) {
+  return d_backward_impl("ndp_d_backward", d_params, action, action_rep, code, ld_code, code_rep, m, d_logits, grad, d_action,
+                         nullptr, 0, ws, stream);
+}
+
+int ndp_d_input_grad(const float* d_params, const float* action, int action_rep, const float* code, int64_t ld_code,
+                     int code_rep, int64_t m, const float* d_logits, float* grad, float* d_action, float* d_code,
+                     int64_t ld_dcode, float* ws, void* stream) {
+  NDP_CHECK_ARG(d_code, "ndp_d_input_grad: null d_code (ndp_d_backward is the call without it)");
+  return d_backward_impl("ndp_d_input_grad", d_params, action, action_rep, code, ld_code, code_rep, m, d_logits, grad, d_action,
+                         d_code, ld_dcode, ws, stream);
 }
 
 int ndp_adam_step(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,

@@ -528,6 +528,55 @@ __device__ __forceinline__ void layer_dgrad_narrow(const float* dY, int ldd,
   }
 }
 
+// The last hop of a data gradient, to the network's 256 code INPUTS (no activation in front of them):
+//   dX[R x 256] = dY[R x OUT] . W[OUT x ldw][:, 0:256]      dY in LDS, W = the first layer's weight rows (native layout,
+//   already offset to the first code column), dX straight to global rows row0 .. (rows >= m are not written).
+//   Wave w owns columns [64 w, 64 w + 64) as four 16-column MFMA tiles; lane (q, c) pairs element s of its dY vector
+//   (k = 16 t + 4 q + s, as layer_dgrad_run) with weight row k, column 64 w + 16 n + c: 16 lanes read 64 contiguous
+//   bytes of a weight row, and write 64 contiguous bytes of an output row.
+template <int RT, int OUT>
+__device__ __forceinline__ void input_dgrad_code(const float* dY, int ldd, const float* __restrict__ W, int ldw,
+                                                 float* __restrict__ dX, int64_t ldx, int64_t row0, int64_t m) {
+  static_assert(OUT % 16 == 0, "input_dgrad_code shape");
+  constexpr int NIT = OUT / 16;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & 15, q = lane >> 4;
+  const float* wp = W + (size_t)(4 * q) * ldw + 64 * wave + c;
+  const float* dp = dY + c * ldd + 4 * q;
+  f32x4 acc[RT][4];
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[r][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < NIT; ++t) {
+    float bv[4][4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int n = 0; n < 4; ++n) bv[s][n] = wp[(size_t)(16 * t + s) * ldw + 16 * n];
+    f32x4 av[RT];
+#pragma unroll
+    for (int r = 0; r < RT; ++r) av[r] = *reinterpret_cast<const f32x4*>(dp + r * 16 * ldd + 16 * t);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[r][n] = mfma16(av[r][s], bv[s][n], acc[r][n]);
+  }
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t row = row0 + r * 16 + 4 * q + i;
+      if (row < m) {
+#pragma unroll
+        for (int n = 0; n < 4; ++n) dX[row * ldx + 64 * wave + 16 * n + c] = acc[r][n][i];
+      }
+    }
+}
+
 // Write-through (sc1) 16-byte store of hand-off data -- what the NEXT kernel reads -- at base[off .. off + 3]; `base` is
 // wave-uniform.  The bytes leave the XCD's L2 while the kernel still computes, so the end-of-kernel release finds no
 // dirty lines to write back on the critical path; a 16-byte sc1 store issues like a plain one.  The buffer form is the

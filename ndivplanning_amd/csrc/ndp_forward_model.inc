@@ -28,6 +28,7 @@
 // bit-reproducible.
 
 #include <atomic>
+#include <unordered_map>
 
 namespace ndp {
 
@@ -1258,6 +1259,103 @@ __global__ __launch_bounds__(kThreads) void k_fm_bn_bwd_apply(FmEltArgs a) {
     }
   }
 }
+// BatchNorm + ReLU backward for RUNNING statistics (eval mode: mean and invstd are constants of the input, so no batch sum
+// enters): dx = [y > 0] * dy * gamma * invstd, written over x; invstd as k_fm_bn_eval_stats left it.
+__global__ __launch_bounds__(kThreads) void k_fm_bn_eval_bwd_apply(FmEltArgs a) {
+  const int c4 = a.C / 4;
+  const int64_t total = (int64_t)a.P * c4;
+  for (int it = 0; it < a.iters; ++it) {
+    f32x4 yv[kFmEltPerThread], dv[kFmEltPerThread];
+    int cgv[kFmEltPerThread];
+    int64_t pv[kFmEltPerThread];
+#pragma unroll
+    for (int k = 0; k < kFmEltPerThread; ++k) {
+      const int64_t i = (((int64_t)blockIdx.x * a.iters + it) * kFmEltPerThread + k) * kThreads + threadIdx.x;
+      cgv[k] = (int)(i % c4);
+      pv[k] = i < total ? i / c4 : -1;
+      yv[k] = dv[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (pv[k] >= 0) {
+        yv[k] = *reinterpret_cast<const f32x4*>(a.y + pv[k] * a.y_ld + 4 * cgv[k]);
+        dv[k] = *reinterpret_cast<const f32x4*>(a.dy + pv[k] * a.dy_ld + 4 * cgv[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < kFmEltPerThread; ++k) {
+      if (pv[k] < 0) continue;
+      const int cg = cgv[k];
+      const f32x4 is = *reinterpret_cast<const f32x4*>(a.invstd + 4 * cg), ga = *reinterpret_cast<const f32x4*>(a.gamma + 4 * cg);
+      f32x4 dx;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) dx[e] = yv[k][e] > 0.f ? dv[k][e] * (ga[e] * is[e]) : 0.f;
+      *reinterpret_cast<f32x4*>(a.out + pv[k] * a.out_ld + 4 * cg) = dx;
+    }
+  }
+}
+
+// Data gradient of conv1 (3 -> 64, 3x3, stride 2, pad 1) in gather form, plus the identity of the eval-mode output
+// (out = state_cur + residual):  d_cur[n][ci][ih][iw] = d_out[n][ci][ih][iw] + sum over the taps (kh, kw) with
+// ih + 1 - kh = 2 oh, iw + 1 - kw = 2 ow -- at most 2 x 2 output positions -- and the 64 channels of
+// draw1[(n, oh, ow)][co] * W[co][kh][kw][ci].  Every sum is taken in one fixed order by one thread: no float atomics.
+// One workgroup per (image, oh): output rows oh and oh + 1 of draw1 (2 x 64 pixels x 64 channels, the 1 MB per image that
+// bounds the kernel, read as whole 256-byte rows) are staged in LDS and feed input rows 2 oh (needs oh) and 2 oh + 1
+// (needs oh and oh + 1), one thread per input pixel.  Row stride 68 floats (lds_ld): the ds_read_b128 of a wave's
+// neighbouring pixels spread over the banks.  The blocks behind the images' copy d_actions out of dz's action columns
+// (128..131, where k_fm_image_cols put the actions in z); nimg_rows == 0: only those.
+struct FmC1DgArgs {
+  const float* draw1; const float* w; const float* d_out; float* d_cur; int64_t nimg_rows;   // nimg_rows = n * 64, or 0
+  const float* dz; float* d_actions; int64_t nimg;                                           // d_actions null: no copy
+};
+constexpr int kFmC1LD = 68;
+__global__ __launch_bounds__(kThreads) void k_fm_conv1_dgrad(FmC1DgArgs a) {
+  __shared__ __attribute__((aligned(16))) float D[2 * 64 * kFmC1LD];
+  __shared__ __attribute__((aligned(16))) float Ws[27 * 64];               // [k = (kh * 3 + kw) * 3 + ci][co]
+  if ((int64_t)blockIdx.x >= a.nimg_rows) {
+    const int64_t i = ((int64_t)blockIdx.x - a.nimg_rows) * kThreads + threadIdx.x;
+    if (a.d_actions != nullptr && i < a.nimg * 4) a.d_actions[i] = a.dz[(i >> 2) * 160 + 128 + (i & 3)];
+    return;
+  }
+  const int64_t n = (int64_t)blockIdx.x >> 6;
+  const int oh = (int)blockIdx.x & 63;
+  for (int i = threadIdx.x; i < 27 * 64; i += kThreads) {
+    const int co = i & 63, k = i >> 6;                                   // P1 of conv1: [co][tap][ci -> 32]
+    Ws[i] = a.w[(size_t)co * 9 * 32 + (k / 3) * 32 + (k % 3)];
+  }
+  for (int i = threadIdx.x; i < 2 * 64 * 16; i += kThreads) {
+    const int c4 = i & 15, px = (i >> 4) & 63, r = i >> 10;
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (oh + r < 64) v = *reinterpret_cast<const f32x4*>(a.draw1 + ((n * 64 + oh + r) * 64 + px) * 64 + 4 * c4);
+    *reinterpret_cast<f32x4*>(D + (r * 64 + px) * kFmC1LD + 4 * c4) = v;
+  }
+  __syncthreads();
+  const int iw = threadIdx.x & 127, ir = threadIdx.x >> 7;                 // input row 2 oh + ir
+  // rows: ir == 0 -> (kh 1, staged row 0); ir == 1 -> (kh 2, row 0), (kh 0, row 1).  Columns alike from iw's parity.
+  const int nrow = ir + 1, ncol = (iw & 1) + 1;
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int u = 0; u < nrow; ++u) {
+    const int kh = ir == 0 ? 1 : (u == 0 ? 2 : 0), r = u;
+    for (int v = 0; v < ncol; ++v) {
+      const int kw = (iw & 1) == 0 ? 1 : (v == 0 ? 2 : 0);
+      const int ow = (iw + 1 - kw) >> 1;
+      if (ow >= 64) continue;                                             // (iw = 127, kw = 0: past the map; row oh + 1 = 64 is staged as zeros)
+      const float* d = D + (r * 64 + ow) * kFmC1LD;
+      const float* w = Ws + (kh * 3 + kw) * 3 * 64;
+#pragma unroll 4
+      for (int c4 = 0; c4 < 16; ++c4) {
+        const f32x4 dv = *reinterpret_cast<const f32x4*>(d + 4 * c4);
+#pragma unroll
+        for (int ci = 0; ci < 3; ++ci) {
+          const f32x4 wv = *reinterpret_cast<const f32x4*>(w + ci * 64 + 4 * c4);
+          acc[ci] = fmaf(dv[0], wv[0], acc[ci]); acc[ci] = fmaf(dv[1], wv[1], acc[ci]);
+          acc[ci] = fmaf(dv[2], wv[2], acc[ci]); acc[ci] = fmaf(dv[3], wv[3], acc[ci]);
+        }
+      }
+    }
+  }
+  const int64_t base = n * 3 * 16384 + (int64_t)(2 * oh + ir) * 128 + iw;
+#pragma unroll
+  for (int ci = 0; ci < 3; ++ci) a.d_cur[base + ci * 16384] = a.d_out[base + ci * 16384] + acc[ci];
+}
+
 // a bias gradient that is a plain column sum (conv4, conv5, conv6): accumulator -> grad, one workgroup
 struct FmBiasFinishArgs { FmStatFin fin; int cols; };
 __global__ __launch_bounds__(kThreads) void k_fm_bias_finish(FmBiasFinishArgs a) {
@@ -2778,6 +2876,108 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
 #undef FM_TRY
 }
 
+// BatchNorm b + ReLU backward with running statistics (k_fm_bn_eval_bwd_apply): raw := d loss / d raw
+static int fm_bn_eval_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int64_t P, const float* params, const FmWs& ws) {
+  const int C = kFmBnC[b];
+  FmEltArgs e;
+  memset(&e, 0, sizeof(e));
+  e.y = y.p; e.y_ld = y.ld; e.dy = dy.p; e.dy_ld = dy.ld; e.out = raw.p; e.out_ld = raw.ld;
+  e.invstd = ws.bn_invstd + fm_bn_stat_index(b);
+  e.gamma = params + fm_bn_offset(kFmNet, b, false);
+  e.C = C; e.P = (int)P;
+  e.iters = fm_elt_iters(P, C);
+  KTimer kt("k_fm_bn_eval_bwd_apply", st);
+  hipLaunchKernelGGL(k_fm_bn_eval_bwd_apply, fm_elt_grid(P, C), dim3(kThreads), 0, st, e);
+  return check_launch("k_fm_bn_eval_bwd_apply");
+}
+
+// Input gradients of the eval-mode forward pass (ndp_fm_input_grads): fm_backward's data-gradient chain alone, from
+// d loss / d (pre-tanh output) in y2 to d_actions (the action columns of dz) and, when d_cur != null, on through the encoder
+// to the image.  No weight gradient, no slab, no side stream, no bucket event, no statistics epilogue but the ReLU backward
+// of conv4 / conv5 (whose bias sums land in accumulators nobody reads); BatchNorm backward with the running statistics.
+static int fm_input_grads(hipStream_t st, const float* params, const float* d_out, int64_t n, float* d_cur, float* d_actions,
+                          const FmWs& ws) {
+  fm_attrs();
+  const float* P = params;
+  auto W1 = [&](int l) { return P + fm_param_offset(kFmNet, l, false); };
+  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kFmNet, l)); };
+  float* const* t = ws.t;
+  const int64_t npix = n * 16384;
+  int rc;
+#define FM_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+  const FmEpReq none = fm_ep_none();
+  {
+    FmR2Args r2;
+    memset(&r2, 0, sizeof(r2));
+    r2.y2 = t[FMT_Y2]; r2.w = W1(13); r2.dr1 = t[FMT_DR1]; r2.npix = npix;
+    KTimer kt("k_fm_r2_dgrad", st);
+    hipLaunchKernelGGL(k_fm_r2_dgrad, dim3((unsigned)((npix + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, r2);
+  }
+  FM_TRY(check_launch("k_fm_r2_dgrad"));
+  FM_TRY(fm_bn_eval_bwd(st, 9, {t[FMT_RAWR1], kFmR1LD}, {t[FMT_R1], kFmR1LD}, {t[FMT_DR1], kFmR1LD}, npix, P, ws));
+  FM_TRY(fm_r1(st, "k_fm_dgrad[refine1]", true, t[FMT_RAWR1], W2(12), nullptr, t[FMT_DUP6], n, none, ws));
+  FM_TRY(fm_bn_eval_bwd(st, 8, {t[FMT_RAWU6], 32}, {t[FMT_UP6], 32}, {t[FMT_DUP6], 32}, npix, P, ws));
+  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv6]", 0, {t[FMT_RAWU6], 32}, 128, 2, W1(11), nullptr, {t[FMT_DCAT6], 128}, 64, 64, n, 32, 128, 4, 1, 0, 0, ws));
+  FM_TRY(fm_bn_eval_bwd(st, 7, {t[FMT_RAWU5], 64}, {t[FMT_CAT6], 128}, {t[FMT_DCAT6], 128}, n * 4096, P, ws));
+  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv5]", 0, {t[FMT_RAWU5], 64}, 64, 2, W1(10), nullptr, {t[FMT_DCAT5], 256}, 32, 32, n, 64, 256, 4, 1, 0, 0, ws));
+  FM_TRY(fm_bn_eval_bwd(st, 6, {t[FMT_RAWU4], 128}, {t[FMT_CAT5], 256}, {t[FMT_DCAT5], 256}, n * 1024, P, ws));
+  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv4]", 0, {t[FMT_RAWU4], 128}, 32, 2, W1(9), nullptr, {t[FMT_DCAT4], 512}, 16, 16, n, 128, 512, 4, 1, 0, 0, ws));
+  FM_TRY(fm_bn_eval_bwd(st, 5, {t[FMT_RAWU3], 256}, {t[FMT_CAT4], 512}, {t[FMT_DCAT4], 512}, n * 256, P, ws));
+  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv3]", 0, {t[FMT_RAWU3], 256}, 16, 2, W1(8), nullptr, {t[FMT_DCAT3], 1024}, 8, 8, n, 256, 1024, 4, 1, 0, 0, ws));
+  FM_TRY(fm_bn_eval_bwd(st, 4, {t[FMT_RAWU2], 512}, {t[FMT_CAT3], 1024}, {t[FMT_DCAT3], 1024}, n * 64, P, ws));
+  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv2]", 0, {t[FMT_RAWU2], 512}, 8, 2, W1(7), nullptr, {t[FMT_DCAT2], 2048}, 4, 4, n, 512, 2048, 4, 1, 0, 0, ws));
+  FM_TRY(fm_bn_eval_bwd(st, 3, {t[FMT_RAWU1], 1024}, {t[FMT_CAT2], 2048}, {t[FMT_DCAT2], 2048}, n * 16, P, ws));
+  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv1]", 0, {t[FMT_RAWU1], 1024}, 4, 1, W1(6), nullptr, {t[FMT_DZ], 160}, 1, 1, n, 1024, 160, 4, 0, 0, 0, ws));
+  FmC1DgArgs c1;
+  memset(&c1, 0, sizeof(c1));
+  c1.dz = t[FMT_DZ]; c1.d_actions = d_actions; c1.nimg = n;
+  if (d_cur != nullptr) {
+    // the encoder half: conv6, conv5, conv4 (ReLU backward in the epilogue), conv3 .. conv1 (BatchNorm backward between)
+    FmEpReq rq = fm_ep_bias(3, 21, {t[FMT_CAT2] + 1024, 2048});
+    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv6]", 3, {t[FMT_DZ], 160}, 1, 1, W2(5), nullptr, {t[FMT_DCAT2] + 1024, 2048}, 4, 1, n, 128, 1024, 1, 0, 0, 1, ws, 0, &rq));
+    rq = fm_ep_bias(3, 22, {t[FMT_CAT3] + 512, 1024});
+    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv5]", 2, {t[FMT_DCAT2] + 1024, 2048}, 4, 1, W2(4), nullptr, {t[FMT_DCAT3] + 512, 1024}, 8, 4, n, 1024, 512, 2, 0, 0, 1, ws, 0, &rq));
+    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv4]", 2, {t[FMT_DCAT3] + 512, 1024}, 8, 1, W2(3), nullptr, {t[FMT_DCAT4] + 256, 512}, 16, 8, n, 512, 256, 2, 0, 0, 1, ws));
+    FM_TRY(fm_bn_eval_bwd(st, 2, {t[FMT_RAW3], 256}, {t[FMT_CAT4] + 256, 512}, {t[FMT_DCAT4] + 256, 512}, n * 256, P, ws));
+    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv3]", 2, {t[FMT_RAW3], 256}, 16, 1, W2(2), nullptr, {t[FMT_DCAT5] + 128, 256}, 32, 16, n, 256, 128, 2, 0, 0, 1, ws));
+    FM_TRY(fm_bn_eval_bwd(st, 1, {t[FMT_RAW2], 128}, {t[FMT_CAT5] + 128, 256}, {t[FMT_DCAT5] + 128, 256}, n * 1024, P, ws));
+    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv2]", 2, {t[FMT_RAW2], 128}, 32, 1, W2(1), nullptr, {t[FMT_DCAT6] + 64, 128}, 64, 32, n, 128, 64, 2, 0, 0, 1, ws));
+    FM_TRY(fm_bn_eval_bwd(st, 0, {t[FMT_RAW1], 64}, {t[FMT_CAT6] + 64, 128}, {t[FMT_DCAT6] + 64, 128}, n * 4096, P, ws));
+    c1.draw1 = t[FMT_RAW1]; c1.w = W1(0); c1.d_out = d_out; c1.d_cur = d_cur; c1.nimg_rows = n * 64;
+  }
+  const int64_t copy_blocks = d_actions != nullptr ? (n * 4 + kThreads - 1) / kThreads : 0;
+  if (c1.nimg_rows + copy_blocks > 0) {
+    KTimer kt("k_fm_conv1_dgrad", st);
+    hipLaunchKernelGGL(k_fm_conv1_dgrad, dim3((unsigned)(c1.nimg_rows + copy_blocks)), dim3(kThreads), 0, st, c1);
+    FM_TRY(check_launch("k_fm_conv1_dgrad"));
+  }
+  return NDP_OK;
+#undef FM_TRY
+}
+
+// Which workspaces hold the activations of an eval-mode forward pass that no later call has touched (ndp_fm_input_grads
+// consumes them): workspace pointer -> images.  Host-side bookkeeping only; every entry point that writes activations
+// drops the workspace's entry first.
+static std::mutex g_fm_eval_mutex;
+static std::unordered_map<const float*, int64_t> g_fm_eval_fresh;
+static void fm_eval_forget(const float* ws) {
+  std::lock_guard<std::mutex> lock(g_fm_eval_mutex);
+  g_fm_eval_fresh.erase(ws);
+}
+static void fm_eval_mark(const float* ws, int64_t n) {
+  std::lock_guard<std::mutex> lock(g_fm_eval_mutex);
+  g_fm_eval_fresh[ws] = n;
+}
+// takes the entry: the images of the fresh eval-mode forward in ws, or 0
+static int64_t fm_eval_take(const float* ws) {
+  std::lock_guard<std::mutex> lock(g_fm_eval_mutex);
+  auto it = g_fm_eval_fresh.find(ws);
+  if (it == g_fm_eval_fresh.end()) return 0;
+  const int64_t n = it->second;
+  g_fm_eval_fresh.erase(it);
+  return n;
+}
+
 // the body of ndp_fm_layout / ndp_ae_layout (include/ndp.h); `who`: the entry point, for its error strings
 static int fm_layout(const FmNet& net, const char* who, int what, int index, int64_t* offset, int64_t* dims) {
   NDP_CHECK_ARG(offset && dims, "%s: null pointer", who);
@@ -2828,9 +3028,14 @@ static int fm_forward_any(const float* params, float* running_stats, const void*
                 (!running_stats || aligned16(running_stats)), "%s: buffers must be 16-byte aligned", who);
   hipStream_t st = (hipStream_t)stream;
   const FmWs ws = fm_ws(workspace, n_images);
+  fm_eval_forget(workspace);
   int rc = fm_forward(st, params, running_stats, state_cur, u8, actions, n_images, training, ws);
   if (rc) return rc;
-  if (!training) return fm_loss(st, state_cur, nullptr, u8, n_images, 0, out, nullptr, nullptr, nullptr, ws);
+  if (!training) {
+    rc = fm_loss(st, state_cur, nullptr, u8, n_images, 0, out, nullptr, nullptr, nullptr, ws);
+    if (rc == NDP_OK) fm_eval_mark(workspace, n_images);     // ndp_fm_input_grads may follow
+    return rc;
+  }
   // training mode returns the residual (forward_encoder.py:111-112): y2 -> NCHW
   FmLossArgs a;
   memset(&a, 0, sizeof(a));
@@ -2861,6 +3066,7 @@ static int fm_train_grads_any(const float* params, float* running_stats, const v
   hipStream_t st = (hipStream_t)stream;
   const FmWs ws = fm_ws(workspace, n_images);
   const FmLossArgs la = fm_loss_args(state_cur, state_fut, u8, n_images, 1, resid_out, ws);
+  fm_eval_forget(workspace);
   int rc = fm_forward(st, params, running_stats, state_cur, u8, actions, n_images, 1, ws, true, &la);
   if (rc) return rc;
   rc = fm_loss(st, state_cur, state_fut, u8, n_images, 1, resid_out, loss, loss_sum, grad, ws, true);
@@ -2917,9 +3123,35 @@ int ndp_fm_backward(const float* params, const float* d_resid, int64_t n_images,
                 "ndp_fm_backward: buffers must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const FmWs ws = fm_ws(workspace, n_images);
+  fm_eval_forget(workspace);
   int rc = fm_loss(st, d_resid, nullptr, false, n_images, 3, nullptr, nullptr, nullptr, grad, ws);
   if (rc) return rc;
   return fm_backward(st, params, n_images, grad, ws);
+}
+
+int ndp_fm_input_grads(const float* params, const float* d_out, int64_t n_images, float* d_state_cur, float* d_actions,
+                       float* workspace, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(params && d_out && workspace && n_images >= 1 && n_images <= 8192, "ndp_fm_input_grads: bad arguments");
+  NDP_CHECK_ARG(d_state_cur || d_actions, "ndp_fm_input_grads: neither d_state_cur nor d_actions is asked for");
+  NDP_CHECK_ARG(aligned16(params) && aligned16(d_out) && aligned16(workspace), "ndp_fm_input_grads: buffers must be 16-byte aligned");
+  const int64_t fresh = fm_eval_take(workspace);
+  if (fresh != n_images)
+    return fail(NDP_E_UNSUPPORTED, "ndp_fm_input_grads: the workspace does not hold the activations of an eval-mode ndp_fm_forward "
+                "on %lld images (another call ran in between, or they were consumed already)", (long long)n_images);
+  hipStream_t st = (hipStream_t)stream;
+  const FmWs ws = fm_ws(workspace, n_images);
+  // d out / d residual = 1 (out = state_cur + residual): y2 := d_out * (1 - y2^2), the gradient at the pre-tanh output
+  FmLossArgs a;
+  memset(&a, 0, sizeof(a));
+  a.y2 = ws.t[FMT_Y2]; a.cur = d_out; a.partial = ws.loss_partial; a.npix = n_images * 16384; a.training = 3;
+  {
+    KTimer kt("k_fm_loss", st);
+    hipLaunchKernelGGL(k_fm_loss, dim3((unsigned)(n_images * 64)), dim3(kThreads), 0, st, a);
+  }
+  int rc = check_launch("k_fm_loss");
+  if (rc) return rc;
+  return fm_input_grads(st, params, d_out, n_images, d_state_cur, d_actions, ws);
 }
 
 int ndp_fm_apply_adam(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int32_t* step_count, float lr,

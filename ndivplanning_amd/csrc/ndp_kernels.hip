@@ -348,6 +348,7 @@ struct DArgs {
   float *dy1, *dy2, *dy3, *dl;
   float* xa;                  // [npass*mpad x 4] action inputs, for k_wgrad
   float* d_action;            // [m x 4] or null (pass 0)
+  float* d_code; int64_t ld_dcode;   // [m x 256] (row stride ld_dcode) or null: dLoss/d code of pass 0 (needs code_rep == 1)
   float* loss_partials;       // [ntiles] raw BCE sums over all passes, or null
   NdivArgs nd;                // blocks ntiles.. : NDiv (cx <= 4, cz <= 2), nd.n == 0 -> none
 };
@@ -497,6 +498,8 @@ __global__ __launch_bounds__(kThreads) void k_d(DArgs a) {
     for (int o = 0; o < 64; ++o) s = fmaf(H1[i * 68 + o], n.w1[o * 260 + j], s);
     if (row < a.m) a.d_action[row * ADIM + j] = s;
   }
+  // dLoss/d code = dY1 . W1[:, 4:260]   (pass 0): 64x the work of the action columns, on the matrix pipe
+  if (a.d_code != nullptr) input_dgrad_code<1, 64>(H1, 68, n.w1 + ADIM, 260, a.d_code, a.ld_dcode, row0, a.m);
   NDP_STAMP(11);
   NDP_STAMP_FLUSH(12, 2);
 }
@@ -558,6 +561,32 @@ __global__ __launch_bounds__(kThreads) void k_g_bwd(GBwdArgs a) {
   store_tile<1, 64>(a.dy2 + row0 * 64, 64, H2, 68);
   store_tile<1, 128>(a.dy3 + row0 * 128, 128, H3, 132);
   store_tile<1, 256>(a.dy4 + row0 * 256, 256, H4, 260);
+}
+
+// The last hop of the Decoder's data path, to its input z = cat[code, noise]:  d_z [m x (256 + nz)] = dY1 . W1, from the
+// dY1 k_g_bwd left in the workspace.  One workgroup per 16-row tile: the 256 code columns on the matrix pipe
+// (input_dgrad_code), the <= 16 noise columns as a narrow tail (one thread per row and column, as d_action in k_d).
+struct GInGradArgs {
+  const float* w1; int ld1, nz;       // fc1.weight [128][256 + nz]
+  const float* dy1;                   // [mpad x 128]
+  float* d_z; int64_t ld_dz;          // [m x (256 + nz)], row stride ld_dz
+  int64_t m;
+};
+__global__ __launch_bounds__(kThreads) void k_g_in_dgrad(GInGradArgs a) {
+  constexpr int R = 16;
+  __shared__ __attribute__((aligned(16))) float DY[R * 132];
+  const int64_t row0 = (int64_t)blockIdx.x * R;
+  load_tile<1, 128>(DY, 132, a.dy1 + row0 * 128, 128);
+  __syncthreads();
+  input_dgrad_code<1, 128>(DY, 132, a.w1, a.ld1, a.d_z, a.ld_dz, row0, a.m);
+  const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
+  const int64_t row = row0 + i;
+  if (j < a.nz && row < a.m) {
+    float s = 0.f;
+#pragma unroll 8
+    for (int o = 0; o < 128; ++o) s = fmaf(DY[i * 132 + o], a.w1[(size_t)o * a.ld1 + CODE + j], s);
+    a.d_z[row * a.ld_dz + CODE + j] = s;
+  }
 }
 
 // Per-tile segment sums of a pre-activation gradient tile for the K-deduplicated fc1 weight

@@ -413,6 +413,41 @@ def module_loop_mpc(encode, generate, forward, frames, actions, rollouts, horizo
     return choices, torch.stack(chosen), torch.stack(errors)
 
 
+# ---------------------------------------------------------------------- differentiating the planner's score
+def goal_loss_and_grad(fwd_model, state, goal, actions):
+    """The score mpc_eval.py:159-165 gives a sampled action sequence -- the MSE between the forward model's Th-step
+    eval-mode rollout from `state` and the goal image -- and its gradient with respect to the actions.
+    state, goal [B,3,128,128]; actions [B,Th,4].  Returns (loss [B], d sum(loss) / d actions [B,Th,4]).  The rollout is
+    Th forwards of `fwd_model` (a ForwardAutoencoder in eval mode) inside input_gradients() and one backward through
+    them (ndp_fm_input_grads per step).  Not used by the drop-in scripts, which reproduce the reference's output."""
+    from .input_grad import input_gradients
+    if fwd_model.training:
+        raise _capi.NdpError("goal_loss_and_grad needs the forward model in eval mode (fwd_model.eval())")
+    acts = actions.detach().clone().requires_grad_(True)
+    with torch.enable_grad(), input_gradients():
+        cur = state.detach()
+        for t in range(int(acts.shape[1])):
+            cur = fwd_model(cur, acts[:, t])
+        loss = ((cur - goal.detach()) ** 2).flatten(1).mean(dim=1)
+        grad, = torch.autograd.grad(loss.sum(), acts)
+    return loss.detach(), grad
+
+
+def refine_actions(fwd_model, state, goal, actions, steps, optimizer_factory):
+    """`steps` optimiser steps on the actions against goal_loss_and_grad's score; optimizer_factory([actions]) -> a
+    torch optimiser (e.g. lambda p: torch.optim.SGD(p, lr=0.1)).  Returns (refined actions, loss [B] before each step)."""
+    acts = actions.detach().clone().requires_grad_(True)
+    opt = optimizer_factory([acts])
+    losses = []
+    for _ in range(int(steps)):
+        loss, grad = goal_loss_and_grad(fwd_model, state, goal, acts)
+        opt.zero_grad()
+        acts.grad = grad
+        opt.step()
+        losses.append(loss)
+    return acts.detach(), losses
+
+
 # ---------------------------------------------------------------------- what the three drop-in scripts share
 def eval_settings(kind, config, dataset, generator=None):
     """The scripts' hyperparameters, checked where the reference would fail (with a message instead of a shape error

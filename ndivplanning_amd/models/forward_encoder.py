@@ -15,16 +15,22 @@ no_grad, and training mode WITH autograd recording, where the residual carries a
 `ndp_fm_backward` (the reference's own loop, `loss = mse(model(cur, a), fut - cur); loss.backward(); optimizer.step()`,
 train_forward_model.py:102-110, runs unchanged, with torch's optimizer on the module's parameters).  The fast way to
 train is `ndivplanning_amd.forward_trainer.ForwardModelTrainer`, which owns the flat parameter vector the kernels read
-and runs forward, loss, backward and Adam in HIP without repacking.  There is no CPU path and no gradient with respect
-to the images or actions (the reference never asks for one): both raise.  `Encoder` / `Decoder` called on their own
-(nobody in the reference does) keep PyTorch's operators."""
+and runs forward, loss, backward and Adam in HIP without repacking.  There is no CPU path.  A gradient with respect to
+the images or actions (the reference never asks for one) raises -- except in eval mode inside
+`ndivplanning_amd.input_grad.input_gradients()`, where the output carries a grad_fn whose backward is
+`ndp_fm_input_grads` (the data-gradient chain alone, BatchNorm with the running statistics).  Each such forward keeps a
+workspace of its own from the module's pool until its backward has run, so a rollout of several forwards followed by
+one backward works.  `Encoder` / `Decoder` called on their own (nobody in the reference does) keep PyTorch's
+operators."""
 from functools import partial
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import _capi, flat_params
+from torch.autograd.function import once_differentiable
+
+from .. import _capi, flat_params, input_grad
 
 ENC_CHANNELS = (3, 64, 128, 256, 512, 1024)
 LAYER_NAMES = ("encoder.conv1", "encoder.conv2", "encoder.conv3", "encoder.conv4", "encoder.conv5", "encoder.conv6",
@@ -153,6 +159,62 @@ class _TrainingForward(torch.autograd.Function):
         return (None, None, None, None) + tuple(by_name.get(n) for n in ctx.names)
 
 
+class _EvalInputGradForward(torch.autograd.Function):
+    """out = model(state_cur, actions) in eval mode, differentiable with respect to state_cur (float frames) and actions:
+    forward = ndp_fm_forward(training = 0) on a workspace taken from the module's pool, backward = ndp_fm_input_grads on
+    that workspace, which then goes back to the pool."""
+
+    @staticmethod
+    def forward(ctx, model, state_cur, actions):
+        out, entry = model._forward_eval_pooled(state_cur, actions)
+        ctx.entry, ctx.serial, ctx.n = entry, entry["serial"], int(state_cur.shape[0])
+        ctx.state_dtype, ctx.action_dtype = state_cur.dtype, actions.dtype
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_out):
+        lib = _capi.load()
+        entry = ctx.entry
+        if entry["serial"] != ctx.serial or entry["consumed"]:
+            raise _capi.NdpError("backward through a ForwardAutoencoder forward whose activations are gone: its input gradients "
+                                 "were computed already (one backward per forward)")
+        want_state, want_actions = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        d = d_out.detach().contiguous().float()
+        if d.data_ptr() % 16:
+            d = d.clone()
+        d_state = torch.empty_like(d) if want_state else None
+        d_actions = torch.empty(ctx.n, 4, dtype=torch.float32, device=d.device) if want_actions else None
+        cache = entry["cache"]
+        with _capi.on_device(d):
+            _capi.check(lib.ndp_fm_input_grads(_capi.ptr(cache["params"]), _capi.ptr(d), ctx.n, _capi.ptr(d_state),
+                                               _capi.ptr(d_actions), _capi.ptr(entry["ws"]), _capi.stream_ptr(d.device)),
+                        "ndp_fm_input_grads")
+        entry["consumed"] = True
+        cache["pool"].append(entry)                        # (a cache that was replaced meanwhile is garbage with its pool)
+        return (None, d_state.to(ctx.state_dtype) if want_state else None,
+                d_actions.to(ctx.action_dtype) if want_actions else None)
+
+
+def saved_relu_masks(out):
+    """{site in RELU_SITES (feat1..5, up1..6, r1): bool tensor, NCHW}: which elements every ReLU of the forward pass that
+    produced `out` let through -- `out` as returned by an eval-mode ForwardAutoencoder inside input_gradients().  Read from
+    that call's own workspace (the maps of ForwardModelTrainer.activation), before or after its backward, as long as no
+    later forward has taken the workspace over."""
+    from ..forward_trainer import ForwardModelTrainer
+    fn = out.grad_fn
+    entry = getattr(fn, "entry", None)
+    if entry is None or entry["serial"] != fn.serial:
+        raise _capi.NdpError("saved_relu_masks: not the output of an input-gradient forward whose workspace is still its own")
+    lib, n = _capi.load(), fn.n
+    masks = {}
+    for name, (idx, side, ld, c0, c1) in ForwardModelTrainer._MAPS.items():
+        off = lib.ndp_fm_workspace_offset(n, idx)
+        view = entry["ws"][off:off + n * side * side * ld].view(n, side, side, ld)
+        masks[name] = (view[..., c0:c1] > 0).permute(0, 3, 1, 2).contiguous()
+    return masks
+
+
 class ForwardAutoencoder(nn.Module):
     def __init__(self):
         super().__init__()
@@ -180,16 +242,53 @@ class ForwardAutoencoder(nn.Module):
         """Drop the packed parameter copies: the next forward re-reads the module's tensors."""
         self.__dict__.pop("_ndp_cache", None)
 
-    def _forward_hip(self, state_cur, actions):
-        lib = _capi.load()
-        dev = state_cur.device
-        n = int(state_cur.shape[0])
+    def _cache_for(self, dev):
+        """The packed parameters / running statistics for `dev` (re-packed when a tensor of the module changed), with the
+        workspace of the plain forward and the pool of the input-gradient forwards."""
         cache = self.__dict__.get("_ndp_cache")
         if cache is None or cache["versions"] != self._versions() or cache["device"] != dev:
             params, stats = pack_module(self, dev)
             cache = {"versions": self._versions(), "device": dev, "params": params, "stats": stats, "ws": None, "n": 0,
-                     "packed": False}
+                     "packed": False, "pool": []}
             self.__dict__["_ndp_cache"] = cache
+        return cache
+
+    def _forward_eval_pooled(self, state_cur, actions):
+        """Eval-mode forward on a workspace of its own (for _EvalInputGradForward): (out, pool entry).  An entry is a
+        whole workspace, its second weight order packed once -- re-packed only with the cache, i.e. when _versions()
+        changes; it is out of the pool from here until its backward has run."""
+        lib = _capi.load()
+        dev = state_cur.device
+        n = int(state_cur.shape[0])
+        cache = self._cache_for(dev)
+        entry = next((e for e in cache["pool"] if e["n"] >= n), None)
+        if entry is not None:
+            cache["pool"].remove(entry)
+        else:
+            entry = {"ws": torch.empty(lib.ndp_fm_workspace_floats(n), dtype=torch.float32, device=dev), "n": n,
+                     "packed": False, "serial": 0, "cache": cache}
+        u8 = state_cur.dtype == torch.uint8
+        if u8 and tuple(state_cur.shape[1:]) != (128, 128, 3):
+            raise _capi.NdpError("byte frames must be [n,128,128,3], got %s" % (tuple(state_cur.shape),))
+        x = state_cur.detach().contiguous() if u8 else state_cur.detach().contiguous().float()
+        a = actions.detach().contiguous().float()
+        out = torch.empty(n, 3, 128, 128, dtype=torch.float32, device=dev)
+        entry["serial"], entry["consumed"] = entry["serial"] + 1, False
+        with _capi.on_device(x):
+            st = _capi.stream_ptr(dev)
+            if not entry["packed"]:
+                _capi.check(lib.ndp_fm_pack_params(_capi.ptr(cache["params"]), _capi.ptr(entry["ws"]), st), "ndp_fm_pack_params")
+                entry["packed"] = True
+            fn = lib.ndp_fm_forward_u8 if u8 else lib.ndp_fm_forward
+            _capi.check(fn(_capi.ptr(cache["params"]), _capi.ptr(cache["stats"]), _capi.ptr(x), _capi.ptr(a), n, 0,
+                           _capi.ptr(out), _capi.ptr(entry["ws"]), st), "ndp_fm_forward_u8" if u8 else "ndp_fm_forward")
+        return out, entry
+
+    def _forward_hip(self, state_cur, actions):
+        lib = _capi.load()
+        dev = state_cur.device
+        n = int(state_cur.shape[0])
+        cache = self._cache_for(dev)
         if cache["ws"] is None or cache["n"] < n:
             cache["ws"] = torch.empty(lib.ndp_fm_workspace_floats(n), dtype=torch.float32, device=dev)
             cache["n"], cache["packed"] = n, False
@@ -227,8 +326,14 @@ class ForwardAutoencoder(nn.Module):
         if actions.device != state_cur.device:
             raise _capi.NdpError("state_cur is on %s, actions on %s" % (state_cur.device, actions.device))
         if torch.is_grad_enabled() and (state_cur.requires_grad or actions.requires_grad):
-            raise NotImplementedError("ForwardAutoencoder gives no gradient with respect to its inputs (the reference "
-                                      "never asks for one)")
+            if not input_grad.enabled():
+                raise NotImplementedError("ForwardAutoencoder gives no gradient with respect to its inputs (the reference "
+                                          "never asks for one); in eval mode it does inside "
+                                          "ndivplanning_amd.input_grad.input_gradients()")
+            if self.training:
+                raise NotImplementedError("ForwardAutoencoder gives input gradients in eval mode only: in training mode the "
+                                          "batch statistics depend on the input")
+            return _EvalInputGradForward.apply(self, state_cur, actions)
         named = [(n, p) for n, p in self.named_parameters() if p.requires_grad]
         if torch.is_grad_enabled() and self.training and named:
             # the reference's own training loop: the residual gets a grad_fn whose backward is the HIP backward pass

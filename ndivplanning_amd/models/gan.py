@@ -9,11 +9,16 @@ a `torch.autograd.Function`; parameters live in one flat fp32 buffer per network
 (the `fc*.weight/bias` parameters are views into it), which is what the kernels
 and the fused trainer (`ndivplanning_amd.trainer.GanTrainer`) read and update.
 There is no CPU path: calling `forward` on CPU tensors raises.
+
+Gradients with respect to the INPUTS (z; action and state_code) are opt-in: inside
+`ndivplanning_amd.input_grad.input_gradients()` the outputs are differentiable in them too
+(ndp_g_input_grad / ndp_d_input_grad); outside it a request for one raises, as the
+reference's training path never makes one.
 """
 import torch
 import torch.nn as nn
 
-from .. import _capi
+from .. import _capi, input_grad
 
 CODE_DIM = _capi.CODE_DIM
 ACTION_DIM = _capi.ACTION_DIM
@@ -87,7 +92,7 @@ class _GForward(torch.autograd.Function):
         nz = module.noise_dim
         m, width = z.shape
         ld = z.stride(0)
-        need_grad = any(ctx.needs_input_grad[2:])
+        need_grad = any(ctx.needs_input_grad[2:]) or ctx.needs_input_grad[0]
         acts = _capi.empty(lib.ndp_g_acts_floats(m), z) if need_grad else None
         out = torch.empty((m, ACTION_DIM), dtype=torch.float32, device=z.device)
         noise_view = z[:, CODE_DIM:]
@@ -108,19 +113,27 @@ class _GForward(torch.autograd.Function):
         nz = module.noise_dim
         ld = z.stride(0)
         d_action = d_action.contiguous()
-        grad = torch.empty_like(flat)
+        want_params, want_z = any(ctx.needs_input_grad[2:]), ctx.needs_input_grad[0]
+        grad = torch.empty_like(flat) if want_params else None
         ws = _capi.empty(lib.ndp_g_bwd_ws_floats(m, nz), z)
         noise_view = z[:, CODE_DIM:]
+        d_z = torch.empty((m, CODE_DIM + nz), dtype=torch.float32, device=z.device) if want_z else None
         with _capi.on_device(z):
-            _capi.check(lib.ndp_g_backward(_capi.ptr(flat), nz, _capi.ptr(z), ld, 1, _capi.ptr(noise_view), ld, m,
-                                           _capi.ptr(acts), _capi.ptr(d_action), _capi.ptr(grad), _capi.ptr(ws),
-                                           _capi.stream_ptr()), "ndp_g_backward")
+            if want_params:
+                _capi.check(lib.ndp_g_backward(_capi.ptr(flat), nz, _capi.ptr(z), ld, 1, _capi.ptr(noise_view), ld, m,
+                                               _capi.ptr(acts), _capi.ptr(d_action), _capi.ptr(grad), _capi.ptr(ws),
+                                               _capi.stream_ptr()), "ndp_g_backward")
+            if want_z:
+                # after ndp_g_backward: one more launch on the dY1 it left in ws; parameters frozen: the data path alone
+                _capi.check(lib.ndp_g_input_grad(_capi.ptr(flat), nz, _capi.ptr(z), ld, m, _capi.ptr(acts),
+                                                 None if want_params else _capi.ptr(d_action), _capi.ptr(d_z),
+                                                 CODE_DIM + nz, _capi.ptr(ws), _capi.stream_ptr()), "ndp_g_input_grad")
         grads, off = [], 0
         for p in module._param_list():
             n = p.numel()
-            grads.append(grad[off:off + n].view(p.shape))
+            grads.append(grad[off:off + n].view(p.shape) if want_params else None)
             off += n
-        return (None, None) + tuple(grads)
+        return (d_z, None) + tuple(grads)
 
 
 class Decoder(_FlatParamsMixin, nn.Module):
@@ -151,9 +164,10 @@ class Decoder(_FlatParamsMixin, nn.Module):
             raise _capi.NdpError("Decoder expects [M, %d], got %s" % (CODE_DIM + self.noise_dim, tuple(z.shape)))
         if not 1 <= self.noise_dim <= _capi.MAX_NOISE_DIM:
             raise _capi.NdpError("noise_dim=%d outside 1..%d" % (self.noise_dim, _capi.MAX_NOISE_DIM))
-        if z.requires_grad:
+        if z.requires_grad and not input_grad.enabled():
             raise NotImplementedError("gradient w.r.t. the generator input is not part of the training path "
-                                      "(the reference detaches the codes, train_gan.py:152-153)")
+                                      "(the reference detaches the codes, train_gan.py:152-153); it is computed inside "
+                                      "ndivplanning_amd.input_grad.input_gradients()")
         if z.stride(1) != 1:
             z = z.contiguous()
         if self.fc1.weight.device != z.device:
@@ -172,6 +186,7 @@ class _DForward(torch.autograd.Function):
             _capi.check(lib.ndp_d_forward(_capi.ptr(flat), _capi.ptr(action), 1, _capi.ptr(code), code.stride(0), 1, m,
                                           _capi.ptr(logits), _capi.stream_ptr()), "ndp_d_forward")
         ctx.module, ctx.m = module, m
+        ctx.input_grads = input_grad.enabled()
         ctx.save_for_backward(action, code)
         return logits
 
@@ -183,23 +198,32 @@ class _DForward(torch.autograd.Function):
         flat = module.flat_parameters()
         want_params = any(ctx.needs_input_grad[3:])
         want_action = ctx.needs_input_grad[0]
-        if ctx.needs_input_grad[1]:
+        want_code = ctx.needs_input_grad[1]
+        if want_code and not ctx.input_grads:
             raise NotImplementedError("gradient w.r.t. state_code is not part of the training path "
-                                      "(codes are detached, train_gan.py:152-153)")
+                                      "(codes are detached, train_gan.py:152-153); it is computed when the forward call "
+                                      "runs inside ndivplanning_amd.input_grad.input_gradients()")
         d_logits = d_logits.contiguous().view(-1)
         grad = torch.empty_like(flat) if want_params else None
         d_action = torch.empty_like(action) if want_action else None
         ws = _capi.empty(lib.ndp_d_bwd_ws_floats(m), action) if want_params else None
+        d_code = torch.empty((m, CODE_DIM), dtype=torch.float32, device=action.device) if want_code else None
         with _capi.on_device(action):
-            _capi.check(lib.ndp_d_backward(_capi.ptr(flat), _capi.ptr(action), 1, _capi.ptr(code), code.stride(0), 1, m,
-                                           _capi.ptr(d_logits), _capi.ptr(grad), _capi.ptr(d_action), _capi.ptr(ws),
-                                           _capi.stream_ptr()), "ndp_d_backward")
+            if want_code:                                      # the same launches, k_d writes d_code on its way out
+                _capi.check(lib.ndp_d_input_grad(_capi.ptr(flat), _capi.ptr(action), 1, _capi.ptr(code), code.stride(0), 1,
+                                                 m, _capi.ptr(d_logits), _capi.ptr(grad), _capi.ptr(d_action),
+                                                 _capi.ptr(d_code), CODE_DIM, _capi.ptr(ws), _capi.stream_ptr()),
+                            "ndp_d_input_grad")
+            else:
+                _capi.check(lib.ndp_d_backward(_capi.ptr(flat), _capi.ptr(action), 1, _capi.ptr(code), code.stride(0), 1, m,
+                                               _capi.ptr(d_logits), _capi.ptr(grad), _capi.ptr(d_action), _capi.ptr(ws),
+                                               _capi.stream_ptr()), "ndp_d_backward")
         grads, off = [], 0
         for p in module._param_list():
             n = p.numel()
             grads.append(grad[off:off + n].view(p.shape) if want_params else None)
             off += n
-        return (d_action, None, None) + tuple(grads)
+        return (d_action, d_code, None) + tuple(grads)
 
 
 class Discriminator(_FlatParamsMixin, nn.Module):
