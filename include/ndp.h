@@ -478,6 +478,32 @@ int ndp_ae_train_grads_dp(const float *params, float *running_stats, const float
 int ndp_ae_grad_buckets(int64_t *offsets, int64_t *counts, int capacity, int *n_buckets);
 int ndp_ae_bucket_wait(int bucket, void *stream);
 
+/* Eval-mode Decoder (image_autoencoder.py:80-87 under .eval()) and reconstruction error.  The five BatchNorms are folded
+ * into the transposed convolutions ON THE HOST, in fp32: scale = gamma / sqrt(running_var + 1e-5), w' = w * scale[cout],
+ * b' = (b - running_mean) * scale + beta (models/image_autoencoder.py: fold_decoder_params); the kernels never read a
+ * BatchNorm tensor and launch no BatchNorm kernel.  folded_params: ndp_ae_decoder_param_floats() floats, deconv1..6, per
+ * layer the weight [cin_pad][kh][kw][cout_pad] then the bias [cout_pad] (deconv6's cout 3 -> 4); ndp_ae_decoder_layout:
+ * as ndp_fm_layout with what 0 / 1 (this network has no BatchNorm: what 2..5 is NDP_E_ARG).
+ * workspace: ndp_ae_decode_workspace_floats(n) floats (0 for n < 1); it grows with n only up to
+ * ndp_ae_decode_pass_images() images, the pass size in which ndp_ae_decode walks a larger batch.  Its head holds the
+ * second weight order of deconv1..5: call ndp_ae_decode_pack whenever folded_params changed or the workspace is new.
+ *   ndp_ae_decode   codes [n,128] -> recon_f32 [n,3,128,128] (NCHW, or NULL) and / or recon_u8 [n,128,128,3] (HWC bytes,
+ *                   trunc(((y + 1) / 2) * 255) in fp32: the reference's denorm(...).astype(np.uint8),
+ *                   train_autoencoder.py:42-43, 97-100; or NULL).  With ONE target -- target_f32 [n,3,128,128] or
+ *                   target_u8 [n,128,128,3] byte frames, normalised as the loader does, (b / 255 - 0.5) * 2 --
+ *                   sq_err[i] (or NULL) = the mean squared error of image i over its 49,152 values and mean_err[0] (or
+ *                   NULL) = the mean of sq_err over the batch.  Fixed summation order, no float atomics: two calls give
+ *                   the same bits.  Two targets, sq_err / mean_err without a target, no output at all, n < 1: NDP_E_ARG,
+ *                   nothing launched.  Float buffers 16-byte aligned, byte buffers 4-byte aligned. */
+int64_t ndp_ae_decoder_param_floats(void);
+int ndp_ae_decoder_layout(int what, int index, int64_t *offset, int64_t *dims /* [6] */);
+int64_t ndp_ae_decode_workspace_floats(int64_t n_images);
+int64_t ndp_ae_decode_pass_images(void);
+int ndp_ae_decode_pack(const float *folded_params, float *workspace, void *stream);
+int ndp_ae_decode(const float *folded_params, const float *codes, int64_t n_images, float *recon_f32,
+                  unsigned char *recon_u8, const float *target_f32, const unsigned char *target_u8,
+                  float *sq_err, float *mean_err, float *workspace, void *stream);
+
 /* ------------------------------------------------------------- evaluation ---
  * The glue of the evaluation scripts (control_evaluation.py, complete_eval.py, mpc_eval.py) between the encoder, the
  * generator and the forward model (csrc/ndp_eval.inc).  Images are `values` contiguous floats each (3*128*128 for the

@@ -138,6 +138,13 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
     "ndp_ae_grad_buckets": (c_int, [POINTER(c_int64), POINTER(c_int64), c_int, POINTER(c_int)]),
     "ndp_ae_bucket_wait": (c_int, [c_int, c_void_p]),
+    "ndp_ae_decoder_param_floats": (c_int64, []),
+    "ndp_ae_decoder_layout": (c_int, [c_int, c_int, POINTER(c_int64), POINTER(c_int64)]),
+    "ndp_ae_decode_workspace_floats": (c_int64, [c_int64]),
+    "ndp_ae_decode_pass_images": (c_int64, []),
+    "ndp_ae_decode_pack": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "ndp_ae_decode": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p]),
     "ndp_eval_score_select": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ndp_eval_mse_ws_floats": (c_int64, [c_int64]),

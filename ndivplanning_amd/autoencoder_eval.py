@@ -1,0 +1,176 @@
+"""What a trained image autoencoder is asked after training, on the gfx950 kernels: what a code decodes to, what the
+reconstructions look like and how large the reconstruction error is on held-out trajectories.
+
+    decode(decoder, codes)                    codes [n,128] / [n,128,1,1]  ->  images, float NCHW or bytes HWC
+    reconstruct(encoder, decoder, images)     decoder(encoder(x)), the MSE of every image against x and their mean
+    evaluate(encoder, decoder, dataset)       the same over a PushDataset / SyntheticPushDataset (JPEG mode included)
+    python -m ndivplanning_amd.autoencoder_eval --encoder encoder_N.pt --decoder decoder_N.pt --data DIR [--save-dir DIR]
+
+The codes come from the eval-mode `Encoder` (ndp_encoder_forward / _u8), the images from `ndp_ae_decode`
+(csrc/ndp_autoencoder.inc: the eval-mode decoder with its BatchNorms folded into the weights, and an output kernel that
+also writes the reference's bytes, `denorm(...).astype(np.uint8)` of train_autoencoder.py:42-43, 97-100, and the squared
+error against the input).  Both modules are used in eval mode; there is no CPU path (`NdpError`), and nothing here
+synchronises with the host: every result is a device tensor."""
+import importlib
+import os
+from argparse import ArgumentParser
+
+import torch
+
+from . import _capi
+from . import jpeg as jpeg_frames
+from .models import image_autoencoder as IA
+
+OUTPUTS = ("float", "bytes")
+
+
+def _check_out(out):
+    if out not in OUTPUTS:
+        raise ValueError("out must be 'float' or 'bytes', got %r" % (out,))
+
+
+def _require_gpu(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("%s must be a torch.Tensor" % name)
+    if not t.is_cuda:
+        raise _capi.NdpError("%s is on %s: ndivplanning_amd computes only on a ROCm GPU (no CPU fallback)" % (name, t.device))
+    return t
+
+
+def _require_eval(**modules):
+    for name, m in modules.items():
+        if m.training:
+            raise _capi.NdpError("the %s is in training mode: call .eval() first (these are the eval-mode kernels)" % name)
+
+
+def decode(decoder, codes, out="float"):
+    """The image every code decodes to: float32 [n,3,128,128] in [-1,1] (out="float") or uint8 [n,128,128,3], the
+    reference's denormalised bytes (out="bytes")."""
+    _check_out(out)
+    _require_gpu(codes, "codes")
+    _require_eval(decoder=decoder)
+    return IA.decoder_forward_hip(decoder, codes, out=out)[0]
+
+
+def _encode(encoder, images):
+    _require_gpu(images, "images")
+    with torch.no_grad():
+        return encoder(images.detach())
+
+
+def reconstruct(encoder, decoder, images, out="float", errors=True):
+    """(reconstruction, per-image MSE [n], mean MSE [1]) of `images`, float32 [n,3,128,128] in [-1,1] or byte frames
+    uint8 [n,128,128,3] (normalised as the loader does, as the kernels read them).  The error is against the input
+    itself; errors=False: (reconstruction, None, None)."""
+    _check_out(out)
+    _require_eval(encoder=encoder, decoder=decoder)
+    codes = _encode(encoder, images)
+    return IA.decoder_forward_hip(decoder, codes, out=out, target=images if errors else None, errors=errors)
+
+
+def _batches(dataset, batch_size, device, jpeg_decoder):
+    """The dataset's frames, `batch_size` trajectories at a time, as the kernels take them: float NCHW, or byte frames
+    for a dataset that yields bytes or JPEG streams.  The trajectories are read by index in order -- no DataLoader, so
+    no random number of the process is drawn (validation inside a training run must not move its shuffling)."""
+    for lo in range(0, len(dataset), batch_size):
+        items = [dataset[i][0] for i in range(lo, min(lo + batch_size, len(dataset)))]
+        if jpeg_decoder is not None:
+            buffer, offsets = jpeg_frames.pack_jpegs([s for item in items for s in item])
+            yield jpeg_decoder.decode(buffer, offsets)
+        else:
+            frames = torch.stack(items).to(device, non_blocking=True)
+            yield frames.view(-1, *frames.shape[2:]).contiguous()
+
+
+def evaluate(encoder, decoder, dataset, batch_size=16, device=None, keep=0):
+    """The reconstruction error over every frame of `dataset` (PushDataset / SyntheticPushDataset: images, byte frames or
+    JPEG streams, which `jpeg.JpegDecoder` decodes on the device): (mean MSE [1], per-image MSE [frames]) -- device
+    tensors, no host synchronisation per batch.  keep > 0: also the first `keep` (input bytes, reconstruction bytes)
+    pairs, uint8 [keep,128,128,3] each, as a third result."""
+    _require_eval(encoder=encoder, decoder=decoder)
+    device = torch.device(device) if device is not None else next(decoder.parameters()).device
+    if device.type != "cuda":
+        raise _capi.NdpError("the modules are on %s: ndivplanning_amd computes only on a ROCm GPU (no CPU fallback)" % device)
+    if len(dataset) == 0 or int(batch_size) < 1:
+        raise ValueError("evaluate needs a non-empty dataset and batch_size >= 1")
+    jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
+    per_image, pairs, kept = [], [], 0
+    for frames in _batches(dataset, int(batch_size), device, jpeg_decoder):
+        recon, sq, _ = reconstruct(encoder, decoder, frames, out="bytes", errors=True)
+        per_image.append(sq)
+        if kept < keep:
+            k = min(keep - kept, int(frames.shape[0]))
+            pairs.append((_to_bytes(frames[:k]), recon[:k]))
+            kept += k
+    if jpeg_decoder is not None:
+        jpeg_decoder.finish()
+    per_image = torch.cat(per_image)
+    mean = per_image.double().mean().float().view(1)                     # (of the fp32 per-image values, in fp64: as ndp_ae_decode's)
+    if keep > 0:
+        return mean, per_image, (torch.cat([a for a, _ in pairs]), torch.cat([b for _, b in pairs]))
+    return mean, per_image
+
+
+def _to_bytes(frames):
+    """Input frames as displayable bytes HWC: byte frames as they are, floats denormalised as the reference does."""
+    if frames.dtype == torch.uint8:
+        return frames
+    return (((frames + 1.0) / 2.0) * 255.0).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+
+def save_pairs(inputs, recons, save_dir):
+    """input_NNN.png / recon_NNN.png from byte frames [k,128,128,3] (PIL)."""
+    from PIL import Image
+    os.makedirs(save_dir, exist_ok=True)
+    paths = []
+    for i, (a, b) in enumerate(zip(inputs.cpu().numpy(), recons.cpu().numpy())):
+        for name, frame in (("input", a), ("recon", b)):
+            path = os.path.join(save_dir, "%s_%03d.png" % (name, i))
+            Image.fromarray(frame).save(path)
+            paths.append(path)
+    return paths
+
+
+def load_module(path, device):
+    """torch.load of a whole-module checkpoint of train_autoencoder.py (a local, trusted file: module pickles need
+    weights_only=False), in eval mode on `device`.  The checkpoints name the classes `models.image_autoencoder.*`: the
+    root-level shim of that name is imported first where it is on sys.path."""
+    try:
+        importlib.import_module("models.image_autoencoder")
+    except ImportError:
+        pass
+    return torch.load(path, map_location="cpu", weights_only=False).to(device).eval()
+
+
+def make_parser():
+    parser = ArgumentParser(description="Reconstruction error (and reconstructions) of a trained image autoencoder")
+    parser.add_argument("--encoder", required=True, help="whole-module checkpoint (encoder_N.pt of train_autoencoder.py)")
+    parser.add_argument("--decoder", required=True, help="whole-module checkpoint (decoder_N.pt)")
+    parser.add_argument("--data", required=True, help="trajectory directory, or synthetic:<N>:images|jpeg")
+    parser.add_argument("--raw-jpeg", action="store_true",
+                        help="read the directory's JPEG streams as they are and decode them on the GPU")
+    parser.add_argument("--batch-size", type=int, default=16, help="trajectories per batch")
+    parser.add_argument("--device", default="cuda")
+    parser.add_argument("--save-dir", default=None, help="write the first --num-save input / reconstruction pairs here as PNG")
+    parser.add_argument("--num-save", type=int, default=8)
+    return parser
+
+
+def main(argv=None, log=print):
+    args = make_parser().parse_args(argv)
+    from .train_autoencoder import make_dataset
+    device = torch.device(args.device)
+    encoder, decoder = load_module(args.encoder, device), load_module(args.decoder, device)
+    dataset = make_dataset(args.data, raw_jpeg=args.raw_jpeg)
+    keep = args.num_save if args.save_dir else 0
+    result = evaluate(encoder, decoder, dataset, batch_size=args.batch_size, device=device, keep=keep)
+    mean = float(result[0].item())
+    log("val_recon_loss:", mean, "frames:", int(result[1].numel()))
+    if args.save_dir:
+        save_pairs(result[2][0], result[2][1], args.save_dir)
+        log("wrote %d pairs to %s" % (int(result[2][0].shape[0]), args.save_dir))
+    return mean
+
+
+if __name__ == "__main__":
+    main()

@@ -88,6 +88,36 @@ __device__ __forceinline__ void ae_out_stage_weights(float* Ws, const float* __r
   __syncthreads();
 }
 
+// acc = bias + the (at most) four taps' 64-channel sums of output pixel (oy, ox) of image img: the arithmetic of deconv6,
+// shared by the training kernel (k_ae_out_fwd_loss) and the eval-mode one (k_ae_out_fwd) -- one order of fmaf per channel
+__device__ __forceinline__ void ae_out_pixel(float (&acc)[3], const float* up5, const float* Ws, const float* bias,
+                                             int64_t img, int oy, int ox) {
+  acc[0] = bias[0]; acc[1] = bias[1]; acc[2] = bias[2];
+#pragma unroll
+  for (int ay = 0; ay < 2; ++ay) {
+    const int ky = ((oy + 1) & 1) + 2 * ay, iy = (oy + 1 - ky) >> 1;
+    if ((unsigned)iy >= 64u) continue;
+#pragma unroll
+    for (int ax = 0; ax < 2; ++ax) {
+      const int kx = ((ox + 1) & 1) + 2 * ax, ix = (ox + 1 - kx) >> 1;
+      if ((unsigned)ix >= 64u) continue;
+      const float* src = up5 + ((img << 12) + iy * 64 + ix) * 64;
+      const float* wt = Ws + (ky * 4 + kx) * 4;
+#pragma unroll 4
+      for (int c4 = 0; c4 < 16; ++c4) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * c4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const f32x4 wv = *reinterpret_cast<const f32x4*>(wt + (4 * c4 + e) * 64);
+          acc[0] = fmaf(v[e], wv[0], acc[0]);
+          acc[1] = fmaf(v[e], wv[1], acc[1]);
+          acc[2] = fmaf(v[e], wv[2], acc[2]);
+        }
+      }
+    }
+  }
+}
+
 // one thread per output pixel
 __global__ __launch_bounds__(kThreads) void k_ae_out_fwd_loss(AeOutArgs a) {
   __shared__ __attribute__((aligned(16))) float Ws[kAeOutW];
@@ -99,30 +129,8 @@ __global__ __launch_bounds__(kThreads) void k_ae_out_fwd_loss(AeOutArgs a) {
   if (p < a.npix) {
     const int64_t img = p >> 14;
     const int oy = (int)(p >> 7) & 127, ox = (int)p & 127;
-    float acc[3] = {a.bias[0], a.bias[1], a.bias[2]};
-#pragma unroll
-    for (int ay = 0; ay < 2; ++ay) {
-      const int ky = ((oy + 1) & 1) + 2 * ay, iy = (oy + 1 - ky) >> 1;
-      if ((unsigned)iy >= 64u) continue;
-#pragma unroll
-      for (int ax = 0; ax < 2; ++ax) {
-        const int kx = ((ox + 1) & 1) + 2 * ax, ix = (ox + 1 - kx) >> 1;
-        if ((unsigned)ix >= 64u) continue;
-        const float* src = a.up5 + ((img << 12) + iy * 64 + ix) * 64;
-        const float* wt = Ws + (ky * 4 + kx) * 4;
-#pragma unroll 4
-        for (int c4 = 0; c4 < 16; ++c4) {
-          const f32x4 v = *reinterpret_cast<const f32x4*>(src + 4 * c4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const f32x4 wv = *reinterpret_cast<const f32x4*>(wt + (4 * c4 + e) * 64);
-            acc[0] = fmaf(v[e], wv[0], acc[0]);
-            acc[1] = fmaf(v[e], wv[1], acc[1]);
-            acc[2] = fmaf(v[e], wv[2], acc[2]);
-          }
-        }
-      }
-    }
+    float acc[3];
+    ae_out_pixel(acc, a.up5, Ws, a.bias, img, oy, ox);
     const float scale = 2.0f / (3.0f * (float)a.npix);
     const int64_t base = img * 3 * 16384 + (p & 16383);
 #pragma unroll
@@ -138,6 +146,92 @@ __global__ __launch_bounds__(kThreads) void k_ae_out_fwd_loss(AeOutArgs a) {
   sq = block_sum(sq, red);
   const float g0 = block_sum(g[0], red), g1 = block_sum(g[1], red), g2 = block_sum(g[2], red);
   if (threadIdx.x == 0) *reinterpret_cast<f32x4*>(a.partial + 4 * (size_t)blockIdx.x) = f32x4{sq, g0, g1, g2};
+}
+
+// ------------------------------------------------------------------------------------------ eval-mode output layer
+// y = tanh(b + deconv6(up5)) with nothing of the training loss in it: no g6, no gradient sums.  One thread per output
+// pixel, the arithmetic of k_ae_out_fwd_loss (ae_out_pixel).  Outputs, each optional: floats NCHW [n][3][128][128] and
+// bytes HWC [n][128][128][3] = trunc(((y + 1) / 2) * 255) in fp32, the reference's denorm(...).astype(np.uint8)
+// (train_autoencoder.py:42-43, 97-100).  TGT: what the reconstruction is compared with -- 0 nothing, 1 floats NCHW,
+// 2 byte frames HWC normalised through u8_norm_table (the floats the loader would have uploaded) -- and then the
+// workgroup's squared-error sum goes to partial[block].  A workgroup is 256 consecutive pixels of ONE image (16,384 =
+// 64 x 256), so partial[64 i .. 64 i + 63] are image i's; a workgroup's 768 bytes (in and out) are contiguous and 4-byte
+// aligned: they pass through LDS as 192 dwords.
+struct AeEvalOutArgs {
+  const float* up5; const float* w; const float* bias;
+  const float* tgt_f32; const unsigned char* tgt_u8;
+  float* recon; unsigned char* recon_u8; float* partial;
+};
+template <int TGT>
+__global__ __launch_bounds__(kThreads) void k_ae_out_fwd(AeEvalOutArgs a) {
+  __shared__ __attribute__((aligned(16))) float Ws[kAeOutW];
+  __shared__ float red[4];
+  __shared__ float lut[TGT == 2 ? 256 : 1];
+  __shared__ unsigned int tin[TGT == 2 ? 192 : 1];
+  __shared__ unsigned int tout[192];
+  const int t = threadIdx.x;
+  const int64_t p = (int64_t)blockIdx.x * kThreads + t;               // (the grid is exactly n x 64 workgroups)
+  if (TGT == 2) {
+    u8_norm_table(lut);
+    if (t < 192) tin[t] = reinterpret_cast<const unsigned int*>(a.tgt_u8 + (int64_t)blockIdx.x * (kThreads * 3))[t];
+  }
+  ae_out_stage_weights(Ws, a.w);                                       // (ends with a barrier: lut and tin are visible)
+  const int64_t img = p >> 14;
+  const int oy = (int)(p >> 7) & 127, ox = (int)p & 127;
+  float acc[3];
+  ae_out_pixel(acc, a.up5, Ws, a.bias, img, oy, ox);
+  const int64_t base = img * 3 * 16384 + (p & 16383);
+  float sq = 0.f;
+#pragma unroll
+  for (int e = 0; e < 3; ++e) {
+    const float y = tanhf(acc[e]);
+    if (a.recon != nullptr) a.recon[base + e * 16384] = y;
+    if (a.recon_u8 != nullptr)
+      reinterpret_cast<unsigned char*>(tout)[3 * t + e] = (unsigned char)(int)(((y + 1.0f) / 2.0f) * 255.0f);
+    if (TGT != 0) {
+      const float x = TGT == 1 ? a.tgt_f32[base + e * 16384] : lut[reinterpret_cast<const unsigned char*>(tin)[3 * t + e]];
+      const float d = y - x;
+      sq += d * d;
+    }
+  }
+  if (a.recon_u8 != nullptr) {                                         // (uniform)
+    __syncthreads();
+    if (t < 192) reinterpret_cast<unsigned int*>(a.recon_u8 + (int64_t)blockIdx.x * (kThreads * 3))[t] = tout[t];
+  }
+  if (TGT != 0) {
+    sq = block_sum(sq, red);
+    if (t == 0) a.partial[blockIdx.x] = sq;
+  }
+}
+
+// The errors of one pass of np images: thread i sums image i's 64 partial sums in index order (fp32) -> sq_err[i] =
+// sum / 49,152; thread 0 then adds the pass's per-image values, in image order, to the call's running sum -- a double,
+// so that the batch mean is the correctly rounded mean of the fp32 per-image values whatever the batch size -- and the
+// last pass writes mean_err = running / n.  No atomics: two runs give the same bits.
+constexpr int kAeDecPass = 128;                                        // images per pass of ndp_ae_decode
+struct AeErrArgs { const float* partial; float* sq_err; float* mean_err; double* running; int np, first, last; int64_t n; };
+__global__ __launch_bounds__(kThreads) void k_ae_err_finish(AeErrArgs a) {
+  __shared__ float vals[kAeDecPass];
+  const int i = threadIdx.x;
+  if (i < a.np) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(a.partial + 64 * i);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const f32x4 v = src[j];
+      s += v[0]; s += v[1]; s += v[2]; s += v[3];
+    }
+    s = s / 49152.0f;
+    vals[i] = s;
+    if (a.sq_err != nullptr) a.sq_err[i] = s;
+  }
+  __syncthreads();
+  if (i == 0) {
+    double r = a.first ? 0.0 : *a.running;
+    for (int j = 0; j < a.np; ++j) r += (double)vals[j];
+    *a.running = r;
+    if (a.last && a.mean_err != nullptr) *a.mean_err = (float)(r / (double)a.n);
+  }
 }
 
 // d up5 [i][ci] = sum over the 16 taps (ky, kx) and co < 3 of g6[(2 iy - 1 + ky, 2 ix - 1 + kx)][co] * W[ci][ky kx][co].
@@ -508,9 +602,146 @@ static int ae_train_grads(const char* name, const float* params, float* running_
   return ae_backward(st, params, n_images, grad, ws, sync, buckets);
 }
 
+// ------------------------------------------------------------------------------------------ eval-mode decoder
+// Decoder.forward in eval mode (image_autoencoder.py:80-87) with the BatchNorms folded into the transposed convolutions on
+// the host (models/image_autoencoder.py: fold_decoder_params; relu(bn(deconv(x))) = relu(deconv'(x)) with w' = w * scale,
+// b' = (b - running_mean) * scale + beta, scale = gamma / sqrt(running_var + eps)).  The folded decoder is a network of
+// its own in the sense of ndp_forward_model.inc's tables: deconv1..6, NO BatchNorm, no gradient buckets; its parameter
+// vector is [W (P1)][bias] per layer, the second weight order of deconv1..5 is made from it by k_fm_pack into the head of
+// the decode workspace.  Launches per pass: deconv1 (mode 3; k_fm_rows_cls up to 4 images), deconv2..4 (mode 1, K split
+// where fm_gemm chooses it: + k_fm_splitk_reduce), deconv5 (k_fm_deconv32<true> from 16 images, else mode 1), every one
+// with bias + ReLU in its epilogue, writing the next layer's input map; k_ae_out_fwd; with a target k_ae_err_finish.
+// Not one BatchNorm launch, not one map written twice.
+constexpr int kAeDecLayers = 6;
+static const FmLayer kAeDec[kAeDecLayers] = {
+    {FM_DECONV, 128, 1024, 1, 4, 4, 1, 0, 128, 1024, FM_P2_DECONV1},    // 0 deconv1
+    {FM_DECONV, 1024, 512, 4, 8, 4, 2, 1, 1024, 512, FM_P2_DECONV_S2},  // 1 deconv2
+    {FM_DECONV, 512, 256, 8, 16, 4, 2, 1, 512, 256, FM_P2_DECONV_S2},   // 2 deconv3
+    {FM_DECONV, 256, 128, 16, 32, 4, 2, 1, 256, 128, FM_P2_DECONV_S2},  // 3 deconv4
+    {FM_DECONV, 128, 64, 32, 64, 4, 2, 1, 128, 64, FM_P2_DECONV_S2},    // 4 deconv5
+    {FM_DECONV, 64, 3, 64, 128, 4, 2, 1, 64, 4, FM_P2_NONE},            // 5 deconv6 (k_ae_out_fwd reads P1)
+};
+static const FmNet kAeDecNet = {kAeDec, kAeDecLayers, 0, nullptr, nullptr, 0};
+// Workspace (floats): [P2 of deconv1..5][up1..up5 x min(n, kAeDecPass) images][squared-error partial sums: 64 per image
+// of a pass][the running sum of the per-image errors: one double][split-K partial sums]
+enum AeDecTensor { ADT_U1 = 0, ADT_U2, ADT_U3, ADT_U4, ADT_U5, ADT_COUNT };
+static const int64_t kAeDecTensorFloats[ADT_COUNT] = {16 * 1024, 64 * 512, 256 * 256, 1024 * 128, 4096 * 64};   // per image
+static int64_t ae_dec_cap(int64_t n) { return n < kAeDecPass ? n : kAeDecPass; }
+static int64_t ae_dec_tensor_offset(int64_t cap, int t) {
+  int64_t o = fm_p2_offset(kAeDecNet, kAeDecLayers);
+  for (int i = 0; i < t; ++i) o += cap * kAeDecTensorFloats[i];
+  return o;
+}
+static int64_t ae_dec_ws_floats(int64_t n) {
+  const int64_t cap = ae_dec_cap(n);
+  return ae_dec_tensor_offset(cap, ADT_COUNT) + cap * 64 + 4 + kFmPartCap;
+}
+
+// one pass: np <= kAeDecPass codes -> up5 in the workspace
+static int ae_decode_pass(hipStream_t st, const float* P, const float* codes, int64_t np, const FmWs& ws, float* const* t) {
+  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kAeDecNet, l)); };
+  auto B = [&](int l) { return P + fm_param_offset(kAeDecNet, l, true); };
+  int rc;
+#define AE_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
+  AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv1]", 3, {const_cast<float*>(codes), 128}, 1, 1, W2(0), B(0), {t[ADT_U1], 1024}, 4, 1, np, 128, 1024, 1, 0, 1, 0, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv2]", 1, {t[ADT_U1], 1024}, 4, 1, W2(1), B(1), {t[ADT_U2], 512}, 8, 4, np, 1024, 512, 2, 0, 1, 0, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv3]", 1, {t[ADT_U2], 512}, 8, 1, W2(2), B(2), {t[ADT_U3], 256}, 16, 8, np, 512, 256, 2, 0, 1, 0, ws));
+  AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv4]", 1, {t[ADT_U3], 256}, 16, 1, W2(3), B(3), {t[ADT_U4], 128}, 32, 16, np, 256, 128, 2, 0, 1, 0, ws));
+  if (np * 1024 / kFmBM * 2 >= 256)                                    // (as ae_forward_loss: enough tiles from 16 images)
+    AE_TRY(fm_deconv32(st, "k_fm_gemm[aed.deconv5]", {t[ADT_U4], 128}, 32, W2(4), B(4), {t[ADT_U5], 64}, np, 128, 64, fm_ep_none(), ws, true));
+  else AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv5]", 1, {t[ADT_U4], 128}, 32, 1, W2(4), B(4), {t[ADT_U5], 64}, 64, 32, np, 128, 64, 2, 0, 1, 0, ws));
+#undef AE_TRY
+  return NDP_OK;
+}
+
+static int ae_decode(const float* params, const float* codes, int64_t n, float* recon_f32, unsigned char* recon_u8,
+                     const float* target_f32, const unsigned char* target_u8, float* sq_err, float* mean_err,
+                     float* workspace, void* stream) {
+  NDP_CHECK_ARG(params && codes && workspace && n >= 1, "ndp_ae_decode: bad arguments");
+  NDP_CHECK_ARG(!(target_f32 && target_u8), "ndp_ae_decode: at most one target");
+  const bool tgt = target_f32 || target_u8;
+  NDP_CHECK_ARG(tgt || (!sq_err && !mean_err), "ndp_ae_decode: sq_err / mean_err need a target");
+  NDP_CHECK_ARG(recon_f32 || recon_u8 || sq_err || mean_err, "ndp_ae_decode: no output requested");
+  NDP_CHECK_ARG(aligned16(params) && aligned16(codes) && aligned16(workspace) && (!recon_f32 || aligned16(recon_f32)) &&
+                (!target_f32 || aligned16(target_f32)), "ndp_ae_decode: float buffers must be 16-byte aligned");
+  NDP_CHECK_ARG((reinterpret_cast<uintptr_t>(recon_u8) & 3) == 0 && (reinterpret_cast<uintptr_t>(target_u8) & 3) == 0,
+                "ndp_ae_decode: byte buffers must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  fm_attrs();
+  const int64_t cap = ae_dec_cap(n);
+  FmWs ws;
+  memset(&ws, 0, sizeof(ws));
+  ws.p2 = workspace;
+  float* t[ADT_COUNT];
+  for (int i = 0; i < ADT_COUNT; ++i) t[i] = workspace + ae_dec_tensor_offset(cap, i);
+  float* partial = workspace + ae_dec_tensor_offset(cap, ADT_COUNT);
+  double* running = reinterpret_cast<double*>(partial + cap * 64);
+  ws.part = partial + cap * 64 + 4;
+  const bool errs = tgt && (sq_err || mean_err);
+  for (int64_t i0 = 0; i0 < n; i0 += kAeDecPass) {
+    const int64_t np = n - i0 < kAeDecPass ? n - i0 : kAeDecPass;
+    int rc = ae_decode_pass(st, params, codes + i0 * 128, np, ws, t);
+    if (rc) return rc;
+    AeEvalOutArgs o;
+    memset(&o, 0, sizeof(o));
+    o.up5 = t[ADT_U5]; o.w = params + fm_param_offset(kAeDecNet, 5, false); o.bias = params + fm_param_offset(kAeDecNet, 5, true);
+    o.recon = recon_f32 ? recon_f32 + i0 * 49152 : nullptr;
+    o.recon_u8 = recon_u8 ? recon_u8 + i0 * 49152 : nullptr;
+    o.partial = partial;
+    const dim3 grid((unsigned)(np * 64));
+    {
+      KTimer kt("k_ae_out_fwd", st);
+      if (errs && target_f32) {
+        o.tgt_f32 = target_f32 + i0 * 49152;
+        hipLaunchKernelGGL(k_ae_out_fwd<1>, grid, dim3(kThreads), 0, st, o);
+      } else if (errs) {
+        o.tgt_u8 = target_u8 + i0 * 49152;
+        hipLaunchKernelGGL(k_ae_out_fwd<2>, grid, dim3(kThreads), 0, st, o);
+      } else {
+        hipLaunchKernelGGL(k_ae_out_fwd<0>, grid, dim3(kThreads), 0, st, o);
+      }
+    }
+    rc = check_launch("k_ae_out_fwd");
+    if (rc) return rc;
+    if (!errs) continue;
+    AeErrArgs e;
+    memset(&e, 0, sizeof(e));
+    e.partial = partial; e.sq_err = sq_err ? sq_err + i0 : nullptr; e.mean_err = mean_err; e.running = running;
+    e.np = (int)np; e.first = i0 == 0; e.last = i0 + np == n; e.n = n;
+    KTimer kt("k_ae_err_finish", st);
+    hipLaunchKernelGGL(k_ae_err_finish, dim3(1), dim3(kThreads), 0, st, e);
+    rc = check_launch("k_ae_err_finish");
+    if (rc) return rc;
+  }
+  return NDP_OK;
+}
+
 }  // namespace ndp
 
 extern "C" {
+
+int64_t ndp_ae_decoder_param_floats(void) { return ndp::fm_param_floats(ndp::kAeDecNet); }
+int ndp_ae_decoder_layout(int what, int index, int64_t* offset, int64_t* dims) {
+  return ndp::fm_layout(ndp::kAeDecNet, "ndp_ae_decoder_layout", what, index, offset, dims);
+}
+int64_t ndp_ae_decode_pass_images(void) { return ndp::kAeDecPass; }
+int64_t ndp_ae_decode_workspace_floats(int64_t n_images) { return n_images < 1 ? 0 : ndp::ae_dec_ws_floats(n_images); }
+
+int ndp_ae_decode_pack(const float* folded_params, float* workspace, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(folded_params && workspace && aligned16(folded_params) && aligned16(workspace), "ndp_ae_decode_pack: bad arguments");
+  FmWs ws;
+  memset(&ws, 0, sizeof(ws));
+  ws.p2 = workspace;
+  return fm_pack((hipStream_t)stream, kAeDecNet, folded_params, ws);
+}
+
+int ndp_ae_decode(const float* folded_params, const float* codes, int64_t n_images, float* recon_f32, unsigned char* recon_u8,
+                  const float* target_f32, const unsigned char* target_u8, float* sq_err, float* mean_err, float* workspace,
+                  void* stream) {
+  return ndp::ae_decode(folded_params, codes, n_images, recon_f32, recon_u8, target_f32, target_u8, sq_err, mean_err,
+                        workspace, stream);
+}
 
 int64_t ndp_ae_param_floats(void) { return ndp::fm_param_floats(ndp::kAeNet); }
 int64_t ndp_ae_stat_floats(void) { return ndp::fm_stat_offset(ndp::kAeBns, false); }

@@ -507,12 +507,15 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
 // those classes: 9 operand tiles and 9 barriers per 32 channels for the same MFMAs, a quarter of the workgroups.
 // Weights: the mode-1 order [cls][co][kh'][kw'][ci]; class (py, px) meets tap (dy, dx) in {-1, 0, 1}^2 at kh' = dy - py + 1,
 // kw' = dx - px + 1 when both are 0 or 1.  Statistics (mode 1) over the 32 output channels, all classes together.
+// RELU: the stored output is max(v, 0) (the eval-mode decoder of ndp_autoencoder.inc, BatchNorm folded into w and bias: no
+// statistics there); the training paths' instantiation, RELU = false, is the kernel as it was.
 struct FmDcArgs {
   const float* src; const float* w; const float* bias; float* out;
   int src_ld, SH, SW, out_ld, M, C, N, mtiles;        // N output channels: blockIdx.y = which 32 of them
   FmStatEp ep;
 };
 constexpr int fm_deconv32_lds_floats() { return 2 * (kFmBM + 128) * kFmLD; }
+template <bool RELU>
 __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int BM = kFmBM, BK = kFmBK, LD = kFmLD, NB = 128;           // NB: 4 classes x 32 output channels
@@ -647,7 +650,11 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
       float* orow = a.out + pix * a.out_ld + co0;
 #pragma unroll
       for (int jn = 0; jn < 2; ++jn) {
-        const f32x4 v = acc[i][u * 2 + jn] + bias4[jn];
+        f32x4 v = acc[i][u * 2 + jn] + bias4[jn];
+        if constexpr (RELU) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
+        }
         *reinterpret_cast<f32x4*>(orow + jn * 16 + 4 * q) = v;
         cs1[jn] += v;
         cs2[jn] += v * v;
@@ -2163,7 +2170,8 @@ static void fm_attrs() {
   std::call_once(device_once(g_fm_attr_once), [] {
     allow_lds(k_fm_gemm<128>, fm_gemm_lds_floats<128>() * 4);
     allow_lds(k_fm_gemm<32>, fm_gemm_lds_floats<32>() * 4);
-    allow_lds(k_fm_deconv32, fm_deconv32_lds_floats() * 4);
+    allow_lds(k_fm_deconv32<false>, fm_deconv32_lds_floats() * 4);
+    allow_lds(k_fm_deconv32<true>, fm_deconv32_lds_floats() * 4);
     allow_lds((k_fm_wgrad<64, 64>), (fm_wgrad_lds_floats<64, 64>() * 4));
     allow_lds((k_fm_wgrad<32, 64>), (fm_wgrad_lds_floats<32, 64>() * 4));
     allow_lds((k_fm_wgrad<32, 16>), (fm_wgrad_lds_floats<32, 16>() * 4));
@@ -2465,7 +2473,7 @@ static int fm_bn_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int
 
 // deconv6's forward pass, the four parity classes per workgroup (k_fm_deconv32)
 static int fm_deconv32(hipStream_t st, const char* label, FmView src, int SH, const float* w, const float* bias, FmView out,
-                       int64_t n, int C, int N, const FmEpReq& rq, const FmWs& ws) {
+                       int64_t n, int C, int N, const FmEpReq& rq, const FmWs& ws, bool relu = false) {
   FmDcArgs a;
   memset(&a, 0, sizeof(a));
   a.src = src.p; a.src_ld = src.ld; a.SH = a.SW = SH; a.w = w; a.bias = bias; a.out = out.p; a.out_ld = out.ld;
@@ -2474,7 +2482,9 @@ static int fm_deconv32(hipStream_t st, const char* label, FmView src, int SH, co
   fm_ep_fill(a.ep, rq, ws);
   const unsigned gx = a.mtiles >= 8 ? 8u * (unsigned)((a.mtiles + 7) / 8) : (unsigned)a.mtiles;
   KTimer kt(label, st);
-  hipLaunchKernelGGL(k_fm_deconv32, dim3(gx, (unsigned)(N / 32)), dim3(kThreads), fm_deconv32_lds_floats() * 4, st, a);
+  const dim3 grid(gx, (unsigned)(N / 32));
+  if (relu) hipLaunchKernelGGL(k_fm_deconv32<true>, grid, dim3(kThreads), fm_deconv32_lds_floats() * 4, st, a);
+  else hipLaunchKernelGGL(k_fm_deconv32<false>, grid, dim3(kThreads), fm_deconv32_lds_floats() * 4, st, a);
   return check_launch(label);
 }
 

@@ -10,8 +10,11 @@ On the GAN path the encoder runs in eval mode ahead of the step and its output i
 `csrc/ndp_encoder.inc` (`ndp_encoder_forward`: implicit-GEMM convolutions on the fp32 matrix pipe, BatchNorm folded into
 the weights).  Training both modules (train_autoencoder.py) goes through `ndivplanning_amd.autoencoder_trainer`
 (`ndp_ae_train_grads` / `ndp_ae_apply_adam`, csrc/ndp_autoencoder.inc), which owns the flat vectors `pack_autoencoder`
-builds.  A forward in training mode or with gradients, and every `Decoder.forward`, keep PyTorch's operators so that the
-classes still behave like nn.Modules there."""
+builds.  The eval-mode `Decoder` -- eval mode, CUDA float32 codes [n,128,1,1], nothing for autograd to record -- runs on
+`ndp_ae_decode`: the five BatchNorms folded into the transposed convolutions on the host (`fold_decoder_params`), the
+chain of csrc/ndp_autoencoder.inc, no BatchNorm launch (`ndivplanning_amd.autoencoder_eval` adds the byte output and the
+reconstruction error).  A forward in training mode, with gradients, on the CPU or on another shape or dtype keeps
+PyTorch's operators (`_forward_torch`), so that the classes still behave like nn.Modules there."""
 from functools import partial
 from types import SimpleNamespace
 
@@ -100,6 +103,21 @@ class Decoder(nn.Module):
             normal_init(self._modules[name], mean, std)
 
     def forward(self, z):
+        # the kernels only where PyTorch would record nothing: eval mode, CUDA float32 codes [n,128,1,1], and autograd
+        # off or with nothing to differentiate; every other case is the PyTorch forward, unchanged
+        if (not self.training and isinstance(z, torch.Tensor) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 4
+                and tuple(z.shape[1:]) == (128, 1, 1)
+                and not (torch.is_grad_enabled() and (z.requires_grad or any(p.requires_grad for p in self.parameters())))):
+            return decoder_forward_hip(self, z)[0]
+        return self._forward_torch(z)
+
+    def __getstate__(self):
+        state = self.__dict__.copy()                 # whole-module pickles carry no kernel scratch
+        state.pop("_ndp_packed", None)
+        state.pop("_ndp_ws", None)
+        return state
+
+    def _forward_torch(self, z):
         for i in range(1, 6):
             z = F.relu(getattr(self, "deconv%d_bn" % i)(getattr(self, "deconv%d" % i)(z)))
         return torch.tanh(self.deconv6(z))
@@ -204,3 +222,120 @@ def _encoder_forward_hip(enc, x):
         _capi.check(fn(_capi.ptr(cache[1]), _capi.ptr(x), n, _capi.ptr(codes), _capi.ptr(ws), _capi.stream_ptr()),
                     "ndp_encoder_forward_u8" if u8 else "ndp_encoder_forward")
     return codes.view(n, 128, 1, 1)
+
+
+# ---------------------------------------------------------------- eval-mode Decoder on ndp_ae_decode
+def fold_decoder_layers(dec, dtype=torch.float32):
+    """[(w', b')] of deconv1..6 in the module's own shapes, eval-mode BatchNorm of deconv1..5 folded in, computed in
+    `dtype` in this order: scale = gamma / sqrt(running_var + eps); w' = w * scale[cout]; b' = (b - running_mean) * scale
+    + beta.  relu(bn(deconv(x))) == relu(conv_transpose2d(x, w', b')) in eval mode."""
+    out = []
+    with torch.no_grad():
+        for i in range(1, 7):
+            deconv = getattr(dec, "deconv%d" % i)
+            w, b = deconv.weight.detach().to(dtype), deconv.bias.detach().to(dtype)
+            if i <= 5:
+                bn = getattr(dec, "deconv%d_bn" % i)
+                scale = bn.weight.detach().to(dtype) / torch.sqrt(bn.running_var.detach().to(dtype) + bn.eps)
+                w = w * scale.view(1, -1, 1, 1)                          # ConvTranspose2d: [cin][cout][kh][kw]
+                b = (b - bn.running_mean.detach().to(dtype)) * scale + bn.bias.detach().to(dtype)
+            out.append((w, b))
+    return out
+
+
+_DEC_FLAT = flat_params.FlatParams("ndp_ae_decoder_layout", "ndp_ae_decoder_param_floats", None,
+                                   ["deconv%d" % i for i in range(1, 7)], [])
+
+
+def fold_decoder_params(dec):
+    """The flat parameter vector `ndp_ae_decode` reads (layout: include/ndp.h, eval-mode Decoder), on the module's
+    device: `fold_decoder_layers` in fp32, per layer the weight as [cin_pad][kh][kw][cout_pad], then the bias."""
+    from .. import _capi
+    lib = _capi.load()
+    device = dec.deconv1.weight.device
+    params = torch.zeros(lib.ndp_ae_decoder_param_floats(), dtype=torch.float32, device=device)
+    for i, (w, b) in enumerate(fold_decoder_layers(dec, torch.float32)):
+        off, d = _DEC_FLAT.layout(0, i)
+        params[off:off + d[0] * d[1] * d[2]] = flat_params.to_kernel_layout(w, d[0], d[2]).reshape(-1)
+        boff, _ = _DEC_FLAT.layout(1, i)
+        params[boff:boff + b.numel()] = b
+    return params
+
+
+def _decoder_state_key(dec):
+    ts = list(dec.parameters()) + list(dec.buffers())
+    return tuple((t.data_ptr(), t._version) for t in ts)
+
+
+def _decoder_packed(dec, device, n):
+    """(folded parameters, workspace with their second weight order in its head) for n images on `device`, cached on the
+    module by the versions of its parameters and buffers and by the device."""
+    from .. import _capi
+    lib = _capi.load()
+    key = _decoder_state_key(dec)
+    cache = dec.__dict__.get("_ndp_packed")
+    fresh = cache is None or cache[0] != key or cache[1].device != device
+    if fresh:
+        cache = (key, fold_decoder_params(dec).to(device))
+        dec.__dict__["_ndp_packed"] = cache
+    ws = dec.__dict__.get("_ndp_ws")
+    need = lib.ndp_ae_decode_workspace_floats(n)
+    if ws is None or ws.numel() < need or ws.device != device:
+        ws = torch.empty(need, device=device, dtype=torch.float32)
+        dec.__dict__["_ndp_ws"] = ws
+        fresh = True
+    if fresh:
+        with torch.cuda.device(device):
+            _capi.check(lib.ndp_ae_decode_pack(_capi.ptr(cache[1]), _capi.ptr(ws), _capi.stream_ptr()), "ndp_ae_decode_pack")
+    return cache[1], ws
+
+
+def decoder_forward_hip(dec, codes, out="float", target=None, errors=False):
+    """ndp_ae_decode on codes [n,128,1,1] / [n,128] (CUDA float32): (reconstruction, per-image MSE, mean MSE).
+    out: "float" -> [n,3,128,128] float32, "bytes" -> [n,128,128,3] uint8, None -> no reconstruction; target (float NCHW
+    or byte frames HWC) with errors=True -> the MSE of every image against it [n] and their mean [1], else None."""
+    from .. import _capi
+    lib = _capi.load()
+    if out not in ("float", "bytes", None):
+        raise ValueError("out must be 'float', 'bytes' or None, got %r" % (out,))
+    _capi.require_gpu_f32(codes, "codes")
+    if codes.dim() not in (2, 4) or codes.shape[1] != 128 or codes.numel() != codes.shape[0] * 128:
+        raise _capi.NdpError("Decoder expects codes [n,128,1,1], got %s" % (tuple(codes.shape),))
+    if dec.training:
+        raise _capi.NdpError("ndp_ae_decode is the eval-mode Decoder: call decoder.eval() first")
+    n = int(codes.shape[0])
+    dev = codes.device
+    codes = codes.detach().contiguous()
+    recon = None
+    if out == "float":
+        recon = torch.empty(n, 3, 128, 128, device=dev, dtype=torch.float32)
+    elif out == "bytes":
+        recon = torch.empty(n, 128, 128, 3, device=dev, dtype=torch.uint8)
+    sq = mean = tf = tu = None
+    if errors:
+        if target is None:
+            raise _capi.NdpError("errors=True needs a target")
+        if not isinstance(target, torch.Tensor) or not target.is_cuda or target.device != dev:
+            raise _capi.NdpError("the target must be on %s (no CPU fallback)" % dev)
+        if target.dtype == torch.uint8 and tuple(target.shape) == (n, 128, 128, 3):
+            tu = target.contiguous()
+        elif target.dtype == torch.float32 and tuple(target.shape) == (n, 3, 128, 128):
+            tf = target.detach().contiguous()
+        else:
+            raise _capi.NdpError("the target must be float32 [%d,3,128,128] or uint8 [%d,128,128,3], got %s %s"
+                                 % (n, n, target.dtype, tuple(target.shape)))
+        sq = torch.empty(n, device=dev, dtype=torch.float32)
+        mean = torch.empty(1, device=dev, dtype=torch.float32)
+    if n == 0:
+        if mean is not None:
+            mean.fill_(float("nan"))
+        return recon, sq, mean
+    if recon is None and not errors:
+        raise _capi.NdpError("nothing to compute: no reconstruction and no errors requested")
+    params, ws = _decoder_packed(dec, dev, n)
+    p = _capi.ptr
+    with torch.cuda.device(dev):
+        _capi.check(lib.ndp_ae_decode(p(params), p(codes), n, p(recon) if out == "float" else None,
+                                      p(recon) if out == "bytes" else None, p(tf), p(tu), p(sq), p(mean), p(ws),
+                                      _capi.stream_ptr()), "ndp_ae_decode")
+    return recon, sq, mean

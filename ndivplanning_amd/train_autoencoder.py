@@ -7,7 +7,12 @@ What differs from the reference, on purpose:
     as defaults (data `128_128_data`, 16 trajectories per batch, shuffled, 50 epochs, lr 2e-4, betas (0.5, 0.999));
   * `synthetic:<N>:images` as the data path gives N seeded synthetic trajectories (the HDF5 loader needs h5py, see
     utils/trajectory_loader.py);
-  * visdom is optional: with it importable (and `visdom=True`) the loss is plotted every `report_freq` steps.
+  * visdom is optional: with it importable (and `visdom=True`) the loss is plotted every `report_freq` steps;
+  * `val_data` (`--val-data`): held-out trajectories.  At the end of every `val_every`-th epoch rank 0 writes the
+    trainer's vectors into the modules, evaluates them in eval mode on the kernels (`autoencoder_eval.evaluate`), logs
+    `epoch, "val_recon_loss:", value`, shows the first input and reconstruction through visdom as the reference does
+    every 10 steps (train_autoencoder.py:96-103, win 1 / 2) and puts the modules back into training mode.  It draws no
+    random number and changes nothing the trainer reads: the training losses are bit-identical with and without it.
 The whole modules are saved as models/encoder_{epoch}.pt / models/decoder_{epoch}.pt when epoch % 10 == 1
 (train_autoencoder.py:92-97), after the trainer's flat vectors are written back into them.
 
@@ -69,7 +74,7 @@ def build_models(device):
 
 def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS, lr=LR_RATE, betas=(0.5, 0.999),
           device="cuda", save_dir="models", report_freq=REPORT_FREQ, visdom=False, log=print, sync_batchnorm=True,
-          grad_exchange="bucketed", raw_jpeg=False):
+          grad_exchange="bucketed", raw_jpeg=False, val_data=None, val_every=1):
     """The reference's loop; returns (encoder, decoder, per-step losses).  Under torch.distributed.run: data parallel
     (module docstring); `device` is then the local rank's GPU, every rank returns the same losses."""
     if grad_exchange not in ("bucketed", "single"):
@@ -77,6 +82,8 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
     rank, world, local_rank = dp.env_world()
     if batch_size % world != 0:                                        # (before any process group or GPU is touched)
         raise ValueError("batch_size=%d trajectories must be a multiple of the %d ranks" % (batch_size, world))
+    if val_data is not None and int(val_every) < 1:
+        raise ValueError("val_every must be >= 1, got %r" % (val_every,))
     own_group = False
     if world > 1:
         device = torch.device("cuda", 0 if os.environ.get("NDP_BENCH_ONE_GPU") == "1" else local_rank)
@@ -91,6 +98,7 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
     np.random.seed(1)
     dataset = make_dataset(data_path, raw_jpeg=raw_jpeg)
     loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True, **jpeg_frames.loader_kwargs(dataset))
+    val_dataset = make_dataset(val_data, seed=2, raw_jpeg=raw_jpeg) if val_data is not None and rank == 0 else None
     # JPEG frames are decoded on the device, then normalised by ndp_eval_frames_u8; failures raise one batch later
     jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
     encoder, decoder = build_models(device)
@@ -119,7 +127,7 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
                 display = visualizer(port=8082)
             except Exception as e:  # pragma: no cover - visdom is optional
                 log("visdom unavailable (%s): no plots" % e)
-        losses = []
+        losses, val_losses = [], []
         step = 0
         warned = False
         for epoch in range(num_epochs):
@@ -155,6 +163,9 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
                 jpeg_decoder.finish()
             if world > 1:
                 dp.assert_replicas_identical([trainer.params], grad_exchange, "end of epoch %d" % epoch)
+            if val_dataset is not None and (epoch + 1) % int(val_every) == 0:
+                val_losses.append((epoch, validate(trainer, val_dataset, batch_size, device, display)))
+                log(epoch, "val_recon_loss:", val_losses[-1][1])
             if epoch % 10 == 1 and rank == 0:
                 os.makedirs(save_dir, exist_ok=True)
                 trainer.sync_to_modules()
@@ -169,7 +180,29 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
         if own_group and dist.is_initialized():
             dist.destroy_process_group()
     train.last_trainer = trainer                                       # tests: the replica's flat vectors
+    train.last_val_losses = val_losses                                 # [(epoch, val_recon_loss)]
     return encoder, decoder, losses
+
+
+def validate(trainer, val_dataset, batch_size, device, display=None):
+    """The mean reconstruction error of the trainer's current parameters over `val_dataset`, eval mode, on the kernels
+    (autoencoder_eval.evaluate); with a visdom display also the first input and reconstruction (the reference's win 1 /
+    2).  The modules come back in training mode; the trainer's own vectors are only read."""
+    from . import autoencoder_eval
+    encoder, decoder = trainer.sync_to_modules()
+    encoder.eval()
+    decoder.eval()
+    try:
+        result = autoencoder_eval.evaluate(encoder, decoder, val_dataset, batch_size=batch_size, device=device,
+                                           keep=1 if display is not None else 0)
+        if display is not None:
+            display.vis.image(result[2][0][0].permute(2, 0, 1).cpu().numpy(), win=1, opts={"caption": "state_cur_vis"})
+            display.vis.image(result[2][1][0].permute(2, 0, 1).cpu().numpy(), win=2, opts={"caption": "state_cur_hat_vis"})
+    finally:
+        for m in (encoder.train(), decoder.train()):                   # the eval kernels' scratch goes back to the allocator
+            m.__dict__.pop("_ndp_packed", None)
+            m.__dict__.pop("_ndp_ws", None)
+    return float(result[0].item())
 
 
 def make_parser():
@@ -182,6 +215,10 @@ def make_parser():
     parser.add_argument("--epochs", type=int, default=NUM_EPOCHS)
     parser.add_argument("--lr", type=float, default=LR_RATE)
     parser.add_argument("--save-dir", default="models")
+    parser.add_argument("--val-data", default=None,
+                        help="held-out trajectories (as --data): their reconstruction error is logged after every "
+                             "--val-every-th epoch")
+    parser.add_argument("--val-every", type=int, default=1)
     parser.add_argument("--visdom", action="store_true", help="plot the loss through visdom")
     parser.add_argument("--no-sync-batchnorm", dest="sync_batchnorm", action="store_false",
                         help="data parallel: BatchNorm statistics per rank instead of over all ranks' images")
@@ -195,7 +232,7 @@ def main(argv=None):
     args = make_parser().parse_args(argv)
     return train(args.data, batch_size=args.batch_size, num_epochs=args.epochs, lr=args.lr, save_dir=args.save_dir,
                  visdom=args.visdom, sync_batchnorm=args.sync_batchnorm, grad_exchange=args.grad_exchange,
-                 raw_jpeg=args.raw_jpeg)
+                 raw_jpeg=args.raw_jpeg, val_data=args.val_data, val_every=args.val_every)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,14 @@ of the HIP step.  Usage: python scripts/bench_autoencoder.py [N ...]   (default:
 python scripts/bench_autoencoder.py --shards [N ...]   (default: 240 120 60 30, the per-rank share of the reference's 240
 images at 1, 2, 4, 8 ranks): per-rank compute time of one step at each shard size, through ndp_ae_train_grads and through
 ndp_ae_train_grads_dp at world 1 (no statistics callback, no collective: the bucket events recorded and the weight-gradient
-slabs summed per bucket) -- what bucketing costs on the compute path.  The two are timed alternately, median of STEPS."""
+slabs summed per bucket) -- what bucketing costs on the compute path.  The two are timed alternately, median of STEPS.
+
+python scripts/bench_autoencoder.py --eval [N ...]   (default: 240 16 1): the eval-mode autoencoder
+(ndivplanning_amd.autoencoder_eval: ndp_encoder_forward + ndp_ae_decode) -- `reconstruct` (codes, reconstruction,
+per-image and mean error) and `decode` alone -- against the same two through PyTorch-ROCm
+(`dec._forward_torch(enc._forward_torch(x))` / `dec._forward_torch(z)`, eval mode, no_grad; the reconstruct arm with the
+same per-image and mean error).  The four arms alternate, median of STEPS after WARMUP; then the per-kernel split of one
+HIP reconstruct.  --eval-once N: one HIP reconstruct + decode after a warm-up, for a kernel trace."""
 import os
 import sys
 import time
@@ -125,8 +132,81 @@ def shards(sizes):
                               100 * (med["dp"] - med["plain"]) / med["plain"]))
 
 
+def eval_models():
+    """Eval-mode modules with non-trivial BatchNorm statistics (what a trained checkpoint has)."""
+    enc, dec = models()
+    gen = torch.Generator().manual_seed(5)
+    with torch.no_grad():
+        for m in [*enc.modules(), *dec.modules()]:
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.copy_(0.5 + torch.rand(m.num_features, generator=gen))
+                m.running_mean.copy_(0.1 * torch.randn(m.num_features, generator=gen))
+                m.running_var.copy_(0.5 + torch.rand(m.num_features, generator=gen))
+    return enc.eval(), dec.eval()
+
+
+def eval_mode(sizes):
+    from ndivplanning_amd import autoencoder_eval as AE
+    enc, dec = eval_models()
+    print("eval-mode autoencoder, median of %d after %d warm-up, the four arms alternating" % (STEPS, WARMUP))
+    for n in sizes:
+        x = torch.rand(n, 3, 128, 128, device=DEV) * 2 - 1
+        with torch.no_grad():
+            z = enc(x)
+
+        def torch_reconstruct():
+            with torch.no_grad():
+                y = dec._forward_torch(enc._forward_torch(x))
+                sq = ((y - x) ** 2).reshape(n, -1).mean(dim=1)
+                return y, sq, sq.mean()
+
+        def torch_decode():
+            with torch.no_grad():
+                return dec._forward_torch(z)
+        arms = (("hip reconstruct", lambda: AE.reconstruct(enc, dec, x)), ("torch reconstruct", torch_reconstruct),
+                ("hip decode", lambda: AE.decode(dec, z)), ("torch decode", torch_decode))
+        for _ in range(WARMUP):
+            for _, fn in arms:
+                fn()
+        torch.cuda.synchronize()
+        ts = {name: [] for name, _ in arms}
+        for _ in range(STEPS):
+            for name, fn in arms:
+                t0 = time.perf_counter()
+                fn()
+                torch.cuda.synchronize()
+                ts[name].append(time.perf_counter() - t0)
+        med = {k: 1e3 * sorted(v)[len(v) // 2] for k, v in ts.items()}
+        print("n=%d  reconstruct: hip %.3f ms  pytorch-rocm %.3f ms  (%.2fx)   decode: hip %.3f ms  pytorch-rocm %.3f ms  "
+              "(%.2fx)" % (n, med["hip reconstruct"], med["torch reconstruct"], med["torch reconstruct"] / med["hip reconstruct"],
+                           med["hip decode"], med["torch decode"], med["torch decode"] / med["hip decode"]))
+        _capi.timing_enable(True)
+        AE.reconstruct(enc, dec, x)
+        torch.cuda.synchronize()
+        split = sorted(_capi.timing_collect().items(), key=lambda kv: -kv[1][0])
+        _capi.timing_enable(False)
+        total = sum(v[0] for _, v in split)
+        for name, (ms, cnt) in split[:16]:
+            print("   %-26s %8.3f ms (%2d launches) %5.1f %%" % (name, ms, cnt, 100 * ms / total))
+
+
+def eval_once(n):
+    from ndivplanning_amd import autoencoder_eval as AE
+    enc, dec = eval_models()
+    x = torch.rand(n, 3, 128, 128, device=DEV) * 2 - 1
+    for _ in range(3):
+        _, _, mean = AE.reconstruct(enc, dec, x)
+        out = AE.decode(dec, enc(x).detach(), out="bytes")
+    torch.cuda.synchronize()
+    print("n=%d mean error %.6f, bytes %s" % (n, mean.item(), tuple(out.shape)))
+
+
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["--shards"]:
+    if sys.argv[1:2] == ["--eval"]:
+        eval_mode([int(a) for a in sys.argv[2:]] or [240, 16, 1])
+    elif sys.argv[1:2] == ["--eval-once"]:
+        eval_once(int(sys.argv[2]) if len(sys.argv) > 2 else 240)
+    elif sys.argv[1:2] == ["--shards"]:
         shards([int(a) for a in sys.argv[2:]] or [240, 120, 60, 30])
     else:
         main([int(a) for a in sys.argv[1:]] or [240, 16])
