@@ -66,6 +66,25 @@ __host__ __device__ inline int rd(const uint8_t* stage, const uint8_t* s, int64_
   return p < kStage ? stage[p] : s[p];
 }
 
+// The rules of the entropy data [e0, mark) of a stream of `len` bytes, shared by k_jpeg_parse and the host driver of the
+// tests (tests/jpeg_host_driver.hip).  A marker: a 0xFF not followed by 0x00 (fill bytes and a 0xFF that ends the stream
+// included); the first one at or after e0 ends the data.
+__host__ __device__ inline bool marker_at(const uint8_t* stage, const uint8_t* s, int32_t p, int32_t len) {
+  return rd(stage, s, p) == 0xFF && (p + 1 >= len || rd(stage, s, p + 1) != 0x00);
+}
+
+// A stuffed byte: the 0x00 after a 0xFF of the data; unstuffing drops it.
+__host__ __device__ inline bool stuffed_at(const uint8_t* stage, const uint8_t* s, int32_t p, int32_t e0) {
+  return p > e0 && rd(stage, s, p) == 0x00 && rd(stage, s, p - 1) == 0xFF;
+}
+
+// The data must end at EOI, after any fill bytes (a truncated stream, or another marker inside the scan, is corrupt).
+__host__ __device__ inline bool eoi_at(const uint8_t* stage, const uint8_t* s, int32_t mark, int32_t len) {
+  int32_t p = mark;
+  for (int fill = 0; fill < 64 && p < len && rd(stage, s, p) == 0xFF; ++fill) ++p;
+  return p > mark && p < len && rd(stage, s, p) == 0xD9;
+}
+
 // The marker walk SOI .. SOS.  Returns an NDP_JPEG_* status; on NDP_JPEG_OK, h describes the frame.  `stage` holds the
 // first min(len, kStage) bytes of `s` (the same bytes: it only saves global reads).
 __host__ __device__ inline int parse_headers(const uint8_t* stage, const uint8_t* s, int64_t len, Header* h) {
@@ -227,6 +246,13 @@ __host__ __device__ inline bool same_state(const EState& a, const EState& b) {
   return a.pos == b.pos && a.k == b.k && a.bp == b.bp;
 }
 
+// Chunk length in bits for `avail` bits of unstuffed data: at most kEntropyThreads chunks, each a multiple of 32 bits
+// and at least kMinChunkBits long.
+__host__ __device__ inline int32_t chunk_bits(int32_t avail) {
+  const int32_t even = ((avail + kEntropyThreads - 1) / kEntropyThreads + 31) & ~31;
+  return even > kMinChunkBits ? even : kMinChunkBits;
+}
+
 // The one-lane bit reader and symbol loop: a 64-bit MSB-first buffer refilled a word at a time, the next word already
 // loaded.  `words` (LDS on the device) holds the first `split` words; a stream longer than that reads the rest from `far`
 // (FAR = true; a separate instantiation, so the common one has no global load whose wait would also wait for the
@@ -363,27 +389,31 @@ __host__ __device__ inline bool write_chunk(Lane<FAR>& ln, const EState& entry, 
   return true;
 }
 
-// libjpeg's jidctint.c (islow), CONST_BITS 13, PASS1_BITS 2; the output clamp of libjpeg-turbo's SIMD IDCT.
+// libjpeg's jidctint.c (islow), CONST_BITS 13, PASS1_BITS 2; the output clamp of libjpeg-turbo's SIMD IDCT.  The sums
+// and products are taken modulo 2^32 (unsigned, then an arithmetic shift of the same bits): the same results wherever
+// jidctint.c's int arithmetic is defined, i.e. for every stream an encoder writes, and defined results for the
+// coefficients of a corrupt one (any int16 times any uint16).
 #define NDP_JPEG_IDCT_1D(I0, I1, I2, I3, I4, I5, I6, I7, O0, O1, O2, O3, O4, O5, O6, O7, RND, SH)   \
   do {                                                                                             \
-    int z2 = (I2), z3 = (I6);                                                                      \
-    int z1 = (z2 + z3) * 4433;                                                                     \
-    int tmp2 = z1 + z3 * -15137, tmp3 = z1 + z2 * 6270;                                            \
-    z2 = (I0); z3 = (I4);                                                                          \
-    int tmp0 = (z2 + z3) * 8192, tmp1 = (z2 - z3) * 8192;                                          \
-    const int tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;  \
-    tmp0 = (I7); tmp1 = (I5); tmp2 = (I3); tmp3 = (I1);                                            \
+    typedef uint32_t U;                                                                            \
+    U z2 = (U)(I2), z3 = (U)(I6);                                                                  \
+    U z1 = (z2 + z3) * 4433u;                                                                      \
+    U tmp2 = z1 + z3 * (U)-15137, tmp3 = z1 + z2 * 6270u;                                          \
+    z2 = (U)(I0); z3 = (U)(I4);                                                                    \
+    U tmp0 = (z2 + z3) * 8192u, tmp1 = (z2 - z3) * 8192u;                                          \
+    const U tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;    \
+    tmp0 = (U)(I7); tmp1 = (U)(I5); tmp2 = (U)(I3); tmp3 = (U)(I1);                                \
     z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;                                          \
-    int z4 = tmp1 + tmp3;                                                                          \
-    const int z5 = (z3 + z4) * 9633;                                                               \
-    tmp0 *= 2446; tmp1 *= 16819; tmp2 *= 25172; tmp3 *= 12299;                                     \
-    z1 *= -7373; z2 *= -20995; z3 *= -16069; z4 *= -3196;                                          \
+    U z4 = tmp1 + tmp3;                                                                            \
+    const U z5 = (z3 + z4) * 9633u;                                                                \
+    tmp0 *= 2446u; tmp1 *= 16819u; tmp2 *= 25172u; tmp3 *= 12299u;                                 \
+    z1 *= (U)-7373; z2 *= (U)-20995; z3 *= (U)-16069; z4 *= (U)-3196;                              \
     z3 += z5; z4 += z5;                                                                            \
     tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;                            \
-    O0 = (tmp10 + tmp3 + (RND)) >> (SH); O7 = (tmp10 - tmp3 + (RND)) >> (SH);                      \
-    O1 = (tmp11 + tmp2 + (RND)) >> (SH); O6 = (tmp11 - tmp2 + (RND)) >> (SH);                      \
-    O2 = (tmp12 + tmp1 + (RND)) >> (SH); O5 = (tmp12 - tmp1 + (RND)) >> (SH);                      \
-    O3 = (tmp13 + tmp0 + (RND)) >> (SH); O4 = (tmp13 - tmp0 + (RND)) >> (SH);                      \
+    O0 = (int)(tmp10 + tmp3 + (U)(RND)) >> (SH); O7 = (int)(tmp10 - tmp3 + (U)(RND)) >> (SH);      \
+    O1 = (int)(tmp11 + tmp2 + (U)(RND)) >> (SH); O6 = (int)(tmp11 - tmp2 + (U)(RND)) >> (SH);      \
+    O2 = (int)(tmp12 + tmp1 + (U)(RND)) >> (SH); O5 = (int)(tmp12 - tmp1 + (U)(RND)) >> (SH);      \
+    O3 = (int)(tmp13 + tmp0 + (U)(RND)) >> (SH); O4 = (int)(tmp13 - tmp0 + (U)(RND)) >> (SH);      \
   } while (0)
 
 __host__ __device__ inline uint8_t clamp_u8(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
@@ -502,7 +532,7 @@ __global__ __launch_bounds__(jpeg::kParseThreads) void k_jpeg_parse(const uint8_
   const int32_t chunk = (span + kParseThreads - 1) / kParseThreads;
   const int32_t c0 = e0 + tid * chunk, c1 = c0 + chunk < (int32_t)len ? c0 + chunk : (int32_t)len;
   for (int32_t p = c0; p < c1; ++p) {
-    if (rd(stage, s, p) == 0xFF && (p + 1 >= (int32_t)len || rd(stage, s, p + 1) != 0x00)) {
+    if (marker_at(stage, s, p, (int32_t)len)) {
       atomicMin(&s_mark, p);
       break;
     }
@@ -525,7 +555,7 @@ __global__ __launch_bounds__(jpeg::kParseThreads) void k_jpeg_parse(const uint8_
   const int32_t mark = s_mark;
   const int32_t u1 = c1 < mark ? c1 : mark;
   int32_t keep = 0;
-  for (int32_t p = c0; p < u1; ++p) keep += !(p > e0 && rd(stage, s, p) == 0x00 && rd(stage, s, p - 1) == 0xFF);
+  for (int32_t p = c0; p < u1; ++p) keep += !stuffed_at(stage, s, p, e0);
   s_scan[tid] = keep;
   __syncthreads();
   for (int off = 1; off < kParseThreads; off <<= 1) {
@@ -537,18 +567,13 @@ __global__ __launch_bounds__(jpeg::kParseThreads) void k_jpeg_parse(const uint8_
   uint8_t* out = L.compact + d->cstart;
   int32_t o = s_scan[tid] - keep;
   for (int32_t p = c0; p < u1; ++p) {
-    const int b = rd(stage, s, p);
-    if (!(p > e0 && b == 0x00 && rd(stage, s, p - 1) == 0xFF)) out[o++] = (uint8_t)b;
+    if (!stuffed_at(stage, s, p, e0)) out[o++] = (uint8_t)rd(stage, s, p);
   }
   if (tid == kParseThreads - 1) {
     const int32_t total = s_scan[tid];
     for (int32_t p = total; p < ((total + 3) & ~3); ++p) out[p] = 0;      // the last word's tail
-    // the data must end at EOI (a truncated stream, or a marker inside the scan, is corrupt)
-    int32_t p = mark;
-    for (int fill = 0; fill < 64 && p < (int32_t)len && rd(stage, s, p) == 0xFF; ++fill) ++p;
-    const bool eoi = p > mark && p < (int32_t)len && rd(stage, s, p) == 0xD9;
     d->ncompact = total;
-    d->status = eoi ? NDP_JPEG_OK : NDP_JPEG_CORRUPT;
+    d->status = eoi_at(stage, s, mark, (int32_t)len) ? NDP_JPEG_OK : NDP_JPEG_CORRUPT;
   }
 }
 
@@ -560,7 +585,7 @@ __device__ inline void entropy_frame(const jpeg::Layout& L, jpeg::Desc* d, int64
   const int c = threadIdx.x;
   const int32_t nbytes = d->ncompact;
   const int32_t avail = nbytes * 8;
-  const int32_t chunk = max(kMinChunkBits, ((avail + kEntropyThreads - 1) / kEntropyThreads + 31) & ~31);
+  const int32_t chunk = chunk_bits(avail);
   const int nchunks = (avail + chunk - 1) / chunk;
   const int32_t end = min((c + 1) * chunk, avail);
   Lane<FAR> ln{words, kStreamLdsBytes / 4, reinterpret_cast<const uint32_t*>(L.compact + d->cstart), (nbytes + 3) >> 2,
