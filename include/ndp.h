@@ -572,6 +572,29 @@ int ndp_jpeg_decode_u8(const uint8_t *streams, const int64_t *offsets /* [n+1], 
                        uint8_t *frames_hwc /* [n][128][128][3] */, int32_t *status /* [n], device */, void *workspace,
                        int64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------- Lanczos resize ---
+ * A live environment renders camera frames of any size (MuJoCo: 500x500); the reference turns them into the networks'
+ * input with PIL: Image.fromarray(frame).resize((128, 128), Image.LANCZOS) (MPC_gym_eval.py:68-77,
+ * generate_trajectories.py:113-118).  ndp_resize_lanczos_u8 does that on the device, bit-identical to Pillow's 8-bit
+ * resampler (fixed-point coefficients with 22 fractional bits, horizontal pass rounded to bytes, then the vertical pass;
+ * a pass whose input size is 128 is skipped, so a 128x128 frame is copied).
+ *   ndp_resize_workspace_bytes(H, W)  bytes of the coefficient tables of one frame size; 0 unless 1 <= H, W <= 2048
+ *   ndp_resize_build_tables           host only, no GPU call: fills `tables_host` (4-byte aligned, `bytes` >= the above)
+ *                                     in double arithmetic.  The caller copies the tables to device memory once per
+ *                                     (H, W) and owns them.
+ *   ndp_resize_lanczos_u8             frames_hwc [n][H][W][3] bytes -> out_hwc [n][128][128][3] bytes and, when `images`
+ *                                     is not NULL, images [n,3,128,128] fp32 in [-1,1] of the same bytes (the table of
+ *                                     ndp_eval_frames_u8), in ONE launch.  tables: device copy of the built tables
+ *                                     (table_bytes >= ndp_resize_workspace_bytes(H, W)); a table that was built for
+ *                                     another size gives wrong pixels but no access outside the frames.
+ *                                     rows_per_band: 0 (chosen from n), or 1, 2, 4, 8, 16 output rows per workgroup --
+ *                                     the result does not depend on it.  All device pointers 4-byte aligned;
+ *                                     1 <= n_images <= 65536.  Integer arithmetic, no atomics: bit-reproducible. */
+int64_t ndp_resize_workspace_bytes(int64_t height, int64_t width);
+int ndp_resize_build_tables(int64_t height, int64_t width, void *tables_host, int64_t bytes);
+int ndp_resize_lanczos_u8(const uint8_t *frames_hwc, int64_t n_images, int64_t height, int64_t width, const void *tables,
+                          int64_t table_bytes, int rows_per_band, uint8_t *out_hwc, float *images, void *stream);
+
 /* ------------------------------------------------------------ measurement ---
  * Per-kernel timing for bench.py: while enabled (per host thread) every kernel
  * this library launches is bracketed by hipEvents recorded on the stream it is

@@ -154,6 +154,10 @@ SIGNATURES = {
     "ndp_eval_frames_u8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "ndp_jpeg_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "ndp_jpeg_decode_u8": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ndp_resize_workspace_bytes": (c_int64, [c_int64, c_int64]),
+    "ndp_resize_build_tables": (c_int, [c_int64, c_int64, c_void_p, c_int64]),
+    "ndp_resize_lanczos_u8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                      c_void_p]),
     "ndp_timing_enable": (c_int, [c_int]),
     "ndp_timing_collect": (c_int, [ctypes.c_char_p, c_int, POINTER(c_float), POINTER(c_int32), c_int]),
 }

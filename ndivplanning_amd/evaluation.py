@@ -177,8 +177,15 @@ def noise_piece_shapes(kind, batch, seq_length, num_sample, noise_dim, rollouts=
     loader batch, in the reference's order:
       open    control_evaluation.py:112: N = batch * (T-1), once
       closed  complete_eval.py:126: N = batch, once per step
-      mpc     mpc_eval.py:141: N = rollouts, once per horizon step of every planning step (batch 1)."""
+      mpc     mpc_eval.py:141: N = rollouts, once per horizon step of every planning step (batch 1)
+      mpc_gym MPC_gym_eval.py:141,188: N = rollouts, `horizon` times per planning step -- the horizon does not shrink
+              towards the end of the trajectory (batch 1, num_sample 1: the `.squeeze(1)` of :215 needs it)."""
     t1 = int(seq_length) - 1
+    if kind == "mpc_gym":
+        if int(num_sample) != 1:
+            raise ValueError("MPC_gym_eval needs evaluation.num_sample == 1 (MPC_gym_eval.py:215 squeezes the sample axis "
+                             "of the [R,K,4] actions)")
+        return [(rollouts, num_sample, noise_dim)] * (t1 * int(horizon))
     if kind == "open":
         return [(batch * t1, num_sample, noise_dim)]
     if kind == "closed":
@@ -188,7 +195,7 @@ def noise_piece_shapes(kind, batch, seq_length, num_sample, noise_dim, rollouts=
         for image_num in range(t1):
             shapes += [(rollouts, num_sample, noise_dim)] * min(int(horizon), t1 - image_num)   # mpc_eval.py:131
         return shapes
-    raise ValueError("kind must be 'open', 'closed' or 'mpc'")
+    raise ValueError("kind must be 'open', 'closed', 'mpc' or 'mpc_gym'")
 
 
 def draw_noise(shapes, pin=False):
@@ -375,6 +382,156 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
             "image_error_sum": image_error_sum, "action_error": action_error}
 
 
+# ---------------------------------------------------------------------- one observation in, one action out
+def plan_step_noise_floats(batch, rollouts, horizon, noise_dim):
+    """Floats of noise one plan_step call consumes: B * R * nz per horizon step."""
+    return int(horizon) * int(batch) * int(rollouts) * int(noise_dim)
+
+
+def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, seed=0, choice=None):
+    """One planning step of MPC_gym_eval.py:183-225 for B environments at once, rows [B][R]: from the observed `state`
+    [B,3,128,128], R rollouts of Th steps through encoder, generator and forward model, scored against the goal image.
+
+    The semantics are the live script's, which differ from mpc_eval.py's (mpc_plan) and are reproduced on purpose: the
+    horizon is the full Th at every planning step (:188, the shrinking bound is commented out); the rollouts' LAST
+    predictions are scored against `goal` [B,3,128,128] (:221); min_error = 10000000000, strict `<` in rollout order,
+    so the first minimum wins and a NaN is never chosen (:183, :219-224).  Deduplicated as in mpc_plan: the caller
+    encodes the goal once (`goal_code` [B,128]); the state is encoded once and its code broadcast to the R rows at
+    ts = 0.  noise: None (device draws of ndp_uniform_noise with `seed`), or the Th pieces [B*R, nz] in order
+    (plan_step_noise_floats(...) floats; at B = 1 the reference's draws, noise kind "mpc_gym").  choice: None, or [B]
+    int32 indices that replace the rule.  No host synchronisation when the inputs are on the device.  Returns device
+    tensors (action [B,4], choice [B] int32, rollout_errors [B,R], actions0 [B,R,4])."""
+    r, th = int(rollouts), int(horizon)
+    if r < 1 or th < 1:
+        raise ValueError("rollouts and horizon must be >= 1, got %d, %d" % (r, th))
+    if state.dim() != 4 or tuple(state.shape[1:]) != (3, 128, 128) or tuple(goal.shape) != tuple(state.shape):
+        raise _capi.NdpError("state and goal must both be [B,3,128,128], got %s and %s"
+                             % (tuple(state.shape), tuple(goal.shape)))
+    b, nz, dev = int(state.shape[0]), models.noise_dim, models.device
+    br = b * r
+    if tuple(goal_code.shape) != (b, 128):
+        raise _capi.NdpError("goal_code must be [%d,128], got %s" % (b, tuple(goal_code.shape)))
+    need = plan_step_noise_floats(b, r, th, nz)
+    if noise is None:
+        noise = models.uniform(need, seed)
+    else:
+        if noise.numel() != need:
+            raise ValueError("noise has %d floats, plan_step needs %d" % (noise.numel(), need))
+        noise = noise.reshape(-1).to(dev, non_blocking=True).float()
+    forced = None
+    if choice is not None:
+        forced = torch.as_tensor(choice, dtype=torch.int32).reshape(b).to(dev, non_blocking=True)
+    state = state.contiguous()
+    code_in = models.g_input(models.encode(state), r, goal_code, r, br)
+    act0 = models.generate(code_in, noise[:br * nz])
+    rep = torch.empty(br, 3, 128, 128, dtype=torch.float32, device=dev)
+    rep.view(b, r, IMAGE_VALUES).copy_(state.view(b, 1, IMAGE_VALUES).expand(b, r, IMAGE_VALUES))
+    pred = models.forward(rep, act0)
+    for ts in range(1, th):                                   # the full horizon, MPC_gym_eval.py:188
+        code_in = models.g_input(models.encode(pred), 1, goal_code, r, br)
+        act = models.generate(code_in, noise[ts * br * nz:(ts + 1) * br * nz])
+        pred = models.forward(pred, act)
+    err = torch.empty(b, r, dtype=torch.float32, device=dev)
+    pick = torch.empty(b, dtype=torch.int32, device=dev)
+    action = torch.empty(b, 4, dtype=torch.float32, device=dev)
+    # nobody reads the chosen rollout's prediction (the environment gives the next state): no pred0 / pred_out copy
+    models.score_select(pred, b, r, goal.contiguous(), act0, None, forced, err, pick, action, None)
+    return action, pick, err, act0.view(b, r, 4)
+
+
+class MpcController:
+    """Closed-loop control of B live environments: camera frames in, actions out.
+
+        ctrl = MpcController(models, rollouts, horizon, frame_shape=(500, 500))
+        ctrl.reset(goal_frames)                # bytes [B,128,128,3] or floats [B,3,128,128]: the goal is encoded once
+        actions, info = ctrl.act(raw_frames)   # bytes [B,H,W,3], host (numpy / tensor) or device
+
+    act: the frames go through a pinned staging buffer (allocated once) and an asynchronous upload, are resized to
+    128x128 on the device exactly as PIL's Image.LANCZOS does (ndp_resize_lanczos_u8: bytes and normalised floats in one
+    launch; 128x128 frames take its copy path), plan_step picks the actions, and ONE host synchronisation brings them
+    back, because the environment needs them.  `info`: state_u8 [B,128,128,3] (what MPC_gym_eval.get_state resizes to),
+    state [B,3,128,128], rollout_errors [B,R], choice [B], actions0 [B,R,4], all on the device."""
+
+    def __init__(self, models, rollouts, horizon, frame_shape=None, seed=0):
+        from .resize import LanczosResizer
+        self.models, self.rollouts, self.horizon = models, int(rollouts), int(horizon)
+        if self.rollouts < 1 or self.horizon < 1:
+            raise ValueError("rollouts and horizon must be >= 1")
+        self.resizer = LanczosResizer(models.device)
+        self.frame_shape = None                               # None: the first frame tells
+        if frame_shape is not None:
+            self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
+            self.resizer.tables(*self.frame_shape)            # built and uploaded here, not in the control loop
+        self.seed, self.steps = int(seed), 0
+        self.goal = self.goal_code = None
+        self._staging = self._actions = self._uploaded = None
+        self._upload_pending = False
+        self._event = torch.cuda.Event()
+
+    def reset(self, goal_frames):
+        self.goal = self.models.images(torch.as_tensor(goal_frames))
+        self.goal_code = self.models.encode(self.goal)
+        b = int(self.goal.shape[0])
+        if self._actions is None or int(self._actions.shape[0]) != b:
+            self._actions = torch.empty(b, 4, dtype=torch.float32, pin_memory=True)
+            self._staging = None
+        if self._staging is None and self.frame_shape is not None:
+            self._staging = torch.empty((b,) + self.frame_shape + (3,), dtype=torch.uint8, pin_memory=True)
+        self.steps = 0
+
+    def observe(self, raw_frames):
+        """bytes [B,H,W,3], host or device -> (resized bytes [B,128,128,3], normalised floats [B,3,128,128]) on the
+        device.  Host frames pass through the one pinned staging buffer: a call first waits for the previous call's upload
+        to have left that buffer -- only where no plan() lay between, whose one synchronisation covers the upload --, then
+        nothing waits."""
+        if self.goal is None:
+            raise _capi.NdpError("MpcController.reset(goal_frames) comes before the first frame")
+        raw = torch.as_tensor(raw_frames)
+        if raw.dtype != torch.uint8 or raw.dim() != 4 or int(raw.shape[3]) != 3:
+            raise _capi.NdpError("frames must be uint8 [B,H,W,3], got %s %s" % (raw.dtype, tuple(raw.shape)))
+        if self.frame_shape is None:
+            self.frame_shape = (int(raw.shape[1]), int(raw.shape[2]))
+        want = (int(self.goal.shape[0]),) + self.frame_shape + (3,)
+        if tuple(raw.shape) != want:
+            raise _capi.NdpError("frames must be uint8 %s, got %s" % (want, tuple(raw.shape)))
+        if not raw.is_cuda:
+            if self._staging is None:
+                self._staging = torch.empty(want, dtype=torch.uint8, pin_memory=True)
+            elif self._upload_pending:
+                self._uploaded.synchronize()                  # the last upload has read the buffer
+            self._staging.copy_(raw)
+            with _capi.on_device(self.models.device):
+                raw = self._staging.to(self.models.device, non_blocking=True)
+                if self._uploaded is None:
+                    self._uploaded = torch.cuda.Event()
+                self._uploaded.record()
+                self._upload_pending = True
+        return self.resizer(raw)
+
+    def plan(self, state, noise=None, choice=None):
+        """plan_step on `state` and the goal of reset(), then the one host synchronisation.  Returns (actions [B,4] on
+        the host, info)."""
+        if noise is None:
+            seed = self.seed + self.steps
+        else:
+            seed = 0
+        action, pick, err, act0 = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts, self.horizon,
+                                            noise=noise, seed=seed, choice=choice)
+        self.steps += 1
+        with _capi.on_device(self.models.device):
+            self._actions.copy_(action, non_blocking=True)
+            self._event.record()
+        self._event.synchronize()                             # the environment needs the action
+        self._upload_pending = False                          # the frames' upload came before it on the stream
+        return self._actions.clone(), {"state": state, "action": action, "rollout_errors": err, "choice": pick, "actions0": act0}
+
+    def act(self, raw_frames, noise=None, choice=None):
+        state_u8, state = self.observe(raw_frames)
+        actions, info = self.plan(state, noise=noise, choice=choice)
+        info["state_u8"] = state_u8
+        return actions, info
+
+
 # ---------------------------------------------------------------------- the reference's per-call loop
 def module_loop_mpc(encode, generate, forward, frames, actions, rollouts, horizon, noise, noise_dim):
     """mpc_eval.py's planning loop for ONE trajectory, restated on three callables (encode [n,3,128,128] -> [n,128],
@@ -508,9 +665,12 @@ def make_eval_dataset(config):
                        raw_uint8=bool(config.get("raw_uint8", True)))
 
 
-def script_main(fetch, argv=None):
+def script_main(fetch, argv=None, add_arguments=None, prepare=None):
     """The scripts' __main__ (control_evaluation.py:160-187 and its twins): CLI, config, dataset, the three whole-module
-    pickles, then `fetch`.  Prints the returned pair."""
+    pickles, then `fetch`.  Prints the returned tuple.  add_arguments(parser): a script's own flags beside the common ones.
+    prepare(namespace): called after parsing and before anything is loaded; what it returns (a tuple, e.g. the parsed
+    arguments in front and a live environment behind) is wrapped around fetch's arguments as
+    fetch(*before, image_encoder, fwd_model_autoencoder, generator, dataset, config, *after)."""
     import os
     from argparse import ArgumentParser
 
@@ -519,7 +679,10 @@ def script_main(fetch, argv=None):
     from .utils.file import make_paths_absolute
     parser = ArgumentParser(description="Interact with your training script")
     parser = add_common_arguments(parser)
+    if add_arguments is not None:
+        add_arguments(parser)
     namespace = parser.parse_args(argv)
+    before, after = prepare(namespace) if prepare is not None else ((), ())
     config = override_dotmap(namespace, "config_file")
     config = make_paths_absolute(os.getcwd(), config, log_not_exist=True)
     if not torch.cuda.is_available():
@@ -530,8 +693,11 @@ def script_main(fetch, argv=None):
     image_encoder = torch.load(config.image_encoder_model_path, map_location=gpu_id, weights_only=False)
     generator = torch.load(config.gan_decoder_model_path, map_location=gpu_id, weights_only=False)
     fwd_model_autoencoder = torch.load(config.forward_model_autoencoder_path, map_location=gpu_id, weights_only=False)
-    result = fetch(image_encoder, fwd_model_autoencoder, generator, dataset, config)
-    print("avg_action_error, avg_image_loss:", result[0], result[1])
+    result = fetch(*before, image_encoder, fwd_model_autoencoder, generator, dataset, config, *after)
+    if len(result) == 2:
+        print("avg_action_error, avg_image_loss:", result[0], result[1])
+    else:
+        print("avg_action_error, avg_image_loss, avg_goal_error, success_rate:", *result)
     return result
 
 
