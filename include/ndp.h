@@ -572,6 +572,32 @@ int ndp_jpeg_decode_u8(const uint8_t *streams, const int64_t *offsets /* [n+1], 
                        uint8_t *frames_hwc /* [n][128][128][3] */, int32_t *status /* [n], device */, void *workspace,
                        int64_t workspace_bytes, void *stream);
 
+/* ------------------------------------------------------------- JPEG encode ---
+ * The reference writes every camera frame with PIL: im.save(format="jpeg", quality=95) (generate_trajectories.py:
+ * 113-122).  ndp_jpeg_encode_u8 writes the same bytes on the device: baseline, 8-bit, 128x128, 4:2:0, the Annex K
+ * quantisation tables scaled for quality 95, the standard Huffman tables, no restart markers; libjpeg's fixed-point
+ * colour conversion, h2v2 box downsampling, integer islow forward DCT and sign-magnitude quantisation.  Exact for every
+ * pixel array, not only camera-like ones.  The output is what ndp_jpeg_decode_u8 reads.
+ *   frames_hwc  [n][128][128][3] device bytes, 4-byte aligned
+ *   streams     device bytes: frame i is streams[offsets[i] .. offsets[i+1]), offsets[0] = 0; nothing is written at or
+ *               beyond streams + capacity
+ *   offsets     [n+1] device int64 (written)
+ *   status      [n] device int32: NDP_JPEG_OK, or NDP_JPEG_WORKSPACE for the first frame that does not fit in what is
+ *               left of `capacity` and for every frame after it (their length is 0; the frames before are intact)
+ *   workspace   ndp_jpeg_encode_workspace_bytes(n) bytes, 256-byte aligned (0 for a bad request).  After the call the
+ *               n int64 at byte ndp_jpeg_encode_lengths_offset(n) of it (-1 for a bad n; host only) are the stream
+ *               lengths of all n frames, of those that did not fit too: their sum is the capacity that fits the batch
+ * ndp_jpeg_encode_max_stream_bytes (host only): the longest stream a frame can give -- header, the entropy bound
+ * derived from the Huffman tables with every byte stuffed, EOI; capacity = n * that always fits.
+ * No host synchronisation, no allocation; 1 <= n_images <= 65536.  Integer arithmetic, atomics in LDS only (OR): two
+ * runs give the same bytes. */
+int64_t ndp_jpeg_encode_workspace_bytes(int64_t n_images);
+int64_t ndp_jpeg_encode_max_stream_bytes(void);
+int64_t ndp_jpeg_encode_lengths_offset(int64_t n_images);
+int ndp_jpeg_encode_u8(const uint8_t *frames_hwc, int64_t n_images, uint8_t *streams, int64_t capacity,
+                       int64_t *offsets /* [n+1], device */, int32_t *status /* [n], device */, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------- Lanczos resize ---
  * A live environment renders camera frames of any size (MuJoCo: 500x500); the reference turns them into the networks'
  * input with PIL: Image.fromarray(frame).resize((128, 128), Image.LANCZOS) (MPC_gym_eval.py:68-77,

@@ -154,6 +154,10 @@ SIGNATURES = {
     "ndp_eval_frames_u8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "ndp_jpeg_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "ndp_jpeg_decode_u8": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ndp_jpeg_encode_workspace_bytes": (c_int64, [c_int64]),
+    "ndp_jpeg_encode_max_stream_bytes": (c_int64, []),
+    "ndp_jpeg_encode_lengths_offset": (c_int64, [c_int64]),
+    "ndp_jpeg_encode_u8": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ndp_resize_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "ndp_resize_build_tables": (c_int, [c_int64, c_int64, c_void_p, c_int64]),
     "ndp_resize_lanczos_u8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p,

@@ -1878,4 +1878,5 @@ __global__ __launch_bounds__(kThreads) void k_philox(float* out, int64_t n, uint
 #include "ndp_autoencoder.inc"
 #include "ndp_eval.inc"
 #include "ndp_jpeg.inc"
+#include "ndp_jpeg_enc.inc"
 #include "ndp_resize.inc"

@@ -1,4 +1,5 @@
-"""Device-side JPEG decode of trajectory frames (ndp_jpeg_decode_u8, include/ndp.h).
+"""Device-side JPEG decode and encode of trajectory frames (ndp_jpeg_decode_u8, ndp_jpeg_encode_u8, include/ndp.h;
+DESIGN.md sections 5f and 5i).
 
 The reference stores every camera frame as a JPEG (generate_trajectories.py:113-122: PIL, quality 95, 4:2:0, 128x128)
 and decodes it with PIL on the host (utils/hdf5_load.py:9-11).  Here the loader workers only pack the streams
@@ -7,6 +8,9 @@ and decodes it with PIL on the host (utils/hdf5_load.py:9-11).  Here the loader 
 
 Formats other than the reference writer's (progressive, restart intervals, other sampling factors or sizes, ...) are
 not decoded: each frame has a status (STATUS below), and `check` decides when a nonzero one raises.
+
+`JpegEncoder` is the other direction: [n,128,128,3] uint8 frames -> the streams the reference's writer gives
+(generate_trajectories.py:113-122), byte for byte, in the packed layout above.
 """
 import numpy as np
 import torch
@@ -181,3 +185,130 @@ class JpegDecoder:
         if bad.numel():
             i = int(bad[0])
             raise JpegDecodeError(i, int(host_status[i]))
+
+
+class JpegEncodeError(_capi.NdpError):
+    pass
+
+
+class JpegEncoder:
+    """Holds the encode workspace of one device.  The streams are the reference writer's, byte for byte (PIL,
+    `format="jpeg", quality=95`: baseline, 4:2:0, standard Huffman tables); only 128x128 frames are encoded.
+
+    Capacity: a stream is 0.9-24 KB (24 KB: noise of only 0 and 255) but the bound that holds for every pixel array is
+    `max_stream_bytes` (about 160 KB), so by default a batch gets DEFAULT_FRAME_BYTES a frame.  If a frame did not fit
+    (status 4 on the last frame; only hand-made worst cases get there), the lengths of all frames, which every call leaves
+    in the workspace, are summed and the batch is encoded again into exactly that many bytes."""
+
+    DEFAULT_FRAME_BYTES = 32768
+    EAGER_FRAME_BYTES = 8192            # encode_to_bytes: what its first (usually only) download takes per frame
+
+    def __init__(self, device=None):
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type != "cuda":
+            raise _capi.NdpError("JpegEncoder encodes on a ROCm GPU only (got %s)" % self.device)
+        self.lib = _capi.load()
+        self.max_stream_bytes = int(self.lib.ndp_jpeg_encode_max_stream_bytes())
+        self.status = None              # int32 [n] device tensor of the last encode
+        self._ws = None
+
+    def _workspace(self, n):
+        need = int(self.lib.ndp_jpeg_encode_workspace_bytes(int(n)))
+        if need <= 0:
+            raise _capi.NdpError("ndp_jpeg_encode_workspace_bytes(%d) refused the batch" % n)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _frames(self, frames):
+        if not isinstance(frames, torch.Tensor):
+            frames = torch.as_tensor(frames)
+        if frames.dtype != torch.uint8 or frames.dim() not in (4, 5) or tuple(frames.shape[-3:]) != FRAME_SHAPE:
+            raise _capi.NdpError("frames must be uint8 [n,128,128,3] or [B,T,128,128,3], got %s %s"
+                                 % (frames.dtype, tuple(frames.shape)))
+        x = frames.to(self.device, non_blocking=True).contiguous().view((-1,) + FRAME_SHAPE)
+        if x.shape[0] < 1:
+            raise _capi.NdpError("no frames to encode")
+        return x.clone() if x.data_ptr() % 4 else x
+
+    def _launch(self, x, capacity):
+        """One allocation: offsets int64 [n+1], status int32 [n], padding to 16 bytes, then `capacity` stream bytes.
+        Returns (blob, offsets, status, streams), the last three views of the first."""
+        n = int(x.shape[0])
+        meta = (8 * (n + 1) + 4 * n + 15) // 16 * 16
+        blob = torch.empty(meta + int(capacity), dtype=torch.uint8, device=self.device)
+        offsets = blob[:8 * (n + 1)].view(torch.int64)
+        status = blob[8 * (n + 1):8 * (n + 1) + 4 * n].view(torch.int32)
+        streams = blob[meta:]
+        ws = self._workspace(n)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_jpeg_encode_u8(_capi.ptr(x), n, _capi.ptr(streams), int(capacity), _capi.ptr(offsets),
+                                                    _capi.ptr(status), _capi.ptr(ws), int(ws.numel()),
+                                                    _capi.stream_ptr(self.device)), "ndp_jpeg_encode_u8")
+        self.status = status
+        return blob, offsets, status, streams
+
+    def _needed(self, n):
+        """The bytes the last batch of n frames takes: the sum of the lengths the call left in the workspace."""
+        at = int(self.lib.ndp_jpeg_encode_lengths_offset(n))
+        return int(self._ws[at:at + 8 * n].view(torch.int64).sum())
+
+    @staticmethod
+    def _tail(blob, n):
+        """(offsets[n], status[n-1]) of a launch's blob, in one small copy."""
+        host = blob[8 * n:8 * (n + 1) + 4 * n].cpu()
+        return int(host[:8].view(torch.int64)), int(host[-4:].view(torch.int32))
+
+    def encode(self, frames, capacity=None):
+        """frames: uint8 [n,128,128,3] or [B,T,128,128,3], host or device -> (buffer uint8 [bytes], offsets int64 [n+1])
+        on the device: stream i is buffer[offsets[i]:offsets[i+1]], what pack_jpegs makes and JpegDecoder.decode takes.
+
+        capacity None: the default a frame; the total and the last status are read back in one copy (one
+        synchronisation) and the buffer is exactly that long.  A batch that did not fit is encoded again into the sum of
+        its lengths (one more read).  capacity given: no host synchronisation and no retry; the buffer is `capacity`
+        long, a frame that did not fit and every later one have length 0 and `self.status` 4."""
+        x = self._frames(frames)
+        n = int(x.shape[0])
+        if capacity is not None:
+            _, offsets, _, streams = self._launch(x, int(capacity))
+            return streams, offsets
+        capacity = n * self.DEFAULT_FRAME_BYTES
+        for attempt in range(2):
+            blob, offsets, _, streams = self._launch(x, capacity)
+            total, last = self._tail(blob, n)       # a frame that fits has every earlier one fit too
+            if last == 0:
+                return streams[:total], offsets
+            capacity = self._needed(n)
+        raise JpegEncodeError("%d frames did not fit the %d bytes their own lengths add up to" % (n, capacity))
+
+    def encode_frames(self, frames, capacity=None):
+        """uint8 [B,T,128,128,3], host or device -> JpegFrames [B,T] on the device (what JpegDecoder.decode_frames
+        takes)."""
+        shape = tuple(torch.as_tensor(frames).shape) if not isinstance(frames, torch.Tensor) else tuple(frames.shape)
+        if len(shape) != 5:
+            raise _capi.NdpError("encode_frames takes [B,T,128,128,3], got %s" % (shape,))
+        buffer, offsets = self.encode(frames, capacity=capacity)
+        return JpegFrames(buffer, offsets, shape[0], shape[1])
+
+    def encode_to_bytes(self, frames):
+        """-> list of n bytes objects, what generate_trajectories.py stores per frame.  One download and one
+        synchronisation while the streams average EAGER_FRAME_BYTES or less (camera frames are 4-7 KB): offsets,
+        statuses and the head of the stream buffer come back in one copy; a longer batch takes a second copy for the
+        rest, and one that did not fit the default capacity is encoded again as in `encode`."""
+        x = self._frames(frames)
+        n = int(x.shape[0])
+        capacity = n * self.DEFAULT_FRAME_BYTES
+        for attempt in range(2):
+            blob, offsets, status, streams = self._launch(x, capacity)
+            meta = int(blob.numel() - streams.numel())
+            head = blob[:meta + min(capacity, n * self.EAGER_FRAME_BYTES)].cpu().numpy()
+            off = head[:8 * (n + 1)].view(np.int64)
+            st = head[8 * (n + 1):8 * (n + 1) + 4 * n].view(np.int32)
+            if int(st[-1]) != 0:
+                capacity = self._needed(n)
+                continue
+            data = head[meta:]
+            if int(off[-1]) > data.size:
+                data = np.concatenate([data, streams[data.size:int(off[-1])].cpu().numpy()])
+            return [data[off[i]:off[i + 1]].tobytes() for i in range(n)]
+        raise JpegEncodeError("%d frames did not fit the %d bytes their own lengths add up to" % (n, capacity))
