@@ -534,7 +534,27 @@ int ndp_ae_decode(const float *folded_params, const float *codes, int64_t n_imag
  *                          ndp_g_forward (ld_code 256)
  *   ndp_eval_frames_u8     replaces  the host-side normalisation of the loader's frames (utils/hdf5_load.py:9-11):
  *                          frames_hwc [n][128][128][3] bytes -> images [n,3,128,128] in [-1,1], with the 256-entry table
- *                          of ndp_encoder_forward_u8 (bit-identical to the float path). */
+ *                          of ndp_encoder_forward_u8 (bit-identical to the float path).
+ *   ndp_fm_score           scores n predictions of the eval-mode forward model, pred [n,3,128,128] (= state_cur +
+ *                          residual, the output of ndp_fm_forward(training = 0)), in ONE launch (forward_model_eval.py):
+ *                          - pred_err [n] (or NULL): the MSE of prediction i over its 49,152 values against target row
+ *                            target_idx ? target_idx[i] : i of EXACTLY ONE of target_f32 [n_target,3,128,128] and
+ *                            target_u8 [n_target,128,128,3] (byte frames, normalised through the table of
+ *                            ndp_eval_frames_u8: the bits of the floats of the same bytes).  The difference is taken in
+ *                            fp32, its square summed in fp64 in a fixed order, the mean rounded to fp32;
+ *                          - base_err [n] (required with a base frame, else NULL): the same MSE between base row
+ *                            base_idx ? base_idx[i] : i of base_f32 [n_base,3,128,128] or base_u8 [n_base,128,128,3] (at
+ *                            most one) and the same target: the error of predicting "the frame does not change";
+ *                          - pred_u8 [n,128,128,3] (or NULL): HWC bytes trunc(((y + 1) / 2) * 255), the fp32 operations
+ *                            of ndp_ae_decode in the same order -- the reference's denorm(...).astype(np.uint8),
+ *                            train_forward_model.py:116-145.  DEVIATION: state + residual can leave [-1, 1]; values
+ *                            below 0 / from 255 up are written as 0 / 255 and NaN as 0, where numpy's cast wraps.
+ *                          An index outside its array gives NaN for that image's error (base_err also where the target
+ *                          index is bad) and nothing is read through it; the bytes do not depend on the indices.  No gathered
+ *                          copy, no scratch, no atomics: two calls give the same bits.  Two targets, no target, two base
+ *                          frames, a base frame without base_err (or base_err / base_idx without one), no output at all,
+ *                          n < 1 or n_target < 1: NDP_E_ARG, nothing launched.  Float images 16-byte aligned, byte
+ *                          frames 4-byte aligned.  The caller owns every buffer. */
 int ndp_eval_score_select(const float *pred, int64_t n_traj, int rollouts, const float *target, int64_t n_target,
                           const int32_t *target_idx, int64_t values, const float *actions0, const float *pred0,
                           const int32_t *forced, float *err, int32_t *choice, float *action_out, float *pred_out,
@@ -545,6 +565,10 @@ int ndp_eval_mse(const float *a, int64_t n_a, const float *b, int64_t n_b, const
 int ndp_eval_g_input(const float *state_code, int64_t n_state, int state_rep, const float *goal_code, int64_t n_goal,
                      int goal_rep, int64_t rows, float *out, void *stream);
 int ndp_eval_frames_u8(const uint8_t *frames_hwc, int64_t n_images, float *images, void *stream);
+int ndp_fm_score(const float *pred, int64_t n_images, const float *target_f32, const uint8_t *target_u8,
+                 int64_t n_target, const int32_t *target_idx, const float *base_f32, const uint8_t *base_u8,
+                 int64_t n_base, const int32_t *base_idx, float *pred_err, float *base_err, uint8_t *pred_u8,
+                 void *stream);
 
 /* ------------------------------------------------------------- JPEG decode ---
  * The frames of the reference's trajectory bundles are JPEG streams (generate_trajectories.py:113-122: PIL, quality 95);

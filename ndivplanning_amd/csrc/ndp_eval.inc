@@ -231,3 +231,180 @@ int ndp_eval_frames_u8(const uint8_t* frames_hwc, int64_t n_images, float* image
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------ forward-model scoring
+// k_fm_score: what an evaluation of the forward model does with every prediction (forward_model_eval.py), in one launch:
+// the MSE of the prediction against its target frame, the MSE of a base frame against the same target ("the frame does
+// not change": the persistence baseline) and the reference's display bytes, denorm(...).astype(np.uint8) of
+// train_forward_model.py:116-145.  Targets and base frames are floats NCHW or byte frames HWC (normalised through
+// u8_norm_table: the floats of the same bytes, bit for bit) and are addressed through index maps: no gathered copy.
+// One workgroup of 768 threads per prediction.  The image is walked in 16 tiles of 1,024 pixels: thread t owns, in every
+// tile, the four consecutive pixels 4 (t % 256) .. + 3 of plane t / 256 -- one 16-byte load per float operand -- while
+// the 3,072 bytes of a tile's HWC byte frames (in and out) are contiguous: they pass through LDS as 768 dwords, one per
+// thread, so that the byte loads and stores are coalesced and the NCHW <-> HWC transposition happens in LDS (byte address
+// 12 (t % 256) + 3 e + plane: a wave's stride is 3 dwords, conflict-free).  The difference is taken in fp32, its square
+// accumulated in fp64: by the thread over its tiles in order, then over the workgroup by a fixed tree (768 -> 512 ->
+// 256 .. 1).  No atomics, no scratch memory: two calls give the same bits.
+namespace ndp {
+namespace fm_score {
+
+constexpr int kScoreThreads = 768;                    // 3 planes x 256 pixel quads
+constexpr int kPlane = 128 * 128;
+constexpr int kValues = 3 * kPlane;              // 49,152 per image
+constexpr int kTilePixels = 1024;
+constexpr int kTiles = kPlane / kTilePixels;     // 16
+constexpr int kTileBytes = 3 * kTilePixels;      // of an HWC byte frame: kScoreThreads dwords
+
+// u8_norm_table's entry (utils/hdf5_load.py:9-11)
+__host__ __device__ inline float norm_u8(int b) { return ((float)b / 255.0f - 0.5f) * 2.0f; }
+
+// trunc(((y + 1) / 2) * 255) as ndp_ae_decode writes it, saturated: the forward model's state + residual can leave
+// [-1, 1] (numpy's cast wraps there; a display wants the nearest end).  NaN -> 0.
+__host__ __device__ inline unsigned char to_byte(float y) {
+  const float v = ((y + 1.0f) / 2.0f) * 255.0f;
+  return !(v > 0.0f) ? (unsigned char)0 : v >= 255.0f ? (unsigned char)255 : (unsigned char)(int)v;
+}
+
+__host__ __device__ inline double sq_diff(float a, float b) {
+  const float d = a - b;
+  return (double)d * (double)d;
+}
+
+// the row image i addresses (idx NULL: i itself), -1 where it is outside 0 .. rows - 1
+__host__ __device__ inline int64_t row_of(const int32_t* idx, int64_t i, int64_t rows) {
+  const int64_t r = idx ? (int64_t)idx[i] : i;
+  return r >= 0 && r < rows ? r : -1;
+}
+
+// thread t in tile `tile`: its plane, its first pixel in the tile, the float offset of that pixel in an NCHW image
+__host__ __device__ inline void thread_elems(int t, int tile, int* plane, int* lp0, int* off) {
+  *plane = t >> 8;
+  *lp0 = 4 * (t & 255);
+  *off = *plane * kPlane + tile * kTilePixels + *lp0;
+}
+
+// the byte of (pixel lp of the tile, plane) in the tile's HWC bytes
+__host__ __device__ inline int tile_byte(int lp, int plane) { return lp * 3 + plane; }
+
+}  // namespace fm_score
+
+struct FmScoreArgs {
+  const float* pred;
+  const float* tgt_f32; const unsigned char* tgt_u8; int64_t n_target; const int32_t* target_idx;
+  const float* base_f32; const unsigned char* base_u8; int64_t n_base; const int32_t* base_idx;
+  float* pred_err; float* base_err; unsigned char* pred_u8;
+};
+
+// the workgroup's sum of `v` in a fixed order; every thread calls it (uniform)
+__device__ __forceinline__ double fm_score_block_sum(double v, double* red) {
+  const int t = threadIdx.x;
+  red[t] = v;
+  __syncthreads();
+  if (t < 256) red[t] += red[t + 512];
+  __syncthreads();
+  for (int w = 256; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  const double s = red[0];
+  __syncthreads();
+  return s;
+}
+
+// TGT / BASE: 1 floats NCHW, 2 byte frames HWC; BASE 0: no base frame
+template <int TGT, int BASE>
+__global__ __launch_bounds__(fm_score::kScoreThreads) void k_fm_score(FmScoreArgs a) {
+  using namespace fm_score;
+  __shared__ float lut[(TGT == 2 || BASE == 2) ? 256 : 1];
+  __shared__ unsigned int tin[TGT == 2 ? kScoreThreads : 1];
+  __shared__ unsigned int bin[BASE == 2 ? kScoreThreads : 1];
+  __shared__ unsigned int tout[kScoreThreads];
+  __shared__ double red[kScoreThreads];
+  const int t = threadIdx.x;
+  const int64_t img = blockIdx.x;
+  if (TGT == 2 || BASE == 2) u8_norm_table(lut);                       // (visible behind the first barrier below)
+  const int64_t tr = row_of(a.target_idx, img, a.n_target);
+  const int64_t br = BASE != 0 ? row_of(a.base_idx, img, a.n_base) : -1;
+  const bool do_pred = a.pred_err != nullptr && tr >= 0;              // (all four: uniform over the workgroup)
+  const bool do_base = BASE != 0 && tr >= 0 && br >= 0;
+  const bool do_tgt = do_pred || do_base;
+  const bool do_bytes = a.pred_u8 != nullptr;
+  const float* pred = a.pred + img * kValues;
+  double sp = 0.0, sb = 0.0;
+  for (int tile = 0; tile < kTiles; ++tile) {
+    int plane, lp0, off;
+    thread_elems(t, tile, &plane, &lp0, &off);
+    if (TGT == 2 && do_tgt)
+      tin[t] = reinterpret_cast<const unsigned int*>(a.tgt_u8 + tr * kValues + (int64_t)tile * kTileBytes)[t];
+    if (BASE == 2 && do_base)
+      bin[t] = reinterpret_cast<const unsigned int*>(a.base_u8 + br * kValues + (int64_t)tile * kTileBytes)[t];
+    f32x4 y = {0.f, 0.f, 0.f, 0.f}, x = y, b = y;
+    if (do_pred || do_bytes) y = *reinterpret_cast<const f32x4*>(pred + off);
+    if (TGT == 1 && do_tgt) x = *reinterpret_cast<const f32x4*>(a.tgt_f32 + tr * kValues + off);
+    if (BASE == 1 && do_base) b = *reinterpret_cast<const f32x4*>(a.base_f32 + br * kValues + off);
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int byte = tile_byte(lp0 + e, plane);
+      if (TGT == 2 && do_tgt) x[e] = lut[reinterpret_cast<const unsigned char*>(tin)[byte]];
+      if (BASE == 2 && do_base) b[e] = lut[reinterpret_cast<const unsigned char*>(bin)[byte]];
+      if (do_pred) sp += sq_diff(y[e], x[e]);
+      if (do_base) sb += sq_diff(b[e], x[e]);
+      if (do_bytes) reinterpret_cast<unsigned char*>(tout)[byte] = to_byte(y[e]);
+    }
+    __syncthreads();
+    if (do_bytes)
+      reinterpret_cast<unsigned int*>(a.pred_u8 + img * kValues + (int64_t)tile * kTileBytes)[t] = tout[t];
+  }
+  if (a.pred_err != nullptr) {
+    const double s = fm_score_block_sum(sp, red);
+    if (t == 0) a.pred_err[img] = do_pred ? (float)(s / (double)kValues) : NAN;
+  }
+  if (BASE != 0) {
+    const double s = fm_score_block_sum(sb, red);
+    if (t == 0) a.base_err[img] = do_base ? (float)(s / (double)kValues) : NAN;
+  }
+}
+
+template <int TGT>
+static void fm_score_launch(int base, unsigned grid, hipStream_t st, const FmScoreArgs& a) {
+  const dim3 g(grid), b(fm_score::kScoreThreads);
+  if (base == 0) hipLaunchKernelGGL((k_fm_score<TGT, 0>), g, b, 0, st, a);
+  else if (base == 1) hipLaunchKernelGGL((k_fm_score<TGT, 1>), g, b, 0, st, a);
+  else hipLaunchKernelGGL((k_fm_score<TGT, 2>), g, b, 0, st, a);
+}
+
+}  // namespace ndp
+
+extern "C" {
+
+int ndp_fm_score(const float* pred, int64_t n_images, const float* target_f32, const uint8_t* target_u8, int64_t n_target,
+                 const int32_t* target_idx, const float* base_f32, const uint8_t* base_u8, int64_t n_base,
+                 const int32_t* base_idx, float* pred_err, float* base_err, uint8_t* pred_u8, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(pred != nullptr, "ndp_fm_score: null pointer (pred)");
+  NDP_CHECK_ARG(n_images >= 1 && n_images <= kEvalMaxPairs, "ndp_fm_score: bad image count %lld", (long long)n_images);
+  NDP_CHECK_ARG(!(target_f32 && target_u8), "ndp_fm_score: two targets given (float and byte frames)");
+  NDP_CHECK_ARG(target_f32 || target_u8, "ndp_fm_score: no target given");
+  NDP_CHECK_ARG(n_target >= 1, "ndp_fm_score: n_target %lld must be >= 1", (long long)n_target);
+  NDP_CHECK_ARG(!(base_f32 && base_u8), "ndp_fm_score: two base frames given (float and byte frames)");
+  const bool has_base = base_f32 || base_u8;
+  NDP_CHECK_ARG(!has_base || base_err, "ndp_fm_score: a base frame is given without base_err");
+  NDP_CHECK_ARG(has_base || (!base_err && !base_idx), "ndp_fm_score: base_err / base_idx without a base frame");
+  NDP_CHECK_ARG(!has_base || n_base >= 1, "ndp_fm_score: n_base %lld must be >= 1", (long long)n_base);
+  NDP_CHECK_ARG(pred_err || base_err || pred_u8, "ndp_fm_score: no output requested");
+  NDP_CHECK_ARG(((reinterpret_cast<uintptr_t>(pred) | reinterpret_cast<uintptr_t>(target_f32) |
+                  reinterpret_cast<uintptr_t>(base_f32)) & 15) == 0, "ndp_fm_score: float images must be 16-byte aligned");
+  NDP_CHECK_ARG(((reinterpret_cast<uintptr_t>(target_u8) | reinterpret_cast<uintptr_t>(base_u8) |
+                  reinterpret_cast<uintptr_t>(pred_u8)) & 3) == 0, "ndp_fm_score: byte frames must be 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  FmScoreArgs a{pred, target_f32, target_u8, n_target, target_idx, base_f32, base_u8, has_base ? n_base : 0, base_idx,
+                pred_err, base_err, pred_u8};
+  const int base = base_f32 ? 1 : base_u8 ? 2 : 0;
+  KTimer kt("k_fm_score", st);
+  if (target_f32) fm_score_launch<1>(base, (unsigned)n_images, st, a);
+  else fm_score_launch<2>(base, (unsigned)n_images, st, a);
+  return check_launch("k_fm_score");
+}
+
+}  // extern "C"

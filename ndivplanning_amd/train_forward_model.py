@@ -14,6 +14,15 @@ What differs from the reference, on purpose:
     takes batch_size / world_size trajectories of each (identically shuffled) batch, the flat gradient is averaged over
     RCCL between backward and Adam (ndivplanning_amd/dp.py::mean_all_reduce).  BatchNorm statistics are per rank, as with
     torch's DistributedDataParallel; a final batch that does not split evenly is dropped; rank 0 saves.
+  * three optional keys, `training.forward.val_data_path` (held-out trajectories: a directory or `synthetic:<N>[:mode]`),
+    `val_every` (epochs, default 1) and `val_horizon` (default 1): at the end of every `val_every`-th epoch rank 0 writes
+    the trainer's flat vectors into the module (they are the source of truth and are never read back), evaluates it in
+    eval mode on the kernels (`forward_model_eval.evaluate`) and logs `val_pred_loss` (the one-step error) and
+    `val_persistence_loss` (the error of "the frame does not change"), then one line per further horizon.  Validation
+    changes no bit of training: it reads the trajectories by index (no random number is drawn), the forward pass is in
+    eval mode (the running statistics are read, never moved; the cross-rank BatchNorm hook belongs to training-mode
+    calls and is not invoked), it issues no collective -- the other ranks simply meet rank 0 at the next epoch's first
+    all-reduce -- and the module is back in training mode afterwards.  Without `val_data_path` nothing changes.
 The whole module is saved every `epochs_per_stage` epochs as the reference does (train_forward_model.py:151-163), after
 the trainer's flat vectors are written back into it."""
 import importlib
@@ -131,6 +140,13 @@ def train(config):
                                   reduce_fn=dp.mean_all_reduce(world) if world > 1 and exchange == "single" else None,
                                   bucket_reduce=dp.BucketedMeanAllReduce(world) if world > 1 and exchange == "bucketed" else None)
 
+    # held-out trajectories (optional): rank 0 alone reads and evaluates them
+    val_path, val_every, val_horizon = _optional(f, "val_data_path", None), int(_optional(f, "val_every", 1)), int(_optional(f, "val_horizon", 1))
+    if val_path is not None and (val_every < 1 or val_horizon < 1):
+        raise ValueError("training.forward.val_every and val_horizon must be >= 1, got %r and %r" % (val_every, val_horizon))
+    val_dataset = make_val_dataset(config, val_path) if val_path is not None and rank == 0 else None
+    val_history = []
+
     history = []
     step = 0
     for epoch in range(num_epochs):
@@ -162,6 +178,8 @@ def train(config):
         if display is not None:                                      # pragma: no cover
             display.plot("loss", "train", "Forward Model Loss", epoch, avg_loss)
         logging.info("{}, {}: reconstruction loss per epoch: {}".format(epoch, step, avg_loss))
+        if val_dataset is not None and (epoch + 1) % val_every == 0:
+            val_history.append((epoch, validate(trainer, val_dataset, val_horizon, local_batch)))
         if epoch % epochs_per_stage == epochs_per_stage - 1 and rank == 0:   # train_forward_model.py:151-163
             os.makedirs(config.forward_save_path, exist_ok=True)
             trainer.sync_to_module()
@@ -170,7 +188,51 @@ def train(config):
     trainer.sync_to_module()
     trainer.close()
     train.last_trainer = trainer                                       # tests: the replica's flat vectors
+    train.last_val = val_history                                       # [(epoch, {one_step_mse, horizon_mse, persistence_mse, counts})]
     return history
+
+
+def _optional(node, key, default):
+    """node[key] of a DotMap / dict node, `default` where the key is absent (a DotMap reads a missing key as an empty map)."""
+    value = node.get(key, None) if hasattr(node, "get") else None
+    return default if value is None or (isinstance(value, dict) and not value) else value
+
+
+def make_val_dataset(config, path):
+    """The held-out trajectories of `training.forward.val_data_path`, made as `make_dataset` makes the training set
+    (same trajectory_length and frame format); a synthetic set is seeded apart from the training set."""
+    from .utils.trajectory_loader import PushDataset, SyntheticPushDataset
+    path = str(path)
+    if path.startswith("synthetic:") or "/synthetic:" in path:
+        spec = path[path.index("synthetic:"):].split(":")
+        mode = spec[2] if len(spec) > 2 else "images"
+        if mode not in ("images", "frames_u8", "jpeg"):
+            raise ValueError("the forward model is validated on images: use `synthetic:<N>:images`, `:frames_u8` or `:jpeg`")
+        return SyntheticPushDataset(int(spec[1]), seq_length=config.trajectory_length, mode=mode, seed=int(config.random_seed) + 1)
+    return PushDataset(path, seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)),
+                       raw_jpeg=bool(_get(config, "raw_jpeg", False)))
+
+
+def validate(trainer, val_dataset, horizon, batch_size):
+    """The prediction error of the trainer's current parameters over `val_dataset`, in eval mode on the kernels
+    (forward_model_eval.evaluate), logged; returns the means as host lists.  The trainer's flat vectors are the source of
+    truth: they are written into the module first and nothing is read back, no random number is drawn, no collective
+    is issued (rank 0 calls this alone), and eval mode neither moves the running statistics nor invokes the cross-rank
+    BatchNorm hook, which belongs to training-mode calls.  The module returns to training mode."""
+    from . import forward_model_eval
+    model = trainer.sync_to_module()
+    model.eval()
+    try:
+        result = forward_model_eval.evaluate(model, val_dataset, horizon=horizon, batch_size=batch_size, device=trainer.device)
+        means = {k: result[k].tolist() for k in ("one_step_mse", "horizon_mse", "persistence_mse", "counts")}
+    finally:
+        model.train()
+        model.invalidate_cache()                                       # the eval pass's scratch goes back to the allocator
+    logging.info("val_pred_loss: {} val_persistence_loss: {}".format(means["one_step_mse"][0], means["persistence_mse"][0]))
+    for h in range(1, len(means["horizon_mse"])):
+        logging.info("val horizon {}: model_mse {} persistence_mse {} count {}".format(
+            h + 1, means["horizon_mse"][h], means["persistence_mse"][h], means["counts"][h]))
+    return means
 
 
 def main(argv=None):
