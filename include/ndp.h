@@ -554,7 +554,38 @@ int ndp_ae_decode(const float *folded_params, const float *codes, int64_t n_imag
  *                          copy, no scratch, no atomics: two calls give the same bits.  Two targets, no target, two base
  *                          frames, a base frame without base_err (or base_err / base_idx without one), no output at all,
  *                          n < 1 or n_target < 1: NDP_E_ARG, nothing launched.  Float images 16-byte aligned, byte
- *                          frames 4-byte aligned.  The caller owns every buffer. */
+ *                          frames 4-byte aligned.  The caller owns every buffer.
+ *   ndp_gan_score          scores n conditioning rows of K samples of the action generator, action_hat [n,K,4] (what
+ *                          ndp_g_forward writes for m = n * K rows with code_rep = K), in ONE launch (gan_eval.py).  Inputs
+ *                          (device pointers): action [n,4] the true actions, or NULL; noise [n,K,nz], or NULL (nz is read
+ *                          only with it); fake_logits [n,K] = ndp_d_forward on the samples, or NULL.  Outputs, each may be
+ *                          NULL, at least one required; e_k is the error of sample k:
+ *                          - sample_err [n,K]: e_k = the mean of the 4 squares of the fp32 differences between sample k
+ *                            and the true action, summed in fp64 in index order, rounded to fp32 (ndp_fm_score's
+ *                            convention);
+ *                          - mean_err [n]: the mean over all K * 4 squares, fp64 sum in (k, component) order, rounded
+ *                            once; its mean over rows is mse(repeat_interleave(actions, K), action_hat)
+ *                            (control_evaluation.py:140-142);
+ *                          - best_err [n], best_k [n] int32: the smallest e_k, the first minimum wins; a NaN e_k is never
+ *                            chosen while a non-NaN one exists; all NaN: k = 0 and NaN;
+ *                          - best_curve [n,K]: the running minimum over samples 0 .. k under the same rule (its mean over
+ *                            rows is the best-of-(k + 1) curve);
+ *                          - spread [n]: the mean over the K (K - 1) ordered pairs i != j of ||a_i - a_j||_2 (fp32
+ *                            distances as ndp_ndiv_fwd_bwd takes them, summed in fp64 per sample i over j, then over i);
+ *                            K = 1: NaN (0/0);
+ *                          - ndiv [n] (needs noise): the row's share of ndp_ndiv_fwd_bwd's loss, sum_{i,j} relu(0.8 *
+ *                            dz_ij / sum_j dz_ij - dx_ij / sum_j dx_ij), every term in fp32 in that kernel's operation
+ *                            order (fmaf chains, sqrtf, fp32 row sums in j order, a separately rounded product and
+ *                            difference), NaN propagating as there; the K terms of sample i are summed in fp64 in j
+ *                            order, the K subtotals in i order, rounded once;
+ *                          - d_fake_prob [n] (needs fake_logits): the mean over k of sigmoid(logit), the sigmoid in the
+ *                            form the BCE kernels use, 1 / (1 + expf(-x)) in fp32, summed in fp64 in k order;
+ *                          - d_pick_k [n] int32 (needs fake_logits), d_pick_err [n] (needs action too): the sample with
+ *                            the largest logit (first maximum, NaN never chosen; all NaN: 0) and its e_k.
+ *                          1 <= K <= NDP_MAX_SAMPLES, 1 <= nz <= 16, n >= 1, n * K < 2^31.  An output without the input
+ *                          it needs, no output at all, a limit exceeded: NDP_E_ARG, nothing launched.  No scratch buffer,
+ *                          no atomics (two calls give the same bits), no host synchronisation.  The caller owns every
+ *                          buffer. */
 int ndp_eval_score_select(const float *pred, int64_t n_traj, int rollouts, const float *target, int64_t n_target,
                           const int32_t *target_idx, int64_t values, const float *actions0, const float *pred0,
                           const int32_t *forced, float *err, int32_t *choice, float *action_out, float *pred_out,
@@ -569,6 +600,10 @@ int ndp_fm_score(const float *pred, int64_t n_images, const float *target_f32, c
                  int64_t n_target, const int32_t *target_idx, const float *base_f32, const uint8_t *base_u8,
                  int64_t n_base, const int32_t *base_idx, float *pred_err, float *base_err, uint8_t *pred_u8,
                  void *stream);
+int ndp_gan_score(const float *action_hat, int64_t n, int k, const float *action, const float *noise, int nz,
+                  const float *fake_logits, float *sample_err, float *mean_err, float *best_err, int32_t *best_k,
+                  float *best_curve, float *spread, float *ndiv, float *d_fake_prob, int32_t *d_pick_k,
+                  float *d_pick_err, void *stream);
 
 /* ------------------------------------------------------------- JPEG decode ---
  * The frames of the reference's trajectory bundles are JPEG streams (generate_trajectories.py:113-122: PIL, quality 95);

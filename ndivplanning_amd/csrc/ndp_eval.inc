@@ -408,3 +408,215 @@ int ndp_fm_score(const float* pred, int64_t n_images, const float* target_f32, c
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ generator scoring
+// k_gan_score: what an evaluation of the action generator does with the K samples of every conditioning row
+// (gan_eval.py), in one launch: each sample's error against the true action, their mean, the best of the K (and the
+// running best of the first k + 1: the whole best-of-k curve from one evaluation at K), how far apart the samples are,
+// the row's share of the Normalized-Diversification loss and what the discriminator makes of the samples.
+// k_ndiv's layout: one thread per (row, sample); K <= 64: 64 threads, a wave holds 64 / K rows, else 256 threads and
+// 256 / K rows.  The rows' samples, noise and logits sit in LDS.  Pass 1: thread i computes e_i, the row sums s_i =
+// sum_j d_ij of x and z in fp32 in j order (ndiv_block's arithmetic) and sum_j dx_ij in fp64; pass 2: its K hinge terms,
+// summed in fp64 in j order.  Then the row's thread 0 walks the K per-sample values in index order: the fp64 sums over
+// i, the arg-min / arg-max and the running minimum are serial loops of K steps -- a fixed order by construction.  No
+// atomics, no scratch buffer: two calls give the same bits.  The per-element arithmetic is in ndp::gan_score, __host__
+// __device__: tests/gan_score_host_driver.hip runs exactly these functions by this schedule on the CPU.
+namespace ndp {
+namespace gan_score {
+
+constexpr int kActionDim = 4;
+constexpr int kMaxNoise = 16;
+
+__host__ __device__ inline int block_threads(int k) { return k <= 64 ? 64 : 256; }
+__host__ __device__ inline int rows_per_block(int k) { return block_threads(k) / k; }
+
+// the LDS of a block of `slots` = rows_per_block * k (row, sample) slots: two fp64 arrays, then the fp32 ones
+__host__ __device__ inline size_t lds_bytes(int slots, int nz) {
+  return (size_t)slots * (2 * sizeof(double) + (kActionDim + nz + 4) * sizeof(float));
+}
+
+// e_k: the mean of the 4 squares of the fp32 differences, summed in fp64 in index order, rounded to fp32
+__host__ __device__ inline float sample_error(const float* x, const float* a) {
+  double s = 0.0;
+  for (int d = 0; d < kActionDim; ++d) {
+    const float e = x[d] - a[d];
+    s += (double)e * (double)e;
+  }
+  return (float)(s / (double)kActionDim);
+}
+
+// one more sample's 4 squares onto the row's fp64 sum, in (k, component) order
+__host__ __device__ inline double add_squares(double s, const float* x, const float* a) {
+  for (int d = 0; d < kActionDim; ++d) {
+    const float e = x[d] - a[d];
+    s += (double)e * (double)e;
+  }
+  return s;
+}
+
+// ||a - b||_2 over c channels as ndiv_block takes it: an fmaf chain from 0 in channel order, then sqrtf
+__host__ __device__ inline float distance(const float* a, const float* b, int c) {
+  float d2 = 0.f;
+  for (int d = 0; d < c; ++d) {
+    const float e = a[d] - b[d];
+    d2 = fmaf(e, e, d2);
+  }
+  return sqrtf(d2);
+}
+
+// relu(0.8 * dz / sz - dx / sx), two roundings for the product and the difference (never contracted), NaN kept
+__host__ __device__ inline float hinge(float dz, float sz, float dx, float sx) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const float h = __fsub_rn(__fmul_rn(dz / sz, 0.8f), dx / sx);
+#else
+  volatile float m = (dz / sz) * 0.8f;
+  const float h = m - dx / sx;
+#endif
+  return (h > 0.f || h != h) ? h : 0.f;
+}
+
+// the repository's BCE kernels' sigmoid (k_d: 1 / (1 + expf(-x)))
+__host__ __device__ inline float sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+// does `v` replace the running minimum `best`?  The first minimum wins; NaN is never chosen while a non-NaN exists.
+__host__ __device__ inline bool better_min(float v, float best) { return v == v && (best != best || v < best); }
+__host__ __device__ inline bool better_max(float v, float best) { return v == v && (best != best || v > best); }
+
+}  // namespace gan_score
+
+struct GanScoreArgs {
+  const float* x; const float* action; const float* z; const float* logits;
+  int64_t n; int k; int nz; int rows_per_block;
+  float* sample_err; float* mean_err; float* best_err; int32_t* best_k; float* best_curve;
+  float* spread; float* ndiv; float* d_fake_prob; int32_t* d_pick_k; float* d_pick_err;
+};
+
+__global__ __launch_bounds__(256) void k_gan_score(GanScoreArgs a) {
+  using namespace gan_score;
+  extern __shared__ __attribute__((aligned(16))) double gs_smem[];
+  const int k = a.k, nz = a.nz, G = a.rows_per_block, slots = G * k;
+  double* hs = gs_smem;                                  // [slots] sum_j hinge_ij
+  double* ds = hs + slots;                               // [slots] sum_j dx_ij
+  float* xs = reinterpret_cast<float*>(ds + slots);      // [slots,4]
+  float* zs = xs + slots * kActionDim;                   // [slots,nz]
+  float* sx = zs + slots * nz;                           // [slots]
+  float* sz = sx + slots;                                // [slots]
+  float* es = sz + slots;                                // [slots] e_k
+  float* ls = es + slots;                                // [slots] logits
+  const int nthreads = blockDim.x, t = threadIdx.x;
+  const int64_t n0 = (int64_t)blockIdx.x * G;
+  const int nrows = (int)((a.n - n0) < G ? (a.n - n0) : G);
+  const int nact = nrows * k;
+  const bool pairs = a.spread != nullptr || a.ndiv != nullptr;
+  for (int idx = t; idx < nact * kActionDim; idx += nthreads) xs[idx] = a.x[n0 * k * kActionDim + idx];
+  if (a.ndiv != nullptr)
+    for (int idx = t; idx < nact * nz; idx += nthreads) zs[idx] = a.z[n0 * k * nz + idx];
+  if (a.logits != nullptr)
+    for (int idx = t; idx < nact; idx += nthreads) ls[idx] = a.logits[n0 * k + idx];
+  __syncthreads();
+  const bool on = t < nact;
+  const int g = on ? t / k : 0;
+  const int64_t row = n0 + g;
+  if (on) {
+    if (a.action != nullptr) {
+      const float e = sample_error(xs + t * kActionDim, a.action + row * kActionDim);
+      es[t] = e;
+      if (a.sample_err != nullptr) a.sample_err[n0 * k + t] = e;
+    }
+    if (pairs) {
+      float ssx = 0.f, ssz = 0.f;
+      double dsum = 0.0;
+      for (int j = 0; j < k; ++j) {
+        const float dx = distance(xs + t * kActionDim, xs + (g * k + j) * kActionDim, kActionDim);
+        ssx += dx;
+        dsum += (double)dx;
+        if (a.ndiv != nullptr) ssz += distance(zs + t * nz, zs + (g * k + j) * nz, nz);
+      }
+      sx[t] = ssx;
+      sz[t] = ssz;
+      ds[t] = dsum;
+    }
+  }
+  __syncthreads();
+  if (on && a.ndiv != nullptr) {
+    const float sxi = sx[t], szi = sz[t];
+    double h = 0.0;
+    for (int j = 0; j < k; ++j) {
+      const float dx = distance(xs + t * kActionDim, xs + (g * k + j) * kActionDim, kActionDim);
+      const float dz = distance(zs + t * nz, zs + (g * k + j) * nz, nz);
+      h += (double)hinge(dz, szi, dx, sxi);
+    }
+    hs[t] = h;
+  }
+  __syncthreads();
+  if (!on || t != g * k) return;                         // the row's thread 0 walks its K samples in index order
+  const int s0 = g * k;
+  if (a.action != nullptr) {
+    double sum = 0.0;
+    float best = es[s0];
+    int bk = 0;
+    for (int i = 0; i < k; ++i) {
+      if (a.mean_err != nullptr) sum = add_squares(sum, xs + (s0 + i) * kActionDim, a.action + row * kActionDim);
+      if (better_min(es[s0 + i], best)) { best = es[s0 + i]; bk = i; }
+      if (a.best_curve != nullptr) a.best_curve[row * k + i] = best;
+    }
+    if (a.mean_err != nullptr) a.mean_err[row] = (float)(sum / (double)(k * kActionDim));
+    if (a.best_err != nullptr) a.best_err[row] = best;
+    if (a.best_k != nullptr) a.best_k[row] = bk;
+  }
+  if (a.spread != nullptr) {
+    double sum = 0.0;
+    for (int i = 0; i < k; ++i) sum += ds[s0 + i];
+    a.spread[row] = (float)(sum / ((double)k * (double)(k - 1)));
+  }
+  if (a.ndiv != nullptr) {
+    double sum = 0.0;
+    for (int i = 0; i < k; ++i) sum += hs[s0 + i];
+    a.ndiv[row] = (float)sum;
+  }
+  if (a.logits != nullptr) {
+    double sum = 0.0;
+    float top = ls[s0];
+    int pk = 0;
+    for (int i = 0; i < k; ++i) {
+      if (a.d_fake_prob != nullptr) sum += (double)sigmoid(ls[s0 + i]);
+      if (better_max(ls[s0 + i], top)) { top = ls[s0 + i]; pk = i; }
+    }
+    if (a.d_fake_prob != nullptr) a.d_fake_prob[row] = (float)(sum / (double)k);
+    if (a.d_pick_k != nullptr) a.d_pick_k[row] = pk;
+    if (a.d_pick_err != nullptr) a.d_pick_err[row] = es[s0 + pk];
+  }
+}
+
+}  // namespace ndp
+
+extern "C" {
+
+int ndp_gan_score(const float* action_hat, int64_t n, int k, const float* action, const float* noise, int nz,
+                  const float* fake_logits, float* sample_err, float* mean_err, float* best_err, int32_t* best_k,
+                  float* best_curve, float* spread, float* ndiv, float* d_fake_prob, int32_t* d_pick_k, float* d_pick_err,
+                  void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(action_hat != nullptr, "ndp_gan_score: null pointer (action_hat)");
+  NDP_CHECK_ARG(k >= 1 && k <= NDP_MAX_SAMPLES, "ndp_gan_score: k=%d outside 1..%d", k, NDP_MAX_SAMPLES);
+  NDP_CHECK_ARG(n >= 1 && n * k < (1ll << 31), "ndp_gan_score: bad row count %lld", (long long)n);
+  NDP_CHECK_ARG(sample_err || mean_err || best_err || best_k || best_curve || spread || ndiv || d_fake_prob || d_pick_k ||
+                d_pick_err, "ndp_gan_score: no output requested");
+  NDP_CHECK_ARG(action || !(sample_err || mean_err || best_err || best_k || best_curve || d_pick_err),
+                "ndp_gan_score: sample_err / mean_err / best_err / best_k / best_curve / d_pick_err need the true actions");
+  NDP_CHECK_ARG(noise || !ndiv, "ndp_gan_score: ndiv needs the noise");
+  NDP_CHECK_ARG(!noise || (nz >= 1 && nz <= gan_score::kMaxNoise), "ndp_gan_score: nz=%d outside 1..%d", nz,
+                gan_score::kMaxNoise);
+  NDP_CHECK_ARG(fake_logits || !(d_fake_prob || d_pick_k || d_pick_err),
+                "ndp_gan_score: d_fake_prob / d_pick_k / d_pick_err need fake_logits");
+  hipStream_t st = (hipStream_t)stream;
+  const int threads = gan_score::block_threads(k), G = gan_score::rows_per_block(k);
+  GanScoreArgs a{action_hat, action, ndiv ? noise : nullptr, fake_logits, n, k, ndiv ? nz : 0, G,
+                 sample_err, mean_err, best_err, best_k, best_curve, spread, ndiv, d_fake_prob, d_pick_k, d_pick_err};
+  const size_t lds = gan_score::lds_bytes(G * k, a.nz);
+  KTimer kt("k_gan_score", st);
+  hipLaunchKernelGGL(k_gan_score, dim3((unsigned)((n + G - 1) / G)), dim3(threads), lds, st, a);
+  return check_launch("k_gan_score");
+}
+
+}  // extern "C"

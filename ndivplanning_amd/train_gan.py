@@ -25,6 +25,17 @@ launch are staged into separate input slots, the arithmetic is unchanged),
 `training.gan.cache_codes` (default true: encode every trajectory once, the encoder being frozen).
 In data-parallel runs each rank caches only the trajectories of its own shard positions, so the
 cache fills over several epochs there.
+
+Validation (optional): `training.gan.val_data_path` (held-out trajectories, the forms of `train_data_path`),
+`val_every` (epochs, default 1) and `val_num_sample` (default `num_sample`).  At the end of every `val_every`-th
+epoch rank 0 evaluates the live decoder and discriminator -- their parameters are views into the trainer's flat
+buffers, nothing is copied -- with `gan_eval.evaluate` and logs `val_action_loss`, `val_best_action_loss`,
+`val_div_loss` and `val_spread` on one line after the epoch line.  It changes no bit of training: the trajectories
+are read by index, the noise comes from `ndp_uniform_noise` with a seed and buffers of its own (no generator that
+training reads is drawn from, the trainer's noise counter and captured graph are not touched), and the modules go
+back into training mode.  In a data-parallel run rank 0 evaluates alone and issues no collective while doing so;
+the in-kernel gradient exchange waits with a 10 s time-out (dp.py), so after a validation epoch all ranks meet at
+one barrier of the process group before any of them launches the next step.  Without the key nothing is added.
 """
 import importlib
 import logging
@@ -129,6 +140,42 @@ def encode_batch(frames, encoder, seq_length):
     return torch.cat([cur, tgt], dim=2).reshape(b * (t - 1), -1).contiguous()
 
 
+# the validation noise's Philox key: apart from every trainer's (random_seed * 1000 + rank)
+VAL_NOISE_SEED = 1 << 40
+
+
+def make_val_dataset(config, path):
+    """The held-out trajectories of `training.gan.val_data_path`, made as `make_dataset` makes the training set (same
+    trajectory_length); a synthetic set is seeded apart from the training set."""
+    path = str(path)
+    if path.startswith("synthetic:") or "/synthetic:" in path:
+        spec = path[path.index("synthetic:"):].split(":")
+        mode = spec[2] if len(spec) > 2 else "codes"
+        return SyntheticPushDataset(int(spec[1]), seq_length=config.trajectory_length, mode=mode, seed=int(config.random_seed) + 1)
+    return PushDataset(path, seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)),
+                       raw_jpeg=bool(_get(config, "raw_jpeg", False)))
+
+
+def validate(decoder, discriminator, encoder, val_dataset, num_sample, batch_size, seed, device):
+    """gan_eval.evaluate on the live modules, logged; returns the means as host floats.  Rank 0 calls this alone: no
+    collective is issued, no generator that training reads is drawn from, and the modules return to training mode."""
+    from . import gan_eval
+    decoder.eval()
+    discriminator.eval()
+    try:
+        result = gan_eval.evaluate(decoder, val_dataset, encoder=encoder, discriminator=discriminator, num_sample=num_sample,
+                                   batch_size=batch_size, seed=seed, device=device)
+        means = {k: float(result[k].item()) for k in ("action_mse", "best_action_mse", "ndiv_per_row", "spread", "d_fake_prob",
+                                                      "d_real_prob", "d_pick_mse")}
+        means["best_of_k_curve"] = result["best_of_k_curve"].tolist()
+    finally:
+        decoder.train()
+        discriminator.train()
+    logging.info("val_action_loss: {} val_best_action_loss: {} val_div_loss: {} val_spread: {}".format(
+        means["action_mse"], means["best_action_mse"], means["ndiv_per_row"], means["spread"]))
+    return means
+
+
 def epoch_batches(n_items, batch_size, generator):
     """Shuffled index batches of one epoch (ragged tail dropped): what DataLoader(shuffle=True,
     drop_last=True) does, as an explicit list so that cached epochs can follow the same order."""
@@ -150,6 +197,11 @@ def train(config):
     use_graph = bool(_get(g, "use_graph", True))
     steps_per_launch = int(_get(g, "steps_per_launch", 16))
     cache_codes = bool(_get(g, "cache_codes", True))
+    val_path, val_every = _get(g, "val_data_path", None), int(_get(g, "val_every", 1))
+    val_num_sample = int(_get(g, "val_num_sample", num_sample))
+    if val_path is not None and (val_every < 1 or not 1 <= val_num_sample <= 256):
+        raise ValueError("training.gan.val_every must be >= 1 and val_num_sample in 1..256, got %r and %r"
+                         % (val_every, val_num_sample))
 
     rank, world, local_rank = dp.env_world()
     if not torch.cuda.is_available():
@@ -214,6 +266,14 @@ def train(config):
         code_cache = torch.zeros(len(dataset), seq_length, 128, device=device)
         action_cache = torch.zeros(len(dataset), seq_length, 4, device=device)
         cached = torch.zeros(len(dataset), dtype=torch.bool)
+    # held-out trajectories (optional): rank 0 alone reads and evaluates them
+    val_dataset = make_val_dataset(config, val_path) if val_path is not None and rank == 0 else None
+    val_encoder = encoder
+    if val_dataset is not None and encoder is None and getattr(val_dataset, "mode", "images") != "codes":
+        rng_state = torch.get_rng_state()            # a seeded stand-in encoder draws from torch's generator: put it back
+        val_encoder = load_encoder(config, device)
+        torch.set_rng_state(rng_state)
+    val_history = []
     history = []
     # Replicas apply the same Adam update to the same summed gradients, so their parameters must stay bit-identical.
     # The in-kernel exchange has its own time-out word, but a sum that arrived WRONG (a flag overtaking its data on a
@@ -297,11 +357,25 @@ def train(config):
                 display.plot("gan", "discriminator", "GAN Loss", epoch, d_avg)
                 display.plot("gan", "generator", "GAN Loss", epoch, g_avg)
                 display.plot("pairwise_div", "loss", "Pairwise Divergence Loss", epoch, div_avg)
-            if epoch % epochs_per_stage == epochs_per_stage - 1:                # train_gan.py:249-266
-                os.makedirs(config.gan_save_path, exist_ok=True)
-                torch.cuda.synchronize(device)
-                torch.save(discriminator, os.path.join(config.gan_save_path, "gan_discriminator_{}.pt".format(epoch)))
-                torch.save(decoder, os.path.join(config.gan_save_path, "gan_decoder_{}.pt".format(epoch)))
+        if val_path is not None and (epoch + 1) % val_every == 0:
+            if val_dataset is not None:
+                means = validate(decoder, discriminator, val_encoder, val_dataset, val_num_sample, local_batch,
+                                 VAL_NOISE_SEED + random_seed, device)
+                val_history.append((epoch, means))
+                if display is not None:
+                    display.plot("val_action", "mean", "Validation Action Loss", epoch, means["action_mse"])
+                    display.plot("val_action", "best", "Validation Action Loss", epoch, means["best_action_mse"])
+                    display.plot("val_div", "loss", "Validation Pairwise Divergence Loss", epoch, means["ndiv_per_row"])
+                    display.plot("val_div", "spread", "Validation Pairwise Divergence Loss", epoch, means["spread"])
+            if world > 1:                    # rank 0 evaluated alone: meet before any rank launches the next step
+                dp.dist.barrier()
+        if rank == 0 and epoch % epochs_per_stage == epochs_per_stage - 1:      # train_gan.py:249-266
+            os.makedirs(config.gan_save_path, exist_ok=True)
+            torch.cuda.synchronize(device)
+            torch.save(discriminator, os.path.join(config.gan_save_path, "gan_discriminator_{}.pt".format(epoch)))
+            torch.save(decoder, os.path.join(config.gan_save_path, "gan_decoder_{}.pt".format(epoch)))
+    train.last_params = (trainer.g_flat, trainer.d_flat)               # tests: the replica's flat vectors
+    train.last_val = val_history                                       # [(epoch, {action_mse, best_action_mse, ...})]
     if p2p is not None:
         del trainer
         p2p.close()
