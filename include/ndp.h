@@ -585,7 +585,30 @@ int ndp_ae_decode(const float *folded_params, const float *codes, int64_t n_imag
  *                          1 <= K <= NDP_MAX_SAMPLES, 1 <= nz <= 16, n >= 1, n * K < 2^31.  An output without the input
  *                          it needs, no output at all, a limit exceeded: NDP_E_ARG, nothing launched.  No scratch buffer,
  *                          no atomics (two calls give the same bits), no host synchronisation.  The caller owns every
- *                          buffer. */
+ *                          buffer.
+ *   ndp_image_quality      SSIM and PSNR of n_pairs image pairs (image_quality.py; nothing in the reference computes
+ *                          either).  Pair p compares a[a_idx ? a_idx[p] : p] with b[b_idx ? b_idx[p] : p]; each side is
+ *                          EXACTLY ONE of floats [n,3,128,128] in [-1, 1] and byte frames [n,128,128,3] (through the
+ *                          table of ndp_eval_frames_u8: the bits of the floats of the same bytes).
+ *                          - scale: u = (x + 1) * 0.5 in fp32, clamped to [0, 1] (-Inf -> 0, +Inf -> 1); a NaN stays
+ *                            NaN and makes both results of its pair NaN;
+ *                          - psnr [n_pairs] (or NULL): the fp32 differences of u, their squares summed in fp64 in a fixed
+ *                            order, mse = sum / 49152, 10 * log10(1 / mse) in fp64 rounded to fp32; mse == 0: +Inf;
+ *                          - ssim [n_pairs] (or NULL): Wang et al. 2004 as scikit-image computes it with
+ *                            gaussian_weights=True, sigma=1.5, use_sample_covariance=False, data_range=1: per channel an
+ *                            11-tap separable Gaussian g[i] ~ exp(-(i-5)^2 / (2 * 1.5^2)) (normalised in double, rounded
+ *                            to fp32 once) over the windows wholly inside the image (118 x 118 positions) gives ux, uy,
+ *                            uxx, uyy, uxy of x, y, x*x, y*y, x*y; vx = uxx - ux*ux, vy = uyy - uy*uy, vxy = uxy - ux*uy;
+ *                            S = ((2 ux uy + C1)(2 vxy + C2)) / ((ux ux + uy uy + C1)(vx + vy + C2)), C1 = 0.01^2,
+ *                            C2 = 0.03^2; the mean of the 3 * 118 * 118 values of S, summed in fp64 in a fixed order,
+ *                            rounded to fp32 once.  Filtering and S are fp32, in an operation order that gives an image
+ *                            against itself exactly 1.0f.
+ *                          An index outside its array gives NaN for both results of that pair; nothing is read through
+ *                          it.  workspace: ndp_image_quality_ws_bytes(n_pairs) bytes (0 for a bad request), 8-byte
+ *                          aligned; float images 16-byte aligned.  Both or neither pointer of a side, no output,
+ *                          n_pairs < 1, n_a < 1, n_b < 1, a workspace that is too small: NDP_E_ARG, nothing launched.
+ *                          No atomics, no host synchronisation; two calls give the same bits, and the result does not
+ *                          depend on how the rows are split over workgroups.  The caller owns every buffer. */
 int ndp_eval_score_select(const float *pred, int64_t n_traj, int rollouts, const float *target, int64_t n_target,
                           const int32_t *target_idx, int64_t values, const float *actions0, const float *pred0,
                           const int32_t *forced, float *err, int32_t *choice, float *action_out, float *pred_out,
@@ -604,6 +627,10 @@ int ndp_gan_score(const float *action_hat, int64_t n, int k, const float *action
                   const float *fake_logits, float *sample_err, float *mean_err, float *best_err, int32_t *best_k,
                   float *best_curve, float *spread, float *ndiv, float *d_fake_prob, int32_t *d_pick_k,
                   float *d_pick_err, void *stream);
+int64_t ndp_image_quality_ws_bytes(int64_t n_pairs);
+int ndp_image_quality(const float *a_f32, const uint8_t *a_u8, int64_t n_a, const int32_t *a_idx, const float *b_f32,
+                      const uint8_t *b_u8, int64_t n_b, const int32_t *b_idx, int64_t n_pairs, float *ssim, float *psnr,
+                      void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------- JPEG decode ---
  * The frames of the reference's trajectory bundles are JPEG streams (generate_trajectories.py:113-122: PIL, quality 95);

@@ -156,6 +156,9 @@ SIGNATURES = {
                              c_void_p, c_void_p, c_void_p, c_void_p]),
     "ndp_gan_score": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ndp_image_quality_ws_bytes": (c_int64, [c_int64]),
+    "ndp_image_quality": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64,
+                                  c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ndp_jpeg_workspace_bytes": (c_int64, [c_int64, c_int64]),
     "ndp_jpeg_decode_u8": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ndp_jpeg_encode_workspace_bytes": (c_int64, [c_int64]),

@@ -10,7 +10,8 @@ The codes come from the eval-mode `Encoder` (ndp_encoder_forward / _u8), the ima
 (csrc/ndp_autoencoder.inc: the eval-mode decoder with its BatchNorms folded into the weights, and an output kernel that
 also writes the reference's bytes, `denorm(...).astype(np.uint8)` of train_autoencoder.py:42-43, 97-100, and the squared
 error against the input).  Both modules are used in eval mode; there is no CPU path (`NdpError`), and nothing here
-synchronises with the host: every result is a device tensor."""
+synchronises with the host: every result is a device tensor.  evaluate(quality=True) / --quality add SSIM and PSNR of
+every reconstruction against its input (`ndp_image_quality`, image_quality.py); off by default, nothing else changes."""
 import importlib
 import os
 from argparse import ArgumentParser
@@ -18,6 +19,7 @@ from argparse import ArgumentParser
 import torch
 
 from . import _capi
+from . import image_quality as IQ
 from . import jpeg as jpeg_frames
 from .models import image_autoencoder as IA
 
@@ -82,11 +84,13 @@ def _batches(dataset, batch_size, device, jpeg_decoder):
             yield frames.view(-1, *frames.shape[2:]).contiguous()
 
 
-def evaluate(encoder, decoder, dataset, batch_size=16, device=None, keep=0):
+def evaluate(encoder, decoder, dataset, batch_size=16, device=None, keep=0, quality=False):
     """The reconstruction error over every frame of `dataset` (PushDataset / SyntheticPushDataset: images, byte frames or
     JPEG streams, which `jpeg.JpegDecoder` decodes on the device): (mean MSE [1], per-image MSE [frames]) -- device
     tensors, no host synchronisation per batch.  keep > 0: also the first `keep` (input bytes, reconstruction bytes)
-    pairs, uint8 [keep,128,128,3] each, as a third result."""
+    pairs, uint8 [keep,128,128,3] each, as a third result.  quality=True: the last result is a dict of the unquantised
+    reconstructions' SSIM and PSNR against their inputs, {"ssim" [frames], "psnr" [frames], "mean_ssim" [1], "mean_psnr"
+    [1]} (means in fp64 over the fp32 values, none skipped); the results before it hold the same bits."""
     _require_eval(encoder=encoder, decoder=decoder)
     device = torch.device(device) if device is not None else next(decoder.parameters()).device
     if device.type != "cuda":
@@ -94,21 +98,31 @@ def evaluate(encoder, decoder, dataset, batch_size=16, device=None, keep=0):
     if len(dataset) == 0 or int(batch_size) < 1:
         raise ValueError("evaluate needs a non-empty dataset and batch_size >= 1")
     jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
-    per_image, pairs, kept = [], [], 0
+    per_image, pairs, kept, ssim, psnr = [], [], 0, [], []
     for frames in _batches(dataset, int(batch_size), device, jpeg_decoder):
-        recon, sq, _ = reconstruct(encoder, decoder, frames, out="bytes", errors=True)
+        recon, sq, _ = reconstruct(encoder, decoder, frames, out="float" if quality else "bytes", errors=True)
         per_image.append(sq)
+        if quality:
+            s, p = IQ.image_quality(recon, frames)
+            ssim.append(s)
+            psnr.append(p)
         if kept < keep:
             k = min(keep - kept, int(frames.shape[0]))
+            if quality:                                                  # the bytes of the few that are kept
+                recon = reconstruct(encoder, decoder, frames[:k].contiguous(), out="bytes", errors=False)[0]
             pairs.append((_to_bytes(frames[:k]), recon[:k]))
             kept += k
     if jpeg_decoder is not None:
         jpeg_decoder.finish()
     per_image = torch.cat(per_image)
     mean = per_image.double().mean().float().view(1)                     # (of the fp32 per-image values, in fp64: as ndp_ae_decode's)
+    result = (mean, per_image)
     if keep > 0:
-        return mean, per_image, (torch.cat([a for a, _ in pairs]), torch.cat([b for _, b in pairs]))
-    return mean, per_image
+        result += ((torch.cat([a for a, _ in pairs]), torch.cat([b for _, b in pairs])),)
+    if quality:
+        ssim, psnr = torch.cat(ssim), torch.cat(psnr)
+        result += ({"ssim": ssim, "psnr": psnr, "mean_ssim": IQ.mean(ssim), "mean_psnr": IQ.mean(psnr)},)
+    return result
 
 
 def _to_bytes(frames):
@@ -153,6 +167,7 @@ def make_parser():
     parser.add_argument("--device", default="cuda")
     parser.add_argument("--save-dir", default=None, help="write the first --num-save input / reconstruction pairs here as PNG")
     parser.add_argument("--num-save", type=int, default=8)
+    parser.add_argument("--quality", action="store_true", help="also print the mean SSIM and PSNR of the reconstructions")
     return parser
 
 
@@ -163,9 +178,11 @@ def main(argv=None, log=print):
     encoder, decoder = load_module(args.encoder, device), load_module(args.decoder, device)
     dataset = make_dataset(args.data, raw_jpeg=args.raw_jpeg)
     keep = args.num_save if args.save_dir else 0
-    result = evaluate(encoder, decoder, dataset, batch_size=args.batch_size, device=device, keep=keep)
+    result = evaluate(encoder, decoder, dataset, batch_size=args.batch_size, device=device, keep=keep, quality=args.quality)
     mean = float(result[0].item())
     log("val_recon_loss:", mean, "frames:", int(result[1].numel()))
+    if args.quality:
+        log("val_recon_ssim:", float(result[-1]["mean_ssim"].item()), "val_recon_psnr:", float(result[-1]["mean_psnr"].item()))
     if args.save_dir:
         save_pairs(result[2][0], result[2][1], args.save_dir)
         log("wrote %d pairs to %s" % (int(result[2][0].shape[0]), args.save_dir))

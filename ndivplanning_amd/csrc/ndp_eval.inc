@@ -620,3 +620,293 @@ int ndp_gan_score(const float* action_hat, int64_t n, int k, const float* action
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------------ image quality
+// k_image_quality: SSIM and PSNR of image pairs, 3 x 128 x 128 each, floats NCHW in [-1, 1] or byte frames HWC.  The
+// definition (DESIGN 5l): u = clamp((x + 1) / 2, 0, 1) in fp32 with NaN kept (bytes through u8_norm_table: the bits of the
+// floats of the same bytes); PSNR = 10 log10(1 / mse) of the fp32 differences of u, squares summed in fp64; SSIM in the
+// form scikit-image computes with gaussian_weights=True, sigma=1.5, use_sample_covariance=False, data_range=1: an 11-tap
+// separable Gaussian over the windows wholly inside the image (118 x 118 positions per channel), filtering and S in fp32,
+// the 41,772 values of S summed in fp64.
+// One workgroup per (pair, channel, band of ROWS = 16 or 32 output rows): ROWS + 10 rows of both operands are scaled into LDS, the
+// five maps x, y, xx, yy, xy are filtered along the rows into LDS, then 16 consecutive lanes own one output row: lane j
+// filters columns j, j + 16, ... down the 11 rows, evaluates S and adds it to its fp64 sum in column order; the 16 sums
+// are folded by a fixed butterfly.  The squared differences of the band's own input rows are summed by the same lane
+// schedule.  What leaves a workgroup is one fp64 sum per output row and per input row, in the workspace: which workgroup
+// computed a row does not show in it, so the result does not depend on ROWS.  k_image_quality_finish, one workgroup per
+// pair, adds the 354 and 384 row sums by a fixed tree and writes the two floats.  No atomics, no host synchronisation:
+// two calls give the same bits.  The arithmetic and the schedule are in ndp::image_quality, __host__ __device__:
+// tests/image_quality_host_driver.hip runs exactly these functions on the CPU.
+namespace ndp {
+namespace image_quality {
+
+constexpr int kSide = 128, kPlane = kSide * kSide, kValues = 3 * kPlane;
+constexpr int kTaps = 11, kHalo = kTaps - 1;
+constexpr int kOut = kSide - kHalo;               // 118 window positions per axis
+constexpr int kSsimValues = 3 * kOut * kOut;      // 41,772
+constexpr int kRowLanes = 16;                     // lanes that share one row's sum
+constexpr int kSsimRows = 3 * kOut, kPsnrRows = 3 * kSide;
+constexpr int kRowSums = kSsimRows + kPsnrRows;   // doubles per pair in the workspace: [3][118] then [3][128]
+constexpr int kFinishThreads = 256;               // folds up to 512 row sums
+
+// g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum, computed in double and rounded to fp32 once (the host driver recomputes it)
+__host__ __device__ inline float tap(int i) {
+  constexpr float g[6] = {0x1.10656p-2f, 0x1.b43c4p-3f, 0x1.bff0fep-4f, 0x1.26eb18p-5f, 0x1.f1fe02p-8f, 0x1.0d956cp-10f};
+  return g[i < 5 ? 5 - i : i - 5];
+}
+
+// [-1, 1] -> [0, 1], clamped; -Inf -> 0, +Inf -> 1, NaN stays NaN (both comparisons are false)
+__host__ __device__ inline float unit(float x) {
+  const float u = (x + 1.0f) * 0.5f;
+  return u < 0.0f ? 0.0f : u > 1.0f ? 1.0f : u;
+}
+
+// one rounding: the products that are filtered, never contracted into the filter's first fmaf
+__host__ __device__ inline float product(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// the filter: an fmaf chain from 0 in tap order over v[0], v[stride], ..
+__host__ __device__ inline float filter(const float* v, int stride) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int k = 0; k < kTaps; ++k) acc = fmaf(tap(k), v[k * stride], acc);
+  return acc;
+}
+
+// S at one position from the five filtered moments.  Every operation is rounded on its own (no contraction), in an
+// order that makes numerator and denominator the same bits when the operands are: 2ab = ab + ab, 2v = v + v.
+__host__ __device__ inline float ssim_at(float ux, float uy, float uxx, float uyy, float uxy) {
+#pragma clang fp contract(off)
+  constexpr float c1 = (float)(0.01 * 0.01), c2 = (float)(0.03 * 0.03);
+  const float mxx = ux * ux, myy = uy * uy, mxy = ux * uy;
+  const float vx = uxx - mxx, vy = uyy - myy, vxy = uxy - mxy;
+  const float num = (2.0f * mxy + c1) * (2.0f * vxy + c2);
+  const float den = ((mxx + myy) + c1) * ((vx + vy) + c2);
+  return num / den;
+}
+
+__host__ __device__ inline double sq_diff(float a, float b) {
+#pragma clang fp contract(off)
+  const float d = a - b;
+  return (double)d * (double)d;
+}
+
+// ---- the band schedule
+__host__ __device__ inline int bands(int rows) { return (kOut + rows - 1) / rows; }
+__host__ __device__ inline int block_threads(int rows) { return rows * kRowLanes; }
+
+// band `band` of `rows` output rows: its first row (output and input), how many output rows it computes, how many input
+// rows it stages and how many of those it owns for PSNR (the last band also owns the 10 rows below its windows)
+__host__ __device__ inline void band_rows(int band, int rows, int* r0, int* out_rows, int* in_rows, int* own_rows) {
+  *r0 = band * rows;
+  *out_rows = kOut - *r0 < rows ? kOut - *r0 : rows;
+  *in_rows = *out_rows + kHalo;
+  *own_rows = band == bands(rows) - 1 ? *in_rows : *out_rows;
+}
+
+// horizontal pass, item i of in_rows * 118: its staged row and its first column
+__host__ __device__ inline void h_item(int i, int* row, int* col) {
+  *row = i / kOut;
+  *col = i - *row * kOut;
+}
+
+// where pair p, channel c keeps its row sums
+__host__ __device__ inline int64_t ssim_slot(int64_t pair, int c, int row) { return pair * kRowSums + c * kOut + row; }
+__host__ __device__ inline int64_t psnr_slot(int64_t pair, int c, int row) {
+  return pair * kRowSums + kSsimRows + c * kSide + row;
+}
+
+// the results from the two folded sums
+__host__ __device__ inline float ssim_of(double sum) { return (float)(sum / (double)kSsimValues); }
+__host__ __device__ inline float psnr_of(double sum) {
+  const double mse = sum / (double)kValues;
+  return mse == 0.0 ? INFINITY : (float)(10.0 * log10(1.0 / mse));
+}
+
+}  // namespace image_quality
+
+struct ImageQualityArgs {
+  const float* a_f32; const unsigned char* a_u8; int64_t n_a; const int32_t* a_idx;
+  const float* b_f32; const unsigned char* b_u8; int64_t n_b; const int32_t* b_idx;
+  int64_t n_pairs;
+  double* sums;                                      // [n_pairs][kRowSums]
+  float* ssim; float* psnr;
+};
+
+// rows [r0, r0 + in_rows) of channel c of one image, scaled, into dst[in_rows][128]
+__device__ __forceinline__ void iq_stage(const float* f32, const unsigned char* u8, int64_t row, int c, int r0, int in_rows,
+                                         const float* lut, float* dst) {
+  using namespace image_quality;
+  const int t = threadIdx.x, nt = blockDim.x;
+  if (f32) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(f32 + row * kValues + c * kPlane + r0 * kSide);
+    for (int i = t; i < in_rows * (kSide / 4); i += nt) {
+      const f32x4 v = src[i];
+      *reinterpret_cast<f32x4*>(dst + 4 * i) = f32x4{unit(v[0]), unit(v[1]), unit(v[2]), unit(v[3])};
+    }
+  } else {
+    const unsigned char* src = u8 + row * kValues + (int64_t)r0 * kSide * 3 + c;
+    for (int i = t; i < in_rows * kSide; i += nt) dst[i] = unit(lut[src[3 * i]]);
+  }
+}
+
+// the sum over the 16 lanes of a row, the same bits in each: v[j] += v[j + w], w = 8, 4, 2, 1
+__device__ __forceinline__ double iq_row_fold(double v) {
+#pragma unroll
+  for (int w = image_quality::kRowLanes / 2; w > 0; w >>= 1) v += __shfl_xor(v, w, image_quality::kRowLanes);
+  return v;
+}
+
+template <int ROWS>
+__global__ __launch_bounds__(ROWS * image_quality::kRowLanes) void k_image_quality(ImageQualityArgs a) {
+  using namespace image_quality;
+  constexpr int kIn = ROWS + kHalo;
+  __shared__ __attribute__((aligned(16))) float xs[kIn * kSide];
+  __shared__ __attribute__((aligned(16))) float ys[kIn * kSide];
+  __shared__ float hs[5][kIn * kOut];                 // x, y, xx, yy, xy filtered along the rows
+  __shared__ float lut[256];
+  const int t = threadIdx.x, nt = ROWS * kRowLanes;
+  const int nb = bands(ROWS);
+  const int band = blockIdx.x % nb, c = (blockIdx.x / nb) % 3;
+  const int64_t pair = blockIdx.x / (3 * nb);
+  const int64_t ra = fm_score::row_of(a.a_idx, pair, a.n_a), rb = fm_score::row_of(a.b_idx, pair, a.n_b);
+  if (ra < 0 || rb < 0) return;                       // (uniform) the finish kernel writes NaN and reads no sum
+  int r0, out_rows, in_rows, own_rows;
+  band_rows(band, ROWS, &r0, &out_rows, &in_rows, &own_rows);
+  if (a.a_u8 || a.b_u8) {
+    u8_norm_table(lut);
+    __syncthreads();
+  }
+  iq_stage(a.a_f32, a.a_u8, ra, c, r0, in_rows, lut, xs);
+  iq_stage(a.b_f32, a.b_u8, rb, c, r0, in_rows, lut, ys);
+  __syncthreads();
+  const int lane = t % kRowLanes, group = t / kRowLanes;
+  if (a.psnr) {                                       // own_rows <= ROWS + 10 <= 2 ROWS: at most two rounds
+    for (int r = group; r < own_rows; r += ROWS) {
+      double s = 0.0;
+      for (int col = lane; col < kSide; col += kRowLanes) s += sq_diff(xs[r * kSide + col], ys[r * kSide + col]);
+      s = iq_row_fold(s);
+      if (lane == 0) a.sums[psnr_slot(pair, c, r0 + r)] = s;
+    }
+  }
+  if (!a.ssim) return;
+  for (int i = t; i < in_rows * kOut; i += nt) {
+    int row, col;
+    h_item(i, &row, &col);
+    float x[kTaps], y[kTaps], xx[kTaps], yy[kTaps], xy[kTaps];
+#pragma unroll
+    for (int k = 0; k < kTaps; ++k) {
+      x[k] = xs[row * kSide + col + k];
+      y[k] = ys[row * kSide + col + k];
+      xx[k] = product(x[k], x[k]);
+      yy[k] = product(y[k], y[k]);
+      xy[k] = product(x[k], y[k]);
+    }
+    hs[0][i] = filter(x, 1);
+    hs[1][i] = filter(y, 1);
+    hs[2][i] = filter(xx, 1);
+    hs[3][i] = filter(yy, 1);
+    hs[4][i] = filter(xy, 1);
+  }
+  __syncthreads();
+  if (group < out_rows) {                             // (uniform over each 16 lanes)
+    double s = 0.0;
+    for (int col = lane; col < kOut; col += kRowLanes) {
+      const int at = group * kOut + col;
+      s += (double)ssim_at(filter(hs[0] + at, kOut), filter(hs[1] + at, kOut), filter(hs[2] + at, kOut),
+                           filter(hs[3] + at, kOut), filter(hs[4] + at, kOut));
+    }
+    s = iq_row_fold(s);
+    if (lane == 0) a.sums[ssim_slot(pair, c, r0 + group)] = s;
+  }
+}
+
+// the sum of v[0 .. n), n <= 512, by a fixed tree over 512 slots (the empty ones hold 0); every thread calls it
+__device__ __forceinline__ double iq_finish_sum(const double* v, int n, double* red) {
+  constexpr int T = image_quality::kFinishThreads;
+  const int t = threadIdx.x;
+  red[t] = (t < n ? v[t] : 0.0) + (t + T < n ? v[t + T] : 0.0);
+  __syncthreads();
+  for (int w = T / 2; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  const double s = red[0];
+  __syncthreads();
+  return s;
+}
+
+__global__ __launch_bounds__(image_quality::kFinishThreads) void k_image_quality_finish(ImageQualityArgs a) {
+  using namespace image_quality;
+  __shared__ double red[kFinishThreads];
+  const int64_t pair = blockIdx.x;
+  const bool ok = fm_score::row_of(a.a_idx, pair, a.n_a) >= 0 && fm_score::row_of(a.b_idx, pair, a.n_b) >= 0;
+  if (!ok) {                                          // (uniform) nothing was written for this pair, nothing is read
+    if (threadIdx.x == 0) {
+      if (a.ssim) a.ssim[pair] = NAN;
+      if (a.psnr) a.psnr[pair] = NAN;
+    }
+    return;
+  }
+  if (a.ssim) {
+    const double s = iq_finish_sum(a.sums + ssim_slot(pair, 0, 0), kSsimRows, red);
+    if (threadIdx.x == 0) a.ssim[pair] = ssim_of(s);
+  }
+  if (a.psnr) {
+    const double s = iq_finish_sum(a.sums + psnr_slot(pair, 0, 0), kPsnrRows, red);
+    if (threadIdx.x == 0) a.psnr[pair] = psnr_of(s);
+  }
+}
+
+// 16-row bands (24 workgroups of 256 threads per pair) while each of them still gets a CU of its own (24 n <= 256), 32-row
+// bands (12 of 512 threads: two waves per SIMD, and 42 rows filtered for 32 instead of 26 for 16) beyond that.  Measured
+// on an MI355X (DESIGN 5l): 16 rows win by 5 % at 1 .. 10 pairs, 32 rows by 20 to 35 % at 16 .. 224.
+__host__ __device__ inline int image_quality_band_rows(int64_t n_pairs) { return n_pairs <= 10 ? 16 : 32; }
+
+}  // namespace ndp
+
+extern "C" {
+
+int64_t ndp_image_quality_ws_bytes(int64_t n_pairs) {
+  return n_pairs < 1 || n_pairs > ndp::kEvalMaxPairs ? 0
+                                                     : n_pairs * ndp::image_quality::kRowSums * (int64_t)sizeof(double);
+}
+
+int ndp_image_quality(const float* a_f32, const uint8_t* a_u8, int64_t n_a, const int32_t* a_idx, const float* b_f32,
+                      const uint8_t* b_u8, int64_t n_b, const int32_t* b_idx, int64_t n_pairs, float* ssim, float* psnr,
+                      void* workspace, int64_t workspace_bytes, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG((a_f32 != nullptr) != (a_u8 != nullptr),
+                "ndp_image_quality: exactly one of a_f32 and a_u8 must be given");
+  NDP_CHECK_ARG((b_f32 != nullptr) != (b_u8 != nullptr),
+                "ndp_image_quality: exactly one of b_f32 and b_u8 must be given");
+  NDP_CHECK_ARG(ssim || psnr, "ndp_image_quality: no output requested (null pointer ssim and psnr)");
+  NDP_CHECK_ARG(n_pairs >= 1 && n_a >= 1 && n_b >= 1 && n_pairs <= kEvalMaxPairs,
+                "ndp_image_quality: bad sizes (n_pairs %lld, n_a %lld, n_b %lld)", (long long)n_pairs, (long long)n_a,
+                (long long)n_b);
+  NDP_CHECK_ARG(workspace && workspace_bytes >= ndp_image_quality_ws_bytes(n_pairs),
+                "ndp_image_quality: workspace of %lld bytes, %lld needed", (long long)workspace_bytes,
+                (long long)ndp_image_quality_ws_bytes(n_pairs));
+  NDP_CHECK_ARG((reinterpret_cast<uintptr_t>(workspace) & 7) == 0, "ndp_image_quality: workspace must be 8-byte aligned");
+  NDP_CHECK_ARG(((reinterpret_cast<uintptr_t>(a_f32) | reinterpret_cast<uintptr_t>(b_f32)) & 15) == 0,
+                "ndp_image_quality: float images must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  ImageQualityArgs a{a_f32, a_u8, n_a, a_idx, b_f32, b_u8, n_b, b_idx, n_pairs, reinterpret_cast<double*>(workspace),
+                     ssim, psnr};
+  const int rows = image_quality_band_rows(n_pairs);
+  const unsigned grid = (unsigned)(n_pairs * 3 * image_quality::bands(rows));
+  {
+    KTimer kt("k_image_quality", st);
+    if (rows == 16) hipLaunchKernelGGL(k_image_quality<16>, dim3(grid), dim3(image_quality::block_threads(16)), 0, st, a);
+    else hipLaunchKernelGGL(k_image_quality<32>, dim3(grid), dim3(image_quality::block_threads(32)), 0, st, a);
+    const int rc = check_launch("k_image_quality");
+    if (rc) return rc;
+  }
+  KTimer kt("k_image_quality_finish", st);
+  hipLaunchKernelGGL(k_image_quality_finish, dim3((unsigned)n_pairs), dim3(image_quality::kFinishThreads), 0, st, a);
+  return check_launch("k_image_quality_finish");
+}
+
+}  // extern "C"

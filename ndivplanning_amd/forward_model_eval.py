@@ -13,7 +13,9 @@ the scoring from `ndp_fm_score` (csrc/ndp_eval.inc: one launch gives every predi
 the MSE of the start frame against the same target and the reference's display bytes, `denorm(...).astype(np.uint8)` of
 train_forward_model.py:116-145; targets and start frames are addressed through index maps, no gathered copy).  The
 module is used in eval mode; there is no CPU path (`NdpError`), and nothing here synchronises with the host per batch:
-every result is a device tensor."""
+every result is a device tensor.  quality=True (predict, rollout, evaluate; --quality) adds SSIM and PSNR of the
+same pairs -- prediction against target, start frame against target -- from `ndp_image_quality` (image_quality.py): the MSE
+rewards a blurred prediction, these do not.  Off by default, and nothing else changes with it."""
 import importlib
 import os
 from argparse import ArgumentParser
@@ -22,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _capi
+from . import image_quality as IQ
 from . import jpeg as jpeg_frames
 from .autoencoder_eval import _check_out, _require_eval, _require_gpu, _to_bytes
 
@@ -89,27 +92,39 @@ def _mean(per_image):
     return per_image.double().mean().float().view(1)                 # of the fp32 per-image values, in fp64
 
 
-def predict(fwd_model, state, actions, target=None, out="float"):
+def _quality(pred, base, target, base_idx=None, target_idx=None):
+    """(ssim, psnr, persistence_ssim, persistence_psnr): two ndp_image_quality launches, the predictions against their
+    targets, then the base frames against the same targets."""
+    ssim, psnr = IQ.image_quality(pred, target, b_idx=target_idx)
+    base_ssim, base_psnr = IQ.image_quality(base, target, a_idx=base_idx, b_idx=target_idx)
+    return ssim, psnr, base_ssim, base_psnr
+
+
+def predict(fwd_model, state, actions, target=None, out="float", quality=False):
     """(next_state, per-image MSE [n], persistence MSE [n], mean MSE [1]) of one eval-mode step from `state`, float32
     [n,3,128,128] in [-1,1] or byte frames uint8 [n,128,128,3] (normalised as the loader does, as the kernels read them).
     next_state: float32 NCHW (out="float") or the reference's bytes HWC (out="bytes": below 0 / above 255 saturate).  The
     errors are against `target` (float or byte frames); the persistence MSE is that of `state` itself against the target.
-    Without a target the three error results are None."""
+    Without a target the three error results are None.  quality=True: four more results follow, SSIM and PSNR per image of
+    the prediction and of `state` itself against the target (ssim, psnr, persistence_ssim, persistence_psnr [n]; None
+    without a target)."""
     _check_out(out)
     _require_eval(fwd_model=fwd_model)
     _require_gpu(state, "state")
     pred = _forward(fwd_model, state, actions)
     if target is None:
-        return (score(pred, out_bytes=True)[2] if out == "bytes" else pred), None, None, None
+        return ((score(pred, out_bytes=True)[2] if out == "bytes" else pred), None, None, None) + ((None,) * 4 if quality else ())
     err, base_err, pred_u8 = score(pred, target, base=state, out_bytes=out == "bytes")
-    return (pred_u8 if out == "bytes" else pred), err, base_err, _mean(err)
+    extra = _quality(pred, state, target) if quality else ()
+    return ((pred_u8 if out == "bytes" else pred), err, base_err, _mean(err)) + extra
 
 
-def rollout(fwd_model, state0, actions, targets=None, out="float"):
+def rollout(fwd_model, state0, actions, targets=None, out="float", quality=False):
     """H eval-mode steps from state0 [B,...] (float NCHW or byte frames) with actions [B,H,4], every step on the model's
     own fp32 prediction of the step before, as `mpc_plan` does (bytes are never fed back).  Returns (predictions
     [B,H,3,128,128] float32 or [B,H,128,128,3] bytes, err [B,H], persistence [B,H]); targets [B,H,...] float or byte
-    frames, None: the two errors are None.  persistence[b,h] is the error of state0[b] against target h."""
+    frames, None: the two errors are None.  persistence[b,h] is the error of state0[b] against target h.  quality=True:
+    (ssim, psnr, persistence_ssim, persistence_psnr), [B,H] each, follow (None without targets)."""
     _check_out(out)
     _require_eval(fwd_model=fwd_model)
     _require_gpu(state0, "state0")
@@ -124,6 +139,7 @@ def rollout(fwd_model, state0, actions, targets=None, out="float"):
         flat_targets = _images(targets, "targets")                  # row b * H + h
     rows = torch.arange(bsz, device=dev, dtype=torch.int32) * steps
     preds, errs, bases, state = [], [], [], state0
+    quals = [[], [], [], []]
     for h in range(steps):
         state = _forward(fwd_model, state, actions[:, h].contiguous())
         want_bytes = out == "bytes"
@@ -131,13 +147,17 @@ def rollout(fwd_model, state0, actions, targets=None, out="float"):
             err, base_err, pred_u8 = score(state, flat_targets, rows + h, base=state0, out_bytes=want_bytes)
             errs.append(err)
             bases.append(base_err)
+            if quality:
+                for q, v in zip(quals, _quality(state, state0, flat_targets, target_idx=rows + h)):
+                    q.append(v)
         elif want_bytes:
             pred_u8 = score(state, out_bytes=True)[2]
         preds.append(pred_u8 if want_bytes else state)
     preds = torch.stack(preds, dim=1)
     if flat_targets is None:
-        return preds, None, None
-    return preds, torch.stack(errs, dim=1), torch.stack(bases, dim=1)
+        return (preds, None, None) + ((None,) * 4 if quality else ())
+    extra = tuple(torch.stack(q, dim=1) for q in quals) if quality else ()
+    return (preds, torch.stack(errs, dim=1), torch.stack(bases, dim=1)) + extra
 
 
 def rollout_schedule(T, horizon=None):
@@ -184,7 +204,10 @@ def _maps(sched, T, b, device):
                   for col in step) for step in sched]
 
 
-def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=0):
+QUALITY_KEYS = ("ssim", "psnr", "persistence_ssim", "persistence_psnr")
+
+
+def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=0, quality=False):
     """The multi-step prediction error over `dataset` (PushDataset / SyntheticPushDataset: images, byte frames or JPEG
     streams, which `jpeg.JpegDecoder` decodes on the device), from EVERY start frame: pass h of a batch of B trajectories
     runs the B * (T - h) starts still alive (rollout_schedule) in ONE forward call, on their own predictions of pass
@@ -196,7 +219,12 @@ def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=
         errors [P], persistence [P], index [P,3] int32 (trajectory, start, h)      every prediction's own values
       keep > 0: also `strips`, the first `keep` starts that live for all H steps (trajectory-major), as bytes:
         {"start" [k,128,128,3], "targets" [k,H,128,128,3], "predictions" [k,H,128,128,3]}
-    The means are taken in fp64 over the fp32 per-prediction values."""
+      quality=True: also horizon_ssim, horizon_psnr, persistence_ssim, persistence_psnr [H] (of the start frame against the
+        same target) and `quality`, a dict of every prediction's own ssim, psnr, persistence_ssim, persistence_psnr [P] in
+        `errors`' order: two ndp_image_quality launches per pass, the predictions against `frames` through the target
+        rows, then `frames` through the start rows against the same targets.  Every other key holds the same bits.
+    The means are taken in fp64 over the fp32 per-prediction values; a PSNR mean skips no value (an infinite value gives an
+    infinite mean)."""
     _require_eval(fwd_model=fwd_model)
     if len(dataset) == 0 or int(batch_size) < 1:
         raise ValueError("evaluate needs a non-empty dataset and batch_size >= 1 (dataset: %d trajectories, batch_size %r)"
@@ -212,6 +240,8 @@ def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=
     jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
     errs, bases = [[] for _ in range(H)], [[] for _ in range(H)]     # per step, for the means
     all_err, all_base, index = [], [], []                             # in the order computed: batch, h, trajectory, start
+    quals = {k: [[] for _ in range(H)] for k in QUALITY_KEYS} if quality else {}
+    all_qual = {k: [] for k in quals}
     strips = {"start": [], "targets": [], "predictions": []}
     maps, kept, first_traj = {}, 0, 0
     full = T - H                                                      # starts per trajectory that live for all H steps
@@ -234,6 +264,10 @@ def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=
             bases[h - 1].append(base_err)
             all_err.append(err)
             all_base.append(base_err)
+            if quality:
+                for k, v in zip(QUALITY_KEYS, _quality(state, frames, frames, base_idx=start_rows, target_idx=target_rows)):
+                    quals[k][h - 1].append(v)
+                    all_qual[k].append(v)
             index.append(np.stack([np.repeat(np.arange(first_traj, first_traj + b), alive), np.tile(np.asarray(starts), b),
                                    np.full(b * alive, h)], axis=1))
             if want > 0:
@@ -258,6 +292,11 @@ def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=
         "index": torch.from_numpy(np.concatenate(index).astype(np.int32)).to(device),
     }
     result["one_step_mse"] = result["horizon_mse"][:1].clone()
+    if quality:
+        for k in QUALITY_KEYS:
+            name = k if k.startswith("persistence_") else "horizon_" + k
+            result[name] = torch.cat([IQ.mean(torch.cat(quals[k][h])) for h in range(H)])
+        result["quality"] = {k: torch.cat(v) for k, v in all_qual.items()}
     if keep > 0:
         result["strips"] = {k: torch.cat(v) for k, v in strips.items()}
     return result
@@ -316,6 +355,8 @@ def make_parser():
     parser.add_argument("--device", default="cuda")
     parser.add_argument("--save-dir", default=None, help="write the first --num-save prediction strips here as PNG")
     parser.add_argument("--num-save", type=int, default=8)
+    parser.add_argument("--quality", action="store_true",
+                        help="also print SSIM and PSNR per horizon, of the model and of the persistence baseline")
     return parser
 
 
@@ -325,12 +366,18 @@ def main(argv=None, log=print):
     model = load_module(args.model, device)
     dataset = make_dataset(args.data, seq_length=args.seq_length, raw_jpeg=args.raw_jpeg)
     keep = args.num_save if args.save_dir else 0
-    result = evaluate(model, dataset, horizon=args.horizon, batch_size=args.batch_size, device=device, keep=keep)
+    result = evaluate(model, dataset, horizon=args.horizon, batch_size=args.batch_size, device=device, keep=keep,
+                      quality=args.quality)
     one_step = float(result["one_step_mse"].item())
     log("val_pred_loss:", one_step, "trajectories:", len(dataset))
     rows = zip(result["horizon_mse"].tolist(), result["persistence_mse"].tolist(), result["counts"].tolist())
     for h, (model_mse, base_mse, count) in enumerate(rows, start=1):
         log("horizon %d: model_mse %.8g persistence_mse %.8g count %d" % (h, model_mse, base_mse, count))
+    if args.quality:
+        rows = zip(*(result[k].tolist() for k in ("horizon_ssim", "persistence_ssim", "horizon_psnr", "persistence_psnr")))
+        for h, (model_ssim, base_ssim, model_psnr, base_psnr) in enumerate(rows, start=1):
+            log("horizon %d: model_ssim %.8g persistence_ssim %.8g model_psnr %.8g persistence_psnr %.8g"
+                % (h, model_ssim, base_ssim, model_psnr, base_psnr))
     if args.save_dir:
         paths = save_strips(result["strips"], args.save_dir)
         log("wrote %d strips to %s" % (len(paths), args.save_dir))

@@ -13,6 +13,8 @@ What differs from the reference, on purpose:
     `epoch, "val_recon_loss:", value`, shows the first input and reconstruction through visdom as the reference does
     every 10 steps (train_autoencoder.py:96-103, win 1 / 2) and puts the modules back into training mode.  It draws no
     random number and changes nothing the trainer reads: the training losses are bit-identical with and without it.
+    `val_quality` (`--val-quality`, default off) also logs `epoch, "val_ssim:", value, "val_psnr:", value`, the mean SSIM
+    and PSNR of the reconstructions (`autoencoder_eval.evaluate(quality=True)`); the same holds.
 The whole modules are saved as models/encoder_{epoch}.pt / models/decoder_{epoch}.pt when epoch % 10 == 1
 (train_autoencoder.py:92-97), after the trainer's flat vectors are written back into them.
 
@@ -74,7 +76,7 @@ def build_models(device):
 
 def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS, lr=LR_RATE, betas=(0.5, 0.999),
           device="cuda", save_dir="models", report_freq=REPORT_FREQ, visdom=False, log=print, sync_batchnorm=True,
-          grad_exchange="bucketed", raw_jpeg=False, val_data=None, val_every=1):
+          grad_exchange="bucketed", raw_jpeg=False, val_data=None, val_every=1, val_quality=False):
     """The reference's loop; returns (encoder, decoder, per-step losses).  Under torch.distributed.run: data parallel
     (module docstring); `device` is then the local rank's GPU, every rank returns the same losses."""
     if grad_exchange not in ("bucketed", "single"):
@@ -127,7 +129,7 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
                 display = visualizer(port=8082)
             except Exception as e:  # pragma: no cover - visdom is optional
                 log("visdom unavailable (%s): no plots" % e)
-        losses, val_losses = [], []
+        losses, val_losses, val_quality_log = [], [], []
         step = 0
         warned = False
         for epoch in range(num_epochs):
@@ -164,8 +166,12 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
             if world > 1:
                 dp.assert_replicas_identical([trainer.params], grad_exchange, "end of epoch %d" % epoch)
             if val_dataset is not None and (epoch + 1) % int(val_every) == 0:
-                val_losses.append((epoch, validate(trainer, val_dataset, batch_size, device, display)))
+                quality = {} if val_quality else None
+                val_losses.append((epoch, validate(trainer, val_dataset, batch_size, device, display, quality=quality)))
                 log(epoch, "val_recon_loss:", val_losses[-1][1])
+                if val_quality:
+                    val_quality_log.append((epoch, quality["mean_ssim"], quality["mean_psnr"]))
+                    log(epoch, "val_ssim:", quality["mean_ssim"], "val_psnr:", quality["mean_psnr"])
             if epoch % 10 == 1 and rank == 0:
                 os.makedirs(save_dir, exist_ok=True)
                 trainer.sync_to_modules()
@@ -181,20 +187,24 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
             dist.destroy_process_group()
     train.last_trainer = trainer                                       # tests: the replica's flat vectors
     train.last_val_losses = val_losses                                 # [(epoch, val_recon_loss)]
+    train.last_val_quality = val_quality_log                           # [(epoch, val_ssim, val_psnr)] with val_quality
     return encoder, decoder, losses
 
 
-def validate(trainer, val_dataset, batch_size, device, display=None):
+def validate(trainer, val_dataset, batch_size, device, display=None, quality=None):
     """The mean reconstruction error of the trainer's current parameters over `val_dataset`, eval mode, on the kernels
     (autoencoder_eval.evaluate); with a visdom display also the first input and reconstruction (the reference's win 1 /
-    2).  The modules come back in training mode; the trainer's own vectors are only read."""
+    2).  The modules come back in training mode; the trainer's own vectors are only read.  quality: None, or a dict that
+    receives mean_ssim and mean_psnr of the reconstructions as host floats."""
     from . import autoencoder_eval
     encoder, decoder = trainer.sync_to_modules()
     encoder.eval()
     decoder.eval()
     try:
         result = autoencoder_eval.evaluate(encoder, decoder, val_dataset, batch_size=batch_size, device=device,
-                                           keep=1 if display is not None else 0)
+                                           keep=1 if display is not None else 0, quality=quality is not None)
+        if quality is not None:
+            quality.update(mean_ssim=float(result[-1]["mean_ssim"].item()), mean_psnr=float(result[-1]["mean_psnr"].item()))
         if display is not None:
             display.vis.image(result[2][0][0].permute(2, 0, 1).cpu().numpy(), win=1, opts={"caption": "state_cur_vis"})
             display.vis.image(result[2][1][0].permute(2, 0, 1).cpu().numpy(), win=2, opts={"caption": "state_cur_hat_vis"})
@@ -219,6 +229,8 @@ def make_parser():
                         help="held-out trajectories (as --data): their reconstruction error is logged after every "
                              "--val-every-th epoch")
     parser.add_argument("--val-every", type=int, default=1)
+    parser.add_argument("--val-quality", action="store_true",
+                        help="with --val-data: also log val_ssim and val_psnr, the mean SSIM and PSNR of the reconstructions")
     parser.add_argument("--visdom", action="store_true", help="plot the loss through visdom")
     parser.add_argument("--no-sync-batchnorm", dest="sync_batchnorm", action="store_false",
                         help="data parallel: BatchNorm statistics per rank instead of over all ranks' images")
@@ -232,7 +244,7 @@ def main(argv=None):
     args = make_parser().parse_args(argv)
     return train(args.data, batch_size=args.batch_size, num_epochs=args.epochs, lr=args.lr, save_dir=args.save_dir,
                  visdom=args.visdom, sync_batchnorm=args.sync_batchnorm, grad_exchange=args.grad_exchange,
-                 raw_jpeg=args.raw_jpeg, val_data=args.val_data, val_every=args.val_every)
+                 raw_jpeg=args.raw_jpeg, val_data=args.val_data, val_every=args.val_every, val_quality=args.val_quality)
 
 
 if __name__ == "__main__":

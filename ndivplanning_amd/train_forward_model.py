@@ -23,6 +23,8 @@ What differs from the reference, on purpose:
     eval mode (the running statistics are read, never moved; the cross-rank BatchNorm hook belongs to training-mode
     calls and is not invoked), it issues no collective -- the other ranks simply meet rank 0 at the next epoch's first
     all-reduce -- and the module is back in training mode afterwards.  Without `val_data_path` nothing changes.
+    `training.forward.val_quality` (default off) also logs `val_ssim` and `val_psnr` (`forward_model_eval.evaluate(
+    quality=True)`), with their persistence values; the same argument holds, training stays bit-identical.
 The whole module is saved every `epochs_per_stage` epochs as the reference does (train_forward_model.py:151-163), after
 the trainer's flat vectors are written back into it."""
 import importlib
@@ -144,6 +146,7 @@ def train(config):
     val_path, val_every, val_horizon = _optional(f, "val_data_path", None), int(_optional(f, "val_every", 1)), int(_optional(f, "val_horizon", 1))
     if val_path is not None and (val_every < 1 or val_horizon < 1):
         raise ValueError("training.forward.val_every and val_horizon must be >= 1, got %r and %r" % (val_every, val_horizon))
+    val_quality = bool(_optional(f, "val_quality", False))
     val_dataset = make_val_dataset(config, val_path) if val_path is not None and rank == 0 else None
     val_history = []
 
@@ -179,7 +182,7 @@ def train(config):
             display.plot("loss", "train", "Forward Model Loss", epoch, avg_loss)
         logging.info("{}, {}: reconstruction loss per epoch: {}".format(epoch, step, avg_loss))
         if val_dataset is not None and (epoch + 1) % val_every == 0:
-            val_history.append((epoch, validate(trainer, val_dataset, val_horizon, local_batch)))
+            val_history.append((epoch, validate(trainer, val_dataset, val_horizon, local_batch, quality=val_quality)))
         if epoch % epochs_per_stage == epochs_per_stage - 1 and rank == 0:   # train_forward_model.py:151-163
             os.makedirs(config.forward_save_path, exist_ok=True)
             trainer.sync_to_module()
@@ -213,18 +216,23 @@ def make_val_dataset(config, path):
                        raw_jpeg=bool(_get(config, "raw_jpeg", False)))
 
 
-def validate(trainer, val_dataset, horizon, batch_size):
+def validate(trainer, val_dataset, horizon, batch_size, quality=False):
     """The prediction error of the trainer's current parameters over `val_dataset`, in eval mode on the kernels
     (forward_model_eval.evaluate), logged; returns the means as host lists.  The trainer's flat vectors are the source of
     truth: they are written into the module first and nothing is read back, no random number is drawn, no collective
     is issued (rank 0 calls this alone), and eval mode neither moves the running statistics nor invokes the cross-rank
-    BatchNorm hook, which belongs to training-mode calls.  The module returns to training mode."""
+    BatchNorm hook, which belongs to training-mode calls.  The module returns to training mode.  quality: also SSIM and
+    PSNR per horizon (horizon_ssim, horizon_psnr, persistence_ssim, persistence_psnr), logged as val_ssim / val_psnr."""
     from . import forward_model_eval
     model = trainer.sync_to_module()
     model.eval()
     try:
-        result = forward_model_eval.evaluate(model, val_dataset, horizon=horizon, batch_size=batch_size, device=trainer.device)
-        means = {k: result[k].tolist() for k in ("one_step_mse", "horizon_mse", "persistence_mse", "counts")}
+        result = forward_model_eval.evaluate(model, val_dataset, horizon=horizon, batch_size=batch_size, device=trainer.device,
+                                             quality=quality)
+        keys = ("one_step_mse", "horizon_mse", "persistence_mse", "counts")
+        if quality:
+            keys += ("horizon_ssim", "horizon_psnr", "persistence_ssim", "persistence_psnr")
+        means = {k: result[k].tolist() for k in keys}
     finally:
         model.train()
         model.invalidate_cache()                                       # the eval pass's scratch goes back to the allocator
@@ -232,6 +240,11 @@ def validate(trainer, val_dataset, horizon, batch_size):
     for h in range(1, len(means["horizon_mse"])):
         logging.info("val horizon {}: model_mse {} persistence_mse {} count {}".format(
             h + 1, means["horizon_mse"][h], means["persistence_mse"][h], means["counts"][h]))
+    if quality:
+        for h in range(len(means["horizon_ssim"])):
+            logging.info("val horizon {}: val_ssim: {} val_psnr: {} persistence_ssim {} persistence_psnr {}".format(
+                h + 1, means["horizon_ssim"][h], means["horizon_psnr"][h], means["persistence_ssim"][h],
+                means["persistence_psnr"][h]))
     return means
 
 
