@@ -707,6 +707,36 @@ int ndp_resize_build_tables(int64_t height, int64_t width, void *tables_host, in
 int ndp_resize_lanczos_u8(const uint8_t *frames_hwc, int64_t n_images, int64_t height, int64_t width, const void *tables,
                           int64_t table_bytes, int rows_per_band, uint8_t *out_hwc, float *images, void *stream);
 
+/* -------------------------------------------------------- trajectory store ---
+ * A directory of trajectory bundles (bundle.py) kept in device memory, and the assembly of a batch
+ * from it (trajectory_store.py): B trajectory indices and a window of seq_length steps from seq_start become the packed
+ * JPEG streams that ndp_jpeg_decode_u8 takes plus the matching rows of the float tables.
+ *   blob           device bytes of all streams back to back, 4-byte aligned; blob_bytes is the size of the allocation:
+ *                  nothing is read at or past blob + blob_bytes, or before blob
+ *   frame_offsets  [n_traj * steps + 1] device int64, non-decreasing within 0..blob_bytes: frame t of trajectory i is
+ *                  blob[frame_offsets[i * steps + t] .. frame_offsets[i * steps + t + 1])
+ *   states / actions / goal   [n_traj][steps][25] / [n_traj][steps][4] / [n_traj][3] device floats
+ *   indices        [batch] device int64.  An index outside 0..n_traj-1 gives that trajectory zero-length streams and all-zero
+ *                  rows, sets NDP_STORE_BAD_INDEX in *status and causes no access outside the tables.  Duplicates are fine.
+ *   out_buffer     device bytes, 16-byte aligned, `capacity` long (batch * seq_length * the longest stream always fits).
+ *                  Stream s = b * seq_length + t of the batch is out_buffer[out_offsets[s] .. out_offsets[s+1]),
+ *                  out_offsets[0] = 0: the bytes and the offsets that packing the same streams in the same order on the
+ *                  host gives.  Nothing is written at or past out_offsets[batch * seq_length], nor at or past `capacity`
+ *                  (a batch that does not fit sets NDP_STORE_CAPACITY; out_offsets are then still the full ones).
+ *   out_offsets    [batch * seq_length + 1] device int64
+ *   out_states / out_actions / out_goal   [batch][seq_length][25] / [batch][seq_length][4] / [batch][3] device floats, the
+ *                  tables' bits
+ *   status         one device int32, written by every call: 0 or an OR of NDP_STORE_*
+ * n_traj * steps and batch * seq_length are at most 2^22; seq_start + seq_length <= steps.  Two launches, no host
+ * synchronisation, no allocation, no atomics: two calls give the same bytes. */
+#define NDP_STORE_BAD_INDEX 1
+#define NDP_STORE_CAPACITY  2
+int ndp_store_gather(const uint8_t *blob, int64_t blob_bytes, const int64_t *frame_offsets, const float *states,
+                     const float *actions, const float *goal, int64_t n_traj, int steps, const int64_t *indices,
+                     int64_t batch, int seq_start, int seq_length, uint8_t *out_buffer, int64_t capacity,
+                     int64_t *out_offsets, float *out_states, float *out_actions, float *out_goal, int32_t *status,
+                     void *stream);
+
 /* ------------------------------------------------------------ measurement ---
  * Per-kernel timing for bench.py: while enabled (per host thread) every kernel
  * this library launches is bracketed by hipEvents recorded on the stream it is

@@ -169,6 +169,8 @@ SIGNATURES = {
     "ndp_resize_build_tables": (c_int, [c_int64, c_int64, c_void_p, c_int64]),
     "ndp_resize_lanczos_u8": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p,
                                       c_void_p]),
+    "ndp_store_gather": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64,
+                                 c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ndp_timing_enable": (c_int, [c_int]),
     "ndp_timing_collect": (c_int, [ctypes.c_char_p, c_int, POINTER(c_float), POINTER(c_int32), c_int]),
 }

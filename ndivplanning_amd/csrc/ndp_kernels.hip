@@ -1880,3 +1880,4 @@ __global__ __launch_bounds__(kThreads) void k_philox(float* out, int64_t n, uint
 #include "ndp_jpeg.inc"
 #include "ndp_jpeg_enc.inc"
 #include "ndp_resize.inc"
+#include "ndp_store.inc"

@@ -1,6 +1,6 @@
 """Drop-in for the reference's `generate_trajectories.py`: roll a HER actor out in a live environment and store the
 trajectories (JPEG frames, states, actions, goal) as HDF5 bundles -- the data every training and evaluation script here
-reads.  Same `process_inputs`, `render`, `generate_trajectory(env, actor_network, args)` -> (image_frames: list of T
+reads -- or, with `--bundle-format ndpt`, as the project's own bundles (ndivplanning_amd/bundle.py; no h5py).  Same `process_inputs`, `render`, `generate_trajectory(env, actor_network, args)` -> (image_frames: list of T
 bytes, states [T,25], actions [T,4], desired_goal) and CLI, including the `simplify_task` / `goal_inline` branch and the
 reference's order of np.random draws.
 
@@ -187,6 +187,9 @@ _FLAGS = (
     ("--image-shape", dict(nargs=2, type=int, default=IMAGE_SHAPE,
                            help="stored frame size; only 128 128 is supported (the reference's default is 500 500)")),
     ("--outdir", dict(default="data", type=dir_exists_write_privileges, help="existing, writable directory for the bundles")),
+    ("--bundle-format", dict(choices=("h5", "ndpt"), default="h5",
+                             help="h5: the reference's HDF5 bundles (needs h5py); ndpt: the project's own bundles "
+                                  "(ndivplanning_amd/bundle.py), trajectory_bundle_NNNNN.ndpt, no h5py")),
 )
 
 
@@ -218,12 +221,48 @@ def _make_environment(gym, name):
     return env, sizes
 
 
+def _bundle_format(argv):
+    """The value of --bundle-format, read ahead of the full parse: it decides whether h5py is imported at all."""
+    import sys
+    ahead = argparse.ArgumentParser(add_help=False)
+    ahead.add_argument("--bundle-format", choices=("h5", "ndpt"), default="h5")
+    return ahead.parse_known_args(sys.argv[1:] if argv is None else argv)[0].bundle_format
+
+
+def write_bundles(args, make_trajectory, open_h5=None):
+    """args.num_files bundles of args.num_trajectory_per_file trajectories each, from make_trajectory() -> (image_frames,
+    states, actions, goal).  A trajectory that fails is reported and left out; the bundle goes on.  open_h5: h5py.File
+    for --bundle-format h5; an ndpt bundle is collected and written by ndivplanning_amd.bundle.write_bundle (a bundle
+    none of whose trajectories succeeded is reported and not written)."""
+    def fill(number, write):
+        for ix in range(args.num_trajectory_per_file):
+            try:
+                write(ix, *make_trajectory())
+            except Exception as e:          # the reference skips a failed trajectory too
+                print("trajectory {:05d} of bundle {:05d} was not written: {}".format(ix, number, e))
+
+    for number in range(args.filename_start_idx, args.filename_start_idx + args.num_files):
+        stem = os.path.join(args.outdir, "trajectory_bundle_{:05d}".format(number))
+        if args.bundle_format == "ndpt":
+            from .bundle import SUFFIX, write_bundle
+            kept = []
+            fill(number, lambda ix, *item: kept.append(item))
+            if kept:
+                write_bundle(stem + SUFFIX, kept)
+            else:
+                print("bundle {:05d} was not written: no trajectory succeeded".format(number))
+        else:
+            with open_h5(stem + ".h5", "w") as bundle:
+                fill(number, lambda ix, *item: write_trajectory(bundle, ix, *item))
+
+
 def main(argv=None):
     """The reference's command line: args.num_files bundles of args.num_trajectory_per_file trajectories each.  A
     trajectory that fails is reported and left out; the bundle goes on."""
     global o_mean, o_std, g_mean, g_std
+    fmt = _bundle_format(argv)
     gym = _import("gym", "with the FetchPush-v1 MuJoCo environment")
-    h5py = _import("h5py", "to write the trajectory bundles")
+    h5py = _import("h5py", "to write the trajectory bundles") if fmt == "h5" else None
     her = _import("hindsight_experience_replay.rl_modules.models", "the HER actor network of the pretrained model")
     args = _parser().parse_args(argv)
     _check_image_shape(args)
@@ -232,13 +271,7 @@ def main(argv=None):
     policy = her.actor(sizes)
     policy.load_state_dict(weights)
     policy.eval()
-    for number in range(args.filename_start_idx, args.filename_start_idx + args.num_files):
-        with h5py.File(os.path.join(args.outdir, "trajectory_bundle_{:05d}.h5".format(number)), "w") as bundle:
-            for ix in range(args.num_trajectory_per_file):
-                try:
-                    write_trajectory(bundle, ix, *generate_trajectory(env, policy, args))
-                except Exception as e:          # the reference skips a failed trajectory too
-                    print("trajectory {:05d} of bundle {:05d} was not written: {}".format(ix, number, e))
+    write_bundles(args, lambda: generate_trajectory(env, policy, args), h5py.File if h5py is not None else None)
 
 
 if __name__ == "__main__":

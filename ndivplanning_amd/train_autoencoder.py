@@ -15,6 +15,9 @@ What differs from the reference, on purpose:
     random number and changes nothing the trainer reads: the training losses are bit-identical with and without it.
     `val_quality` (`--val-quality`, default off) also logs `epoch, "val_ssim:", value, "val_psnr:", value`, the mean SSIM
     and PSNR of the reconstructions (`autoencoder_eval.evaluate(quality=True)`); the same holds.
+  * `device_store` (`--device-store`, default off; needs a directory of .ndpt bundles, ndivplanning_amd/bundle.py) keeps
+    the whole directory in device memory and assembles every batch there (trajectory_store.py) instead of going through
+    a DataLoader: the same batches in the same order, decoded by the same JPEG decoder.
 The whole modules are saved as models/encoder_{epoch}.pt / models/decoder_{epoch}.pt when epoch % 10 == 1
 (train_autoencoder.py:92-97), after the trainer's flat vectors are written back into them.
 
@@ -54,7 +57,8 @@ def norm(image):
 
 
 def make_dataset(path, seed=1, raw_jpeg=False):
-    """synthetic:<N>:images|jpeg, or the HDF5 directory (raw_jpeg: its JPEG streams, decoded on the device)."""
+    """synthetic:<N>:images|jpeg, or the trajectory directory (HDF5 or .ndpt bundles; raw_jpeg: its JPEG streams, decoded
+    on the device)."""
     path = str(path)
     if path.startswith("synthetic:"):
         spec = path.split(":")
@@ -76,7 +80,7 @@ def build_models(device):
 
 def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS, lr=LR_RATE, betas=(0.5, 0.999),
           device="cuda", save_dir="models", report_freq=REPORT_FREQ, visdom=False, log=print, sync_batchnorm=True,
-          grad_exchange="bucketed", raw_jpeg=False, val_data=None, val_every=1, val_quality=False):
+          grad_exchange="bucketed", raw_jpeg=False, val_data=None, val_every=1, val_quality=False, device_store=False):
     """The reference's loop; returns (encoder, decoder, per-step losses).  Under torch.distributed.run: data parallel
     (module docstring); `device` is then the local rank's GPU, every rank returns the same losses."""
     if grad_exchange not in ("bucketed", "single"):
@@ -84,6 +88,9 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
     rank, world, local_rank = dp.env_world()
     if batch_size % world != 0:                                        # (before any process group or GPU is touched)
         raise ValueError("batch_size=%d trajectories must be a multiple of the %d ranks" % (batch_size, world))
+    if device_store:
+        from .trajectory_store import DeviceTrajectoryStore, StoreLoader, require_bundle_dir
+        store_dir = require_bundle_dir(data_path, "device_store")
     if val_data is not None and int(val_every) < 1:
         raise ValueError("val_every must be >= 1, got %r" % (val_every,))
     own_group = False
@@ -103,6 +110,12 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
     val_dataset = make_dataset(val_data, seed=2, raw_jpeg=raw_jpeg) if val_data is not None and rank == 0 else None
     # JPEG frames are decoded on the device, then normalised by ndp_eval_frames_u8; failures raise one batch later
     jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
+    if device_store:
+        # the directory's bundles stay in device memory and every batch is assembled there (trajectory_store.py): the same
+        # batches in the same order as the DataLoader's, this rank's rows only, decoded by the same decoder
+        loader = StoreLoader(DeviceTrajectoryStore(store_dir, device), batch_size, 0, dataset.seq_length, shuffle=True,
+                             rank=rank, world=world)
+        jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred")
     encoder, decoder = build_models(device)
     trainer, bucket_group = None, None
     try:
@@ -135,7 +148,7 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
         for epoch in range(num_epochs):
             for i, inputs in enumerate(loader):
                 images, _, _, _ = inputs
-                if world > 1:
+                if world > 1 and not device_store:                     # (a StoreLoader yields this rank's rows already)
                     if images.shape[0] != batch_size:                  # ragged final batch: skipped on every rank
                         if rank == 0 and not warned:
                             warnings.warn("train_autoencoder: a final batch of %d trajectories does not split over %d "
@@ -220,6 +233,9 @@ def make_parser():
     parser.add_argument("--data", default="128_128_data", help="trajectory directory, or synthetic:<N>:images|jpeg")
     parser.add_argument("--raw-jpeg", action="store_true",
                         help="read the directory's JPEG streams as they are and decode them on the GPU")
+    parser.add_argument("--device-store", action="store_true",
+                        help="keep the directory's .ndpt bundles in GPU memory and assemble every batch there "
+                             "(ndivplanning_amd/trajectory_store.py) instead of through a DataLoader")
     parser.add_argument("--batch-size", type=int, default=BATCH_SIZE,
                         help="trajectories per step (under torch.distributed.run: over all ranks)")
     parser.add_argument("--epochs", type=int, default=NUM_EPOCHS)
@@ -244,7 +260,7 @@ def main(argv=None):
     args = make_parser().parse_args(argv)
     return train(args.data, batch_size=args.batch_size, num_epochs=args.epochs, lr=args.lr, save_dir=args.save_dir,
                  visdom=args.visdom, sync_batchnorm=args.sync_batchnorm, grad_exchange=args.grad_exchange,
-                 raw_jpeg=args.raw_jpeg, val_data=args.val_data, val_every=args.val_every, val_quality=args.val_quality)
+                 raw_jpeg=args.raw_jpeg, val_data=args.val_data, val_every=args.val_every, val_quality=args.val_quality, device_store=args.device_store)
 
 
 if __name__ == "__main__":

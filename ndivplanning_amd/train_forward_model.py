@@ -87,6 +87,10 @@ def train(config):
     random_seed = int(config.random_seed)
     lr_rate, num_epochs, batch_size = float(f.learning_rate), int(f.num_epochs), int(f.batch_size)
     epochs_per_stage = int(f.epochs_per_stage)
+    device_store = bool(_optional(f, "device_store", False))
+    if device_store:                                                 # (before any GPU or process group is touched)
+        from .trajectory_store import DeviceTrajectoryStore, StoreLoader, require_bundle_dir
+        store_dir = require_bundle_dir(config.train_data_path, "training.forward.device_store")
     rank, world, local_rank = dp.env_world()
     if not torch.cuda.is_available():
         from . import _capi
@@ -116,6 +120,12 @@ def train(config):
     loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True, **jpeg_frames.loader_kwargs(dataset))
     # JPEG frames (`synthetic:<N>:jpeg`, `raw_jpeg: true`) are decoded on the device; failures raise one batch later
     jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
+    if device_store:
+        # the directory's bundles stay in device memory and every batch is assembled there (trajectory_store.py): the same
+        # batches in the same order as the DataLoader's, this rank's rows only, decoded by the same decoder
+        loader = StoreLoader(DeviceTrajectoryStore(store_dir, device), batch_size, 0, int(config.trajectory_length),
+                             shuffle=True, rank=rank, world=world)
+        jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred")
 
     model = ForwardAutoencoder().to(device)                          # train_forward_model.py:67-70
     model.decoder.weight_init(mean=0.0, std=0.02)
@@ -156,7 +166,7 @@ def train(config):
         trainer.loss_sum.zero_()
         pairs = 0
         for images, _, actions, _ in loader:
-            if world > 1:
+            if world > 1 and not device_store:                       # (a StoreLoader yields this rank's rows already)
                 if images.shape[0] != batch_size:                    # ragged final batch: does not split evenly
                     continue
                 lo, hi = dp.shard_bounds(batch_size, rank, world)

@@ -2,12 +2,12 @@
 (utils/trajectory_loader.py:38-72): (images [T,3,H,W] f32 in [-1,1], states [T,25],
 actions [T,4], goal [3]).
 
-`PushDataset` reads the reference's HDF5 bundles (generate_trajectories.py:275-324) and
-needs h5py + PIL, which this image lacks: it raises a clear error at construction.  The
-input pipeline is a "next" row of the scope table; the training
-path is exercised with `SyntheticPushDataset`, which has the same output contract, plus a
-`codes` mode that yields per-frame 128-d codes instead of images (what a cache of the
-frozen encoder's outputs would hold)."""
+`PushDataset` reads a trajectory directory: the project's own `.ndpt` bundles (ndivplanning_amd/bundle.py: numpy for the
+container, PIL only to decode to pixels on the host, no h5py) or the reference's HDF5 bundles
+(generate_trajectories.py:275-324), which need h5py -- where that is missing it raises a clear error at construction
+(`python -m ndivplanning_amd.bundle convert` turns HDF5 directories into bundles on a machine that has it).
+`SyntheticPushDataset` has the same output contract without any stored data, plus a `codes` mode that yields per-frame
+128-d codes instead of images (what a cache of the frozen encoder's outputs would hold)."""
 import numpy as np
 import torch
 
@@ -85,9 +85,17 @@ def norm_frame(image):
 
 
 class PushDataset(torch.utils.data.Dataset):
-    """The reference's HDF5 + JPEG dataset (utils/trajectory_loader.py:17-72)."""
+    """The reference's HDF5 + JPEG dataset (utils/trajectory_loader.py:17-72).  A directory whose files all end in .ndpt
+    is read by `bundle.BundleDataset` instead (same contract, no h5py); a directory that mixes the two is an error."""
 
     def __init__(self, datadir, seq_start=0, seq_length=15, transform=None, raw_uint8=False, raw_jpeg=False):
+        from ..bundle import BundleDataset, is_bundle_dir
+        self._bundles = None
+        if is_bundle_dir(datadir):
+            self._bundles = BundleDataset(datadir, seq_start, seq_length, transform, raw_uint8, raw_jpeg)
+            for name, value in vars(self._bundles).items():      # mode (jpeg only), seq_length, files, total_seq_ct, ...
+                setattr(self, name, value)
+            return
         # raw_uint8: images as the decoder's bytes [T,H,W,3] instead of the normalised float tensor [T,3,H,W]; the
         # kernels apply the reference's normalisation (utils/hdf5_load.py:9-11) as they read (a quarter of the upload)
         # raw_jpeg: images as the stored JPEG streams, a list of T bytes objects, untouched (no PIL); batch them with
@@ -119,6 +127,8 @@ class PushDataset(torch.utils.data.Dataset):
     def __getitem__(self, index):
         import io
 
+        if self._bundles is not None:
+            return self._bundles[index]
         import h5py
         file_index = int(np.argmax(self.file_seq_cts > index))
         seq_index = index if file_index == 0 else index - int(self.file_seq_cts[file_index - 1])
