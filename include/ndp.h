@@ -429,6 +429,41 @@ int ndp_fm_apply_adam(float *params, const float *grad, float *exp_avg, float *e
 int ndp_fm_input_grads(const float *params, const float *d_out, int64_t n_images,
                        float *d_state_cur, float *d_actions, float *workspace, void *stream);
 
+/* ndp_fm_backward with the gradient of the TRAINING-mode pass with respect to its inputs as well: the same precondition
+ * (a training-mode ndp_fm_forward on this workspace came first), the same launches and bit for bit the same `grad`, plus
+ * d_state_cur [n,3,128,128] (or NULL) = d loss / d state_cur through the network alone -- the training-mode output is
+ * the residual, so there is no identity term; a caller that forms state_cur + residual adds it -- and d_actions [n,4]
+ * (or NULL).  One more launch on the caller's stream, beside the last weight gradient. */
+int ndp_fm_backward_inputs(const float *params, const float *d_resid, int64_t n_images, float *grad,
+                           float *d_state_cur, float *d_actions, float *workspace, void *stream);
+/* Multi-step rollout training: for a window of H + 1 frames x_0 .. x_H and H actions per trajectory,
+ *   s_0 = x_0;  r_k = model(s_k, a_k) in training mode;  s_{k+1} = s_k + r_k (not detached);
+ *   loss_k = mean((s_{k+1} - x_{k+1})^2);  L = (loss_0 + .. + loss_{H-1}) / H
+ * and the gradient of L through every path.  The caller keeps one workspace per pass (each needs ndp_fm_pack_params
+ * after every ndp_fm_apply_adam: the second weight order lives in the workspace's head), runs ndp_fm_forward(training)
+ * on s_k for k = 0 .. H-1 with ndp_fm_rollout_advance behind each, then for k = H-1 .. 0 ndp_fm_backward_inputs with
+ * d_resid = G_{k+1} and, for k >= 1, ndp_fm_rollout_chain; ndp_fm_grad_sum adds the H gradients.  With N = n*3*128*128:
+ *   ndp_fm_rollout_begin    state = x_0 as contiguous floats.  frames: image i at frames + i * image_stride ELEMENTS
+ *                           (floats [3][128][128], or with frames_u8 != 0 bytes [128][128][3], normalised as
+ *                           ndp_encoder_forward_u8 describes: the floats the loader would upload, bit for bit)
+ *   ndp_fm_rollout_advance  state_next = state + resid;  local_next = (2 / (H N)) (state_next - target) = local_{k+1};
+ *                           step_losses[step] = loss_step;  loss[0] = (step == 0 ? 0 : loss[0]) + loss_step / steps;
+ *                           after the last step *loss_sum += loss[0] (NULL: not kept).  target: as `frames` above.
+ *                           workspace: that of pass `step` (its loss scratch holds the blocks' sums)
+ *   ndp_fm_rollout_chain    g = (local + g_next) + d_state_cur = G_k, elementwise over [n,3,128,128]; g may be `local`
+ *   ndp_fm_grad_sum         out = ((g_0 + g_1) + ..) + g_{count-1}, vector h at grads + h * stride, `floats` long
+ * Every sum is taken in one fixed order (squares in fp64, no float atomics): two runs give the same bits.  All launches
+ * go to `stream`. */
+int ndp_fm_rollout_begin(const void *frames, int frames_u8, int64_t image_stride, int64_t n_images,
+                         float *state, void *stream);
+int ndp_fm_rollout_advance(const float *state, const float *resid, const void *target, int target_u8,
+                           int64_t image_stride, int64_t n_images, int step, int steps,
+                           float *state_next, float *local_next, float *step_losses, float *loss,
+                           float *loss_sum, float *workspace, void *stream);
+int ndp_fm_rollout_chain(const float *local, const float *g_next, const float *d_state_cur,
+                         int64_t n_images, float *g, void *stream);
+int ndp_fm_grad_sum(const float *grads, int64_t stride, int count, int64_t floats, float *out, void *stream);
+
 /* ------------------------------------------------------- image autoencoder ---
  * models.image_autoencoder.Encoder + Decoder (image_autoencoder.py:14-87) and one iteration of their training loop
  * (train_autoencoder.py:79-90).  Additive to the forward-model family above, same conventions:

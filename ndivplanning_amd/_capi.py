@@ -124,6 +124,12 @@ SIGNATURES = {
     "ndp_fm_input_grads": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ndp_fm_apply_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                   c_void_p, c_void_p]),
+    "ndp_fm_backward_inputs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ndp_fm_rollout_begin": (c_int, [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p]),
+    "ndp_fm_rollout_advance": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ndp_fm_rollout_chain": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ndp_fm_grad_sum": (c_int, [c_void_p, c_int64, c_int, c_int64, c_void_p, c_void_p]),
     "ndp_ae_param_floats": (c_int64, []),
     "ndp_ae_stat_floats": (c_int64, []),
     "ndp_ae_workspace_floats": (c_int64, [c_int64]),

@@ -1308,11 +1308,13 @@ __global__ __launch_bounds__(kThreads) void k_fm_bn_eval_bwd_apply(FmEltArgs a) 
 // (needs oh and oh + 1), one thread per input pixel.  Row stride 68 floats (lds_ld): the ds_read_b128 of a wave's
 // neighbouring pixels spread over the banks.  The blocks behind the images' copy d_actions out of dz's action columns
 // (128..131, where k_fm_image_cols put the actions in z); nimg_rows == 0: only those.
+// IDENT = false: the training-mode output is the residual alone (ndp_fm_backward_inputs): no d_out term, d_out is not read.
 struct FmC1DgArgs {
   const float* draw1; const float* w; const float* d_out; float* d_cur; int64_t nimg_rows;   // nimg_rows = n * 64, or 0
   const float* dz; float* d_actions; int64_t nimg;                                           // d_actions null: no copy
 };
 constexpr int kFmC1LD = 68;
+template <bool IDENT>
 __global__ __launch_bounds__(kThreads) void k_fm_conv1_dgrad(FmC1DgArgs a) {
   __shared__ __attribute__((aligned(16))) float D[2 * 64 * kFmC1LD];
   __shared__ __attribute__((aligned(16))) float Ws[27 * 64];               // [k = (kh * 3 + kw) * 3 + ci][co]
@@ -1360,7 +1362,7 @@ __global__ __launch_bounds__(kThreads) void k_fm_conv1_dgrad(FmC1DgArgs a) {
   }
   const int64_t base = n * 3 * 16384 + (int64_t)(2 * oh + ir) * 128 + iw;
 #pragma unroll
-  for (int ci = 0; ci < 3; ++ci) a.d_cur[base + ci * 16384] = a.d_out[base + ci * 16384] + acc[ci];
+  for (int ci = 0; ci < 3; ++ci) a.d_cur[base + ci * 16384] = IDENT ? a.d_out[base + ci * 16384] + acc[ci] : acc[ci];
 }
 
 // a bias gradient that is a plain column sum (conv4, conv5, conv6): accumulator -> grad, one workgroup
@@ -1732,6 +1734,179 @@ __global__ __launch_bounds__(kThreads) void k_fm_loss_final(const float* partial
       bias_grad[threadIdx.x - 1] = (float)t;
     }
   }
+}
+
+// ------------------------------------------------------------------------------------------ rollout links
+// Training on a window of H + 1 frames (DESIGN 5n): pass k runs the network on the state s_k the passes before it
+// predicted, s_{k+1} = s_k + r_k is not detached, and the loss is the mean over the H steps of mean((s_{k+1} - x_{k+1})^2).
+// Between the passes -- ndp_fm_forward (training) and ndp_fm_backward_inputs, one workspace per pass -- run four small
+// elementwise kernels over the n x 3 x 128 x 128 values of a state, float NCHW, 16 bytes per access:
+//   begin    s_0 = x_0, gathered from the window (image stride `stride`: floats NCHW, or byte frames HWC normalised as
+//            u8_norm_table does -- the floats the loader would have uploaded, bit for bit)
+//   advance  s_{k+1} = s_k + r_k;  d = s_{k+1} - x_{k+1};  local_{k+1} = (2 / (H N)) d;  the block's sum of d^2
+//   final    loss_k = (sum of the blocks' sums) / N;  L = (k == 0 ? 0 : L) + loss_k / H;  after the last step loss_sum += L
+//   chain    G_k = (local_k + G_{k+1}) + dcur_k        -- what pass k - 1 receives as d loss / d residual
+// and, over the flat gradient, the sum of the passes' gradients in pass order:  grad = ((g_0 + g_1) + ...) + g_{H-1}.
+// Squares are taken and added in fp64 (the product of two floats is exact there: contraction cannot change a bit), a
+// thread's twelve in the order channel, pixel; a block's 256 in a fixed tree; the blocks' in a fixed order by one
+// workgroup.  No float atomics anywhere: two runs give the same bits.
+// A thread owns four neighbouring pixels of one image in all three channels: three 16-byte accesses per float array,
+// and the 12 bytes (one load) that hold exactly those pixels of a byte frame.
+// The arithmetic and the schedule are in ndp::fm_rollout, __host__ __device__: tests/fm_rollout_host_driver.hip runs
+// them on the CPU by the kernels' schedule under the sanitizers.
+namespace fm_rollout {
+constexpr int kPlane = 128 * 128, kValues = 3 * kPlane;
+constexpr int kQuads = kPlane / 4;                                        // pixel quads (threads) per image
+constexpr int kBlocksPerImage = kQuads / kThreads;                        // 16
+static_assert(kQuads % kThreads == 0, "a block never spans two images");
+
+struct LinkArgs {
+  const float* state; const float* resid;                                 // s_k, r_k: contiguous [n][3][128][128]
+  const void* target; int target_u8; int64_t stride;                      // x_{k+1} (begin: x_0): image i at target + i * stride elements
+  float* state_next; float* local_next;                                   // s_{k+1} (begin: s_0), local_{k+1}
+  double* partial; int64_t nquads; float scale;                           // [blocks]; n * kQuads; 2 / (H N) in fp32
+};
+
+// u8_norm_table's entry (utils/hdf5_load.py:9-11)
+__host__ __device__ inline float norm_u8(int b) { return ((float)b / 255.0f - 0.5f) * 2.0f; }
+__host__ __device__ inline int64_t link_blocks(int64_t n) { return n * kBlocksPerImage; }
+__host__ __device__ inline float loss_scale(int64_t n, int steps) { return (float)(2.0 / ((double)steps * (double)(n * kValues))); }
+
+// the 12 bytes that hold pixels pix .. pix + 3 of image img of a byte frame, loaded once per thread (4-byte aligned: pix % 4 == 0)
+struct QuadBytes { uint32_t w[3]; };
+__host__ __device__ inline QuadBytes target_bytes(const LinkArgs& a, int64_t img, int pix) {
+  QuadBytes q = {{0u, 0u, 0u}};
+  if (a.target_u8) {
+    typedef uint32_t word __attribute__((may_alias));
+    const word* pw = reinterpret_cast<const word*>(static_cast<const unsigned char*>(a.target) + img * a.stride + (int64_t)pix * 3);
+    q.w[0] = pw[0]; q.w[1] = pw[1]; q.w[2] = pw[2];
+  }
+  return q;
+}
+// the four target values of channel c at pixels pix .. pix + 3 of image img; lut: the 256 floats of norm_u8
+__host__ __device__ inline f32x4 target_quad(const LinkArgs& a, const QuadBytes& q, int64_t img, int pix, int c, const float* lut) {
+  if (!a.target_u8)
+    return *reinterpret_cast<const f32x4*>(static_cast<const float*>(a.target) + img * a.stride + (int64_t)c * kPlane + pix);
+  f32x4 x;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int b = e * 3 + c;                                               // byte of (pixel e, channel c)
+    x[e] = lut[(q.w[b >> 2] >> (8 * (b & 3))) & 255u];
+  }
+  return x;
+}
+// begin: thread q of the launch
+__host__ __device__ inline void begin_thread(const LinkArgs& a, int64_t q, const float* lut) {
+  const int64_t img = q / kQuads;
+  const int pix = (int)(q % kQuads) * 4;
+  const QuadBytes by = target_bytes(a, img, pix);
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+    *reinterpret_cast<f32x4*>(a.state_next + img * kValues + (int64_t)c * kPlane + pix) = target_quad(a, by, img, pix, c, lut);
+}
+// advance: thread q of the launch; returns its sum of squared errors
+__host__ __device__ inline double advance_thread(const LinkArgs& a, int64_t q, const float* lut) {
+  const int64_t img = q / kQuads;
+  const int pix = (int)(q % kQuads) * 4;
+  const QuadBytes by = target_bytes(a, img, pix);
+  double sq = 0.0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int64_t at = img * kValues + (int64_t)c * kPlane + pix;
+    const f32x4 s = *reinterpret_cast<const f32x4*>(a.state + at);
+    const f32x4 r = *reinterpret_cast<const f32x4*>(a.resid + at);
+    const f32x4 x = target_quad(a, by, img, pix, c, lut);
+    const f32x4 sn = s + r;
+    const f32x4 d = sn - x;
+    *reinterpret_cast<f32x4*>(a.state_next + at) = sn;
+    *reinterpret_cast<f32x4*>(a.local_next + at) = a.scale * d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sq += (double)d[e] * (double)d[e];
+  }
+  return sq;
+}
+// the block's tree over its threads' sums in red[kThreads]: step `w` (128, 64 .. 1) for thread t < w
+__host__ __device__ inline void tree_step(double* red, int w, int t) { red[t] += red[t + w]; }
+// final: thread t's share of the blocks' sums, then thread 0's sum of the shares
+__host__ __device__ inline double final_share(const double* partial, int64_t count, int t) {
+  double s = 0.0;
+  for (int64_t i = t; i < count; i += kThreads) s += partial[i];
+  return s;
+}
+__host__ __device__ inline void final_write(const double* red, int64_t values, int step, int steps, float* step_losses,
+                                            float* loss, float* loss_sum) {
+  double t = 0.0;
+  for (int i = 0; i < kThreads; ++i) t += red[i];
+  const double lk = t / (double)values;
+  step_losses[step] = (float)lk;
+  const float l = (step == 0 ? 0.f : *loss) + (float)(lk / (double)steps);
+  *loss = l;
+  if (step == steps - 1 && loss_sum != nullptr) *loss_sum += l;
+}
+// chain: float4 i
+__host__ __device__ inline void chain_quad(const float* local, const float* g_next, const float* d_cur, float* g, int64_t i) {
+  const f32x4 l = reinterpret_cast<const f32x4*>(local)[i];
+  const f32x4 u = reinterpret_cast<const f32x4*>(g_next)[i];
+  const f32x4 d = reinterpret_cast<const f32x4*>(d_cur)[i];
+  reinterpret_cast<f32x4*>(g)[i] = (l + u) + d;
+}
+// gradient sum: thread i of the launch -- float4 i of the vector, or (behind the float4s) one of the up to 3 last floats
+__host__ __device__ inline int64_t sum_threads(int64_t floats) { return floats / 4 + floats % 4; }
+__host__ __device__ inline void sum_thread(const float* grads, int64_t stride, int count, int64_t floats, float* out, int64_t i) {
+  const int64_t n4 = floats / 4;
+  if (i < n4) {
+    f32x4 s = reinterpret_cast<const f32x4*>(grads)[i];
+    for (int h = 1; h < count; ++h) s += reinterpret_cast<const f32x4*>(grads + (int64_t)h * stride)[i];
+    reinterpret_cast<f32x4*>(out)[i] = s;
+  } else {
+    const int64_t j = 4 * n4 + (i - n4);
+    float s = grads[j];
+    for (int h = 1; h < count; ++h) s += grads[(int64_t)h * stride + j];
+    out[j] = s;
+  }
+}
+}  // namespace fm_rollout
+
+__global__ __launch_bounds__(kThreads) void k_fm_rollout_begin(fm_rollout::LinkArgs a) {
+  __shared__ float lut[256];
+  if (a.target_u8) {
+    u8_norm_table(lut);
+    __syncthreads();
+  }
+  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (q < a.nquads) fm_rollout::begin_thread(a, q, lut);
+}
+__global__ __launch_bounds__(kThreads) void k_fm_rollout_advance(fm_rollout::LinkArgs a) {
+  __shared__ float lut[256];
+  __shared__ double red[kThreads];
+  if (a.target_u8) {
+    u8_norm_table(lut);
+    __syncthreads();
+  }
+  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  red[threadIdx.x] = q < a.nquads ? fm_rollout::advance_thread(a, q, lut) : 0.0;
+  __syncthreads();
+  for (int w = kThreads / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) fm_rollout::tree_step(red, w, threadIdx.x);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) a.partial[blockIdx.x] = red[0];
+}
+__global__ __launch_bounds__(kThreads) void k_fm_rollout_loss_final(const double* partial, int64_t count, int64_t values, int step,
+                                                                    int steps, float* step_losses, float* loss, float* loss_sum) {
+  __shared__ double red[kThreads];
+  red[threadIdx.x] = fm_rollout::final_share(partial, count, threadIdx.x);
+  __syncthreads();
+  if (threadIdx.x == 0) fm_rollout::final_write(red, values, step, steps, step_losses, loss, loss_sum);
+}
+__global__ __launch_bounds__(kThreads) void k_fm_rollout_chain(const float* local, const float* g_next, const float* d_cur, float* g,
+                                                               int64_t n4) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < n4) fm_rollout::chain_quad(local, g_next, d_cur, g, i);
+}
+__global__ __launch_bounds__(kThreads) void k_fm_grad_sum(const float* grads, int64_t stride, int count, int64_t floats, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i < fm_rollout::sum_threads(floats)) fm_rollout::sum_thread(grads, stride, count, floats, out, i);
 }
 
 // ------------------------------------------------------------------------------------------ P1 -> P2
@@ -2720,8 +2895,12 @@ static FmBucketEvents* fm_bucket_events(FmBucketEventSet& set, const FmNet& net)
   return be->ok ? be : nullptr;
 }
 
-// backward pass: from d loss / d (pre-tanh output) in y2 to every gradient in `grad` (flat, the parameters' layout)
-static int fm_backward(hipStream_t st, const float* params, int64_t n, float* grad, const FmWs& ws, bool cleared = false) {
+// backward pass: from d loss / d (pre-tanh output) in y2 to every gradient in `grad` (flat, the parameters' layout).
+// d_cur / d_actions (ndp_fm_backward_inputs, either may be null): the gradient with respect to the image through the
+// network alone and to the actions, one more launch on `st` behind the chain's last BatchNorm backward; `grad` and the
+// launches that produce it are the same with and without them.
+static int fm_backward(hipStream_t st, const float* params, int64_t n, float* grad, const FmWs& ws, bool cleared = false,
+                       float* d_cur = nullptr, float* d_actions = nullptr) {
   FmSide* side = fm_side();
   hipStream_t sw = side ? side->stream : st;                        // where the weight gradients go
   FmBucketEvents* buckets = fm_bucket_events(g_fm_buckets, kFmNet);
@@ -2873,6 +3052,18 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
   FM_TRY(fm_bn_bwd(st, 0, {t[FMT_RAW1], 64}, {t[FMT_CAT6] + 64, 128}, {t[FMT_DCAT6] + 64, 128}, n * 4096, P, grad, ws));
   fork();
   FM_TRY(fm_wgrad(sw, "k_fm_wgrad[conv1]", {t[FMT_RAW1], 64}, 64, 64, {t[FMT_COLS], 32}, 64, 1, 1, 0, 32, n, GW(0), ws, plan, true));   // (columns)
+  if (d_cur != nullptr || d_actions != nullptr) {
+    // RAW1 holds d loss / d raw1 since fm_bn_bwd(st, 0, ...): the data gradient of conv1 reads it on `st` while
+    // k_fm_wgrad[conv1] reads it on the side stream -- neither writes it; dz is complete since k_fm_dgrad[deconv1]
+    FmC1DgArgs c1;
+    memset(&c1, 0, sizeof(c1));
+    c1.dz = t[FMT_DZ]; c1.d_actions = d_actions; c1.nimg = n;
+    if (d_cur != nullptr) { c1.draw1 = t[FMT_RAW1]; c1.w = W1(0); c1.d_cur = d_cur; c1.nimg_rows = n * 64; }
+    const int64_t copy_blocks = d_actions != nullptr ? (n * 4 + kThreads - 1) / kThreads : 0;
+    KTimer kt("k_fm_conv1_dgrad", st);
+    hipLaunchKernelGGL(k_fm_conv1_dgrad<false>, dim3((unsigned)(c1.nimg_rows + copy_blocks)), dim3(kThreads), 0, st, c1);
+    FM_TRY(check_launch("k_fm_conv1_dgrad"));
+  }
   if (side) {
     hipEventRecord(side->join, side->stream);
     hipStreamWaitEvent(st, side->join, 0);
@@ -2958,7 +3149,7 @@ static int fm_input_grads(hipStream_t st, const float* params, const float* d_ou
   const int64_t copy_blocks = d_actions != nullptr ? (n * 4 + kThreads - 1) / kThreads : 0;
   if (c1.nimg_rows + copy_blocks > 0) {
     KTimer kt("k_fm_conv1_dgrad", st);
-    hipLaunchKernelGGL(k_fm_conv1_dgrad, dim3((unsigned)(c1.nimg_rows + copy_blocks)), dim3(kThreads), 0, st, c1);
+    hipLaunchKernelGGL(k_fm_conv1_dgrad<true>, dim3((unsigned)(c1.nimg_rows + copy_blocks)), dim3(kThreads), 0, st, c1);
     FM_TRY(check_launch("k_fm_conv1_dgrad"));
   }
   return NDP_OK;
@@ -3137,6 +3328,100 @@ int ndp_fm_backward(const float* params, const float* d_resid, int64_t n_images,
   int rc = fm_loss(st, d_resid, nullptr, false, n_images, 3, nullptr, nullptr, nullptr, grad, ws);
   if (rc) return rc;
   return fm_backward(st, params, n_images, grad, ws);
+}
+
+int ndp_fm_backward_inputs(const float* params, const float* d_resid, int64_t n_images, float* grad, float* d_state_cur,
+                           float* d_actions, float* workspace, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(params && d_resid && grad && workspace && n_images >= 1 && n_images <= 8192, "ndp_fm_backward_inputs: bad arguments");
+  NDP_CHECK_ARG(aligned16(params) && aligned16(d_resid) && aligned16(grad) && aligned16(workspace) &&
+                (!d_state_cur || aligned16(d_state_cur)), "ndp_fm_backward_inputs: buffers must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const FmWs ws = fm_ws(workspace, n_images);
+  fm_eval_forget(workspace);
+  int rc = fm_loss(st, d_resid, nullptr, false, n_images, 3, nullptr, nullptr, nullptr, grad, ws);
+  if (rc) return rc;
+  return fm_backward(st, params, n_images, grad, ws, false, d_state_cur, d_actions);
+}
+
+static int fm_rollout_link_args(ndp::fm_rollout::LinkArgs& a, const void* target, int target_u8, int64_t stride, int64_t n_images,
+                                const char* who) {
+  using namespace ndp;
+  NDP_CHECK_ARG(target && n_images >= 1 && n_images <= 8192, "%s: bad arguments", who);
+  NDP_CHECK_ARG(target_u8 ? (stride >= fm_rollout::kValues && stride % 4 == 0 && ((uintptr_t)target & 3) == 0)
+                          : (stride >= fm_rollout::kValues && stride % 4 == 0 && aligned16(target)),
+                "%s: frames must be 16-byte (bytes: 4-byte) aligned, their image stride a multiple of 4 and at least one image", who);
+  memset(&a, 0, sizeof(a));
+  a.target = target; a.target_u8 = target_u8 ? 1 : 0; a.stride = stride; a.nquads = n_images * fm_rollout::kQuads;
+  return NDP_OK;
+}
+
+int ndp_fm_rollout_begin(const void* frames, int frames_u8, int64_t image_stride, int64_t n_images, float* state, void* stream) {
+  using namespace ndp;
+  fm_rollout::LinkArgs a;
+  int rc = fm_rollout_link_args(a, frames, frames_u8, image_stride, n_images, "ndp_fm_rollout_begin");
+  if (rc) return rc;
+  NDP_CHECK_ARG(state && aligned16(state), "ndp_fm_rollout_begin: state must be a 16-byte aligned buffer");
+  a.state_next = state;
+  hipStream_t st = (hipStream_t)stream;
+  KTimer kt("k_fm_rollout_begin", st);
+  hipLaunchKernelGGL(k_fm_rollout_begin, dim3((unsigned)fm_rollout::link_blocks(n_images)), dim3(kThreads), 0, st, a);
+  return check_launch("k_fm_rollout_begin");
+}
+
+int ndp_fm_rollout_advance(const float* state, const float* resid, const void* target, int target_u8, int64_t image_stride,
+                           int64_t n_images, int step, int steps, float* state_next, float* local_next, float* step_losses,
+                           float* loss, float* loss_sum, float* workspace, void* stream) {
+  using namespace ndp;
+  fm_rollout::LinkArgs a;
+  int rc = fm_rollout_link_args(a, target, target_u8, image_stride, n_images, "ndp_fm_rollout_advance");
+  if (rc) return rc;
+  NDP_CHECK_ARG(state && resid && state_next && local_next && step_losses && loss && workspace, "ndp_fm_rollout_advance: null pointer");
+  NDP_CHECK_ARG(steps >= 1 && step >= 0 && step < steps, "ndp_fm_rollout_advance: step %d of %d", step, steps);
+  NDP_CHECK_ARG(aligned16(state) && aligned16(resid) && aligned16(state_next) && aligned16(local_next) && aligned16(workspace),
+                "ndp_fm_rollout_advance: buffers must be 16-byte aligned");
+  const FmWs ws = fm_ws(workspace, n_images);
+  a.state = state; a.resid = resid; a.state_next = state_next; a.local_next = local_next;
+  a.partial = reinterpret_cast<double*>(ws.loss_partial);              // n x 256 floats: room for the n x 16 sums
+  a.scale = fm_rollout::loss_scale(n_images, steps);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t blocks = fm_rollout::link_blocks(n_images);
+  {
+    KTimer kt("k_fm_rollout_advance", st);
+    hipLaunchKernelGGL(k_fm_rollout_advance, dim3((unsigned)blocks), dim3(kThreads), 0, st, a);
+  }
+  rc = check_launch("k_fm_rollout_advance");
+  if (rc) return rc;
+  KTimer kt("k_fm_rollout_loss_final", st);
+  hipLaunchKernelGGL(k_fm_rollout_loss_final, dim3(1), dim3(kThreads), 0, st, (const double*)a.partial, blocks,
+                     n_images * (int64_t)fm_rollout::kValues, step, steps, step_losses, loss, loss_sum);
+  return check_launch("k_fm_rollout_loss_final");
+}
+
+int ndp_fm_rollout_chain(const float* local, const float* g_next, const float* d_state_cur, int64_t n_images, float* g, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(local && g_next && d_state_cur && g && n_images >= 1 && n_images <= 8192, "ndp_fm_rollout_chain: bad arguments");
+  NDP_CHECK_ARG(aligned16(local) && aligned16(g_next) && aligned16(d_state_cur) && aligned16(g),
+                "ndp_fm_rollout_chain: buffers must be 16-byte aligned");
+  const int64_t n4 = n_images * fm_rollout::kValues / 4;
+  hipStream_t st = (hipStream_t)stream;
+  KTimer kt("k_fm_rollout_chain", st);
+  hipLaunchKernelGGL(k_fm_rollout_chain, dim3((unsigned)((n4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, local, g_next,
+                     d_state_cur, g, n4);
+  return check_launch("k_fm_rollout_chain");
+}
+
+int ndp_fm_grad_sum(const float* grads, int64_t stride, int count, int64_t floats, float* out, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(grads && out && count >= 1 && count <= 64 && floats >= 1 && floats <= ((int64_t)1 << 36), "ndp_fm_grad_sum: bad arguments");
+  NDP_CHECK_ARG(aligned16(grads) && aligned16(out) && stride % 4 == 0 && (count == 1 || stride >= floats),
+                "ndp_fm_grad_sum: vectors must be 16-byte aligned, `stride` floats apart (a multiple of 4, no overlap)");
+  const int64_t threads = fm_rollout::sum_threads(floats);
+  hipStream_t st = (hipStream_t)stream;
+  KTimer kt("k_fm_grad_sum", st);
+  hipLaunchKernelGGL(k_fm_grad_sum, dim3((unsigned)((threads + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, grads, stride, count,
+                     floats, out);
+  return check_launch("k_fm_grad_sum");
 }
 
 int ndp_fm_input_grads(const float* params, const float* d_out, int64_t n_images, float* d_state_cur, float* d_actions,

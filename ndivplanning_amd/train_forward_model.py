@@ -25,6 +25,10 @@ What differs from the reference, on purpose:
     all-reduce -- and the module is back in training mode afterwards.  Without `val_data_path` nothing changes.
     `training.forward.val_quality` (default off) also logs `val_ssim` and `val_psnr` (`forward_model_eval.evaluate(
     quality=True)`), with their persistence values; the same argument holds, training stays bit-identical.
+  * `training.forward.rollout_steps` (default 1: the loop above, bit for bit): with H > 1 the inner loop runs over the
+    windows of H + 1 frames, `ForwardModelTrainer.step_rollout` unrolls the model H steps on its own predictions and
+    takes one Adam step on the mean of the H step losses, differentiated through every path; `step` and the epoch's
+    average count windows.  One process only.
 The whole module is saved every `epochs_per_stage` epochs as the reference does (train_forward_model.py:151-163), after
 the trainer's flat vectors are written back into it."""
 import importlib
@@ -92,6 +96,18 @@ def train(config):
         from .trajectory_store import DeviceTrajectoryStore, StoreLoader, require_bundle_dir
         store_dir = require_bundle_dir(config.train_data_path, "training.forward.device_store")
     rank, world, local_rank = dp.env_world()
+    rollout_steps = _optional(f, "rollout_steps", 1)                  # (checked before any GPU or process group is touched)
+    if isinstance(rollout_steps, bool) or int(rollout_steps) != rollout_steps or int(rollout_steps) < 1:
+        raise ValueError("training.forward.rollout_steps must be an integer >= 1, got %r" % (rollout_steps,))
+    rollout_steps = int(rollout_steps)
+    trajectory_length = _optional(config, "trajectory_length", None)
+    if trajectory_length is not None and int(trajectory_length) < rollout_steps + 1:
+        raise ValueError("training.forward.rollout_steps=%d needs windows of %d frames, trajectory_length is %d"
+                         % (rollout_steps, rollout_steps + 1, int(trajectory_length)))
+    if rollout_steps > 1 and world > 1:
+        raise ValueError("training.forward.rollout_steps=%d with %d ranks: multi-step rollouts train on one process (the "
+                         "bucketed gradient exchange and the cross-rank BatchNorm statistics assume one pass per iteration)"
+                         % (rollout_steps, world))
     if not torch.cuda.is_available():
         from . import _capi
         raise _capi.NdpError("train_forward_model needs a ROCm GPU (gpu_id %r); there is no CPU path" % (config.gpu_id,))
@@ -117,6 +133,9 @@ def train(config):
     dataset = make_dataset(config)
     if getattr(dataset, "mode", "images") not in ("images", "frames_u8", "jpeg"):
         raise ValueError("the forward model trains on images: use `synthetic:<N>:images` or an HDF5 directory")
+    if dataset.seq_length < rollout_steps + 1:                       # (a config without trajectory_length)
+        raise ValueError("training.forward.rollout_steps=%d needs windows of %d frames, the trajectories have %d"
+                         % (rollout_steps, rollout_steps + 1, dataset.seq_length))
     loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True, **jpeg_frames.loader_kwargs(dataset))
     # JPEG frames (`synthetic:<N>:jpeg`, `raw_jpeg: true`) are decoded on the device; failures raise one batch later
     jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
@@ -150,7 +169,8 @@ def train(config):
     trainer = ForwardModelTrainer(model, batch=local_batch, lr=lr_rate, betas=(0.5, 0.999),
                                   sync_batchnorm_world=world if (world > 1 and sync_bn) else 1,
                                   reduce_fn=dp.mean_all_reduce(world) if world > 1 and exchange == "single" else None,
-                                  bucket_reduce=dp.BucketedMeanAllReduce(world) if world > 1 and exchange == "bucketed" else None)
+                                  bucket_reduce=dp.BucketedMeanAllReduce(world) if world > 1 and exchange == "bucketed" else None,
+                                  rollout_steps=rollout_steps)
 
     # held-out trajectories (optional): rank 0 alone reads and evaluates them
     val_path, val_every, val_horizon = _optional(f, "val_data_path", None), int(_optional(f, "val_every", 1)), int(_optional(f, "val_horizon", 1))
@@ -177,6 +197,14 @@ def train(config):
             if images.dtype != torch.uint8:                          # byte frames [B,T,128,128,3]: normalised by the kernels
                 images = images.float()
             actions = actions.to(device, non_blocking=True).float()
+            if rollout_steps > 1:
+                # windows of rollout_steps + 1 frames: the model is unrolled on its own predictions and trained through them
+                for image_num in range(dataset.seq_length - rollout_steps):
+                    trainer.step_rollout(images[:, image_num:image_num + rollout_steps + 1],
+                                         actions[:, image_num:image_num + rollout_steps])
+                    step += 1
+                    pairs += 1
+                continue
             for image_num in range(dataset.seq_length - 1):          # train_forward_model.py:98-112
                 trainer.step(images[:, image_num].contiguous(), images[:, image_num + 1].contiguous(),
                              actions[:, image_num].contiguous())
