@@ -1,20 +1,18 @@
 """Shared by the forward-model evaluation tests (tests/test_forward_model_eval.py, tests/test_fm_score_host.py,
 tests/test_gpu_forward_model_eval.py): the plain numpy restatement of ndp_fm_score's definition, the inputs that sit on
-the byte boundaries, the golden file's recipe replayed through the oracle, and the build and run of
-tests/fm_score_host_driver.hip.  The driver is an ordinary program: it is started as a child process, nothing is
-preloaded and nothing of it is loaded into Python."""
+the byte boundaries, the golden file's recipe replayed through the oracle, and the run of
+tests/host_drivers/fm_score.inc through tests/host_driver.py."""
 import importlib.util
 import os
-import subprocess
 
 import numpy as np
 import torch
 
-import jpeg_core_host as J
+import host_driver
+from quality_common import as_float_images, norm_table, ulps  # noqa: F401  (the tests reach them through this module)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCE = os.path.join(HERE, "fm_score_host_driver.hip")
 VALUES = 3 * 128 * 128
 F32 = np.float32
 
@@ -28,19 +26,6 @@ def recipe():
 
 
 # ------------------------------------------------------------------------------------------ the stated definition
-def norm_table():
-    """The 256-entry table of ndp_eval_frames_u8: ((float)i / 255 - 0.5) * 2 in fp32."""
-    return (np.arange(256, dtype=F32) / F32(255.0) - F32(0.5)) * F32(2.0)
-
-
-def as_float_images(frames):
-    """float32 [m,3,128,128] of float images (as they are) or byte frames [m,128,128,3] (through the table)."""
-    frames = np.asarray(frames)
-    if frames.dtype == np.uint8:
-        return np.ascontiguousarray(norm_table()[frames].transpose(0, 3, 1, 2))
-    return frames.astype(F32, copy=False)
-
-
 def want_bytes(pred):
     """uint8 [n,128,128,3]: trunc(((y + 1) / 2) * 255) in fp32, in that order, saturated to 0 / 255, NaN -> 0."""
     y = np.asarray(pred, F32)
@@ -67,12 +52,6 @@ def want_mse(a, a_idx, b, b_idx):
     return out
 
 
-def ulps(got, want64):
-    """|got - want| in units of the fp32 spacing at want (got float32, want float64)."""
-    want64 = np.asarray(want64, np.float64)
-    return np.abs(np.asarray(got, np.float64) - want64) / np.spacing(np.abs(want64).astype(F32)).astype(np.float64)
-
-
 def boundary_images(n, seed=0):
     """float32 [n,3,128,128] predictions for the byte test: image 0 plane 0 sits exactly on the byte boundaries 2k/255 - 1
     and one fp32 ulp either side of them, plane 1 runs beyond +-1 (both saturations), plane 2 holds NaN, +-inf and noise;
@@ -90,44 +69,24 @@ def boundary_images(n, seed=0):
 
 
 # ------------------------------------------------------------------------------------------ the host driver
-def build_driver(out_dir, sanitize=True):
-    exe = os.path.join(str(out_dir), "fm_score_host_driver")
-    cmd = [J._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + (J.SANITIZE if sanitize else [])
-    cmd += ["-Wno-unused-value", "-Wno-pass-failed", "-Wno-invalid-offsetof", "-Wno-dangling-else", SOURCE, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        if sanitize and J._RUNTIME_MISSING.search(res.stdout):
-            raise J.NoSanitizerRuntime(res.stdout[-2000:])
-        raise RuntimeError("hipcc failed:\n" + res.stdout[-4000:])
-    return exe
+def build_driver(out_dir=None, sanitize=True):
+    return host_driver.build(sanitize)
 
 
 def run_driver(exe, cases, work_dir, timeout=900):
     """cases: dicts with pred float32 [n,3,128,128], target / base (float32 NCHW or uint8 HWC; base may be None),
     target_idx / base_idx (int32 [n] or None), bytes (bool).  Asserts that the child exits 0 with no sanitizer report.
     Returns [(pred_err float32 [n], base_err float32 [n], bytes uint8 [n,128,128,3])]."""
-    src, dst = os.path.join(str(work_dir), "cases.bin"), os.path.join(str(work_dir), "report.bin")
-    with open(src, "wb") as f:
-        f.write(np.int32(len(cases)).tobytes())
-        for c in cases:
-            n, base = len(c["pred"]), c.get("base")
-            kind = lambda a: 0 if a is None else 2 if a.dtype == np.uint8 else 1       # noqa: E731
-            head = [n, len(c["target"]), 0 if base is None else len(base), kind(c["target"]), kind(base),
-                    c.get("target_idx") is not None, c.get("base_idx") is not None, bool(c.get("bytes"))]
-            f.write(np.array(head, np.int32).tobytes())
-            f.write(np.ascontiguousarray(c["pred"], F32).tobytes())
-            for a in (c["target"], base):
-                if a is not None:
-                    f.write(np.ascontiguousarray(a).tobytes())
-            for idx in (c.get("target_idx"), c.get("base_idx")):
-                if idx is not None:
-                    f.write(np.ascontiguousarray(idx, np.int32).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, src, dst], env=env, capture_output=True, text=True, timeout=timeout)
-    text = p.stdout + p.stderr
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    raw = np.fromfile(dst, np.uint8)
+    parts = [np.int32(len(cases)).tobytes()]
+    for c in cases:
+        n, base = len(c["pred"]), c.get("base")
+        kind = lambda a: 0 if a is None else 2 if a.dtype == np.uint8 else 1       # noqa: E731
+        head = [n, len(c["target"]), 0 if base is None else len(base), kind(c["target"]), kind(base),
+                c.get("target_idx") is not None, c.get("base_idx") is not None, bool(c.get("bytes"))]
+        parts += [np.array(head, np.int32).tobytes(), np.ascontiguousarray(c["pred"], F32).tobytes()]
+        parts += [np.ascontiguousarray(a).tobytes() for a in (c["target"], base) if a is not None]
+        parts += [np.ascontiguousarray(i, np.int32).tobytes() for i in (c.get("target_idx"), c.get("base_idx")) if i is not None]
+    raw = np.frombuffer(host_driver.run("fm_score", b"".join(parts), work_dir, timeout=timeout, exe=exe), np.uint8)
     out, pos = [], 0
     for c in cases:
         n = len(c["pred"])
@@ -137,8 +96,6 @@ def run_driver(exe, cases, work_dir, timeout=900):
         out.append((err, base_err, by))
         pos += 8 * n + n * VALUES
     assert pos == raw.size, (pos, raw.size)
-    os.remove(src)
-    os.remove(dst)
     return out
 
 

@@ -1,19 +1,17 @@
 """Shared by the generator evaluation tests (tests/test_gan_eval.py, tests/test_gan_score_host.py,
 tests/test_gpu_gan_eval.py): the plain numpy restatement of ndp_gan_score's definition (include/ndp.h), the same formulas
 in fp64 and in fp32 through torch on the CPU (the yardstick of the bounds), the cases, the comparison that both the host
-driver and the kernel must pass, and the build and run of tests/gan_score_host_driver.hip.  The driver is an ordinary
-program: it is started as a child process, nothing is preloaded and nothing of it is loaded into Python."""
+driver and the kernel must pass, and the run of tests/host_drivers/gan_score.inc through tests/host_driver.py."""
 import os
-import subprocess
 
 import numpy as np
 import torch
 
-import jpeg_core_host as J
+import host_driver
+from quality_common import ulps
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SOURCE = os.path.join(HERE, "gan_score_host_driver.hip")
 GOLDEN = os.path.join(HERE, "golden", "gan_eval_case.npz")
 F32 = np.float32
 OUTPUTS = ("sample_err", "mean_err", "best_err", "best_k", "best_curve", "spread", "ndiv", "d_fake_prob", "d_pick_k", "d_pick_err")
@@ -109,12 +107,6 @@ def torch_fp32(x, noise=None, logits=None):
     return out
 
 
-def ulps(got, want64):
-    """|got - want| in units of the fp32 spacing at want (got float32, want float64)."""
-    want64 = np.asarray(want64, np.float64)
-    return np.abs(np.asarray(got, np.float64) - want64) / np.spacing(np.abs(want64).astype(F32)).astype(np.float64)
-
-
 def tolerance(name, want64, want32, k):
     """The bound on |got - want64| for spread / ndiv / d_fake_prob: max(4 x the distance of the same formula in fp32
     through torch on the CPU, a floor) -- the floor is 4 ulp of the value (spread, d_fake_prob) or 8 K 2^-24 absolute
@@ -197,40 +189,23 @@ def cases():
 
 
 # ------------------------------------------------------------------------------------------ the host driver
-def build_driver(out_dir, sanitize=True):
-    exe = os.path.join(str(out_dir), "gan_score_host_driver")
-    cmd = [J._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + (J.SANITIZE if sanitize else [])
-    cmd += ["-Wno-unused-value", "-Wno-pass-failed", "-Wno-invalid-offsetof", "-Wno-dangling-else", SOURCE, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        if sanitize and J._RUNTIME_MISSING.search(res.stdout):
-            raise J.NoSanitizerRuntime(res.stdout[-2000:])
-        raise RuntimeError("hipcc failed:\n" + res.stdout[-4000:])
-    return exe
+def build_driver(out_dir=None, sanitize=True):
+    return host_driver.build(sanitize)
 
 
 def run_driver(exe, case_list, work_dir, timeout=600):
     """case_list: [(case, wanted outputs or None)].  Asserts that the child exits 0 with no sanitizer report.  Returns
     [{output: array}] with every output at its full size; one that was not wanted holds the sentinel -7."""
-    src, dst = os.path.join(str(work_dir), "cases.bin"), os.path.join(str(work_dir), "report.bin")
-    with open(src, "wb") as f:
-        f.write(np.int32(len(case_list)).tobytes())
-        for c, wanted in case_list:
-            n, k = c["x"].shape[:2]
-            wanted = available(c) if wanted is None else wanted
-            mask = sum(1 << i for i, o in enumerate(OUTPUTS) if o in wanted)
-            nz = c["noise"].shape[2] if c["noise"] is not None else 1
-            head = [n, k, nz, c["action"] is not None, c["noise"] is not None, c["logits"] is not None, mask]
-            f.write(np.array(head, np.int32).tobytes())
-            for a in (c["x"], c["action"], c["noise"], c["logits"]):
-                if a is not None:
-                    f.write(np.ascontiguousarray(a, F32).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, src, dst], env=env, capture_output=True, text=True, timeout=timeout)
-    text = p.stdout + p.stderr
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    raw = np.fromfile(dst, np.uint8)
+    parts = [np.int32(len(case_list)).tobytes()]
+    for c, wanted in case_list:
+        n, k = c["x"].shape[:2]
+        wanted = available(c) if wanted is None else wanted
+        mask = sum(1 << i for i, o in enumerate(OUTPUTS) if o in wanted)
+        nz = c["noise"].shape[2] if c["noise"] is not None else 1
+        head = [n, k, nz, c["action"] is not None, c["noise"] is not None, c["logits"] is not None, mask]
+        parts.append(np.array(head, np.int32).tobytes())
+        parts += [np.ascontiguousarray(a, F32).tobytes() for a in (c["x"], c["action"], c["noise"], c["logits"]) if a is not None]
+    raw = np.frombuffer(host_driver.run("gan_score", b"".join(parts), work_dir, timeout=timeout, exe=exe), np.uint8)
     results, pos = [], 0
     for c, _ in case_list:
         n, k = c["x"].shape[:2]
@@ -242,6 +217,4 @@ def run_driver(exe, case_list, work_dir, timeout=600):
             pos += size
         results.append(got)
     assert pos == raw.size, (pos, raw.size)
-    os.remove(src)
-    os.remove(dst)
     return results

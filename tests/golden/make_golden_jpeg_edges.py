@@ -4,7 +4,7 @@ decoder takes another path than on tests/golden/jpeg_case.npz.
 
 Every stream is written by PIL on libjpeg-turbo (asserted), 128x128, 4:2:0; some then have bytes edited by hand, and for
 those PIL must still decode the stream, to the bytes asserted here.  Each class's property is asserted with the report of
-the host driver of the decoder's core (tests/jpeg_host_driver.hip, built by tests/jpeg_core_host.py), so the coverage is
+the host driver of the decoder's core (tests/host_drivers/jpeg.inc, run by tests/jpeg_core_host.py), so the coverage is
 proven, not assumed.
 
 Stored (tests/golden/jpeg_edges.npz):

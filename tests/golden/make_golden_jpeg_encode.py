@@ -19,7 +19,7 @@ Stored (tests/golden/jpeg_encode_case.npz):
   env_index [4] int64                           the corpus rows that are tests/fake_push_env.py frames
                                                 (jpeg_enc_core_host.env_frames) resized by PIL (LANCZOS)
 
-The census comes from the encoder's host driver (tests/jpeg_enc_host_driver.hip, built without sanitizers here), and is
+The census comes from the encoder's host driver (tests/host_drivers/jpeg_enc.inc, built without sanitizers here), and is
 kept only because the driver's streams equal PIL's for every frame (asserted).  The two padding classes are found by a
 seeded search over corner-noise frames.  check_classes (tests/jpeg_enc_core_host.py) asserts that every class is present.
 

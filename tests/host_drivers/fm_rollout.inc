@@ -1,6 +1,6 @@
-// fm_rollout_host_driver.hip -- the rollout link kernels and the gradient sum (k_fm_rollout_begin, k_fm_rollout_advance,
+// fm_rollout.inc -- the rollout link kernels and the gradient sum (k_fm_rollout_begin, k_fm_rollout_advance,
 // k_fm_rollout_loss_final, k_fm_rollout_chain, k_fm_grad_sum; csrc/ndp_forward_model.inc) run on the CPU, for
-// tests/test_fm_rollout_host.py.  It includes the library's source as the library build does and calls the __host__
+// tests/test_fm_rollout_host.py.  main.hip includes it behind the library's source (see there); it calls the __host__
 // __device__ functions the kernels call (ndp::fm_rollout) by the kernels' schedule: workgroups of 256 threads, one
 // thread per four neighbouring pixels (begin, advance) or per float4 (chain, gradient sum), the block's fixed tree over
 // its threads' fp64 sums "in LDS", then the one workgroup of the final pass.  What the kernels do outside those
@@ -8,7 +8,7 @@
 // device's own form of those is seen only by the GPU tests (tests/test_gpu_forward_rollout.py).  It makes no HIP runtime
 // call and needs no GPU.
 //
-// Usage: fm_rollout_host_driver IN OUT
+// Usage: host_driver fm_rollout IN OUT
 //   IN   int32 cases, then per case 8 int32 (kind, n, steps, step, target_u8, stride, count, floats) and
 //        kind 0 begin         frames ((n - 1) * stride + 49,152 floats or bytes)
 //        kind 1 advance       state, resid (n x 49,152 floats each), target (as frames), loss, loss_sum (one float each)
@@ -18,29 +18,13 @@
 //        (the sentinel -7 where not written), loss, loss_sum;  2: g;  3: out [floats]
 // Every buffer -- inputs, outputs, each LDS array -- is an allocation of exactly its size, so a sanitizer sees any access
 // past it.
-#include "../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-namespace {
+namespace host::fm_rollout {
 
 using namespace ndp::fm_rollout;
 using ndp::kThreads;
 
 template <class T>
-struct Exact {
-  T* p;
-  size_t n;
-  explicit Exact(size_t count) : p(nullptr), n(count) {
-    if (posix_memalign(reinterpret_cast<void**>(&p), 16, count ? count * sizeof(T) : 16) != 0) abort();   // (16-byte accesses)
-  }
-  ~Exact() { free(p); }
-  Exact(const Exact&) = delete;
-  bool read(FILE* f) { return fread(p, sizeof(T), n, f) == n; }
-  bool write(FILE* f) const { return fwrite(p, sizeof(T), n, f) == n; }
-};
+using Exact = host::Exact<T, 16>;                                       // (16-byte accesses)
 
 struct Case {
   int32_t kind, n, steps, step, target_u8, stride, count, floats;
@@ -81,29 +65,19 @@ void run_advance(const LinkArgs& a, int64_t n, int step, int steps, float* step_
   final_write(red.p, n * (int64_t)kValues, step, steps, step_losses, loss, loss_sum);
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: %s IN OUT\n", argv[0]);
-    return 2;
-  }
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) {
-    fprintf(stderr, "cannot open %s or %s\n", argv[1], argv[2]);
-    return 2;
-  }
+int run(int argc, char** argv) {
+  FILE *in, *out;
+  if (!open_files(argc, argv, &in, &out)) return kBadInput;
   static_assert(kQuads == 4096 && kBlocksPerImage == 16 && kValues == 49152, "the schedule");
   int32_t cases = 0;
-  if (fread(&cases, 4, 1, in) != 1 || cases < 0) return 2;
+  if (!read_pod(in, &cases) || cases < 0) return kBadInput;
   for (int32_t ci = 0; ci < cases; ++ci) {
     Case c;
-    if (fread(&c, sizeof(c), 1, in) != 1) return 2;
-    if (c.kind < 0 || c.kind > 3 || c.n < 1) return 2;
+    if (!read_pod(in, &c)) return kBadInput;
+    if (c.kind < 0 || c.kind > 3 || c.n < 1) return kBadInput;
     const size_t values = (size_t)c.n * kValues;
     if (c.kind == 0 || c.kind == 1) {
-      if (c.stride < kValues || c.stride % 4 != 0) return 2;
+      if (c.stride < kValues || c.stride % 4 != 0) return kBadInput;
       const size_t frame_elems = (size_t)(c.n - 1) * c.stride + kValues;
       Exact<float> tf(c.target_u8 ? 0 : frame_elems);
       Exact<unsigned char> t8(c.target_u8 ? frame_elems : 0);
@@ -112,49 +86,49 @@ int main(int argc, char** argv) {
       a.target_u8 = c.target_u8; a.stride = c.stride; a.nquads = (int64_t)c.n * kQuads;
       a.target = c.target_u8 ? static_cast<const void*>(t8.p) : static_cast<const void*>(tf.p);
       if (c.kind == 0) {
-        if (!tf.read(in) || !t8.read(in)) return 2;
+        if (!tf.read(in) || !t8.read(in)) return kBadInput;
         Exact<float> state(values);
         a.state_next = state.p;
         run_begin(a, c.n);
-        if (!state.write(out)) return 2;
+        if (!state.write(out)) return kBadInput;
       } else {
-        if (c.steps < 1 || c.step < 0 || c.step >= c.steps) return 2;
+        if (c.steps < 1 || c.step < 0 || c.step >= c.steps) return kBadInput;
         Exact<float> state(values), resid(values), state_next(values), local_next(values), step_losses((size_t)c.steps);
         Exact<float> loss(1), loss_sum(1);
         Exact<double> partial((size_t)link_blocks(c.n));
-        if (!state.read(in) || !resid.read(in) || !tf.read(in) || !t8.read(in) || !loss.read(in) || !loss_sum.read(in)) return 2;
-        for (int i = 0; i < c.steps; ++i) step_losses.p[i] = -7.0f;
+        if (!state.read(in) || !resid.read(in) || !tf.read(in) || !t8.read(in) || !loss.read(in) || !loss_sum.read(in)) return kBadInput;
+        step_losses.fill(-7.0f);
         a.state = state.p; a.resid = resid.p; a.state_next = state_next.p; a.local_next = local_next.p; a.partial = partial.p;
         a.scale = loss_scale(c.n, c.steps);
         run_advance(a, c.n, c.step, c.steps, step_losses.p, loss.p, loss_sum.p);
         if (!state_next.write(out) || !local_next.write(out) || !partial.write(out) || !step_losses.write(out) ||
             !loss.write(out) || !loss_sum.write(out))
-          return 2;
+          return kBadInput;
       }
     } else if (c.kind == 2) {
       Exact<float> local(values), g_next(values), d_cur(values);
-      if (!local.read(in) || !g_next.read(in) || !d_cur.read(in)) return 2;
+      if (!local.read(in) || !g_next.read(in) || !d_cur.read(in)) return kBadInput;
       const int64_t n4 = (int64_t)values / 4;                           // k_fm_rollout_chain
       for (int64_t b = 0; b < (n4 + kThreads - 1) / kThreads; ++b)
         for (int t = 0; t < kThreads; ++t) {
           const int64_t i = b * kThreads + t;
           if (i < n4) chain_quad(local.p, g_next.p, d_cur.p, local.p, i);
         }
-      if (!local.write(out)) return 2;
+      if (!local.write(out)) return kBadInput;
     } else {
-      if (c.count < 1 || c.floats < 1 || c.stride % 4 != 0 || (c.count > 1 && c.stride < c.floats)) return 2;
+      if (c.count < 1 || c.floats < 1 || c.stride % 4 != 0 || (c.count > 1 && c.stride < c.floats)) return kBadInput;
       Exact<float> grads((size_t)(c.count - 1) * c.stride + c.floats), sum((size_t)c.floats);
-      if (!grads.read(in)) return 2;
+      if (!grads.read(in)) return kBadInput;
       const int64_t threads = sum_threads(c.floats);                    // k_fm_grad_sum
       for (int64_t b = 0; b < (threads + kThreads - 1) / kThreads; ++b)
         for (int t = 0; t < kThreads; ++t) {
           const int64_t i = b * kThreads + t;
           if (i < threads) sum_thread(grads.p, c.stride, c.count, c.floats, sum.p, i);
         }
-      if (!sum.write(out)) return 2;
+      if (!sum.write(out)) return kBadInput;
     }
   }
-  fclose(in);
-  if (fclose(out) != 0) return 2;
-  return 0;
+  return close_files(in, out);
 }
+
+}  // namespace host::fm_rollout

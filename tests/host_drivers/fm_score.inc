@@ -1,5 +1,5 @@
-// fm_score_host_driver.hip -- the forward-model scoring kernel (k_fm_score, csrc/ndp_eval.inc) run on the CPU, for
-// tests/test_fm_score_host.py.  It includes the library's source as the library build does and calls the __host__
+// fm_score.inc -- the forward-model scoring kernel (k_fm_score, csrc/ndp_eval.inc) run on the CPU, for
+// tests/test_fm_score_host.py.  main.hip includes it behind the library's source (see there); it calls the __host__
 // __device__ functions the kernel calls (fm_score::row_of, thread_elems, tile_byte, norm_u8, sq_diff, to_byte) by the
 // kernel's schedule: one "workgroup" of 768 threads per prediction, 16 tiles, per tile the staging of the HWC bytes "in
 // LDS", the threads' four elements, the byte tile written back, then the fixed 768 -> 512 -> 256 .. 1 tree over the
@@ -7,7 +7,7 @@
 // restated here and tested as a copy; a slip in the device's own form of those is seen only by the GPU tests
 // (tests/test_gpu_forward_model_eval.py).  It makes no HIP runtime call and needs no GPU.
 //
-// Usage: fm_score_host_driver IN OUT
+// Usage: host_driver fm_score IN OUT
 //   IN   int32 cases, then per case 8 int32 (n, n_target, n_base, target kind 1 floats / 2 bytes, base kind 0 none / 1 / 2,
 //        has target_idx, has base_idx, want bytes), pred n x 49,152 floats, the targets (n_target x 49,152 floats or
 //        bytes), the base frames, target_idx [n] int32 if present, base_idx [n] int32 if present
@@ -15,25 +15,9 @@
 //        (0xA5 where not wanted)
 // Every buffer -- inputs, outputs, index maps, each LDS array -- is an allocation of exactly its size, so a sanitizer sees
 // any access past it.
-#include "../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-namespace {
+namespace host::fm_score {
 
 using namespace ndp::fm_score;
-
-template <class T>
-struct Exact {
-  T* p;
-  size_t n;
-  explicit Exact(size_t count) : p(static_cast<T*>(malloc(count ? count * sizeof(T) : 1))), n(count) {}
-  ~Exact() { free(p); }
-  Exact(const Exact&) = delete;
-  bool read(FILE* f) { return fread(p, sizeof(T), n, f) == n; }
-};
 
 struct Case {
   int32_t n, n_target, n_base, tgt_kind, base_kind, has_tidx, has_bidx, want_bytes;
@@ -91,26 +75,16 @@ void score_image(const Case& c, int64_t img, const float* pred, const float* tgt
   }
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: %s IN OUT\n", argv[0]);
-    return 2;
-  }
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) {
-    fprintf(stderr, "cannot open %s or %s\n", argv[1], argv[2]);
-    return 2;
-  }
+int run(int argc, char** argv) {
+  FILE *in, *out;
+  if (!open_files(argc, argv, &in, &out)) return kBadInput;
   static_assert(kScoreThreads * 4 == kTileBytes && kTiles * kTilePixels == kPlane && kValues == 49152, "the schedule");
   int32_t cases = 0;
-  if (fread(&cases, 4, 1, in) != 1 || cases < 0) return 2;
+  if (!read_pod(in, &cases) || cases < 0) return kBadInput;
   for (int32_t ci = 0; ci < cases; ++ci) {
     Case c;
-    if (fread(&c, sizeof(c), 1, in) != 1) return 2;
-    if (c.n < 1 || c.n_target < 1 || (c.base_kind != 0 && c.n_base < 1)) return 2;
+    if (!read_pod(in, &c)) return kBadInput;
+    if (c.n < 1 || c.n_target < 1 || (c.base_kind != 0 && c.n_base < 1)) return kBadInput;
     const size_t n = (size_t)c.n;
     Exact<float> pred(n * kValues);
     Exact<float> tgt_f32(c.tgt_kind == 1 ? (size_t)c.n_target * kValues : 0);
@@ -120,20 +94,21 @@ int main(int argc, char** argv) {
     Exact<int32_t> tidx(c.has_tidx ? n : 0), bidx(c.has_bidx ? n : 0);
     if (!pred.read(in) || !tgt_f32.read(in) || !tgt_u8.read(in) || !base_f32.read(in) || !base_u8.read(in) ||
         !tidx.read(in) || !bidx.read(in))
-      return 2;
+      return kBadInput;
     Exact<float> pred_err(n), base_err(n);
     Exact<unsigned char> bytes(n * kValues);
-    for (size_t i = 0; i < n; ++i) pred_err.p[i] = base_err.p[i] = -7.0f;
-    memset(bytes.p, 0xA5, n * kValues);
+    pred_err.fill(-7.0f);
+    base_err.fill(-7.0f);
+    bytes.fill(0xA5);
     for (int64_t img = 0; img < c.n; ++img)
       score_image(c, img, pred.p, c.tgt_kind == 1 ? tgt_f32.p : nullptr, c.tgt_kind == 2 ? tgt_u8.p : nullptr,
                   c.has_tidx ? tidx.p : nullptr, c.base_kind == 1 ? base_f32.p : nullptr,
                   c.base_kind == 2 ? base_u8.p : nullptr, c.has_bidx ? bidx.p : nullptr, pred_err.p, base_err.p, bytes.p);
-    fwrite(pred_err.p, 4, n, out);
-    fwrite(base_err.p, 4, n, out);
-    fwrite(bytes.p, 1, n * kValues, out);
+    pred_err.write(out);
+    base_err.write(out);
+    bytes.write(out);
   }
-  fclose(in);
-  if (fclose(out) != 0) return 2;
-  return 0;
+  return close_files(in, out);
 }
+
+}  // namespace host::fm_score

@@ -1,5 +1,5 @@
-// gan_score_host_driver.hip -- the generator scoring kernel (k_gan_score, csrc/ndp_eval.inc) run on the CPU, for
-// tests/test_gan_score_host.py.  It includes the library's source as the library build does and calls the __host__
+// gan_score.inc -- the generator scoring kernel (k_gan_score, csrc/ndp_eval.inc) run on the CPU, for
+// tests/test_gan_score_host.py.  main.hip includes it behind the library's source (see there); it calls the __host__
 // __device__ functions the kernel calls (gan_score::block_threads, rows_per_block, lds_bytes, sample_error, add_squares,
 // distance, hinge, sigmoid, better_min, better_max) by the kernel's schedule: blocks of rows_per_block(K) rows, the
 // rows' samples, noise and logits staged "in LDS", pass 1 (e_k, the fp32 row sums, the fp64 distance sums), pass 2 (the
@@ -7,7 +7,7 @@
 // loops, the barriers' phases, the LDS carving -- is restated here and tested as a copy; a slip in the device's own form
 // of those is seen only by the GPU tests (tests/test_gpu_gan_eval.py).  It makes no HIP runtime call and needs no GPU.
 //
-// Usage: gan_score_host_driver IN OUT
+// Usage: host_driver gan_score IN OUT
 //   IN   int32 cases, then per case 7 int32 (n, K, nz, has action, has noise, has logits, output mask: bit o set = output
 //        o wanted, in the order of ndp_gan_score's arguments), action_hat n x K x 4 floats, action n x 4 floats if
 //        present, noise n x K x nz floats if present, logits n x K floats if present
@@ -16,27 +16,9 @@
 //        an output that was not wanted holds the sentinel -7
 // Every buffer -- inputs, outputs, each LDS array -- is an allocation of exactly its size, so a sanitizer sees any access
 // past it; an input or output that is absent is a null pointer.
-#include "../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-namespace {
+namespace host::gan_score {
 
 using namespace ndp::gan_score;
-
-template <class T>
-struct Exact {
-  T* p;
-  size_t n;
-  explicit Exact(size_t count) : p(count ? static_cast<T*>(malloc(count * sizeof(T))) : nullptr), n(count) {}
-  ~Exact() { free(p); }
-  Exact(const Exact&) = delete;
-  bool read(FILE* f) { return n == 0 || fread(p, sizeof(T), n, f) == n; }
-  void fill(T v) { for (size_t i = 0; i < n; ++i) p[i] = v; }
-  void write(FILE* f) const { fwrite(p, sizeof(T), n, f); }
-};
 
 // k_gan_score for the workgroup `block`
 void score_block(const ndp::GanScoreArgs& a, int64_t block) {
@@ -131,29 +113,19 @@ void score_block(const ndp::GanScoreArgs& a, int64_t block) {
   }
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: %s IN OUT\n", argv[0]);
-    return 2;
-  }
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) {
-    fprintf(stderr, "cannot open %s or %s\n", argv[1], argv[2]);
-    return 2;
-  }
+int run(int argc, char** argv) {
+  FILE *in, *out;
+  if (!open_files(argc, argv, &in, &out)) return kBadInput;
   int32_t cases = 0;
-  if (fread(&cases, 4, 1, in) != 1 || cases < 0) return 2;
+  if (!read_pod(in, &cases) || cases < 0) return kBadInput;
   for (int32_t ci = 0; ci < cases; ++ci) {
     int32_t h[7];
-    if (fread(h, sizeof(h), 1, in) != 1) return 2;
+    if (!read_pod(in, &h)) return kBadInput;
     const int n = h[0], k = h[1], nz = h[2], mask = h[6];
-    if (n < 1 || k < 1 || k > 256 || nz < 1 || nz > kMaxNoise) return 2;
+    if (n < 1 || k < 1 || k > 256 || nz < 1 || nz > kMaxNoise) return kBadInput;
     const size_t rows = (size_t)n, flat = rows * k;
     Exact<float> x(flat * kActionDim), action(h[3] ? rows * kActionDim : 0), noise(h[4] ? flat * nz : 0), logits(h[5] ? flat : 0);
-    if (!x.read(in) || !action.read(in) || !noise.read(in) || !logits.read(in)) return 2;
+    if (!x.read(in) || !action.read(in) || !noise.read(in) || !logits.read(in)) return kBadInput;
     auto want = [mask](int o) { return (mask >> o) & 1; };
     // exact-size outputs for the kernel (absent: null) and full-size, sentinel-filled ones for the report
     Exact<float> sample_err(want(0) ? flat : 0), mean_err(want(1) ? rows : 0), best_err(want(2) ? rows : 0);
@@ -181,7 +153,7 @@ int main(int argc, char** argv) {
     put_f(sample_err, flat); put_f(mean_err, rows); put_f(best_err, rows); put_i(best_k, rows); put_f(best_curve, flat);
     put_f(spread, rows); put_f(ndiv, rows); put_f(d_fake_prob, rows); put_i(d_pick_k, rows); put_f(d_pick_err, rows);
   }
-  fclose(in);
-  if (fclose(out) != 0) return 2;
-  return 0;
+  return close_files(in, out);
 }
+
+}  // namespace host::gan_score

@@ -1,5 +1,5 @@
-// image_quality_host_driver.hip -- the image-quality kernels (k_image_quality, k_image_quality_finish, csrc/ndp_eval.inc)
-// run on the CPU, for tests/test_image_quality_host.py.  It includes the library's source as the library build does and
+// image_quality.inc -- the image-quality kernels (k_image_quality, k_image_quality_finish, csrc/ndp_eval.inc)
+// run on the CPU, for tests/test_image_quality_host.py.  main.hip includes it behind the library's source (see there); it
 // calls the __host__ __device__ functions the kernels call (image_quality::tap, unit, product, filter, ssim_at, sq_diff,
 // bands, band_rows, h_item, ssim_slot, psnr_slot, ssim_of, psnr_of; fm_score::row_of, norm_u8) by the kernels' schedule:
 // one "workgroup" of 16 * rows threads per (pair, channel, band), the two operands' rows scaled "into LDS", the band's own
@@ -9,35 +9,18 @@
 // folds -- is restated here and tested as a copy; a slip in the device's own form of those is seen only by the GPU tests
 // (tests/test_gpu_image_quality.py).  It makes no HIP runtime call and needs no GPU.
 //
-// Usage: image_quality_host_driver IN OUT
+// Usage: host_driver image_quality IN OUT
 //   IN   int32 cases, then per case 8 int32 (n_pairs, n_a, n_b, a kind 1 floats / 2 bytes, b kind, index maps: bit 0
 //        a_idx, bit 1 b_idx, output rows per band, wanted: bit 0 ssim, bit 1 psnr), a (n_a x 49,152 floats or bytes), b,
 //        a_idx [n_pairs] int32 if present, b_idx [n_pairs] int32 if present
 //   OUT  per case ssim [n_pairs] floats, psnr [n_pairs] floats (the sentinel -7 where not wanted)
 // Every buffer -- inputs, outputs, index maps, the workspace, each LDS array -- is an allocation of exactly its size, so a
 // sanitizer sees any access past it.  Exit 3: the tap table is not the double computation rounded once.
-#include "../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-namespace {
+namespace host::image_quality {
 
 using namespace ndp::image_quality;
 using ndp::fm_score::norm_u8;
 using ndp::fm_score::row_of;
-
-template <class T>
-struct Exact {
-  T* p;
-  size_t n;
-  explicit Exact(size_t count) : p(static_cast<T*>(malloc(count ? count * sizeof(T) : 1))), n(count) {}
-  ~Exact() { free(p); }
-  Exact(const Exact&) = delete;
-  bool read(FILE* f) { return fread(p, sizeof(T), n, f) == n; }
-};
 
 struct Case {
   int32_t n_pairs, n_a, n_b, a_kind, b_kind, maps, rows, want;
@@ -159,50 +142,41 @@ bool taps_are_the_double_computation() {
   return true;
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: %s IN OUT\n", argv[0]);
-    return 2;
-  }
+int run(int argc, char** argv) {
   static_assert(kRowSums == 3 * 118 + 3 * 128 && kSsimRows <= 2 * kFinishThreads && kPsnrRows <= 2 * kFinishThreads &&
                     kSsimValues == 41772 && kValues == 49152, "the schedule");
   if (!taps_are_the_double_computation()) return 3;
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) {
-    fprintf(stderr, "cannot open %s or %s\n", argv[1], argv[2]);
-    return 2;
-  }
+  FILE *in, *out;
+  if (!open_files(argc, argv, &in, &out)) return kBadInput;
   int32_t cases = 0;
-  if (fread(&cases, 4, 1, in) != 1 || cases < 0) return 2;
+  if (!read_pod(in, &cases) || cases < 0) return kBadInput;
   for (int32_t ci = 0; ci < cases; ++ci) {
     Case k;
-    if (fread(&k, sizeof(k), 1, in) != 1) return 2;
-    if (k.n_pairs < 1 || k.n_a < 1 || k.n_b < 1 || k.rows < 1 || k.rows > kOut || !(k.want & 3)) return 2;
+    if (!read_pod(in, &k)) return kBadInput;
+    if (k.n_pairs < 1 || k.n_a < 1 || k.n_b < 1 || k.rows < 1 || k.rows > kOut || !(k.want & 3)) return kBadInput;
     const size_t n = (size_t)k.n_pairs;
     Exact<float> a_f32(k.a_kind == 1 ? (size_t)k.n_a * kValues : 0), b_f32(k.b_kind == 1 ? (size_t)k.n_b * kValues : 0);
     Exact<unsigned char> a_u8(k.a_kind == 2 ? (size_t)k.n_a * kValues : 0), b_u8(k.b_kind == 2 ? (size_t)k.n_b * kValues : 0);
     Exact<int32_t> a_idx(k.maps & 1 ? n : 0), b_idx(k.maps & 2 ? n : 0);
     if (!a_f32.read(in) || !a_u8.read(in) || !b_f32.read(in) || !b_u8.read(in) || !a_idx.read(in) || !b_idx.read(in))
-      return 2;
+      return kBadInput;
     const Operand a{k.a_kind == 1 ? a_f32.p : nullptr, k.a_kind == 2 ? a_u8.p : nullptr};
     const Operand b{k.b_kind == 1 ? b_f32.p : nullptr, k.b_kind == 2 ? b_u8.p : nullptr};
     const int32_t* ai = k.maps & 1 ? a_idx.p : nullptr;
     const int32_t* bi = k.maps & 2 ? b_idx.p : nullptr;
     Exact<double> sums(n * kRowSums);
     Exact<float> ssim(n), psnr(n);
-    for (size_t i = 0; i < n * kRowSums; ++i) sums.p[i] = -7.0;
-    for (size_t i = 0; i < n; ++i) ssim.p[i] = psnr.p[i] = -7.0f;
+    sums.fill(-7.0);
+    ssim.fill(-7.0f);
+    psnr.fill(-7.0f);
     const int nb = bands(k.rows);
     for (int64_t block = 0; block < (int64_t)n * 3 * nb; ++block)
       band_block(k, a, ai, b, bi, block / (3 * nb), (int)((block / nb) % 3), (int)(block % nb), sums.p);
     for (int64_t pair = 0; pair < k.n_pairs; ++pair) finish_block(k, ai, bi, pair, sums.p, ssim.p, psnr.p);
-    fwrite(ssim.p, 4, n, out);
-    fwrite(psnr.p, 4, n, out);
+    ssim.write(out);
+    psnr.write(out);
   }
-  fclose(in);
-  if (fclose(out) != 0) return 2;
-  return 0;
+  return close_files(in, out);
 }
+
+}  // namespace host::image_quality

@@ -1,5 +1,5 @@
-// jpeg_host_driver.hip -- the JPEG decoder's core (csrc/ndp_jpeg.inc) run on the CPU, for tests/test_jpeg_core_host.py
-// and tests/golden/make_golden_jpeg_edges.py.  It includes the library's source as the library build does and calls the
+// jpeg.inc -- the JPEG decoder's core (csrc/ndp_jpeg.inc) run on the CPU, for tests/test_jpeg_core_host.py
+// and tests/golden/make_golden_jpeg_edges.py.  main.hip includes it behind the library's source (see there); it calls the
 // __host__ __device__ functions the kernels call (parse_headers, derive_table, lut_entry, marker_at, stuffed_at, eoi_at,
 // chunk_bits, Lane, sync_chunk, write_chunk, idct_islow, ycc_pixel); it makes no HIP runtime call and needs no GPU.
 // What the kernels do outside those functions is restated here, not shared, and is tested as a copy: the round loop
@@ -8,7 +8,7 @@
 // (pixels).  A slip in the device's own form of those (a round cap, the flags hand-off, the int4 unpacking) is seen
 // only by the GPU tests, which compare with PIL (tests/test_gpu_jpeg_edges.py, tests/test_gpu_jpeg.py).
 //
-// Usage: jpeg_host_driver IN OUT [frames]
+// Usage: host_driver jpeg IN OUT [frames]
 //   IN   int32 n, then n x (int32 len, len bytes): the streams
 //   OUT  per stream kRecordInts int32 (see Record), then, with `frames`, the 128x128x3 bytes of the chunked decode and of
 //        the serial decode
@@ -17,14 +17,7 @@
 // per chunk, DC running sums per component).  Serial: one Lane from bit 0, 384 blocks one after the other.  Both then go
 // through idct_islow and ycc_pixel.  Each stream, its staged head, its unstuffed data and the part of them "in LDS" live
 // in allocations of exactly their own size, so a sanitizer sees any read past them.
-#include "../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-namespace {
+namespace host::jpeg {
 
 using namespace ndp::jpeg;
 
@@ -50,15 +43,6 @@ struct Tables {
   uint16_t lut[4 << kLook];
   int32_t maxc[4 * 18], voff[4 * 18];
   uint8_t hval[4 * 256];
-};
-
-// An exact-size copy: a read one byte past it is a sanitizer report.
-template <class T>
-struct Exact {
-  T* p;
-  explicit Exact(size_t n) : p(static_cast<T*>(malloc(n ? n * sizeof(T) : 1))) {}
-  ~Exact() { free(p); }
-  Exact(const Exact&) = delete;
 };
 
 // What k_jpeg_parse does for one frame.  Returns the status; on NDP_JPEG_OK the tables and the unstuffed data (padded
@@ -275,28 +259,18 @@ void decode(const uint8_t* s, int32_t len, Record* rec, uint8_t* chunked, uint8_
   rec->frames_equal = memcmp(chunked, serial, kFrame) == 0;
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: %s IN OUT [frames]\n", argv[0]);
-    return 2;
-  }
+int run(int argc, char** argv) {
+  FILE *in, *out;
+  if (!open_files(argc, argv, &in, &out)) return kBadInput;
   const bool with_frames = argc > 3 && strcmp(argv[3], "frames") == 0;
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) {
-    fprintf(stderr, "cannot open %s or %s\n", argv[1], argv[2]);
-    return 2;
-  }
   int32_t n = 0;
-  if (fread(&n, 4, 1, in) != 1 || n < 0) return 2;
+  if (!read_pod(in, &n) || n < 0) return kBadInput;
   std::vector<uint8_t> chunked(kFrame), serial(kFrame);
   for (int32_t i = 0; i < n; ++i) {
     int32_t len = 0;
-    if (fread(&len, 4, 1, in) != 1 || len < 0 || len >= (1 << 28)) return 2;
+    if (!read_pod(in, &len) || len < 0 || len >= (1 << 28)) return kBadInput;
     Exact<uint8_t> s((size_t)len);
-    if (len && fread(s.p, 1, (size_t)len, in) != (size_t)len) return 2;
+    if (!s.read(in)) return kBadInput;
     Record rec;
     decode(s.p, len, &rec, chunked.data(), serial.data());
     static_assert(kRecordInts == 12, "tests/test_jpeg_core_host.py reads 12 int32 per stream");
@@ -306,7 +280,7 @@ int main(int argc, char** argv) {
       fwrite(serial.data(), 1, kFrame, out);
     }
   }
-  fclose(in);
-  if (fclose(out) != 0) return 2;
-  return 0;
+  return close_files(in, out);
 }
+
+}  // namespace host::jpeg

@@ -1,5 +1,5 @@
-// jpeg_enc_host_driver.hip -- the JPEG encoder's core (csrc/ndp_jpeg_enc.inc) run on the CPU, for
-// tests/test_jpeg_encode_core_host.py.  It includes the library's source as the library build does and calls the
+// jpeg_enc.inc -- the JPEG encoder's core (csrc/ndp_jpeg_enc.inc) run on the CPU, for
+// tests/test_jpeg_encode_core_host.py.  main.hip includes it behind the library's source (see there); it calls the
 // __host__ __device__ functions the kernels call (block_coefs, dc_predecessor, encode_block with BitCounter and
 // BitWriter, pad_bits, stuff_chunk, entropy_byte) and reads the tables the kernels read (kT); it makes no HIP runtime
 // call and needs no GPU.  What k_jpeg_enc_dct and k_jpeg_enc_pack do outside those functions is restated here, not shared,
@@ -7,7 +7,7 @@
 // k_jpeg_enc_offsets (the scan of the frame lengths against the capacity, its tile carry) has no part here: only the GPU
 // tests cover it (tests/test_gpu_jpeg_encode.py: 1,025 frames, the capacity cuts, the retry).
 //
-// Usage: jpeg_enc_host_driver IN OUT
+// Usage: host_driver jpeg_enc IN OUT
 //   IN   int32 nf, nf x 49152 bytes (frames [128][128][3]), int32 nc, nc x 24576 int16 (coefficient sets [384][64]:
 //        blocks in scan order, zig-zag order, DC as values -- what k_jpeg_enc_dct leaves in the workspace)
 //   OUT  per item kRecordInts int32 (see Record), then the stream of the kernels' schedule (Record::len bytes)
@@ -15,14 +15,7 @@
 // bits ORed into words, padding, 0xFF counts per lane, scan, stuffed bytes).  Serial: one bit writer from bit 0, block
 // after block, stuffing as it goes (jchuff.c's emit_bits), with its own walk over the coefficients.  The bit buffer is
 // an allocation of exactly its own size, so a sanitizer sees any access past it.
-#include "../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-namespace {
+namespace host::jpeg_enc {
 
 using namespace ndp::jpegenc;
 
@@ -45,12 +38,7 @@ constexpr int kFrame = kSize * kSize * 3;
 constexpr int kCoefs = kBlocks * 64;
 
 template <class T>
-struct Exact {
-  T* p;
-  explicit Exact(size_t n) : p(static_cast<T*>(aligned_alloc(16, ((n ? n * sizeof(T) : 1) + 15) / 16 * 16))) {}
-  ~Exact() { free(p); }
-  Exact(const Exact&) = delete;
-};
+using Exact = host::Exact<T, 16>;
 
 // k_jpeg_enc_pack<true> for one frame's coefficients.
 void scheduled(const int16_t* coef, std::vector<uint8_t>* out, Record* rec) {
@@ -196,34 +184,24 @@ void encode(const int16_t* coef, FILE* out) {
   fwrite(a.data(), 1, a.size(), out);
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: %s IN OUT\n", argv[0]);
-    return 2;
-  }
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) {
-    fprintf(stderr, "cannot open %s or %s\n", argv[1], argv[2]);
-    return 2;
-  }
+int run(int argc, char** argv) {
+  FILE *in, *out;
+  if (!open_files(argc, argv, &in, &out)) return kBadInput;
   int32_t nf = 0, nc = 0;
-  if (fread(&nf, 4, 1, in) != 1 || nf < 0) return 2;
+  if (!read_pod(in, &nf) || nf < 0) return kBadInput;
   Exact<uint8_t> frame(kFrame);
   Exact<int16_t> coef(kCoefs);
   for (int32_t i = 0; i < nf; ++i) {
-    if (fread(frame.p, 1, kFrame, in) != (size_t)kFrame) return 2;
+    if (!frame.read(in)) return kBadInput;
     for (int g = 0; g < kBlocks; ++g) block_coefs(frame.p, g, coef.p + g * 64);      // k_jpeg_enc_dct
     encode(coef.p, out);
   }
-  if (fread(&nc, 4, 1, in) != 1 || nc < 0) return 2;
+  if (!read_pod(in, &nc) || nc < 0) return kBadInput;
   for (int32_t i = 0; i < nc; ++i) {
-    if (fread(coef.p, 2, kCoefs, in) != (size_t)kCoefs) return 2;
+    if (!coef.read(in)) return kBadInput;
     encode(coef.p, out);
   }
-  fclose(in);
-  if (fclose(out) != 0) return 2;
-  return 0;
+  return close_files(in, out);
 }
+
+}  // namespace host::jpeg_enc

@@ -1,5 +1,5 @@
-// resize_host_driver.hip -- the Lanczos resize (csrc/ndp_resize.inc) run on the CPU, for tests/test_resize_core_host.py.
-// It includes the library's source as the library build does and calls the __host__ __device__ functions the kernel
+// resize.inc -- the Lanczos resize (csrc/ndp_resize.inc) run on the CPU, for tests/test_resize_core_host.py.
+// main.hip includes it behind the library's source (see there); it calls the __host__ __device__ functions the kernel
 // calls (make_plan, build_tables, safe_bounds, band_rows, sample, finish) and the host functions of the launch
 // (choose_rb, tile_rows_for, lds_bytes); it makes no HIP runtime call and needs no GPU.  What k_resize_lanczos does
 // outside those functions is restated here and tested as a copy: the loop over a band's input rows, the placement of
@@ -7,20 +7,13 @@
 // those (the dword loads of a misaligned row, the four-bytes-per-thread vertical pass, the float output) is seen only
 // by the GPU tests (tests/test_gpu_resize.py).
 //
-// Usage: resize_host_driver IN OUT
+// Usage: host_driver resize IN OUT
 //   IN   int32 n, then n x (int32 H, int32 W, H*W*3 bytes of frame, 128*128*3 bytes expected)
 //   OUT  per case kRecordInts int32 (see Record), then the 128x128x3 bytes of the resize by the n = 1 schedule
 // Every frame is resized by every band split the launch can choose (n = 1 .. 64 images) that fits LDS.  The frame, every
 // raw input row "in LDS", every band's tile and the tables live in allocations of exactly their own size, so a sanitizer
 // sees any access past them.
-#include "../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-namespace {
+namespace host::resize {
 
 using namespace ndp::resize;
 
@@ -35,14 +28,6 @@ struct Record {
 };
 constexpr int kRecordInts = sizeof(Record) / 4;
 constexpr int kFrame = kOut * kRowBytes;
-
-template <class T>
-struct Exact {
-  T* p;
-  explicit Exact(size_t n) : p(static_cast<T*>(malloc(n ? n * sizeof(T) : 1))) {}
-  ~Exact() { free(p); }
-  Exact(const Exact&) = delete;
-};
 
 // k_resize_lanczos for one frame with bands of rb rows.  Returns false where a band needs more rows than the launch
 // would have allocated.
@@ -93,30 +78,20 @@ bool resize_frame(const uint8_t* frame, const Plan& p, const int32_t* tab, int r
   return true;
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: %s IN OUT\n", argv[0]);
-    return 2;
-  }
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) {
-    fprintf(stderr, "cannot open %s or %s\n", argv[1], argv[2]);
-    return 2;
-  }
+int run(int argc, char** argv) {
+  FILE *in, *out;
+  if (!open_files(argc, argv, &in, &out)) return kBadInput;
   int32_t n = 0;
-  if (fread(&n, 4, 1, in) != 1 || n < 0) return 2;
+  if (!read_pod(in, &n) || n < 0) return kBadInput;
   for (int32_t i = 0; i < n; ++i) {
     int32_t hw[2];
-    if (fread(hw, 4, 2, in) != 2) return 2;
+    if (!read_pod(in, &hw)) return kBadInput;
     Plan p;
-    if (!make_plan(hw[0], hw[1], &p)) return 2;
+    if (!make_plan(hw[0], hw[1], &p)) return kBadInput;
     if (ndp_resize_workspace_bytes(hw[0], hw[1]) != p.ints * 4) return 3;
     const size_t bytes = (size_t)p.h * p.w * 3;
     Exact<uint8_t> frame(bytes), want(kFrame), got(kFrame), first(kFrame);
-    if (fread(frame.p, 1, bytes, in) != bytes || fread(want.p, 1, kFrame, in) != (size_t)kFrame) return 2;
+    if (!frame.read(in) || !want.read(in)) return kBadInput;
     Exact<int32_t> tab((size_t)p.ints);
     Exact<double> scratch((size_t)(p.kx > p.ky ? p.kx : p.ky));
     const int64_t worst = build_tables(p, tab.p, scratch.p);
@@ -149,7 +124,7 @@ int main(int argc, char** argv) {
     fwrite(&rec, sizeof(rec), 1, out);
     fwrite(first.p, 1, kFrame, out);
   }
-  fclose(in);
-  if (fclose(out) != 0) return 2;
-  return 0;
+  return close_files(in, out);
 }
+
+}  // namespace host::resize

@@ -1,5 +1,5 @@
-// store_gather_host_driver.hip -- the trajectory store's batch gather (k_store_scan, k_store_copy, csrc/ndp_store.inc)
-// run on the CPU, for tests/test_store_gather_host.py.  It includes the library's source as the library build does and
+// store_gather.inc -- the trajectory store's batch gather (k_store_scan, k_store_copy, csrc/ndp_store.inc)
+// run on the CPU, for tests/test_store_gather_host.py.  main.hip includes it behind the library's source (see there); it
 // calls the __host__ __device__ functions the kernels call (store::scan_run_sum, any_bad_index, scan_run_write,
 // row_blocks, gather_row_word, copy_blocks, chunk_count, stream_of, copy_word) by the kernels' schedule: workgroup 0 of
 // k_store_scan with its 1024 threads' runs, the row workgroups' grid-stride loops, then k_store_copy's workgroups, each
@@ -8,35 +8,18 @@
 // copy; a slip in the device's own form of those is seen only by the GPU test (tests/test_gpu_trajectory_store.py).  It
 // makes no HIP runtime call and needs no GPU.
 //
-// Usage: store_gather_host_driver IN OUT
+// Usage: host_driver store_gather IN OUT
 //   IN   int64 N, T, blob bytes; frame offsets int64 [N*T+1]; states float [N*T*25]; actions float [N*T*4]; goal float
 //        [N*3]; the blob; int64 cases; per case int64 B, seq_start, seq_length, capacity, then indices int64 [B]
 //   OUT  per case: int64 status, int64 count of changed bytes in out_buffer[offsets[n] .. capacity), offsets int64 [n+1],
 //        states float [n*25], actions float [n*4], goal float [B*3], then the offsets[n] used bytes of the buffer
 // Every buffer is an allocation of exactly its size (the blob is NOT padded: the store does not pad it either), so a
 // sanitizer sees any access past it; the output buffer is filled with the canary 0xC5 before the run.
-#include "../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-
-namespace {
+namespace host::store_gather {
 
 using namespace ndp::store;
 
 constexpr uint8_t kCanary = 0xC5;
-
-template <class T>
-struct Exact {
-  T* p;
-  size_t n;
-  explicit Exact(size_t count) : p(count ? static_cast<T*>(malloc(count * sizeof(T))) : nullptr), n(count) {}
-  ~Exact() { free(p); }
-  Exact(const Exact&) = delete;
-  bool read(FILE* f) { return n == 0 || fread(p, sizeof(T), n, f) == n; }
-  void write(FILE* f, size_t count) const { if (count) fwrite(p, sizeof(T), count, f); }
-};
 
 void run_scan(const Args& a) {
   const int64_t n = n_streams(a);
@@ -73,41 +56,31 @@ void run_copy(const Args& a) {
   }
 }
 
-}  // namespace
-
-int main(int argc, char** argv) {
-  if (argc < 3) {
-    fprintf(stderr, "usage: %s IN OUT\n", argv[0]);
-    return 2;
-  }
-  FILE* in = fopen(argv[1], "rb");
-  FILE* out = fopen(argv[2], "wb");
-  if (!in || !out) {
-    fprintf(stderr, "cannot open %s or %s\n", argv[1], argv[2]);
-    return 2;
-  }
+int run(int argc, char** argv) {
+  FILE *in, *out;
+  if (!open_files(argc, argv, &in, &out)) return kBadInput;
   int64_t head[3];
-  if (fread(head, sizeof(head), 1, in) != 1) return 2;
+  if (!read_pod(in, &head)) return kBadInput;
   const int64_t N = head[0], T = head[1], blob_bytes = head[2];
-  if (N < 1 || T < 1 || blob_bytes < 0 || N * T > kMaxStreams) return 2;
+  if (N < 1 || T < 1 || blob_bytes < 0 || N * T > kMaxStreams) return kBadInput;
   const size_t frames = (size_t)(N * T);
   Exact<int64_t> frame_offsets(frames + 1);
   Exact<float> states(frames * kStateDim), actions(frames * kActionDim), goal((size_t)N * kGoalDim);
   Exact<uint8_t> blob((size_t)blob_bytes);
-  if (!frame_offsets.read(in) || !states.read(in) || !actions.read(in) || !goal.read(in) || !blob.read(in)) return 2;
+  if (!frame_offsets.read(in) || !states.read(in) || !actions.read(in) || !goal.read(in) || !blob.read(in)) return kBadInput;
   int64_t cases = 0;
-  if (fread(&cases, 8, 1, in) != 1 || cases < 0) return 2;
+  if (!read_pod(in, &cases) || cases < 0) return kBadInput;
   for (int64_t ci = 0; ci < cases; ++ci) {
     int64_t h[4];
-    if (fread(h, sizeof(h), 1, in) != 1) return 2;
+    if (!read_pod(in, &h)) return kBadInput;
     const int64_t B = h[0], seq_start = h[1], seq_length = h[2], capacity = h[3];
-    if (B < 1 || seq_start < 0 || seq_length < 1 || seq_start + seq_length > T || capacity < 0) return 2;
+    if (B < 1 || seq_start < 0 || seq_length < 1 || seq_start + seq_length > T || capacity < 0) return kBadInput;
     const size_t n = (size_t)(B * seq_length);
-    if ((int64_t)n > kMaxStreams) return 2;
+    if ((int64_t)n > kMaxStreams) return kBadInput;
     Exact<int64_t> indices((size_t)B), out_offsets(n + 1);
-    if (!indices.read(in)) return 2;
+    if (!indices.read(in)) return kBadInput;
     Exact<uint8_t> buffer((size_t)capacity);
-    if (capacity) memset(buffer.p, kCanary, (size_t)capacity);
+    buffer.fill(kCanary);
     Exact<float> out_states(n * kStateDim), out_actions(n * kActionDim), out_goal((size_t)B * kGoalDim);
     Exact<int32_t> status(1);
     Args a{blob.p, blob_bytes, frame_offsets.p, reinterpret_cast<const uint32_t*>(states.p),
@@ -122,13 +95,13 @@ int main(int argc, char** argv) {
     const int64_t st = status.p[0];
     fwrite(&st, 8, 1, out);
     fwrite(&changed, 8, 1, out);
-    out_offsets.write(out, n + 1);
-    out_states.write(out, out_states.n);
-    out_actions.write(out, out_actions.n);
-    out_goal.write(out, out_goal.n);
+    out_offsets.write(out);
+    out_states.write(out);
+    out_actions.write(out);
+    out_goal.write(out);
     buffer.write(out, (size_t)used);
   }
-  fclose(in);
-  if (fclose(out) != 0) return 2;
-  return 0;
+  return close_files(in, out);
 }
+
+}  // namespace host::store_gather

@@ -1,17 +1,11 @@
-"""Build and run tests/jpeg_host_driver.hip, the JPEG decoder's core on the CPU (used by tests/test_jpeg_core_host.py and
-tests/golden/make_golden_jpeg_edges.py).  The driver is an ordinary program: it is started as a child process, nothing is
-preloaded and nothing of it is loaded into Python."""
+"""Run tests/host_drivers/jpeg.inc, the JPEG decoder's core on the CPU, through tests/host_driver.py (used by
+tests/test_jpeg_core_host.py and tests/golden/make_golden_jpeg_edges.py)."""
 import hashlib
-import os
-import re
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(HERE, "jpeg_host_driver.hip")
-# the sanitizers go on the host half only: the device half is what ships and never runs here
-SANITIZE = ["-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined"]
+import host_driver
+
 FIELDS = ("status", "status_serial", "frames_equal", "rounds", "nchunks", "ncompact", "max_dc_cat", "zrl", "no_eob", "slow",
           "max_abs", "reserved")
 CENSUS = ("rounds", "nchunks", "ncompact", "max_dc_cat", "zrl", "no_eob", "slow", "max_abs")
@@ -20,59 +14,20 @@ OK = 0
 LDS = 24576                                                  # kStreamLdsBytes of csrc/ndp_jpeg.inc
 
 
-class NoSanitizerRuntime(RuntimeError):
-    pass
-
-
-# the linker's own words for a runtime library that is not there; any other failure is a build break
-_RUNTIME_MISSING = re.compile(r"(cannot find|cannot open|unable to find|no such file)[^\n]*libclang_rt\.(asan|ubsan)"
-                              r"|libclang_rt\.(asan|ubsan)[^\n]*(cannot find|cannot open|no such file)", re.I)
-
-
-def _hipcc():
-    import sys
-    sys.path.insert(0, os.path.dirname(HERE))
-    from ndivplanning_amd import _build
-    return _build._hipcc()
-
-
-def build_driver(out_dir, sanitize=True):
-    """Compile the driver into out_dir and return its path.  Raises NoSanitizerRuntime where the toolchain cannot link
-    the sanitizers' runtimes."""
-    exe = os.path.join(str(out_dir), "jpeg_host_driver")
-    cmd = [_hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + (SANITIZE if sanitize else [])
-    cmd += ["-Wno-unused-value", "-Wno-pass-failed", "-Wno-invalid-offsetof", "-Wno-dangling-else", SOURCE, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        if sanitize and _RUNTIME_MISSING.search(res.stdout):     # the link step did not find the runtimes
-            raise NoSanitizerRuntime(res.stdout[-2000:])
-        raise RuntimeError("hipcc failed:\n" + res.stdout[-4000:])
-    return exe
+def build_driver(out_dir=None, sanitize=True):
+    return host_driver.build(sanitize)
 
 
 def run_driver(exe, streams, work_dir, frames=False, timeout=900):
     """Decode `streams` (bytes each) in a child process; asserts that it exits 0 with no sanitizer report.  Returns
     (records: {field: int32 [n]}, chunked, serial) where the last two are uint8 [n,128,128,3], or None without `frames`."""
-    src, dst = os.path.join(str(work_dir), "streams.bin"), os.path.join(str(work_dir), "report.bin")
-    with open(src, "wb") as f:
-        f.write(np.int32(len(streams)).tobytes())
-        for s in streams:
-            f.write(np.int32(len(s)).tobytes())
-            f.write(bytes(s))
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, src, dst] + (["frames"] if frames else []), env=env, capture_output=True, text=True,
-                       timeout=timeout)
-    text = p.stdout + p.stderr
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    raw = np.fromfile(dst, np.uint8)
+    payload = np.int32(len(streams)).tobytes() + b"".join(np.int32(len(s)).tobytes() + bytes(s) for s in streams)
+    raw = np.frombuffer(host_driver.run("jpeg", payload, work_dir, ["frames"] if frames else [], timeout, exe), np.uint8)
     n, per = len(streams), 4 * len(FIELDS) + (2 * FRAME if frames else 0)
     assert raw.size == n * per, (raw.size, n, per)
     raw = raw.reshape(n, per)
     ints = raw[:, :4 * len(FIELDS)].copy().view(np.int32)
     rec = {k: ints[:, i].copy() for i, k in enumerate(FIELDS)}
-    os.remove(src)
-    os.remove(dst)
     if not frames:
         return rec, None, None
     pix = raw[:, 4 * len(FIELDS):].reshape(n, 2, 128, 128, 3)

@@ -1,17 +1,10 @@
-"""Build and run tests/jpeg_enc_host_driver.hip, the JPEG encoder's core on the CPU, and rebuild the encoder corpus of
+"""Run tests/host_drivers/jpeg_enc.inc, the JPEG encoder's core on the CPU, through tests/host_driver.py, and rebuild the encoder corpus of
 tests/golden/jpeg_encode_case.npz (used by tests/test_jpeg_encode_core_host.py, tests/test_jpeg_encode_golden.py,
-tests/test_gpu_jpeg_encode.py and tests/golden/make_golden_jpeg_encode.py).  The driver is an ordinary program: it is
-started as a child process, nothing is preloaded and nothing of it is loaded into Python.  The build recipe, the
-sanitizer flags and the test for a toolchain without the runtimes are tests/jpeg_core_host.py's."""
-import os
-import subprocess
-
+tests/test_gpu_jpeg_encode.py and tests/golden/make_golden_jpeg_encode.py)."""
 import numpy as np
 
-import jpeg_core_host as H
+import host_driver
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(HERE, "jpeg_enc_host_driver.hip")
 FIELDS = ("len", "len_serial", "equal", "total_bits", "entropy_bytes", "stuffed", "last_ff", "zrl", "eob_only", "max_dc_cat",
           "max_stream", "reserved")
 CENSUS = ("total_bits", "entropy_bytes", "stuffed", "last_ff", "zrl", "eob_only", "max_dc_cat")
@@ -21,17 +14,8 @@ STORED, UNIFORM_NOISE, BINARY_NOISE, CORNER_NOISE = 0, 1, 2, 3      # `kind` of 
 ENV_ACTIONS = ((1.0, 0.5, -0.5, 0.0), (-1.0, -1.0, 1.0, 0.0), (0.3, -0.9, 0.2, 0.0))
 
 
-def build_driver(out_dir, sanitize=True):
-    """jpeg_core_host.build_driver for the encoder's driver."""
-    exe = os.path.join(str(out_dir), "jpeg_enc_host_driver")
-    cmd = [H._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + (H.SANITIZE if sanitize else [])
-    cmd += ["-Wno-unused-value", "-Wno-pass-failed", "-Wno-invalid-offsetof", "-Wno-dangling-else", SOURCE, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        if sanitize and H._RUNTIME_MISSING.search(res.stdout):
-            raise H.NoSanitizerRuntime(res.stdout[-2000:])
-        raise RuntimeError("hipcc failed:\n" + res.stdout[-4000:])
-    return exe
+def build_driver(out_dir=None, sanitize=True):
+    return host_driver.build(sanitize)
 
 
 def run_driver(exe, frames, coefs, work_dir, timeout=900):
@@ -40,20 +24,8 @@ def run_driver(exe, frames, coefs, work_dir, timeout=900):
     bytes, the scheduled writer's)."""
     frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, 128, 128, 3)
     coefs = np.ascontiguousarray(coefs, np.int16).reshape(-1, BLOCKS, 64)
-    src, dst = os.path.join(str(work_dir), "frames.bin"), os.path.join(str(work_dir), "streams.bin")
-    with open(src, "wb") as f:
-        f.write(np.int32(len(frames)).tobytes())
-        f.write(frames.tobytes())
-        f.write(np.int32(len(coefs)).tobytes())
-        f.write(coefs.tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, src, dst], env=env, capture_output=True, text=True, timeout=timeout)
-    text = p.stdout + p.stderr
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    raw = open(dst, "rb").read()
-    os.remove(src)
-    os.remove(dst)
+    payload = np.int32(len(frames)).tobytes() + frames.tobytes() + np.int32(len(coefs)).tobytes() + coefs.tobytes()
+    raw = host_driver.run("jpeg_enc", payload, work_dir, timeout=timeout, exe=exe)
     n = len(frames) + len(coefs)
     rec = {k: np.zeros(n, np.int32) for k in FIELDS}
     streams, at = [], 0

@@ -2,17 +2,12 @@
 tests/test_gpu_image_quality.py) and by tests/golden/make_golden_image_quality.py: the plain numpy restatements of
 ndp_image_quality's definition -- the fp32 scaling, PSNR, SSIM by the direct valid-window sum in fp64 and in
 fp32, and SSIM by the scikit-image route (scipy's gaussian_filter over the whole channel, cropped by 5) -- the golden
-file's pairs, and the build and run of tests/image_quality_host_driver.hip.  The driver is an ordinary program: it is
-started as a child process, nothing is preloaded and nothing of it is loaded into Python."""
-import os
-import subprocess
-
+file's pairs, and the run of tests/host_drivers/image_quality.inc through tests/host_driver.py.  `norm_table`,
+`as_float_images` and `ulps` are also the forward-model and generator evaluation tests' (fm_eval_common, gan_eval_common)."""
 import numpy as np
 
-import jpeg_core_host as J
+import host_driver
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(HERE, "image_quality_host_driver.hip")
 VALUES = 3 * 128 * 128
 OUT = 118
 F32 = np.float32
@@ -150,49 +145,30 @@ def as_float(x):
 
 
 # ------------------------------------------------------------------------------------------ the host driver
-def build_driver(out_dir, sanitize=True):
-    exe = os.path.join(str(out_dir), "image_quality_host_driver")
-    cmd = [J._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + (J.SANITIZE if sanitize else [])
-    cmd += ["-Wno-unused-value", "-Wno-pass-failed", "-Wno-invalid-offsetof", "-Wno-dangling-else", SOURCE, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        if sanitize and J._RUNTIME_MISSING.search(res.stdout):
-            raise J.NoSanitizerRuntime(res.stdout[-2000:])
-        raise RuntimeError("hipcc failed:\n" + res.stdout[-4000:])
-    return exe
+def build_driver(out_dir=None, sanitize=True):
+    return host_driver.build(sanitize)
 
 
 def run_driver(exe, cases, work_dir, timeout=900):
     """cases: dicts with a, b (float32 [m,3,128,128] or uint8 [m,128,128,3]), a_idx / b_idx (int32 [n] or None), n
     (pairs), rows (output rows per band), ssim / psnr (bool, default True).  Asserts that the child exits 0 with no
     sanitizer report.  Returns [(ssim float32 [n], psnr float32 [n])], -7 where not wanted."""
-    src, dst = os.path.join(str(work_dir), "cases.bin"), os.path.join(str(work_dir), "report.bin")
-    with open(src, "wb") as f:
-        f.write(np.int32(len(cases)).tobytes())
-        for c in cases:
-            kind = lambda a: 2 if a.dtype == np.uint8 else 1       # noqa: E731
-            maps = (1 if c.get("a_idx") is not None else 0) | (2 if c.get("b_idx") is not None else 0)
-            want = (1 if c.get("ssim", True) else 0) | (2 if c.get("psnr", True) else 0)
-            head = [c["n"], len(c["a"]), len(c["b"]), kind(c["a"]), kind(c["b"]), maps, c["rows"], want]
-            f.write(np.array(head, np.int32).tobytes())
-            for a in (c["a"], c["b"]):
-                f.write(np.ascontiguousarray(a).tobytes())
-            for idx in (c.get("a_idx"), c.get("b_idx")):
-                if idx is not None:
-                    assert len(idx) == c["n"]
-                    f.write(np.ascontiguousarray(idx, np.int32).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, src, dst], env=env, capture_output=True, text=True, timeout=timeout)
-    text = p.stdout + p.stderr
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    raw = np.fromfile(dst, F32)
+    parts = [np.int32(len(cases)).tobytes()]
+    for c in cases:
+        kind = lambda a: 2 if a.dtype == np.uint8 else 1       # noqa: E731
+        maps = (1 if c.get("a_idx") is not None else 0) | (2 if c.get("b_idx") is not None else 0)
+        want = (1 if c.get("ssim", True) else 0) | (2 if c.get("psnr", True) else 0)
+        head = [c["n"], len(c["a"]), len(c["b"]), kind(c["a"]), kind(c["b"]), maps, c["rows"], want]
+        parts += [np.array(head, np.int32).tobytes(), np.ascontiguousarray(c["a"]).tobytes(), np.ascontiguousarray(c["b"]).tobytes()]
+        for idx in (c.get("a_idx"), c.get("b_idx")):
+            if idx is not None:
+                assert len(idx) == c["n"]
+                parts.append(np.ascontiguousarray(idx, np.int32).tobytes())
+    raw = np.frombuffer(host_driver.run("image_quality", b"".join(parts), work_dir, timeout=timeout, exe=exe), F32)
     out, pos = [], 0
     for c in cases:
         n = c["n"]
         out.append((raw[pos:pos + n].copy(), raw[pos + n:pos + 2 * n].copy()))
         pos += 2 * n
     assert pos == raw.size, (pos, raw.size)
-    os.remove(src)
-    os.remove(dst)
     return out

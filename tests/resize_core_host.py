@@ -1,15 +1,9 @@
 """Shared by the resize tests (tests/test_resize_core_host.py, tests/test_gpu_resize.py, tests/golden/make_golden_resize.py):
-the frame sizes and contents, PIL's resize, and the build and run of tests/resize_host_driver.hip.  The driver is an
-ordinary program: it is started as a child process, nothing is preloaded and nothing of it is loaded into Python."""
-import os
-import subprocess
-
+the frame sizes and contents, PIL's resize, and the run of tests/host_drivers/resize.inc through tests/host_driver.py."""
 import numpy as np
 
-import jpeg_core_host as J
+import host_driver
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(HERE, "resize_host_driver.hip")
 SIZES = ((500, 500), (480, 640), (37, 53), (129, 127), (128, 300), (300, 128), (128, 128), (1, 1), (1, 2048), (2048, 1),
          (2048, 2048))                                        # (H, W)
 CONTENTS = ("noise", "binary", "gradient")
@@ -37,38 +31,20 @@ def pil_resize(frame):
     return np.array(Image.fromarray(frame).resize((128, 128), Image.LANCZOS))
 
 
-def build_driver(out_dir, sanitize=True):
-    exe = os.path.join(str(out_dir), "resize_host_driver")
-    cmd = [J._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + (J.SANITIZE if sanitize else [])
-    cmd += ["-Wno-unused-value", "-Wno-pass-failed", "-Wno-invalid-offsetof", "-Wno-dangling-else", SOURCE, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        if sanitize and J._RUNTIME_MISSING.search(res.stdout):
-            raise J.NoSanitizerRuntime(res.stdout[-2000:])
-        raise RuntimeError("hipcc failed:\n" + res.stdout[-4000:])
-    return exe
+def build_driver(out_dir=None, sanitize=True):
+    return host_driver.build(sanitize)
 
 
 def run_driver(exe, cases, work_dir, timeout=900):
     """cases: [(frame uint8 [h,w,3], expected uint8 [128,128,3])].  Asserts that the child exits 0 with no sanitizer
     report.  Returns ({field: int32 [n]}, resized uint8 [n,128,128,3])."""
-    src, dst = os.path.join(str(work_dir), "frames.bin"), os.path.join(str(work_dir), "report.bin")
-    with open(src, "wb") as f:
-        f.write(np.int32(len(cases)).tobytes())
-        for frame, want in cases:
-            f.write(np.array(frame.shape[:2], np.int32).tobytes())
-            f.write(np.ascontiguousarray(frame, np.uint8).tobytes())
-            f.write(np.ascontiguousarray(want, np.uint8).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, src, dst], env=env, capture_output=True, text=True, timeout=timeout)
-    text = p.stdout + p.stderr
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    raw = np.fromfile(dst, np.uint8)
+    parts = [np.int32(len(cases)).tobytes()]
+    for frame, want in cases:
+        parts += [np.array(frame.shape[:2], np.int32).tobytes(), np.ascontiguousarray(frame, np.uint8).tobytes(),
+                  np.ascontiguousarray(want, np.uint8).tobytes()]
+    raw = np.frombuffer(host_driver.run("resize", b"".join(parts), work_dir, timeout=timeout, exe=exe), np.uint8)
     per = 4 * len(FIELDS) + FRAME
     assert raw.size == len(cases) * per, (raw.size, len(cases), per)
     raw = raw.reshape(len(cases), per)
     ints = raw[:, :4 * len(FIELDS)].copy().view(np.int32)
-    os.remove(src)
-    os.remove(dst)
     return {k: ints[:, i].copy() for i, k in enumerate(FIELDS)}, raw[:, 4 * len(FIELDS):].reshape(-1, 128, 128, 3)

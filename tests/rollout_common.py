@@ -1,20 +1,17 @@
 """What the multi-step rollout tests share: the definition restated on the oracle's forward pass,
 the gradient recursion the device implements, the plain numpy restatement of the link kernels' arithmetic and
-schedule, and the build / run of the sanitized CPU driver (tests/fm_rollout_host_driver.hip).  No GPU is touched here."""
-import os
+schedule, and the run of the sanitized CPU driver (tests/host_drivers/fm_rollout.inc, through tests/host_driver.py).  No
+GPU is touched here."""
 import struct
-import subprocess
 from collections import OrderedDict
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-import jpeg_core_host as J
+import host_driver
 from oracle import forward_model_oracle as FO
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(HERE, "fm_rollout_host_driver.hip")
 PLANE, VALUES, THREADS = 128 * 128, 3 * 128 * 128, 256
 F32 = np.float32
 
@@ -136,16 +133,8 @@ def want_advance(state, resid, target, step, steps, loss, loss_sum):
 
 
 # ------------------------------------------------------------------------------------------ the CPU driver
-def build_driver(out_dir, sanitize=True):
-    exe = os.path.join(str(out_dir), "fm_rollout_host_driver")
-    cmd = [J._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + (J.SANITIZE if sanitize else [])
-    cmd += ["-Wno-unused-value", "-Wno-pass-failed", "-Wno-invalid-offsetof", "-Wno-dangling-else", SOURCE, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        if sanitize and J._RUNTIME_MISSING.search(res.stdout):
-            raise J.NoSanitizerRuntime(res.stdout[-2000:])
-        raise RuntimeError("hipcc failed:\n" + res.stdout[-4000:])
-    return exe
+def build_driver(out_dir=None, sanitize=True):
+    return host_driver.build(sanitize)
 
 
 def _strided(images, stride):
@@ -163,36 +152,27 @@ def run_driver(exe, cases, work_dir, timeout=900):
     """cases: dicts with kind 'begin' (frames, stride), 'advance' (state, resid, target, stride, step, steps, loss, loss_sum),
     'chain' (local, g_next, d_cur) or 'sum' (grads [count, floats], stride).  Asserts that the child exits 0 with no
     sanitizer report.  Returns per case the outputs the driver's header lists."""
-    src, dst = os.path.join(str(work_dir), "cases.bin"), os.path.join(str(work_dir), "report.bin")
     kinds = {"begin": 0, "advance": 1, "chain": 2, "sum": 3}
-    with open(src, "wb") as f:
-        f.write(struct.pack("<i", len(cases)))
-        for c in cases:
-            k = kinds[c["kind"]]
-            if k in (0, 1):
-                tgt = c["frames"] if k == 0 else c["target"]
-                n = tgt.shape[0]
-                f.write(struct.pack("<8i", k, n, c.get("steps", 1), c.get("step", 0), int(tgt.dtype == np.uint8), c["stride"], 0, 0))
-                if k == 1:
-                    f.write(np.ascontiguousarray(c["state"], F32).tobytes())
-                    f.write(np.ascontiguousarray(c["resid"], F32).tobytes())
-                f.write(_strided(tgt, c["stride"]).tobytes())
-                if k == 1:
-                    f.write(np.array([c["loss"], c["loss_sum"]], F32).tobytes())
-            elif k == 2:
-                f.write(struct.pack("<8i", k, c["local"].shape[0], 0, 0, 0, 0, 0, 0))
-                for name in ("local", "g_next", "d_cur"):
-                    f.write(np.ascontiguousarray(c[name], F32).tobytes())
-            else:
-                count, floats = c["grads"].shape
-                f.write(struct.pack("<8i", k, 1, 0, 0, 0, c["stride"], count, floats))
-                f.write(_strided(np.ascontiguousarray(c["grads"], F32), c["stride"]).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, src, dst], env=env, capture_output=True, text=True, timeout=timeout)
-    text = p.stdout + p.stderr
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    raw = np.fromfile(dst, np.uint8)
+    parts = [struct.pack("<i", len(cases))]
+    for c in cases:
+        k = kinds[c["kind"]]
+        if k in (0, 1):
+            tgt = c["frames"] if k == 0 else c["target"]
+            n = tgt.shape[0]
+            parts.append(struct.pack("<8i", k, n, c.get("steps", 1), c.get("step", 0), int(tgt.dtype == np.uint8), c["stride"], 0, 0))
+            if k == 1:
+                parts += [np.ascontiguousarray(c["state"], F32).tobytes(), np.ascontiguousarray(c["resid"], F32).tobytes()]
+            parts.append(_strided(tgt, c["stride"]).tobytes())
+            if k == 1:
+                parts.append(np.array([c["loss"], c["loss_sum"]], F32).tobytes())
+        elif k == 2:
+            parts.append(struct.pack("<8i", k, c["local"].shape[0], 0, 0, 0, 0, 0, 0))
+            parts += [np.ascontiguousarray(c[name], F32).tobytes() for name in ("local", "g_next", "d_cur")]
+        else:
+            count, floats = c["grads"].shape
+            parts += [struct.pack("<8i", k, 1, 0, 0, 0, c["stride"], count, floats),
+                      _strided(np.ascontiguousarray(c["grads"], F32), c["stride"]).tobytes()]
+    raw = np.frombuffer(host_driver.run("fm_rollout", b"".join(parts), work_dir, timeout=timeout, exe=exe), np.uint8)
     out, pos = [], 0
 
     def take(count, dtype):
@@ -215,6 +195,4 @@ def run_driver(exe, cases, work_dir, timeout=900):
         else:
             out.append(take(c["grads"].shape[1], F32))
     assert pos == raw.size, (pos, raw.size)
-    os.remove(src)
-    os.remove(dst)
     return out

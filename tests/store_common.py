@@ -1,17 +1,11 @@
 """Shared by the trajectory-store tests (tests/test_store_gather_host.py, tests/test_gpu_trajectory_store.py): the
 random-byte corpora, the gather cases, what a gather must give -- `pack_jpegs` of the selected streams in batch order plus
-numpy slices of the tables -- and the build and run of tests/store_gather_host_driver.hip.  The driver is an ordinary
-program: it is started as a child process, nothing is preloaded and nothing of it is loaded into Python."""
-import os
-import subprocess
-
+numpy slices of the tables -- and the run of tests/host_drivers/store_gather.inc through tests/host_driver.py."""
 import numpy as np
 
-import jpeg_core_host as J
+import host_driver
 from ndivplanning_amd.bundle import ACTION_DIM, GOAL_DIM, STATE_DIM
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(HERE, "store_gather_host_driver.hip")
 CHUNK_BYTES = 4096                  # one workgroup's chunk (ndp::store::kChunkBytes)
 LONG_STREAM = 70001                 # longer than a chunk and than 65,537 bytes: split over 18 workgroups
 LENGTHS = (0, 1, 2, 15, 16, 17, 31, 33, 63, 64, 65, 255, 256, 257, 4093, 4099, LONG_STREAM)
@@ -145,36 +139,20 @@ def check(name, got, want):
 
 
 # ------------------------------------------------------------------------------------------ the host driver
-def build_driver(out_dir, sanitize=True):
-    exe = os.path.join(str(out_dir), "store_gather_host_driver")
-    cmd = [J._hipcc(), "--offload-arch=gfx950", "-O1", "-g", "-std=c++17"] + (J.SANITIZE if sanitize else [])
-    cmd += ["-Wno-unused-value", "-Wno-pass-failed", "-Wno-invalid-offsetof", "-Wno-dangling-else", SOURCE, "-o", exe]
-    res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if res.returncode != 0:
-        if sanitize and J._RUNTIME_MISSING.search(res.stdout):
-            raise J.NoSanitizerRuntime(res.stdout[-2000:])
-        raise RuntimeError("hipcc failed:\n" + res.stdout[-4000:])
-    return exe
+def build_driver(out_dir=None, sanitize=True):
+    return host_driver.build(sanitize)
 
 
 def run_driver(exe, corpus, case_list, work_dir, timeout=600):
     """Asserts that the child exits 0 with no sanitizer report.  Returns per case ((buffer, offsets, states, actions,
     goal, status), bytes changed past offsets[-1])."""
-    src, dst = os.path.join(str(work_dir), "cases.bin"), os.path.join(str(work_dir), "report.bin")
-    with open(src, "wb") as f:
-        f.write(np.array([corpus["n"], corpus["steps"], corpus["blob"].size], np.int64).tobytes())
-        for a in (corpus["offsets"], corpus["states"], corpus["actions"], corpus["goal"], corpus["blob"]):
-            f.write(np.ascontiguousarray(a).tobytes())
-        f.write(np.int64(len(case_list)).tobytes())
-        for _, indices, seq_start, seq_length in case_list:
-            f.write(np.array([len(indices), seq_start, seq_length, capacity(corpus, indices, seq_length)], np.int64).tobytes())
-            f.write(np.ascontiguousarray(indices, np.int64).tobytes())
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:exitcode=86", UBSAN_OPTIONS="print_stacktrace=1")
-    p = subprocess.run([exe, src, dst], env=env, capture_output=True, text=True, timeout=timeout)
-    text = p.stdout + p.stderr
-    assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    raw = np.fromfile(dst, np.uint8)
+    parts = [np.array([corpus["n"], corpus["steps"], corpus["blob"].size], np.int64).tobytes()]
+    parts += [np.ascontiguousarray(corpus[k]).tobytes() for k in ("offsets", "states", "actions", "goal", "blob")]
+    parts.append(np.int64(len(case_list)).tobytes())
+    for _, indices, seq_start, seq_length in case_list:
+        parts += [np.array([len(indices), seq_start, seq_length, capacity(corpus, indices, seq_length)], np.int64).tobytes(),
+                  np.ascontiguousarray(indices, np.int64).tobytes()]
+    raw = np.frombuffer(host_driver.run("store_gather", b"".join(parts), work_dir, timeout=timeout, exe=exe), np.uint8)
     results, pos = [], 0
 
     def take(count, dtype):
@@ -194,6 +172,4 @@ def run_driver(exe, corpus, case_list, work_dir, timeout=600):
         buffer = take(int(offsets[-1]), np.uint8)
         results.append(((buffer, offsets, states, actions, goal, status), changed))
     assert pos == raw.size, (pos, raw.size)
-    os.remove(src)
-    os.remove(dst)
     return results

@@ -1,5 +1,5 @@
 """The rollout link kernels and the gradient sum (csrc/ndp_forward_model.inc, namespace ndp::fm_rollout) on the CPU, under
-AddressSanitizer and UndefinedBehaviorSanitizer.  tests/fm_rollout_host_driver.hip includes the library's source and runs
+AddressSanitizer and UndefinedBehaviorSanitizer.  tests/host_drivers/fm_rollout.inc follows the library's source in main.hip and runs
 the kernels' cores by their schedule, every buffer (inputs with their image stride, outputs, each LDS array) in an
 allocation of exactly its size.  The expected values are the plain numpy restatement in tests/rollout_common.py: every
 addition is in a fixed order, so sums and adds must agree to the bit.  The sanitizers are on the host half of the
@@ -8,15 +8,16 @@ tests/test_gpu_forward_rollout.py)."""
 import numpy as np
 import pytest
 
+import host_driver
 import rollout_common as C
 
 F32 = np.float32
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
+def driver():
     # a toolchain that cannot link the sanitizers' runtimes fails here: without them this file proves nothing
-    return C.build_driver(tmp_path_factory.mktemp("fm_rollout_host_driver"))
+    return host_driver.build()
 
 
 def _images(rng, n):

@@ -1,5 +1,5 @@
 """The forward-model scoring kernel's core (k_fm_score, csrc/ndp_eval.inc) on the CPU, under AddressSanitizer and
-UndefinedBehaviorSanitizer.  tests/fm_score_host_driver.hip includes the library's source and scores n = 1, 3, 5
+UndefinedBehaviorSanitizer.  tests/host_drivers/fm_score.inc follows the library's source in main.hip and scores n = 1, 3, 5
 predictions by the kernel's schedule with the library's own __host__ __device__ functions, every buffer (inputs, index
 maps, outputs, each LDS array) in an allocation of exactly its size.  The expected values are the plain numpy restatement
 of the stated definition (tests/fm_eval_common.py).  The sanitizers are on the host half of the stand-alone driver only;
@@ -8,12 +8,13 @@ import numpy as np
 import pytest
 
 import fm_eval_common as C
+import host_driver
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
+def driver():
     # a toolchain that cannot link the sanitizers' runtimes fails here: without them this file proves nothing
-    return C.build_driver(tmp_path_factory.mktemp("fm_score_host_driver"))
+    return host_driver.build()
 
 
 def _cases():

@@ -1,5 +1,5 @@
 """The generator scoring kernel's core (k_gan_score, csrc/ndp_eval.inc) on the CPU, under AddressSanitizer and
-UndefinedBehaviorSanitizer.  tests/gan_score_host_driver.hip includes the library's source and scores every case by the
+UndefinedBehaviorSanitizer.  tests/host_drivers/gan_score.inc follows the library's source in main.hip and scores every case by the
 kernel's schedule with the library's own __host__ __device__ functions (namespace ndp::gan_score), every buffer (inputs,
 outputs, each LDS array) in an allocation of exactly its size.  The expected values are the plain numpy restatement of the
 stated definition (tests/gan_eval_common.py).  The sanitizers are on the host half of the stand-alone driver only; it runs
@@ -8,12 +8,13 @@ import numpy as np
 import pytest
 
 import gan_eval_common as C
+import host_driver
 
 
 @pytest.fixture(scope="module")
 def report(tmp_path_factory):
     # a toolchain that cannot link the sanitizers' runtimes fails here: without them this file proves nothing
-    driver = C.build_driver(tmp_path_factory.mktemp("gan_score_host_driver"))
+    driver = host_driver.build()
     case_list = C.cases()
     return case_list, C.run_driver(driver, case_list, tmp_path_factory.mktemp("gan_score_cases"))
 

@@ -1,5 +1,5 @@
 """The image-quality kernels' core (k_image_quality, k_image_quality_finish, csrc/ndp_eval.inc) on the CPU, under
-AddressSanitizer and UndefinedBehaviorSanitizer.  tests/image_quality_host_driver.hip includes the library's source and
+AddressSanitizer and UndefinedBehaviorSanitizer.  tests/host_drivers/image_quality.inc follows the library's source in main.hip and
 scores n = 1, 3, 5 pairs by the kernels' schedule with the library's own __host__ __device__ functions, with 16 and with 32
 output rows per band (8 and 4 bands, the kernel's two instantiations), every buffer (inputs, index maps, workspace,
 outputs, each LDS array) in an allocation of exactly its size.  The expected values are the golden file's (tests/golden/image_quality_case.npz: SSIM by
@@ -11,15 +11,16 @@ GPU: tests/test_gpu_image_quality.py)."""
 import numpy as np
 import pytest
 
+import host_driver
 import quality_common as Q
 
 ROWS = (16, 32)
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
+def driver():
     # a toolchain that cannot link the sanitizers' runtimes fails here: without them this file proves nothing
-    return Q.build_driver(tmp_path_factory.mktemp("image_quality_host_driver"))
+    return host_driver.build()
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """The JPEG decoder's core (csrc/ndp_jpeg.inc) on the CPU, under AddressSanitizer and UndefinedBehaviorSanitizer (signed
-overflow included).  tests/jpeg_host_driver.hip includes the library's source and calls the __host__ __device__ functions
+overflow included).  tests/host_drivers/jpeg.inc follows the library's source in main.hip and calls the __host__ __device__ functions
 the kernels call; it decodes every stream twice, by k_jpeg_entropy's schedule of chunks and sync rounds run serially and by
 one lane from bit 0, and the two must agree for every stream, valid or not (every chunk's entry is
 exact by induction).  The streams: the edge corpus tests/golden/jpeg_edges.npz (made by
@@ -12,6 +12,7 @@ import io
 import numpy as np
 import pytest
 
+import host_driver
 import jpeg_core_host as H
 from conftest import load_golden
 
@@ -19,10 +20,10 @@ N_MUTATIONS = 3200
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
+def driver():
     try:
-        return H.build_driver(tmp_path_factory.mktemp("jpeg_host_driver"))
-    except H.NoSanitizerRuntime as e:
+        return host_driver.build()
+    except host_driver.NoSanitizerRuntime as e:
         pytest.skip("this toolchain cannot link the sanitizers' runtimes: " + str(e)[-300:])
 
 

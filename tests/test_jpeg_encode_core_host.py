@@ -1,5 +1,5 @@
 """The JPEG encoder's core (csrc/ndp_jpeg_enc.inc) on the CPU, under AddressSanitizer and UndefinedBehaviorSanitizer
-(signed overflow included).  tests/jpeg_enc_host_driver.hip includes the library's source and runs the __host__ __device__
+(signed overflow included).  tests/host_drivers/jpeg_enc.inc follows the library's source in main.hip and runs the __host__ __device__
 functions the kernels call by the kernels' schedule, serially: colour conversion, downsampling, DCT and quantisation per
 block; bit counts per block, scan, bits ORed into words of a buffer of exactly its own size, padding, stuffing by lane.
 Every stream must be the fixture's (PIL's) bytes and must equal what a plain one-lane bit writer in the same driver gives.
@@ -9,16 +9,16 @@ GPU: tests/test_gpu_jpeg_encode.py).  Most of the time is the one compilation.""
 import numpy as np
 import pytest
 
-import jpeg_core_host as H
+import host_driver
 import jpeg_enc_core_host as E
 from conftest import load_golden
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
+def driver():
     try:
-        return E.build_driver(tmp_path_factory.mktemp("jpeg_enc_host_driver"))
-    except H.NoSanitizerRuntime as e:
+        return host_driver.build()
+    except host_driver.NoSanitizerRuntime as e:
         pytest.skip("this toolchain cannot link the sanitizers' runtimes: " + str(e)[-300:])
 
 

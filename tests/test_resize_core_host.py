@@ -1,5 +1,5 @@
 """The Lanczos resize (csrc/ndp_resize.inc) on the CPU, under AddressSanitizer and UndefinedBehaviorSanitizer (signed
-overflow included).  tests/resize_host_driver.hip includes the library's source, builds the coefficient tables with the
+overflow included).  tests/host_drivers/resize.inc follows the library's source in main.hip, builds the coefficient tables with the
 library's own function and resizes every frame by the kernel's schedule (every band split a launch can choose), with the
 frame, each raw row, each band's tile and the tables in allocations of exactly their size.  The expected bytes are this
 machine's PIL's, computed here.  The sanitizers are on the host half of the stand-alone driver only; it runs as an ordinary
@@ -13,14 +13,15 @@ import numpy as np
 import pytest
 import torch
 
+import host_driver
 import resize_core_host as R
 from conftest import load_golden
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
+def driver():
     # a toolchain that cannot link the sanitizers' runtimes fails here: without them this file proves nothing
-    return R.build_driver(tmp_path_factory.mktemp("resize_host_driver"))
+    return host_driver.build()
 
 
 @pytest.fixture(scope="module")

@@ -1,5 +1,5 @@
 """The trajectory store's batch gather (k_store_scan, k_store_copy, csrc/ndp_store.inc) on the CPU, under
-AddressSanitizer and UndefinedBehaviorSanitizer.  tests/store_gather_host_driver.hip includes the library's source and
+AddressSanitizer and UndefinedBehaviorSanitizer.  tests/host_drivers/store_gather.inc follows the library's source in main.hip and
 runs every case by the kernels' schedule with the library's own __host__ __device__ functions (namespace ndp::store), every
 buffer in an allocation of exactly its size -- the blob included, which the store does not pad: the copy's aligned reads
 around an unaligned source range must narrow at the blob's two ends by themselves.  The streams are random bytes.  The
@@ -9,13 +9,14 @@ involved (the same cases on the GPU: tests/test_gpu_trajectory_store.py)."""
 import numpy as np
 import pytest
 
+import host_driver
 import store_common as C
 
 
 @pytest.fixture(scope="module")
-def driver(tmp_path_factory):
+def driver():
     # a toolchain that cannot link the sanitizers' runtimes fails here: without them this file proves nothing
-    return C.build_driver(tmp_path_factory.mktemp("store_gather_host_driver"))
+    return host_driver.build()
 
 
 @pytest.fixture(scope="module")
