@@ -215,6 +215,16 @@ typedef struct ndp_step_buffers {
 } ndp_step_buffers;
 
 int64_t ndp_step_workspace_floats(const ndp_step_config *cfg);
+/* Float offset inside that workspace of what a step leaves behind, for tests.  tensor:
+ *   0..3  G's saved activations h1..h4, [pad(M),128] [pad(M),64] [pad(M),128] [pad(M),256] (written by phase A only)
+ *   4     factor * dNDiv/d action_hat, [pad(M),4] (written by the NDiv blocks only)
+ *   5     dLoss/d action_hat, NDiv term included: what G's backward starts from, [pad(M),4] (phase B)
+ *   6..8  D's saved activations h1..h3 of the first D step, [pad(FLAT) + pad(M), 64 | 128 | 256]: the distinct real
+ *         rows, then from row pad(FLAT) the fake rows (phase B leaves them alone)
+ *   9..11 the same of a repeat D step (run_g_forward = 0), which overwrites 6..8: [2 pad(M), .], real rows then fake rows
+ * -1: bad config or index. */
+#define NDP_STEP_TENSORS 12
+int64_t ndp_step_workspace_offset(const ndp_step_config *cfg, int tensor);
 
 /* codes [flat,256], actions [flat,4] (ground truth), noise [flat,K,nz].
  * run_g_forward: 1 on the first D step of an iteration, 0 on repeats

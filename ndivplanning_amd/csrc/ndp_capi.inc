@@ -837,7 +837,7 @@ static int step_ndiv_threads(const ndp_step_config* c) {
   return step_ndiv_fused(c) ? kThreads : ndiv_block_threads(c->num_sample);
 }
 
-static int64_t step_floats(const ndp_step_config* c, StepWs* out, float* base) {
+static int64_t step_floats(const ndp_step_config* c, StepWs* out, float* base, int64_t* test_offsets = nullptr) {
   const int64_t m = c->flat * c->num_sample, mpad = pad_rows(m);
   int64_t o = 0;
   const int64_t o_acts = o; o += g_acts_floats(mpad);
@@ -861,6 +861,16 @@ static int64_t step_floats(const ndp_step_config* c, StepWs* out, float* base) {
     out->acts = g_acts(base + o_acts, mpad);
     out->gb = base + o_gb; out->db = base + o_db; out->d_action = base + o_da; out->nd_grad = base + o_ng;
     out->nd_part = base + o_np; out->nd_count = npart;
+  }
+  if (test_offsets) {                                  // ndp_step_workspace_offset (the order of NDP_STEP_TENSORS in ndp.h)
+    test_offsets[0] = o_acts; test_offsets[1] = o_acts + mpad * 128; test_offsets[2] = o_acts + mpad * (128 + 64);
+    test_offsets[3] = o_acts + mpad * (128 + 64 + 128); test_offsets[4] = o_ng;
+    test_offsets[5] = o_gb + mpad * (128 + 64 + 128 + 256);       // dy5 of g_bwd_ws
+    const int64_t rows[2] = {step_d_rows(c), 2 * mpad};           // the layouts of d_bwd_ws_rows: first / repeat D step
+    for (int r = 0; r < 2; ++r) {
+      test_offsets[6 + 3 * r] = o_db + rows[r] * 4; test_offsets[7 + 3 * r] = o_db + rows[r] * (4 + 64);
+      test_offsets[8 + 3 * r] = o_db + rows[r] * (4 + 64 + 128);
+    }
   }
   return o;
 }
@@ -989,6 +999,16 @@ int ndp_p2p_all_reduce(const ndp_p2p* c, int net, const float* in, float* out, i
 int64_t ndp_step_workspace_floats(const ndp_step_config* cfg) {
   if (!cfg || cfg->flat < 1 || cfg->num_sample < 1 || cfg->num_sample > NDP_MAX_SAMPLES) return 0;
   return step_floats(cfg, nullptr, nullptr);
+}
+
+int64_t ndp_step_workspace_offset(const ndp_step_config* cfg, int tensor) {
+  if (!cfg || cfg->flat < 1 || cfg->num_sample < 1 || cfg->num_sample > NDP_MAX_SAMPLES || cfg->noise_dim < 1 ||
+      cfg->noise_dim > NDP_MAX_NOISE_DIM || cfg->flat >= (1ll << 28) || cfg->flat * cfg->num_sample >= (1ll << 28) ||
+      tensor < 0 || tensor >= NDP_STEP_TENSORS)
+    return -1;
+  int64_t at[NDP_STEP_TENSORS];
+  step_floats(cfg, nullptr, nullptr, at);
+  return at[tensor];
 }
 
 int ndp_step_d_grads(const ndp_step_config* c, const ndp_step_buffers* b, const float* codes, const float* actions,

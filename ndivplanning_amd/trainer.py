@@ -366,6 +366,34 @@ class GanTrainer:
         v = self.losses_dev.tolist()
         return v[0], v[1], v[2]
 
+    _ACTIVATIONS = {"g.h1": (0, 128), "g.h2": (1, 64), "g.h3": (2, 128), "g.h4": (3, 256), "nd_grad": (4, ACTION_DIM),
+                    "d_action": (5, ACTION_DIM), "d.h1": (6, 64), "d.h2": (7, 128), "d.h3": (8, 256)}
+
+    def activation(self, name, repeat=False):
+        """What the last step left in the workspace, for tests (ndp_step_workspace_offset): views, not copies.
+        "g.h1".."g.h4": G's saved (post-ReLU) activations, "nd_grad": the NDiv gradient w.r.t. action_hat already scaled
+        by pairwise_div_factor, "d_action": dLoss/d action_hat that G's backward started from (NDiv term included) --
+        the first M rows of each.  "d.h1".."d.h3": D's saved (post-leaky-ReLU) activations of the D step as a pair
+        (real, fake): the FLAT distinct real rows and the M fake rows of the first D step of an iteration, or, with
+        `repeat`, the M real and M fake rows of a repeat D step (discrim_steps > 1), which overwrites the former.
+        Valid after step() in every mode: the regions are disjoint from everything else in the workspace; only phase
+        A's G forward writes h1..h4 (phase B and k_wgrad[G] read them), only the NDiv blocks write nd_grad, only phase B
+        writes d_action, and phase B does not touch D's activations."""
+        try:
+            idx, width = self._ACTIVATIONS[name]
+        except KeyError:
+            raise ValueError("activation %r: one of %s" % (name, ", ".join(self._ACTIVATIONS))) from None
+        is_d = name.startswith("d.h")
+        off = self.lib.ndp_step_workspace_offset(ctypes.byref(self.cfg), idx + (3 if is_d and repeat else 0))
+        if off < 0:
+            raise _capi.NdpError("ndp_step_workspace_offset refused the step configuration")
+        mpad = _capi.pad_rows(self.m)
+        if not is_d:
+            return self.workspace[off:off + mpad * width].view(mpad, width)[:self.m]
+        real_pad, real = (mpad, self.m) if repeat else (_capi.pad_rows(self.flat), self.flat)
+        rows = self.workspace[off:off + (real_pad + mpad) * width].view(real_pad + mpad, width)
+        return rows[:real], rows[real_pad:real_pad + self.m]
+
     def pop_loss_sums(self):
         """Running sums of the three losses since the last call (one sync per epoch
         instead of the reference's three per step, train_gan.py:205-207)."""

@@ -69,6 +69,10 @@ def _fp64_grads(g, d, codes, actions, noise, lr, factor, d_post=None):
 
 def _grad_close_adjudicated(mine, ref32, ref64, what, margin=4.0):
     """|mine - fp64| <= max(1e-5 * scale, margin * |reference fp32 - fp64|) (max norm)."""
+    # On a G gradient this net-wide max-norm bound is loose once FLAT reaches a few hundred: the two references take
+    # their own ReLU and hinge decisions and differ by 2e-3 at FLAT = 175 / K = 6, 0.6 at FLAT = 448, 5 at FLAT = 896
+    # (max |g| ~ 40), so a kernel that lost a whole 64 x 64 job would pass.  tests/test_gpu_step_gradients.py holds the
+    # same 4 x / 1e-5 per parameter tensor with the run's decisions injected into both references, at every launch plan.
     mine, ref32, ref64 = mine.detach().cpu().double(), ref32.detach().cpu().double(), ref64.double()
     assert torch.isfinite(mine).all(), what + ": non-finite"
     scale = max(1.0, ref64.abs().max().item())
