@@ -782,6 +782,42 @@ int ndp_store_gather(const uint8_t *blob, int64_t blob_bytes, const int64_t *fra
                      int64_t *out_offsets, float *out_states, float *out_actions, float *out_goal, int32_t *status,
                      void *stream);
 
+/* ------------------------------------------- planner: cross-entropy refinement ---
+ * One iteration of the cross-entropy method on a scored population of action sequences (evaluation.py: mpc_plan /
+ * plan_step with `cem`), in ONE launch, one workgroup of 256 threads per trajectory.  A population is seq [Th][B][R][4]:
+ * slice ts is the [B*R,4] action operand of ndp_fm_forward, no gather.
+ *   err        [B,R] device: the population's scores (ndp_eval_score_select's err)
+ *   seq_in     [Th,B,R,4] device: the population that was scored
+ *   normal     [Th,B,R,4] device: standard normal draws (ndp_normal_noise); row 0 of every (ts, b) is not read
+ *   first      1: mean / std / best_err are only written (no smoothing, no running minimum); 0: they are in/out
+ *   low4/high4 host, 4 floats each: the bounds of the 4 action components
+ *   mean, std  [B,Th,4] device; seq_out [Th,B,R,4] device; best_err [B] device; elite_idx [B,elites] device int32 or NULL
+ * Ranking: row i comes before row j when e_i < e_j, or e_i == e_j and i < j; a NaN error comes after every number,
+ * NaNs among themselves by index.  Rank 0 is the row ndp_eval_score_select picks without `forced` (whenever that
+ * error is below its sentinel 1e10).  E' = min(elites, number of non-NaN errors); elite_idx[b] = the E' best rows in rank
+ * order, then -1.
+ * Refit, per component d of the D = 4 Th: the fp64 sum over the E' elites in rank order / E'; the fp64 sum of the
+ * squared deviations from that mean / E' (population variance), fp64 sqrt; unless `first`, mean = momentum * mean_old +
+ * (1 - momentum) * m and likewise std, in fp64, each product and sum rounded (no contraction); std = max(std, min_std);
+ * each rounded to fp32 once.  E' == 0: mean and std stay (with `first`: 0 and min_std).
+ * Resample: row 0 of seq_out is the rank-0 row of seq_in, bit for bit (E' == 0: row 0).  Every other element is
+ * (float)((double)std * (double)n + (double)mean) -- the product is exact in fp64 --, clamped to [low, high] of its
+ * component with fmaxf / fminf; a NaN stays NaN.
+ * best_err[b] = min(best_err[b], e_rank0); a NaN never replaces a number (with `first`: e_rank0).
+ * 1 <= B <= 65535, 2 <= R <= NDP_MAX_SAMPLES, 1 <= elites <= R, 1 <= Th <= 32, low <= high per component,
+ * 0 <= momentum < 1, min_std >= 0; seq_in, normal and seq_out 16-byte aligned.  A limit exceeded, seq_out aliasing
+ * seq_in or normal, a null required pointer: NDP_E_ARG, nothing launched.  No atomics, no scratch memory, no host
+ * synchronisation: two calls give the same bits.  The caller owns every buffer.
+ *
+ * ndp_normal_noise: out[0 .. n) standard normal, Box-Muller over ndp_uniform_noise's stream: with U = the uniforms of
+ * the same (seed, *offset_dev), pair j takes u1 = U[2j], u2 = U[2j+1], r = sqrtf(-2 logf(1 - u1)) (1 - u1 > 0: no
+ * infinity), out[2j] = r cosf(2 pi u2), out[2j+1] = r sinf(2 pi u2) in fp32; an odd n drops the last sine. */
+int ndp_plan_cem_update(const float *err, const float *seq_in, const float *normal, int64_t n_traj, int rollouts,
+                        int steps, int elites, int first, float momentum, float min_std, const float *low4,
+                        const float *high4, float *mean, float *std, float *seq_out, float *best_err,
+                        int32_t *elite_idx, void *stream);
+int ndp_normal_noise(float *out, int64_t n, uint64_t seed, const int32_t *offset_dev, void *stream);
+
 /* ------------------------------------------------------------ measurement ---
  * Per-kernel timing for bench.py: while enabled (per host thread) every kernel
  * this library launches is bracketed by hipEvents recorded on the stream it is

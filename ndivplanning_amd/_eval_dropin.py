@@ -27,6 +27,8 @@ def fetch(kind, image_encoder, fwd_model_autoencoder, generator, dataset, config
     np.random.seed(seed)
     loader = data.DataLoader(dataset, batch_size=bs, shuffle=False, **E.jpeg.loader_kwargs(dataset))
     shapes = E.noise_piece_shapes(kind, bs, dataset.seq_length, k, nz, r, th)
+    # the optional `mpc.cem` mapping turns the cross-entropy planner on (evaluation.CemSettings; absent: off)
+    cem = E.cem_from_config(config) if kind == "mpc" else None
     action_error_sum = torch.zeros(1, dtype=torch.float32, device=models.device)
     image_error_sum = None
     for i, inputs in enumerate(loader):
@@ -42,7 +44,10 @@ def fetch(kind, image_encoder, fwd_model_autoencoder, generator, dataset, config
         elif kind == "closed":
             res = E.closed_loop(models, images, actions, k, noise, action_error_acc=action_error_sum, on_step=print)
         else:
-            res = E.mpc_plan(models, images, actions, r, th, noise=noise, on_step=print)
+            if cem is None:
+                res = E.mpc_plan(models, images, actions, r, th, noise=noise, on_step=print)
+            else:                                          # the normal draws: the device's, one stream per trajectory
+                res = E.mpc_plan(models, images, actions, r, th, noise=noise, on_step=print, cem=cem, seed=seed + i)
             models.mse(actions[:, :t1].contiguous(), res["actions"], 1, t1 * 4, acc=action_error_sum)
         image_error_sum = res["image_error_sum"][0]
         if kind != "open":

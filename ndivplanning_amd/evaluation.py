@@ -16,6 +16,10 @@ What the loops deduplicate against the reference, with the same arithmetic per i
   * the rollouts are scored and chosen on the device (mpc_eval.py:159-165: one host sync per rollout), and the chosen
     rollout's ts = 0 prediction becomes the next state (mpc_eval.py:167-169 recomputes it with one more forward call);
   * `mpc_plan` runs B trajectories at once: every launch serves B * R images.
+
+Beyond the reference: `cem=CemSettings(...)` on mpc_plan / plan_step / MpcController refines the rollouts' action
+sequences by the cross-entropy method before the choice (csrc/ndp_plan.inc: ndp_plan_cem_update, ndp_normal_noise); off by
+default, and then nothing here computes anything else than before.
 """
 import torch
 
@@ -170,6 +174,28 @@ class EvalModels:
                         "ndp_uniform_noise")
         return out
 
+    def normal(self, n, seed):
+        """n standard normal floats on the device (ndp_normal_noise).  They come from counter offset 1 of `seed`'s
+        stream, so they are independent of uniform(n, seed), which reads offset 0."""
+        if getattr(self, "_normal_offset", None) is None:
+            self._normal_offset = torch.ones(1, dtype=torch.int32, device=self.device)
+        out = torch.empty(max(int(n), 1), dtype=torch.float32, device=self.device)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_normal_noise(_ptr(out), max(int(n), 1), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                                  _ptr(self._normal_offset), self._stream()), "ndp_normal_noise")
+        return out
+
+    def cem_update(self, err, seq_in, normal, settings, first, mean, std, seq_out, best_err, elite_idx=None):
+        """ndp_plan_cem_update on the population seq_in [Th,B,R,4] with the scores err [B,R]: refits mean / std
+        [B,Th,4] (in/out unless `first`), writes the next population to seq_out and the running minimum to best_err."""
+        th, b, r = int(seq_in.shape[0]), int(seq_in.shape[1]), int(seq_in.shape[2])
+        low, high = (_capi.c_float * 4)(*settings.low), (_capi.c_float * 4)(*settings.high)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_plan_cem_update(_ptr(err), _ptr(seq_in), _ptr(normal), b, r, th, settings.elite_count(r),
+                                                     1 if first else 0, settings.momentum, settings.min_std, low, high,
+                                                     _ptr(mean), _ptr(std), _ptr(seq_out), _ptr(best_err), _ptr(elite_idx),
+                                                     self._stream()), "ndp_plan_cem_update")
+
 
 # ---------------------------------------------------------------------- the reference's noise stream (CPU)
 def noise_piece_shapes(kind, batch, seq_length, num_sample, noise_dim, rollouts=None, horizon=None):
@@ -302,13 +328,195 @@ def closed_loop(models, frames, actions, num_sample, noise, action_error_acc=Non
             "action_error": action_error}
 
 
+# ---------------------------------------------------------------------- cross-entropy refinement of the proposals
+class CemSettings:
+    """The opt-in planner of mpc_plan / plan_step / MpcController (`cem=`): `iterations` rounds of the cross-entropy
+    method after the first population.  Each round refits a diagonal Gaussian over the Th x 4 action sequence to the
+    `elites` best rollouts (ndp_plan_cem_update), resamples R - 1 sequences from it beside the best one, and scores them
+    with Th open-loop forward-model passes.
+      iterations  rounds after population 0 (0: population 0 alone, today's planner bit for bit)
+      elites      rollouts the Gaussian is fitted to; None: max(1, R // 4)
+      momentum    weight of the previous fit in the smoothed one, 0 <= momentum < 1
+      min_std     floor of the fitted deviation
+      proposal    population 0: "generator" (the closed-loop generator rollouts) or "uniform" (low + (high - low) * u
+                  from the same noise stream, the baseline)
+      low, high   bounds of the 4 action components: one number for all, or 4
+    The defaults are hyperparameters, not measurements."""
+
+    FIELDS = ("iterations", "elites", "momentum", "min_std", "proposal", "low", "high")
+
+    def __init__(self, iterations=3, elites=None, momentum=0.1, min_std=0.05, proposal="generator", low=-1.0, high=1.0):
+        def integer(v, name):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("cem.%s must be an integer, got %r" % (name, v))
+            return int(v)
+
+        def four(v, name):
+            vals = [float(x) for x in v] if hasattr(v, "__len__") else [float(v)] * 4
+            if len(vals) != 4 or any(x != x or x in (float("inf"), float("-inf")) for x in vals):
+                raise ValueError("cem.%s must be one finite number or 4, got %r" % (name, v))
+            return tuple(vals)
+
+        self.iterations = integer(iterations, "iterations")
+        if self.iterations < 0:
+            raise ValueError("cem.iterations must be >= 0, got %d" % self.iterations)
+        self.elites = None if elites is None else integer(elites, "elites")
+        if self.elites is not None and not 1 <= self.elites <= _capi.MAX_SAMPLES:
+            raise ValueError("cem.elites must lie in 1..%d (and not above the rollouts), got %d"
+                             % (_capi.MAX_SAMPLES, self.elites))
+        self.momentum, self.min_std = float(momentum), float(min_std)
+        if not 0.0 <= self.momentum < 1.0:
+            raise ValueError("cem.momentum must lie in [0, 1), got %r" % (momentum,))
+        if not 0.0 <= self.min_std < float("inf"):
+            raise ValueError("cem.min_std must be finite and >= 0, got %r" % (min_std,))
+        if proposal not in ("generator", "uniform"):
+            raise ValueError("cem.proposal must be 'generator' or 'uniform', got %r" % (proposal,))
+        self.proposal = proposal
+        self.low, self.high = four(low, "low"), four(high, "high")
+        if any(lo > hi for lo, hi in zip(self.low, self.high)):
+            raise ValueError("cem.low must not exceed cem.high, got %r and %r" % (self.low, self.high))
+
+    @classmethod
+    def from_config(cls, mapping):
+        """The optional `mpc.cem` mapping of a config (keys: the fields' names); absent or empty: None, the planner off."""
+        if mapping is None or (hasattr(mapping, "__len__") and len(mapping) == 0):
+            return None
+        if not hasattr(mapping, "keys"):
+            raise ValueError("mpc.cem must be a mapping of %s, got %r" % (", ".join(cls.FIELDS), mapping))
+        unknown = sorted(set(mapping.keys()) - set(cls.FIELDS))
+        if unknown:
+            raise ValueError("mpc.cem has unknown keys %s (known: %s)" % (unknown, ", ".join(cls.FIELDS)))
+        return cls(**{k: mapping[k] for k in mapping.keys()})
+
+    def elite_count(self, rollouts):
+        r = int(rollouts)
+        if r < 2 or r > _capi.MAX_SAMPLES:
+            raise ValueError("the cross-entropy planner needs 2..%d rollouts, got %d" % (_capi.MAX_SAMPLES, r))
+        e = max(1, r // 4) if self.elites is None else self.elites
+        if e > r:
+            raise ValueError("cem.elites=%d exceeds the %d rollouts" % (e, r))
+        return e
+
+    def __repr__(self):
+        return "CemSettings(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f in self.FIELDS)
+
+
+CEM_MAX_HORIZON = 32
+
+
+def cem_normal_floats(batch, rollouts, horizon, iterations, seq_length=None):
+    """Standard normal floats the planner consumes with `cem`: iterations * steps * B * R * 4 per planning step.
+    seq_length None: one plan_step call (steps = Th); otherwise one mpc_plan call on T = seq_length frames, whose
+    planning step i has steps = min(Th, T - 1 - i)."""
+    per = int(iterations) * int(batch) * int(rollouts) * 4
+    if seq_length is None:
+        return per * int(horizon)
+    t1 = int(seq_length) - 1
+    return per * sum(min(int(horizon), t1 - i) for i in range(t1))
+
+
+def cem_from_config(config, rollouts=None, horizon=None):
+    """The CemSettings of a config's optional `mpc.cem` mapping, checked against mpc.rollouts and mpc.time_horizon;
+    None when the key is absent."""
+    mpc = config.get("mpc") if hasattr(config, "get") else None
+    cem = CemSettings.from_config(mpc.get("cem") if mpc is not None and hasattr(mpc, "get") else None)
+    if cem is not None:
+        _cem_check(cem, int(mpc.rollouts) if rollouts is None else rollouts,
+                   int(mpc.time_horizon) if horizon is None else horizon)
+    return cem
+
+
+def _cem_check(cem, rollouts, horizon):
+    if not isinstance(cem, CemSettings):
+        raise TypeError("cem must be an evaluation.CemSettings, got %r" % (cem,))
+    cem.elite_count(rollouts)
+    if int(horizon) > CEM_MAX_HORIZON:
+        raise ValueError("the cross-entropy planner takes a horizon of at most %d, got %d" % (CEM_MAX_HORIZON, int(horizon)))
+
+
+def _cem_normal(models, normal, need, seed):
+    if normal is None:
+        return models.normal(need, seed)
+    if normal.numel() != need:
+        raise ValueError("normal has %d floats, the planner needs %d" % (normal.numel(), need))
+    return normal.reshape(-1).to(models.device, non_blocking=True).float()
+
+
+def _cem_population0(models, cem, state, goal_code, b, r, steps, noise, rep):
+    """Population 0 of one planning step from `state` [B,3,128,128]: the action sequences seq [steps,B,R,4] and what
+    they lead to (the last predictions, the ts = 0 predictions).  noise: the step's `steps` pieces of B * R * nz floats.
+    "generator": mpc_plan's closed-loop rollouts, launch for launch.  "uniform": low + (high - low) * u, where component
+    c of row i at horizon step ts reads float c % nz of that row's piece (nz >= 4: four independent draws)."""
+    nz, br, dev = models.noise_dim, b * r, models.device
+    seq = torch.empty(steps, b, r, 4, dtype=torch.float32, device=dev)
+    rep.view(b, r, IMAGE_VALUES).copy_(state.view(b, 1, IMAGE_VALUES).expand(b, r, IMAGE_VALUES))
+    if cem.proposal == "uniform":
+        low = torch.tensor(cem.low, dtype=torch.float32).to(dev, non_blocking=True)
+        high = torch.tensor(cem.high, dtype=torch.float32).to(dev, non_blocking=True)
+        u = noise[:steps * br * nz].view(steps, b, r, nz)
+        u = torch.cat([u] * ((3 + nz) // nz), dim=3)[..., :4]   # component c reads float c % nz
+        torch.addcmul(low, u, high - low, out=seq)
+        torch.minimum(seq, high, out=seq)                       # low + (high - low) * u can round past high
+        pred = pred0 = models.forward(rep, seq[0].view(br, 4))
+        for ts in range(1, steps):
+            pred = models.forward(pred, seq[ts].view(br, 4))
+        return seq, pred, pred0
+    code_in = models.g_input(models.encode(state), r, goal_code, r, br)
+    act0 = models.generate(code_in, noise[:br * nz])
+    seq[0].view(br, 4).copy_(act0)
+    pred = pred0 = models.forward(rep, act0)
+    for ts in range(1, steps):
+        code_in = models.g_input(models.encode(pred), 1, goal_code, r, br)
+        act = models.generate(code_in, noise[ts * br * nz:(ts + 1) * br * nz])
+        seq[ts].view(br, 4).copy_(act)
+        pred = models.forward(pred, act)
+    return seq, pred, pred0
+
+
+def _cem_step(models, cem, state, goal, goal_code, b, r, steps, noise, normal, rep, forced, out_err, out_choice, out_act,
+              pred_out, curve, best):
+    """One planning step with `cem`: population 0, then `iterations` x (ndp_plan_cem_update, `steps` open-loop forward
+    passes on the B * R rows, ndp_eval_score_select).  The last selection (the only one `forced` applies to) fills
+    out_err [B,R], out_choice [B], out_act [B,4] and pred_out (or None) exactly as the planner without `cem` does;
+    curve [I+1,B] receives the chosen row's error per population, best [B] the least of them.  Returns (the last
+    population [steps,B,R,4], mean, std [B,steps,4])."""
+    dev, br, its = models.device, b * r, cem.iterations
+    seq, pred, pred0 = _cem_population0(models, cem, state, goal_code, b, r, steps, noise, rep)
+    mean = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
+    std = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
+    if its:
+        err = torch.empty(b, r, dtype=torch.float32, device=dev)
+        pick = torch.empty(b, dtype=torch.int32, device=dev)
+        act = torch.empty(b, 4, dtype=torch.float32, device=dev)
+        per = steps * br * 4
+    for it in range(its):
+        models.score_select(pred, b, r, goal, seq[0], None, None, err, pick, act, None)
+        curve[it].copy_(err.gather(1, pick.long().view(b, 1)).view(b))
+        nxt = torch.empty_like(seq)
+        models.cem_update(err, seq, normal[it * per:(it + 1) * per], cem, it == 0, mean, std, nxt, best)
+        seq = nxt
+        rep.view(b, r, IMAGE_VALUES).copy_(state.view(b, 1, IMAGE_VALUES).expand(b, r, IMAGE_VALUES))
+        pred = pred0 = models.forward(rep, seq[0].view(br, 4))
+        for ts in range(1, steps):
+            pred = models.forward(pred, seq[ts].view(br, 4))
+    models.score_select(pred, b, r, goal, seq[0], pred0 if pred_out is not None else None, forced, out_err, out_choice,
+                        out_act, pred_out)
+    curve[its].copy_(out_err.gather(1, out_choice.long().view(b, 1)).view(b))
+    if its:
+        torch.fmin(best, curve[its], out=best)
+    else:
+        best.copy_(curve[0])
+    return seq, mean, std
+
+
 def mpc_noise_floats(batch, seq_length, rollouts, horizon, noise_dim):
     """Floats of noise one mpc_plan call consumes: B * R * nz per horizon step."""
     t1 = int(seq_length) - 1
     return sum(min(int(horizon), t1 - i) for i in range(t1)) * int(batch) * int(rollouts) * int(noise_dim)
 
 
-def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=None, seed=0, on_step=None):
+def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=None, seed=0, on_step=None, cem=None,
+             normal=None):
     """mpc_eval.py:112-184 for B trajectories at once, rows [B][R].
 
     frames [B,T,3,128,128] float or [B,T,128,128,3] bytes, actions [B,T,4].  noise: None (device draws of
@@ -320,10 +528,19 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     predictions (mpc_eval.py:131); score against the GOAL image (:161), choose (:159-165), and the chosen rollout's
     ts = 0 prediction is the next state (:167-169).  Nothing synchronises with the host.  Returns device tensors:
     choices [T-1,B] int32, rollout_errors [T-1,B,R], actions [B,T-1,4], image_errors [T-1,B], image_error_sum [B],
-    action_error [B]."""
+    action_error [B].
+
+    cem: None, or a CemSettings: every planning step refines its population by `cem.iterations` rounds of the
+    cross-entropy method before it chooses (_cem_step; `choices` replace the last selection only); with 0 iterations and
+    the "generator" proposal every result above has the bits of the call without `cem`.  normal: None (device draws of
+    ndp_normal_noise with `seed`), or the flat stream [planning step][iteration][steps,B,R,4] (cem_normal_floats(B, R,
+    Th, I, seq_length=T) floats).  Added results: best_curve [T-1,I+1,B] the chosen row's error per population, best_err
+    [T-1,B] the least of them, cem_mean / cem_std [B,steps,4] the last planning step's fit (zeros with 0 iterations)."""
     r, th = int(rollouts), int(horizon)
     if r < 1 or th < 1:
         raise ValueError("rollouts and horizon must be >= 1, got %d, %d" % (r, th))
+    if cem is not None:
+        _cem_check(cem, r, th)
     imgs, b, t = _frames(models, frames)
     t1, nz, br = t - 1, models.noise_dim, b * r
     if t1 < 1:
@@ -354,10 +571,28 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     fut_idx = (torch.arange(b, device=dev, dtype=torch.int32) * t).view(1, b) + \
         torch.arange(1, t, device=dev, dtype=torch.int32).view(t1, 1)      # frame image_num + 1 of every trajectory
     off = 0
+    if cem is not None:
+        normal = _cem_normal(models, normal, cem_normal_floats(b, r, th, cem.iterations, seq_length=t), seed)
+        curve = torch.empty(t1, cem.iterations + 1, b, dtype=torch.float32, device=dev)
+        best = torch.empty(t1, b, dtype=torch.float32, device=dev)
+        n_off = 0
     for image_num in range(t1):
         if on_step is not None:
             on_step(image_num)
         steps = min(th, t1 - image_num)                                    # mpc_eval.py:131
+        if cem is not None:
+            nxt = torch.empty(b, 3, 128, 128, dtype=torch.float32, device=dev)
+            n_need = cem.iterations * steps * br * 4
+            _, cem_mean, cem_std = _cem_step(
+                models, cem, state, goal, goal_code, b, r, steps, noise[off:off + steps * br * nz],
+                normal[n_off:n_off + n_need], rep, None if forced is None else forced[image_num], out_err[image_num],
+                out_choice[image_num], out_act[image_num], nxt, curve[image_num], best[image_num])
+            off += steps * br * nz
+            n_off += n_need
+            state = nxt
+            models.mse(state, imgs, b, IMAGE_VALUES, b_idx=fut_idx[image_num], out=image_errors[image_num],
+                       acc=image_error_sum)
+            continue
         code_in = models.g_input(models.encode(state), r, goal_code, r, br)
         act0 = models.generate(code_in, noise[off:off + br * nz])
         off += br * nz
@@ -378,8 +613,11 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     chosen = out_act.transpose(0, 1).contiguous()                         # torch.cat(best_action_list), :178
     want = actions.to(dev).float()[:, :t1].contiguous()
     action_error = models.mse(want, chosen, b, t1 * 4)
-    return {"choices": out_choice, "rollout_errors": out_err, "actions": chosen, "image_errors": image_errors,
-            "image_error_sum": image_error_sum, "action_error": action_error}
+    res = {"choices": out_choice, "rollout_errors": out_err, "actions": chosen, "image_errors": image_errors,
+           "image_error_sum": image_error_sum, "action_error": action_error}
+    if cem is not None:
+        res.update(best_curve=curve, best_err=best, cem_mean=cem_mean, cem_std=cem_std)
+    return res
 
 
 # ---------------------------------------------------------------------- one observation in, one action out
@@ -388,7 +626,7 @@ def plan_step_noise_floats(batch, rollouts, horizon, noise_dim):
     return int(horizon) * int(batch) * int(rollouts) * int(noise_dim)
 
 
-def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, seed=0, choice=None):
+def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, seed=0, choice=None, cem=None, normal=None):
     """One planning step of MPC_gym_eval.py:183-225 for B environments at once, rows [B][R]: from the observed `state`
     [B,3,128,128], R rollouts of Th steps through encoder, generator and forward model, scored against the goal image.
 
@@ -400,10 +638,18 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
     ts = 0.  noise: None (device draws of ndp_uniform_noise with `seed`), or the Th pieces [B*R, nz] in order
     (plan_step_noise_floats(...) floats; at B = 1 the reference's draws, noise kind "mpc_gym").  choice: None, or [B]
     int32 indices that replace the rule.  No host synchronisation when the inputs are on the device.  Returns device
-    tensors (action [B,4], choice [B] int32, rollout_errors [B,R], actions0 [B,R,4])."""
+    tensors (action [B,4], choice [B] int32, rollout_errors [B,R], actions0 [B,R,4]).
+
+    cem: None, or a CemSettings: `cem.iterations` rounds of the cross-entropy method refine the population before the
+    choice (_cem_step; `choice` replaces the last selection only).  normal: None (device draws of ndp_normal_noise with
+    `seed`), or the flat stream [iteration][Th,B,R,4] (cem_normal_floats(B, R, Th, I) floats).  With `cem` a fifth
+    value follows the four, which describe the last population: a dict of best_curve [I+1,B], best_err [B], cem_mean and
+    cem_std [B,Th,4]; with 0 iterations and the "generator" proposal the four have the bits of the call without `cem`."""
     r, th = int(rollouts), int(horizon)
     if r < 1 or th < 1:
         raise ValueError("rollouts and horizon must be >= 1, got %d, %d" % (r, th))
+    if cem is not None:
+        _cem_check(cem, r, th)
     if state.dim() != 4 or tuple(state.shape[1:]) != (3, 128, 128) or tuple(goal.shape) != tuple(state.shape):
         raise _capi.NdpError("state and goal must both be [B,3,128,128], got %s and %s"
                              % (tuple(state.shape), tuple(goal.shape)))
@@ -422,6 +668,17 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
     if choice is not None:
         forced = torch.as_tensor(choice, dtype=torch.int32).reshape(b).to(dev, non_blocking=True)
     state = state.contiguous()
+    if cem is not None:
+        normal = _cem_normal(models, normal, cem_normal_floats(b, r, th, cem.iterations), seed)
+        rep = torch.empty(br, 3, 128, 128, dtype=torch.float32, device=dev)
+        err = torch.empty(b, r, dtype=torch.float32, device=dev)
+        pick = torch.empty(b, dtype=torch.int32, device=dev)
+        action = torch.empty(b, 4, dtype=torch.float32, device=dev)
+        curve = torch.empty(cem.iterations + 1, b, dtype=torch.float32, device=dev)
+        best = torch.empty(b, dtype=torch.float32, device=dev)
+        seq, mean, std = _cem_step(models, cem, state, goal.contiguous(), goal_code, b, r, th, noise, normal, rep, forced,
+                                   err, pick, action, None, curve, best)
+        return action, pick, err, seq[0], {"best_curve": curve, "best_err": best, "cem_mean": mean, "cem_std": std}
     code_in = models.g_input(models.encode(state), r, goal_code, r, br)
     act0 = models.generate(code_in, noise[:br * nz])
     rep = torch.empty(br, 3, 128, 128, dtype=torch.float32, device=dev)
@@ -452,11 +709,17 @@ class MpcController:
     back, because the environment needs them.  `info`: state_u8 [B,128,128,3] (what MPC_gym_eval.get_state resizes to),
     state [B,3,128,128], rollout_errors [B,R], choice [B], actions0 [B,R,4], all on the device."""
 
-    def __init__(self, models, rollouts, horizon, frame_shape=None, seed=0):
+    def __init__(self, models, rollouts, horizon, frame_shape=None, seed=0, cem=None, normal=None):
         from .resize import LanczosResizer
         self.models, self.rollouts, self.horizon = models, int(rollouts), int(horizon)
         if self.rollouts < 1 or self.horizon < 1:
             raise ValueError("rollouts and horizon must be >= 1")
+        if cem is not None:
+            _cem_check(cem, self.rollouts, self.horizon)
+        # cem: a CemSettings turns plan_step's cross-entropy refinement on for every plan(); `info` then also carries
+        # best_curve, best_err, cem_mean, cem_std.  normal: None (device draws, seeded as the noise is), or the flat
+        # stream of successive plan() calls since reset(), [call][iteration][Th,B,R,4]; plan(normal=) overrides it
+        self.cem, self.normal = cem, normal
         self.resizer = LanczosResizer(models.device)
         self.frame_shape = None                               # None: the first frame tells
         if frame_shape is not None:
@@ -508,26 +771,35 @@ class MpcController:
                 self._upload_pending = True
         return self.resizer(raw)
 
-    def plan(self, state, noise=None, choice=None):
+    def plan(self, state, noise=None, choice=None, normal=None):
         """plan_step on `state` and the goal of reset(), then the one host synchronisation.  Returns (actions [B,4] on
         the host, info)."""
         if noise is None:
             seed = self.seed + self.steps
         else:
             seed = 0
-        action, pick, err, act0 = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts, self.horizon,
-                                            noise=noise, seed=seed, choice=choice)
+        extra = {}
+        if self.cem is None:
+            action, pick, err, act0 = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts, self.horizon,
+                                                noise=noise, seed=seed, choice=choice)
+        else:
+            if normal is None and self.normal is not None:
+                per = cem_normal_floats(int(state.shape[0]), self.rollouts, self.horizon, self.cem.iterations)
+                normal = self.normal.reshape(-1)[self.steps * per:(self.steps + 1) * per]
+            action, pick, err, act0, extra = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts,
+                                                       self.horizon, noise=noise, seed=self.seed + self.steps, choice=choice,
+                                                       cem=self.cem, normal=normal)
         self.steps += 1
         with _capi.on_device(self.models.device):
             self._actions.copy_(action, non_blocking=True)
             self._event.record()
         self._event.synchronize()                             # the environment needs the action
         self._upload_pending = False                          # the frames' upload came before it on the stream
-        return self._actions.clone(), {"state": state, "action": action, "rollout_errors": err, "choice": pick, "actions0": act0}
+        return self._actions.clone(), dict(extra, state=state, action=action, rollout_errors=err, choice=pick, actions0=act0)
 
-    def act(self, raw_frames, noise=None, choice=None):
+    def act(self, raw_frames, noise=None, choice=None, normal=None):
         state_u8, state = self.observe(raw_frames)
-        actions, info = self.plan(state, noise=noise, choice=choice)
+        actions, info = self.plan(state, noise=noise, choice=choice, normal=normal)
         info["state_u8"] = state_u8
         return actions, info
 
