@@ -818,6 +818,66 @@ int ndp_plan_cem_update(const float *err, const float *seq_in, const float *norm
                         int32_t *elite_idx, void *stream);
 int ndp_normal_noise(float *out, int64_t n, uint64_t seed, const int32_t *offset_dev, void *stream);
 
+/* --------------------------------------------------------------- push world ---
+ * A small FetchPush-like world of the project's own (push_world.py): a gripper, a block and a goal
+ * on a table, the reference's 4-component actions, n environments at once.  The world is in metres.
+ *
+ * State per environment: fp32 state[8] = gx, gy, gz, ox, oy, oz, tx, ty -- gripper xyz, object xyz, goal xy.  oz (0.425)
+ * and the goal never change in a step. */
+#define NDP_WORLD_X0        1.09     /* the table window: [X0, X0 + SIDE] x [Y0, Y0 + SIDE] */
+#define NDP_WORLD_Y0        0.50
+#define NDP_WORLD_SIDE      0.50
+#define NDP_WORLD_REST_X    1.34     /* gripper rest position */
+#define NDP_WORLD_REST_Y    0.75
+#define NDP_WORLD_Z_MIN     0.42     /* gripper height range */
+#define NDP_WORLD_Z_MAX     0.60
+#define NDP_WORLD_Z_CONTACT 0.47     /* below this height the gripper touches the block */
+#define NDP_WORLD_OBJECT_Z  0.425
+#define NDP_WORLD_R_G       0.02     /* gripper radius */
+#define NDP_WORLD_R_O       0.03     /* object radius */
+#define NDP_WORLD_R         (NDP_WORLD_R_G + NDP_WORLD_R_O)   /* contact distance */
+#define NDP_WORLD_STEP      0.05     /* move per step at full action */
+#define NDP_WORLD_SUB       4        /* substeps per step */
+#define NDP_WORLD_RING      0.008    /* width of the goal ring */
+#define NDP_WORLD_SHADOW    0.6      /* shadow offset per metre of height above Z_MIN, in both axes */
+/* Step.  All arithmetic is fp64 on the fp32 inputs, every operation rounded on its own (no contraction), the results
+ * rounded to fp32 once at the end.  clamp(v, lo, hi) is v < lo ? lo : (v > hi ? hi : v).
+ *     a_c = NaN -> 0;  m = STEP * clamp(a[0:3], -1, 1) / SUB         a[3] is ignored (FetchPush locks the fingers)
+ *     SUB times:
+ *         g = clamp(g + m) to [X0, X0+SIDE] x [Y0, Y0+SIDE] x [Z_MIN, Z_MAX]
+ *         if g.z < Z_CONTACT:
+ *             d = o.xy - g.xy;  r2 = d.x*d.x + d.y*d.y
+ *             if r2 < R*R:
+ *                 f = R / sqrt(r2);  o.xy = r2 > 0 ? (g.x + d.x*f, g.y + d.y*f) : (g.x + R, g.y)
+ *                 clamp o.xy to [X0+R_O, X0+SIDE-R_O] x [Y0+R_O, Y0+SIDE-R_O]
+ * A raised gripper passes over the block; a block pushed against the wall stays there and the gripper may overlap it; a
+ * gripper that descends onto the block pushes it out sideways.
+ *
+ * Render.  Frames are S x S bytes HWC (row py, column px, RGB), S a multiple of 4, 32 <= S <= 1024.  One quantisation,
+ * then integers: q(v) = llrint(v * (16 * S / SIDE)) in fp64, round-half-even, v * scale saturated to [-8192, 24576]
+ * first (NaN: -8192) so that int32 holds every squared distance; the unit is a sixteenth of a pixel.  Centres are
+ * (q(x - X0), q(y - Y0)); radii are q(radius).
+ * Coverage: pixel (px, py) has 16 sample points (16 px + 2 + 4 i, 16 py + 2 + 4 j), i, j in 0..3.  A sample is inside a
+ * disc iff dx^2 + dy^2 <= r^2, inside a ring iff rin^2 <= dx^2 + dy^2 <= rout^2; k = the samples inside, 0..16.
+ * Blend, per channel and in this order, c = (c * (16 - k) + fg * k + 8) >> 4:
+ *   1 table    (168, 160, 150), minus 12 on each channel where ((px / (S/8)) + (py / (S/8))) & 1 (integer divisions)
+ *   2 goal     ring about t, rout = R_O, rin = R_O - RING, colour (40, 200, 60)
+ *   3 shadow   disc R_G about (g.x + SHADOW * (g.z - Z_MIN), g.y + SHADOW * (g.z - Z_MIN)), fg = (c * 10 + 8) >> 4 of
+ *              the colour under it
+ *   4 object   disc R_O about o.xy, colour (20, 20, 235)
+ *   5 gripper  disc of radius R_G * (1 + (g.z - Z_MIN) / (Z_MAX - Z_MIN)) about g.xy, colour (250, 245, 10)
+ * Shapes at the window's edge are clipped by the frame.
+ *
+ *   ndp_world_step_render  state_in [n][8], actions [n][4] -> state_out [n][8] (not state_in) and, unless frames_hwc is
+ *                          NULL, the frames [n][S][S][3] of the NEW state; one launch
+ *   ndp_world_render       the frames of a given state; one launch
+ * size as above, 1 <= n <= 65535, frames_hwc 4-byte aligned.  A bad size or n, a null required pointer, state_out ==
+ * state_in: NDP_E_ARG, nothing launched.  No atomics, no scratch memory, no host synchronisation: two calls give the same
+ * bits.  The caller owns every buffer. */
+int ndp_world_step_render(const float *state_in, const float *actions, int64_t n, int size, float *state_out,
+                          uint8_t *frames_hwc, void *stream);
+int ndp_world_render(const float *state, int64_t n, int size, uint8_t *frames_hwc, void *stream);
+
 /* ------------------------------------------------------------ measurement ---
  * Per-kernel timing for bench.py: while enabled (per host thread) every kernel
  * this library launches is bracketed by hipEvents recorded on the stream it is

@@ -182,6 +182,8 @@ SIGNATURES = {
                                     POINTER(c_float), POINTER(c_float), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
     "ndp_normal_noise": (c_int, [c_void_p, c_int64, c_uint64, c_void_p, c_void_p]),
+    "ndp_world_step_render": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "ndp_world_render": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),
     "ndp_timing_enable": (c_int, [c_int]),
     "ndp_timing_collect": (c_int, [ctypes.c_char_p, c_int, POINTER(c_float), POINTER(c_int32), c_int]),
 }

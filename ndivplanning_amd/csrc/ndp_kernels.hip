@@ -1882,3 +1882,4 @@ __global__ __launch_bounds__(kThreads) void k_philox(float* out, int64_t n, uint
 #include "ndp_resize.inc"
 #include "ndp_store.inc"
 #include "ndp_plan.inc"
+#include "ndp_world.inc"

@@ -1,0 +1,255 @@
+"""The push world (include/ndp.h, "push world") restated in numpy from the header's words: the step in fp64, the render
+in integers after the one quantisation.  Nothing here is shared with the library, so a result is compared bit for bit
+and needs no tolerance.  Also the case list the CPU and GPU tests share, the packing of tests/host_drivers/world_main.hip's
+files, and the starts (push_world.starts: the only starts there are; their properties are pinned in
+tests/test_push_world.py)."""
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+X0, Y0, SIDE = 1.09, 0.50, 0.50
+REST = (1.34, 0.75)
+Z_MIN, Z_MAX, Z_CONTACT = 0.42, 0.60, 0.47
+OBJECT_Z = 0.425
+R_G, R_O = 0.02, 0.03
+R = R_G + R_O
+STEP, SUB = 0.05, 4
+RING, SHADOW = 0.008, 0.6
+Q_MIN, Q_MAX = -8192, 24576
+TABLE = (168, 160, 150)
+GOAL_RGB, OBJECT_RGB, GRIPPER_RGB = (40, 200, 60), (20, 20, 235), (250, 245, 10)
+
+
+def clamp(v, lo, hi):
+    return np.where(v < lo, lo, np.where(v > hi, hi, v))
+
+
+def step(state, actions):
+    """state [n,8], actions [n,4] float32 -> the successor states [n,8] float32."""
+    s = np.asarray(state, np.float32).reshape(-1, 8)
+    a = np.asarray(actions, np.float32).reshape(-1, 4)
+    g = s[:, 0:3].astype(np.float64)
+    o = s[:, 3:5].astype(np.float64)
+    ac = a[:, 0:3].astype(np.float64)
+    ac = clamp(np.where(np.isnan(ac), 0.0, ac), -1.0, 1.0)
+    m = STEP * ac / SUB
+    g_lo, g_hi = np.array([X0, Y0, Z_MIN]), np.array([X0 + SIDE, Y0 + SIDE, Z_MAX])
+    o_lo, o_hi = np.array([X0 + R_O, Y0 + R_O]), np.array([X0 + SIDE - R_O, Y0 + SIDE - R_O])
+    for _ in range(SUB):
+        g = clamp(g + m, g_lo, g_hi)
+        d = o - g[:, 0:2]
+        r2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]
+        touch = (g[:, 2] < Z_CONTACT) & (r2 < R * R)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            f = R / np.sqrt(r2)
+            apart = np.stack([g[:, 0] + d[:, 0] * f, g[:, 1] + d[:, 1] * f], axis=1)
+        centred = np.stack([g[:, 0] + R, g[:, 1]], axis=1)
+        pushed = clamp(np.where((r2 > 0)[:, None], apart, centred), o_lo, o_hi)
+        o = np.where(touch[:, None], pushed, o)
+    out = s.copy()
+    out[:, 0:3] = g.astype(np.float32)
+    out[:, 3:5] = o.astype(np.float32)
+    return out
+
+
+def quant(v, size):
+    with np.errstate(invalid="ignore"):
+        s = np.asarray(v, np.float64) * (16.0 * size / SIDE)
+        s = np.where(s >= Q_MIN, s, float(Q_MIN))
+        s = np.where(s > Q_MAX, float(Q_MAX), s)
+    return np.rint(s).astype(np.int64)
+
+
+def scene(state_row, size):
+    """The quantised layers of one state: (cx, cy, rin, rout) per layer, in sixteenths of a pixel."""
+    s = np.asarray(state_row, np.float32).astype(np.float64)
+    lift = s[2] - Z_MIN
+    return {
+        "goal": (quant(s[6] - X0, size), quant(s[7] - Y0, size), quant(R_O - RING, size), quant(R_O, size)),
+        "shadow": (quant(s[0] + SHADOW * lift - X0, size), quant(s[1] + SHADOW * lift - Y0, size), 0, quant(R_G, size)),
+        "object": (quant(s[3] - X0, size), quant(s[4] - Y0, size), 0, quant(R_O, size)),
+        "gripper": (quant(s[0] - X0, size), quant(s[1] - Y0, size), 0, quant(R_G * (1.0 + lift / (Z_MAX - Z_MIN)), size)),
+    }
+
+
+def coverage(layer, size):
+    """k [S,S] (row py, column px): how many of each pixel's 16 samples the layer holds."""
+    cx, cy, rin, rout = (int(v) for v in layer)
+    at = 16 * np.arange(size, dtype=np.int64)[:, None] + 2 + 4 * np.arange(4, dtype=np.int64)[None, :]     # [S,4]
+    dx2 = ((at - cx) ** 2)[None, None, :, :]
+    dy2 = ((at - cy) ** 2)[:, :, None, None]
+    d2 = dx2 + dy2                                                                                         # [py,j,px,i]
+    return ((d2 >= rin * rin) & (d2 <= rout * rout)).sum(axis=(1, 3))
+
+
+def blend(c, fg, k):
+    return (c * (16 - k[:, :, None]) + fg * k[:, :, None] + 8) >> 4
+
+
+def table(size):
+    cell = size // 8
+    idx = np.arange(size) // cell
+    dark = ((idx[None, :] + idx[:, None]) & 1) * 12
+    return np.array(TABLE, np.int64)[None, None, :] - dark[:, :, None]
+
+
+def render_one(state_row, size):
+    sc = scene(state_row, size)
+    c = table(size)
+    c = blend(c, np.array(GOAL_RGB, np.int64), coverage(sc["goal"], size))
+    c = blend(c, (c * 10 + 8) >> 4, coverage(sc["shadow"], size))
+    c = blend(c, np.array(OBJECT_RGB, np.int64), coverage(sc["object"], size))
+    c = blend(c, np.array(GRIPPER_RGB, np.int64), coverage(sc["gripper"], size))
+    assert c.min() >= 0 and c.max() <= 255
+    return c.astype(np.uint8)
+
+
+_render_cache = {}
+
+
+def render(state, size):
+    """state [n,8] float32 -> frames [n,S,S,3] uint8.  Computed once per (state bits, size) and shared."""
+    s = np.ascontiguousarray(np.asarray(state, np.float32).reshape(-1, 8))
+    out = np.empty((s.shape[0], size, size, 3), np.uint8)
+    for i, row in enumerate(s):
+        key = (row.tobytes(), int(size))
+        if key not in _render_cache:
+            _render_cache[key] = render_one(row, size)
+        out[i] = _render_cache[key]
+    return out
+
+
+def starts(kind, seed, indices):
+    from ndivplanning_amd import push_world
+    return push_world.starts(kind, seed, indices)
+
+
+def observation(state):
+    s = np.asarray(state, np.float32).reshape(-1, 8)
+    obs = np.zeros((s.shape[0], 25), np.float32)
+    obs[:, 0:6] = s[:, 0:6]
+    obs[:, 6:9] = s[:, 3:6] - s[:, 0:3]
+    return obs
+
+
+# ---------------------------------------------------------------------------------------------------------------- cases
+def _state(g, o, t):
+    return np.array([g[0], g[1], g[2], o[0], o[1], OBJECT_Z, t[0], t[1]], np.float32)
+
+
+def cases():
+    """[(name, state [8], action [4])]: every branch of the step and every clipping of the render."""
+    f32 = np.float32
+    mid = (X0 + SIDE / 2, Y0 + SIDE / 2)
+    goal = (1.45, 0.85)
+    hi_x, hi_y = X0 + SIDE, Y0 + SIDE
+    sixteenth = 5.0 / 256.0                      # of a pixel at S = 32: 0.5 / 32 / 16 m = STEP * 5 / 256
+    out = [
+        ("r2 == 0", _state((1.30, 0.70, 0.44), (1.30, 0.70), goal), (0, 0, 0, 0)),
+        ("at Z_CONTACT, the fp32 below it", _state((1.30, 0.70, f32(0.47)), (1.32, 0.71), goal), (0, 0, 0, 0)),
+        ("at Z_CONTACT, the fp32 above it", _state((1.30, 0.70, np.nextafter(f32(0.47), f32(1))), (1.32, 0.71), goal),
+         (0, 0, 0, 0)),
+        ("rising out of contact", _state((1.30, 0.70, 0.46), (1.33, 0.70), goal), (1, 0, 1, 0)),
+        ("a NaN action component", _state((1.30, 0.70, 0.44), (1.36, 0.71), goal), (np.nan, 0.5, np.nan, np.nan)),
+        ("actions beyond +-1", _state((1.30, 0.70, 0.50), (1.40, 0.80), goal), (3, -7, 0.2, 9)),
+        ("infinite actions", _state((1.30, 0.70, 0.50), (1.40, 0.80), goal), (np.inf, -np.inf, -np.inf, 0)),
+        ("the block into the wall", _state((hi_x - R_O - 0.005 - R, 0.70, 0.44), (hi_x - R_O - 0.005, 0.70), goal),
+         (1, 0, 0, 0)),
+        ("the block into the corner", _state((X0 + R_O + 0.06, Y0 + R_O + 0.06, 0.44), (X0 + R_O + 0.01, Y0 + R_O + 0.01),
+                                             goal), (-1, -1, 0, 0)),
+        ("across the cornered block", _state((X0 + R_O + 0.045, Y0 + R_O + 0.045, 0.44), (X0 + R_O + 0.01, Y0 + R_O + 0.01),
+                                             goal), (-1, -1, 0, 0)),
+        ("gripper at the left edge", _state((X0, mid[1], 0.44), (1.30, 0.70), goal), (-1, 0, 0, 0)),
+        ("gripper at the right edge", _state((hi_x, mid[1], 0.60), (1.30, 0.70), goal), (1, 0, 1, 0)),
+        ("gripper at the top edge", _state((mid[0], Y0, 0.42), (1.30, 0.70), goal), (0, -1, -1, 0)),
+        ("gripper at the bottom edge", _state((mid[0], hi_y, 0.60), (1.30, 0.70), goal), (0, 1, 0, 0)),
+        ("gripper in corner 00", _state((X0, Y0, 0.53), (1.30, 0.70), goal), (-1, -1, 0, 0)),
+        ("gripper in corner 10", _state((hi_x, Y0, 0.60), (1.30, 0.70), goal), (1, -1, 0, 0)),
+        ("gripper in corner 01", _state((X0, hi_y, 0.60), (1.30, 0.70), goal), (-1, 1, 0, 0)),
+        ("gripper in corner 11", _state((hi_x, hi_y, 0.60), (1.30, 0.70), goal), (1, 1, 1, 0)),
+        ("raised over the block", _state((1.30, 0.70, 0.55), (1.30, 0.70), goal), (0.3, 0, 0, 0)),
+        ("descending onto the block", _state((1.30, 0.70, 0.48), (1.31, 0.705), goal), (0, 0, -1, 0)),
+        ("goal and block coincide", _state((1.20, 0.60, 0.53), (1.40, 0.80), (1.40, 0.80)), (0.5, 0.5, 0, 0)),
+        ("a sixteenth of a pixel", _state((1.25, 0.75, 0.44), (1.35, 0.80), goal), (sixteenth, 0, 0, 0)),
+        ("two sixteenths down", _state((1.25, 0.75, 0.44), (1.35, 0.80), goal), (0, 2 * sixteenth, 0, 0)),
+        ("three sixteenths, pushing", _state((1.25, 0.75, 0.44), (1.25 + R, 0.75), goal), (3 * sixteenth, sixteenth, 0, 0)),
+        ("a plain diagonal push", _state((1.30, 0.70, 0.44), (1.33, 0.735), goal), (0.8, 0.9, 0, 0)),
+        ("a state from outside the window", _state((0.90, 1.20, 0.70), (1.00, 0.40), (1.70, 0.30)), (1, -1, 0, 0)),
+        ("the block under the goal ring and the shadow", _state((1.40, 0.80, 0.50), (1.45, 0.85), goal), (0, 0, 0, 0)),
+    ]
+    return [(name, st, np.array(ac, np.float32)) for name, st, ac in out]
+
+
+def case_arrays(count=None):
+    """(states [m,8], actions [m,4]) of the cases, repeated cyclically to `count` rows."""
+    cs = cases()
+    m = len(cs) if count is None else int(count)
+    states = np.stack([cs[i % len(cs)][1] for i in range(m)])
+    actions = np.stack([cs[i % len(cs)][2] for i in range(m)])
+    return states, actions
+
+
+# ---------------------------------------------------------------------------------------- the host driver's two files
+HOST_SIZES = (32, 36, 128)
+
+
+def host_runs():
+    """[(size, with_frames, states [n,8], actions [n,4])]: every case at every size in runs of n = 3, every case alone
+    (n = 1) at S = 32, and one run that steps without frames."""
+    states, actions = case_arrays()
+    m = len(states)
+    runs = []
+    for size in HOST_SIZES:
+        for lo in range(0, m, 3):
+            idx = [(lo + k) % m for k in range(3)]
+            runs.append((size, 1, states[idx], actions[idx]))
+    for i in range(m):
+        runs.append((32, 1, states[i:i + 1], actions[i:i + 1]))
+    runs.append((36, 1, states[3:4], actions[3:4]))
+    runs.append((128, 1, states[7:8], actions[7:8]))
+    runs.append((32, 0, states[0:3], actions[0:3]))
+    return runs
+
+
+def pack(runs):
+    parts = [np.array([len(runs)], "<i4").tobytes()]
+    for size, with_frames, states, actions in runs:
+        parts.append(np.array([len(states), size, with_frames], "<i4").tobytes())
+        parts.append(np.ascontiguousarray(states, "<f4").tobytes())
+        parts.append(np.ascontiguousarray(actions, "<f4").tobytes())
+    return b"".join(parts)
+
+
+def unpack(runs, raw):
+    """Per run {state_out [n,8], step_frames (None without frames), render_frames [n,S,S,3]}."""
+    at, out = 0, []
+    for size, with_frames, states, _ in runs:
+        n = len(states)
+        px = n * size * size * 3
+        got = {"state_out": np.frombuffer(raw, "<f4", n * 8, at).reshape(n, 8)}
+        at += 4 * n * 8
+        got["step_frames"] = None
+        if with_frames:
+            got["step_frames"] = np.frombuffer(raw, np.uint8, px, at).reshape(n, size, size, 3)
+            at += px
+        got["render_frames"] = np.frombuffer(raw, np.uint8, px, at).reshape(n, size, size, 3)
+        at += px
+        out.append(got)
+    assert at == len(raw), (at, len(raw))
+    return out
+
+
+def bits_equal(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def ulp_distance(a, b):
+    """Per component, the distance in fp32 ulps between two finite arrays (0: the same bits or +-0)."""
+    def key(x):
+        i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7FFFFFFF), i)
+    return np.abs(key(a) - key(b))
