@@ -12,7 +12,6 @@ also writes the reference's bytes, `denorm(...).astype(np.uint8)` of train_autoe
 error against the input).  Both modules are used in eval mode; there is no CPU path (`NdpError`), and nothing here
 synchronises with the host: every result is a device tensor.  evaluate(quality=True) / --quality add SSIM and PSNR of
 every reconstruction against its input (`ndp_image_quality`, image_quality.py); off by default, nothing else changes."""
-import importlib
 import os
 from argparse import ArgumentParser
 
@@ -21,28 +20,9 @@ import torch
 from . import _capi
 from . import image_quality as IQ
 from . import jpeg as jpeg_frames
+from ._eval_io import OUTPUTS, _check_out, _require_eval, _require_gpu, _to_bytes, fp64_mean, load_module  # noqa: F401
+from ._eval_io import trajectory_batches
 from .models import image_autoencoder as IA
-
-OUTPUTS = ("float", "bytes")
-
-
-def _check_out(out):
-    if out not in OUTPUTS:
-        raise ValueError("out must be 'float' or 'bytes', got %r" % (out,))
-
-
-def _require_gpu(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("%s must be a torch.Tensor" % name)
-    if not t.is_cuda:
-        raise _capi.NdpError("%s is on %s: ndivplanning_amd computes only on a ROCm GPU (no CPU fallback)" % (name, t.device))
-    return t
-
-
-def _require_eval(**modules):
-    for name, m in modules.items():
-        if m.training:
-            raise _capi.NdpError("the %s is in training mode: call .eval() first (these are the eval-mode kernels)" % name)
 
 
 def decode(decoder, codes, out="float"):
@@ -70,20 +50,6 @@ def reconstruct(encoder, decoder, images, out="float", errors=True):
     return IA.decoder_forward_hip(decoder, codes, out=out, target=images if errors else None, errors=errors)
 
 
-def _batches(dataset, batch_size, device, jpeg_decoder):
-    """The dataset's frames, `batch_size` trajectories at a time, as the kernels take them: float NCHW, or byte frames
-    for a dataset that yields bytes or JPEG streams.  The trajectories are read by index in order -- no DataLoader, so
-    no random number of the process is drawn (validation inside a training run must not move its shuffling)."""
-    for lo in range(0, len(dataset), batch_size):
-        items = [dataset[i][0] for i in range(lo, min(lo + batch_size, len(dataset)))]
-        if jpeg_decoder is not None:
-            buffer, offsets = jpeg_frames.pack_jpegs([s for item in items for s in item])
-            yield jpeg_decoder.decode(buffer, offsets)
-        else:
-            frames = torch.stack(items).to(device, non_blocking=True)
-            yield frames.view(-1, *frames.shape[2:]).contiguous()
-
-
 def evaluate(encoder, decoder, dataset, batch_size=16, device=None, keep=0, quality=False):
     """The reconstruction error over every frame of `dataset` (PushDataset / SyntheticPushDataset: images, byte frames or
     JPEG streams, which `jpeg.JpegDecoder` decodes on the device): (mean MSE [1], per-image MSE [frames]) -- device
@@ -99,7 +65,8 @@ def evaluate(encoder, decoder, dataset, batch_size=16, device=None, keep=0, qual
         raise ValueError("evaluate needs a non-empty dataset and batch_size >= 1")
     jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
     per_image, pairs, kept, ssim, psnr = [], [], 0, [], []
-    for frames in _batches(dataset, int(batch_size), device, jpeg_decoder):
+    for frames, _, _ in trajectory_batches(dataset, int(batch_size), device, jpeg_decoder, actions=False):
+        frames = frames.view(-1, *frames.shape[2:])                      # [b*T,...]
         recon, sq, _ = reconstruct(encoder, decoder, frames, out="float" if quality else "bytes", errors=True)
         per_image.append(sq)
         if quality:
@@ -115,7 +82,7 @@ def evaluate(encoder, decoder, dataset, batch_size=16, device=None, keep=0, qual
     if jpeg_decoder is not None:
         jpeg_decoder.finish()
     per_image = torch.cat(per_image)
-    mean = per_image.double().mean().float().view(1)                     # (of the fp32 per-image values, in fp64: as ndp_ae_decode's)
+    mean = fp64_mean(per_image)                                          # (as ndp_ae_decode's)
     result = (mean, per_image)
     if keep > 0:
         result += ((torch.cat([a for a, _ in pairs]), torch.cat([b for _, b in pairs])),)
@@ -123,13 +90,6 @@ def evaluate(encoder, decoder, dataset, batch_size=16, device=None, keep=0, qual
         ssim, psnr = torch.cat(ssim), torch.cat(psnr)
         result += ({"ssim": ssim, "psnr": psnr, "mean_ssim": IQ.mean(ssim), "mean_psnr": IQ.mean(psnr)},)
     return result
-
-
-def _to_bytes(frames):
-    """Input frames as displayable bytes HWC: byte frames as they are, floats denormalised as the reference does."""
-    if frames.dtype == torch.uint8:
-        return frames
-    return (((frames + 1.0) / 2.0) * 255.0).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
 def save_pairs(inputs, recons, save_dir):
@@ -143,17 +103,6 @@ def save_pairs(inputs, recons, save_dir):
             Image.fromarray(frame).save(path)
             paths.append(path)
     return paths
-
-
-def load_module(path, device):
-    """torch.load of a whole-module checkpoint of train_autoencoder.py (a local, trusted file: module pickles need
-    weights_only=False), in eval mode on `device`.  The checkpoints name the classes `models.image_autoencoder.*`: the
-    root-level shim of that name is imported first where it is on sys.path."""
-    try:
-        importlib.import_module("models.image_autoencoder")
-    except ImportError:
-        pass
-    return torch.load(path, map_location="cpu", weights_only=False).to(device).eval()
 
 
 def make_parser():

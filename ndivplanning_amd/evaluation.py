@@ -24,6 +24,7 @@ default, and then nothing here computes anything else than before.
 import torch
 
 from . import _capi, jpeg
+from ._eval_io import config_cli, device_of, load_eval_models  # noqa: F401 (device_of: the scripts read it from here)
 from .models.forward_encoder import pack_module
 from .models.image_autoencoder import pack_encoder_params
 
@@ -919,22 +920,15 @@ def eval_settings(kind, config, dataset, generator=None):
 def make_eval_dataset(config):
     """PushDataset(evaluation_data_path, seq_length=trajectory_length, raw_uint8=True), or `synthetic:<N>:images|frames_u8` seeded
     trajectories as for train_data_path."""
-    from .utils.trajectory_loader import PushDataset, SyntheticPushDataset
-    path = str(config.evaluation_data_path)
-    if path.startswith("synthetic:") or "/synthetic:" in path:
-        spec = path[path.index("synthetic:"):].split(":")
-        mode = spec[2] if len(spec) > 2 else "images"
-        if mode not in ("images", "frames_u8", "jpeg"):
-            raise ValueError("evaluation needs images: use synthetic:<N>:images, synthetic:<N>:frames_u8 or "
-                             "synthetic:<N>:jpeg")
-        return SyntheticPushDataset(int(spec[1]), seq_length=int(config.trajectory_length), mode=mode,
-                                    seed=int(config.random_seed))
+    from .utils.trajectory_loader import open_dataset
     # decoded frames stay bytes (normalised by ndp_eval_frames_u8); `raw_uint8: false` gives the reference's floats;
     # `raw_jpeg: true` yields the JPEG streams, decoded on the device
-    if bool(config.get("raw_jpeg", False)):
-        return PushDataset(config.evaluation_data_path, seq_length=int(config.trajectory_length), raw_jpeg=True)
-    return PushDataset(config.evaluation_data_path, seq_length=int(config.trajectory_length),
-                       raw_uint8=bool(config.get("raw_uint8", True)))
+    frames = {"raw_jpeg": True} if bool(config.get("raw_jpeg", False)) else {"raw_uint8": bool(config.get("raw_uint8", True))}
+    return open_dataset(config.evaluation_data_path, seq_length=int(config.trajectory_length), seed=int(config.random_seed),
+                        default_mode="images", modes=("images", "frames_u8", "jpeg"),
+                        mode_error="evaluation needs images: use synthetic:<N>:images, synthetic:<N>:frames_u8 or "
+                                   "synthetic:<N>:jpeg",
+                        push=dict(seq_length=int(config.trajectory_length), **frames))
 
 
 def script_main(fetch, argv=None, add_arguments=None, prepare=None):
@@ -943,36 +937,20 @@ def script_main(fetch, argv=None, add_arguments=None, prepare=None):
     prepare(namespace): called after parsing and before anything is loaded; what it returns (a tuple, e.g. the parsed
     arguments in front and a live environment behind) is wrapped around fetch's arguments as
     fetch(*before, image_encoder, fwd_model_autoencoder, generator, dataset, config, *after)."""
-    import os
     from argparse import ArgumentParser
 
-    from .utils.argparse_util import override_dotmap
     from .utils.cli_arguments.common_arguments import add_common_arguments
-    from .utils.file import make_paths_absolute
     parser = ArgumentParser(description="Interact with your training script")
     parser = add_common_arguments(parser)
     if add_arguments is not None:
         add_arguments(parser)
-    namespace = parser.parse_args(argv)
-    before, after = prepare(namespace) if prepare is not None else ((), ())
-    config = override_dotmap(namespace, "config_file")
-    config = make_paths_absolute(os.getcwd(), config, log_not_exist=True)
-    if not torch.cuda.is_available():
-        raise _capi.NdpError("evaluation needs a ROCm GPU; there is no CPU path")
-    gpu_id = device_of(config)
+    _, config, wrapped = config_cli(parser, argv, "evaluation", prepare)
+    before, after = wrapped if prepare is not None else ((), ())
     dataset = make_eval_dataset(config)
-    # local, trusted whole-module pickles written by the training scripts: weights_only=False is required
-    image_encoder = torch.load(config.image_encoder_model_path, map_location=gpu_id, weights_only=False)
-    generator = torch.load(config.gan_decoder_model_path, map_location=gpu_id, weights_only=False)
-    fwd_model_autoencoder = torch.load(config.forward_model_autoencoder_path, map_location=gpu_id, weights_only=False)
+    image_encoder, generator, fwd_model_autoencoder, _ = load_eval_models(config)
     result = fetch(*before, image_encoder, fwd_model_autoencoder, generator, dataset, config, *after)
     if len(result) == 2:
         print("avg_action_error, avg_image_loss:", result[0], result[1])
     else:
         print("avg_action_error, avg_image_loss, avg_goal_error, success_rate:", *result)
     return result
-
-
-def device_of(config):
-    gpu = config.gpu_id
-    return torch.device("cuda", gpu) if isinstance(gpu, int) else torch.device(gpu)

@@ -16,7 +16,6 @@ module is used in eval mode; there is no CPU path (`NdpError`), and nothing here
 every result is a device tensor.  quality=True (predict, rollout, evaluate; --quality) adds SSIM and PSNR of the
 same pairs -- prediction against target, start frame against target -- from `ndp_image_quality` (image_quality.py): the MSE
 rewards a blurred prediction, these do not.  Off by default, and nothing else changes with it."""
-import importlib
 import os
 from argparse import ArgumentParser
 
@@ -26,7 +25,8 @@ import torch
 from . import _capi
 from . import image_quality as IQ
 from . import jpeg as jpeg_frames
-from .autoencoder_eval import _check_out, _require_eval, _require_gpu, _to_bytes
+from ._eval_io import _check_out, _require_eval, _require_gpu, _to_bytes, fp64_mean, load_module, trajectory_batches
+from .utils.trajectory_loader import open_dataset
 
 IMAGE = (3, 128, 128)
 FRAME = (128, 128, 3)
@@ -88,10 +88,6 @@ def _forward(fwd_model, state, actions):
         return fwd_model(state, actions.detach().float())
 
 
-def _mean(per_image):
-    return per_image.double().mean().float().view(1)                 # of the fp32 per-image values, in fp64
-
-
 def _quality(pred, base, target, base_idx=None, target_idx=None):
     """(ssim, psnr, persistence_ssim, persistence_psnr): two ndp_image_quality launches, the predictions against their
     targets, then the base frames against the same targets."""
@@ -116,7 +112,7 @@ def predict(fwd_model, state, actions, target=None, out="float", quality=False):
         return ((score(pred, out_bytes=True)[2] if out == "bytes" else pred), None, None, None) + ((None,) * 4 if quality else ())
     err, base_err, pred_u8 = score(pred, target, base=state, out_bytes=out == "bytes")
     extra = _quality(pred, state, target) if quality else ()
-    return ((pred_u8 if out == "bytes" else pred), err, base_err, _mean(err)) + extra
+    return ((pred_u8 if out == "bytes" else pred), err, base_err, fp64_mean(err)) + extra
 
 
 def rollout(fwd_model, state0, actions, targets=None, out="float", quality=False):
@@ -178,24 +174,6 @@ def rollout_schedule(T, horizon=None):
     return steps
 
 
-def _batches(dataset, batch_size, device, jpeg_decoder):
-    """(frames [b*T,...], actions [b,T,4], b) for `batch_size` trajectories at a time: float NCHW, or byte frames for a
-    dataset that yields bytes or JPEG streams.  The trajectories are read by index in order -- no DataLoader, so no
-    random number of the process is drawn (validation inside a training run must not move its shuffling)."""
-    for lo in range(0, len(dataset), batch_size):
-        items = [dataset[i] for i in range(lo, min(lo + batch_size, len(dataset)))]
-        actions = torch.stack([torch.as_tensor(it[2]) for it in items]).to(device, non_blocking=True).float()
-        if jpeg_decoder is not None:
-            buffer, offsets = jpeg_frames.pack_jpegs([s for it in items for s in it[0]])
-            frames = jpeg_decoder.decode(buffer, offsets)
-        else:
-            frames = torch.stack([it[0] for it in items]).to(device, non_blocking=True)
-            frames = frames.view(-1, *frames.shape[2:]).contiguous()
-            if frames.dtype != torch.uint8:
-                frames = frames.float()
-        yield frames, actions, len(items)
-
-
 def _maps(sched, T, b, device):
     """Per step the int32 device index maps of a batch of b trajectories whose frames are rows traj * T + frame:
     (start rows, action rows, target rows), trajectory-major."""
@@ -245,7 +223,8 @@ def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=
     strips = {"start": [], "targets": [], "predictions": []}
     maps, kept, first_traj = {}, 0, 0
     full = T - H                                                      # starts per trajectory that live for all H steps
-    for frames, actions, b in _batches(dataset, int(batch_size), device, jpeg_decoder):
+    for frames, actions, b in trajectory_batches(dataset, int(batch_size), device, jpeg_decoder):
+        frames = frames.view(-1, *frames.shape[2:])                  # [b*T,...]
         if b not in maps:
             maps[b] = _maps(sched, T, b, device)
         flat_actions = actions.reshape(b * T, 4)
@@ -285,8 +264,8 @@ def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=
     per_h = [torch.cat(errs[h]) for h in range(H)]
     per_h_base = [torch.cat(bases[h]) for h in range(H)]
     result = {
-        "horizon_mse": torch.cat([_mean(e) for e in per_h]),
-        "persistence_mse": torch.cat([_mean(e) for e in per_h_base]),
+        "horizon_mse": torch.cat([fp64_mean(e) for e in per_h]),
+        "persistence_mse": torch.cat([fp64_mean(e) for e in per_h_base]),
         "counts": torch.tensor([int(e.numel()) for e in per_h], dtype=torch.int64, device=device),
         "errors": torch.cat(all_err), "persistence": torch.cat(all_base),
         "index": torch.from_numpy(np.concatenate(index).astype(np.int32)).to(device),
@@ -318,29 +297,12 @@ def save_strips(strips, save_dir):
     return paths
 
 
-def load_module(path, device):
-    """torch.load of a whole-module checkpoint of train_forward_model.py (a local, trusted file: module pickles need
-    weights_only=False), in eval mode on `device`.  The checkpoints name the class `models.forward_encoder.
-    ForwardAutoencoder`: the root-level shim of that name is imported first where it is on sys.path."""
-    try:
-        importlib.import_module("models.forward_encoder")
-    except ImportError:
-        pass
-    return torch.load(path, map_location="cpu", weights_only=False).to(device).eval()
-
-
 def make_dataset(path, seq_length=15, seed=2, raw_jpeg=False):
     """synthetic:<N>:images|frames_u8|jpeg, or the HDF5 directory (byte frames; raw_jpeg: its JPEG streams, decoded on
     the device)."""
-    from .utils.trajectory_loader import PushDataset, SyntheticPushDataset
-    path = str(path)
-    if path.startswith("synthetic:") or "/synthetic:" in path:
-        spec = path[path.index("synthetic:"):].split(":")
-        mode = spec[2] if len(spec) > 2 else "images"
-        if mode not in ("images", "frames_u8", "jpeg"):
-            raise ValueError("the forward model predicts images: use synthetic:<N>:images, :frames_u8 or :jpeg, got %r" % mode)
-        return SyntheticPushDataset(int(spec[1]), seq_length=int(seq_length), mode=mode, seed=seed)
-    return PushDataset(path, seq_length=int(seq_length), raw_uint8=not raw_jpeg, raw_jpeg=raw_jpeg)
+    return open_dataset(path, seq_length=int(seq_length), seed=seed, default_mode="images", modes=("images", "frames_u8", "jpeg"),
+                        mode_error="the forward model predicts images: use synthetic:<N>:images, :frames_u8 or :jpeg, got %(mode)r",
+                        push=dict(seq_length=int(seq_length), raw_uint8=not raw_jpeg, raw_jpeg=raw_jpeg))
 
 
 def make_parser():

@@ -13,7 +13,6 @@ from `ndp_uniform_noise` (a seed and buffers of its own: torch's generators are 
 `ndp_d_forward`, the scores from `ndp_gan_score` (csrc/ndp_eval.inc; include/ndp.h states every output).  The modules are
 used in eval mode; there is no CPU path, and nothing here synchronises with the host per batch: every result is a device
 tensor.  Argument errors are ValueErrors raised before any launch."""
-import importlib
 from argparse import ArgumentParser
 
 import numpy as np
@@ -21,6 +20,8 @@ import torch
 
 from . import _capi
 from . import jpeg as jpeg_frames
+from ._eval_io import fp64_mean, load_module, trajectory_batches
+from .utils.trajectory_loader import open_dataset
 
 CODE_DIM, ACTION_DIM = _capi.CODE_DIM, _capi.ACTION_DIM
 OUTPUTS = ("sample_err", "mean_err", "best_err", "best_k", "best_curve", "spread", "ndiv", "d_fake_prob", "d_pick_k", "d_pick_err")
@@ -162,27 +163,8 @@ def _yields_codes(frames):
 
 
 def _batches(dataset, first, batch_size, device, jpeg_decoder):
-    """(frames [b,T,...], actions [b,T,4], b) for `batch_size` trajectories at a time: cached codes [b,T,128], float
-    images, or byte frames for a dataset that yields bytes or JPEG streams.  The trajectories are read by index in order
-    -- no DataLoader, so no random number of the process is drawn (validation inside a training run must not move its
-    shuffling)."""
-    T = int(dataset.seq_length)
-    for lo in range(0, len(dataset), batch_size):
-        items = [first if i == 0 else dataset[i] for i in range(lo, min(lo + batch_size, len(dataset)))]
-        actions = torch.stack([torch.as_tensor(it[2]) for it in items]).to(device, non_blocking=True).float()
-        if jpeg_decoder is not None:
-            buffer, offsets = jpeg_frames.pack_jpegs([s for it in items for s in it[0]])
-            frames = jpeg_decoder.decode(buffer, offsets)
-            frames = frames.view(len(items), T, *frames.shape[1:])
-        else:
-            frames = torch.stack([it[0] for it in items]).to(device, non_blocking=True)
-            if frames.dtype != torch.uint8:
-                frames = frames.float()
-        yield frames, actions, len(items)
-
-
-def _mean(per_row):
-    return per_row.double().mean(dim=0).float().reshape(-1)          # of the fp32 per-row values, in fp64
+    """trajectory_batches with the item `evaluate` has read already: (frames [b,T,...], actions [b,T,4], b)."""
+    return trajectory_batches(dataset, batch_size, device, jpeg_decoder, first=first)
 
 
 def evaluate(generator, dataset, encoder=None, discriminator=None, num_sample=6, batch_size=16, seed=0, device=None):
@@ -246,44 +228,26 @@ def evaluate(generator, dataset, encoder=None, discriminator=None, num_sample=6,
         jpeg_decoder.finish()
     rows = {o: torch.cat(v) for o, v in rows.items()}
     result = {
-        "action_mse": _mean(rows["mean_err"]), "best_action_mse": _mean(rows["best_err"]),
-        "best_of_k_curve": _mean(rows["best_curve"]), "spread": _mean(rows["spread"]), "ndiv_per_row": _mean(rows["ndiv"]),
-        "count": total,
+        "action_mse": fp64_mean(rows["mean_err"], 0), "best_action_mse": fp64_mean(rows["best_err"], 0),
+        "best_of_k_curve": fp64_mean(rows["best_curve"], 0), "spread": fp64_mean(rows["spread"], 0),
+        "ndiv_per_row": fp64_mean(rows["ndiv"], 0), "count": total,
         "index": torch.from_numpy(np.stack([np.repeat(np.arange(len(dataset)), T - 1), np.tile(np.arange(T - 1), len(dataset))],
                                            axis=1).astype(np.int32)).to(device),
     }
     if discriminator is not None:
         rows["d_real_prob"] = torch.cat(real_probs)
-        result.update(d_fake_prob=_mean(rows["d_fake_prob"]), d_real_prob=_mean(rows["d_real_prob"]),
-                      d_pick_mse=_mean(rows["d_pick_err"]))
+        result.update(d_fake_prob=fp64_mean(rows["d_fake_prob"], 0), d_real_prob=fp64_mean(rows["d_real_prob"], 0),
+                      d_pick_mse=fp64_mean(rows["d_pick_err"], 0))
     rows["action_hat"], rows["noise"] = torch.cat(hats), noise_all
     result["rows"] = rows
     return result
 
 
-def load_module(path, device):
-    """torch.load of a whole-module checkpoint of train_gan.py / train_autoencoder.py (a local, trusted file: module
-    pickles need weights_only=False), in eval mode on `device`.  The checkpoints name the classes `models.gan.Decoder`,
-    `models.gan.Discriminator` and `models.image_autoencoder.Encoder`: the root-level shims of those names are imported
-    first where they are on sys.path."""
-    for name in ("models.gan", "models.image_autoencoder"):
-        try:
-            importlib.import_module(name)
-        except ImportError:
-            pass
-    return torch.load(path, map_location="cpu", weights_only=False).to(device).eval()
-
-
 def make_dataset(path, seq_length=15, seed=2, raw_jpeg=False):
     """synthetic:<N>[:codes|images|frames_u8|jpeg] (codes by default, as train_gan's), or the HDF5 directory (byte frames;
     raw_jpeg: its JPEG streams, decoded on the device)."""
-    from .utils.trajectory_loader import PushDataset, SyntheticPushDataset
-    path = str(path)
-    if path.startswith("synthetic:") or "/synthetic:" in path:
-        spec = path[path.index("synthetic:"):].split(":")
-        mode = spec[2] if len(spec) > 2 else "codes"
-        return SyntheticPushDataset(int(spec[1]), seq_length=int(seq_length), mode=mode, seed=seed)
-    return PushDataset(path, seq_length=int(seq_length), raw_uint8=not raw_jpeg, raw_jpeg=raw_jpeg)
+    return open_dataset(path, seq_length=int(seq_length), seed=seed, default_mode="codes",
+                        push=dict(seq_length=int(seq_length), raw_uint8=not raw_jpeg, raw_jpeg=raw_jpeg))
 
 
 def make_parser():

@@ -14,6 +14,7 @@ same bits."""
 import torch
 
 from . import _capi
+from ._eval_io import fp64_mean
 
 IMAGE = (3, 128, 128)
 FRAME = (128, 128, 3)
@@ -89,7 +90,4 @@ def image_quality(a, b, a_idx=None, b_idx=None, ssim=True, psnr=True):
     return out_ssim, out_psnr
 
 
-def mean(values):
-    """[1] float32: the mean of the fp32 per-pair values, taken in fp64.  No value is skipped: an infinite PSNR gives an
-    infinite mean."""
-    return values.double().mean().float().view(1)
+mean = fp64_mean          # [1] float32: the mean of the fp32 per-pair values, taken in fp64; no value is skipped

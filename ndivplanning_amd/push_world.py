@@ -507,25 +507,19 @@ def _mpc_main(argv):
     from argparse import ArgumentParser
 
     from . import evaluation as E
-    from .utils.argparse_util import override_dotmap
+    from ._eval_io import config_cli, load_eval_models
     from .utils.cli_arguments.common_arguments import add_common_arguments
-    from .utils.file import make_paths_absolute
     parser = add_common_arguments(ArgumentParser(description="closed-loop MPC in the push world"))
     parser.add_argument("--envs", type=int, default=16)
     parser.add_argument("--steps", type=int, default=14)
     parser.add_argument("--start", default="simplified")
-    namespace = parser.parse_args(argv)
-    _check_n(namespace.envs)
-    _check_start(namespace.start)
-    config = override_dotmap(namespace, "config_file")
-    config = make_paths_absolute(os.getcwd(), config, log_not_exist=True)
-    if not torch.cuda.is_available():
-        raise _capi.NdpError("the push world needs a ROCm GPU; there is no CPU path")
-    gpu_id = E.device_of(config)
-    # local, trusted whole-module pickles written by the training scripts: weights_only=False is required
-    image_encoder = torch.load(config.image_encoder_model_path, map_location=gpu_id, weights_only=False)
-    generator = torch.load(config.gan_decoder_model_path, map_location=gpu_id, weights_only=False)
-    fwd_model_autoencoder = torch.load(config.forward_model_autoencoder_path, map_location=gpu_id, weights_only=False)
+
+    def check(ns):
+        _check_n(ns.envs)
+        _check_start(ns.start)
+
+    namespace, config, _ = config_cli(parser, argv, "the push world", prepare=check)
+    image_encoder, generator, fwd_model_autoencoder, gpu_id = load_eval_models(config)
     for module in (image_encoder, generator, fwd_model_autoencoder):
         module.eval()
     models = E.EvalModels(image_encoder, fwd_model_autoencoder, generator, gpu_id)

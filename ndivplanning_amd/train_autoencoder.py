@@ -40,7 +40,7 @@ from . import _capi, dp
 from . import jpeg as jpeg_frames
 from .autoencoder_trainer import AutoencoderTrainer
 from .models.image_autoencoder import Decoder, Encoder
-from .utils.trajectory_loader import PushDataset, SyntheticPushDataset
+from .utils.trajectory_loader import open_dataset
 
 LR_RATE = 2e-4
 NUM_EPOCHS = 50
@@ -59,14 +59,9 @@ def norm(image):
 def make_dataset(path, seed=1, raw_jpeg=False):
     """synthetic:<N>:images|jpeg, or the trajectory directory (HDF5 or .ndpt bundles; raw_jpeg: its JPEG streams, decoded
     on the device)."""
-    path = str(path)
-    if path.startswith("synthetic:"):
-        spec = path.split(":")
-        mode = spec[2] if len(spec) > 2 else "images"
-        if mode not in ("images", "jpeg"):
-            raise ValueError("the autoencoder trains on images: use synthetic:<N>:images or synthetic:<N>:jpeg")
-        return SyntheticPushDataset(int(spec[1]), seq_length=15, mode=mode, seed=seed)
-    return PushDataset(path, raw_jpeg=raw_jpeg) if raw_jpeg else PushDataset(path)
+    return open_dataset(path, seq_length=15, seed=seed, default_mode="images", modes=("images", "jpeg"),
+                        mode_error="the autoencoder trains on images: use synthetic:<N>:images or synthetic:<N>:jpeg",
+                        push={"raw_jpeg": True} if raw_jpeg else None)
 
 
 def build_models(device):

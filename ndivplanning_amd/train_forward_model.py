@@ -44,10 +44,11 @@ from . import dp
 from . import jpeg as jpeg_frames
 from .forward_trainer import ForwardModelTrainer
 from .models.forward_encoder import Decoder, Encoder, ForwardAutoencoder
-from .train_gan import _get, denorm, make_dataset, norm  # noqa: F401
+from .train_gan import denorm, make_dataset, norm, push_arguments  # noqa: F401
 from .utils.argparse_util import override_dotmap
 from .utils.cli_arguments.common_arguments import add_common_arguments
 from .utils.file import make_paths_absolute
+from .utils.trajectory_loader import open_dataset
 
 
 def bind_reference_class_paths():
@@ -242,16 +243,9 @@ def _optional(node, key, default):
 def make_val_dataset(config, path):
     """The held-out trajectories of `training.forward.val_data_path`, made as `make_dataset` makes the training set
     (same trajectory_length and frame format); a synthetic set is seeded apart from the training set."""
-    from .utils.trajectory_loader import PushDataset, SyntheticPushDataset
-    path = str(path)
-    if path.startswith("synthetic:") or "/synthetic:" in path:
-        spec = path[path.index("synthetic:"):].split(":")
-        mode = spec[2] if len(spec) > 2 else "images"
-        if mode not in ("images", "frames_u8", "jpeg"):
-            raise ValueError("the forward model is validated on images: use `synthetic:<N>:images`, `:frames_u8` or `:jpeg`")
-        return SyntheticPushDataset(int(spec[1]), seq_length=config.trajectory_length, mode=mode, seed=int(config.random_seed) + 1)
-    return PushDataset(path, seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)),
-                       raw_jpeg=bool(_get(config, "raw_jpeg", False)))
+    return open_dataset(path, seq_length=config.trajectory_length, seed=int(config.random_seed) + 1, default_mode="images",
+                        modes=("images", "frames_u8", "jpeg"), push=push_arguments(config),
+                        mode_error="the forward model is validated on images: use `synthetic:<N>:images`, `:frames_u8` or `:jpeg`")
 
 
 def validate(trainer, val_dataset, horizon, batch_size, quality=False):

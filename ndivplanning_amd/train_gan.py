@@ -58,7 +58,7 @@ from .trainer import GanTrainer  # noqa: E402
 from .utils.argparse_util import override_dotmap  # noqa: E402
 from .utils.cli_arguments.common_arguments import add_common_arguments  # noqa: E402
 from .utils.file import make_paths_absolute  # noqa: E402
-from .utils.trajectory_loader import PushDataset, SyntheticPushDataset  # noqa: E402
+from .utils.trajectory_loader import open_dataset  # noqa: E402
 
 
 def denorm(tensor):
@@ -97,18 +97,17 @@ def bind_reference_class_paths():
     return missing
 
 
+def push_arguments(config):
+    """PushDataset's keyword arguments as the trainers' configuration states them.  Decoded frames stay bytes until the
+    first convolution reads them (ndp_encoder_forward_u8 / ndp_fm_*_u8): `raw_uint8: false` restores the reference's
+    host-side float tensors; `raw_jpeg: true` yields the stored JPEG streams, decoded on the device (ndivplanning_amd.jpeg)."""
+    return dict(seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)),
+                raw_jpeg=bool(_get(config, "raw_jpeg", False)))
+
+
 def make_dataset(config):
-    path = str(config.train_data_path)
-    if path.startswith("synthetic:") or "/synthetic:" in path:
-        spec = path[path.index("synthetic:"):].split(":")
-        n = int(spec[1])
-        mode = spec[2] if len(spec) > 2 else "codes"
-        return SyntheticPushDataset(n, seq_length=config.trajectory_length, mode=mode, seed=int(config.random_seed))
-    # decoded frames stay bytes until the first convolution reads them (ndp_encoder_forward_u8 / ndp_fm_*_u8):
-    # `raw_uint8: false` restores the reference's host-side float tensors; `raw_jpeg: true` yields the stored JPEG
-    # streams, decoded on the device (ndivplanning_amd.jpeg)
-    return PushDataset(config.train_data_path, seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)),
-                       raw_jpeg=bool(_get(config, "raw_jpeg", False)))
+    return open_dataset(config.train_data_path, seq_length=config.trajectory_length, seed=int(config.random_seed),
+                        default_mode="codes", push=push_arguments(config))
 
 
 def load_encoder(config, device):
@@ -147,13 +146,8 @@ VAL_NOISE_SEED = 1 << 40
 def make_val_dataset(config, path):
     """The held-out trajectories of `training.gan.val_data_path`, made as `make_dataset` makes the training set (same
     trajectory_length); a synthetic set is seeded apart from the training set."""
-    path = str(path)
-    if path.startswith("synthetic:") or "/synthetic:" in path:
-        spec = path[path.index("synthetic:"):].split(":")
-        mode = spec[2] if len(spec) > 2 else "codes"
-        return SyntheticPushDataset(int(spec[1]), seq_length=config.trajectory_length, mode=mode, seed=int(config.random_seed) + 1)
-    return PushDataset(path, seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)),
-                       raw_jpeg=bool(_get(config, "raw_jpeg", False)))
+    return open_dataset(path, seq_length=config.trajectory_length, seed=int(config.random_seed) + 1, default_mode="codes",
+                        push=push_arguments(config))
 
 
 def validate(decoder, discriminator, encoder, val_dataset, num_sample, batch_size, seed, device):

@@ -151,3 +151,19 @@ class PushDataset(torch.utils.data.Dataset):
         if self.transform:
             images = self.transform(images)
         return images, states, actions, goal
+
+
+def open_dataset(path, seq_length, seed, default_mode, modes=None, mode_error=None, push=None):
+    """The one way from a data path to a dataset, for every trainer and evaluation script.  `synthetic:<N>[:mode]`, at
+    the start of the path or behind a directory prefix (what `make_paths_absolute` makes of it), gives
+    `SyntheticPushDataset(N, seq_length, mode or default_mode, seed)`; a mode outside `modes` (None: any the class takes)
+    is a ValueError with the caller's own text, `mode_error` (`%(mode)r` in it stands for the mode).  Any other path is a
+    trajectory directory: `PushDataset(path, **push)`, the caller's keyword arguments and nothing else."""
+    path = str(path)
+    if path.startswith("synthetic:") or "/synthetic:" in path:
+        spec = path[path.index("synthetic:"):].split(":")
+        mode = spec[2] if len(spec) > 2 else default_mode
+        if modes is not None and mode not in modes:
+            raise ValueError(mode_error % {"mode": mode})
+        return SyntheticPushDataset(int(spec[1]), seq_length=seq_length, mode=mode, seed=seed)
+    return PushDataset(path, **(push or {}))

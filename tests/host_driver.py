@@ -1,7 +1,7 @@
 """Build and run tests/host_drivers/main.hip: the kernels' schedules replayed on the CPU under AddressSanitizer and UBSan,
 one program for every driver body.  The helper modules (jpeg_core_host, jpeg_enc_core_host, resize_core_host,
-fm_eval_common, gan_eval_common, quality_common, store_common, rollout_common) pack a body's cases, call `run` and parse
-its report.  The program is an ordinary one: it is started as a child process, nothing is preloaded and nothing of it is
+fm_eval_common, gan_eval_common, quality_common, store_common, rollout_common, plan_common, world_common) pack a body's
+cases and parse its report; they or their test modules call `run`.  The program is an ordinary one: it is started as a child process, nothing is preloaded and nothing of it is
 loaded into Python."""
 import atexit
 import os
@@ -56,9 +56,10 @@ def build(sanitize=True):
     return exe
 
 
-def run(name, payload, work_dir, args=(), timeout=900, exe=None):
-    """Run the driver body `name` on `payload` (bytes: its IN file) in a child process; asserts that it exits 0 with no
-    sanitizer report.  Returns the bytes of its OUT file; both files are removed."""
+def run(name, payload, work_dir, args=(), timeout=900, exe=None, expect=0):
+    """Run the driver body `name` on `payload` (bytes: its IN file) in a child process; asserts that it exits with
+    status `expect` and no sanitizer report.  Returns the bytes of its OUT file (expect != 0, a refused input: None, OUT
+    is not read); both files are removed."""
     src, dst = os.path.join(str(work_dir), name + "_in.bin"), os.path.join(str(work_dir), name + "_out.bin")
     with open(src, "wb") as f:
         f.write(payload)
@@ -66,9 +67,12 @@ def run(name, payload, work_dir, args=(), timeout=900, exe=None):
     p = subprocess.run([exe or build(), name, src, dst, *args], env=env, capture_output=True, text=True, timeout=timeout)
     text = p.stdout + p.stderr
     assert "Sanitizer" not in text and "runtime error" not in text, text[-4000:]
-    assert p.returncode == 0, (p.returncode, text[-2000:])
-    with open(dst, "rb") as f:
-        report = f.read()
+    assert p.returncode == expect, (p.returncode, text[-2000:])
+    report = None
+    if expect == 0:
+        with open(dst, "rb") as f:
+            report = f.read()
     os.remove(src)
-    os.remove(dst)
+    if os.path.exists(dst):
+        os.remove(dst)
     return report

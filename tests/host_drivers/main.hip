@@ -22,6 +22,8 @@
 #include "image_quality.inc"
 #include "store_gather.inc"
 #include "fm_rollout.inc"
+#include "plan_cem.inc"
+#include "world.inc"
 
 int main(int argc, char** argv) {
   static const struct {
@@ -36,6 +38,8 @@ int main(int argc, char** argv) {
       {"image_quality", host::image_quality::run},
       {"store_gather", host::store_gather::run},
       {"fm_rollout", host::fm_rollout::run},
+      {"plan_cem", host::plan_cem::run},
+      {"world", host::world::run},
   };
   for (const auto& d : drivers)
     if (argc > 1 && strcmp(argv[1], d.name) == 0) return d.run(argc - 1, argv + 1);

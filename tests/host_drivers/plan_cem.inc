@@ -1,24 +1,18 @@
-// plan_cem_main.hip -- the planner's cross-entropy update (k_plan_cem_update, csrc/ndp_plan.inc) run on the CPU, for
-// tests/test_plan_cem_host.py.  A stand-alone program beside main.hip, built with the same command line: it includes
-// the library's source as the library build does and calls the __host__ __device__ functions the kernel calls
+// plan_cem.inc -- the planner's cross-entropy update (k_plan_cem_update, csrc/ndp_plan.inc) run on the CPU, for
+// tests/test_plan_cem_host.py.  main.hip includes it behind the library's source (see there); it calls the __host__
+// __device__ functions the kernel calls
 // (ndp::plan::rank_of, refit, sample, best_of, seq_index) by the kernel's schedule, thread by thread: the errors staged
 // "in LDS", every thread's rank, the refit of component d by thread d, then the walk over the (ts, rollout) pairs.  What
 // k_plan_cem_update does outside those functions -- the loops, the barriers' phases, the count of the non-NaN errors --
 // is restated here and tested as a copy; a slip in the device's own form of those is seen only by the GPU tests
 // (tests/test_gpu_plan_cem.py).  It makes no HIP runtime call and needs no GPU.
 //
-// Usage: plan_cem plan_cem IN OUT
+// Usage: host_driver plan_cem IN OUT
 //   IN   int32 cases, then per case 6 int32 (B, R, E, Th, first, elite_idx wanted), 2 floats (momentum, min_std), low[4],
 //        high[4], err [B,R], seq_in [Th,B,R,4], normal [Th,B,R,4], mean [B,Th,4], std [B,Th,4], best_err [B]
 //   OUT  per case mean, std [B,Th,4], seq_out [Th,B,R,4], best_err [B], elite_idx [B,E] int32 (-7 where not wanted)
 // Every buffer -- inputs, outputs, each LDS array -- is an allocation of exactly its size (exact.h; the 16-byte operands
 // aligned to 16), so a sanitizer sees any access past it.
-#include "../../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstring>
-
-#include "exact.h"
-
 namespace host::plan_cem {
 
 using namespace ndp::plan;
@@ -109,9 +103,3 @@ int run(int argc, char** argv) {
 }
 
 }  // namespace host::plan_cem
-
-int main(int argc, char** argv) {
-  if (argc > 1 && strcmp(argv[1], "plan_cem") == 0) return host::plan_cem::run(argc - 1, argv + 1);
-  fprintf(stderr, "usage: %s plan_cem IN OUT\n", argv[0]);
-  return host::kBadInput;
-}

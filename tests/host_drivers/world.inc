@@ -1,6 +1,6 @@
-// world_main.hip -- the push world's two kernels (k_world_step_render, k_world_render, csrc/ndp_world.inc) run on the CPU,
-// for tests/test_world_host.py.  A stand-alone program beside main.hip, built with the same command line: it includes the
-// library's source as the library build does and calls the __host__ __device__ functions the kernels call
+// world.inc -- the push world's two kernels (k_world_step_render, k_world_render, csrc/ndp_world.inc) run on the CPU,
+// for tests/test_world_host.py.  main.hip includes it behind the library's source (see there); it calls the __host__
+// __device__ functions the kernels call
 // (ndp::world::step, quantise, span_begin, span_finish, pixel_offset) by the kernels' schedule, workgroup by workgroup
 // and thread by thread: every thread below S*S/4 finds its span and the table under it, thread 0 advances the state and
 // quantises the scene "in LDS", workgroup 0 of an environment writes state_out, every live thread lays the layers over
@@ -9,18 +9,12 @@
 // slip in the device's own form of those is seen only by the GPU tests (tests/test_gpu_push_world.py).  It makes no HIP
 // runtime call and needs no GPU.
 //
-// Usage: world world IN OUT
+// Usage: host_driver world IN OUT
 //   IN   int32 runs, then per run 3 int32 (n, S, with_frames), state_in [n,8], actions [n,4]
 //   OUT  per run state_out [n,8], with_frames: the frames of the step [n,S,S,3]; then the frames k_world_render draws of
 //        state_in [n,S,S,3]
 // Every buffer -- inputs, outputs, each LDS object -- is an allocation of exactly its size (exact.h), so a sanitizer sees
 // any access past it.
-#include "../../ndivplanning_amd/csrc/ndp_kernels.hip"
-
-#include <cstring>
-
-#include "exact.h"
-
 namespace host::world {
 
 using namespace ndp::world;
@@ -101,9 +95,3 @@ int run(int argc, char** argv) {
 }
 
 }  // namespace host::world
-
-int main(int argc, char** argv) {
-  if (argc > 1 && strcmp(argv[1], "world") == 0) return host::world::run(argc - 1, argv + 1);
-  fprintf(stderr, "usage: %s world IN OUT\n", argv[0]);
-  return host::kBadInput;
-}

@@ -1,7 +1,7 @@
 """What the tests of the planner's cross-entropy refinement share (tests/test_plan_cem_host.py on the CPU,
 tests/test_gpu_plan_cem.py on the GPU): the plain numpy restatement of ndp_plan_cem_update as include/ndp.h states it,
 the fp64 restatement of ndp_normal_noise's Box-Muller, the cases, and the packing for
-tests/host_drivers/plan_cem_main.hip."""
+tests/host_drivers/plan_cem.inc (a body of tests/host_driver.py's program)."""
 import ctypes
 import struct
 
@@ -156,7 +156,7 @@ def check_special(c, got):
 
 # ---------------------------------------------------------------------------------------------- the host driver
 def pack(case_list):
-    """IN of plan_cem_main.hip: int32 cases; per case 6 int32 (B, R, E, Th, first, elite_idx wanted), 2 floats (momentum,
+    """IN of plan_cem.inc: int32 cases; per case 6 int32 (B, R, E, Th, first, elite_idx wanted), 2 floats (momentum,
     min_std), low[4], high[4], err [B,R], seq_in and normal [Th,B,R,4], mean and std [B,Th,4], best_err [B]."""
     blob = [struct.pack("<i", len(case_list))]
     for c in case_list:

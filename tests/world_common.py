@@ -1,7 +1,7 @@
 """The push world (include/ndp.h, "push world") restated in numpy from the header's words: the step in fp64, the render
 in integers after the one quantisation.  Nothing here is shared with the library, so a result is compared bit for bit
-and needs no tolerance.  Also the case list the CPU and GPU tests share, the packing of tests/host_drivers/world_main.hip's
-files, and the starts (push_world.starts: the only starts there are; their properties are pinned in
+and needs no tolerance.  Also the case list the CPU and GPU tests share, the packing of tests/host_drivers/world.inc's
+files (a body of tests/host_driver.py's program), and the starts (push_world.starts: the only starts there are; their properties are pinned in
 tests/test_push_world.py)."""
 import os
 import sys
