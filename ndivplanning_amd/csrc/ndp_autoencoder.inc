@@ -13,9 +13,11 @@
 // k_fm_adam_pack).  Its maps are NHWC with the channel count as the pixel stride (nothing is concatenated).  Its eight
 // BatchNorms have the channel counts of the forward model's first eight (conv1..3_bn, deconv1..5_bn), so they use those
 // BatchNorm indices, statistics slots and scratch; where their tensors live comes from FmBnAt.  What this file says about
-// the network is its table (kAeNet: layers, BatchNorm count, gradient buckets), its workspace tensors, the output layer's
-// kernels and the two launch sequences; every size, offset, pack and optimizer segment comes from the table through the
-// helpers of ndp_forward_model.inc, which is also how a further network of the family would be added.
+// the network is its table (kAeNet: layers, launch labels, BatchNorm count, gradient buckets), its workspace tensors and
+// where the maps live in them (ae_maps), the output layer's kernels and the two launch sequences, which name layers and
+// no sizes; every size, offset, pack and optimizer segment and the geometry of every layer launch comes from the table
+// through the helpers of ndp_forward_model.inc (fm_geom, fm_layer_fwd / _dgrad / _wgrad), which is also how a further
+// network of the family would be added -- as the folded decoder below (kAeDecNet, ae_dec_maps) is.
 //
 // New here: deconv6, 64 -> 3 channels at 128 x 128.  As a GEMM its three output channels would be padded to 32 (ten
 // times the MACs, a 32-wide output map); instead three small VALU kernels sized to what they move, as k_fm_r2_*:
@@ -63,9 +65,13 @@ constexpr int64_t kAeMaxImages = 8192;
 constexpr int kAeBuckets = 6;
 static const int kAeBucketFirst[kAeBuckets] = {8, 7, 5, 4, 0, -1};
 static const int kAeBucketEnd[kAeBuckets] = {12, 8, 7, 5, 4, -1};
-// the table every host helper of ndp_forward_model.inc reads (sizes, offsets, fm_pack, fm_adam_pack, fm_layout, buckets);
-// deconv6 has no second weight order (FM_P2_NONE): the kernels below read P1
-static const FmNet kAeNet = {kAe, kAeLayers, kAeBns, kAeBucketFirst, kAeBucketEnd, kAeBuckets};
+static const FmLabels kAeLabels[kAeLayers] = {
+    FM_LABELS("ae.conv1"), FM_LABELS("ae.conv2"), FM_LABELS("ae.conv3"), FM_LABELS("ae.conv4"), FM_LABELS("ae.conv5"),
+    FM_LABELS("ae.conv6"), FM_LABELS("ae.deconv1"), FM_LABELS("ae.deconv2"), FM_LABELS("ae.deconv3"), FM_LABELS("ae.deconv4"),
+    FM_LABELS("ae.deconv5"), FM_LABELS("ae.deconv6")};
+// the table every host helper of ndp_forward_model.inc reads (sizes, offsets, fm_pack, fm_adam_pack, fm_layout, buckets,
+// the layer launches); deconv6 has no second weight order (FM_P2_NONE): the kernels below read P1
+static const FmNet kAeNet = {kAe, kAeLayers, kAeBns, kAeBucketFirst, kAeBucketEnd, kAeBuckets, kAeLabels};
 static_assert(kAeBuckets <= kFmMaxBuckets, "FmBucketEvents::ev");
 static FmBucketEventSet g_ae_buckets;
 
@@ -396,60 +402,66 @@ static AeWs ae_ws(float* ws, int64_t n) {
   return w;
 }
 
+// where the maps live (FmMaps): nothing is concatenated, every map's pixel stride is its channel count
+static FmMaps ae_maps(const AeWs& aw) {
+  float* const* t = aw.t;
+  auto at = [&](int tensor, int ld) { return FmView{t[tensor], ld}; };
+  FmMaps m;
+  memset(&m, 0, sizeof(m));
+  m.in[0] = at(AET_COLS, 32);   m.raw[0] = at(AET_RAW1, 64);                                       // conv1
+  m.in[1] = at(AET_A1, 64);     m.raw[1] = at(AET_RAW2, 128);    m.din[1] = at(AET_DA1, 64);       // conv2
+  m.in[2] = at(AET_A2, 128);    m.raw[2] = at(AET_RAW3, 256);    m.din[2] = at(AET_DA2, 128);      // conv3
+  m.in[3] = at(AET_A3, 256);                                     m.din[3] = at(AET_DA3, 256);      // conv4
+  m.in[4] = at(AET_A4, 512);                                     m.din[4] = at(AET_DA4, 512);      // conv5
+  m.in[5] = at(AET_A5, 1024);                                    m.din[5] = at(AET_DA5, 1024);     // conv6
+  m.in[6] = at(AET_Z, 128);     m.raw[6] = at(AET_RAWU1, 1024);  m.din[6] = at(AET_DZ, 128);       // deconv1
+  m.in[7] = at(AET_U1, 1024);   m.raw[7] = at(AET_RAWU2, 512);   m.din[7] = at(AET_DU1, 1024);     // deconv2
+  m.in[8] = at(AET_U2, 512);    m.raw[8] = at(AET_RAWU3, 256);   m.din[8] = at(AET_DU2, 512);      // deconv3
+  m.in[9] = at(AET_U3, 256);    m.raw[9] = at(AET_RAWU4, 128);   m.din[9] = at(AET_DU3, 256);      // deconv4
+  m.in[10] = at(AET_U4, 128);   m.raw[10] = at(AET_RAWU5, 64);   m.din[10] = at(AET_DU4, 128);     // deconv5
+  m.in[11] = at(AET_U5, 64);                                     m.din[11] = at(AET_DU5, 64);      // deconv6 (k_ae_out_*)
+  m.in[12] = at(AET_G6, 4);                                                                        // (d loss / d pre-tanh output)
+  fm_maps_close(m, kAeNet);
+  return m;
+}
+
 // forward pass, training mode, through the loss: g6 = d loss / d (pre-tanh output), loss partial sums
 static int ae_forward_loss(hipStream_t st, const float* params, float* running, const float* images, int64_t n, float* recon,
                            const AeWs& aw, const FmStatSync* sync) {
   fm_attrs();
   const FmWs& ws = aw.fm;
-  const float* P = params;
-  auto W1 = [&](int l) { return P + fm_param_offset(kAeNet, l, false); };
-  auto B = [&](int l) { return P + fm_param_offset(kAeNet, l, true); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kAeNet, l)); };
-  auto BN = [&](int b) { return fm_bn_at(kAeNet, b, params, running, nullptr, sync); };   // (sync: the caller's, never ndp_fm_set_stat_sync's)
-  float* const* t = aw.t;
+  const FmMaps m = ae_maps(aw);
+  const FmRun r = {st, kAeNet, m, ws, n, params, running, nullptr, sync};   // (sync: the caller's, never ndp_fm_set_stat_sync's)
   int rc;
-#define AE_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
   {
     // conv1's columns, and every statistics accumulator of the step zeroed (k_fm_image_cols without actions)
     KTimer kt("k_fm_image_cols", st);
     const int64_t opix = n * 4096;
     const int64_t zero_words = fm_stat_offset_words(kFmStatSlots);
     const unsigned blocks = (unsigned)((opix + kThreads - 1) / kThreads + (zero_words / 2 + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(k_fm_image_cols<false>, dim3(blocks), dim3(kThreads), 0, st, (const void*)images, opix, t[AET_COLS],
+    hipLaunchKernelGGL(k_fm_image_cols<false>, dim3(blocks), dim3(kThreads), 0, st, (const void*)images, opix, m.in[0].p,
                        (const float*)nullptr, (int64_t)0, (float*)nullptr, ws.stat_acc, zero_words);
   }
-  AE_TRY(check_launch("k_fm_image_cols"));
-  FmEpReq eps_[kAeBns];
-  for (int b = 0; b < kAeBns; ++b) eps_[b] = fm_ep_bn_fwd(b);
-  auto EP = [&](int b) { return (const FmEpReq*)&eps_[b]; };
-  // ---- encoder (image_autoencoder.py:36-49)
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv1]", 0, {t[AET_COLS], 32}, 64, 1, W2(0), B(0), {t[AET_RAW1], 64}, 64, 64, n, 32, 64, 1, 0, 0, 0, ws, 0, EP(0)));
-  AE_TRY(fm_bn_fwd_at(st, 0, {t[AET_RAW1], 64}, n * 4096, {t[AET_A1], 64}, BN(0), 1, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv2]", 0, {t[AET_A1], 64}, 64, 2, W1(1), B(1), {t[AET_RAW2], 128}, 32, 32, n, 64, 128, 3, 1, 0, 0, ws, 0, EP(1)));
-  AE_TRY(fm_bn_fwd_at(st, 1, {t[AET_RAW2], 128}, n * 1024, {t[AET_A2], 128}, BN(1), 1, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv3]", 0, {t[AET_A2], 128}, 32, 2, W1(2), B(2), {t[AET_RAW3], 256}, 16, 16, n, 128, 256, 3, 1, 0, 0, ws, 0, EP(2)));
-  AE_TRY(fm_bn_fwd_at(st, 2, {t[AET_RAW3], 256}, n * 256, {t[AET_A3], 256}, BN(2), 1, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv4]", 0, {t[AET_A3], 256}, 16, 2, W1(3), B(3), {t[AET_A4], 512}, 8, 8, n, 256, 512, 3, 1, 1, 0, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv5]", 0, {t[AET_A4], 512}, 8, 2, W1(4), B(4), {t[AET_A5], 1024}, 4, 4, n, 512, 1024, 3, 1, 1, 0, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.conv6]", 0, {t[AET_A5], 1024}, 4, 1, W1(5), B(5), {t[AET_Z], 128}, 1, 1, n, 1024, 128, 4, 0, 0, 0, ws));
-  // ---- decoder (image_autoencoder.py:80-87)
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv1]", 3, {t[AET_Z], 128}, 1, 1, W2(6), B(6), {t[AET_RAWU1], 1024}, 4, 1, n, 128, 1024, 1, 0, 0, 0, ws, 0, EP(3)));
-  AE_TRY(fm_bn_fwd_at(st, 3, {t[AET_RAWU1], 1024}, n * 16, {t[AET_U1], 1024}, BN(3), 1, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv2]", 1, {t[AET_U1], 1024}, 4, 1, W2(7), B(7), {t[AET_RAWU2], 512}, 8, 4, n, 1024, 512, 2, 0, 0, 0, ws, 0, EP(4)));
-  AE_TRY(fm_bn_fwd_at(st, 4, {t[AET_RAWU2], 512}, n * 64, {t[AET_U2], 512}, BN(4), 1, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv3]", 1, {t[AET_U2], 512}, 8, 1, W2(8), B(8), {t[AET_RAWU3], 256}, 16, 8, n, 512, 256, 2, 0, 0, 0, ws, 0, EP(5)));
-  AE_TRY(fm_bn_fwd_at(st, 5, {t[AET_RAWU3], 256}, n * 256, {t[AET_U3], 256}, BN(5), 1, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv4]", 1, {t[AET_U3], 256}, 16, 1, W2(9), B(9), {t[AET_RAWU4], 128}, 32, 16, n, 256, 128, 2, 0, 0, 0, ws, 0, EP(6)));
-  AE_TRY(fm_bn_fwd_at(st, 6, {t[AET_RAWU4], 128}, n * 1024, {t[AET_U4], 128}, BN(6), 1, ws));
-  if (n * 1024 / kFmBM * 2 >= 256)                                     // (the four parity classes per workgroup: enough tiles from 16 images)
-    AE_TRY(fm_deconv32(st, "k_fm_gemm[ae.deconv5]", {t[AET_U4], 128}, 32, W2(10), B(10), {t[AET_RAWU5], 64}, n, 128, 64, *EP(7), ws));
-  else AE_TRY(fm_gemm(st, "k_fm_gemm[ae.deconv5]", 1, {t[AET_U4], 128}, 32, 1, W2(10), B(10), {t[AET_RAWU5], 64}, 64, 32, n, 128, 64, 2, 0, 0, 0, ws, 0, EP(7)));
-  AE_TRY(fm_bn_fwd_at(st, 7, {t[AET_RAWU5], 64}, n * 4096, {t[AET_U5], 64}, BN(7), 1, ws));
+  FM_TRY(check_launch("k_fm_image_cols"));
+  const FmEpReq none = fm_ep_none();
+  // ---- encoder (image_autoencoder.py:36-49): conv1 (its columns) .. conv3 + BatchNorm, conv4 / conv5 + ReLU, conv6
+  for (int l = 0; l < 3; ++l) {
+    FM_TRY(fm_layer_fwd(r, l, 0, fm_ep_bn_fwd(fm_bn_of(kAeNet, l))));
+    FM_TRY(fm_layer_bn_fwd(r, l, 1));
+  }
+  FM_TRY(fm_layer_fwd(r, 3, 1, none));
+  FM_TRY(fm_layer_fwd(r, 4, 1, none));
+  FM_TRY(fm_layer_fwd(r, 5, 0, none));
+  // ---- decoder (image_autoencoder.py:80-87): deconv1 .. deconv5 + BatchNorm, the output layer with the loss
+  for (int l = 6; l < 11; ++l) {
+    FM_TRY(fm_layer_fwd(r, l, 0, fm_ep_bn_fwd(fm_bn_of(kAeNet, l))));
+    FM_TRY(fm_layer_bn_fwd(r, l, 1));
+  }
   {
     AeOutArgs o;
     memset(&o, 0, sizeof(o));
-    o.up5 = t[AET_U5]; o.w = W1(11); o.bias = B(11); o.img = images; o.g6 = t[AET_G6]; o.recon = recon;
-    o.partial = ws.loss_partial; o.npix = n * 16384;
+    o.up5 = m.in[11].p; o.w = fm_w1(r, 11); o.bias = fm_bias(r, 11); o.img = images;
+    o.g6 = m.in[12].p; o.recon = recon; o.partial = ws.loss_partial; o.npix = n * 16384;
     KTimer kt("k_ae_out_fwd_loss", st);
     hipLaunchKernelGGL(k_ae_out_fwd_loss, dim3((unsigned)((o.npix + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, o);
   }
@@ -461,36 +473,19 @@ static int ae_forward_loss(hipStream_t st, const float* params, float* running, 
 static int ae_backward(hipStream_t st, const float* params, int64_t n, float* grad, const AeWs& aw, const FmStatSync* sync,
                        FmBucketEvents* buckets) {
   const FmWs& ws = aw.fm;
-  const float* P = params;
-  auto W1 = [&](int l) { return P + fm_param_offset(kAeNet, l, false); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kAeNet, l)); };
-  auto GW = [&](int l) { return grad + fm_param_offset(kAeNet, l, false); };
-  auto BN = [&](int b) { return fm_bn_at(kAeNet, b, params, nullptr, grad, sync); };
-  float* const* t = aw.t;
+  const FmMaps m = ae_maps(aw);
+  const FmRun r = {st, kAeNet, m, ws, n, params, nullptr, grad, sync};
   int rc;
-  FmSlabPlan plan;
-  memset(&plan, 0, sizeof(plan));
-  plan.a.remap_seg = -1;
+  FmSlabPlan plan = fm_plan_new();
   // bucket b is complete behind everything launched so far but the row-chunk slabs of its layers: sum them now, then
   // record its event
   auto close_bucket = [&](int b) -> int {
     if (buckets == nullptr) return NDP_OK;
-    const int r = fm_slab_sums(st, plan);
-    plan.a.nseg = 0; plan.a.remap_seg = -1; plan.a.block_begin[0] = 0; plan.blocks = 0;   // (slab memory is not reused: plan.used keeps growing)
-    if (r != NDP_OK) return r;
+    const int rs = fm_slab_sums(st, plan);
+    fm_plan_reset(plan);
+    if (rs != NDP_OK) return rs;
     if (hipEventRecord(buckets->ev[b], st) != hipSuccess) return fail(NDP_E_LAUNCH, "autoencoder: hipEventRecord failed");
     return NDP_OK;
-  };
-  auto bias_finish = [&](int i) -> int {                               // conv6 / conv5 / conv4 (statistics slot 20 + i)
-    const int layer[3] = {5, 4, 3};
-    FmBiasFinishArgs bf;
-    memset(&bf, 0, sizeof(bf));
-    bf.fin = fm_fin(20 + i, 1, 1, ws);
-    bf.fin.out1 = grad + fm_param_offset(kAeNet, layer[i], true);
-    bf.cols = fm_stat_cols(20 + i);
-    KTimer kt("k_fm_bias_finish", st);
-    hipLaunchKernelGGL(k_fm_bias_finish, dim3(1), dim3(kThreads), 0, st, bf);
-    return check_launch("k_fm_bias_finish");
   };
   const int64_t in_pix = n * 4096;
   {
@@ -501,84 +496,56 @@ static int ae_backward(hipStream_t st, const float* params, int64_t n, float* gr
     if (nblk > kFmSlabCap / kAeOutW) nblk = kFmSlabCap / kAeOutW;
     o.rows_per_block = (in_pix + nblk - 1) / nblk;
     nblk = (in_pix + o.rows_per_block - 1) / o.rows_per_block;
-    o.up5 = t[AET_U5]; o.g6 = t[AET_G6]; o.slabs = ws.slabs; o.npix = in_pix;
-    FmSlabSumArgs& ps = plan.a;
-    ps.slabs[ps.nseg] = o.slabs; ps.grad[ps.nseg] = GW(11); ps.nchunks[ps.nseg] = (int)nblk; ps.n4[ps.nseg] = kAeOutW / 4;
-    ps.block_begin[ps.nseg] = plan.blocks;
-    plan.blocks += (kAeOutW / 4 + kThreads - 1) / kThreads;
-    ps.block_begin[++ps.nseg] = plan.blocks;
-    plan.used += nblk * kAeOutW;
+    o.up5 = m.in[11].p; o.g6 = m.in[12].p; o.npix = in_pix;
+    o.slabs = fm_plan_append(plan, ws, grad + fm_param_offset(kAeNet, 11, false), nblk, kAeOutW, kAeOutW / 4);
     KTimer kt("k_ae_out_wgrad", st);
     hipLaunchKernelGGL(k_ae_out_wgrad, dim3((unsigned)nblk), dim3(kThreads), 0, st, o);
   }
-  AE_TRY(check_launch("k_ae_out_wgrad"));
+  FM_TRY(check_launch("k_ae_out_wgrad"));
   {
     // deconv6's data gradient + the BatchNorm-backward sums of deconv5_bn over it
     AeOutArgs o;
     memset(&o, 0, sizeof(o));
-    o.w = W1(11); o.g6 = t[AET_G6]; o.du5 = t[AET_DU5]; o.npix = in_pix;
-    const FmEpReq rq = fm_ep_bn_bwd(7, {t[AET_RAWU5], 64}, {t[AET_U5], 64}, ws);
-    fm_ep_fill(o.ep, rq, ws);
+    o.w = fm_w1(r, 11); o.g6 = m.in[12].p; o.du5 = m.din[11].p; o.npix = in_pix;
+    fm_ep_fill(o.ep, fm_ep_bn_bwd_of(r, 10), ws);
     KTimer kt("k_ae_out_dgrad", st);
     hipLaunchKernelGGL(k_ae_out_dgrad, dim3((unsigned)((in_pix + kAeDgradRows - 1) / kAeDgradRows)), dim3(kThreads), 0, st, o);
   }
-  AE_TRY(check_launch("k_ae_out_dgrad"));
+  FM_TRY(check_launch("k_ae_out_dgrad"));
   // deconv5 .. deconv2: dense = the layer's input map, gathered = d(raw output) at the 4x4 stride-2 taps; every data
   // gradient leaves the sums the next BatchNorm backward needs
-  AE_TRY(fm_bn_bwd_at(st, 7, {t[AET_RAWU5], 64}, {t[AET_U5], 64}, {t[AET_DU5], 64}, n * 4096, BN(7), ws));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv5]", {t[AET_U4], 128}, 32, 128, {t[AET_RAWU5], 64}, 64, 2, 4, 1, 64, n, GW(10), ws, plan));
-  FmEpReq rq = fm_ep_bn_bwd(6, {t[AET_RAWU4], 128}, {t[AET_U4], 128}, ws);
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv5]", 0, {t[AET_RAWU5], 64}, 64, 2, W1(10), nullptr, {t[AET_DU4], 128}, 32, 32, n, 64, 128, 4, 1, 0, 0, ws, 0, &rq));
-  AE_TRY(fm_bn_bwd_at(st, 6, {t[AET_RAWU4], 128}, {t[AET_U4], 128}, {t[AET_DU4], 128}, n * 1024, BN(6), ws));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv4]", {t[AET_U3], 256}, 16, 256, {t[AET_RAWU4], 128}, 32, 2, 4, 1, 128, n, GW(9), ws, plan));
-  rq = fm_ep_bn_bwd(5, {t[AET_RAWU3], 256}, {t[AET_U3], 256}, ws);
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv4]", 0, {t[AET_RAWU4], 128}, 32, 2, W1(9), nullptr, {t[AET_DU3], 256}, 16, 16, n, 128, 256, 4, 1, 0, 0, ws, 0, &rq));
-  AE_TRY(fm_bn_bwd_at(st, 5, {t[AET_RAWU3], 256}, {t[AET_U3], 256}, {t[AET_DU3], 256}, n * 256, BN(5), ws));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv3]", {t[AET_U2], 512}, 8, 512, {t[AET_RAWU3], 256}, 16, 2, 4, 1, 256, n, GW(8), ws, plan));
-  AE_TRY(close_bucket(0));
-  rq = fm_ep_bn_bwd(4, {t[AET_RAWU2], 512}, {t[AET_U2], 512}, ws);
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv3]", 0, {t[AET_RAWU3], 256}, 16, 2, W1(8), nullptr, {t[AET_DU2], 512}, 8, 8, n, 256, 512, 4, 1, 0, 0, ws, 0, &rq));
-  AE_TRY(fm_bn_bwd_at(st, 4, {t[AET_RAWU2], 512}, {t[AET_U2], 512}, {t[AET_DU2], 512}, n * 64, BN(4), ws));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv2]", {t[AET_U1], 1024}, 4, 1024, {t[AET_RAWU2], 512}, 8, 2, 4, 1, 512, n, GW(7), ws, plan));
-  AE_TRY(close_bucket(1));
-  rq = fm_ep_bn_bwd(3, {t[AET_RAWU1], 1024}, {t[AET_U1], 1024}, ws);
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv2]", 0, {t[AET_RAWU2], 512}, 8, 2, W1(7), nullptr, {t[AET_DU1], 1024}, 4, 4, n, 512, 1024, 4, 1, 0, 0, ws, 0, &rq));
+  for (int l = 10; l >= 7; --l) {
+    FM_TRY(fm_layer_bn_bwd(r, l));
+    FM_TRY(fm_layer_wgrad(r, st, l, plan));
+    if (l <= 8) FM_TRY(close_bucket(8 - l));                            // bucket 0 ends with deconv3, 1 with deconv2
+    FM_TRY(fm_layer_dgrad(r, l, 0, fm_ep_bn_bwd_of(r, l - 1)));
+  }
   // deconv1: a 4x4 "image" of d(raw) per code
-  AE_TRY(fm_bn_bwd_at(st, 3, {t[AET_RAWU1], 1024}, {t[AET_U1], 1024}, {t[AET_DU1], 1024}, n * 16, BN(3), ws));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.deconv1]", {t[AET_Z], 128}, 1, 128, {t[AET_RAWU1], 1024}, 4, 1, 4, 0, 1024, n, GW(6), ws, plan));
+  FM_TRY(fm_layer_bn_bwd(r, 6));
+  FM_TRY(fm_layer_wgrad(r, st, 6, plan));
   // conv6: d code, whose column sums are conv6's bias gradient
-  rq = fm_ep_bias(4, 20, {nullptr, 0});
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.deconv1]", 0, {t[AET_RAWU1], 1024}, 4, 1, W1(6), nullptr, {t[AET_DZ], 128}, 1, 1, n, 1024, 128, 4, 0, 0, 0, ws, 0, &rq));
-  AE_TRY(bias_finish(0));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv6]", {t[AET_DZ], 128}, 1, 128, {t[AET_A5], 1024}, 4, 1, 4, 0, 1024, n, GW(5), ws, plan));
-  AE_TRY(close_bucket(2));
+  FM_TRY(fm_layer_dgrad(r, 6, 0, fm_ep_bias(4, 20, {nullptr, 0})));
+  FM_TRY(fm_bias_finish(r, st, 0));
+  FM_TRY(fm_layer_wgrad(r, st, 5, plan));
+  FM_TRY(close_bucket(2));
   // conv5, conv4 (ReLU, no BatchNorm): the ReLU's backward is applied as the finished gradient is written
-  rq = fm_ep_bias(3, 21, {t[AET_A5], 1024});
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv6]", 3, {t[AET_DZ], 128}, 1, 1, W2(5), nullptr, {t[AET_DA5], 1024}, 4, 1, n, 128, 1024, 1, 0, 0, 0, ws, 0, &rq));
-  AE_TRY(bias_finish(1));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv5]", {t[AET_DA5], 1024}, 4, 1024, {t[AET_A4], 512}, 8, 2, 3, 1, 512, n, GW(4), ws, plan));
-  AE_TRY(close_bucket(3));
-  rq = fm_ep_bias(3, 22, {t[AET_A4], 512});
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv5]", 2, {t[AET_DA5], 1024}, 4, 1, W2(4), nullptr, {t[AET_DA4], 512}, 8, 4, n, 1024, 512, 2, 0, 0, 0, ws, 0, &rq));
-  AE_TRY(bias_finish(2));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv4]", {t[AET_DA4], 512}, 8, 512, {t[AET_A3], 256}, 16, 2, 3, 1, 256, n, GW(3), ws, plan));
-  rq = fm_ep_bn_bwd(2, {t[AET_RAW3], 256}, {t[AET_A3], 256}, ws);
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv4]", 2, {t[AET_DA4], 512}, 8, 1, W2(3), nullptr, {t[AET_DA3], 256}, 16, 8, n, 512, 256, 2, 0, 0, 0, ws, 0, &rq));
-  // conv3 .. conv1 (the images need no gradient: conv1's data gradient is skipped)
-  AE_TRY(fm_bn_bwd_at(st, 2, {t[AET_RAW3], 256}, {t[AET_A3], 256}, {t[AET_DA3], 256}, n * 256, BN(2), ws));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv3]", {t[AET_RAW3], 256}, 16, 256, {t[AET_A2], 128}, 32, 2, 3, 1, 128, n, GW(2), ws, plan));
-  rq = fm_ep_bn_bwd(1, {t[AET_RAW2], 128}, {t[AET_A2], 128}, ws);
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv3]", 2, {t[AET_RAW3], 256}, 16, 1, W2(2), nullptr, {t[AET_DA2], 128}, 32, 16, n, 256, 128, 2, 0, 0, 0, ws, 0, &rq));
-  AE_TRY(fm_bn_bwd_at(st, 1, {t[AET_RAW2], 128}, {t[AET_A2], 128}, {t[AET_DA2], 128}, n * 1024, BN(1), ws));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv2]", {t[AET_RAW2], 128}, 32, 128, {t[AET_A1], 64}, 64, 2, 3, 1, 64, n, GW(1), ws, plan));
-  rq = fm_ep_bn_bwd(0, {t[AET_RAW1], 64}, {t[AET_A1], 64}, ws);
-  AE_TRY(fm_gemm(st, "k_fm_dgrad[ae.conv2]", 2, {t[AET_RAW2], 128}, 32, 1, W2(1), nullptr, {t[AET_DA1], 64}, 64, 32, n, 128, 64, 2, 0, 0, 0, ws, 0, &rq));
-  AE_TRY(fm_bn_bwd_at(st, 0, {t[AET_RAW1], 64}, {t[AET_A1], 64}, {t[AET_DA1], 64}, n * 4096, BN(0), ws));
-  AE_TRY(fm_wgrad(st, "k_fm_wgrad[ae.conv1]", {t[AET_RAW1], 64}, 64, 64, {t[AET_COLS], 32}, 64, 1, 1, 0, 32, n, GW(0), ws, plan, true));   // (columns)
+  FM_TRY(fm_layer_dgrad(r, 5, 0, fm_ep_bias(3, 21, m.in[5])));
+  FM_TRY(fm_bias_finish(r, st, 1));
+  FM_TRY(fm_layer_wgrad(r, st, 4, plan));
+  FM_TRY(close_bucket(3));
+  FM_TRY(fm_layer_dgrad(r, 4, 0, fm_ep_bias(3, 22, m.in[4])));
+  FM_TRY(fm_bias_finish(r, st, 2));
+  FM_TRY(fm_layer_wgrad(r, st, 3, plan));
+  FM_TRY(fm_layer_dgrad(r, 3, 0, fm_ep_bn_bwd_of(r, 2)));
+  // conv3 .. conv1 (the images need no gradient: conv1's data gradient is skipped; its weight gradient: the columns)
+  for (int l = 2; l >= 0; --l) {
+    FM_TRY(fm_layer_bn_bwd(r, l));
+    FM_TRY(fm_layer_wgrad(r, st, l, plan));
+    if (l > 0) FM_TRY(fm_layer_dgrad(r, l, 0, fm_ep_bn_bwd_of(r, l - 1)));
+  }
   if (buckets == nullptr) return fm_slab_sums(st, plan);
-  AE_TRY(close_bucket(4));
+  FM_TRY(close_bucket(4));
   return close_bucket(5);                                              // (nothing left to sum: the BatchNorm parameters)
-#undef AE_TRY
 }
 
 // one training iteration's gradients: ndp_ae_train_grads (sync, buckets null) and ndp_ae_train_grads_dp
@@ -621,7 +588,10 @@ static const FmLayer kAeDec[kAeDecLayers] = {
     {FM_DECONV, 128, 64, 32, 64, 4, 2, 1, 128, 64, FM_P2_DECONV_S2},    // 4 deconv5
     {FM_DECONV, 64, 3, 64, 128, 4, 2, 1, 64, 4, FM_P2_NONE},            // 5 deconv6 (k_ae_out_fwd reads P1)
 };
-static const FmNet kAeDecNet = {kAeDec, kAeDecLayers, 0, nullptr, nullptr, 0};
+static const FmLabels kAeDecLabels[kAeDecLayers] = {
+    FM_LABELS("aed.deconv1"), FM_LABELS("aed.deconv2"), FM_LABELS("aed.deconv3"), FM_LABELS("aed.deconv4"),
+    FM_LABELS("aed.deconv5"), FM_LABELS("aed.deconv6")};
+static const FmNet kAeDecNet = {kAeDec, kAeDecLayers, 0, nullptr, nullptr, 0, kAeDecLabels};
 // Workspace (floats): [P2 of deconv1..5][up1..up5 x min(n, kAeDecPass) images][squared-error partial sums: 64 per image
 // of a pass][the running sum of the per-image errors: one double][split-K partial sums]
 enum AeDecTensor { ADT_U1 = 0, ADT_U2, ADT_U3, ADT_U4, ADT_U5, ADT_COUNT };
@@ -637,20 +607,22 @@ static int64_t ae_dec_ws_floats(int64_t n) {
   return ae_dec_tensor_offset(cap, ADT_COUNT) + cap * 64 + 4 + kFmPartCap;
 }
 
-// one pass: np <= kAeDecPass codes -> up5 in the workspace
+// where a pass' maps live (FmMaps): the caller's codes, then up1 .. up5 (t: the workspace tensors), each layer writing the next one's input
+static FmMaps ae_dec_maps(const float* codes, float* const* t) {
+  FmMaps m;
+  memset(&m, 0, sizeof(m));
+  m.in[0] = {const_cast<float*>(codes), 128};
+  for (int i = 0; i < ADT_COUNT; ++i) m.in[i + 1] = {t[i], kAeDec[i].cout_pad};
+  fm_maps_close(m, kAeDecNet);
+  return m;
+}
+
+// one pass: np <= kAeDecPass codes -> up5 in the workspace; every layer with bias + ReLU in its epilogue
 static int ae_decode_pass(hipStream_t st, const float* P, const float* codes, int64_t np, const FmWs& ws, float* const* t) {
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kAeDecNet, l)); };
-  auto B = [&](int l) { return P + fm_param_offset(kAeDecNet, l, true); };
+  const FmMaps m = ae_dec_maps(codes, t);
+  const FmRun r = {st, kAeDecNet, m, ws, np, P, nullptr, nullptr, nullptr};
   int rc;
-#define AE_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
-  AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv1]", 3, {const_cast<float*>(codes), 128}, 1, 1, W2(0), B(0), {t[ADT_U1], 1024}, 4, 1, np, 128, 1024, 1, 0, 1, 0, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv2]", 1, {t[ADT_U1], 1024}, 4, 1, W2(1), B(1), {t[ADT_U2], 512}, 8, 4, np, 1024, 512, 2, 0, 1, 0, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv3]", 1, {t[ADT_U2], 512}, 8, 1, W2(2), B(2), {t[ADT_U3], 256}, 16, 8, np, 512, 256, 2, 0, 1, 0, ws));
-  AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv4]", 1, {t[ADT_U3], 256}, 16, 1, W2(3), B(3), {t[ADT_U4], 128}, 32, 16, np, 256, 128, 2, 0, 1, 0, ws));
-  if (np * 1024 / kFmBM * 2 >= 256)                                    // (as ae_forward_loss: enough tiles from 16 images)
-    AE_TRY(fm_deconv32(st, "k_fm_gemm[aed.deconv5]", {t[ADT_U4], 128}, 32, W2(4), B(4), {t[ADT_U5], 64}, np, 128, 64, fm_ep_none(), ws, true));
-  else AE_TRY(fm_gemm(st, "k_fm_gemm[aed.deconv5]", 1, {t[ADT_U4], 128}, 32, 1, W2(4), B(4), {t[ADT_U5], 64}, 64, 32, np, 128, 64, 2, 0, 1, 0, ws));
-#undef AE_TRY
+  for (int l = 0; l < 5; ++l) FM_TRY(fm_layer_fwd(r, l, 1, fm_ep_none()));
   return NDP_OK;
 }
 
@@ -715,6 +687,8 @@ static int ae_decode(const float* params, const float* codes, int64_t n, float* 
   }
   return NDP_OK;
 }
+
+#undef FM_TRY
 
 }  // namespace ndp
 

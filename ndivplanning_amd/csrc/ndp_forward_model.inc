@@ -35,16 +35,24 @@ namespace ndp {
 // ------------------------------------------------------------------------------------------ network tables
 // A network of this family is an FmNet: its layers, how many of the BatchNorms below it uses, and its gradient buckets.
 // Every size, offset and pack / optimizer segment on the host side is derived from that table (the helpers below,
-// fm_pack, fm_adam_pack, fm_layout, fm_bucket_range); the instances are kFmNet here and kAeNet in ndp_autoencoder.inc.
-// A further network adds its table, its workspace tensors and its own forward / backward launch sequence -- nothing else.
+// fm_pack, fm_adam_pack, fm_layout, fm_bucket_range), and so is the geometry of every layer launch (fm_geom; fm_layer_fwd,
+// fm_layer_dgrad, fm_layer_wgrad); the instances are kFmNet here, kAeNet and kAeDecNet in ndp_autoencoder.inc.
+// A further network adds its table with its launch labels, its workspace tensors, where its maps live in them (an FmMaps)
+// and its launch sequences: one line per launch that names the layer -- no size, stride or tensor offset is written there.
 enum { FM_CONV = 0, FM_DECONV = 1 };
 // p2: how the layer's second weight order is made from P1 -- a k_fm_pack kind (see there), or none (the layer reads P1 only)
 enum { FM_P2_NONE = -1, FM_P2_CONV_S2 = 0, FM_P2_REFINE = 1, FM_P2_CONV6 = 2, FM_P2_DECONV_S2 = 3, FM_P2_DECONV1 = 4, FM_P2_COLUMNS = 5 };
 struct FmLayer { int kind, cin, cout, hin, hout, ksz, stride, pad, cin_pad, cout_pad, p2; };
+// kernel-timer labels of a layer's launches: forward, data gradient, weight gradient (static strings: benchmarks and tests
+// filter on them)
+enum { FM_FWD = 0, FM_DGRAD = 1, FM_WGRAD = 2 };
+struct FmLabels { const char* of[3]; };
+#define FM_LABELS(name) {{"k_fm_gemm[" name "]", "k_fm_dgrad[" name "]", "k_fm_wgrad[" name "]"}}
 struct FmNet {
   const FmLayer* layer; int layers;
   int bns;                                              // it uses the first `bns` of kFmBnC / kFmBnLayer
   const int* bucket_first; const int* bucket_end; int buckets;   // layer ranges [first, end); first -1: the BatchNorm parameters
+  const FmLabels* label;
 };
 constexpr int kFmLayers = 14;
 static const FmLayer kFm[kFmLayers] = {
@@ -63,6 +71,10 @@ static const FmLayer kFm[kFmLayers] = {
     {FM_CONV, 32, 16, 128, 128, 3, 1, 1, 32, 16, FM_P2_REFINE},         // 12 decoder.conv_refine_1
     {FM_CONV, 16, 3, 128, 128, 3, 1, 1, 32, 4, FM_P2_REFINE},           // 13 decoder.conv_refine_2
 };
+static const FmLabels kFmLabels[kFmLayers] = {
+    FM_LABELS("conv1"), FM_LABELS("conv2"), FM_LABELS("conv3"), FM_LABELS("conv4"), FM_LABELS("conv5"), FM_LABELS("conv6"),
+    FM_LABELS("deconv1"), FM_LABELS("deconv2"), FM_LABELS("deconv3"), FM_LABELS("deconv4"), FM_LABELS("deconv5"),
+    FM_LABELS("deconv6"), FM_LABELS("refine1"), FM_LABELS("refine2")};
 // Gradient buckets for a data-parallel driver (SURVEY.md section 8e / 8f-4: "RCCL all-reduce ... overlapped with backward"):
 // ranges of the flat gradient in the order in which the backward pass completes them.  The weight gradients are produced
 // last layer first, so the range of layers 9..13 is final while the data-gradient chain is still at deconv3; one event per
@@ -80,7 +92,13 @@ constexpr int kFmBns = 10;
 constexpr int kFmBnC[kFmBns] = {64, 128, 256, 1024, 512, 256, 128, 64, 32, 16};   // conv1..3, deconv1..6, conv_refine_1
 static const int kFmBnLayer[kFmBns] = {0, 1, 2, 6, 7, 8, 9, 10, 11, 12};
 constexpr float kFmBnEps = 1e-5f, kFmBnMomentum = 0.1f;
-static const FmNet kFmNet = {kFm, kFmLayers, kFmBns, kFmBucketFirst, kFmBucketEnd, kFmBuckets};
+static const FmNet kFmNet = {kFm, kFmLayers, kFmBns, kFmBucketFirst, kFmBucketEnd, kFmBuckets, kFmLabels};
+// the BatchNorm behind layer l of `net`, or -1
+static int fm_bn_of(const FmNet& net, int l) {
+  for (int b = 0; b < net.bns; ++b)
+    if (kFmBnLayer[b] == l) return b;
+  return -1;
+}
 // channels of the BatchNorms before b: where b's batch mean / invstd / mean residual start in their scratch vectors
 constexpr int fm_bn_stat_index(int b) {
   int o = 0;
@@ -2270,6 +2288,8 @@ __global__ __launch_bounds__(kThreads) void k_fm_r1_dgrad(FmR1Args a) {
 // ------------------------------------------------------------------------------------------ host side
 // Workspace (floats): [P2 weights][statistics scratch][per-image maps x n][loss partial sums][level-1 statistics partial
 // sums][split-K partial sums][weight-gradient slabs]
+// the launch sequences (here and in ndp_autoencoder.inc): a step that fails ends the sequence with its code, in `int rc`
+#define FM_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
 constexpr int64_t kFmPartCap = (int64_t)12 << 20;      // split-K partial sums (floats)
 constexpr int64_t kFmSlabCap = (int64_t)32 << 20;      // row-chunk slabs of the weight gradients (floats)
 enum FmTensor {
@@ -2407,15 +2427,15 @@ constexpr int kFmSplitTarget = 256;
 // rq: statistics of the finished output, from this launch's epilogue or -- with a K split -- from the split sums'.
 static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int SH, int ss, const float* w, const float* bias,
                    FmView out, int OH, int GH, int64_t n, int C, int N, int KH, int pad, int act, int accumulate,
-                   const FmWs& ws, int zero_to = 0, const FmEpReq* rq = nullptr) {
+                   const FmWs& ws, const FmEpReq* rq = nullptr) {
   FmGemmArgs a;
   memset(&a, 0, sizeof(a));
   a.src = src.p; a.w = w; a.bias = bias; a.out = out.p; a.part = ws.part;
   a.src_ld = src.ld; a.SH = a.SW = SH; a.ss = ss;
   a.out_ld = out.ld; a.OH = a.OW = OH;
   a.GH = a.GW = GH; a.M = (int)(n * GH * GH); a.C = C; a.N = N;
-  a.mode = mode; a.KH = a.KW = KH; a.pad = pad; a.act = act; a.accumulate = accumulate; a.zero_to = zero_to;
-  if (mode == 3 && a.M <= 64 && C <= kFmRowsMaxC && C % 32 == 0 && N % 16 == 0 && zero_to == 0) {
+  a.mode = mode; a.KH = a.KW = KH; a.pad = pad; a.act = act; a.accumulate = accumulate;
+  if (mode == 3 && a.M <= 64 && C <= kFmRowsMaxC && C % 32 == 0 && N % 16 == 0) {
     // a few images: one wave per (class, 16 columns), weights straight into MFMA operands (k_fm_rows_cls)
     const FmEpReq none0 = fm_ep_none();
     fm_ep_fill(a.ep, rq ? *rq : none0, ws);
@@ -2435,7 +2455,7 @@ static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int 
   // (kFmSplitTarget), each with at least 8 K steps
   const int64_t tiles = (int64_t)a.mtiles * a.ntiles * ncls;
   int nsplit = 1;
-  while (zero_to == 0 && tiles * nsplit < kFmSplitTarget && nsplit * 8 <= ksteps && nsplit < 128 &&
+  while (tiles * nsplit < kFmSplitTarget && nsplit * 8 <= ksteps && nsplit < 128 &&
          (int64_t)ncls * nsplit * 2 * a.M * N <= kFmPartCap) nsplit *= 2;
   a.steps_per_split = (ksteps + nsplit - 1) / nsplit;
   a.nsplit = (ksteps + a.steps_per_split - 1) / a.steps_per_split;
@@ -2481,6 +2501,25 @@ static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int 
 // Layers whose weight gradient is computed in row chunks leave their slabs in the workspace; fm_slab_sums adds them all
 // in one launch at the end of the backward pass.
 struct FmSlabPlan { FmSlabSumArgs a; int64_t used; int blocks; };
+// no segment planned (a new plan; a bucket's slabs summed -- slab memory is not reused: plan.used keeps growing)
+static void fm_plan_reset(FmSlabPlan& plan) { plan.a.nseg = 0; plan.a.remap_seg = -1; plan.a.block_begin[0] = 0; plan.blocks = 0; }
+static FmSlabPlan fm_plan_new() {
+  FmSlabPlan plan;
+  memset(&plan, 0, sizeof(plan));
+  fm_plan_reset(plan);
+  return plan;
+}
+// the next segment: `nchunks` slabs of chunk_floats floats at ws.slabs + plan.used, their first n4 float4 summed into grad
+static float* fm_plan_append(FmSlabPlan& plan, const FmWs& ws, float* grad, int64_t nchunks, int64_t chunk_floats, int64_t n4) {
+  FmSlabSumArgs& p = plan.a;
+  float* slabs = ws.slabs + plan.used;
+  p.slabs[p.nseg] = slabs; p.grad[p.nseg] = grad; p.nchunks[p.nseg] = (int)nchunks; p.n4[p.nseg] = n4;
+  p.block_begin[p.nseg] = plan.blocks;
+  plan.blocks += (int)((n4 + kThreads - 1) / kThreads);
+  p.block_begin[++p.nseg] = plan.blocks;
+  plan.used += nchunks * chunk_floats;
+  return slabs;
+}
 static int fm_wgrad(hipStream_t st, const char* label, FmView dense, int DH, int J, FmView gath, int SH, int ss, int KH,
                     int pad, int C, int64_t n, float* grad, const FmWs& ws, FmSlabPlan& plan, bool conv1_columns = false) {
   FmWgradArgs a;
@@ -2504,16 +2543,10 @@ static int fm_wgrad(hipStream_t st, const char* label, FmView dense, int DH, int
   const int nchunks = (a.M + a.rows_per_chunk - 1) / a.rows_per_chunk;
   if (conv1_columns && (plan.a.nseg >= kFmMaxSeg || (int64_t)nchunks * a.slab_floats > kFmSlabCap - plan.used))
     return fail(NDP_E_UNSUPPORTED, "fm_wgrad: no slab space for conv1's column gradient");
-  a.slabs = (nchunks == 1 && !conv1_columns) ? grad : ws.slabs + plan.used;
+  a.slabs = grad;
   if (nchunks > 1 || conv1_columns) {
-    FmSlabSumArgs& p = plan.a;
-    if (conv1_columns) p.remap_seg = p.nseg;
-    const int64_t n4 = conv1_columns ? 64 * 9 * 8 : a.slab_floats / 4;
-    p.slabs[p.nseg] = a.slabs; p.grad[p.nseg] = grad; p.nchunks[p.nseg] = nchunks; p.n4[p.nseg] = n4;
-    p.block_begin[p.nseg] = plan.blocks;
-    plan.blocks += (int)((n4 + kThreads - 1) / kThreads);
-    p.block_begin[++p.nseg] = plan.blocks;
-    plan.used += (int64_t)nchunks * a.slab_floats;
+    if (conv1_columns) plan.a.remap_seg = plan.a.nseg;
+    a.slabs = fm_plan_append(plan, ws, grad, nchunks, a.slab_floats, conv1_columns ? 64 * 9 * 8 : a.slab_floats / 4);
   }
   const dim3 grid((unsigned)tiles, (unsigned)nchunks);
   KTimer kt(label, st);
@@ -2613,10 +2646,6 @@ static int fm_bn_fwd_at(hipStream_t st, int b, FmView raw, int64_t P, FmView des
   hipLaunchKernelGGL(k_fm_bn_apply, fm_elt_grid(P, e.zero_to > C ? e.zero_to : C), dim3(kThreads), 0, st, e);
   return check_launch("k_fm_bn_apply");
 }
-static int fm_bn_fwd(hipStream_t st, int b, FmView raw, int64_t P, FmView dest, const float* params, float* running,
-                     int training, const FmWs& ws) {
-  return fm_bn_fwd_at(st, b, raw, P, dest, fm_bn_at(kFmNet, b, params, running, nullptr, &g_fm_sync), training, ws);
-}
 // BatchNorm b + ReLU backward: raw (x) := d loss / d x, from the sums the launch that produced dy accumulated; writes the
 // BatchNorm weight / bias gradients and the gradient of the convolution bias in front of it (layer l: the column sum of
 // dx -- zero but for rounding, as in the reference)
@@ -2640,10 +2669,6 @@ static int fm_bn_bwd_at(hipStream_t st, int b, FmView raw, FmView y, FmView dy, 
     hipLaunchKernelGGL(k_fm_bn_bwd_apply, fm_elt_grid(P, C), dim3(kThreads), 0, st, e);
   }
   return check_launch("k_fm_bn_bwd_apply");
-}
-static int fm_bn_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int64_t P, const float* params, float* grad,
-                     const FmWs& ws) {
-  return fm_bn_bwd_at(st, b, raw, y, dy, P, fm_bn_at(kFmNet, b, params, nullptr, grad, &g_fm_sync), ws);
 }
 
 // deconv6's forward pass, the four parity classes per workgroup (k_fm_deconv32)
@@ -2676,6 +2701,170 @@ static int fm_r1(hipStream_t st, const char* label, bool dgrad, const float* src
   if (dgrad) hipLaunchKernelGGL(k_fm_r1_dgrad, dim3(blocks), dim3(kThreads), 0, st, a);
   else hipLaunchKernelGGL(k_fm_r1_fwd, dim3(blocks), dim3(kThreads), 0, st, a);
   return check_launch(label);
+}
+
+// ------------------------------------------------------------------------------------------ layer launches
+// What a launch of layer l needs beyond its tensors follows from the layer's table row: fm_geom, a pure function (the
+// CPU test tests/test_fm_geometry_host.py compares it with the recorded argument lists for every layer of every network).
+//   forward          conv1 as a one-tap GEMM over its columns (FM_P2_COLUMNS); a convolution gathers its taps (mode 0, P1);
+//                    deconv1 is sixteen one-tap classes (mode 3, P2); a stride-2 transposed convolution four 2x2 classes
+//                    (mode 1, P2) or, all four classes per workgroup, k_fm_deconv32 (see fm_geom)
+//   data gradient    of a transposed convolution: the convolution of d(raw output) with P1 (mode 0); of conv6: sixteen
+//                    one-tap classes (mode 3, P2); of a stride-2 convolution: four parity classes (mode 2, P2)
+//   weight gradient  dense = d(raw output) of a convolution / the input of a transposed one (DH x DH pixels, J channels),
+//                    gathered = the other one (SH x SH pixels, C channels)
+// mode < 0: the layer has no launch of that kind here (the refinement stage and the autoencoder's output layer have their
+// own kernels; conv1's data gradient is k_fm_conv1_dgrad).
+struct FmGeom {
+  int mode, SH, ss, OH, GH, C, N, KH, pad;   // fm_gemm's arguments (weight gradient: SH, ss, C, KH, pad of the gathered map)
+  int p2;                                    // the launch reads the second weight order
+  int deconv32;                              // forward: k_fm_deconv32 instead of mode 1
+  int DH, J, columns;                        // weight gradient: the dense map; conv1's column form
+};
+static FmGeom fm_geom(const FmNet& net, int l, int dir, int64_t n) {
+  const FmLayer& L = net.layer[l];
+  const bool conv = L.kind == FM_CONV, columns = L.p2 == FM_P2_COLUMNS;
+  FmGeom g;
+  memset(&g, 0, sizeof(g));
+  g.mode = -1;
+  if (L.p2 == FM_P2_NONE || (L.p2 == FM_P2_REFINE && dir != FM_WGRAD) || (columns && dir == FM_DGRAD)) return g;
+  g.ss = L.stride; g.KH = L.ksz; g.pad = L.pad;
+  if (dir == FM_WGRAD) {
+    g.mode = 0;
+    g.DH = conv ? L.hout : L.hin; g.J = conv ? L.cout_pad : L.cin_pad;
+    g.SH = conv ? L.hin : L.hout; g.C = conv ? L.cin_pad : L.cout_pad;
+    g.columns = columns;
+  } else if (dir == FM_FWD) {
+    g.SH = L.hin; g.OH = L.hout; g.GH = conv ? L.hout : L.hin; g.C = L.cin_pad; g.N = L.cout_pad;
+    g.mode = conv ? 0 : (L.p2 == FM_P2_DECONV1 ? 3 : 1);
+    g.p2 = !conv || columns;
+    // k_fm_deconv32: 32 output channels always; 64 as two halves where those make enough tiles (deconv5: from 16 images)
+    g.deconv32 = g.mode == 1 && (L.cout_pad == 32 || (L.cout_pad == 64 && n * L.hin * L.hin / kFmBM * 2 >= 256));
+  } else {
+    g.SH = L.hout; g.OH = L.hin; g.GH = conv ? L.hout : L.hin; g.C = L.cout_pad; g.N = L.cin_pad;
+    g.mode = !conv ? 0 : (L.p2 == FM_P2_CONV6 ? 3 : 2);
+    g.p2 = conv;
+  }
+  if (columns) { g.SH = L.hout; g.ss = 1; g.KH = 1; g.pad = 0; }            // (the taps are in the columns)
+  if (g.mode == 1 || g.mode == 2) { g.ss = 1; g.KH = 2; g.pad = 0; }        // (per class; k_fm_gemm's fm_class has the rest)
+  if (g.mode == 3) { g.ss = 1; g.KH = 1; g.pad = 0; }
+  return g;
+}
+
+// Where a network's maps live: for layer l its input map, its raw (pre-BatchNorm) output and the gradient of its input
+// map.  in[l + 1] is the activated output of layer l; a layer without BatchNorm writes it directly (fm_maps_close sets
+// raw[l] = in[l + 1]), and the gradient of its raw output is din[l + 1]; a BatchNorm's backward pass overwrites raw[l]
+// with the gradient of the raw output (fm_draw).
+constexpr int kFmMaxLayers = 14;
+struct FmMaps { FmView in[kFmMaxLayers + 1], raw[kFmMaxLayers], din[kFmMaxLayers + 1]; };
+static void fm_maps_close(FmMaps& m, const FmNet& net) {
+  for (int l = 0; l < net.layers; ++l)
+    if (fm_bn_of(net, l) < 0) m.raw[l] = m.in[l + 1];
+}
+static FmView fm_draw(const FmNet& net, const FmMaps& m, int l) { return fm_bn_of(net, l) >= 0 ? m.raw[l] : m.din[l + 1]; }
+// the two maps of a launch of layer l: forward in[l] -> raw[l]; data gradient d(raw) -> din[l]; weight gradient the dense
+// and the gathered map (fm_geom)
+static void fm_layer_views(const FmNet& net, const FmMaps& m, int l, int dir, FmView* a, FmView* b) {
+  const bool conv = net.layer[l].kind == FM_CONV;
+  if (dir == FM_FWD) { *a = m.in[l]; *b = m.raw[l]; }
+  else if (dir == FM_DGRAD) { *a = fm_draw(net, m, l); *b = m.din[l]; }
+  else { *a = conv ? fm_draw(net, m, l) : m.in[l]; *b = conv ? m.in[l] : fm_draw(net, m, l); }
+}
+// The forward model: cat([up, skip]) is one map of twice the channels, the decoder's half in front (`lo`), the encoder's
+// behind it (`hi`); the gradient maps DCAT* the same way.  This is the only place that says so.
+static FmMaps fm_maps(const FmWs& ws) {
+  float* const* t = ws.t;
+  auto lo = [&](int tensor, int ld) { return FmView{t[tensor], ld}; };
+  auto hi = [&](int tensor, int ld) { return FmView{t[tensor] + ld / 2, ld}; };
+  FmMaps m;
+  memset(&m, 0, sizeof(m));
+  m.in[0] = lo(FMT_COLS, 32);    m.raw[0] = lo(FMT_RAW1, 64);                                          // conv1
+  m.in[1] = hi(FMT_CAT6, 128);   m.raw[1] = lo(FMT_RAW2, 128);    m.din[1] = hi(FMT_DCAT6, 128);       // conv2
+  m.in[2] = hi(FMT_CAT5, 256);   m.raw[2] = lo(FMT_RAW3, 256);    m.din[2] = hi(FMT_DCAT5, 256);       // conv3
+  m.in[3] = hi(FMT_CAT4, 512);                                    m.din[3] = hi(FMT_DCAT4, 512);       // conv4
+  m.in[4] = hi(FMT_CAT3, 1024);                                   m.din[4] = hi(FMT_DCAT3, 1024);      // conv5
+  m.in[5] = hi(FMT_CAT2, 2048);                                   m.din[5] = hi(FMT_DCAT2, 2048);      // conv6
+  m.in[6] = lo(FMT_Z, 160);      m.raw[6] = lo(FMT_RAWU1, 1024);  m.din[6] = lo(FMT_DZ, 160);          // deconv1
+  m.in[7] = lo(FMT_CAT2, 2048);  m.raw[7] = lo(FMT_RAWU2, 512);   m.din[7] = lo(FMT_DCAT2, 2048);      // deconv2
+  m.in[8] = lo(FMT_CAT3, 1024);  m.raw[8] = lo(FMT_RAWU3, 256);   m.din[8] = lo(FMT_DCAT3, 1024);      // deconv3
+  m.in[9] = lo(FMT_CAT4, 512);   m.raw[9] = lo(FMT_RAWU4, 128);   m.din[9] = lo(FMT_DCAT4, 512);       // deconv4
+  m.in[10] = lo(FMT_CAT5, 256);  m.raw[10] = lo(FMT_RAWU5, 64);   m.din[10] = lo(FMT_DCAT5, 256);      // deconv5
+  m.in[11] = lo(FMT_CAT6, 128);  m.raw[11] = lo(FMT_RAWU6, 32);   m.din[11] = lo(FMT_DCAT6, 128);      // deconv6
+  m.in[12] = lo(FMT_UP6, 32);    m.raw[12] = lo(FMT_RAWR1, kFmR1LD); m.din[12] = lo(FMT_DUP6, 32);     // conv_refine_1
+  m.in[13] = lo(FMT_R1, kFmR1LD);                                 m.din[13] = lo(FMT_DR1, kFmR1LD);    // conv_refine_2
+  m.in[14] = lo(FMT_Y2, 4);                                                                            // (the pre-tanh output, then its gradient)
+  fm_maps_close(m, kFmNet);
+  return m;
+}
+
+// One pass over a network: what every layer launch of it shares.  running / grad / sync as fm_bn_at takes them.
+struct FmRun {
+  hipStream_t st; const FmNet& net; const FmMaps& m; const FmWs& ws; int64_t n;
+  const float* params; float* running; float* grad; const FmStatSync* sync;
+};
+static const float* fm_w1(const FmRun& r, int l) { return r.params + fm_param_offset(r.net, l, false); }
+static const float* fm_w2(const FmRun& r, int l) { return r.ws.p2 + fm_p2_offset(r.net, l); }
+static const float* fm_bias(const FmRun& r, int l) { return r.params + fm_param_offset(r.net, l, true); }
+static int64_t fm_out_pixels(const FmRun& r, int l) { return r.n * r.net.layer[l].hout * r.net.layer[l].hout; }
+static int fm_no_launch(const FmRun& r, int l, int dir) {
+  return fail(NDP_E_UNSUPPORTED, "forward model: layer %d has no %s launch", l, r.net.label[l].of[dir]);
+}
+
+// forward of layer l: m.raw[l] = act(bias + layer(m.in[l])); act 0 none, 1 ReLU (k_fm_deconv32: those two only)
+static int fm_layer_fwd(const FmRun& r, int l, int act, const FmEpReq& rq) {
+  const FmGeom g = fm_geom(r.net, l, FM_FWD, r.n);
+  if (g.mode < 0) return fm_no_launch(r, l, FM_FWD);
+  const float* w = g.p2 ? fm_w2(r, l) : fm_w1(r, l);
+  const char* label = r.net.label[l].of[FM_FWD];
+  FmView src, out;
+  fm_layer_views(r.net, r.m, l, FM_FWD, &src, &out);
+  if (g.deconv32 && act <= 1) return fm_deconv32(r.st, label, src, g.SH, w, fm_bias(r, l), out, r.n, g.C, g.N, rq, r.ws, act == 1);
+  return fm_gemm(r.st, label, g.mode, src, g.SH, g.ss, w, fm_bias(r, l), out, g.OH, g.GH, r.n, g.C, g.N, g.KH, g.pad, act, 0, r.ws, &rq);
+}
+// data gradient of layer l: m.din[l] (+)= the gradient of its input from the gradient of its raw output; rq: the sums the
+// backward pass of the layer below needs (fm_ep_bn_bwd_of, fm_ep_bias)
+static int fm_layer_dgrad(const FmRun& r, int l, int accumulate, const FmEpReq& rq) {
+  const FmGeom g = fm_geom(r.net, l, FM_DGRAD, r.n);
+  if (g.mode < 0) return fm_no_launch(r, l, FM_DGRAD);
+  FmView src, out;
+  fm_layer_views(r.net, r.m, l, FM_DGRAD, &src, &out);
+  return fm_gemm(r.st, r.net.label[l].of[FM_DGRAD], g.mode, src, g.SH, g.ss, g.p2 ? fm_w2(r, l) : fm_w1(r, l), nullptr, out, g.OH,
+                 g.GH, r.n, g.C, g.N, g.KH, g.pad, 0, accumulate, r.ws, &rq);
+}
+// weight gradient of layer l into r.grad, on stream sw
+static int fm_layer_wgrad(const FmRun& r, hipStream_t sw, int l, FmSlabPlan& plan) {
+  const FmGeom g = fm_geom(r.net, l, FM_WGRAD, r.n);
+  if (g.mode < 0) return fm_no_launch(r, l, FM_WGRAD);
+  FmView dense, gath;
+  fm_layer_views(r.net, r.m, l, FM_WGRAD, &dense, &gath);
+  return fm_wgrad(sw, r.net.label[l].of[FM_WGRAD], dense, g.DH, g.J, gath, g.SH, g.ss, g.KH, g.pad, g.C, r.n,
+                  r.grad + fm_param_offset(r.net, l, false), r.ws, plan, g.columns != 0);
+}
+// the BatchNorm (+ ReLU) behind layer l: m.raw[l] -> m.in[l + 1]; backward: m.raw[l] := d loss / d raw from m.din[l + 1]
+static int fm_layer_bn_fwd(const FmRun& r, int l, int training) {
+  const int b = fm_bn_of(r.net, l);
+  return fm_bn_fwd_at(r.st, b, r.m.raw[l], fm_out_pixels(r, l), r.m.in[l + 1], fm_bn_at(r.net, b, r.params, r.running, nullptr, r.sync),
+                      training, r.ws);
+}
+static int fm_layer_bn_bwd(const FmRun& r, int l) {
+  const int b = fm_bn_of(r.net, l);
+  return fm_bn_bwd_at(r.st, b, r.m.raw[l], r.m.in[l + 1], r.m.din[l + 1], fm_out_pixels(r, l),
+                      fm_bn_at(r.net, b, r.params, nullptr, r.grad, r.sync), r.ws);
+}
+// the statistics request of the launch that produces m.din[l + 1]: the backward sums of the BatchNorm behind layer l
+static FmEpReq fm_ep_bn_bwd_of(const FmRun& r, int l) { return fm_ep_bn_bwd(fm_bn_of(r.net, l), r.m.raw[l], r.m.in[l + 1], r.ws); }
+
+// bias gradient of conv6 / conv5 / conv4 (i = 0, 1, 2; statistics slot 20 + i): column sums from the accumulator its
+// producer filled
+static int fm_bias_finish(const FmRun& r, hipStream_t st, int i) {
+  FmBiasFinishArgs bf;
+  memset(&bf, 0, sizeof(bf));
+  bf.fin = fm_fin(20 + i, 1, 1, r.ws);
+  bf.fin.out1 = r.grad + fm_param_offset(r.net, 5 - i, true);
+  bf.cols = fm_stat_cols(20 + i);
+  KTimer kt("k_fm_bias_finish", st);
+  hipLaunchKernelGGL(k_fm_bias_finish, dim3(1), dim3(kThreads), 0, st, bf);
+  return check_launch("k_fm_bias_finish");
 }
 
 // layer l of `net` becomes the next segment of a k_fm_pack / k_fm_adam_pack launch: a 32 x 32 tile (or 1,024 elements) per workgroup
@@ -2748,14 +2937,10 @@ static int fm_adam_pack(hipStream_t st, const FmNet& net, float* params, const f
 static int fm_forward(hipStream_t st, const float* params, float* running, const void* cur, bool u8, const float* actions,
                       int64_t n, int training, const FmWs& ws, bool clear_backward_too = false, const FmLossArgs* with_loss = nullptr) {
   fm_attrs();
-  const float* P = params;
-  auto W1 = [&](int l) { return P + fm_param_offset(kFmNet, l, false); };
-  auto B = [&](int l) { return P + fm_param_offset(kFmNet, l, true); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kFmNet, l)); };
-  float* const* t = ws.t;
+  const FmMaps m = fm_maps(ws);
+  const FmRun r = {st, kFmNet, m, ws, n, params, running, nullptr, &g_fm_sync};
   const int64_t npix = n * 16384;
-  // (padded channels must hold finite values where they meet zero weights: k_fm_gemm's zero_to; the refinement stage's
-  // 16-channel maps are stored unpadded, kFmR1LD, and y2 as 3 + 1 channels written by k_fm_r2_fwd)
+  // (the refinement stage's 16-channel maps are stored unpadded, kFmR1LD, and y2 as 3 + 1 channels written by k_fm_r2_fwd)
   {
     KTimer kt("k_fm_image_cols", st);
     const int64_t opix = n * 4096;
@@ -2764,55 +2949,40 @@ static int fm_forward(hipStream_t st, const float* params, float* running, const
     const int64_t zero_words = training ? fm_stat_offset_words(last_slot) - fm_stat_offset_words(0) : 0;
     const unsigned blocks = (unsigned)((opix + kThreads - 1) / kThreads + (n * 32 + kThreads - 1) / kThreads +
                                        (zero_words / 2 + kThreads - 1) / kThreads);
-    if (u8) hipLaunchKernelGGL(k_fm_image_cols<true>, dim3(blocks), dim3(kThreads), 0, st, cur, opix, t[FMT_COLS], actions, n, t[FMT_Z],
+    if (u8) hipLaunchKernelGGL(k_fm_image_cols<true>, dim3(blocks), dim3(kThreads), 0, st, cur, opix, m.in[0].p, actions, n, m.in[6].p,
                                ws.stat_acc + fm_stat_offset_words(0), zero_words);
-    else hipLaunchKernelGGL(k_fm_image_cols<false>, dim3(blocks), dim3(kThreads), 0, st, cur, opix, t[FMT_COLS], actions, n, t[FMT_Z],
+    else hipLaunchKernelGGL(k_fm_image_cols<false>, dim3(blocks), dim3(kThreads), 0, st, cur, opix, m.in[0].p, actions, n, m.in[6].p,
                             ws.stat_acc + fm_stat_offset_words(0), zero_words);
   }
   int rc = check_launch("k_fm_image_cols");
   if (rc) return rc;
-#define FM_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
   // the batch statistics of every BatchNorm come out of the launch that produces its input (training mode)
-  FmEpReq eps_[kFmBns];
-  for (int b = 0; b < kFmBns; ++b) eps_[b] = training ? fm_ep_bn_fwd(b) : fm_ep_none();
-  auto EP = [&](int b) { return (const FmEpReq*)&eps_[b]; };
-  // ---- encoder (forward_encoder.py:41-57)
-  FM_TRY(fm_gemm(st, "k_fm_gemm[conv1]", 0, {t[FMT_COLS], 32}, 64, 1, W2(0), B(0), {t[FMT_RAW1], 64}, 64, 64, n, 32, 64, 1, 0, 0, 0, ws, 0, EP(0)));   // (columns: one tap)
-  FM_TRY(fm_bn_fwd(st, 0, {t[FMT_RAW1], 64}, n * 4096, {t[FMT_CAT6] + 64, 128}, P, running, training, ws));
-  FM_TRY(fm_gemm(st, "k_fm_gemm[conv2]", 0, {t[FMT_CAT6] + 64, 128}, 64, 2, W1(1), B(1), {t[FMT_RAW2], 128}, 32, 32, n, 64, 128, 3, 1, 0, 0, ws, 0, EP(1)));
-  FM_TRY(fm_bn_fwd(st, 1, {t[FMT_RAW2], 128}, n * 1024, {t[FMT_CAT5] + 128, 256}, P, running, training, ws));
-  FM_TRY(fm_gemm(st, "k_fm_gemm[conv3]", 0, {t[FMT_CAT5] + 128, 256}, 32, 2, W1(2), B(2), {t[FMT_RAW3], 256}, 16, 16, n, 128, 256, 3, 1, 0, 0, ws, 0, EP(2)));
-  FM_TRY(fm_bn_fwd(st, 2, {t[FMT_RAW3], 256}, n * 256, {t[FMT_CAT4] + 256, 512}, P, running, training, ws));
-  FM_TRY(fm_gemm(st, "k_fm_gemm[conv4]", 0, {t[FMT_CAT4] + 256, 512}, 16, 2, W1(3), B(3), {t[FMT_CAT3] + 512, 1024}, 8, 8, n, 256, 512, 3, 1, 1, 0, ws));
-  FM_TRY(fm_gemm(st, "k_fm_gemm[conv5]", 0, {t[FMT_CAT3] + 512, 1024}, 8, 2, W1(4), B(4), {t[FMT_CAT2] + 1024, 2048}, 4, 4, n, 512, 1024, 3, 1, 1, 0, ws));
-  FM_TRY(fm_gemm(st, "k_fm_gemm[conv6]", 0, {t[FMT_CAT2] + 1024, 2048}, 4, 1, W1(5), B(5), {t[FMT_Z], 160}, 1, 1, n, 1024, 128, 4, 0, 0, 0, ws));
-  // ---- decoder (forward_encoder.py:86-97)
-  FM_TRY(fm_gemm(st, "k_fm_gemm[deconv1]", 3, {t[FMT_Z], 160}, 1, 1, W2(6), B(6), {t[FMT_RAWU1], 1024}, 4, 1, n, 160, 1024, 1, 0, 0, 0, ws, 0, EP(3)));
-  FM_TRY(fm_bn_fwd(st, 3, {t[FMT_RAWU1], 1024}, n * 16, {t[FMT_CAT2], 2048}, P, running, training, ws));
-  FM_TRY(fm_gemm(st, "k_fm_gemm[deconv2]", 1, {t[FMT_CAT2], 2048}, 4, 1, W2(7), B(7), {t[FMT_RAWU2], 512}, 8, 4, n, 2048, 512, 2, 0, 0, 0, ws, 0, EP(4)));
-  FM_TRY(fm_bn_fwd(st, 4, {t[FMT_RAWU2], 512}, n * 64, {t[FMT_CAT3], 1024}, P, running, training, ws));
-  FM_TRY(fm_gemm(st, "k_fm_gemm[deconv3]", 1, {t[FMT_CAT3], 1024}, 8, 1, W2(8), B(8), {t[FMT_RAWU3], 256}, 16, 8, n, 1024, 256, 2, 0, 0, 0, ws, 0, EP(5)));
-  FM_TRY(fm_bn_fwd(st, 5, {t[FMT_RAWU3], 256}, n * 256, {t[FMT_CAT4], 512}, P, running, training, ws));
-  FM_TRY(fm_gemm(st, "k_fm_gemm[deconv4]", 1, {t[FMT_CAT4], 512}, 16, 1, W2(9), B(9), {t[FMT_RAWU4], 128}, 32, 16, n, 512, 128, 2, 0, 0, 0, ws, 0, EP(6)));
-  FM_TRY(fm_bn_fwd(st, 6, {t[FMT_RAWU4], 128}, n * 1024, {t[FMT_CAT5], 256}, P, running, training, ws));
-  if (n * 1024 / kFmBM * 2 >= 256)                                     // (two halves of 32 channels: enough tiles from 16 images)
-    FM_TRY(fm_deconv32(st, "k_fm_gemm[deconv5]", {t[FMT_CAT5], 256}, 32, W2(10), B(10), {t[FMT_RAWU5], 64}, n, 256, 64, *EP(7), ws));
-  else FM_TRY(fm_gemm(st, "k_fm_gemm[deconv5]", 1, {t[FMT_CAT5], 256}, 32, 1, W2(10), B(10), {t[FMT_RAWU5], 64}, 64, 32, n, 256, 64, 2, 0, 0, 0, ws, 0, EP(7)));
-  FM_TRY(fm_bn_fwd(st, 7, {t[FMT_RAWU5], 64}, n * 4096, {t[FMT_CAT6], 128}, P, running, training, ws));
-  FM_TRY(fm_deconv32(st, "k_fm_gemm[deconv6]", {t[FMT_CAT6], 128}, 64, W2(11), B(11), {t[FMT_RAWU6], 32}, n, 128, 32, *EP(8), ws));
-  FM_TRY(fm_bn_fwd(st, 8, {t[FMT_RAWU6], 32}, npix, {t[FMT_UP6], 32}, P, running, training, ws));
-  FM_TRY(fm_r1(st, "k_fm_gemm[refine1]", false, t[FMT_UP6], W1(12), B(12), t[FMT_RAWR1], n, *EP(9), ws));
-  FM_TRY(fm_bn_fwd(st, 9, {t[FMT_RAWR1], kFmR1LD}, npix, {t[FMT_R1], kFmR1LD}, P, running, training, ws));
+  const FmEpReq none = fm_ep_none();
+  auto EP = [&](int l) { return training ? fm_ep_bn_fwd(fm_bn_of(kFmNet, l)) : none; };
+  // ---- encoder (forward_encoder.py:41-57): conv1 (its columns: one tap) .. conv3 + BatchNorm, conv4 / conv5 + ReLU, conv6
+  for (int l = 0; l < 3; ++l) {
+    FM_TRY(fm_layer_fwd(r, l, 0, EP(l)));
+    FM_TRY(fm_layer_bn_fwd(r, l, training));
+  }
+  FM_TRY(fm_layer_fwd(r, 3, 1, none));
+  FM_TRY(fm_layer_fwd(r, 4, 1, none));
+  FM_TRY(fm_layer_fwd(r, 5, 0, none));
+  // ---- decoder (forward_encoder.py:86-97): deconv1 .. deconv6 + BatchNorm, the refinement stage
+  for (int l = 6; l < 12; ++l) {
+    FM_TRY(fm_layer_fwd(r, l, 0, EP(l)));
+    FM_TRY(fm_layer_bn_fwd(r, l, training));
+  }
+  FM_TRY(fm_r1(st, kFmLabels[12].of[FM_FWD], false, m.in[12].p, fm_w1(r, 12), fm_bias(r, 12), m.raw[12].p, n, EP(12), ws));
+  FM_TRY(fm_layer_bn_fwd(r, 12, training));
   {
     FmR2Args r2;
     memset(&r2, 0, sizeof(r2));
-    r2.r1 = t[FMT_R1]; r2.y2 = t[FMT_Y2]; r2.w = W1(13); r2.bias = B(13); r2.npix = npix;
+    r2.r1 = m.in[13].p; r2.y2 = m.raw[13].p; r2.w = fm_w1(r, 13); r2.bias = fm_bias(r, 13); r2.npix = npix;
     KTimer kt("k_fm_r2_fwd", st);
     if (with_loss) hipLaunchKernelGGL(k_fm_r2_fwd_loss, dim3((unsigned)((npix + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, r2, *with_loss);
     else hipLaunchKernelGGL(k_fm_r2_fwd, dim3((unsigned)((npix + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, r2);
   }
-  FM_TRY(check_launch("k_fm_r2_fwd"));
-  return NDP_OK;
+  return check_launch("k_fm_r2_fwd");
 }
 
 // training 1: MSE, its gradient in y2, and (with grad != null) the bias gradient of conv_refine_2; training 3: `cur` is
@@ -2895,6 +3065,23 @@ static FmBucketEvents* fm_bucket_events(FmBucketEventSet& set, const FmNet& net)
   return be->ok ? be : nullptr;
 }
 
+// conv1's data gradient (d_cur) and the action columns of dz (d_actions), either may be null: one launch behind the
+// chain's last BatchNorm backward, where m.raw[0] holds d loss / d raw1 and m.din[6] is dz.  ident: the eval-mode output
+// is state_cur + residual, so d_out joins d_cur (k_fm_conv1_dgrad<true>); training mode: d_out is not read.
+static int fm_conv1_dgrad(const FmRun& r, bool ident, const float* d_out, float* d_cur, float* d_actions) {
+  if (d_cur == nullptr && d_actions == nullptr) return NDP_OK;
+  FmC1DgArgs c1;
+  memset(&c1, 0, sizeof(c1));
+  c1.dz = r.m.din[6].p; c1.d_actions = d_actions; c1.nimg = r.n;
+  if (d_cur != nullptr) { c1.draw1 = r.m.raw[0].p; c1.w = fm_w1(r, 0); c1.d_out = d_out; c1.d_cur = d_cur; c1.nimg_rows = r.n * 64; }
+  const int64_t copy_blocks = d_actions != nullptr ? (r.n * 4 + kThreads - 1) / kThreads : 0;
+  const dim3 grid((unsigned)(c1.nimg_rows + copy_blocks));
+  KTimer kt("k_fm_conv1_dgrad", r.st);
+  if (!ident) hipLaunchKernelGGL(k_fm_conv1_dgrad<false>, grid, dim3(kThreads), 0, r.st, c1);
+  else hipLaunchKernelGGL(k_fm_conv1_dgrad<true>, grid, dim3(kThreads), 0, r.st, c1);
+  return check_launch("k_fm_conv1_dgrad");
+}
+
 // backward pass: from d loss / d (pre-tanh output) in y2 to every gradient in `grad` (flat, the parameters' layout).
 // d_cur / d_actions (ndp_fm_backward_inputs, either may be null): the gradient with respect to the image through the
 // network alone and to the actions, one more launch on `st` behind the chain's last BatchNorm backward; `grad` and the
@@ -2911,34 +3098,18 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
       hipStreamWaitEvent(side->stream, side->fork, 0);
     }
   };
-  const float* P = params;
-  auto W1 = [&](int l) { return P + fm_param_offset(kFmNet, l, false); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kFmNet, l)); };
-  auto GW = [&](int l) { return grad + fm_param_offset(kFmNet, l, false); };
-  float* const* t = ws.t;
+  const FmMaps m = fm_maps(ws);
+  const FmRun r = {st, kFmNet, m, ws, n, params, nullptr, grad, &g_fm_sync};
   const int64_t npix = n * 16384;
   int rc;
-  FmSlabPlan plan;
-  plan.a.nseg = 0; plan.a.remap_seg = -1; plan.a.block_begin[0] = 0; plan.used = 0; plan.blocks = 0;
+  FmSlabPlan plan = fm_plan_new();
   // bucket b is complete behind everything launched on the weight-gradient stream so far: the row-chunk slabs of its
   // layers are summed now (on that stream), then its event is recorded there
   auto close_bucket = [&](int b) -> int {
-    const int r = fm_slab_sums(sw, plan);
-    plan.a.nseg = 0; plan.a.remap_seg = -1; plan.a.block_begin[0] = 0; plan.blocks = 0;   // (slab memory is not reused: plan.used keeps growing)
-    if (r == NDP_OK && buckets) hipEventRecord(buckets->ev[b], sw);
-    return r;
-  };
-  // bias gradient of conv6 / conv5 / conv4 (slot 20 + i): column sums from the accumulator its producer filled
-  auto bias_finish = [&](int i) -> int {
-    const int layer[3] = {5, 4, 3};
-    FmBiasFinishArgs bf;
-    memset(&bf, 0, sizeof(bf));
-    bf.fin = fm_fin(20 + i, 1, 1, ws);
-    bf.fin.out1 = grad + fm_param_offset(kFmNet, layer[i], true);
-    bf.cols = fm_stat_cols(20 + i);
-    KTimer kt("k_fm_bias_finish", sw);
-    hipLaunchKernelGGL(k_fm_bias_finish, dim3(1), dim3(kThreads), 0, sw, bf);
-    return check_launch("k_fm_bias_finish");
+    const int rs = fm_slab_sums(sw, plan);
+    fm_plan_reset(plan);
+    if (rs == NDP_OK && buckets) hipEventRecord(buckets->ev[b], sw);
+    return rs;
   };
   if (!cleared) FM_TRY(fm_stat_clear(st, ws, 10, kFmStatSlots));
   // conv_refine_2
@@ -2952,13 +3123,8 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
     if (nblk > (kFmSlabCap - plan.used) / slab) nblk = (kFmSlabCap - plan.used) / slab;
     r2.rows_per_block = (int)((npix + nblk - 1) / nblk);
     nblk = (npix + r2.rows_per_block - 1) / r2.rows_per_block;
-    r2.r1 = t[FMT_R1]; r2.y2 = t[FMT_Y2]; r2.slabs = ws.slabs + plan.used; r2.npix = npix;
-    FmSlabSumArgs& ps = plan.a;
-    ps.slabs[ps.nseg] = r2.slabs; ps.grad[ps.nseg] = GW(13); ps.nchunks[ps.nseg] = (int)nblk; ps.n4[ps.nseg] = slab / 4;
-    ps.block_begin[ps.nseg] = plan.blocks;
-    plan.blocks += (int)((slab / 4 + kThreads - 1) / kThreads);
-    ps.block_begin[++ps.nseg] = plan.blocks;
-    plan.used += nblk * slab;
+    r2.r1 = m.in[13].p; r2.y2 = m.raw[13].p; r2.npix = npix;
+    r2.slabs = fm_plan_append(plan, ws, grad + fm_param_offset(kFmNet, 13, false), nblk, slab, slab / 4);
     KTimer kt("k_fm_r2_wgrad", sw);
     hipLaunchKernelGGL(k_fm_r2_wgrad, dim3((unsigned)nblk), dim3(kThreads), 0, sw, r2);
   }
@@ -2968,102 +3134,59 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
     // data gradient of conv_refine_2 + the BatchNorm-backward sums of conv_refine_1_bn over it
     FmR2Args r2;
     memset(&r2, 0, sizeof(r2));
-    r2.y2 = t[FMT_Y2]; r2.w = W1(13); r2.dr1 = t[FMT_DR1]; r2.npix = npix;
+    r2.y2 = m.raw[13].p; r2.w = fm_w1(r, 13); r2.dr1 = m.din[13].p; r2.npix = npix;
     const int nblk = (int)((npix + kThreads - 1) / kThreads);
-    const FmEpReq rq = fm_ep_bn_bwd(9, {t[FMT_RAWR1], kFmR1LD}, {t[FMT_R1], kFmR1LD}, ws);
-    fm_ep_fill(r2.ep, rq, ws);
+    fm_ep_fill(r2.ep, fm_ep_bn_bwd_of(r, 12), ws);
     KTimer kt("k_fm_r2_dgrad", st);
     hipLaunchKernelGGL(k_fm_r2_dgrad, dim3((unsigned)nblk), dim3(kThreads), 0, st, r2);
   }
   FM_TRY(check_launch("k_fm_r2_dgrad"));
   // Every data gradient below leaves, on its way out, the sums the NEXT BatchNorm / ReLU backward needs (FmEpReq).
   // conv_refine_1
-  FM_TRY(fm_bn_bwd(st, 9, {t[FMT_RAWR1], kFmR1LD}, {t[FMT_R1], kFmR1LD}, {t[FMT_DR1], kFmR1LD}, npix, P, grad, ws));
+  FM_TRY(fm_layer_bn_bwd(r, 12));
   fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[refine1]", {t[FMT_RAWR1], kFmR1LD}, 128, 16, {t[FMT_UP6], 32}, 128, 1, 3, 1, 32, n, GW(12), ws, plan));
-  FmEpReq rq = fm_ep_bn_bwd(8, {t[FMT_RAWU6], 32}, {t[FMT_UP6], 32}, ws);
-  FM_TRY(fm_r1(st, "k_fm_dgrad[refine1]", true, t[FMT_RAWR1], W2(12), nullptr, t[FMT_DUP6], n, rq, ws));
+  FM_TRY(fm_layer_wgrad(r, sw, 12, plan));
+  FM_TRY(fm_r1(st, kFmLabels[12].of[FM_DGRAD], true, m.raw[12].p, fm_w2(r, 12), nullptr, m.din[12].p, n, fm_ep_bn_bwd_of(r, 11), ws));
   // deconv6 .. deconv2: dense = the layer's input map, gathered = d(raw output) at the 4x4 stride-2 taps
-  FM_TRY(fm_bn_bwd(st, 8, {t[FMT_RAWU6], 32}, {t[FMT_UP6], 32}, {t[FMT_DUP6], 32}, npix, P, grad, ws));
-  fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[deconv6]", {t[FMT_CAT6], 128}, 64, 128, {t[FMT_RAWU6], 32}, 128, 2, 4, 1, 32, n, GW(11), ws, plan));
-  rq = fm_ep_bn_bwd(7, {t[FMT_RAWU5], 64}, {t[FMT_CAT6], 128}, ws);
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv6]", 0, {t[FMT_RAWU6], 32}, 128, 2, W1(11), nullptr, {t[FMT_DCAT6], 128}, 64, 64, n, 32, 128, 4, 1, 0, 0, ws, 0, &rq));
-  FM_TRY(fm_bn_bwd(st, 7, {t[FMT_RAWU5], 64}, {t[FMT_CAT6], 128}, {t[FMT_DCAT6], 128}, n * 4096, P, grad, ws));
-  fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[deconv5]", {t[FMT_CAT5], 256}, 32, 256, {t[FMT_RAWU5], 64}, 64, 2, 4, 1, 64, n, GW(10), ws, plan));
-  rq = fm_ep_bn_bwd(6, {t[FMT_RAWU4], 128}, {t[FMT_CAT5], 256}, ws);
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv5]", 0, {t[FMT_RAWU5], 64}, 64, 2, W1(10), nullptr, {t[FMT_DCAT5], 256}, 32, 32, n, 64, 256, 4, 1, 0, 0, ws, 0, &rq));
-  FM_TRY(fm_bn_bwd(st, 6, {t[FMT_RAWU4], 128}, {t[FMT_CAT5], 256}, {t[FMT_DCAT5], 256}, n * 1024, P, grad, ws));
-  fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[deconv4]", {t[FMT_CAT4], 512}, 16, 512, {t[FMT_RAWU4], 128}, 32, 2, 4, 1, 128, n, GW(9), ws, plan));
-  FM_TRY(close_bucket(0));
-  rq = fm_ep_bn_bwd(5, {t[FMT_RAWU3], 256}, {t[FMT_CAT4], 512}, ws);
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv4]", 0, {t[FMT_RAWU4], 128}, 32, 2, W1(9), nullptr, {t[FMT_DCAT4], 512}, 16, 16, n, 128, 512, 4, 1, 0, 0, ws, 0, &rq));
-  FM_TRY(fm_bn_bwd(st, 5, {t[FMT_RAWU3], 256}, {t[FMT_CAT4], 512}, {t[FMT_DCAT4], 512}, n * 256, P, grad, ws));
-  fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[deconv3]", {t[FMT_CAT3], 1024}, 8, 1024, {t[FMT_RAWU3], 256}, 16, 2, 4, 1, 256, n, GW(8), ws, plan));
-  FM_TRY(close_bucket(1));
-  rq = fm_ep_bn_bwd(4, {t[FMT_RAWU2], 512}, {t[FMT_CAT3], 1024}, ws);
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv3]", 0, {t[FMT_RAWU3], 256}, 16, 2, W1(8), nullptr, {t[FMT_DCAT3], 1024}, 8, 8, n, 256, 1024, 4, 1, 0, 0, ws, 0, &rq));
-  FM_TRY(fm_bn_bwd(st, 4, {t[FMT_RAWU2], 512}, {t[FMT_CAT3], 1024}, {t[FMT_DCAT3], 1024}, n * 64, P, grad, ws));
-  fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[deconv2]", {t[FMT_CAT2], 2048}, 4, 2048, {t[FMT_RAWU2], 512}, 8, 2, 4, 1, 512, n, GW(7), ws, plan));
-  FM_TRY(close_bucket(2));
-  rq = fm_ep_bn_bwd(3, {t[FMT_RAWU1], 1024}, {t[FMT_CAT2], 2048}, ws);
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv2]", 0, {t[FMT_RAWU2], 512}, 8, 2, W1(7), nullptr, {t[FMT_DCAT2], 2048}, 4, 4, n, 512, 2048, 4, 1, 0, 0, ws, 0, &rq));
+  for (int l = 11; l >= 7; --l) {
+    FM_TRY(fm_layer_bn_bwd(r, l));
+    fork();
+    FM_TRY(fm_layer_wgrad(r, sw, l, plan));
+    if (l <= 9) FM_TRY(close_bucket(9 - l));                          // bucket 0 ends with deconv4, 1 with deconv3, 2 with deconv2
+    FM_TRY(fm_layer_dgrad(r, l, 0, fm_ep_bn_bwd_of(r, l - 1)));
+  }
   // deconv1: a 4x4 "image" of d(raw) per row of z
-  FM_TRY(fm_bn_bwd(st, 3, {t[FMT_RAWU1], 1024}, {t[FMT_CAT2], 2048}, {t[FMT_DCAT2], 2048}, n * 16, P, grad, ws));
+  FM_TRY(fm_layer_bn_bwd(r, 6));
   fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[deconv1]", {t[FMT_Z], 160}, 1, 160, {t[FMT_RAWU1], 1024}, 4, 1, 4, 0, 1024, n, GW(6), ws, plan));
+  FM_TRY(fm_layer_wgrad(r, sw, 6, plan));
   // conv6: d code = dz[:, 0:128], whose column sums are conv6's bias gradient; its data gradient joins the skip gradient
   // of feat_5 in dcat2
-  rq = fm_ep_bias(4, 20, {nullptr, 0});
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv1]", 0, {t[FMT_RAWU1], 1024}, 4, 1, W1(6), nullptr, {t[FMT_DZ], 160}, 1, 1, n, 1024, 160, 4, 0, 0, 0, ws, 0, &rq));
+  FM_TRY(fm_layer_dgrad(r, 6, 0, fm_ep_bias(4, 20, {nullptr, 0})));
   fork();
-  FM_TRY(bias_finish(0));
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[conv6]", {t[FMT_DZ], 160}, 1, 128, {t[FMT_CAT2] + 1024, 2048}, 4, 1, 4, 0, 1024, n, GW(5), ws, plan));
+  FM_TRY(fm_bias_finish(r, sw, 0));
+  FM_TRY(fm_layer_wgrad(r, sw, 5, plan));
   FM_TRY(close_bucket(3));
   // conv5, conv4 (ReLU, no BatchNorm): the ReLU's backward is applied as the finished gradient is written
-  rq = fm_ep_bias(3, 21, {t[FMT_CAT2] + 1024, 2048});
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[conv6]", 3, {t[FMT_DZ], 160}, 1, 1, W2(5), nullptr, {t[FMT_DCAT2] + 1024, 2048}, 4, 1, n, 128, 1024, 1, 0, 0, 1, ws, 0, &rq));
+  FM_TRY(fm_layer_dgrad(r, 5, 1, fm_ep_bias(3, 21, m.in[5])));
   fork();
-  FM_TRY(bias_finish(1));
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[conv5]", {t[FMT_DCAT2] + 1024, 2048}, 4, 1024, {t[FMT_CAT3] + 512, 1024}, 8, 2, 3, 1, 512, n, GW(4), ws, plan));
+  FM_TRY(fm_bias_finish(r, sw, 1));
+  FM_TRY(fm_layer_wgrad(r, sw, 4, plan));
   FM_TRY(close_bucket(4));
-  rq = fm_ep_bias(3, 22, {t[FMT_CAT3] + 512, 1024});
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[conv5]", 2, {t[FMT_DCAT2] + 1024, 2048}, 4, 1, W2(4), nullptr, {t[FMT_DCAT3] + 512, 1024}, 8, 4, n, 1024, 512, 2, 0, 0, 1, ws, 0, &rq));
+  FM_TRY(fm_layer_dgrad(r, 4, 1, fm_ep_bias(3, 22, m.in[4])));
   fork();
-  FM_TRY(bias_finish(2));
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[conv4]", {t[FMT_DCAT3] + 512, 1024}, 8, 512, {t[FMT_CAT4] + 256, 512}, 16, 2, 3, 1, 256, n, GW(3), ws, plan));
-  rq = fm_ep_bn_bwd(2, {t[FMT_RAW3], 256}, {t[FMT_CAT4] + 256, 512}, ws);
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[conv4]", 2, {t[FMT_DCAT3] + 512, 1024}, 8, 1, W2(3), nullptr, {t[FMT_DCAT4] + 256, 512}, 16, 8, n, 512, 256, 2, 0, 0, 1, ws, 0, &rq));
-  // conv3 .. conv1
-  FM_TRY(fm_bn_bwd(st, 2, {t[FMT_RAW3], 256}, {t[FMT_CAT4] + 256, 512}, {t[FMT_DCAT4] + 256, 512}, n * 256, P, grad, ws));
-  fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[conv3]", {t[FMT_RAW3], 256}, 16, 256, {t[FMT_CAT5] + 128, 256}, 32, 2, 3, 1, 128, n, GW(2), ws, plan));
-  rq = fm_ep_bn_bwd(1, {t[FMT_RAW2], 128}, {t[FMT_CAT5] + 128, 256}, ws);
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[conv3]", 2, {t[FMT_RAW3], 256}, 16, 1, W2(2), nullptr, {t[FMT_DCAT5] + 128, 256}, 32, 16, n, 256, 128, 2, 0, 0, 1, ws, 0, &rq));
-  FM_TRY(fm_bn_bwd(st, 1, {t[FMT_RAW2], 128}, {t[FMT_CAT5] + 128, 256}, {t[FMT_DCAT5] + 128, 256}, n * 1024, P, grad, ws));
-  fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[conv2]", {t[FMT_RAW2], 128}, 32, 128, {t[FMT_CAT6] + 64, 128}, 64, 2, 3, 1, 64, n, GW(1), ws, plan));
-  rq = fm_ep_bn_bwd(0, {t[FMT_RAW1], 64}, {t[FMT_CAT6] + 64, 128}, ws);
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[conv2]", 2, {t[FMT_RAW2], 128}, 32, 1, W2(1), nullptr, {t[FMT_DCAT6] + 64, 128}, 64, 32, n, 128, 64, 2, 0, 0, 1, ws, 0, &rq));
-  FM_TRY(fm_bn_bwd(st, 0, {t[FMT_RAW1], 64}, {t[FMT_CAT6] + 64, 128}, {t[FMT_DCAT6] + 64, 128}, n * 4096, P, grad, ws));
-  fork();
-  FM_TRY(fm_wgrad(sw, "k_fm_wgrad[conv1]", {t[FMT_RAW1], 64}, 64, 64, {t[FMT_COLS], 32}, 64, 1, 1, 0, 32, n, GW(0), ws, plan, true));   // (columns)
-  if (d_cur != nullptr || d_actions != nullptr) {
-    // RAW1 holds d loss / d raw1 since fm_bn_bwd(st, 0, ...): the data gradient of conv1 reads it on `st` while
-    // k_fm_wgrad[conv1] reads it on the side stream -- neither writes it; dz is complete since k_fm_dgrad[deconv1]
-    FmC1DgArgs c1;
-    memset(&c1, 0, sizeof(c1));
-    c1.dz = t[FMT_DZ]; c1.d_actions = d_actions; c1.nimg = n;
-    if (d_cur != nullptr) { c1.draw1 = t[FMT_RAW1]; c1.w = W1(0); c1.d_cur = d_cur; c1.nimg_rows = n * 64; }
-    const int64_t copy_blocks = d_actions != nullptr ? (n * 4 + kThreads - 1) / kThreads : 0;
-    KTimer kt("k_fm_conv1_dgrad", st);
-    hipLaunchKernelGGL(k_fm_conv1_dgrad<false>, dim3((unsigned)(c1.nimg_rows + copy_blocks)), dim3(kThreads), 0, st, c1);
-    FM_TRY(check_launch("k_fm_conv1_dgrad"));
+  FM_TRY(fm_bias_finish(r, sw, 2));
+  FM_TRY(fm_layer_wgrad(r, sw, 3, plan));
+  FM_TRY(fm_layer_dgrad(r, 3, 1, fm_ep_bn_bwd_of(r, 2)));
+  // conv3 .. conv1 (conv1's weight gradient: its columns)
+  for (int l = 2; l >= 0; --l) {
+    FM_TRY(fm_layer_bn_bwd(r, l));
+    fork();
+    FM_TRY(fm_layer_wgrad(r, sw, l, plan));
+    if (l > 0) FM_TRY(fm_layer_dgrad(r, l, 1, fm_ep_bn_bwd_of(r, l - 1)));
   }
+  // m.raw[0] holds d loss / d raw1 since fm_layer_bn_bwd(r, 0): the data gradient of conv1 reads it on `st` while
+  // k_fm_wgrad[conv1] reads it on the side stream -- neither writes it; dz is complete since k_fm_dgrad[deconv1]
+  FM_TRY(fm_conv1_dgrad(r, false, nullptr, d_cur, d_actions));
   if (side) {
     hipEventRecord(side->join, side->stream);
     hipStreamWaitEvent(st, side->join, 0);
@@ -3074,21 +3197,22 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
     hipEventRecord(buckets->ev[6], st);
   }
   return NDP_OK;
-#undef FM_TRY
 }
 
-// BatchNorm b + ReLU backward with running statistics (k_fm_bn_eval_bwd_apply): raw := d loss / d raw
-static int fm_bn_eval_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy, int64_t P, const float* params, const FmWs& ws) {
-  const int C = kFmBnC[b];
+// the BatchNorm + ReLU behind layer l backward with running statistics (k_fm_bn_eval_bwd_apply): m.raw[l] := d loss / d raw
+static int fm_layer_bn_eval_bwd(const FmRun& r, int l) {
+  const int b = fm_bn_of(r.net, l), C = kFmBnC[b];
+  const int64_t P = fm_out_pixels(r, l);
   FmEltArgs e;
   memset(&e, 0, sizeof(e));
-  e.y = y.p; e.y_ld = y.ld; e.dy = dy.p; e.dy_ld = dy.ld; e.out = raw.p; e.out_ld = raw.ld;
-  e.invstd = ws.bn_invstd + fm_bn_stat_index(b);
-  e.gamma = params + fm_bn_offset(kFmNet, b, false);
+  e.y = r.m.in[l + 1].p; e.y_ld = r.m.in[l + 1].ld; e.dy = r.m.din[l + 1].p; e.dy_ld = r.m.din[l + 1].ld;
+  e.out = r.m.raw[l].p; e.out_ld = r.m.raw[l].ld;
+  e.invstd = r.ws.bn_invstd + fm_bn_stat_index(b);
+  e.gamma = r.params + fm_bn_offset(r.net, b, false);
   e.C = C; e.P = (int)P;
   e.iters = fm_elt_iters(P, C);
-  KTimer kt("k_fm_bn_eval_bwd_apply", st);
-  hipLaunchKernelGGL(k_fm_bn_eval_bwd_apply, fm_elt_grid(P, C), dim3(kThreads), 0, st, e);
+  KTimer kt("k_fm_bn_eval_bwd_apply", r.st);
+  hipLaunchKernelGGL(k_fm_bn_eval_bwd_apply, fm_elt_grid(P, C), dim3(kThreads), 0, r.st, e);
   return check_launch("k_fm_bn_eval_bwd_apply");
 }
 
@@ -3099,61 +3223,37 @@ static int fm_bn_eval_bwd(hipStream_t st, int b, FmView raw, FmView y, FmView dy
 static int fm_input_grads(hipStream_t st, const float* params, const float* d_out, int64_t n, float* d_cur, float* d_actions,
                           const FmWs& ws) {
   fm_attrs();
-  const float* P = params;
-  auto W1 = [&](int l) { return P + fm_param_offset(kFmNet, l, false); };
-  auto W2 = [&](int l) { return (const float*)(ws.p2 + fm_p2_offset(kFmNet, l)); };
-  float* const* t = ws.t;
+  const FmMaps m = fm_maps(ws);
+  const FmRun r = {st, kFmNet, m, ws, n, params, nullptr, nullptr, nullptr};
   const int64_t npix = n * 16384;
   int rc;
-#define FM_TRY(x) do { rc = (x); if (rc) return rc; } while (0)
   const FmEpReq none = fm_ep_none();
   {
     FmR2Args r2;
     memset(&r2, 0, sizeof(r2));
-    r2.y2 = t[FMT_Y2]; r2.w = W1(13); r2.dr1 = t[FMT_DR1]; r2.npix = npix;
+    r2.y2 = m.raw[13].p; r2.w = fm_w1(r, 13); r2.dr1 = m.din[13].p; r2.npix = npix;
     KTimer kt("k_fm_r2_dgrad", st);
     hipLaunchKernelGGL(k_fm_r2_dgrad, dim3((unsigned)((npix + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, r2);
   }
   FM_TRY(check_launch("k_fm_r2_dgrad"));
-  FM_TRY(fm_bn_eval_bwd(st, 9, {t[FMT_RAWR1], kFmR1LD}, {t[FMT_R1], kFmR1LD}, {t[FMT_DR1], kFmR1LD}, npix, P, ws));
-  FM_TRY(fm_r1(st, "k_fm_dgrad[refine1]", true, t[FMT_RAWR1], W2(12), nullptr, t[FMT_DUP6], n, none, ws));
-  FM_TRY(fm_bn_eval_bwd(st, 8, {t[FMT_RAWU6], 32}, {t[FMT_UP6], 32}, {t[FMT_DUP6], 32}, npix, P, ws));
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv6]", 0, {t[FMT_RAWU6], 32}, 128, 2, W1(11), nullptr, {t[FMT_DCAT6], 128}, 64, 64, n, 32, 128, 4, 1, 0, 0, ws));
-  FM_TRY(fm_bn_eval_bwd(st, 7, {t[FMT_RAWU5], 64}, {t[FMT_CAT6], 128}, {t[FMT_DCAT6], 128}, n * 4096, P, ws));
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv5]", 0, {t[FMT_RAWU5], 64}, 64, 2, W1(10), nullptr, {t[FMT_DCAT5], 256}, 32, 32, n, 64, 256, 4, 1, 0, 0, ws));
-  FM_TRY(fm_bn_eval_bwd(st, 6, {t[FMT_RAWU4], 128}, {t[FMT_CAT5], 256}, {t[FMT_DCAT5], 256}, n * 1024, P, ws));
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv4]", 0, {t[FMT_RAWU4], 128}, 32, 2, W1(9), nullptr, {t[FMT_DCAT4], 512}, 16, 16, n, 128, 512, 4, 1, 0, 0, ws));
-  FM_TRY(fm_bn_eval_bwd(st, 5, {t[FMT_RAWU3], 256}, {t[FMT_CAT4], 512}, {t[FMT_DCAT4], 512}, n * 256, P, ws));
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv3]", 0, {t[FMT_RAWU3], 256}, 16, 2, W1(8), nullptr, {t[FMT_DCAT3], 1024}, 8, 8, n, 256, 1024, 4, 1, 0, 0, ws));
-  FM_TRY(fm_bn_eval_bwd(st, 4, {t[FMT_RAWU2], 512}, {t[FMT_CAT3], 1024}, {t[FMT_DCAT3], 1024}, n * 64, P, ws));
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv2]", 0, {t[FMT_RAWU2], 512}, 8, 2, W1(7), nullptr, {t[FMT_DCAT2], 2048}, 4, 4, n, 512, 2048, 4, 1, 0, 0, ws));
-  FM_TRY(fm_bn_eval_bwd(st, 3, {t[FMT_RAWU1], 1024}, {t[FMT_CAT2], 2048}, {t[FMT_DCAT2], 2048}, n * 16, P, ws));
-  FM_TRY(fm_gemm(st, "k_fm_dgrad[deconv1]", 0, {t[FMT_RAWU1], 1024}, 4, 1, W1(6), nullptr, {t[FMT_DZ], 160}, 1, 1, n, 1024, 160, 4, 0, 0, 0, ws));
-  FmC1DgArgs c1;
-  memset(&c1, 0, sizeof(c1));
-  c1.dz = t[FMT_DZ]; c1.d_actions = d_actions; c1.nimg = n;
+  FM_TRY(fm_layer_bn_eval_bwd(r, 12));
+  FM_TRY(fm_r1(st, kFmLabels[12].of[FM_DGRAD], true, m.raw[12].p, fm_w2(r, 12), nullptr, m.din[12].p, n, none, ws));
+  for (int l = 11; l >= 6; --l) {                                      // deconv6 .. deconv1
+    FM_TRY(fm_layer_bn_eval_bwd(r, l));
+    FM_TRY(fm_layer_dgrad(r, l, 0, none));
+  }
   if (d_cur != nullptr) {
     // the encoder half: conv6, conv5, conv4 (ReLU backward in the epilogue), conv3 .. conv1 (BatchNorm backward between)
-    FmEpReq rq = fm_ep_bias(3, 21, {t[FMT_CAT2] + 1024, 2048});
-    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv6]", 3, {t[FMT_DZ], 160}, 1, 1, W2(5), nullptr, {t[FMT_DCAT2] + 1024, 2048}, 4, 1, n, 128, 1024, 1, 0, 0, 1, ws, 0, &rq));
-    rq = fm_ep_bias(3, 22, {t[FMT_CAT3] + 512, 1024});
-    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv5]", 2, {t[FMT_DCAT2] + 1024, 2048}, 4, 1, W2(4), nullptr, {t[FMT_DCAT3] + 512, 1024}, 8, 4, n, 1024, 512, 2, 0, 0, 1, ws, 0, &rq));
-    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv4]", 2, {t[FMT_DCAT3] + 512, 1024}, 8, 1, W2(3), nullptr, {t[FMT_DCAT4] + 256, 512}, 16, 8, n, 512, 256, 2, 0, 0, 1, ws));
-    FM_TRY(fm_bn_eval_bwd(st, 2, {t[FMT_RAW3], 256}, {t[FMT_CAT4] + 256, 512}, {t[FMT_DCAT4] + 256, 512}, n * 256, P, ws));
-    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv3]", 2, {t[FMT_RAW3], 256}, 16, 1, W2(2), nullptr, {t[FMT_DCAT5] + 128, 256}, 32, 16, n, 256, 128, 2, 0, 0, 1, ws));
-    FM_TRY(fm_bn_eval_bwd(st, 1, {t[FMT_RAW2], 128}, {t[FMT_CAT5] + 128, 256}, {t[FMT_DCAT5] + 128, 256}, n * 1024, P, ws));
-    FM_TRY(fm_gemm(st, "k_fm_dgrad[conv2]", 2, {t[FMT_RAW2], 128}, 32, 1, W2(1), nullptr, {t[FMT_DCAT6] + 64, 128}, 64, 32, n, 128, 64, 2, 0, 0, 1, ws));
-    FM_TRY(fm_bn_eval_bwd(st, 0, {t[FMT_RAW1], 64}, {t[FMT_CAT6] + 64, 128}, {t[FMT_DCAT6] + 64, 128}, n * 4096, P, ws));
-    c1.draw1 = t[FMT_RAW1]; c1.w = W1(0); c1.d_out = d_out; c1.d_cur = d_cur; c1.nimg_rows = n * 64;
+    FM_TRY(fm_layer_dgrad(r, 5, 1, fm_ep_bias(3, 21, m.in[5])));
+    FM_TRY(fm_layer_dgrad(r, 4, 1, fm_ep_bias(3, 22, m.in[4])));
+    FM_TRY(fm_layer_dgrad(r, 3, 1, none));
+    for (int l = 2; l >= 1; --l) {
+      FM_TRY(fm_layer_bn_eval_bwd(r, l));
+      FM_TRY(fm_layer_dgrad(r, l, 1, none));
+    }
+    FM_TRY(fm_layer_bn_eval_bwd(r, 0));
   }
-  const int64_t copy_blocks = d_actions != nullptr ? (n * 4 + kThreads - 1) / kThreads : 0;
-  if (c1.nimg_rows + copy_blocks > 0) {
-    KTimer kt("k_fm_conv1_dgrad", st);
-    hipLaunchKernelGGL(k_fm_conv1_dgrad<true>, dim3((unsigned)(c1.nimg_rows + copy_blocks)), dim3(kThreads), 0, st, c1);
-    FM_TRY(check_launch("k_fm_conv1_dgrad"));
-  }
-  return NDP_OK;
-#undef FM_TRY
+  return fm_conv1_dgrad(r, true, d_out, d_cur, d_actions);
 }
 
 // Which workspaces hold the activations of an eval-mode forward pass that no later call has touched (ndp_fm_input_grads

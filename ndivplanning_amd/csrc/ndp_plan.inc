@@ -13,8 +13,8 @@
 //   4  thread i walks the (ts, r) pairs i, i + 256, ...: consecutive rollouts in consecutive lanes, one 16-byte load of
 //      the normals and one 16-byte store; row 0 is the rank-0 sequence, copied.
 // Every sum has a fixed order, nothing is atomic, nothing spills: two calls give the same bits.  The arithmetic is in
-// ndp::plan, __host__ __device__: tests/host_drivers/plan_cem_main.hip runs exactly these functions by this schedule on
-// the CPU.  Included at the end of ndp_kernels.hip, after ndp_store.inc.
+// ndp::plan, __host__ __device__: tests/host_drivers/plan_cem.inc (a body of main.hip) runs exactly these functions by
+// this schedule on the CPU.  Included at the end of ndp_kernels.hip, after ndp_store.inc.
 
 namespace ndp {
 namespace plan {

@@ -12,8 +12,8 @@
 // which is the identity), so most of a frame is the table's two colours.  Integer arithmetic from the quantisation on,
 // nothing atomic, nothing spilled: two calls give the same bits.
 // The step, the quantisation and the four-pixel span are __host__ __device__ (namespace ndp::world):
-// tests/host_drivers/world_main.hip runs exactly these functions by this schedule on the CPU.  Included at the end of
-// ndp_kernels.hip, after ndp_plan.inc.
+// tests/host_drivers/world.inc (a body of main.hip) runs exactly these functions by this schedule on the CPU.  Included
+// at the end of ndp_kernels.hip, after ndp_plan.inc.
 
 namespace ndp {
 namespace world {

@@ -1,8 +1,9 @@
 // main.hip -- the one host-driver program (built and run by tests/host_driver.py).  It includes the library's source as
 // the library build does, once, and then the driver bodies: each replays one kernel family's schedule on the CPU through
 // the __host__ __device__ functions the kernels call, in allocations of exactly their size (exact.h), so that
-// AddressSanitizer and UBSan see what the device would not report.  The program makes no HIP runtime call and needs no
-// GPU; it is an ordinary program, started as a child process.
+// AddressSanitizer and UBSan see what the device would not report (fm_geometry replays nothing: it reports the launch
+// arguments the host derives from the network tables).  The program makes no HIP runtime call and needs no GPU; it is an
+// ordinary program, started as a child process.
 //
 // Usage: host_driver NAME IN OUT [flags ...]
 // NAME selects the body; each body's header gives the formats of its IN and OUT.
@@ -24,6 +25,7 @@
 #include "fm_rollout.inc"
 #include "plan_cem.inc"
 #include "world.inc"
+#include "fm_geometry.inc"
 
 int main(int argc, char** argv) {
   static const struct {
@@ -40,6 +42,7 @@ int main(int argc, char** argv) {
       {"fm_rollout", host::fm_rollout::run},
       {"plan_cem", host::plan_cem::run},
       {"world", host::world::run},
+      {"fm_geometry", host::fm_geometry::run},
   };
   for (const auto& d : drivers)
     if (argc > 1 && strcmp(argv[1], d.name) == 0) return d.run(argc - 1, argv + 1);

@@ -716,3 +716,80 @@ def test_the_optimizer_launch_leaves_the_second_weight_order_a_full_repack_would
     loss_a = tr.loss.item()
     tr.grads(cur, fut, act)
     assert tr.loss.item() == loss_a
+
+
+# {label: launches} of one training step of each network and one eval-mode decode at n = 2, every launch on the caller's
+# stream: the kernel-timer names are what bench.py and the profiles filter on (prefixes such as "k_fm_gemm[deconv"), so
+# they are pinned here byte for byte, with how often each is launched.
+FM_STEP_LAUNCHES = {
+    "k_fm_adam_pack": 1, "k_fm_bias_finish": 3, "k_fm_bn_apply": 10, "k_fm_bn_bwd_apply": 10, "k_fm_dgrad[conv2]": 1,
+    "k_fm_dgrad[conv3]": 1, "k_fm_dgrad[conv4]": 1, "k_fm_dgrad[conv5]": 1, "k_fm_dgrad[conv6]": 1,
+    "k_fm_dgrad[deconv1]": 1, "k_fm_dgrad[deconv2]": 1, "k_fm_dgrad[deconv3]": 1, "k_fm_dgrad[deconv4]": 1,
+    "k_fm_dgrad[deconv5]": 1, "k_fm_dgrad[deconv6]": 1, "k_fm_dgrad[refine1]": 1, "k_fm_gemm[conv1]": 1,
+    "k_fm_gemm[conv2]": 1, "k_fm_gemm[conv3]": 1, "k_fm_gemm[conv4]": 1, "k_fm_gemm[conv5]": 1, "k_fm_gemm[conv6]": 1,
+    "k_fm_gemm[deconv1]": 1, "k_fm_gemm[deconv2]": 1, "k_fm_gemm[deconv3]": 1, "k_fm_gemm[deconv4]": 1,
+    "k_fm_gemm[deconv5]": 1, "k_fm_gemm[deconv6]": 1, "k_fm_gemm[refine1]": 1, "k_fm_image_cols": 1,
+    "k_fm_r2_dgrad": 1, "k_fm_r2_fwd": 1, "k_fm_r2_wgrad": 1, "k_fm_slab_sum": 2, "k_fm_splitk_reduce": 19,
+    "k_fm_wgrad[conv1]": 1, "k_fm_wgrad[conv2]": 1, "k_fm_wgrad[conv3]": 1, "k_fm_wgrad[conv4]": 1,
+    "k_fm_wgrad[conv5]": 1, "k_fm_wgrad[conv6]": 1, "k_fm_wgrad[deconv1]": 1, "k_fm_wgrad[deconv2]": 1,
+    "k_fm_wgrad[deconv3]": 1, "k_fm_wgrad[deconv4]": 1, "k_fm_wgrad[deconv5]": 1, "k_fm_wgrad[deconv6]": 1,
+    "k_fm_wgrad[refine1]": 1,
+}
+AE_STEP_LAUNCHES = {
+    "k_ae_out_dgrad": 1, "k_ae_out_fwd_loss": 1, "k_ae_out_wgrad": 1, "k_fm_adam_pack": 1, "k_fm_bias_finish": 3,
+    "k_fm_bn_apply": 8, "k_fm_bn_bwd_apply": 8, "k_fm_dgrad[ae.conv2]": 1, "k_fm_dgrad[ae.conv3]": 1,
+    "k_fm_dgrad[ae.conv4]": 1, "k_fm_dgrad[ae.conv5]": 1, "k_fm_dgrad[ae.conv6]": 1, "k_fm_dgrad[ae.deconv1]": 1,
+    "k_fm_dgrad[ae.deconv2]": 1, "k_fm_dgrad[ae.deconv3]": 1, "k_fm_dgrad[ae.deconv4]": 1,
+    "k_fm_dgrad[ae.deconv5]": 1, "k_fm_gemm[ae.conv1]": 1, "k_fm_gemm[ae.conv2]": 1, "k_fm_gemm[ae.conv3]": 1,
+    "k_fm_gemm[ae.conv4]": 1, "k_fm_gemm[ae.conv5]": 1, "k_fm_gemm[ae.conv6]": 1, "k_fm_gemm[ae.deconv1]": 1,
+    "k_fm_gemm[ae.deconv2]": 1, "k_fm_gemm[ae.deconv3]": 1, "k_fm_gemm[ae.deconv4]": 1, "k_fm_gemm[ae.deconv5]": 1,
+    "k_fm_image_cols": 1, "k_fm_slab_sum": 1, "k_fm_splitk_reduce": 18, "k_fm_wgrad[ae.conv1]": 1,
+    "k_fm_wgrad[ae.conv2]": 1, "k_fm_wgrad[ae.conv3]": 1, "k_fm_wgrad[ae.conv4]": 1, "k_fm_wgrad[ae.conv5]": 1,
+    "k_fm_wgrad[ae.conv6]": 1, "k_fm_wgrad[ae.deconv1]": 1, "k_fm_wgrad[ae.deconv2]": 1, "k_fm_wgrad[ae.deconv3]": 1,
+    "k_fm_wgrad[ae.deconv4]": 1, "k_fm_wgrad[ae.deconv5]": 1,
+}
+AE_DECODE_LAUNCHES = {
+    "k_ae_out_fwd": 1, "k_fm_gemm[aed.deconv1]": 1, "k_fm_gemm[aed.deconv2]": 1, "k_fm_gemm[aed.deconv3]": 1,
+    "k_fm_gemm[aed.deconv4]": 1, "k_fm_gemm[aed.deconv5]": 1, "k_fm_splitk_reduce": 4,
+}
+
+
+def test_the_kernel_timer_labels_and_launch_counts_of_a_step_stay_as_they_are():
+    from ndivplanning_amd import _capi
+    from ndivplanning_amd import autoencoder_eval as AE
+    from ndivplanning_amd.autoencoder_trainer import AutoencoderTrainer
+    from ndivplanning_amd.models import image_autoencoder as IA
+    n = 2
+    tr, _ = _hip_trainer(5, n)
+    frames, actions = _inputs(9, n)
+    cur, fut, act = (t.contiguous().to(DEV) for t in (frames[:, 0], frames[:, 1], actions[:, 0]))
+    torch.manual_seed(3)
+    enc, dec = IA.Encoder().to(DEV).train(), IA.Decoder().to(DEV).train()
+    ae = AutoencoderTrainer(enc, dec, batch=n)
+    codes = torch.randn(n, 128, device=DEV)
+    AE.decode(dec.eval(), codes)                                       # (the folded parameters are packed on first use)
+    dec.train()
+    torch.cuda.synchronize()
+
+    def launches(fn):
+        fn()
+        torch.cuda.synchronize()
+        got = _capi.timing_collect()
+        assert len(got) < 64                                           # (timing_collect reports at most 64 names)
+        return {k: v[1] for k, v in got.items()}
+
+    side = tr.lib.ndp_fm_side_stream(0)
+    _capi.timing_enable(True)
+    try:
+        fm_step = launches(lambda: tr.step(cur, fut, act))
+        ae_step = launches(lambda: ae.step(cur))
+        dec.eval()
+        decode = launches(lambda: AE.decode(dec, codes))
+    finally:
+        _capi.timing_enable(False)
+        tr.lib.ndp_fm_side_stream(side)
+    for name, got in (("FM_STEP_LAUNCHES", fm_step), ("AE_STEP_LAUNCHES", ae_step), ("AE_DECODE_LAUNCHES", decode)):
+        print("%s = %r" % (name, dict(sorted(got.items()))))
+    assert fm_step == FM_STEP_LAUNCHES
+    assert ae_step == AE_STEP_LAUNCHES
+    assert decode == AE_DECODE_LAUNCHES
