@@ -1,8 +1,8 @@
 // main.hip -- the one host-driver program (built and run by tests/host_driver.py).  It includes the library's source as
 // the library build does, once, and then the driver bodies: each replays one kernel family's schedule on the CPU through
 // the __host__ __device__ functions the kernels call, in allocations of exactly their size (exact.h), so that
-// AddressSanitizer and UBSan see what the device would not report (fm_geometry replays nothing: it reports the launch
-// arguments the host derives from the network tables).  The program makes no HIP runtime call and needs no GPU; it is an
+// AddressSanitizer and UBSan see what the device would not report (fm_geometry and step_plan replay nothing: they report the
+// launch arguments the host derives from the network tables).  The program makes no HIP runtime call and needs no GPU; it is an
 // ordinary program, started as a child process.
 //
 // Usage: host_driver NAME IN OUT [flags ...]
@@ -26,6 +26,7 @@
 #include "plan_cem.inc"
 #include "world.inc"
 #include "fm_geometry.inc"
+#include "step_plan.inc"
 
 int main(int argc, char** argv) {
   static const struct {
@@ -43,6 +44,7 @@ int main(int argc, char** argv) {
       {"plan_cem", host::plan_cem::run},
       {"world", host::world::run},
       {"fm_geometry", host::fm_geometry::run},
+      {"step_plan", host::step_plan::run},
   };
   for (const auto& d : drivers)
     if (argc > 1 && strcmp(argv[1], d.name) == 0) return d.run(argc - 1, argv + 1);

@@ -17,9 +17,8 @@ Every case runs at pairwise_div_factor 0.1 and 0 (the same kernels; without NDiv
 through the updated D, is held to 1e-5 of its own size), and the three losses and action_hat are held to the fp64 oracle
 at the suite's 1e-4 bounds, so that no case passes on the gradients of a wrong forward.
 
-The tests prove parity, not which plan ran: the plan beside each shape is derived from the thresholds of wgrad_plan,
-wgrad_wide_chunks, several_per_cu, step_code_rows and seg_per_tile in csrc/ndp_capi.inc; a change of a threshold
-updates the table.
+The tests prove parity; which plan runs at each shape -- the plan beside it below -- is asserted on the CPU by
+tests/test_step_plan_host.py, together with these shapes reaching every kernel variant and every branch of the plan.
 
 measured on MI355X (30 cases, 8 s; worst |run - fp64| / bound over the cases, 1 = the bound):
   D gradient   0.70 (fc3.bias at B 128 / K 32, k_wgrad_wide), otherwise <= 0.40; repeat D step 0.35 (fc2.bias)
