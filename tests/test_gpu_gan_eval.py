@@ -200,6 +200,9 @@ def modules(golden):
 
 @pytest.mark.parametrize("num_sample", [1, 6])
 def test_sample_gives_the_bits_of_the_materialised_input(GE, modules, num_sample):
+    """The materialised input is built from the noise the DEVICE drew in the same call: this holds the layout
+    cat(codes[r], noise[r, k]) and repeatability, not the stream.  tests/test_gpu_noise.py holds the drawn noise to the
+    host restatement of the stream (tests/philox_ref.py)."""
     g = modules[0]
     codes = torch.randn(7, 256, generator=torch.Generator().manual_seed(1)).to(DEV)
     cpu_state, gpu_state = torch.get_rng_state(), torch.cuda.get_rng_state(0)

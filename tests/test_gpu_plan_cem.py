@@ -88,7 +88,10 @@ def _draw(lib, fn, n, seed, offset=None):
 
 def test_normal_noise_against_box_muller_on_the_same_uniforms():
     """|device - fp64 restatement| <= 1e-5: r <= sqrt(-2 ln 2^-32) < 6.7, the angle 2 pi u2 is rounded to fp32 (<= 2^-22
-    relative of 6.28) and logf, sqrtf, cosf, sinf add a few ulp: about 6.7e-6.  Measured on an MI355X: see DESIGN 5p."""
+    relative of 6.28) and logf, sqrtf, cosf, sinf add a few ulp: about 6.7e-6.  Measured on an MI355X: see DESIGN 5p.
+    "The same uniforms" are the DEVICE's own here (ndp_uniform_noise with the same seed and offset): this test holds the
+    Box-Muller arithmetic, not the stream.  tests/test_gpu_noise.py holds the stream to the host restatement and the
+    normals to the Box-Muller of the restatement's uniforms."""
     lib = _lib()
     n, seed = 1 << 20, 0x5EED1234
     for offset in (None, 3):
