@@ -44,10 +44,8 @@ def fetch(kind, image_encoder, fwd_model_autoencoder, generator, dataset, config
         elif kind == "closed":
             res = E.closed_loop(models, images, actions, k, noise, action_error_acc=action_error_sum, on_step=print)
         else:
-            if cem is None:
-                res = E.mpc_plan(models, images, actions, r, th, noise=noise, on_step=print)
-            else:                                          # the normal draws: the device's, one stream per trajectory
-                res = E.mpc_plan(models, images, actions, r, th, noise=noise, on_step=print, cem=cem, seed=seed + i)
+            # seed: with `cem`, the device's normal draws, one stream per trajectory (unread without it: the noise is given)
+            res = E.mpc_plan(models, images, actions, r, th, noise=noise, on_step=print, cem=cem, seed=seed + i)
             models.mse(actions[:, :t1].contiguous(), res["actions"], 1, t1 * 4, acc=action_error_sum)
         image_error_sum = res["image_error_sum"][0]
         if kind != "open":

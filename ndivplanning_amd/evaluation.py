@@ -17,9 +17,15 @@ What the loops deduplicate against the reference, with the same arithmetic per i
     rollout's ts = 0 prediction becomes the next state (mpc_eval.py:167-169 recomputes it with one more forward call);
   * `mpc_plan` runs B trajectories at once: every launch serves B * R images.
 
+The planner is one planning step, `_plan_once`, under every entry point (mpc_plan per frame of a recorded trajectory,
+plan_step / MpcController per live observation), on two rollouts: `_rollout_generator`, the closed loop encode ->
+generator -> forward model that leaves its actions in seq [steps,B,R,4], and `_rollout_open`, the forward model alone on
+a given seq.  Population 0 is the first; the last ndp_eval_score_select chooses.
+
 Beyond the reference: `cem=CemSettings(...)` on mpc_plan / plan_step / MpcController refines the rollouts' action
-sequences by the cross-entropy method before the choice (csrc/ndp_plan.inc: ndp_plan_cem_update, ndp_normal_noise); off by
-default, and then nothing here computes anything else than before.
+sequences by the cross-entropy method before the choice (csrc/ndp_plan.inc: ndp_plan_cem_update, ndp_normal_noise): rounds
+of select -> update -> open-loop rollout between population 0 and the choice.  Off by default: no rounds, and then
+nothing here launches anything else than the reference's planner needs.
 """
 import torch
 
@@ -81,10 +87,12 @@ class EvalModels:
                                                      self._stream()), "ndp_encoder_forward")
         return codes
 
-    def generate(self, code, noise, code_rep=1):
-        """code [rows,256], noise [rows*code_rep, nz] -> actions [rows*code_rep, 4] (Decoder.forward of the generator)."""
+    def generate(self, code, noise, code_rep=1, out=None):
+        """code [rows,256], noise [rows*code_rep, nz] -> actions [rows*code_rep, 4] (Decoder.forward of the generator),
+        written to `out` (contiguous, rows*code_rep*4 floats in any shape) when given.  Returns `out`."""
         m = int(code.shape[0]) * int(code_rep)
-        out = torch.empty(m, 4, dtype=torch.float32, device=self.device)
+        if out is None:
+            out = torch.empty(m, 4, dtype=torch.float32, device=self.device)
         with _capi.on_device(self.device):
             _capi.check(self.lib.ndp_g_forward(_ptr(self.g_params), self.noise_dim, _ptr(code), 256, int(code_rep), _ptr(noise),
                                                self.noise_dim, m, None, _ptr(out), self._stream()), "ndp_g_forward")
@@ -443,70 +451,91 @@ def _cem_normal(models, normal, need, seed):
     return normal.reshape(-1).to(models.device, non_blocking=True).float()
 
 
-def _cem_population0(models, cem, state, goal_code, b, r, steps, noise, rep):
-    """Population 0 of one planning step from `state` [B,3,128,128]: the action sequences seq [steps,B,R,4] and what
-    they lead to (the last predictions, the ts = 0 predictions).  noise: the step's `steps` pieces of B * R * nz floats.
-    "generator": mpc_plan's closed-loop rollouts, launch for launch.  "uniform": low + (high - low) * u, where component
-    c of row i at horizon step ts reads float c % nz of that row's piece (nz >= 4: four independent draws)."""
-    nz, br, dev = models.noise_dim, b * r, models.device
-    seq = torch.empty(steps, b, r, 4, dtype=torch.float32, device=dev)
+# ---------------------------------------------------------------------- one planning step
+def _broadcast(state, rep):
+    """rep [B*R,3,128,128] <- every image of state [B,3,128,128] R times, rows [B][R].  Returns rep."""
+    b = int(state.shape[0])
+    r = int(rep.shape[0]) // b
     rep.view(b, r, IMAGE_VALUES).copy_(state.view(b, 1, IMAGE_VALUES).expand(b, r, IMAGE_VALUES))
-    if cem.proposal == "uniform":
-        low = torch.tensor(cem.low, dtype=torch.float32).to(dev, non_blocking=True)
-        high = torch.tensor(cem.high, dtype=torch.float32).to(dev, non_blocking=True)
-        u = noise[:steps * br * nz].view(steps, b, r, nz)
-        u = torch.cat([u] * ((3 + nz) // nz), dim=3)[..., :4]   # component c reads float c % nz
-        torch.addcmul(low, u, high - low, out=seq)
-        torch.minimum(seq, high, out=seq)                       # low + (high - low) * u can round past high
-        pred = pred0 = models.forward(rep, seq[0].view(br, 4))
-        for ts in range(1, steps):
-            pred = models.forward(pred, seq[ts].view(br, 4))
-        return seq, pred, pred0
-    code_in = models.g_input(models.encode(state), r, goal_code, r, br)
-    act0 = models.generate(code_in, noise[:br * nz])
-    seq[0].view(br, 4).copy_(act0)
-    pred = pred0 = models.forward(rep, act0)
-    for ts in range(1, steps):
-        code_in = models.g_input(models.encode(pred), 1, goal_code, r, br)
-        act = models.generate(code_in, noise[ts * br * nz:(ts + 1) * br * nz])
-        seq[ts].view(br, 4).copy_(act)
+    return rep
+
+
+def _rollout_generator(models, state, goal_code, b, r, steps, noise, rep, seq):
+    """The closed-loop rollouts of one planning step from `state` [B,3,128,128]: per horizon step encode, the
+    generator's input with the goal code, R actions per trajectory (written to seq[ts], [B,R,4]) and the forward model
+    on the B * R rows.  At ts = 0 the state is encoded once per trajectory and its code broadcast to the R rows.  noise:
+    the step's `steps` pieces of B * R * nz floats.  Returns (the last predictions, the ts = 0 predictions)."""
+    nz, br = models.noise_dim, b * r
+    pred = _broadcast(state, rep)
+    for ts in range(steps):
+        code_in = models.g_input(models.encode(state if ts == 0 else pred), r if ts == 0 else 1, goal_code, r, br)
+        act = models.generate(code_in, noise[ts * br * nz:(ts + 1) * br * nz], out=seq[ts])
         pred = models.forward(pred, act)
-    return seq, pred, pred0
+        if ts == 0:
+            pred0 = pred
+    return pred, pred0
 
 
-def _cem_step(models, cem, state, goal, goal_code, b, r, steps, noise, normal, rep, forced, out_err, out_choice, out_act,
-              pred_out, curve, best):
-    """One planning step with `cem`: population 0, then `iterations` x (ndp_plan_cem_update, `steps` open-loop forward
-    passes on the B * R rows, ndp_eval_score_select).  The last selection (the only one `forced` applies to) fills
-    out_err [B,R], out_choice [B], out_act [B,4] and pred_out (or None) exactly as the planner without `cem` does;
-    curve [I+1,B] receives the chosen row's error per population, best [B] the least of them.  Returns (the last
-    population [steps,B,R,4], mean, std [B,steps,4])."""
-    dev, br, its = models.device, b * r, cem.iterations
-    seq, pred, pred0 = _cem_population0(models, cem, state, goal_code, b, r, steps, noise, rep)
-    mean = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
-    std = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
-    if its:
-        err = torch.empty(b, r, dtype=torch.float32, device=dev)
-        pick = torch.empty(b, dtype=torch.int32, device=dev)
-        act = torch.empty(b, 4, dtype=torch.float32, device=dev)
-        per = steps * br * 4
+def _rollout_open(models, state, seq, rep):
+    """The open-loop replay of the action sequences seq [steps,B,R,4] from `state`: one forward-model pass on the B * R
+    rows per horizon step, the slice seq[ts] as the action operand.  Returns (the last, the ts = 0 predictions)."""
+    pred = _broadcast(state, rep)
+    for ts in range(int(seq.shape[0])):
+        pred = models.forward(pred, seq[ts])
+        if ts == 0:
+            pred0 = pred
+    return pred, pred0
+
+
+def _uniform_actions(cem, noise, seq, nz):
+    """seq [steps,B,R,4] <- low + (high - low) * u, where component c of row i at horizon step ts reads float c % nz of
+    that row's piece of `noise` (nz >= 4: four independent draws)."""
+    low = torch.tensor(cem.low, dtype=torch.float32).to(seq.device, non_blocking=True)
+    high = torch.tensor(cem.high, dtype=torch.float32).to(seq.device, non_blocking=True)
+    u = noise[:seq.numel() // 4 * nz].view(*seq.shape[:3], nz)
+    u = torch.cat([u] * ((3 + nz) // nz), dim=3)[..., :4]       # component c reads float c % nz
+    torch.addcmul(low, u, high - low, out=seq)
+    torch.minimum(seq, high, out=seq)                           # low + (high - low) * u can round past high
+
+
+def _plan_once(models, cem, state, goal, goal_code, b, r, steps, noise, cem_io, rep, forced, out_err, out_choice, out_act,
+               pred_out):
+    """One planning step from `state` [B,3,128,128], for mpc_plan and plan_step alike.  Population 0 is the generator's
+    closed-loop rollouts (_rollout_generator), or with cem.proposal "uniform" a uniform draw replayed open loop; then
+    `cem.iterations` x (ndp_eval_score_select, ndp_plan_cem_update, _rollout_open) -- none when `cem` is None --; then the
+    last selection, the only one `forced` applies to, which fills out_err [B,R], out_choice [B], out_act [B,4] and
+    pred_out (the chosen ts = 0 prediction, or None).  cem_io: None, or with `cem` (normal, curve, best): the step's
+    normals [iteration][steps,B,R,4]; curve [I+1,B] receives the chosen row's error per population, best [B] the least of
+    them.  Returns (the last population [steps,B,R,4], mean, std [B,steps,4]; None, None without `cem`)."""
+    dev, br = models.device, b * r
+    seq = torch.empty(steps, b, r, 4, dtype=torch.float32, device=dev)
+    if cem is not None and cem.proposal == "uniform":
+        _uniform_actions(cem, noise, seq, models.noise_dim)
+        pred, pred0 = _rollout_open(models, state, seq, rep)
+    else:
+        pred, pred0 = _rollout_generator(models, state, goal_code, b, r, steps, noise, rep, seq)
+    its, per = 0 if cem is None else cem.iterations, steps * br * 4
+    mean = std = None
+    if cem is not None:
+        normal, curve, best = cem_io
+        mean = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
+        std = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
     for it in range(its):
-        models.score_select(pred, b, r, goal, seq[0], None, None, err, pick, act, None)
-        curve[it].copy_(err.gather(1, pick.long().view(b, 1)).view(b))
+        # the outputs of the last selection serve the earlier ones too: it overwrites all three
+        models.score_select(pred, b, r, goal, seq[0], None, None, out_err, out_choice, out_act, None)
+        curve[it].copy_(out_err.gather(1, out_choice.long().view(b, 1)).view(b))
         nxt = torch.empty_like(seq)
-        models.cem_update(err, seq, normal[it * per:(it + 1) * per], cem, it == 0, mean, std, nxt, best)
+        models.cem_update(out_err, seq, normal[it * per:(it + 1) * per], cem, it == 0, mean, std, nxt, best)
         seq = nxt
-        rep.view(b, r, IMAGE_VALUES).copy_(state.view(b, 1, IMAGE_VALUES).expand(b, r, IMAGE_VALUES))
-        pred = pred0 = models.forward(rep, seq[0].view(br, 4))
-        for ts in range(1, steps):
-            pred = models.forward(pred, seq[ts].view(br, 4))
+        pred, pred0 = _rollout_open(models, state, seq, rep)
     models.score_select(pred, b, r, goal, seq[0], pred0 if pred_out is not None else None, forced, out_err, out_choice,
                         out_act, pred_out)
-    curve[its].copy_(out_err.gather(1, out_choice.long().view(b, 1)).view(b))
-    if its:
-        torch.fmin(best, curve[its], out=best)
-    else:
-        best.copy_(curve[0])
+    if cem is not None:
+        curve[its].copy_(out_err.gather(1, out_choice.long().view(b, 1)).view(b))
+        if its:
+            torch.fmin(best, curve[its], out=best)
+        else:
+            best.copy_(curve[0])
     return seq, mean, std
 
 
@@ -532,7 +561,7 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     action_error [B].
 
     cem: None, or a CemSettings: every planning step refines its population by `cem.iterations` rounds of the
-    cross-entropy method before it chooses (_cem_step; `choices` replace the last selection only); with 0 iterations and
+    cross-entropy method before it chooses (_plan_once; `choices` replace the last selection only); with 0 iterations and
     the "generator" proposal every result above has the bits of the call without `cem`.  normal: None (device draws of
     ndp_normal_noise with `seed`), or the flat stream [planning step][iteration][steps,B,R,4] (cem_normal_floats(B, R,
     Th, I, seq_length=T) floats).  Added results: best_curve [T-1,I+1,B] the chosen row's error per population, best_err
@@ -571,43 +600,25 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     image_error_sum = torch.zeros(b, dtype=torch.float32, device=dev)     # reset per trajectory (mpc_eval.py:119)
     fut_idx = (torch.arange(b, device=dev, dtype=torch.int32) * t).view(1, b) + \
         torch.arange(1, t, device=dev, dtype=torch.int32).view(t1, 1)      # frame image_num + 1 of every trajectory
-    off = 0
     if cem is not None:
         normal = _cem_normal(models, normal, cem_normal_floats(b, r, th, cem.iterations, seq_length=t), seed)
         curve = torch.empty(t1, cem.iterations + 1, b, dtype=torch.float32, device=dev)
         best = torch.empty(t1, b, dtype=torch.float32, device=dev)
-        n_off = 0
+    off = n_off = 0
     for image_num in range(t1):
         if on_step is not None:
             on_step(image_num)
         steps = min(th, t1 - image_num)                                    # mpc_eval.py:131
+        n_noise, cem_io = steps * br * nz, None
         if cem is not None:
-            nxt = torch.empty(b, 3, 128, 128, dtype=torch.float32, device=dev)
-            n_need = cem.iterations * steps * br * 4
-            _, cem_mean, cem_std = _cem_step(
-                models, cem, state, goal, goal_code, b, r, steps, noise[off:off + steps * br * nz],
-                normal[n_off:n_off + n_need], rep, None if forced is None else forced[image_num], out_err[image_num],
-                out_choice[image_num], out_act[image_num], nxt, curve[image_num], best[image_num])
-            off += steps * br * nz
-            n_off += n_need
-            state = nxt
-            models.mse(state, imgs, b, IMAGE_VALUES, b_idx=fut_idx[image_num], out=image_errors[image_num],
-                       acc=image_error_sum)
-            continue
-        code_in = models.g_input(models.encode(state), r, goal_code, r, br)
-        act0 = models.generate(code_in, noise[off:off + br * nz])
-        off += br * nz
-        rep.view(b, r, IMAGE_VALUES).copy_(state.view(b, 1, IMAGE_VALUES).expand(b, r, IMAGE_VALUES))
-        pred0 = models.forward(rep, act0)
-        pred = pred0
-        for _ in range(1, steps):
-            code_in = models.g_input(models.encode(pred), 1, goal_code, r, br)
-            act = models.generate(code_in, noise[off:off + br * nz])
-            off += br * nz
-            pred = models.forward(pred, act)
+            n_normal = cem.iterations * steps * br * 4
+            cem_io = normal[n_off:n_off + n_normal], curve[image_num], best[image_num]
+            n_off += n_normal
         nxt = torch.empty(b, 3, 128, 128, dtype=torch.float32, device=dev)
-        models.score_select(pred, b, r, goal, act0, pred0, None if forced is None else forced[image_num],
-                            out_err[image_num], out_choice[image_num], out_act[image_num], nxt)
+        _, cem_mean, cem_std = _plan_once(models, cem, state, goal, goal_code, b, r, steps, noise[off:off + n_noise], cem_io,
+                                          rep, None if forced is None else forced[image_num], out_err[image_num],
+                                          out_choice[image_num], out_act[image_num], nxt)
+        off += n_noise
         state = nxt
         # image_error = mse(state_cur_mpc, state_fut) (mpc_eval.py:173-176): frame image_num + 1, the goal at the end
         models.mse(state, imgs, b, IMAGE_VALUES, b_idx=fut_idx[image_num], out=image_errors[image_num], acc=image_error_sum)
@@ -642,7 +653,7 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
     tensors (action [B,4], choice [B] int32, rollout_errors [B,R], actions0 [B,R,4]).
 
     cem: None, or a CemSettings: `cem.iterations` rounds of the cross-entropy method refine the population before the
-    choice (_cem_step; `choice` replaces the last selection only).  normal: None (device draws of ndp_normal_noise with
+    choice (_plan_once; `choice` replaces the last selection only).  normal: None (device draws of ndp_normal_noise with
     `seed`), or the flat stream [iteration][Th,B,R,4] (cem_normal_floats(B, R, Th, I) floats).  With `cem` a fifth
     value follows the four, which describe the last population: a dict of best_curve [I+1,B], best_err [B], cem_mean and
     cem_std [B,Th,4]; with 0 iterations and the "generator" proposal the four have the bits of the call without `cem`."""
@@ -668,33 +679,22 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
     forced = None
     if choice is not None:
         forced = torch.as_tensor(choice, dtype=torch.int32).reshape(b).to(dev, non_blocking=True)
-    state = state.contiguous()
-    if cem is not None:
-        normal = _cem_normal(models, normal, cem_normal_floats(b, r, th, cem.iterations), seed)
-        rep = torch.empty(br, 3, 128, 128, dtype=torch.float32, device=dev)
-        err = torch.empty(b, r, dtype=torch.float32, device=dev)
-        pick = torch.empty(b, dtype=torch.int32, device=dev)
-        action = torch.empty(b, 4, dtype=torch.float32, device=dev)
-        curve = torch.empty(cem.iterations + 1, b, dtype=torch.float32, device=dev)
-        best = torch.empty(b, dtype=torch.float32, device=dev)
-        seq, mean, std = _cem_step(models, cem, state, goal.contiguous(), goal_code, b, r, th, noise, normal, rep, forced,
-                                   err, pick, action, None, curve, best)
-        return action, pick, err, seq[0], {"best_curve": curve, "best_err": best, "cem_mean": mean, "cem_std": std}
-    code_in = models.g_input(models.encode(state), r, goal_code, r, br)
-    act0 = models.generate(code_in, noise[:br * nz])
     rep = torch.empty(br, 3, 128, 128, dtype=torch.float32, device=dev)
-    rep.view(b, r, IMAGE_VALUES).copy_(state.view(b, 1, IMAGE_VALUES).expand(b, r, IMAGE_VALUES))
-    pred = models.forward(rep, act0)
-    for ts in range(1, th):                                   # the full horizon, MPC_gym_eval.py:188
-        code_in = models.g_input(models.encode(pred), 1, goal_code, r, br)
-        act = models.generate(code_in, noise[ts * br * nz:(ts + 1) * br * nz])
-        pred = models.forward(pred, act)
     err = torch.empty(b, r, dtype=torch.float32, device=dev)
     pick = torch.empty(b, dtype=torch.int32, device=dev)
     action = torch.empty(b, 4, dtype=torch.float32, device=dev)
-    # nobody reads the chosen rollout's prediction (the environment gives the next state): no pred0 / pred_out copy
-    models.score_select(pred, b, r, goal.contiguous(), act0, None, forced, err, pick, action, None)
-    return action, pick, err, act0.view(b, r, 4)
+    cem_io = None
+    if cem is not None:
+        curve = torch.empty(cem.iterations + 1, b, dtype=torch.float32, device=dev)
+        best = torch.empty(b, dtype=torch.float32, device=dev)
+        cem_io = _cem_normal(models, normal, cem_normal_floats(b, r, th, cem.iterations), seed), curve, best
+    # the full horizon (MPC_gym_eval.py:188); nobody reads the chosen rollout's prediction (the environment gives the
+    # next state): no pred_out
+    seq, mean, std = _plan_once(models, cem, state.contiguous(), goal.contiguous(), goal_code, b, r, th, noise, cem_io, rep,
+                                forced, err, pick, action, None)
+    if cem is None:
+        return action, pick, err, seq[0]
+    return action, pick, err, seq[0], {"best_curve": curve, "best_err": best, "cem_mean": mean, "cem_std": std}
 
 
 class MpcController:
@@ -775,21 +775,13 @@ class MpcController:
     def plan(self, state, noise=None, choice=None, normal=None):
         """plan_step on `state` and the goal of reset(), then the one host synchronisation.  Returns (actions [B,4] on
         the host, info)."""
-        if noise is None:
-            seed = self.seed + self.steps
-        else:
-            seed = 0
-        extra = {}
-        if self.cem is None:
-            action, pick, err, act0 = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts, self.horizon,
-                                                noise=noise, seed=seed, choice=choice)
-        else:
-            if normal is None and self.normal is not None:
-                per = cem_normal_floats(int(state.shape[0]), self.rollouts, self.horizon, self.cem.iterations)
-                normal = self.normal.reshape(-1)[self.steps * per:(self.steps + 1) * per]
-            action, pick, err, act0, extra = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts,
-                                                       self.horizon, noise=noise, seed=self.seed + self.steps, choice=choice,
-                                                       cem=self.cem, normal=normal)
+        if self.cem is not None and normal is None and self.normal is not None:
+            per = cem_normal_floats(int(state.shape[0]), self.rollouts, self.horizon, self.cem.iterations)
+            normal = self.normal.reshape(-1)[self.steps * per:(self.steps + 1) * per]
+        action, pick, err, act0, *extra = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts, self.horizon,
+                                                    noise=noise, seed=self.seed + self.steps, choice=choice, cem=self.cem,
+                                                    normal=normal)
+        extra = extra[0] if extra else {}                     # with `cem`: best_curve, best_err, cem_mean, cem_std
         self.steps += 1
         with _capi.on_device(self.models.device):
             self._actions.copy_(action, non_blocking=True)

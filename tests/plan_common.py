@@ -1,11 +1,13 @@
 """What the tests of the planner's cross-entropy refinement share (tests/test_plan_cem_host.py on the CPU,
 tests/test_gpu_plan_cem.py on the GPU): the plain numpy restatement of ndp_plan_cem_update as include/ndp.h states it,
 the fp64 restatement of ndp_normal_noise's Box-Muller, the cases, and the packing for
-tests/host_drivers/plan_cem.inc (a body of tests/host_driver.py's program)."""
+tests/host_drivers/plan_cem.inc (a body of tests/host_driver.py's program); and `RecordingModels`, the stand-in for
+evaluation.EvalModels on which tests/test_planner_calls.py reads the planner's call sequence on the CPU."""
 import ctypes
 import struct
 
 import numpy as np
+import torch
 
 # (B, R, E, Th): the smallest, a few rows, R across a wave, the limits with E = R
 SHAPES = ((1, 2, 1, 1), (3, 5, 2, 3), (2, 65, 16, 4), (1, 256, 256, 32))
@@ -207,3 +209,93 @@ REFUSED = [{"err": None}, {"seq_in": None}, {"normal": None}, {"low": None}, {"h
            {"th": 33}, {"first": 2}, {"momentum": 1.0}, {"momentum": -0.5}, {"momentum": float("nan")}, {"min_std": -1.0},
            {"min_std": float("nan")}, {"low": [-1, -1, 2, -1]}, {"high": [1, float("nan"), 1, 1]}, {"seq_out": 0x2000},
            {"seq_out": 0x3000}, {"seq_in": 0x2004}, {"normal": 0x3008}, {"seq_out": 0x600c}]
+
+
+# ---------------------------------------------------------------------------------------------- the planner's calls
+class RecordingModels:
+    """evaluation.EvalModels' calls as small deterministic torch functions on the CPU; every call appends
+    (name, sizes...) to `calls`:
+      images (n)   encode (n)   g_input (state rows, state_rep, goal rows, goal_rep, rows)   generate (rows)
+      forward (n)   mse (pairs)   score_select (B, R, pred0 given, pred_out given, forced given)   uniform (n)
+      normal (n)   cem_update (Th, B, R, first)"""
+    VALUES = 3 * 128 * 128
+
+    def __init__(self):
+        self.device, self.noise_dim, self.calls = torch.device("cpu"), 2, []
+
+    def images(self, frames):
+        self.calls.append(("images", int(frames.shape[0])))
+        return frames.float().contiguous()
+
+    def encode(self, images):
+        n = int(images.shape[0])
+        self.calls.append(("encode", n))
+        return images.reshape(n, 128, -1).mean(dim=2) * 8
+
+    def g_input(self, state_code, state_rep, goal_code, goal_rep, rows):
+        self.calls.append(("g_input", int(state_code.shape[0]), int(state_rep), int(goal_code.shape[0]), int(goal_rep), int(rows)))
+        return torch.cat([state_code.repeat_interleave(int(state_rep), 0)[:rows],
+                          goal_code.repeat_interleave(int(goal_rep), 0)[:rows]], dim=1)
+
+    def generate(self, code, noise, code_rep=1, out=None):
+        m = int(code.shape[0]) * int(code_rep)
+        self.calls.append(("generate", m))
+        act = torch.tanh(code.repeat_interleave(int(code_rep), 0).view(m, 4, 64).sum(dim=2)
+                         + 3 * noise.reshape(m, self.noise_dim).repeat(1, 2) - 1.5)
+        if out is None:
+            return act
+        out.view(m, 4).copy_(act)
+        return out
+
+    def forward(self, state, actions):
+        n = int(state.shape[0])
+        self.calls.append(("forward", n))
+        a = actions.reshape(n, 4)
+        return 0.9 * state + 0.1 * a[:, :3].reshape(n, 3, 1, 1) * (1 + a[:, 3]).reshape(n, 1, 1, 1)
+
+    def mse(self, a, b, n_pairs, values, group=1, a_idx=None, b_idx=None, out=None, acc=None):
+        n_pairs, group = int(n_pairs), int(group)
+        self.calls.append(("mse", n_pairs))
+        a, b = a.reshape(-1, int(values)), b.reshape(-1, int(values))
+        a = a[:n_pairs] if a_idx is None else a[a_idx.long()]
+        b = b[:n_pairs] if b_idx is None else b[b_idx.long()]
+        res = ((a - b) ** 2).view(n_pairs // group, -1).mean(dim=1)
+        if out is None:
+            out = torch.empty(n_pairs // group)
+        out.copy_(res)
+        if acc is not None:
+            acc.add_(res)
+        return out
+
+    def score_select(self, pred, n_traj, rollouts, target, actions0, pred0, forced, err, choice, action_out, pred_out):
+        b, r = int(n_traj), int(rollouts)
+        self.calls.append(("score_select", b, r, pred0 is not None, pred_out is not None, forced is not None))
+        err.copy_(((pred.reshape(b, r, -1) - target.reshape(b, 1, -1)) ** 2).mean(dim=2))
+        for i in range(b):
+            best, pick = 10000000000.0, 0                             # the rollout rule: the first strict minimum
+            for k in range(r):
+                if err[i, k] < best:
+                    best, pick = float(err[i, k]), k
+            pick = pick if forced is None else int(forced[i])
+            choice[i] = pick
+            action_out[i] = actions0.reshape(b, r, 4)[i, pick]
+            if pred_out is not None:
+                pred_out[i] = pred0.reshape(b, r, *pred_out.shape[1:])[i, pick]
+
+    def uniform(self, n, seed):
+        self.calls.append(("uniform", int(n)))
+        return torch.rand(max(int(n), 1), generator=torch.Generator().manual_seed(int(seed)))
+
+    def normal(self, n, seed):
+        self.calls.append(("normal", int(n)))
+        return torch.randn(max(int(n), 1), generator=torch.Generator().manual_seed(int(seed) + (1 << 32)))
+
+    def cem_update(self, err, seq_in, normal, settings, first, mean, std, seq_out, best_err, elite_idx=None):
+        th, b, r = (int(v) for v in seq_in.shape[:3])
+        self.calls.append(("cem_update", th, b, r, bool(first)))
+        got = cem_update({"err": err.numpy(), "seq_in": seq_in.numpy(), "normal": normal.reshape(th, b, r, 4).numpy(),
+                          "elites": settings.elite_count(r), "first": int(bool(first)), "momentum": settings.momentum,
+                          "min_std": settings.min_std, "low": np.float32(settings.low), "high": np.float32(settings.high),
+                          "mean": mean.numpy(), "std": std.numpy(), "best_err": best_err.numpy()})
+        for dst, key in ((mean, "mean"), (std, "std"), (seq_out, "seq_out"), (best_err, "best_err")):
+            dst.copy_(torch.from_numpy(got[key]))

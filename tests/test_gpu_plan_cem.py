@@ -135,6 +135,8 @@ def _plan_step_inputs(models, b):
 
 
 def test_zero_iterations_give_the_bits_of_the_planner_without_cem(models):
+    """The plain planner, the planner with 0 iterations, and the restatement by hand on EvalModels' calls (_replay, which
+    does not go through the planner) agree bit for bit."""
     from ndivplanning_amd import evaluation as E
     b, t, r, th, nz = 2, 5, 5, 3, 2
     frames, actions = _mpc_inputs(b, t)
@@ -148,6 +150,10 @@ def test_zero_iterations_give_the_bits_of_the_planner_without_cem(models):
         assert with_cem["best_curve"].shape == (t - 1, 1, b)
         picked = plain["rollout_errors"].gather(2, plain["choices"].long().unsqueeze(2)).squeeze(2)
         assert torch.equal(with_cem["best_curve"][:, 0], picked) and torch.equal(with_cem["best_err"], picked)
+        drawn = kw["noise"] if "noise" in kw else models.uniform(noise.numel(), kw["seed"])
+        by_hand = _replay(models, off, frames, r, th, drawn, None)
+        for key in ("choices", "actions", "rollout_errors"):
+            assert torch.equal(plain[key], by_hand[key]), key
     state, goal, goal_code = _plan_step_inputs(models, b)
     step_noise = noise[:E.plan_step_noise_floats(b, r, th, nz)]
     for kw in ({"noise": step_noise}, {"seed": 12}):
@@ -158,10 +164,29 @@ def test_zero_iterations_give_the_bits_of_the_planner_without_cem(models):
             assert torch.equal(x, y)
 
 
+def test_plan_step_is_mpc_plans_first_planning_step(models):
+    """T = Th + 1: mpc_plan's first planning step has the full horizon, and plan_step on (frame 0, last frame) with the
+    same noise runs the same kernels on the same inputs."""
+    from ndivplanning_amd import evaluation as E
+    b, t, r, th, nz = 2, 4, 5, 3, 2
+    frames, actions = _mpc_inputs(b, t)
+    noise = torch.rand(E.mpc_noise_floats(b, t, r, th, nz), generator=torch.Generator().manual_seed(8)).to(DEV)
+    res = E.mpc_plan(models, frames, actions, r, th, noise=noise)
+    state, goal = frames[:, 0].contiguous(), frames[:, t - 1].contiguous()
+    action, choice, errors, actions0 = E.plan_step(models, state, goal, models.encode(goal), r, th,
+                                                   noise=noise[:E.plan_step_noise_floats(b, r, th, nz)])
+    assert torch.equal(choice, res["choices"][0])
+    assert torch.equal(errors, res["rollout_errors"][0])
+    assert torch.equal(action, res["actions"][:, 0])
+    assert actions0.shape == (b, r, 4)
+    assert torch.equal(action, actions0.gather(1, choice.long().view(b, 1, 1).expand(b, 1, 4)).view(b, 4))
+
+
 def _replay(models, cem, frames, r, th, noise, normal):
     """mpc_plan with `cem` restated on EvalModels' calls and ndp_plan_cem_update.  Returns what mpc_plan returns under
-    the same keys, plus `best_trace` [T-1][I][B] (best_err after every update) and `row0` [(before, after)]: the rank-0
-    error and the error of row 0 of the next population, the same sequence re-evaluated."""
+    the same keys (rollout_errors: the err of each planning step's last selection), plus `best_trace` [T-1][I][B]
+    (best_err after every update) and `row0` [(before, after)]: the rank-0 error and the error of row 0 of the next
+    population, the same sequence re-evaluated."""
     from ndivplanning_amd import evaluation as E
     b, t = int(frames.shape[0]), int(frames.shape[1])
     t1, nz, br, its = t - 1, models.noise_dim, b * r, cem.iterations
@@ -169,7 +194,7 @@ def _replay(models, cem, frames, r, th, noise, normal):
     goal = per[:, t1].contiguous().view(b, 3, 128, 128)
     goal_code = models.encode(goal)
     state = per[:, 0].contiguous().view(b, 3, 128, 128)
-    choices, actions, curve, trace, row0 = [], [], [], [], []
+    choices, actions, errors, curve, trace, row0 = [], [], [], [], [], []
     off = n_off = 0
     for image_num in range(t1):
         steps = min(th, t1 - image_num)
@@ -209,12 +234,14 @@ def _replay(models, cem, frames, r, th, noise, normal):
         models.score_select(pred, b, r, goal, seq[0].contiguous(), pred0, None, err, pick, act_out, nxt)
         step_curve.append(err.gather(1, pick.long().view(b, 1)).view(b).clone())
         choices.append(pick.clone())
+        errors.append(err.clone())
         actions.append(act_out.clone())
         curve.append(torch.stack(step_curve))
         trace.append(step_trace)
         state = nxt
     return {"choices": torch.stack(choices), "actions": torch.stack(actions).transpose(0, 1).contiguous(),
-            "best_curve": torch.stack(curve), "cem_mean": mean, "cem_std": std, "best_trace": trace, "row0": row0}
+            "rollout_errors": torch.stack(errors), "best_curve": torch.stack(curve), "cem_mean": mean, "cem_std": std,
+            "best_trace": trace, "row0": row0}
 
 
 @pytest.fixture(scope="module")
@@ -395,6 +422,30 @@ def test_the_planner_kernels_are_timed(models):
     finally:
         _capi.timing_enable(False)
     assert seen["k_plan_cem_update"][1] == 2 * 2 and seen["k_normal_noise"][1] == 1, sorted(seen)
+
+
+def test_launch_counts_of_the_planner_without_cem(models):
+    """mpc_plan without `cem` at T = 4, Th = 2: S = 2 + 2 + 1 horizon steps in T - 1 planning steps.  One generator,
+    one code-input and one forward-model launch per horizon step, one encoder pass per horizon step and one for the goal,
+    one selection per planning step, and nothing of the refinement."""
+    from ndivplanning_amd import _capi
+    from ndivplanning_amd import evaluation as E
+    b, t, r, th = 2, 4, 4, 2
+    frames, actions = _mpc_inputs(b, t)
+    s = sum(min(th, t - 1 - i) for i in range(t - 1))
+    assert s == 5
+    _capi.timing_enable(True)
+    try:
+        E.mpc_plan(models, frames, actions, r, th, seed=1)
+        torch.cuda.synchronize()
+        seen = _capi.timing_collect()
+    finally:
+        _capi.timing_enable(False)
+    counts = {k: v[1] for k, v in seen.items()}
+    print(sorted(counts.items()))
+    assert counts["k_g_fwd"] == s and counts["k_eval_g_input"] == s and counts["k_fm_image_cols"] == s, counts
+    assert counts["k_enc_conv1"] == s + 1 and counts["k_eval_select"] == t - 1, counts
+    assert "k_plan_cem_update" not in counts and "k_normal_noise" not in counts, counts
 
 
 def test_mpc_eval_cli_with_and_without_the_cem_mapping(tmp_path):
