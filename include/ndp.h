@@ -818,6 +818,46 @@ int ndp_plan_cem_update(const float *err, const float *seq_in, const float *norm
                         int32_t *elite_idx, void *stream);
 int ndp_normal_noise(float *out, int64_t n, uint64_t seed, const int32_t *offset_dev, void *stream);
 
+/* ndp_plan_update: ndp_plan_cem_update with the weighting of the refit chosen and its one flag `first` split in two; the
+ * same kernel body, every other argument, limit and refusal as above.  ndp_plan_cem_update is this call with weighting =
+ * NDP_PLAN_ELITES and smooth = !first, and keeps its bits.
+ *   smooth     1: the refit is smoothed against the mean / std it is given (in/out); 0: they are only written.  E' == 0:
+ *              mean and std stay with smooth = 1, are 0 and min_std with smooth = 0
+ *   first      1: best_err is only written; 0: it is the running minimum.  A planning step that starts from a carried
+ *              prior (ndp_plan_warm) runs its first update with smooth = 1, first = 1
+ *   weighting  NDP_PLAN_ELITES: the refit above.  NDP_PLAN_MPPI: ranking, E', elite_idx, row 0, best_err, resampling and
+ *              clamping as above; the refit over the E' elites x_0 .. x_{E'-1} with errors e_0 <= e_1 <= ... in rank
+ *              order weighs them, in fp64: w_0 = 1; w_k = 1 where e_k == e_0; otherwise w_k = exp(-((double)e_k -
+ *              (double)e_0) / (double)temperature), so an infinite e_k weighs 0, and e_0 == inf gives all ones through
+ *              the equality rule, never inf - inf.  W = sum w_k in rank order (W >= 1: no division by zero); m = sum w_k
+ *              x_k / W; s = sqrt(sum w_k (x_k - m)^2 / W): fp64, fixed order, every product and sum rounded (no
+ *              contraction), w_k (d d) with the square first; then the smoothing, the floor and the one rounding to fp32
+ *              as above.  The weights are computed once per elite, not per component.
+ *   temperature  with NDP_PLAN_MPPI finite and > 0, on the scale of err (ndp_eval_score_select: the pixel MSE of normalised
+ *              images); not read with NDP_PLAN_ELITES
+ * weighting, smooth or first outside their values, a bad temperature: NDP_E_ARG, nothing launched.
+ *
+ * ndp_plan_warm: the fit of one planning step turned into the prior and the injected rows of the next, in ONE launch.
+ *   mean_prev, std_prev  [B,steps_prev,4] device: the previous planning step's fit
+ *   normal     [steps,B,W,4] device: standard normal draws; row 0 of every (ts, b) is not read
+ *   mean, std  [B,steps,4] device, written: with src(ts) = min(ts + 1, steps_prev - 1), mean[ts] = mean_prev[src(ts)] bit
+ *              for bit and std[ts] = max(std_prev[src(ts)], warm_std); a NaN deviation gives warm_std
+ *   warm       [steps,B,W,4] device, written: row 0 is mean[ts] clamped to [low, high] of its component (a NaN stays NaN),
+ *              rows 1 .. W-1 are (float)((double)std * (double)n + (double)mean), clamped: ndp_plan_cem_update's draw
+ * 1 <= B <= 65535, 1 <= W = rows <= NDP_MAX_SAMPLES - 1, 1 <= steps <= steps_prev <= 32, warm_std finite and >= 0, low <=
+ * high per component, every buffer 16-byte aligned.  A limit exceeded, a null pointer, a misaligned buffer, an output
+ * that is one of the inputs or another output: NDP_E_ARG, nothing launched.  One thread per row, 16-byte loads and
+ * stores, no atomics, no scratch memory, no host synchronisation: two calls give the same bits. */
+#define NDP_PLAN_ELITES 0
+#define NDP_PLAN_MPPI   1
+int ndp_plan_update(const float *err, const float *seq_in, const float *normal, int64_t n_traj, int rollouts, int steps,
+                    int elites, int weighting, float temperature, int smooth, int first, float momentum, float min_std,
+                    const float *low4, const float *high4, float *mean, float *std, float *seq_out, float *best_err,
+                    int32_t *elite_idx, void *stream);
+int ndp_plan_warm(const float *mean_prev, const float *std_prev, const float *normal, int64_t n_traj, int rows,
+                  int steps_prev, int steps, float warm_std, const float *low4, const float *high4, float *mean,
+                  float *std, float *warm, void *stream);
+
 /* --------------------------------------------------------------- push world ---
  * A small FetchPush-like world of the project's own (push_world.py): a gripper, a block and a goal
  * on a table, the reference's 4-component actions, n environments at once.  The world is in metres.

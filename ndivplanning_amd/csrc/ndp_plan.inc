@@ -1,9 +1,12 @@
 // ndp_plan.inc -- the planner's cross-entropy refinement (evaluation.py: mpc_plan / plan_step with `cem`):
-//   k_plan_cem_update  one CEM iteration on a scored population of action sequences, seq [Th][B][R][4]: rank the R
-//                      rollouts of a trajectory by their goal error, refit a diagonal Gaussian to the E best, draw the
-//                      next population from it (row 0 keeps the best sequence), keep the running minimum of the error
+//   k_plan_update      one iteration on a scored population of action sequences, seq [Th][B][R][4]: rank the R
+//                      rollouts of a trajectory by their goal error, refit a diagonal Gaussian to the E best (equal
+//                      weights: the cross-entropy method, ndp_plan_cem_update; or MPPI's exp(-(e - e_best) / temperature),
+//                      ndp_plan_update), draw the next population from it (row 0 keeps the best sequence), keep the
+//                      running minimum of the error
+//   k_plan_warm        the previous planning step's fit shifted by one action: the next step's prior and its injected rows
 //   k_normal_noise     standard normal draws, Box-Muller over ndp_uniform_noise's stream
-// k_plan_cem_update runs one workgroup of 256 threads per trajectory, in four phases separated by barriers:
+// k_plan_update runs one workgroup of 256 threads per trajectory, in four phases separated by barriers:
 //   1  thread r < R stages err[b][r] in LDS;
 //   2  thread r < R counts the rollouts that beat it: its rank; order[rank] = r in LDS (a permutation: `beats` is a
 //      strict total order).  A NaN error ranks behind every number; among equals and among NaNs the index decides;
@@ -12,9 +15,12 @@
 //      leaves mean and std in LDS; thread 0 also updates best_err, threads < E write elite_idx;
 //   4  thread i walks the (ts, r) pairs i, i + 256, ...: consecutive rollouts in consecutive lanes, one 16-byte load of
 //      the normals and one 16-byte store; row 0 is the rank-0 sequence, copied.
+// With MPPI weighting a phase 2b follows the ranking: thread k < E' leaves w_k in LDS once (256 doubles), and after one
+// more barrier phase 3 sums with them in rank order; no component thread computes an exponential.
 // Every sum has a fixed order, nothing is atomic, nothing spills: two calls give the same bits.  The arithmetic is in
-// ndp::plan, __host__ __device__: tests/host_drivers/plan_cem.inc (a body of main.hip) runs exactly these functions by
-// this schedule on the CPU.  Included at the end of ndp_kernels.hip, after ndp_store.inc.
+// ndp::plan, __host__ __device__: tests/host_drivers/plan_cem.inc (a body of main.hip) and plan_warm.inc (the body of
+// plan_warm_main.hip) run exactly these functions by this schedule on the CPU.  Included at the end of ndp_kernels.hip,
+// after ndp_store.inc.
 
 namespace ndp {
 namespace plan {
@@ -45,6 +51,21 @@ __host__ __device__ inline int64_t seq_index(int ts, int64_t b, int r, int c, in
   return (((int64_t)ts * n_traj + b) * rollouts + r) * kActionDim + c;
 }
 
+// the fit (m, s) of one component smoothed against the previous one in *mean / *std (unless `first`), floored and rounded
+__host__ __device__ inline void settle(double m, double s, int first, float momentum, float min_std, float* mean,
+                                       float* std) {
+#pragma clang fp contract(off)
+  if (!first) {
+    const double mo = (double)momentum, keep = 1.0 - mo;
+    m = mo * (double)*mean + keep * m;
+    s = mo * (double)*std + keep * s;
+  }
+  const double least = (double)min_std;
+  s = s > least ? s : least;                            // a NaN deviation gives the floor
+  *mean = (float)m;
+  *std = (float)s;
+}
+
 // Component (ts, c) of trajectory b refitted to the rows order[0 .. ne): *mean and *std hold the previous fit on entry
 // (unless `first`) and the new one on return.  ne == 0: they stay, or are 0 and min_std with `first`.
 __host__ __device__ inline void refit(const float* seq, int64_t n_traj, int rollouts, int64_t b, int ts, int c,
@@ -63,25 +84,60 @@ __host__ __device__ inline void refit(const float* seq, int64_t n_traj, int roll
     const double d = (double)seq[seq_index(ts, b, order[k], c, n_traj, rollouts)] - m;
     dev += d * d;
   }
-  double s = sqrt(dev / (double)ne);
-  if (!first) {
-    const double mo = (double)momentum, keep = 1.0 - mo;
-    m = mo * (double)*mean + keep * m;
-    s = mo * (double)*std + keep * s;
+  settle(m, sqrt(dev / (double)ne), first, momentum, min_std, mean, std);
+}
+
+// MPPI's weight of the elite with error ek beside the best, e0 <= ek, neither a NaN: equal errors (two infinities too)
+// weigh 1, an infinite ek beside a finite e0 weighs 0
+__host__ __device__ inline double mppi_weight(float ek, float e0, float temperature) {
+#pragma clang fp contract(off)
+  if (ek == e0) return 1.0;
+  return exp(-((double)ek - (double)e0) / (double)temperature);
+}
+
+// refit with the weights w[0 .. ne) of the rows order[0 .. ne), w[0] = 1: m = sum w x / W, s = sqrt(sum w (x - m)^2 / W),
+// W = sum w >= 1, all in rank order; `first` and ne == 0 as in refit
+__host__ __device__ inline void refit_mppi(const float* seq, int64_t n_traj, int rollouts, int64_t b, int ts, int c,
+                                           const int* order, const double* w, int ne, int first, float momentum,
+                                           float min_std, float* mean, float* std) {
+#pragma clang fp contract(off)
+  if (ne == 0) {
+    if (first) { *mean = 0.f; *std = min_std; }
+    return;
   }
-  const double least = (double)min_std;
-  s = s > least ? s : least;                            // a NaN deviation gives the floor
-  *mean = (float)m;
-  *std = (float)s;
+  double total = 0.0, sum = 0.0;
+  for (int k = 0; k < ne; ++k) {
+    total += w[k];
+    sum += w[k] * (double)seq[seq_index(ts, b, order[k], c, n_traj, rollouts)];
+  }
+  const double m = sum / total;
+  double dev = 0.0;
+  for (int k = 0; k < ne; ++k) {
+    const double d = (double)seq[seq_index(ts, b, order[k], c, n_traj, rollouts)] - m;
+    dev += w[k] * (d * d);
+  }
+  settle(m, sqrt(dev / total), first, momentum, min_std, mean, std);
+}
+
+// v clamped to [lo, hi]; a NaN stays NaN
+__host__ __device__ inline float clamp_keep_nan(float v, float lo, float hi) {
+  return v != v ? v : fminf(fmaxf(v, lo), hi);
 }
 
 // one resampled action component: std * n is exact in fp64, so the sum is rounded twice (fp64, then fp32) whether or
 // not the two are contracted; clamped to [lo, hi], a NaN stays NaN
 __host__ __device__ inline float sample(float std, float n, float mean, float lo, float hi) {
 #pragma clang fp contract(off)
-  const float v = (float)((double)std * (double)n + (double)mean);
-  return v != v ? v : fminf(fmaxf(v, lo), hi);
+  return clamp_keep_nan((float)((double)std * (double)n + (double)mean), lo, hi);
 }
+
+// the deviation a planning step carries to the next: floored, a NaN gives the floor
+__host__ __device__ inline float carried_std(float std_prev, float warm_std) {
+  return std_prev > warm_std ? std_prev : warm_std;
+}
+
+// the horizon step of the previous fit that step ts of the next planning step continues
+__host__ __device__ inline int warm_source(int ts, int steps_prev) { return ts + 1 < steps_prev ? ts + 1 : steps_prev - 1; }
 
 // the running minimum of the rank-0 error: a NaN never replaces a number
 __host__ __device__ inline float best_of(float old, float e, int first) {
@@ -98,11 +154,21 @@ struct PlanCemArgs {
   float* mean; float* std; float* seq_out; float* best_err; int32_t* elite_idx;
 };
 
-__global__ __launch_bounds__(plan::kBlock) void k_plan_cem_update(PlanCemArgs a) {
+// what ndp_plan_update adds to ndp_plan_cem_update's arguments; c.first: best_err is only written
+struct PlanUpdateArgs {
+  PlanCemArgs c;
+  int smooth;                                             // the refit smooths against the mean / std it is given
+  float temperature;                                      // kWeighting == NDP_PLAN_MPPI
+};
+
+template <int kWeighting>
+__global__ __launch_bounds__(plan::kBlock) void k_plan_update(PlanUpdateArgs u) {
   using namespace plan;
+  const PlanCemArgs& a = u.c;
   __shared__ float err_s[NDP_MAX_SAMPLES];
   __shared__ int order_s[NDP_MAX_SAMPLES];
   __shared__ float mean_s[kMaxDim], std_s[kMaxDim];
+  __shared__ double w_s[kWeighting == NDP_PLAN_MPPI ? NDP_MAX_SAMPLES : 1];   // the elites' weights; unused without MPPI
   const int t = threadIdx.x, R = a.rollouts, D = a.steps * kActionDim;
   const int64_t b = blockIdx.x;
   float e = 0.f;
@@ -111,10 +177,19 @@ __global__ __launch_bounds__(plan::kBlock) void k_plan_cem_update(PlanCemArgs a)
   if (t < R) order_s[rank_of(err_s, R, t)] = t;
   __syncthreads();
   const int ne = valid < a.elites ? valid : a.elites;
+  const int fresh = !u.smooth;
+  if constexpr (kWeighting == NDP_PLAN_MPPI) {
+    if (t < ne) w_s[t] = mppi_weight(err_s[order_s[t]], err_s[order_s[0]], u.temperature);
+    __syncthreads();
+  }
   if (t < D) {
     float m = 0.f, s = 0.f;
-    if (!a.first) { m = a.mean[b * D + t]; s = a.std[b * D + t]; }
-    refit(a.seq_in, a.n_traj, R, b, t / kActionDim, t % kActionDim, order_s, ne, a.first, a.momentum, a.min_std, &m, &s);
+    if (u.smooth) { m = a.mean[b * D + t]; s = a.std[b * D + t]; }
+    const int ts = t / kActionDim, c = t % kActionDim;
+    if constexpr (kWeighting == NDP_PLAN_MPPI)
+      refit_mppi(a.seq_in, a.n_traj, R, b, ts, c, order_s, w_s, ne, fresh, a.momentum, a.min_std, &m, &s);
+    else
+      refit(a.seq_in, a.n_traj, R, b, ts, c, order_s, ne, fresh, a.momentum, a.min_std, &m, &s);
     mean_s[t] = m;
     std_s[t] = s;
     a.mean[b * D + t] = m;
@@ -141,6 +216,55 @@ __global__ __launch_bounds__(plan::kBlock) void k_plan_cem_update(PlanCemArgs a)
     }
     *reinterpret_cast<float4*>(a.seq_out + at) = o;
   }
+}
+
+struct PlanWarmArgs {
+  const float* mean_prev; const float* std_prev; const float* normal;
+  int64_t n_traj; int rows, steps_prev, steps;
+  float warm_std, low[4], high[4];
+  float* mean; float* std; float* warm;
+};
+
+namespace plan {
+
+// Row i = (ts * B + b) * W + w of the warm launch: the fit of step warm_source(ts) of trajectory b, its deviation floored;
+// w == 0 stores the carried mean and deviation and writes the clamped mean, every other row a draw around it.
+__host__ __device__ inline void warm_row(const PlanWarmArgs& a, int64_t i) {
+  const int w = (int)(i % a.rows);
+  const int64_t b = i / a.rows % a.n_traj;
+  const int ts = (int)(i / a.rows / a.n_traj);
+  const int64_t from = (b * a.steps_prev + warm_source(ts, a.steps_prev)) * kActionDim;
+  const float4 mu = *reinterpret_cast<const float4*>(a.mean_prev + from);
+  float4 sd = *reinterpret_cast<const float4*>(a.std_prev + from);
+  sd.x = carried_std(sd.x, a.warm_std);
+  sd.y = carried_std(sd.y, a.warm_std);
+  sd.z = carried_std(sd.z, a.warm_std);
+  sd.w = carried_std(sd.w, a.warm_std);
+  float4 o;
+  if (w == 0) {
+    const int64_t to = (b * a.steps + ts) * kActionDim;
+    *reinterpret_cast<float4*>(a.mean + to) = mu;
+    *reinterpret_cast<float4*>(a.std + to) = sd;
+    o.x = clamp_keep_nan(mu.x, a.low[0], a.high[0]);
+    o.y = clamp_keep_nan(mu.y, a.low[1], a.high[1]);
+    o.z = clamp_keep_nan(mu.z, a.low[2], a.high[2]);
+    o.w = clamp_keep_nan(mu.w, a.low[3], a.high[3]);
+  } else {
+    const float4 n = *reinterpret_cast<const float4*>(a.normal + i * kActionDim);
+    o.x = sample(sd.x, n.x, mu.x, a.low[0], a.high[0]);
+    o.y = sample(sd.y, n.y, mu.y, a.low[1], a.high[1]);
+    o.z = sample(sd.z, n.z, mu.z, a.low[2], a.high[2]);
+    o.w = sample(sd.w, n.w, mu.w, a.low[3], a.high[3]);
+  }
+  *reinterpret_cast<float4*>(a.warm + i * kActionDim) = o;
+}
+
+}  // namespace plan
+
+// one thread per row of warm [Th][B][W][4]: consecutive rows in consecutive lanes, 16-byte loads and stores
+__global__ __launch_bounds__(plan::kBlock) void k_plan_warm(PlanWarmArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * plan::kBlock + threadIdx.x;
+  if (i < (int64_t)a.steps * a.n_traj * a.rows) plan::warm_row(a, i);
 }
 
 // Box-Muller on one Philox block: thread j owns uniforms 4j .. 4j+3 of the stream (seed, offset), the pairs 2j and
@@ -172,34 +296,94 @@ __global__ __launch_bounds__(kThreads) void k_normal_noise(float* out, int64_t n
 
 extern "C" {
 
+// the checks and the launch behind ndp_plan_cem_update and ndp_plan_update; `who` names the entry point in messages,
+// `label` the launch in the timing table
+static int plan_update_launch(const char* who, const char* label, const float* err, const float* seq_in,
+                              const float* normal, int64_t n_traj, int rollouts, int steps, int elites, int weighting, float temperature,
+                              int smooth, int first, float momentum, float min_std, const float* low4, const float* high4,
+                              float* mean, float* std, float* seq_out, float* best_err, int32_t* elite_idx, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(err && seq_in && normal && low4 && high4 && mean && std && seq_out && best_err, "%s: null pointer", who);
+  NDP_CHECK_ARG(n_traj >= 1 && n_traj <= 65535, "%s: n_traj=%lld outside 1..65535", who, (long long)n_traj);
+  NDP_CHECK_ARG(rollouts >= 2 && rollouts <= NDP_MAX_SAMPLES, "%s: rollouts=%d outside 2..%d", who, rollouts,
+                NDP_MAX_SAMPLES);
+  NDP_CHECK_ARG(elites >= 1 && elites <= rollouts, "%s: elites=%d outside 1..%d", who, elites, rollouts);
+  NDP_CHECK_ARG(steps >= 1 && steps <= plan::kMaxSteps, "%s: steps=%d outside 1..%d", who, steps, plan::kMaxSteps);
+  NDP_CHECK_ARG(first == 0 || first == 1, "%s: first must be 0 or 1", who);
+  NDP_CHECK_ARG(smooth == 0 || smooth == 1, "%s: smooth must be 0 or 1", who);
+  NDP_CHECK_ARG(weighting == NDP_PLAN_ELITES || weighting == NDP_PLAN_MPPI, "%s: weighting=%d is neither NDP_PLAN_ELITES "
+                "nor NDP_PLAN_MPPI", who, weighting);
+  NDP_CHECK_ARG(weighting != NDP_PLAN_MPPI || (temperature > 0.f && temperature < INFINITY),
+                "%s: temperature=%g must be finite and > 0", who, (double)temperature);
+  NDP_CHECK_ARG(momentum >= 0.f && momentum < 1.f, "%s: momentum=%g outside [0, 1)", who, (double)momentum);
+  NDP_CHECK_ARG(min_std >= 0.f, "%s: min_std=%g must be >= 0", who, (double)min_std);
+  for (int c = 0; c < 4; ++c)
+    NDP_CHECK_ARG(low4[c] <= high4[c], "%s: low[%d]=%g above high[%d]=%g (or NaN)", who, c, (double)low4[c], c,
+                  (double)high4[c]);
+  NDP_CHECK_ARG(seq_out != seq_in && seq_out != normal, "%s: seq_out aliases seq_in or normal", who);
+  NDP_CHECK_ARG(aligned16(seq_in) && aligned16(normal) && aligned16(seq_out),
+                "%s: seq_in, normal and seq_out must be 16-byte aligned", who);
+  PlanUpdateArgs u{{err, seq_in, normal, n_traj, rollouts, steps, elites, first, momentum, min_std, {}, {},
+                    mean, std, seq_out, best_err, elite_idx}, smooth, temperature};
+  for (int c = 0; c < 4; ++c) { u.c.low[c] = low4[c]; u.c.high[c] = high4[c]; }
+  hipStream_t st = (hipStream_t)stream;
+  KTimer kt(label, st);
+  if (weighting == NDP_PLAN_MPPI)
+    hipLaunchKernelGGL(k_plan_update<NDP_PLAN_MPPI>, dim3((unsigned)n_traj), dim3(plan::kBlock), 0, st, u);
+  else
+    hipLaunchKernelGGL(k_plan_update<NDP_PLAN_ELITES>, dim3((unsigned)n_traj), dim3(plan::kBlock), 0, st, u);
+  return check_launch(label);
+}
+
 int ndp_plan_cem_update(const float* err, const float* seq_in, const float* normal, int64_t n_traj, int rollouts, int steps,
                         int elites, int first, float momentum, float min_std, const float* low4, const float* high4,
                         float* mean, float* std, float* seq_out, float* best_err, int32_t* elite_idx, void* stream) {
+  return plan_update_launch("ndp_plan_cem_update", "k_plan_cem_update", err, seq_in, normal, n_traj, rollouts, steps,
+                            elites, NDP_PLAN_ELITES, 0.f, first == 0, first, momentum, min_std, low4, high4, mean, std, seq_out,
+                            best_err, elite_idx, stream);
+}
+
+int ndp_plan_update(const float* err, const float* seq_in, const float* normal, int64_t n_traj, int rollouts, int steps,
+                    int elites, int weighting, float temperature, int smooth, int first, float momentum, float min_std,
+                    const float* low4, const float* high4, float* mean, float* std, float* seq_out, float* best_err,
+                    int32_t* elite_idx, void* stream) {
+  return plan_update_launch("ndp_plan_update", "k_plan_update", err, seq_in, normal, n_traj, rollouts, steps, elites,
+                            weighting, temperature, smooth, first, momentum, min_std, low4, high4, mean, std, seq_out,
+                            best_err, elite_idx, stream);
+}
+
+int ndp_plan_warm(const float* mean_prev, const float* std_prev, const float* normal, int64_t n_traj, int rows,
+                  int steps_prev, int steps, float warm_std, const float* low4, const float* high4, float* mean, float* std,
+                  float* warm, void* stream) {
   using namespace ndp;
-  NDP_CHECK_ARG(err && seq_in && normal && low4 && high4 && mean && std && seq_out && best_err,
-                "ndp_plan_cem_update: null pointer");
-  NDP_CHECK_ARG(n_traj >= 1 && n_traj <= 65535, "ndp_plan_cem_update: n_traj=%lld outside 1..65535", (long long)n_traj);
-  NDP_CHECK_ARG(rollouts >= 2 && rollouts <= NDP_MAX_SAMPLES, "ndp_plan_cem_update: rollouts=%d outside 2..%d", rollouts,
-                NDP_MAX_SAMPLES);
-  NDP_CHECK_ARG(elites >= 1 && elites <= rollouts, "ndp_plan_cem_update: elites=%d outside 1..%d", elites, rollouts);
-  NDP_CHECK_ARG(steps >= 1 && steps <= plan::kMaxSteps, "ndp_plan_cem_update: steps=%d outside 1..%d", steps,
+  NDP_CHECK_ARG(mean_prev && std_prev && normal && low4 && high4 && mean && std && warm, "ndp_plan_warm: null pointer");
+  NDP_CHECK_ARG(n_traj >= 1 && n_traj <= 65535, "ndp_plan_warm: n_traj=%lld outside 1..65535", (long long)n_traj);
+  NDP_CHECK_ARG(rows >= 1 && rows <= NDP_MAX_SAMPLES - 1, "ndp_plan_warm: rows=%d outside 1..%d", rows,
+                NDP_MAX_SAMPLES - 1);
+  NDP_CHECK_ARG(steps_prev >= 1 && steps_prev <= plan::kMaxSteps, "ndp_plan_warm: steps_prev=%d outside 1..%d", steps_prev,
                 plan::kMaxSteps);
-  NDP_CHECK_ARG(first == 0 || first == 1, "ndp_plan_cem_update: first must be 0 or 1");
-  NDP_CHECK_ARG(momentum >= 0.f && momentum < 1.f, "ndp_plan_cem_update: momentum=%g outside [0, 1)", (double)momentum);
-  NDP_CHECK_ARG(min_std >= 0.f, "ndp_plan_cem_update: min_std=%g must be >= 0", (double)min_std);
+  NDP_CHECK_ARG(steps >= 1 && steps <= steps_prev, "ndp_plan_warm: steps=%d outside 1..steps_prev=%d", steps, steps_prev);
+  NDP_CHECK_ARG(warm_std >= 0.f && warm_std < INFINITY, "ndp_plan_warm: warm_std=%g must be finite and >= 0",
+                (double)warm_std);
   for (int c = 0; c < 4; ++c)
-    NDP_CHECK_ARG(low4[c] <= high4[c], "ndp_plan_cem_update: low[%d]=%g above high[%d]=%g (or NaN)", c, (double)low4[c], c,
+    NDP_CHECK_ARG(low4[c] <= high4[c], "ndp_plan_warm: low[%d]=%g above high[%d]=%g (or NaN)", c, (double)low4[c], c,
                   (double)high4[c]);
-  NDP_CHECK_ARG(seq_out != seq_in && seq_out != normal, "ndp_plan_cem_update: seq_out aliases seq_in or normal");
-  NDP_CHECK_ARG(aligned16(seq_in) && aligned16(normal) && aligned16(seq_out),
-                "ndp_plan_cem_update: seq_in, normal and seq_out must be 16-byte aligned");
-  PlanCemArgs a{err, seq_in, normal, n_traj, rollouts, steps, elites, first, momentum, min_std, {}, {},
-                mean, std, seq_out, best_err, elite_idx};
+  const float* in[3] = {mean_prev, std_prev, normal};
+  float* out[3] = {mean, std, warm};
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j)
+      NDP_CHECK_ARG(out[i] != in[j], "ndp_plan_warm: an output aliases an input");
+    for (int j = 0; j < i; ++j) NDP_CHECK_ARG(out[i] != out[j], "ndp_plan_warm: two outputs alias");
+  }
+  NDP_CHECK_ARG(aligned16(mean_prev) && aligned16(std_prev) && aligned16(normal) && aligned16(mean) && aligned16(std) &&
+                    aligned16(warm), "ndp_plan_warm: every buffer must be 16-byte aligned");
+  PlanWarmArgs a{mean_prev, std_prev, normal, n_traj, rows, steps_prev, steps, warm_std, {}, {}, mean, std, warm};
   for (int c = 0; c < 4; ++c) { a.low[c] = low4[c]; a.high[c] = high4[c]; }
+  const int64_t n = (int64_t)steps * n_traj * rows;       // at most 32 * 65535 * 255 rows: under 2^23 blocks
   hipStream_t st = (hipStream_t)stream;
-  KTimer kt("k_plan_cem_update", st);
-  hipLaunchKernelGGL(k_plan_cem_update, dim3((unsigned)n_traj), dim3(plan::kBlock), 0, st, a);
-  return check_launch("k_plan_cem_update");
+  KTimer kt("k_plan_warm", st);
+  hipLaunchKernelGGL(k_plan_warm, dim3((unsigned)((n + plan::kBlock - 1) / plan::kBlock)), dim3(plan::kBlock), 0, st, a);
+  return check_launch("k_plan_warm");
 }
 
 int ndp_normal_noise(float* out, int64_t n, uint64_t seed, const int32_t* offset_dev, void* stream) {

@@ -26,6 +26,9 @@ Beyond the reference: `cem=CemSettings(...)` on mpc_plan / plan_step / MpcContro
 sequences by the cross-entropy method before the choice (csrc/ndp_plan.inc: ndp_plan_cem_update, ndp_normal_noise): rounds
 of select -> update -> open-loop rollout between population 0 and the choice.  Off by default: no rounds, and then
 nothing here launches anything else than the reference's planner needs.
+Two further opt-in fields of CemSettings: `weighting="mppi"` weighs the elites by exp(-(e - e_best) / temperature)
+(ndp_plan_update), and `warm_start=True` starts a planning step from the previous step's fit shifted by one action
+(ndp_plan_warm; plan_step's `prior`, carried by mpc_plan and MpcController).
 """
 import torch
 
@@ -205,6 +208,28 @@ class EvalModels:
                                                      _ptr(mean), _ptr(std), _ptr(seq_out), _ptr(best_err), _ptr(elite_idx),
                                                      self._stream()), "ndp_plan_cem_update")
 
+    def plan_update(self, err, seq_in, normal, settings, smooth, first, mean, std, seq_out, best_err, elite_idx=None):
+        """ndp_plan_update: cem_update with settings.weighting / settings.temperature and the two flags apart: `smooth`
+        (the refit is smoothed against the mean / std given) and `first` (best_err is only written)."""
+        th, b, r = int(seq_in.shape[0]), int(seq_in.shape[1]), int(seq_in.shape[2])
+        low, high = (_capi.c_float * 4)(*settings.low), (_capi.c_float * 4)(*settings.high)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_plan_update(_ptr(err), _ptr(seq_in), _ptr(normal), b, r, th, settings.elite_count(r),
+                                                 WEIGHTINGS.index(settings.weighting), settings.temperature or 0.0,
+                                                 1 if smooth else 0, 1 if first else 0, settings.momentum, settings.min_std,
+                                                 low, high, _ptr(mean), _ptr(std), _ptr(seq_out), _ptr(best_err),
+                                                 _ptr(elite_idx), self._stream()), "ndp_plan_update")
+
+    def plan_warm(self, mean_prev, std_prev, normal, settings, mean, std, warm):
+        """ndp_plan_warm: the previous planning step's fit mean_prev / std_prev [B,steps_prev,4] shifted by one action into
+        mean / std [B,steps,4], and the rows warm [steps,B,W,4] the next population receives (row 0: the clamped mean)."""
+        th, b, w = int(warm.shape[0]), int(warm.shape[1]), int(warm.shape[2])
+        low, high = (_capi.c_float * 4)(*settings.low), (_capi.c_float * 4)(*settings.high)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_plan_warm(_ptr(mean_prev), _ptr(std_prev), _ptr(normal), b, w, int(mean_prev.shape[1]),
+                                               th, settings.carried_floor(), low, high, _ptr(mean), _ptr(std), _ptr(warm),
+                                               self._stream()), "ndp_plan_warm")
+
 
 # ---------------------------------------------------------------------- the reference's noise stream (CPU)
 def noise_piece_shapes(kind, batch, seq_length, num_sample, noise_dim, rollouts=None, horizon=None):
@@ -350,11 +375,24 @@ class CemSettings:
       proposal    population 0: "generator" (the closed-loop generator rollouts) or "uniform" (low + (high - low) * u
                   from the same noise stream, the baseline)
       low, high   bounds of the 4 action components: one number for all, or 4
+      weighting   "elites": the `elites` best count equally (the cross-entropy refit); "mppi": they are weighed by
+                  exp(-(e - e_best) / temperature) (ndp_plan_update)
+      temperature None; with "mppi" required, finite and > 0 (in fp32 too).  It is absolute, on the scale of
+                  ndp_eval_score_select's err, the pixel MSE of normalised images; there is no default because nobody has
+                  measured one
+      warm_start  False; True: a planning step starts from the previous step's fit shifted by one action (ndp_plan_warm):
+                  it is the prior the first refit smooths against, and `warm_rows` rows of population 0 are drawn from it.
+                  Needs iterations >= 1: without a refit there is no fit to carry
+      warm_rows   rows R - W .. R - 1 of population 0 that the carried fit replaces; None: max(1, R // 4); 1 <= W <= R - 1
+      warm_std    floor of the carried deviation; None: min_std.  The fit collapses towards min_std within a planning
+                  step, so the carried one is widened again to keep exploring
     The defaults are hyperparameters, not measurements."""
 
-    FIELDS = ("iterations", "elites", "momentum", "min_std", "proposal", "low", "high")
+    FIELDS = ("iterations", "elites", "momentum", "min_std", "proposal", "low", "high", "weighting", "temperature",
+              "warm_start", "warm_rows", "warm_std")
 
-    def __init__(self, iterations=3, elites=None, momentum=0.1, min_std=0.05, proposal="generator", low=-1.0, high=1.0):
+    def __init__(self, iterations=3, elites=None, momentum=0.1, min_std=0.05, proposal="generator", low=-1.0, high=1.0,
+                 weighting="elites", temperature=None, warm_start=False, warm_rows=None, warm_std=None):
         def integer(v, name):
             if isinstance(v, bool) or int(v) != v:
                 raise ValueError("cem.%s must be an integer, got %r" % (name, v))
@@ -384,6 +422,30 @@ class CemSettings:
         self.low, self.high = four(low, "low"), four(high, "high")
         if any(lo > hi for lo, hi in zip(self.low, self.high)):
             raise ValueError("cem.low must not exceed cem.high, got %r and %r" % (self.low, self.high))
+        if weighting not in WEIGHTINGS:
+            raise ValueError("cem.weighting must be 'elites' or 'mppi', got %r" % (weighting,))
+        self.weighting = weighting
+        self.temperature = None if temperature is None else float(temperature)
+        if weighting == "mppi":
+            # the kernel reads it as fp32: it must be finite and > 0 there too
+            if self.temperature is None or not 0.0 < _capi.c_float(self.temperature).value < float("inf"):
+                raise ValueError("cem.weighting 'mppi' needs cem.temperature finite and > 0 (in fp32), got %r" % (temperature,))
+        elif self.temperature is not None:
+            raise ValueError("cem.temperature is read only with cem.weighting 'mppi', got %r" % (temperature,))
+        if not isinstance(warm_start, bool):
+            raise ValueError("cem.warm_start must be true or false, got %r" % (warm_start,))
+        self.warm_start = warm_start
+        if self.warm_start and self.iterations < 1:
+            raise ValueError("cem.warm_start needs cem.iterations >= 1: without a refit there is no fit to carry")
+        self.warm_rows = None if warm_rows is None else integer(warm_rows, "warm_rows")
+        self.warm_std = None if warm_std is None else float(warm_std)
+        if not self.warm_start and (self.warm_rows is not None or self.warm_std is not None):
+            raise ValueError("cem.warm_rows and cem.warm_std are read only with cem.warm_start")
+        if self.warm_rows is not None and not 1 <= self.warm_rows <= _capi.MAX_SAMPLES - 1:
+            raise ValueError("cem.warm_rows must lie in 1..%d (and below the rollouts), got %d"
+                             % (_capi.MAX_SAMPLES - 1, self.warm_rows))
+        if self.warm_std is not None and not 0.0 <= self.warm_std < float("inf"):
+            raise ValueError("cem.warm_std must be finite and >= 0, got %r" % (warm_std,))
 
     @classmethod
     def from_config(cls, mapping):
@@ -406,11 +468,24 @@ class CemSettings:
             raise ValueError("cem.elites=%d exceeds the %d rollouts" % (e, r))
         return e
 
+    def warm_count(self, rollouts):
+        """W: the rows of population 0 that a carried fit replaces."""
+        r = int(rollouts)
+        self.elite_count(r)
+        w = max(1, r // 4) if self.warm_rows is None else self.warm_rows
+        if not 1 <= w <= r - 1:
+            raise ValueError("cem.warm_rows=%d outside 1..%d (the rollouts less one)" % (w, r - 1))
+        return w
+
+    def carried_floor(self):
+        return self.min_std if self.warm_std is None else self.warm_std
+
     def __repr__(self):
         return "CemSettings(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f in self.FIELDS)
 
 
 CEM_MAX_HORIZON = 32
+WEIGHTINGS = ("elites", "mppi")                 # NDP_PLAN_ELITES, NDP_PLAN_MPPI
 
 
 def cem_normal_floats(batch, rollouts, horizon, iterations, seq_length=None):
@@ -422,6 +497,21 @@ def cem_normal_floats(batch, rollouts, horizon, iterations, seq_length=None):
         return per * int(horizon)
     t1 = int(seq_length) - 1
     return per * sum(min(int(horizon), t1 - i) for i in range(t1))
+
+
+def plan_normal_floats(batch, rollouts, horizon, cem, seq_length=None, prior=False):
+    """Standard normal floats the planner consumes with the settings `cem`: cem_normal_floats for the iterations, and
+    ahead of them steps * B * W * 4 for ndp_plan_warm in every planning step that starts from a prior.  seq_length None: one
+    plan_step call, with or without `prior`; otherwise one mpc_plan call on T = seq_length frames, where with
+    cem.warm_start every planning step but the first has one (`prior` is not read)."""
+    b, r, th = int(batch), int(rollouts), int(horizon)
+    n = cem_normal_floats(b, r, th, cem.iterations, seq_length)
+    if seq_length is None:
+        return n + (th * b * cem.warm_count(r) * 4 if prior else 0)
+    if not cem.warm_start:
+        return n
+    t1 = int(seq_length) - 1
+    return n + b * cem.warm_count(r) * 4 * sum(min(th, t1 - i) for i in range(1, t1))
 
 
 def cem_from_config(config, rollouts=None, horizon=None):
@@ -439,6 +529,8 @@ def _cem_check(cem, rollouts, horizon):
     if not isinstance(cem, CemSettings):
         raise TypeError("cem must be an evaluation.CemSettings, got %r" % (cem,))
     cem.elite_count(rollouts)
+    if cem.warm_start:
+        cem.warm_count(rollouts)
     if int(horizon) > CEM_MAX_HORIZON:
         raise ValueError("the cross-entropy planner takes a horizon of at most %d, got %d" % (CEM_MAX_HORIZON, int(horizon)))
 
@@ -460,16 +552,21 @@ def _broadcast(state, rep):
     return rep
 
 
-def _rollout_generator(models, state, goal_code, b, r, steps, noise, rep, seq):
+def _rollout_generator(models, state, goal_code, b, r, steps, noise, rep, seq, warm=None):
     """The closed-loop rollouts of one planning step from `state` [B,3,128,128]: per horizon step encode, the
     generator's input with the goal code, R actions per trajectory (written to seq[ts], [B,R,4]) and the forward model
     on the B * R rows.  At ts = 0 the state is encoded once per trajectory and its code broadcast to the R rows.  noise:
-    the step's `steps` pieces of B * R * nz floats.  Returns (the last predictions, the ts = 0 predictions)."""
+    the step's `steps` pieces of B * R * nz floats.  warm: None, or [steps,B,W,4]: at every horizon step warm[ts] replaces the
+    last W rows of seq[ts] after the generator has written them and before the forward model reads them, so those rows cost
+    no extra forward-model rows (the generator's later actions for them are computed and discarded).  Returns (the last
+    predictions, the ts = 0 predictions)."""
     nz, br = models.noise_dim, b * r
     pred = _broadcast(state, rep)
     for ts in range(steps):
         code_in = models.g_input(models.encode(state if ts == 0 else pred), r if ts == 0 else 1, goal_code, r, br)
         act = models.generate(code_in, noise[ts * br * nz:(ts + 1) * br * nz], out=seq[ts])
+        if warm is not None:
+            seq[ts, :, r - int(warm.shape[2]):].copy_(warm[ts])       # act is seq[ts]
         pred = models.forward(pred, act)
         if ts == 0:
             pred0 = pred
@@ -499,33 +596,54 @@ def _uniform_actions(cem, noise, seq, nz):
 
 
 def _plan_once(models, cem, state, goal, goal_code, b, r, steps, noise, cem_io, rep, forced, out_err, out_choice, out_act,
-               pred_out):
+               pred_out, prior=None):
     """One planning step from `state` [B,3,128,128], for mpc_plan and plan_step alike.  Population 0 is the generator's
     closed-loop rollouts (_rollout_generator), or with cem.proposal "uniform" a uniform draw replayed open loop; then
     `cem.iterations` x (ndp_eval_score_select, ndp_plan_cem_update, _rollout_open) -- none when `cem` is None --; then the
     last selection, the only one `forced` applies to, which fills out_err [B,R], out_choice [B], out_act [B,4] and
     pred_out (the chosen ts = 0 prediction, or None).  cem_io: None, or with `cem` (normal, curve, best): the step's
     normals [iteration][steps,B,R,4]; curve [I+1,B] receives the chosen row's error per population, best [B] the least of
-    them.  Returns (the last population [steps,B,R,4], mean, std [B,steps,4]; None, None without `cem`)."""
+    them.  Returns (the last population [steps,B,R,4], mean, std [B,steps,4]; None, None without `cem`).
+    prior: None, or with cem.warm_start the previous planning step's (mean, std) [B,steps_prev,4], steps <= steps_prev:
+    one ndp_plan_warm shifts it into this step's mean / std and draws W = cem.warm_count(R) rows per horizon step from it,
+    which replace rows R - W .. R - 1 of population 0; the first update then smooths against the shifted fit (smooth = 1,
+    first = 1).  The step's normals are then [steps,B,W,4] ahead of the iterations' blocks.  cem.weighting "mppi" or a
+    prior send every update through ndp_plan_update; otherwise the step is ndp_plan_cem_update's, bit for bit."""
     dev, br = models.device, b * r
     seq = torch.empty(steps, b, r, 4, dtype=torch.float32, device=dev)
+    mean = std = warm = None
+    if prior is not None:
+        normal, curve, best = cem_io
+        n_warm = steps * b * cem.warm_count(r) * 4
+        mean = torch.empty(b, steps, 4, dtype=torch.float32, device=dev)
+        std = torch.empty(b, steps, 4, dtype=torch.float32, device=dev)
+        warm = torch.empty(steps, b, cem.warm_count(r), 4, dtype=torch.float32, device=dev)
+        models.plan_warm(prior[0], prior[1], normal[:n_warm], cem, mean, std, warm)
+        cem_io = normal[n_warm:], curve, best
     if cem is not None and cem.proposal == "uniform":
         _uniform_actions(cem, noise, seq, models.noise_dim)
+        if warm is not None:
+            seq[:, :, r - int(warm.shape[2]):].copy_(warm)
         pred, pred0 = _rollout_open(models, state, seq, rep)
     else:
-        pred, pred0 = _rollout_generator(models, state, goal_code, b, r, steps, noise, rep, seq)
+        pred, pred0 = _rollout_generator(models, state, goal_code, b, r, steps, noise, rep, seq, warm)
     its, per = 0 if cem is None else cem.iterations, steps * br * 4
-    mean = std = None
     if cem is not None:
         normal, curve, best = cem_io
-        mean = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
-        std = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
+        if prior is None:
+            mean = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
+            std = torch.zeros(b, steps, 4, dtype=torch.float32, device=dev)
+    general = cem is not None and (cem.weighting != "elites" or prior is not None)
     for it in range(its):
         # the outputs of the last selection serve the earlier ones too: it overwrites all three
         models.score_select(pred, b, r, goal, seq[0], None, None, out_err, out_choice, out_act, None)
         curve[it].copy_(out_err.gather(1, out_choice.long().view(b, 1)).view(b))
         nxt = torch.empty_like(seq)
-        models.cem_update(out_err, seq, normal[it * per:(it + 1) * per], cem, it == 0, mean, std, nxt, best)
+        if general:
+            models.plan_update(out_err, seq, normal[it * per:(it + 1) * per], cem, it > 0 or prior is not None, it == 0, mean,
+                               std, nxt, best)
+        else:
+            models.cem_update(out_err, seq, normal[it * per:(it + 1) * per], cem, it == 0, mean, std, nxt, best)
         seq = nxt
         pred, pred0 = _rollout_open(models, state, seq, rep)
     models.score_select(pred, b, r, goal, seq[0], pred0 if pred_out is not None else None, forced, out_err, out_choice,
@@ -563,9 +681,11 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     cem: None, or a CemSettings: every planning step refines its population by `cem.iterations` rounds of the
     cross-entropy method before it chooses (_plan_once; `choices` replace the last selection only); with 0 iterations and
     the "generator" proposal every result above has the bits of the call without `cem`.  normal: None (device draws of
-    ndp_normal_noise with `seed`), or the flat stream [planning step][iteration][steps,B,R,4] (cem_normal_floats(B, R,
-    Th, I, seq_length=T) floats).  Added results: best_curve [T-1,I+1,B] the chosen row's error per population, best_err
-    [T-1,B] the least of them, cem_mean / cem_std [B,steps,4] the last planning step's fit (zeros with 0 iterations)."""
+    ndp_normal_noise with `seed`), or the flat stream [planning step][iteration][steps,B,R,4] (plan_normal_floats(B, R,
+    Th, cem, seq_length=T) floats; with cem.warm_start every planning step but the first has [steps,B,W,4] ahead of its
+    iterations, and starts from the fit of the step before it, _plan_once's `prior`).  Added results: best_curve
+    [T-1,I+1,B] the chosen row's error per population, best_err [T-1,B] the least of them, cem_mean / cem_std [B,steps,4]
+    the last planning step's fit (zeros with 0 iterations)."""
     r, th = int(rollouts), int(horizon)
     if r < 1 or th < 1:
         raise ValueError("rollouts and horizon must be >= 1, got %d, %d" % (r, th))
@@ -601,10 +721,11 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     fut_idx = (torch.arange(b, device=dev, dtype=torch.int32) * t).view(1, b) + \
         torch.arange(1, t, device=dev, dtype=torch.int32).view(t1, 1)      # frame image_num + 1 of every trajectory
     if cem is not None:
-        normal = _cem_normal(models, normal, cem_normal_floats(b, r, th, cem.iterations, seq_length=t), seed)
+        normal = _cem_normal(models, normal, plan_normal_floats(b, r, th, cem, seq_length=t), seed)
         curve = torch.empty(t1, cem.iterations + 1, b, dtype=torch.float32, device=dev)
         best = torch.empty(t1, b, dtype=torch.float32, device=dev)
     off = n_off = 0
+    prior = None
     for image_num in range(t1):
         if on_step is not None:
             on_step(image_num)
@@ -612,12 +733,16 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
         n_noise, cem_io = steps * br * nz, None
         if cem is not None:
             n_normal = cem.iterations * steps * br * 4
+            if prior is not None:
+                n_normal += steps * b * cem.warm_count(r) * 4
             cem_io = normal[n_off:n_off + n_normal], curve[image_num], best[image_num]
             n_off += n_normal
         nxt = torch.empty(b, 3, 128, 128, dtype=torch.float32, device=dev)
         _, cem_mean, cem_std = _plan_once(models, cem, state, goal, goal_code, b, r, steps, noise[off:off + n_noise], cem_io,
                                           rep, None if forced is None else forced[image_num], out_err[image_num],
-                                          out_choice[image_num], out_act[image_num], nxt)
+                                          out_choice[image_num], out_act[image_num], nxt, prior)
+        if cem is not None and cem.warm_start:
+            prior = cem_mean, cem_std                                      # shifted by one action at the next step
         off += n_noise
         state = nxt
         # image_error = mse(state_cur_mpc, state_fut) (mpc_eval.py:173-176): frame image_num + 1, the goal at the end
@@ -638,7 +763,8 @@ def plan_step_noise_floats(batch, rollouts, horizon, noise_dim):
     return int(horizon) * int(batch) * int(rollouts) * int(noise_dim)
 
 
-def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, seed=0, choice=None, cem=None, normal=None):
+def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, seed=0, choice=None, cem=None, normal=None,
+              prior=None):
     """One planning step of MPC_gym_eval.py:183-225 for B environments at once, rows [B][R]: from the observed `state`
     [B,3,128,128], R rollouts of Th steps through encoder, generator and forward model, scored against the goal image.
 
@@ -656,7 +782,11 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
     choice (_plan_once; `choice` replaces the last selection only).  normal: None (device draws of ndp_normal_noise with
     `seed`), or the flat stream [iteration][Th,B,R,4] (cem_normal_floats(B, R, Th, I) floats).  With `cem` a fifth
     value follows the four, which describe the last population: a dict of best_curve [I+1,B], best_err [B], cem_mean and
-    cem_std [B,Th,4]; with 0 iterations and the "generator" proposal the four have the bits of the call without `cem`."""
+    cem_std [B,Th,4]; with 0 iterations and the "generator" proposal the four have the bits of the call without `cem`.
+
+    prior: None, or with cem.warm_start (anything else: ValueError) the pair (cem_mean, cem_std) [B,steps_prev,4],
+    steps_prev >= Th, that the previous call returned: the step starts from that fit shifted by one action (_plan_once),
+    and `normal` is then [Th,B,W,4] ahead of the iterations (plan_normal_floats(B, R, Th, cem, prior=True) floats)."""
     r, th = int(rollouts), int(horizon)
     if r < 1 or th < 1:
         raise ValueError("rollouts and horizon must be >= 1, got %d, %d" % (r, th))
@@ -676,6 +806,15 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
         if noise.numel() != need:
             raise ValueError("noise has %d floats, plan_step needs %d" % (noise.numel(), need))
         noise = noise.reshape(-1).to(dev, non_blocking=True).float()
+    if prior is not None:
+        if cem is None or not cem.warm_start:
+            raise ValueError("prior is read only with cem.warm_start")
+        prior = tuple(p.to(dev, non_blocking=True).float().contiguous() for p in prior)
+        if len(prior) != 2 or any(p.dim() != 3 or int(p.shape[0]) != b or int(p.shape[2]) != 4 or
+                                  tuple(p.shape) != tuple(prior[0].shape) for p in prior) or \
+                not th <= int(prior[0].shape[1]) <= CEM_MAX_HORIZON:
+            raise ValueError("prior must be (mean, std), both [%d,steps_prev,4] with %d <= steps_prev <= %d, got %s"
+                             % (b, th, CEM_MAX_HORIZON, [tuple(p.shape) for p in prior]))
     forced = None
     if choice is not None:
         forced = torch.as_tensor(choice, dtype=torch.int32).reshape(b).to(dev, non_blocking=True)
@@ -687,11 +826,11 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
     if cem is not None:
         curve = torch.empty(cem.iterations + 1, b, dtype=torch.float32, device=dev)
         best = torch.empty(b, dtype=torch.float32, device=dev)
-        cem_io = _cem_normal(models, normal, cem_normal_floats(b, r, th, cem.iterations), seed), curve, best
+        cem_io = _cem_normal(models, normal, plan_normal_floats(b, r, th, cem, prior=prior is not None), seed), curve, best
     # the full horizon (MPC_gym_eval.py:188); nobody reads the chosen rollout's prediction (the environment gives the
     # next state): no pred_out
     seq, mean, std = _plan_once(models, cem, state.contiguous(), goal.contiguous(), goal_code, b, r, th, noise, cem_io, rep,
-                                forced, err, pick, action, None)
+                                forced, err, pick, action, None, prior)
     if cem is None:
         return action, pick, err, seq[0]
     return action, pick, err, seq[0], {"best_curve": curve, "best_err": best, "cem_mean": mean, "cem_std": std}
@@ -719,8 +858,11 @@ class MpcController:
             _cem_check(cem, self.rollouts, self.horizon)
         # cem: a CemSettings turns plan_step's cross-entropy refinement on for every plan(); `info` then also carries
         # best_curve, best_err, cem_mean, cem_std.  normal: None (device draws, seeded as the noise is), or the flat
-        # stream of successive plan() calls since reset(), [call][iteration][Th,B,R,4]; plan(normal=) overrides it
+        # stream of successive plan() calls since reset(), [call][iteration][Th,B,R,4]; plan(normal=) overrides it.
+        # With cem.warm_start every plan() after the first since reset() starts from the fit of the one before it
+        # (plan_step's `prior`), and its piece of the stream has [Th,B,W,4] ahead of the iterations
         self.cem, self.normal = cem, normal
+        self._prior, self._normal_off = None, 0
         self.resizer = LanczosResizer(models.device)
         self.frame_shape = None                               # None: the first frame tells
         if frame_shape is not None:
@@ -742,6 +884,7 @@ class MpcController:
         if self._staging is None and self.frame_shape is not None:
             self._staging = torch.empty((b,) + self.frame_shape + (3,), dtype=torch.uint8, pin_memory=True)
         self.steps = 0
+        self._prior, self._normal_off = None, 0               # the next plan() is a first one: no fit to carry
 
     def observe(self, raw_frames):
         """bytes [B,H,W,3], host or device -> (resized bytes [B,128,128,3], normalised floats [B,3,128,128]) on the
@@ -775,13 +918,17 @@ class MpcController:
     def plan(self, state, noise=None, choice=None, normal=None):
         """plan_step on `state` and the goal of reset(), then the one host synchronisation.  Returns (actions [B,4] on
         the host, info)."""
-        if self.cem is not None and normal is None and self.normal is not None:
-            per = cem_normal_floats(int(state.shape[0]), self.rollouts, self.horizon, self.cem.iterations)
-            normal = self.normal.reshape(-1)[self.steps * per:(self.steps + 1) * per]
+        if self.cem is not None:
+            per = plan_normal_floats(int(state.shape[0]), self.rollouts, self.horizon, self.cem, prior=self._prior is not None)
+            if normal is None and self.normal is not None:
+                normal = self.normal.reshape(-1)[self._normal_off:self._normal_off + per]
+            self._normal_off += per
         action, pick, err, act0, *extra = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts, self.horizon,
                                                     noise=noise, seed=self.seed + self.steps, choice=choice, cem=self.cem,
-                                                    normal=normal)
+                                                    normal=normal, prior=self._prior)
         extra = extra[0] if extra else {}                     # with `cem`: best_curve, best_err, cem_mean, cem_std
+        if self.cem is not None and self.cem.warm_start:
+            self._prior = extra["cem_mean"], extra["cem_std"]
         self.steps += 1
         with _capi.on_device(self.models.device):
             self._actions.copy_(action, non_blocking=True)

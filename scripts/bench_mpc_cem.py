@@ -4,9 +4,13 @@ R = 32 rollouts, horizon Th = 5, B = 1 and 64 environments, per planning step:
   uniform I  the same with the uniform proposal (no generator, no encoder inside the horizon)
   single     the single-shot planner (no `cem`) with R * (I + 1) rollouts: the same number of forward-model rows, the
              equal-budget comparison
-and the update launch's own time (k_plan_cem_update, k_normal_noise) from ndp_timing_*.  With random weights the goal
-error says nothing about plan quality: this script reports time only.  Median over STEPS timed repetitions after
-WARMUP.  Usage: python scripts/bench_mpc_cem.py [B ...]   (default: 1 64)"""
+and the launches' own times (k_plan_cem_update or k_plan_update, k_plan_warm, k_normal_noise) from ndp_timing_*.
+  --weighting mppi --temperature T   the refit with MPPI weights (ndp_plan_update) in the cem / uniform arms
+  --warm-start                       adds the arm `warm I` (I >= 1): the same planning step started from the fit of a
+                                     previous one (plan_step's `prior`: one ndp_plan_warm and Th slice copies more)
+With random weights the goal error says nothing about plan quality: this script reports time only.  Median over STEPS
+timed repetitions after WARMUP.  Usage: python scripts/bench_mpc_cem.py [options] [B ...]   (default: 1 64)"""
+import argparse
 import os
 import sys
 import time
@@ -51,8 +55,9 @@ def median_ms(fn):
     return 1e3 * ts[len(ts) // 2]
 
 
-def main(sizes):
+def main(sizes, weighting="elites", temperature=None, warm_start=False):
     nets = modules()
+    how = dict(weighting=weighting, temperature=temperature)
     models = E.EvalModels(*nets, DEV)
     print("R=%d Th=%d: one planning step; forward-model rows per step = B * R * Th * (I + 1)" % (R, TH))
     for b in sizes:
@@ -64,8 +69,15 @@ def main(sizes):
             for i in range(ITERATIONS + 1):
                 row = {}
                 for proposal in ("generator", "uniform"):
-                    cem = E.CemSettings(iterations=i, proposal=proposal)
+                    cem = E.CemSettings(iterations=i, proposal=proposal, **how)
                     row[proposal] = median_ms(lambda: E.plan_step(models, state, goal, goal_code, R, TH, seed=1, cem=cem))
+                warm = ""
+                if warm_start and i >= 1:
+                    cem = E.CemSettings(iterations=i, warm_start=True, **how)
+                    info = E.plan_step(models, state, goal, goal_code, R, TH, seed=1, cem=cem)[4]
+                    prior = info["cem_mean"], info["cem_std"]
+                    warm = "   warm %9.3f ms" % median_ms(lambda: E.plan_step(models, state, goal, goal_code, R, TH, seed=1,
+                                                                               cem=cem, prior=prior))
                 rows = R * (i + 1)
                 if b * rows <= SINGLE_MAX_ROWS and rows <= _capi.MAX_SAMPLES:
                     wide = E.EvalModels(*nets, DEV)                  # its own workspace, released after the measurement
@@ -74,22 +86,30 @@ def main(sizes):
                     torch.cuda.empty_cache()
                 else:
                     single = "not measured (%d rows in one forward-model call: its workspace does not fit)" % (b * rows)
-                print("   I=%d  cem %9.3f ms   uniform %9.3f ms   single-shot with R=%-3d %s   (%d forward-model rows)"
-                      % (i, row["generator"], row["uniform"], rows, single, b * rows * TH))
-            cem = E.CemSettings(iterations=ITERATIONS)
-            E.plan_step(models, state, goal, goal_code, R, TH, seed=1, cem=cem)
+                print("   I=%d  cem %9.3f ms%s   uniform %9.3f ms   single-shot with R=%-3d %s   (%d forward-model rows)"
+                      % (i, row["generator"], warm, row["uniform"], rows, single, b * rows * TH))
+            cem = E.CemSettings(iterations=ITERATIONS, warm_start=warm_start, **how)
+            info = E.plan_step(models, state, goal, goal_code, R, TH, seed=1, cem=cem)[4]
+            prior = (info["cem_mean"], info["cem_std"]) if warm_start else None
+            E.plan_step(models, state, goal, goal_code, R, TH, seed=1, cem=cem, prior=prior)
             torch.cuda.synchronize()
             _capi.timing_enable(True)
-            E.plan_step(models, state, goal, goal_code, R, TH, seed=1, cem=cem)
+            E.plan_step(models, state, goal, goal_code, R, TH, seed=1, cem=cem, prior=prior)
             torch.cuda.synchronize()
             split = sorted(_capi.timing_collect().items(), key=lambda kv: -kv[1][0])
             _capi.timing_enable(False)
         total = sum(v[0] for _, v in split)
         for name, (ms, cnt) in split:
-            if name in ("k_plan_cem_update", "k_normal_noise") or ms >= 0.02 * total:
+            if name in ("k_plan_cem_update", "k_plan_update", "k_plan_warm", "k_normal_noise") or ms >= 0.02 * total:
                 print("   %-26s %8.3f ms (%3d launches, %7.1f us each) %5.1f %%" % (name, ms, cnt, 1e3 * ms / cnt,
                                                                                   100 * ms / total))
 
 
 if __name__ == "__main__":
-    main([int(a) for a in sys.argv[1:]] or [1, 64])
+    ap = argparse.ArgumentParser(description="time the cross-entropy / MPPI planner per planning step")
+    ap.add_argument("sizes", nargs="*", type=int, default=[1, 64], metavar="B")
+    ap.add_argument("--weighting", choices=E.WEIGHTINGS, default="elites")
+    ap.add_argument("--temperature", type=float, default=None, help="required with --weighting mppi")
+    ap.add_argument("--warm-start", action="store_true")
+    ns = ap.parse_args()
+    main(ns.sizes or [1, 64], ns.weighting, ns.temperature, ns.warm_start)
