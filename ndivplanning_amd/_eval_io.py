@@ -32,11 +32,20 @@ def _require_eval(**modules):
             raise _capi.NdpError("the %s is in training mode: call .eval() first (these are the eval-mode kernels)" % name)
 
 
+def denorm(tensor):
+    """[-1, 1] -> [0, 255]: the reference's helper, which its training and evaluation scripts each define."""
+    return ((tensor + 1.0) / 2.0) * 255.0
+
+
+def norm(image):
+    return (image / 255.0 - 0.5) * 2.0
+
+
 def _to_bytes(frames):
     """Input frames as displayable bytes HWC: byte frames as they are, floats denormalised as the reference does."""
     if frames.dtype == torch.uint8:
         return frames
-    return (((frames + 1.0) / 2.0) * 255.0).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+    return denorm(frames).clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
 
 
 def fp64_mean(values, dim=None):

@@ -20,31 +20,24 @@ import ctypes
 import torch
 
 from . import _capi
-from .forward_trainer import FlatTrainer
+from .flat_trainer import FlatTrainer
 from .models import image_autoencoder as IA
 
 
 class AutoencoderTrainer(FlatTrainer):
-    _WORKSPACE_FN, _APPLY_FN = "ndp_ae_workspace_floats", "ndp_ae_apply_adam"
+    _WORKSPACE_FN, _APPLY_FN, _PACK_FN = "ndp_ae_workspace_floats", "ndp_ae_apply_adam", "ndp_ae_pack_params"
     _grad_buckets = staticmethod(_capi.ae_grad_buckets)
 
     def __init__(self, encoder: IA.Encoder, decoder: IA.Decoder, batch: int, lr: float = 2e-4, betas=(0.5, 0.999),
                  eps: float = 1e-8, keep_reconstruction: bool = False, reduce_fn=None, bucket_reduce=None,
                  sync_batchnorm_world: int = 1, stat_group=None):
-        self.lib = _capi.load()
         self.encoder, self.decoder = encoder, decoder
-        dev = next(encoder.parameters()).device
-        if dev.type != "cuda" or next(decoder.parameters()).device != dev:
-            raise _capi.NdpError("AutoencoderTrainer needs both modules on one ROCm GPU (got %s, %s); there is no CPU path"
-                                 % (dev, next(decoder.parameters()).device))
-        self.device, self.batch = dev, int(batch)
+        self._place([encoder, decoder], "both modules on one", batch, reduce_fn, bucket_reduce)
+        dev = self.device
         if self.batch < 1 or self.lib.ndp_ae_workspace_floats(self.batch) <= 0:
             raise _capi.NdpError("AutoencoderTrainer: unsupported batch of %d images" % self.batch)
-        if reduce_fn is not None and bucket_reduce is not None:
-            raise ValueError("give either reduce_fn (one collective) or bucket_reduce (per-bucket, overlapped)")
         if int(sync_batchnorm_world) < 1:
             raise ValueError("sync_batchnorm_world must be >= 1, got %r" % (sync_batchnorm_world,))
-        self.reduce_fn, self.bucket_reduce = reduce_fn, bucket_reduce
         self.sync_world = int(sync_batchnorm_world)
         self._allocate(IA.pack_autoencoder(encoder, decoder, dev), lr, betas, eps)
         self.recon = torch.zeros(self.batch, 3, 128, 128, dtype=torch.float32, device=dev) if keep_reconstruction else None
@@ -58,21 +51,12 @@ class AutoencoderTrainer(FlatTrainer):
             self._stat_cb = _capi.STAT_SYNC_FN(self.stat_sync)
         self._pack()
 
-    def _pack(self):
-        with torch.cuda.device(self.device):
-            _capi.check(self.lib.ndp_ae_pack_params(_capi.ptr(self.params), _capi.ptr(self.workspace),
-                                                    _capi.stream_ptr(self.device)), "ndp_ae_pack_params")
-
     def grads(self, images):
         """forward + loss + backward on images [n,3,128,128] (n <= batch): fills .grad, .loss (device scalar, the
         reference's `recon_loss`), adds it to .loss_sum, moves the running statistics."""
         n = int(images.shape[0]) if images.dim() == 4 else 0
-        if not 1 <= n <= self.batch:
-            raise _capi.NdpError("batch of %d images with a trainer built for at most %d" % (n, self.batch))
-        if (images.device != self.device or images.dtype != torch.float32 or tuple(images.shape) != (n, 3, 128, 128)
-                or not images.is_contiguous()):
-            raise _capi.NdpError("images: expected a contiguous float32 [%d, 3, 128, 128] tensor on %s, got %s %s on %s"
-                                 % (n, self.device, images.dtype, list(images.shape), images.device))
+        self._check_batch(n)
+        self._check(images, (n, 3, 128, 128), "images")
         p = _capi.ptr
         recon = p(self.recon) if self.recon is not None else None
         with torch.cuda.device(self.device):

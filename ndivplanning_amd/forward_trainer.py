@@ -19,61 +19,12 @@ own predictions over a window of H + 1 frames and trained on the mean of the H s
 import torch
 
 from . import _capi
+from .flat_trainer import FlatTrainer
 from .models import forward_encoder as FE
 
 
-class FlatTrainer:
-    """What the trainers of this family share: the flat vectors the kernels read and write, the Adam call, the
-    reduce-then-apply tail of a step and the named views.  A subclass names its entry points, packs its modules,
-    checks its inputs and calls its own `grads()`."""
-    _WORKSPACE_FN = _APPLY_FN = None                     # "ndp_fm_workspace_floats", "ndp_fm_apply_adam"
-    _grad_buckets = None                                 # _capi.fm_grad_buckets
-
-    def _allocate(self, packed, lr, betas, eps):
-        """Buffers of a trainer on self.device for at most self.batch images; packed: (params, running_stats)."""
-        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.params, self.stats = packed
-        self.grad = torch.zeros_like(self.params)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.params), torch.zeros_like(self.params)
-        self.step_word = torch.zeros(4, dtype=torch.int32, device=self.device)      # Adam state word (include/ndp.h)
-        self.loss = torch.zeros(1, **f32)
-        self.loss_sum = torch.zeros(1, **f32)
-        self.workspace = torch.empty(getattr(self.lib, self._WORKSPACE_FN)(self.batch), **f32)
-        self.steps = 0                                                               # Adam steps
-
-    def apply(self):
-        """optimizer.step()"""
-        p = _capi.ptr
-        with torch.cuda.device(self.device):
-            _capi.check(getattr(self.lib, self._APPLY_FN)(p(self.params), p(self.grad), p(self.exp_avg), p(self.exp_avg_sq),
-                                                          p(self.step_word), self.lr, self.betas[0], self.betas[1], self.eps,
-                                                          p(self.workspace), _capi.stream_ptr(self.device)), self._APPLY_FN)
-        self.steps += 1
-
-    def _reduce_and_apply(self):
-        """The rest of a step after grads(): the data-parallel reduction of the gradient (if any), then Adam."""
-        if self.bucket_reduce is not None:
-            self.bucket_reduce(self.grad, self.device)
-        elif self.reduce_fn is not None:
-            self.reduce_fn(self.grad)
-        self.apply()
-        return self.loss
-
-    def gradient_buckets(self):
-        """[(offset, count)] of the flat gradient, in the order the backward pass completes them."""
-        return self._grad_buckets()
-
-    def named_gradients(self):
-        """'encoder.conv1.weight' ... -> gradient in the modules' own tensor shapes (tests, inspection)."""
-        return self._unpack(self.grad)
-
-    def named_parameters(self):
-        return self._unpack(self.params)
-
-
 class ForwardModelTrainer(FlatTrainer):
-    _WORKSPACE_FN, _APPLY_FN = "ndp_fm_workspace_floats", "ndp_fm_apply_adam"
+    _WORKSPACE_FN, _APPLY_FN, _PACK_FN = "ndp_fm_workspace_floats", "ndp_fm_apply_adam", "ndp_fm_pack_params"
     _grad_buckets = staticmethod(_capi.fm_grad_buckets)
 
     def __init__(self, model: FE.ForwardAutoencoder, batch: int, lr: float = 2e-4, betas=(0.5, 0.999), eps: float = 1e-8,
@@ -86,25 +37,16 @@ class ForwardModelTrainer(FlatTrainer):
             # the bucket events are those of the most recent backward pass and the statistics hook is process-wide: both
             # assume one pass per iteration
             raise ValueError("rollout_steps > 1 works with reduce_fn only: not with bucket_reduce or cross-rank BatchNorm")
-        self.lib = _capi.load()
         self.model = model
-        dev = next(model.parameters()).device
-        if dev.type != "cuda":
-            raise _capi.NdpError("ForwardModelTrainer needs the model on a ROCm GPU (got %s); there is no CPU path" % dev)
-        self.device, self.batch = dev, int(batch)
-        if reduce_fn is not None and bucket_reduce is not None:
-            raise ValueError("give either reduce_fn (one collective) or bucket_reduce (per-bucket, overlapped)")
-        self.reduce_fn, self.bucket_reduce = reduce_fn, bucket_reduce
-        self._allocate(FE.pack_module(model, dev), lr, betas, eps)
-        self.resid = torch.zeros(self.batch, 3, 128, 128, dtype=torch.float32, device=dev) if keep_residual else None
+        self._place([model], "the model on a", batch, reduce_fn, bucket_reduce)
+        self._allocate(FE.pack_module(model, self.device), lr, betas, eps)
+        self.resid = torch.zeros(self.batch, 3, 128, 128, dtype=torch.float32, device=self.device) if keep_residual else None
         # BatchNorm statistics over all ranks' images (dp.CrossRankBatchNorm): W ranks x B / W images = one process x B
         self.stat_sync = None
         if int(sync_batchnorm_world) > 1:
             from . import dp
             self.stat_sync = dp.CrossRankBatchNorm(self.workspace, int(sync_batchnorm_world))
-        with torch.cuda.device(dev):
-            _capi.check(self.lib.ndp_fm_pack_params(_capi.ptr(self.params), _capi.ptr(self.workspace),
-                                                    _capi.stream_ptr(dev)), "ndp_fm_pack_params")
+        self._pack()
         self._workspaces = [self.workspace]                          # pass k of a rollout keeps its activations in [k]
         self._extra_stale = False                                    # the extra workspaces' second weight order is behind
         self.rollout_losses = None
@@ -129,28 +71,20 @@ class ForwardModelTrainer(FlatTrainer):
         """The second weight order lives in each workspace's head; ndp_fm_apply_adam rebuilds it in .workspace only.  The
         others are rebuilt here, by the next grads_rollout after the parameters changed: one-pair steps pay nothing."""
         self._extra_stale = False
-        with torch.cuda.device(self.device):
-            for ws in self._workspaces[1:]:
-                _capi.check(self.lib.ndp_fm_pack_params(_capi.ptr(self.params), _capi.ptr(ws), _capi.stream_ptr(self.device)),
-                            "ndp_fm_pack_params")
+        for ws in self._workspaces[1:]:
+            self._pack(ws)
 
     def apply(self):
         """optimizer.step()"""
         super().apply()
         self._extra_stale = True
 
-    def _check(self, t, shape, what, dtype=torch.float32):
-        if t.device != self.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
-            raise _capi.NdpError("%s: expected a contiguous %s %s tensor on %s, got %s %s on %s"
-                                 % (what, dtype, list(shape), self.device, t.dtype, list(t.shape), t.device))
-
     def grads(self, state_cur, state_fut, actions):
         """forward + loss + backward: fills .grad, .loss (device scalar, the reference's `loss`), adds it to .loss_sum.
         Frames: the reference's float tensors [n,3,128,128] in [-1,1], or decoded camera frames as bytes [n,128,128,3]
         (normalised by the kernels as they read them: utils/hdf5_load.py:9-11's formula, a quarter of the upload)."""
         n = int(state_cur.shape[0])
-        if not 1 <= n <= self.batch:
-            raise _capi.NdpError("batch of %d images with a trainer built for at most %d" % (n, self.batch))
+        self._check_batch(n)
         u8 = state_cur.dtype == torch.uint8
         shape = (n, 128, 128, 3) if u8 else (n, 3, 128, 128)
         self._check(state_cur, shape, "state_cur", state_cur.dtype if u8 else torch.float32)
@@ -181,8 +115,7 @@ class ForwardModelTrainer(FlatTrainer):
         if H == 1:
             return self.grads(frames[:, 0].contiguous(), frames[:, 1].contiguous(), actions[:, 0].contiguous())
         n = int(frames.shape[0])
-        if not 1 <= n <= self.batch:
-            raise _capi.NdpError("batch of %d trajectories with a trainer built for at most %d" % (n, self.batch))
+        self._check_batch(n, "trajectories")
         u8 = frames.dtype == torch.uint8
         shape = (n, H + 1, 128, 128, 3) if u8 else (n, H + 1, 3, 128, 128)
         inner = torch.empty(shape[1:], device="meta").stride()
@@ -253,9 +186,7 @@ class ForwardModelTrainer(FlatTrainer):
     def load_from_module(self):
         """Take parameters and running statistics from the module again (after they were changed from outside)."""
         self.params, self.stats = FE.pack_module(self.model, self.device)
-        with torch.cuda.device(self.device):
-            _capi.check(self.lib.ndp_fm_pack_params(_capi.ptr(self.params), _capi.ptr(self.workspace),
-                                                    _capi.stream_ptr(self.device)), "ndp_fm_pack_params")
+        self._pack()
         self._extra_stale = True
 
     def sync_to_module(self):

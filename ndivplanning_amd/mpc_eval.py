@@ -2,15 +2,8 @@
 Same `fetch_push_control_evaluation(image_encoder, fwd_model_autoencoder, generator, dataset, config)` ->
 (avg_action_error, avg_image_loss) and CLI; the loop runs on the gfx950 kernels (ndivplanning_amd/evaluation.py)."""
 from ._eval_dropin import fetch
+from ._eval_io import denorm, norm  # noqa: F401
 from .evaluation import script_main
-
-
-def denorm(tensor):
-    return ((tensor + 1.0) / 2.0) * 255.0
-
-
-def norm(image):
-    return (image / 255.0 - 0.5) * 2.0
 
 
 def fetch_push_control_evaluation(image_encoder, fwd_model_autoencoder, generator, dataset, config):

@@ -36,6 +36,7 @@ import torch
 from torch.utils import data
 
 from . import evaluation as E
+from ._eval_io import denorm, norm  # noqa: F401
 
 NUM_TRAJECTORIES_TO_SAVE = 10
 IMAGE_SHAPE = (128, 128)
@@ -43,14 +44,6 @@ _NO_GYM = ("MPC_gym_eval.main() needs the `gym` package with the FetchPush-v1 (M
            "neither ships nor requires: the environment is the caller's to supply.  With an environment of your own, "
            "call MPC_gym_eval.fetch_push_control_evaluation(args, image_encoder, fwd_model_autoencoder, generator, "
            "dataset, config, env) directly.")
-
-
-def denorm(tensor):
-    return ((tensor + 1.0) / 2.0) * 255.0
-
-
-def norm(image):
-    return (image / 255.0 - 0.5) * 2.0
 
 
 def render(env):

@@ -34,10 +34,10 @@ from argparse import ArgumentParser
 import numpy as np
 import torch
 import torch.distributed as dist
-from torch.utils import data
 
 from . import _capi, dp
-from . import jpeg as jpeg_frames
+from . import _train_io as T
+from ._train_io import denorm, norm  # noqa: F401
 from .autoencoder_trainer import AutoencoderTrainer
 from .models.image_autoencoder import Decoder, Encoder
 from .utils.trajectory_loader import open_dataset
@@ -46,14 +46,6 @@ LR_RATE = 2e-4
 NUM_EPOCHS = 50
 BATCH_SIZE = 16
 REPORT_FREQ = 10
-
-
-def denorm(tensor):
-    return ((tensor + 1.0) / 2.0) * 255.0
-
-
-def norm(image):
-    return (image / 255.0 - 0.5) * 2.0
 
 
 def make_dataset(path, seed=1, raw_jpeg=False):
@@ -83,17 +75,16 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
     rank, world, local_rank = dp.env_world()
     if batch_size % world != 0:                                        # (before any process group or GPU is touched)
         raise ValueError("batch_size=%d trajectories must be a multiple of the %d ranks" % (batch_size, world))
+    store_dir = None
     if device_store:
-        from .trajectory_store import DeviceTrajectoryStore, StoreLoader, require_bundle_dir
+        from .trajectory_store import require_bundle_dir
         store_dir = require_bundle_dir(data_path, "device_store")
     if val_data is not None and int(val_every) < 1:
         raise ValueError("val_every must be >= 1, got %r" % (val_every,))
     own_group = False
-    if world > 1:
-        device = torch.device("cuda", 0 if os.environ.get("NDP_BENCH_ONE_GPU") == "1" else local_rank)
-        torch.cuda.set_device(device)
-        own_group = not dist.is_initialized()
-        dp.init_process_group(device)
+    if world > 1:                                                      # (one process: the caller's `device`, not made current)
+        own_group = not dist.is_initialized()                          # a group this call creates is torn down at its end
+        device = T.open_device(world, local_rank, None)
     device = torch.device(device)
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -101,33 +92,20 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
     torch.manual_seed(1)
     np.random.seed(1)
     dataset = make_dataset(data_path, raw_jpeg=raw_jpeg)
-    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True, **jpeg_frames.loader_kwargs(dataset))
+    # JPEG frames are decoded on the device, then normalised by ndp_eval_frames_u8 (decode_images below)
+    loader, jpeg_decoder = T.open_batch_source(dataset, batch_size, device, store_dir, dataset.seq_length, rank, world)
     val_dataset = make_dataset(val_data, seed=2, raw_jpeg=raw_jpeg) if val_data is not None and rank == 0 else None
-    # JPEG frames are decoded on the device, then normalised by ndp_eval_frames_u8; failures raise one batch later
-    jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
-    if device_store:
-        # the directory's bundles stay in device memory and every batch is assembled there (trajectory_store.py): the same
-        # batches in the same order as the DataLoader's, this rank's rows only, decoded by the same decoder
-        loader = StoreLoader(DeviceTrajectoryStore(store_dir, device), batch_size, 0, dataset.seq_length, shuffle=True,
-                             rank=rank, world=world)
-        jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred")
     encoder, decoder = build_models(device)
     trainer, bucket_group = None, None
     try:
-        dp_kw = {}
         if world > 1:
-            for t in [*encoder.parameters(), *encoder.buffers(), *decoder.parameters(), *decoder.buffers()]:
-                dist.broadcast(t.data, src=0)                          # one set of initial weights: rank 0's
-            if grad_exchange == "single":
-                dp_kw["reduce_fn"] = dp.mean_all_reduce(world)
-            else:
+            T.broadcast_initial_weights([encoder, decoder])
+            if grad_exchange == "bucketed" and sync_batchnorm:
                 # with cross-rank statistics the buckets get a communicator of their own: on the statistics' one they
                 # would queue behind the 8 backward statistics syncs, i.e. behind nearly the whole backward pass
-                bucket_group = dist.new_group(list(range(world))) if sync_batchnorm else None
-                dp_kw["bucket_reduce"] = dp.BucketedMeanAllReduce(world, group=bucket_group,
-                                                                  bucket_ranges=_capi.ae_grad_buckets,
-                                                                  wait="ndp_ae_bucket_wait")
-            dp_kw["sync_batchnorm_world"] = world if sync_batchnorm else 1
+                bucket_group = dist.new_group(list(range(world)))
+        dp_kw = T.dp_trainer_kwargs(world, grad_exchange, sync_batchnorm, group=bucket_group,
+                                    bucket_ranges=_capi.ae_grad_buckets, wait="ndp_ae_bucket_wait")
         trainer = AutoencoderTrainer(encoder.train(), decoder.train(), batch=batch_size // world * 15, lr=lr, betas=betas,
                                      **dp_kw)                          # (15 frames)
         display = None
@@ -139,22 +117,17 @@ def train(data_path="128_128_data", batch_size=BATCH_SIZE, num_epochs=NUM_EPOCHS
                 log("visdom unavailable (%s): no plots" % e)
         losses, val_losses, val_quality_log = [], [], []
         step = 0
-        warned = False
+        skipped = []
+
+        def warn_ragged(rows):                                         # rank 0, the first time
+            if rank == 0 and not skipped:
+                warnings.warn("train_autoencoder: a final batch of %d trajectories does not split over %d ranks; skipped"
+                              % (rows, world))
+            skipped.append(rows)
+
         for epoch in range(num_epochs):
-            for i, inputs in enumerate(loader):
-                images, _, _, _ = inputs
-                if world > 1 and not device_store:                     # (a StoreLoader yields this rank's rows already)
-                    if images.shape[0] != batch_size:                  # ragged final batch: skipped on every rank
-                        if rank == 0 and not warned:
-                            warnings.warn("train_autoencoder: a final batch of %d trajectories does not split over %d "
-                                          "ranks; skipped" % (images.shape[0], world))
-                        warned = True
-                        continue
-                    lo, hi = dp.shard_bounds(batch_size, rank, world)
-                    images = images[lo:hi]
-                if jpeg_decoder is not None:
-                    images = jpeg_decoder.decode_images(images)
-                images = images.to(device)
+            for images, _, _, _ in T.rank_batches(loader, batch_size, rank, world, device_store, on_ragged=warn_ragged):
+                images = T.upload_frames(images, device, jpeg_decoder, "decode_images", non_blocking=False)
                 state_cur = images.view(-1, *(images.size()[2:])).contiguous()
                 recon_loss = trainer.step(state_cur)
                 step += 1

@@ -31,77 +31,46 @@ What differs from the reference, on purpose:
     average count windows.  One process only.
 The whole module is saved every `epochs_per_stage` epochs as the reference does (train_forward_model.py:151-163), after
 the trainer's flat vectors are written back into it."""
-import importlib
 import logging
 import os
-from argparse import ArgumentParser
 
 import numpy as np
 import torch
-from torch.utils import data
 
+from . import _train_io as T
 from . import dp
-from . import jpeg as jpeg_frames
+from ._train_io import cfg_get, cfg_require, denorm, norm  # noqa: F401
 from .forward_trainer import ForwardModelTrainer
 from .models.forward_encoder import Decoder, Encoder, ForwardAutoencoder
-from .train_gan import denorm, make_dataset, norm, push_arguments  # noqa: F401
-from .utils.argparse_util import override_dotmap
-from .utils.cli_arguments.common_arguments import add_common_arguments
-from .utils.file import make_paths_absolute
+from .train_gan import make_dataset, push_arguments
 from .utils.trajectory_loader import open_dataset
 
 
 def bind_reference_class_paths():
-    """Whole-module checkpoints must record `models.forward_encoder.ForwardAutoencoder` (/ Encoder / Decoder): the
-    path the reference's evaluation scripts unpickle (control_evaluation.py:177-180).  See train_gan.py."""
-    missing = []
-    try:
-        mod = importlib.import_module("models.forward_encoder")
-    except ImportError:
-        mod = None
-    for cls in (ForwardAutoencoder, Encoder, Decoder):
-        if mod is not None and getattr(mod, cls.__name__, None) is cls:
-            cls.__module__ = "models.forward_encoder"
-        else:
-            missing.append("models.forward_encoder.%s" % cls.__name__)
-    if missing:
-        logging.warning("checkpoints will record ndivplanning_amd.* class paths: %s do(es) not resolve to this "
-                        "implementation (is the repository root, with its models/ shims, on sys.path?)", ", ".join(missing))
-    return missing
-
-
-def _require(config, dotted):
-    """The value at `a.b.c`, or a KeyError that names the key: a missing key reads as an empty map (DotMap's behaviour,
-    which the reference relies on elsewhere), and float() / int() of that is a TypeError about the wrong thing."""
-    node = config
-    for part in dotted.split("."):
-        node = node.get(part, None) if isinstance(node, dict) else None
-        if node is None:
-            break
-    if node is None or (isinstance(node, dict) and not node):
-        raise KeyError("%s is missing from the config (the reference's config/default.yaml has it)" % dotted)
-    return node
+    """The whole-module checkpoints record `models.forward_encoder.ForwardAutoencoder` (/ Encoder / Decoder), the path
+    the reference's evaluation scripts unpickle (control_evaluation.py:177-180; _train_io.bind_reference_class_paths)."""
+    return T.bind_reference_class_paths({"models.forward_encoder": (ForwardAutoencoder, Encoder, Decoder)})
 
 
 def train(config):
     for key in ("num_epochs", "learning_rate", "batch_size", "epochs_per_stage"):
-        _require(config, "training.forward." + key)
+        cfg_require(config, "training.forward." + key)
     for key in ("random_seed", "train_data_path", "forward_save_path"):
-        _require(config, key)
+        cfg_require(config, key)
     f = config.training.forward
     random_seed = int(config.random_seed)
     lr_rate, num_epochs, batch_size = float(f.learning_rate), int(f.num_epochs), int(f.batch_size)
     epochs_per_stage = int(f.epochs_per_stage)
-    device_store = bool(_optional(f, "device_store", False))
-    if device_store:                                                 # (before any GPU or process group is touched)
-        from .trajectory_store import DeviceTrajectoryStore, StoreLoader, require_bundle_dir
+    store_dir = None
+    if bool(cfg_get(f, "device_store", False)):                      # (before any GPU or process group is touched)
+        from .trajectory_store import require_bundle_dir
         store_dir = require_bundle_dir(config.train_data_path, "training.forward.device_store")
     rank, world, local_rank = dp.env_world()
-    rollout_steps = _optional(f, "rollout_steps", 1)                  # (checked before any GPU or process group is touched)
+    rollout_steps = cfg_get(f, "rollout_steps", 1)                  # (checked before any GPU or process group is touched)
     if isinstance(rollout_steps, bool) or int(rollout_steps) != rollout_steps or int(rollout_steps) < 1:
         raise ValueError("training.forward.rollout_steps must be an integer >= 1, got %r" % (rollout_steps,))
     rollout_steps = int(rollout_steps)
-    trajectory_length = _optional(config, "trajectory_length", None)
+    trajectory_length = cfg_get(config, "trajectory_length", None)
     if trajectory_length is not None and int(trajectory_length) < rollout_steps + 1:
         raise ValueError("training.forward.rollout_steps=%d needs windows of %d frames, trajectory_length is %d"
                          % (rollout_steps, rollout_steps + 1, int(trajectory_length)))
@@ -112,12 +81,7 @@ def train(config):
     if not torch.cuda.is_available():
         from . import _capi
         raise _capi.NdpError("train_forward_model needs a ROCm GPU (gpu_id %r); there is no CPU path" % (config.gpu_id,))
-    gpu = local_rank if world > 1 else config.gpu_id
-    if world > 1 and os.environ.get("NDP_BENCH_ONE_GPU") == "1":      # rehearsal: all ranks on one card
-        gpu = 0
-    device = torch.device("cuda", gpu) if isinstance(gpu, int) else torch.device(gpu)
-    torch.cuda.set_device(device)
-    dp.init_process_group(device)
+    device = T.open_device(world, local_rank, config.gpu_id)
     if batch_size % world != 0:
         raise ValueError("training.forward.batch_size=%d must be a multiple of the %d ranks" % (batch_size, world))
     local_batch = batch_size // world
@@ -137,47 +101,28 @@ def train(config):
     if dataset.seq_length < rollout_steps + 1:                       # (a config without trajectory_length)
         raise ValueError("training.forward.rollout_steps=%d needs windows of %d frames, the trajectories have %d"
                          % (rollout_steps, rollout_steps + 1, dataset.seq_length))
-    loader = data.DataLoader(dataset, batch_size=batch_size, shuffle=True, **jpeg_frames.loader_kwargs(dataset))
-    # JPEG frames (`synthetic:<N>:jpeg`, `raw_jpeg: true`) are decoded on the device; failures raise one batch later
-    jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred") if jpeg_frames.is_jpeg(dataset) else None
-    if device_store:
-        # the directory's bundles stay in device memory and every batch is assembled there (trajectory_store.py): the same
-        # batches in the same order as the DataLoader's, this rank's rows only, decoded by the same decoder
-        loader = StoreLoader(DeviceTrajectoryStore(store_dir, device), batch_size, 0, int(config.trajectory_length),
-                             shuffle=True, rank=rank, world=world)
-        jpeg_decoder = jpeg_frames.JpegDecoder(device, check="deferred")
+    loader, jpeg_decoder = T.open_batch_source(dataset, batch_size, device, store_dir, trajectory_length, rank, world)
 
     model = ForwardAutoencoder().to(device)                          # train_forward_model.py:67-70
     model.decoder.weight_init(mean=0.0, std=0.02)
     model.encoder.weight_init(mean=0.0, std=0.02)
     model.train()
-    if world > 1:                                                    # one set of initial weights: rank 0's
-        import torch.distributed as dist
-        for t in list(model.parameters()) + list(model.buffers()):
-            dist.broadcast(t.data, src=0)
-    # data parallel: the mean of the ranks' gradients, either per gradient bucket on a communication stream while the
-    # backward pass is still running (default) or as ONE collective between backward and Adam
-    # (`training.forward.grad_exchange: single`); two ranks give bit-identical parameters either way
-    exchange = f.get("grad_exchange", None) if hasattr(f, "get") else None
-    exchange = "bucketed" if exchange is None or (isinstance(exchange, dict) and not exchange) else str(exchange)
+    if world > 1:
+        T.broadcast_initial_weights([model])
+    # data parallel (`batch_size` is the GLOBAL batch): `training.forward.grad_exchange` bucketed (default) or single,
+    # `training.forward.sync_batchnorm` (default on; off: 20 fewer small collectives per step), see dp_trainer_kwargs.
+    # The buckets share the statistics' process group.
+    exchange = str(cfg_get(f, "grad_exchange", "bucketed"))
     if exchange not in ("bucketed", "single"):
         raise ValueError("training.forward.grad_exchange must be 'bucketed' or 'single', got %r" % (exchange,))
-    # `batch_size` is the GLOBAL batch: BatchNorm normalises over all ranks' images (exact integer all-reduce of the
-    # statistics accumulators), so W ranks train the single-process step; `training.forward.sync_batchnorm: false` keeps
-    # the statistics per rank (torch DistributedDataParallel without SyncBatchNorm: 20 fewer small collectives per step)
-    sync_bn = f.get("sync_batchnorm", None) if hasattr(f, "get") else None
-    sync_bn = True if sync_bn is None or (isinstance(sync_bn, dict) and not sync_bn) else bool(sync_bn)
-    trainer = ForwardModelTrainer(model, batch=local_batch, lr=lr_rate, betas=(0.5, 0.999),
-                                  sync_batchnorm_world=world if (world > 1 and sync_bn) else 1,
-                                  reduce_fn=dp.mean_all_reduce(world) if world > 1 and exchange == "single" else None,
-                                  bucket_reduce=dp.BucketedMeanAllReduce(world) if world > 1 and exchange == "bucketed" else None,
-                                  rollout_steps=rollout_steps)
+    trainer = ForwardModelTrainer(model, batch=local_batch, lr=lr_rate, betas=(0.5, 0.999), rollout_steps=rollout_steps,
+                                  **T.dp_trainer_kwargs(world, exchange, bool(cfg_get(f, "sync_batchnorm", True))))
 
     # held-out trajectories (optional): rank 0 alone reads and evaluates them
-    val_path, val_every, val_horizon = _optional(f, "val_data_path", None), int(_optional(f, "val_every", 1)), int(_optional(f, "val_horizon", 1))
+    val_path, val_every, val_horizon = cfg_get(f, "val_data_path", None), int(cfg_get(f, "val_every", 1)), int(cfg_get(f, "val_horizon", 1))
     if val_path is not None and (val_every < 1 or val_horizon < 1):
         raise ValueError("training.forward.val_every and val_horizon must be >= 1, got %r and %r" % (val_every, val_horizon))
-    val_quality = bool(_optional(f, "val_quality", False))
+    val_quality = bool(cfg_get(f, "val_quality", False))
     val_dataset = make_val_dataset(config, val_path) if val_path is not None and rank == 0 else None
     val_history = []
 
@@ -186,17 +131,8 @@ def train(config):
     for epoch in range(num_epochs):
         trainer.loss_sum.zero_()
         pairs = 0
-        for images, _, actions, _ in loader:
-            if world > 1 and not device_store:                       # (a StoreLoader yields this rank's rows already)
-                if images.shape[0] != batch_size:                    # ragged final batch: does not split evenly
-                    continue
-                lo, hi = dp.shard_bounds(batch_size, rank, world)
-                images, actions = images[lo:hi], actions[lo:hi]
-            if jpeg_decoder is not None:
-                images = jpeg_decoder.decode_frames(images)
-            images = images.to(device, non_blocking=True)
-            if images.dtype != torch.uint8:                          # byte frames [B,T,128,128,3]: normalised by the kernels
-                images = images.float()
+        for images, _, actions, _ in T.rank_batches(loader, batch_size, rank, world, presharded=store_dir is not None):
+            images = T.upload_frames(images, device, jpeg_decoder)
             actions = actions.to(device, non_blocking=True).float()
             if rollout_steps > 1:
                 # windows of rollout_steps + 1 frames: the model is unrolled on its own predictions and trained through them
@@ -232,12 +168,6 @@ def train(config):
     train.last_trainer = trainer                                       # tests: the replica's flat vectors
     train.last_val = val_history                                       # [(epoch, {one_step_mse, horizon_mse, persistence_mse, counts})]
     return history
-
-
-def _optional(node, key, default):
-    """node[key] of a DotMap / dict node, `default` where the key is absent (a DotMap reads a missing key as an empty map)."""
-    value = node.get(key, None) if hasattr(node, "get") else None
-    return default if value is None or (isinstance(value, dict) and not value) else value
 
 
 def make_val_dataset(config, path):
@@ -281,12 +211,7 @@ def validate(trainer, val_dataset, horizon, batch_size, quality=False):
 
 
 def main(argv=None):
-    parser = ArgumentParser(description="Interact with your training script")
-    parser = add_common_arguments(parser)
-    args = parser.parse_args(argv)
-    config = override_dotmap(args, "config_file")
-    config = make_paths_absolute(os.getcwd(), config, log_not_exist=True)
-    return train(config)
+    return T.config_main(train, argv)
 
 
 if __name__ == "__main__":

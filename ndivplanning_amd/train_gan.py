@@ -37,10 +37,8 @@ back into training mode.  In a data-parallel run rank 0 evaluates alone and issu
 the in-kernel gradient exchange waits with a 10 s time-out (dp.py), so after a validation epoch all ranks meet at
 one barrier of the process group before any of them launches the next step.  Without the key nothing is added.
 """
-import importlib
 import logging
 import os
-from argparse import ArgumentParser
 
 # HSA reads this when the runtime initialises (the first torch.cuda call below): dmabuf IPC is the only
 # mode this platform's driver supports, and the peer-to-peer gradient exchange / RCCL need it
@@ -52,57 +50,26 @@ from torch.utils import data  # noqa: E402
 
 from . import dp  # noqa: E402
 from . import jpeg as jpeg_frames  # noqa: E402
+from ._train_io import cfg_get, config_main, denorm, norm, open_device, upload_frames  # noqa: E402,F401
+from ._train_io import bind_reference_class_paths as _bind  # noqa: E402
 from .models.gan import Decoder, Discriminator  # noqa: E402
 from .models.image_autoencoder import Encoder  # noqa: E402
 from .trainer import GanTrainer  # noqa: E402
-from .utils.argparse_util import override_dotmap  # noqa: E402
-from .utils.cli_arguments.common_arguments import add_common_arguments  # noqa: E402
-from .utils.file import make_paths_absolute  # noqa: E402
 from .utils.trajectory_loader import open_dataset  # noqa: E402
 
 
-def denorm(tensor):
-    return ((tensor + 1.0) / 2.0) * 255.0
-
-
-def norm(image):
-    return (image / 255.0 - 0.5) * 2.0
-
-
-def _get(cfg, key, default):
-    v = cfg.get(key, None) if hasattr(cfg, "get") else None
-    return default if v is None or (isinstance(v, dict) and not v) else v
-
-
 def bind_reference_class_paths():
-    """Whole-module checkpoints (train_gan.py:254-266) must record the classes as `models.gan.Decoder` /
-    `models.gan.Discriminator` (and the encoder as `models.image_autoencoder.Encoder`): those are the paths the
-    reference's evaluation scripts unpickle (control_evaluation.py:175-176).  The root-level shims with those
-    names rename the classes when imported; do that here, so that every way into train() -- the CLI entry, the
-    package, a test -- writes the same pickles.  Returns the names that could not be bound."""
-    missing = []
-    for name, classes in (("models.gan", (Decoder, Discriminator)), ("models.image_autoencoder", (Encoder,))):
-        try:
-            mod = importlib.import_module(name)
-        except ImportError:
-            mod = None
-        for cls in classes:
-            if mod is not None and getattr(mod, cls.__name__, None) is cls:
-                cls.__module__ = name
-            else:
-                missing.append("%s.%s" % (name, cls.__name__))
-    if missing:
-        logging.warning("checkpoints will record ndivplanning_amd.* class paths: %s do(es) not resolve to this "
-                        "implementation (is the repository root, with its models/ shims, on sys.path?)", ", ".join(missing))
-    return missing
+    """The whole-module checkpoints (train_gan.py:254-266) record `models.gan.Decoder` / `models.gan.Discriminator`, and
+    the encoder `models.image_autoencoder.Encoder` (_train_io.bind_reference_class_paths)."""
+    return _bind({"models.gan": (Decoder, Discriminator), "models.image_autoencoder": (Encoder,)})
 
 
 def push_arguments(config):
     """PushDataset's keyword arguments as the trainers' configuration states them.  Decoded frames stay bytes until the
     first convolution reads them (ndp_encoder_forward_u8 / ndp_fm_*_u8): `raw_uint8: false` restores the reference's
     host-side float tensors; `raw_jpeg: true` yields the stored JPEG streams, decoded on the device (ndivplanning_amd.jpeg)."""
-    return dict(seq_length=config.trajectory_length, raw_uint8=bool(_get(config, "raw_uint8", True)),
-                raw_jpeg=bool(_get(config, "raw_jpeg", False)))
+    return dict(seq_length=config.trajectory_length, raw_uint8=bool(cfg_get(config, "raw_uint8", True)),
+                raw_jpeg=bool(cfg_get(config, "raw_jpeg", False)))
 
 
 def make_dataset(config):
@@ -114,7 +81,7 @@ def load_encoder(config, device):
     """torch.load of the pretrained whole-module encoder pickle (train_gan.py:75-76).  A local,
     trusted file written by train_autoencoder.py: weights_only=False is required for module
     pickles.  Without a file (synthetic image runs) a seeded Encoder stands in."""
-    path = _get(config, "image_encoder_model_path", None)
+    path = cfg_get(config, "image_encoder_model_path", None)
     if path and os.path.isfile(path):
         enc = torch.load(path, map_location=device, weights_only=False)
     else:
@@ -183,16 +150,16 @@ def train(config):
     num_epochs, num_sample, noise_dim = int(g.num_epochs), int(g.num_sample), int(g.noise_dim)
     batch_size, dsteps, epochs_per_stage = int(g.batch_size), int(g.discrim_steps_per_gen), int(g.epochs_per_stage)
     lr_rate = float(g.learning_rate)
-    div_factor = g.get("pairwise_div_factor", None)
+    div_factor = cfg_get(g, "pairwise_div_factor", None)
     if div_factor is None or isinstance(div_factor, dict):
         raise KeyError("training.gan.pairwise_div_factor is missing from the config "
                        "(the reference fails at train_gan.py:199 for such a file)")
-    noise_source = _get(g, "noise_source", "device")
-    use_graph = bool(_get(g, "use_graph", True))
-    steps_per_launch = int(_get(g, "steps_per_launch", 16))
-    cache_codes = bool(_get(g, "cache_codes", True))
-    val_path, val_every = _get(g, "val_data_path", None), int(_get(g, "val_every", 1))
-    val_num_sample = int(_get(g, "val_num_sample", num_sample))
+    noise_source = cfg_get(g, "noise_source", "device")
+    use_graph = bool(cfg_get(g, "use_graph", True))
+    steps_per_launch = int(cfg_get(g, "steps_per_launch", 16))
+    cache_codes = bool(cfg_get(g, "cache_codes", True))
+    val_path, val_every = cfg_get(g, "val_data_path", None), int(cfg_get(g, "val_every", 1))
+    val_num_sample = int(cfg_get(g, "val_num_sample", num_sample))
     if val_path is not None and (val_every < 1 or not 1 <= val_num_sample <= 256):
         raise ValueError("training.gan.val_every must be >= 1 and val_num_sample in 1..256, got %r and %r"
                          % (val_every, val_num_sample))
@@ -200,10 +167,9 @@ def train(config):
     rank, world, local_rank = dp.env_world()
     if not torch.cuda.is_available():
         raise RuntimeError("train_gan needs a ROCm GPU: the HIP path has no CPU fallback")
-    gpu = local_rank if world > 1 else int(_get(config, "gpu_id", 0)) % max(torch.cuda.device_count(), 1)
-    device = torch.device("cuda", gpu)
-    torch.cuda.set_device(device)
-    dp.init_process_group(device)
+    # (gpu_id wraps round the cards present; NDP_BENCH_ONE_GPU is not read here: LOCAL_RANK alone places the ranks)
+    device = open_device(world, local_rank, int(cfg_get(config, "gpu_id", 0)) % max(torch.cuda.device_count(), 1),
+                         one_gpu_rehearsal=False)
     if batch_size % world != 0:
         raise ValueError("training.gan.batch_size=%d must be a multiple of the %d ranks" % (batch_size, world))
     local_batch = batch_size // world
@@ -213,7 +179,7 @@ def train(config):
     bind_reference_class_paths()
 
     display = None
-    if rank == 0 and _get(config, "log_port", None):
+    if rank == 0 and cfg_get(config, "log_port", None):
         try:                                  # train_gan.py:68; needs a live visdom server
             from visdom import Visdom        # noqa: F401
             from .vis_tools import visualizer
@@ -309,12 +275,7 @@ def train(config):
                 per_frame, actions = code_cache[mine], action_cache[mine]
             else:
                 frames, _states, actions, _goal = next(loader)
-                frames = frames[lo:hi]
-                if jpeg_decoder is not None:
-                    frames = jpeg_decoder.decode_frames(frames)
-                if frames.dtype != torch.uint8:                      # byte frames [B,T,128,128,3] are uploaded as they are
-                    frames = frames.float()
-                frames = frames.to(device, non_blocking=True)
+                frames = upload_frames(frames[lo:hi], device, jpeg_decoder)
                 actions = actions[lo:hi].float().to(device, non_blocking=True)
                 if frames.dim() == 5:
                     with torch.no_grad():
@@ -377,12 +338,7 @@ def train(config):
 
 
 def main(argv=None):
-    parser = ArgumentParser(description="Interact with your training script")
-    parser = add_common_arguments(parser)
-    args = parser.parse_args(argv)
-    config = override_dotmap(args, "config_file")
-    config = make_paths_absolute(os.getcwd(), config, log_not_exist=True)
-    return train(config)
+    return config_main(train, argv)
 
 
 if __name__ == "__main__":

@@ -152,8 +152,8 @@ def test_validation_keys_are_optional_and_checked():
     from ndivplanning_amd import train_forward_model as TF
     from ndivplanning_amd.utils.file import AttrDict as DotMap
     f = DotMap({"val_every": 2})
-    assert TF._optional(f, "val_data_path", None) is None and TF._optional(f, "val_every", 1) == 2
-    assert TF._optional(f, "val_horizon", 1) == 1
+    assert TF.cfg_get(f, "val_data_path", None) is None and TF.cfg_get(f, "val_every", 1) == 2
+    assert TF.cfg_get(f, "val_horizon", 1) == 1
     config = DotMap({"trajectory_length": 4, "random_seed": 3})
     ds = TF.make_val_dataset(config, "/somewhere/synthetic:5:frames_u8")
     assert len(ds) == 5 and ds.seq_length == 4 and ds.mode == "frames_u8" and ds.seed == 4     # apart from the training set's seed
