@@ -858,6 +858,65 @@ int ndp_plan_warm(const float *mean_prev, const float *std_prev, const float *no
                   int steps_prev, int steps, float warm_std, const float *low4, const float *high4, float *mean,
                   float *std, float *warm, void *stream);
 
+/* ------------------------------------------------ planner: gradient refinement ---
+ * The gradient stage of one planning step (evaluation.py: `grad=GradSettings(...)`): after the
+ * sampling rounds, the G best rows of the population are refined by J steps of gradient descent on the planner's own
+ * score -- the MSE of the forward model's open-loop Th-step prediction against the goal image -- and written over the G
+ * worst rows.  With R rows per trajectory, 1 <= G <= R / 2 (integer division), so the two sets are disjoint and the
+ * originals stay in the population: the last selection can only gain.  Per iteration: Th eval-mode ndp_fm_forward passes
+ * on the B * G rows, each on a workspace of its own, ndp_plan_goal_grad on the last predictions, ndp_fm_input_grads for
+ * ts = Th-1 .. 0 (d_state_cur of pass ts is d_out of pass ts - 1; NULL at ts = 0; d_actions goes to grad[ts]), and
+ * ndp_plan_grad_step.  Rows are independent: the seed is the gradient of the SUM of the rows' errors.
+ *
+ * ndp_plan_goal_grad: pred [n_rows,3,128,128], goal [n_goal,3,128,128]; row i is compared with goal row i /
+ * rows_per_goal; (n_rows - 1) / rows_per_goal < n_goal.  ONE launch, one workgroup per row.
+ *   err [n_rows]   the bits of ndp_eval_score_select's err on the same operands: with d = (double)pred - (double)goal
+ *                  (exact for operands of like magnitude), "thread" t of 256 folds the row's elements t, t + 256, ... in
+ *                  that order into s_t = fma(d, d, s_t) (ONE rounding per element, s_t = 0 at first); red = s; for w =
+ *                  128, 64, .. 1: red[t] += red[t + w] for t < w; err = (float)(red[0] / 49152.0)
+ *   d_pred [n_rows,3,128,128] = (pred - goal) * c with c = (float)(2.0 / 49152.0): one fp32 subtraction and one fp32
+ *                  multiplication, the gradient of the row's err.  A NaN stays NaN
+ * d_pred may be pred itself (in place) or disjoint from it; any other overlap, an output that overlaps goal, err inside
+ * an image buffer, a null pointer, a misaligned image buffer (16 bytes), n_rows < 1, rows_per_goal < 1: NDP_E_ARG.  Loads
+ * and stores are 16 bytes wide; no atomics, no scratch memory: two calls give the same bits.
+ *
+ * ndp_plan_grad_gather: err [B,R] and seq [Th,B,R,4] as in ndp_plan_cem_update, ranked by its order (NaN after every
+ * number, ties and NaNs by index).  ONE launch, one workgroup per trajectory.
+ *   src [B,G] int32   the rows of rank 0 .. G-1;   dst [B,G] int32   the rows of rank R-G .. R-1
+ *   seq_g [Th,B,G,4]  row g = row src[b][g] of seq, bit for bit;   m, v [Th,B,G,4] = 0
+ * 1 <= B <= 65535, 2 <= R <= NDP_MAX_SAMPLES, 1 <= G = rows <= R / 2, 1 <= Th <= 32; seq, seq_g, m, v 16-byte aligned and
+ * pairwise disjoint, src != dst.
+ *
+ * ndp_plan_grad_step: update number t >= 1 of the rows seq_g [Th,B,G,4] (in/out) along grad [Th,B,G,4].  ONE launch, one
+ * thread per row.  Every element in fp64 from the fp32 inputs (lr, beta1, beta2, eps are the fp32 arguments widened),
+ * every product, sum, quotient and root rounded on its own (no contraction):
+ *   NDP_PLAN_SGD   a' = a - lr * g
+ *   NDP_PLAN_ADAM  m' = beta1 * m + (1 - beta1) * g;  v' = beta2 * v + (1 - beta2) * (g * g);
+ *                  a' = a - (lr * (m' / c1)) / (sqrt(v' / c2) + eps),  c_i = 1 - p_i, p_i = beta_i multiplied t times onto
+ *                  1.0 in fp64 (t roundings, no pow); m' and v' enter a' unrounded
+ * a', m' and v' are rounded to fp32 once; a' is then clamped to [low, high] of its component (fmaxf / fminf, a NaN stays
+ * NaN).  m, v [Th,B,G,4] in/out, read and written only by NDP_PLAN_ADAM (NULL allowed with NDP_PLAN_SGD).  A row with a
+ * gradient component among its Th * 4 that is not finite is not moved, and its m and v stay.
+ *   curve_out [B,G] or NULL   receives a copy of err_g [B,G] (required with curve_out): the rows' errors before the update
+ *   dst [B,G] int32 and seq_full [Th,B,R,4], both or neither: row (b, g) of the result -- moved or not -- is also written
+ *                  to row dst[b][g] of seq_full (an index outside 0..R-1: not written); every other row keeps its bits
+ * 1 <= B <= 65535, 1 <= G = rows <= NDP_MAX_SAMPLES / 2, with seq_full 2 G <= R = rollouts <= NDP_MAX_SAMPLES, 1 <= Th <=
+ * 32, 1 <= t <= 65535, lr finite and > 0, 0 <= beta < 1, eps finite and >= 0, low <= high per component; grad, seq_g, m, v,
+ * seq_full 16-byte aligned and pairwise disjoint.
+ * For all three: a limit exceeded, a null required pointer, a misaligned buffer, overlapping outputs: NDP_E_ARG, nothing
+ * launched.  No atomics, no scratch memory, no host synchronisation: two calls give the same bits.  The caller owns
+ * every buffer. */
+#define NDP_PLAN_SGD  0
+#define NDP_PLAN_ADAM 1
+int ndp_plan_goal_grad(const float *pred, int64_t n_rows, const float *goal, int64_t n_goal, int rows_per_goal,
+                       float *err, float *d_pred, void *stream);
+int ndp_plan_grad_gather(const float *err, const float *seq, int64_t n_traj, int rollouts, int steps, int rows,
+                         int32_t *src, int32_t *dst, float *seq_g, float *m, float *v, void *stream);
+int ndp_plan_grad_step(const float *grad, float *seq_g, float *m, float *v, const float *err_g, int64_t n_traj, int rows,
+                       int steps, int t, int optimizer, float lr, float beta1, float beta2, float eps,
+                       const float *low4, const float *high4, float *curve_out, const int32_t *dst, float *seq_full,
+                       int rollouts, void *stream);
+
 /* --------------------------------------------------------------- push world ---
  * A small FetchPush-like world of the project's own (push_world.py): a gripper, a block and a goal
  * on a table, the reference's 4-component actions, n environments at once.  The world is in metres.

@@ -186,6 +186,12 @@ SIGNATURES = {
                                 c_void_p, c_void_p]),
     "ndp_plan_warm": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_float, POINTER(c_float),
                               POINTER(c_float), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ndp_plan_goal_grad": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+    "ndp_plan_grad_gather": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
+    "ndp_plan_grad_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int,
+                                   c_float, c_float, c_float, c_float, POINTER(c_float), POINTER(c_float), c_void_p, c_void_p,
+                                   c_void_p, c_int, c_void_p]),
     "ndp_normal_noise": (c_int, [c_void_p, c_int64, c_uint64, c_void_p, c_void_p]),
     "ndp_world_step_render": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
     "ndp_world_render": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_void_p]),

@@ -29,6 +29,8 @@ def fetch(kind, image_encoder, fwd_model_autoencoder, generator, dataset, config
     shapes = E.noise_piece_shapes(kind, bs, dataset.seq_length, k, nz, r, th)
     # the optional `mpc.cem` mapping turns the cross-entropy planner on (evaluation.CemSettings; absent: off)
     cem = E.cem_from_config(config) if kind == "mpc" else None
+    # the optional `mpc.grad` mapping turns the gradient stage on (evaluation.GradSettings; absent: off)
+    grad = E.grad_from_config(config) if kind == "mpc" else None
     action_error_sum = torch.zeros(1, dtype=torch.float32, device=models.device)
     image_error_sum = None
     for i, inputs in enumerate(loader):
@@ -45,7 +47,7 @@ def fetch(kind, image_encoder, fwd_model_autoencoder, generator, dataset, config
             res = E.closed_loop(models, images, actions, k, noise, action_error_acc=action_error_sum, on_step=print)
         else:
             # seed: with `cem`, the device's normal draws, one stream per trajectory (unread without it: the noise is given)
-            res = E.mpc_plan(models, images, actions, r, th, noise=noise, on_step=print, cem=cem, seed=seed + i)
+            res = E.mpc_plan(models, images, actions, r, th, noise=noise, on_step=print, cem=cem, seed=seed + i, grad=grad)
             models.mse(actions[:, :t1].contiguous(), res["actions"], 1, t1 * 4, acc=action_error_sum)
         image_error_sum = res["image_error_sum"][0]
         if kind != "open":

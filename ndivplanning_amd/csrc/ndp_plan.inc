@@ -17,6 +17,11 @@
 //      the normals and one 16-byte store; row 0 is the rank-0 sequence, copied.
 // With MPPI weighting a phase 2b follows the ranking: thread k < E' leaves w_k in LDS once (256 doubles), and after one
 // more barrier phase 3 sums with them in rank order; no component thread computes an exponential.
+// The gradient stage of the planner (evaluation.py: `grad`, DESIGN.md section 5r) adds three launches:
+//   k_plan_goal_grad   err and d err / d pred of every refined row against its goal image, one workgroup per row
+//   k_plan_grad_gather the G best rows of a scored population gathered into seq_g [Th][B][G][4], their sources and the G
+//                      worst rows' indices (the destinations), zeroed Adam moments
+//   k_plan_grad_step   one SGD or Adam update of seq_g from the backward chain's action gradients, one thread per row
 // Every sum has a fixed order, nothing is atomic, nothing spills: two calls give the same bits.  The arithmetic is in
 // ndp::plan, __host__ __device__: tests/host_drivers/plan_cem.inc (a body of main.hip) and plan_warm.inc (the body of
 // plan_warm_main.hip) run exactly these functions by this schedule on the CPU.  Included at the end of ndp_kernels.hip,
@@ -145,6 +150,146 @@ __host__ __device__ inline float best_of(float old, float e, int first) {
   return (e < old || old != old) ? e : old;
 }
 
+// ---- the gradient stage -------------------------------------------------------------------------------------------
+constexpr int kImageValues = 3 * 128 * 128;               // one image row of ndp_plan_goal_grad
+constexpr int kGoalChunk = 2048;                          // floats of a row between two barriers of k_plan_goal_grad
+constexpr int kGoalSlots = kGoalChunk / kBlock;           // elements of a chunk that one thread's sum owns
+
+// One element of ndp_plan_goal_grad: *d = (p - g) * c in fp32, two roundings; returns the fp64 difference whose square
+// the row's error sums.  A NaN stays NaN.
+__host__ __device__ inline double goal_elem(float p, float g, float c, float* d) {
+#pragma clang fp contract(off)
+  const float diff = p - g;
+  *d = diff * c;
+  return (double)p - (double)g;
+}
+
+// s + d * d with ONE rounding: what k_eval_pair_mse's `s += d * d` compiles to on the device, spelled out so that the
+// host and the device agree
+__host__ __device__ inline double sq_acc(double s, double d) { return fma(d, d, s); }
+
+// k_eval_pair_mse's tree over the 256 threads' sums, then the mean rounded to fp32
+__host__ __device__ inline void tree_step(double* red, int t, int w) { red[t] += red[t + w]; }
+__host__ __device__ inline float goal_mean(double sum) { return (float)(sum / (double)kImageValues); }
+
+// Which row workgroup k of k_plan_goal_grad takes.  Workgroups k and k + 8 share an XCD and its L2 (observed, for speed
+// only), so the rows_per_goal rows of one goal go to workgroups 8 apart: the first of them brings the goal row into that
+// L2 and the others read it there.  Goal j is served on residue j % 8; a k past the last row gives a row >= n_rows.
+constexpr int kXcds = 8;
+__host__ __device__ inline int64_t goal_group(int64_t n_rows, int rows_per_goal) {
+  return rows_per_goal < n_rows ? rows_per_goal : n_rows;            // one goal for every row: one group
+}
+__host__ __device__ inline int64_t goal_row(int64_t k, int64_t n_rows, int rows_per_goal) {
+  const int64_t group = goal_group(n_rows, rows_per_goal), lane = k % kXcds, slot = k / kXcds;
+  return (lane + kXcds * (slot / group)) * group + slot % group;
+}
+// the workgroups that cover n_rows rows: fewer than n_rows + 8 * group
+__host__ __device__ inline int64_t goal_grid(int64_t n_rows, int rows_per_goal) {
+  const int64_t group = goal_group(n_rows, rows_per_goal), goals = (n_rows + group - 1) / group;
+  return (goals + kXcds - 1) / kXcds * kXcds * group;
+}
+
+// beta^t by t roundings: the same double on the host, the device and in a restatement (pow need not be)
+__host__ __device__ inline double pow_steps(double beta, int t) {
+#pragma clang fp contract(off)
+  double p = 1.0;
+  for (int i = 0; i < t; ++i) p = p * beta;
+  return p;
+}
+
+}  // namespace plan
+
+struct PlanGatherArgs {
+  const float* err; const float* seq;
+  int64_t n_traj; int rollouts, steps, rows;
+  int32_t* src; int32_t* dst; float* seq_g; float* m; float* v;
+};
+
+struct PlanStepArgs {
+  const float* grad; float* seq_g; float* m; float* v; const float* err_g;
+  int64_t n_traj; int rows, steps, adam;
+  double lr, beta1, beta2, eps, corr1, corr2;             // corr = 1 - beta^t
+  float low[4], high[4];
+  float* curve_out; const int32_t* dst; float* seq_full; int rollouts;
+};
+
+namespace plan {
+
+// Pair i = ts * G + g of trajectory b in k_plan_grad_gather: the rank-g row of the population into seq_g, zero moments
+__host__ __device__ inline void gather_pair(const PlanGatherArgs& a, int64_t b, int i, const int* order) {
+  const int ts = i / a.rows, g = i % a.rows;
+  const int64_t to = seq_index(ts, b, g, 0, a.n_traj, a.rows);
+  const float4 x = *reinterpret_cast<const float4*>(a.seq + seq_index(ts, b, order[g], 0, a.n_traj, a.rollouts));
+  *reinterpret_cast<float4*>(a.seq_g + to) = x;
+  const float4 zero = {0.f, 0.f, 0.f, 0.f};
+  *reinterpret_cast<float4*>(a.m + to) = zero;
+  *reinterpret_cast<float4*>(a.v + to) = zero;
+}
+
+__host__ __device__ inline bool finite_f(float x) { return x - x == 0.f; }
+
+// one component of ndp_plan_grad_step, fp64 with every operation rounded on its own; *m and *v in/out (Adam only)
+__host__ __device__ inline float step_component(const PlanStepArgs& a, float act, float grad, float* m, float* v, int c) {
+#pragma clang fp contract(off)
+  const double g = (double)grad;
+  double next;
+  if (a.adam) {
+    const double keep1 = 1.0 - a.beta1, keep2 = 1.0 - a.beta2;
+    const double gg = g * g;
+    const double mn = a.beta1 * (double)*m + keep1 * g;
+    const double vn = a.beta2 * (double)*v + keep2 * gg;
+    const double mhat = mn / a.corr1, vhat = vn / a.corr2;
+    const double denom = sqrt(vhat) + a.eps;
+    const double move = (a.lr * mhat) / denom;
+    next = (double)act - move;
+    *m = (float)mn;
+    *v = (float)vn;
+  } else {
+    const double move = a.lr * g;
+    next = (double)act - move;
+  }
+  return clamp_keep_nan((float)next, a.low[c], a.high[c]);
+}
+
+// Row i = b * G + g of ndp_plan_grad_step: the row moves unless one of its Th * 4 gradient components is not finite
+__host__ __device__ inline void step_row(const PlanStepArgs& a, int64_t i) {
+  const int64_t b = i / a.rows;
+  const int g = (int)(i % a.rows);
+  bool ok = true;
+  for (int ts = 0; ts < a.steps; ++ts) {
+    const float4 d = *reinterpret_cast<const float4*>(a.grad + seq_index(ts, b, g, 0, a.n_traj, a.rows));
+    ok = ok && finite_f(d.x) && finite_f(d.y) && finite_f(d.z) && finite_f(d.w);
+  }
+  if (a.curve_out != nullptr) a.curve_out[i] = a.err_g[i];
+  int to = -1;
+  if (a.dst != nullptr) {
+    to = a.dst[i];
+    if (to < 0 || to >= a.rollouts) to = -1;               // nothing is written through an index outside the population
+  }
+  for (int ts = 0; ts < a.steps; ++ts) {
+    const int64_t at = seq_index(ts, b, g, 0, a.n_traj, a.rows);
+    float4 x = *reinterpret_cast<const float4*>(a.seq_g + at);
+    if (ok) {
+      const float4 d = *reinterpret_cast<const float4*>(a.grad + at);
+      float4 m = {0.f, 0.f, 0.f, 0.f}, v = m;
+      if (a.adam) {
+        m = *reinterpret_cast<const float4*>(a.m + at);
+        v = *reinterpret_cast<const float4*>(a.v + at);
+      }
+      x.x = step_component(a, x.x, d.x, &m.x, &v.x, 0);
+      x.y = step_component(a, x.y, d.y, &m.y, &v.y, 1);
+      x.z = step_component(a, x.z, d.z, &m.z, &v.z, 2);
+      x.w = step_component(a, x.w, d.w, &m.w, &v.w, 3);
+      *reinterpret_cast<float4*>(a.seq_g + at) = x;
+      if (a.adam) {
+        *reinterpret_cast<float4*>(a.m + at) = m;
+        *reinterpret_cast<float4*>(a.v + at) = v;
+      }
+    }
+    if (to >= 0) *reinterpret_cast<float4*>(a.seq_full + seq_index(ts, b, to, 0, a.n_traj, a.rollouts)) = x;
+  }
+}
+
 }  // namespace plan
 
 struct PlanCemArgs {
@@ -267,6 +412,81 @@ __global__ __launch_bounds__(plan::kBlock) void k_plan_warm(PlanWarmArgs a) {
   if (i < (int64_t)a.steps * a.n_traj * a.rows) plan::warm_row(a, i);
 }
 
+// One workgroup of 256 threads per row; a row is 24 chunks of 2048 floats.  Per chunk thread t loads pred and goal 16
+// bytes at a time at floats 4t and 1024 + 4t, stores d_pred there, and leaves the 8 fp64 differences in LDS; after the
+// barrier thread t adds the squares of the chunk's elements t, t + 256, ..., t + 1792 to its sum in that order -- so it
+// sums the row's elements t, t + 256, ... as k_eval_pair_mse's thread t does, with the same fused multiply-add -- and the
+// tree and the mean are that kernel's.  Two LDS buffers: one barrier per chunk.  Which workgroup takes which row
+// (goal_row) keeps the rows of one goal on one XCD; the result does not depend on it.
+__global__ __launch_bounds__(plan::kBlock) void k_plan_goal_grad(const float* pred, const float* goal, int64_t n_rows,
+                                                                int rows_per_goal, float c, float* err, float* d_pred) {
+  using namespace plan;
+  __shared__ double diff_s[2][kGoalChunk];
+  const int t = threadIdx.x;
+  const int64_t row = goal_row(blockIdx.x, n_rows, rows_per_goal);
+  if (row >= n_rows) return;                                // the whole workgroup: no barrier is left waiting
+  const float* x = pred + row * kImageValues;
+  const float* y = goal + (row / rows_per_goal) * kImageValues;
+  float* o = d_pred + row * kImageValues;
+  double s = 0.0;
+  for (int chunk = 0; chunk < kImageValues / kGoalChunk; ++chunk) {
+    double* buf = diff_s[chunk & 1];
+    float4 p[2], g[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int at = chunk * kGoalChunk + h * (kGoalChunk / 2) + 4 * t;
+      p[h] = *reinterpret_cast<const float4*>(x + at);
+      g[h] = *reinterpret_cast<const float4*>(y + at);
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int in = h * (kGoalChunk / 2) + 4 * t;
+      float4 d;
+      buf[in + 0] = goal_elem(p[h].x, g[h].x, c, &d.x);
+      buf[in + 1] = goal_elem(p[h].y, g[h].y, c, &d.y);
+      buf[in + 2] = goal_elem(p[h].z, g[h].z, c, &d.z);
+      buf[in + 3] = goal_elem(p[h].w, g[h].w, c, &d.w);
+      *reinterpret_cast<float4*>(o + chunk * kGoalChunk + in) = d;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kGoalSlots; ++k) s = sq_acc(s, buf[t + k * kBlock]);
+  }
+  double* red = diff_s[0];                                  // the last chunk (23) used buffer 1
+  red[t] = s;
+  __syncthreads();
+  for (int w = kBlock / 2; w > 0; w >>= 1) {
+    if (t < w) tree_step(red, t, w);
+    __syncthreads();
+  }
+  if (t == 0) err[row] = goal_mean(red[0]);
+}
+
+// One workgroup per trajectory: k_plan_update's phases 1 and 2 (errors staged, order[rank] = row), then threads < G write
+// src and dst and the (ts, g) pairs are walked 256 at a time.
+__global__ __launch_bounds__(plan::kBlock) void k_plan_grad_gather(PlanGatherArgs a) {
+  using namespace plan;
+  __shared__ float err_s[NDP_MAX_SAMPLES];
+  __shared__ int order_s[NDP_MAX_SAMPLES];
+  const int t = threadIdx.x, R = a.rollouts, G = a.rows;
+  const int64_t b = blockIdx.x;
+  if (t < R) err_s[t] = a.err[b * R + t];
+  __syncthreads();
+  if (t < R) order_s[rank_of(err_s, R, t)] = t;
+  __syncthreads();
+  if (t < G) {
+    a.src[b * G + t] = order_s[t];
+    a.dst[b * G + t] = order_s[R - G + t];
+  }
+  for (int i = t; i < a.steps * G; i += kBlock) gather_pair(a, b, i, order_s);
+}
+
+// one thread per row (b, g)
+__global__ __launch_bounds__(plan::kBlock) void k_plan_grad_step(PlanStepArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * plan::kBlock + threadIdx.x;
+  if (i < a.n_traj * a.rows) plan::step_row(a, i);
+}
+
 // Box-Muller on one Philox block: thread j owns uniforms 4j .. 4j+3 of the stream (seed, offset), the pairs 2j and
 // 2j + 1, and writes out[4j .. 4j+3] (what lies below n of it).
 __global__ __launch_bounds__(kThreads) void k_normal_noise(float* out, int64_t n, uint64_t seed, const int32_t* offset_dev,
@@ -384,6 +604,112 @@ int ndp_plan_warm(const float* mean_prev, const float* std_prev, const float* no
   KTimer kt("k_plan_warm", st);
   hipLaunchKernelGGL(k_plan_warm, dim3((unsigned)((n + plan::kBlock - 1) / plan::kBlock)), dim3(plan::kBlock), 0, st, a);
   return check_launch("k_plan_warm");
+}
+
+// do the n floats at a and the m floats at b share a byte?
+static bool plan_overlap(const float* a, int64_t n, const float* b, int64_t m) { return a < b + m && b < a + n; }
+
+int ndp_plan_goal_grad(const float* pred, int64_t n_rows, const float* goal, int64_t n_goal, int rows_per_goal, float* err,
+                       float* d_pred, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(pred && goal && err && d_pred, "ndp_plan_goal_grad: null pointer");
+  NDP_CHECK_ARG(n_rows >= 1 && n_rows <= kEvalMaxPairs && n_goal >= 1 && rows_per_goal >= 1,
+                "ndp_plan_goal_grad: bad sizes (n_rows %lld, n_goal %lld, rows_per_goal %d)", (long long)n_rows,
+                (long long)n_goal, rows_per_goal);
+  NDP_CHECK_ARG((n_rows - 1) / rows_per_goal < n_goal, "ndp_plan_goal_grad: %lld rows of %d per goal read past the %lld goals",
+                (long long)n_rows, rows_per_goal, (long long)n_goal);
+  NDP_CHECK_ARG(aligned16(pred) && aligned16(goal) && aligned16(d_pred),
+                "ndp_plan_goal_grad: pred, goal and d_pred must be 16-byte aligned");
+  const int64_t all = n_rows * plan::kImageValues;
+  NDP_CHECK_ARG(d_pred == pred || !plan_overlap(d_pred, all, pred, all),
+                "ndp_plan_goal_grad: d_pred must be pred itself or disjoint from it");
+  NDP_CHECK_ARG(!plan_overlap(d_pred, all, goal, n_goal * plan::kImageValues) && !plan_overlap(err, n_rows, d_pred, all) &&
+                    !plan_overlap(err, n_rows, pred, all) && !plan_overlap(err, n_rows, goal, n_goal * plan::kImageValues),
+                "ndp_plan_goal_grad: an output overlaps goal, or err overlaps an image buffer");
+  hipStream_t st = (hipStream_t)stream;
+  KTimer kt("k_plan_goal_grad", st);
+  // fewer than 9 n_rows workgroups: under 2^31 with the limit above
+  hipLaunchKernelGGL(k_plan_goal_grad, dim3((unsigned)plan::goal_grid(n_rows, rows_per_goal)), dim3(plan::kBlock), 0, st, pred,
+                     goal, n_rows, rows_per_goal, (float)(2.0 / (double)plan::kImageValues), err, d_pred);
+  return check_launch("k_plan_goal_grad");
+}
+
+int ndp_plan_grad_gather(const float* err, const float* seq, int64_t n_traj, int rollouts, int steps, int rows, int32_t* src,
+                         int32_t* dst, float* seq_g, float* m, float* v, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(err && seq && src && dst && seq_g && m && v, "ndp_plan_grad_gather: null pointer");
+  NDP_CHECK_ARG(n_traj >= 1 && n_traj <= 65535, "ndp_plan_grad_gather: n_traj=%lld outside 1..65535", (long long)n_traj);
+  NDP_CHECK_ARG(rollouts >= 2 && rollouts <= NDP_MAX_SAMPLES, "ndp_plan_grad_gather: rollouts=%d outside 2..%d", rollouts,
+                NDP_MAX_SAMPLES);
+  NDP_CHECK_ARG(rows >= 1 && rows <= rollouts / 2, "ndp_plan_grad_gather: rows=%d outside 1..rollouts/2=%d", rows,
+                rollouts / 2);
+  NDP_CHECK_ARG(steps >= 1 && steps <= plan::kMaxSteps, "ndp_plan_grad_gather: steps=%d outside 1..%d", steps,
+                plan::kMaxSteps);
+  NDP_CHECK_ARG(aligned16(seq) && aligned16(seq_g) && aligned16(m) && aligned16(v),
+                "ndp_plan_grad_gather: seq, seq_g, m and v must be 16-byte aligned");
+  const int64_t small = (int64_t)steps * n_traj * rows * 4, full = (int64_t)steps * n_traj * rollouts * 4;
+  NDP_CHECK_ARG(!plan_overlap(seq_g, small, m, small) && !plan_overlap(seq_g, small, v, small) &&
+                    !plan_overlap(m, small, v, small) && !plan_overlap(seq_g, small, seq, full) &&
+                    !plan_overlap(m, small, seq, full) && !plan_overlap(v, small, seq, full) && src != dst,
+                "ndp_plan_grad_gather: two outputs overlap, or one overlaps seq");
+  PlanGatherArgs a{err, seq, n_traj, rollouts, steps, rows, src, dst, seq_g, m, v};
+  hipStream_t st = (hipStream_t)stream;
+  KTimer kt("k_plan_grad_gather", st);
+  hipLaunchKernelGGL(k_plan_grad_gather, dim3((unsigned)n_traj), dim3(plan::kBlock), 0, st, a);
+  return check_launch("k_plan_grad_gather");
+}
+
+int ndp_plan_grad_step(const float* grad, float* seq_g, float* m, float* v, const float* err_g, int64_t n_traj, int rows,
+                       int steps, int t, int optimizer, float lr, float beta1, float beta2, float eps, const float* low4,
+                       const float* high4, float* curve_out, const int32_t* dst, float* seq_full, int rollouts,
+                       void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(grad && seq_g && low4 && high4, "ndp_plan_grad_step: null pointer");
+  NDP_CHECK_ARG(optimizer == NDP_PLAN_SGD || optimizer == NDP_PLAN_ADAM, "ndp_plan_grad_step: optimizer=%d is neither "
+                "NDP_PLAN_SGD nor NDP_PLAN_ADAM", optimizer);
+  const bool adam = optimizer == NDP_PLAN_ADAM;
+  NDP_CHECK_ARG(!adam || (m && v), "ndp_plan_grad_step: NDP_PLAN_ADAM needs m and v");
+  NDP_CHECK_ARG(curve_out == nullptr || err_g != nullptr, "ndp_plan_grad_step: curve_out needs err_g");
+  NDP_CHECK_ARG((dst == nullptr) == (seq_full == nullptr), "ndp_plan_grad_step: dst and seq_full must both be given or both "
+                "be NULL");
+  NDP_CHECK_ARG(n_traj >= 1 && n_traj <= 65535, "ndp_plan_grad_step: n_traj=%lld outside 1..65535", (long long)n_traj);
+  NDP_CHECK_ARG(rows >= 1 && rows <= NDP_MAX_SAMPLES / 2, "ndp_plan_grad_step: rows=%d outside 1..%d", rows,
+                NDP_MAX_SAMPLES / 2);
+  NDP_CHECK_ARG(seq_full == nullptr || (rollouts >= 2 * rows && rollouts <= NDP_MAX_SAMPLES),
+                "ndp_plan_grad_step: rollouts=%d outside 2 rows..%d", rollouts, NDP_MAX_SAMPLES);
+  NDP_CHECK_ARG(steps >= 1 && steps <= plan::kMaxSteps, "ndp_plan_grad_step: steps=%d outside 1..%d", steps, plan::kMaxSteps);
+  NDP_CHECK_ARG(t >= 1 && t <= 65535, "ndp_plan_grad_step: t=%d outside 1..65535", t);
+  NDP_CHECK_ARG(lr > 0.f && lr < INFINITY, "ndp_plan_grad_step: lr=%g must be finite and > 0", (double)lr);
+  NDP_CHECK_ARG(!adam || (beta1 >= 0.f && beta1 < 1.f && beta2 >= 0.f && beta2 < 1.f && eps >= 0.f && eps < INFINITY),
+                "ndp_plan_grad_step: beta1=%g, beta2=%g outside [0, 1) or eps=%g not finite and >= 0", (double)beta1,
+                (double)beta2, (double)eps);
+  for (int c = 0; c < 4; ++c)
+    NDP_CHECK_ARG(low4[c] <= high4[c], "ndp_plan_grad_step: low[%d]=%g above high[%d]=%g (or NaN)", c, (double)low4[c], c,
+                  (double)high4[c]);
+  NDP_CHECK_ARG(aligned16(grad) && aligned16(seq_g) && aligned16(m) && aligned16(v) && aligned16(seq_full),
+                "ndp_plan_grad_step: grad, seq_g, m, v and seq_full must be 16-byte aligned");
+  const int64_t small = (int64_t)steps * n_traj * rows * 4, full = (int64_t)steps * n_traj * rollouts * 4;
+  const float* bufs[4] = {grad, seq_g, adam ? m : nullptr, adam ? v : nullptr};
+  for (int i = 0; i < 4; ++i) {
+    if (bufs[i] == nullptr) continue;
+    for (int j = 0; j < i; ++j)
+      NDP_CHECK_ARG(bufs[j] == nullptr || !plan_overlap(bufs[i], small, bufs[j], small),
+                    "ndp_plan_grad_step: two of grad, seq_g, m and v overlap");
+    NDP_CHECK_ARG(seq_full == nullptr || !plan_overlap(bufs[i], small, seq_full, full),
+                  "ndp_plan_grad_step: seq_full overlaps grad, seq_g, m or v");
+  }
+  PlanStepArgs a{grad, seq_g, adam ? m : nullptr, adam ? v : nullptr, err_g, n_traj, rows, steps, adam ? 1 : 0,
+                 (double)lr, (double)beta1, (double)beta2, (double)eps, 1.0, 1.0, {}, {}, curve_out, dst, seq_full, rollouts};
+  if (adam) {
+    a.corr1 = 1.0 - plan::pow_steps(a.beta1, t);
+    a.corr2 = 1.0 - plan::pow_steps(a.beta2, t);
+  }
+  for (int c = 0; c < 4; ++c) { a.low[c] = low4[c]; a.high[c] = high4[c]; }
+  const int64_t n = n_traj * rows;
+  hipStream_t st = (hipStream_t)stream;
+  KTimer kt("k_plan_grad_step", st);
+  hipLaunchKernelGGL(k_plan_grad_step, dim3((unsigned)((n + plan::kBlock - 1) / plan::kBlock)), dim3(plan::kBlock), 0, st, a);
+  return check_launch("k_plan_grad_step");
 }
 
 int ndp_normal_noise(float* out, int64_t n, uint64_t seed, const int32_t* offset_dev, void* stream) {

@@ -29,6 +29,9 @@ nothing here launches anything else than the reference's planner needs.
 Two further opt-in fields of CemSettings: `weighting="mppi"` weighs the elites by exp(-(e - e_best) / temperature)
 (ndp_plan_update), and `warm_start=True` starts a planning step from the previous step's fit shifted by one action
 (ndp_plan_warm; plan_step's `prior`, carried by mpc_plan and MpcController).
+`grad=GradSettings(...)` on the same entry points adds a gradient stage before the choice (_grad_stage; ndp_plan_goal_grad,
+ndp_plan_grad_gather, ndp_plan_grad_step and the forward model's ndp_fm_input_grads): the best rows of the population are
+refined by gradient descent on the planner's score and replace the worst ones.  Off by default, with or without `cem`.
 """
 import torch
 
@@ -229,6 +232,66 @@ class EvalModels:
             _capi.check(self.lib.ndp_plan_warm(_ptr(mean_prev), _ptr(std_prev), _ptr(normal), b, w, int(mean_prev.shape[1]),
                                                th, settings.carried_floor(), low, high, _ptr(mean), _ptr(std), _ptr(warm),
                                                self._stream()), "ndp_plan_warm")
+
+    # ------------------------------------------------------------------ the gradient stage (`grad`)
+    def forward_keep(self, state, actions, slot):
+        """forward() on the workspace of horizon step `slot`, which keeps the pass's activations for input_grads(slot).
+        Every slot has a workspace of its own (made and packed on first use, kept), so Th passes can wait for one
+        backward chain."""
+        n = int(state.shape[0])
+        if n > 8192:
+            raise _capi.NdpError("the forward model takes at most 8192 images per call, got %d" % n)
+        keep = self.__dict__.setdefault("_fm_keep", [])
+        while len(keep) <= slot:
+            keep.append({"ws": None, "n": 0})
+        entry = keep[slot]
+        if entry["ws"] is None or entry["n"] < n:
+            entry["ws"] = torch.empty(self.lib.ndp_fm_workspace_floats(n), dtype=torch.float32, device=self.device)
+            entry["n"] = n
+            with _capi.on_device(self.device):
+                _capi.check(self.lib.ndp_fm_pack_params(_ptr(self.fm_params), _ptr(entry["ws"]), self._stream()),
+                            "ndp_fm_pack_params")
+        out = torch.empty(n, 3, 128, 128, dtype=torch.float32, device=self.device)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_fm_forward(_ptr(self.fm_params), _ptr(self.fm_stats), _ptr(state), _ptr(actions), n, 0,
+                                                _ptr(out), _ptr(entry["ws"]), self._stream()), "ndp_fm_forward")
+        return out
+
+    def input_grads(self, d_out, slot, d_state, d_actions):
+        """ndp_fm_input_grads through the pass forward_keep(..., slot) ran last: d_out [n,3,128,128] -> d_state (or None)
+        and d_actions [n,4] (or None).  One call per forward_keep."""
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_fm_input_grads(_ptr(self.fm_params), _ptr(d_out), int(d_out.shape[0]), _ptr(d_state),
+                                                    _ptr(d_actions), _ptr(self._fm_keep[slot]["ws"]), self._stream()),
+                        "ndp_fm_input_grads")
+
+    def goal_grad(self, pred, goal, rows_per_goal, err, d_pred):
+        """ndp_plan_goal_grad: err [n] = the MSE of pred row i against goal row i // rows_per_goal (score_select's bits),
+        d_pred = its gradient (may be `pred` itself)."""
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_plan_goal_grad(_ptr(pred), int(pred.shape[0]), _ptr(goal), int(goal.shape[0]),
+                                                    int(rows_per_goal), _ptr(err), _ptr(d_pred), self._stream()),
+                        "ndp_plan_goal_grad")
+
+    def grad_gather(self, err, seq, src, dst, seq_g, m, v):
+        """ndp_plan_grad_gather: the G = seq_g.shape[2] best rows of seq [Th,B,R,4] by err [B,R] into seq_g [Th,B,G,4], their
+        indices into src [B,G], the G worst rows' into dst [B,G]; m, v zeroed."""
+        th, b, r = int(seq.shape[0]), int(seq.shape[1]), int(seq.shape[2])
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_plan_grad_gather(_ptr(err), _ptr(seq), b, r, th, int(seq_g.shape[2]), _ptr(src), _ptr(dst),
+                                                      _ptr(seq_g), _ptr(m), _ptr(v), self._stream()), "ndp_plan_grad_gather")
+
+    def grad_step(self, grad, seq_g, m, v, err_g, t, settings, curve_out=None, dst=None, seq_full=None):
+        """ndp_plan_grad_step: update number t (from 1) of seq_g [Th,B,G,4] along grad, by settings.optimizer; curve_out
+        [B,G] receives err_g; with dst and seq_full the result also goes to rows dst of the population seq_full."""
+        th, b, g = int(seq_g.shape[0]), int(seq_g.shape[1]), int(seq_g.shape[2])
+        low, high = (_capi.c_float * 4)(*settings.low), (_capi.c_float * 4)(*settings.high)
+        with _capi.on_device(self.device):
+            _capi.check(self.lib.ndp_plan_grad_step(_ptr(grad), _ptr(seq_g), _ptr(m), _ptr(v), _ptr(err_g), b, g, th, int(t),
+                                                    OPTIMIZERS.index(settings.optimizer), settings.lr, settings.beta1,
+                                                    settings.beta2, settings.eps, low, high, _ptr(curve_out), _ptr(dst),
+                                                    _ptr(seq_full), 0 if seq_full is None else int(seq_full.shape[2]),
+                                                    self._stream()), "ndp_plan_grad_step")
 
 
 # ---------------------------------------------------------------------- the reference's noise stream (CPU)
@@ -486,6 +549,105 @@ class CemSettings:
 
 CEM_MAX_HORIZON = 32
 WEIGHTINGS = ("elites", "mppi")                 # NDP_PLAN_ELITES, NDP_PLAN_MPPI
+OPTIMIZERS = ("sgd", "adam")                    # NDP_PLAN_SGD, NDP_PLAN_ADAM
+
+
+class GradSettings:
+    """The opt-in gradient stage of mpc_plan / plan_step / MpcController (`grad=`; include/ndp.h "planner: gradient
+    refinement"): after the sampling rounds (population 0, and the rounds of `cem` when given) the `rows`
+    best action sequences of every trajectory are refined by `iterations` steps of gradient descent on the planner's own
+    score, through the forward model's exact input gradients, and replace the `rows` worst ones before the last
+    selection.  The originals stay in the population, so the chosen error never rises.  Works with any `cem` or none.
+      iterations  J >= 0 gradient steps (0: the planner without the stage, bit for bit)
+      rows        G, the sequences refined per trajectory, 1 <= G <= R // 2 (so R >= 2); None: max(1, R // 8)
+      lr          step size, finite and > 0 (in fp32 too)
+      optimizer   "adam" (moments start at 0 in every planning step) or "sgd"
+      beta1, beta2, eps   Adam's, 0 <= beta < 1, eps finite and >= 0
+      low, high   bounds of the 4 action components the refined rows are clamped to: one number for all, or 4
+    The defaults are hyperparameters, not measurements."""
+
+    FIELDS = ("iterations", "rows", "lr", "optimizer", "beta1", "beta2", "eps", "low", "high")
+
+    def __init__(self, iterations=3, rows=None, lr=0.05, optimizer="adam", beta1=0.9, beta2=0.999, eps=1e-8, low=-1.0,
+                 high=1.0):
+        def integer(v, name):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("grad.%s must be an integer, got %r" % (name, v))
+            return int(v)
+
+        def four(v, name):
+            vals = [float(x) for x in v] if hasattr(v, "__len__") else [float(v)] * 4
+            if len(vals) != 4 or any(x != x or x in (float("inf"), float("-inf")) for x in vals):
+                raise ValueError("grad.%s must be one finite number or 4, got %r" % (name, v))
+            return tuple(vals)
+
+        self.iterations = integer(iterations, "iterations")
+        if not 0 <= self.iterations <= 65535:
+            raise ValueError("grad.iterations must lie in 0..65535, got %d" % self.iterations)
+        self.rows = None if rows is None else integer(rows, "rows")
+        if self.rows is not None and not 1 <= self.rows <= _capi.MAX_SAMPLES // 2:
+            raise ValueError("grad.rows must lie in 1..%d (and not above half the rollouts), got %d"
+                             % (_capi.MAX_SAMPLES // 2, self.rows))
+        self.lr = float(lr)
+        if not 0.0 < _capi.c_float(self.lr).value < float("inf"):      # the kernel reads it as fp32
+            raise ValueError("grad.lr must be finite and > 0 (in fp32), got %r" % (lr,))
+        if optimizer not in OPTIMIZERS:
+            raise ValueError("grad.optimizer must be 'adam' or 'sgd', got %r" % (optimizer,))
+        self.optimizer = optimizer
+        self.beta1, self.beta2, self.eps = float(beta1), float(beta2), float(eps)
+        for name in ("beta1", "beta2"):
+            if not 0.0 <= _capi.c_float(getattr(self, name)).value < 1.0:
+                raise ValueError("grad.%s must lie in [0, 1) (in fp32), got %r" % (name, getattr(self, name)))
+        if not 0.0 <= self.eps < float("inf"):
+            raise ValueError("grad.eps must be finite and >= 0, got %r" % (eps,))
+        self.low, self.high = four(low, "low"), four(high, "high")
+        if any(lo > hi for lo, hi in zip(self.low, self.high)):
+            raise ValueError("grad.low must not exceed grad.high, got %r and %r" % (self.low, self.high))
+
+    @classmethod
+    def from_config(cls, mapping):
+        """The optional `mpc.grad` mapping of a config (keys: the fields' names); absent or empty: None, the stage off."""
+        if mapping is None or (hasattr(mapping, "__len__") and len(mapping) == 0):
+            return None
+        if not hasattr(mapping, "keys"):
+            raise ValueError("mpc.grad must be a mapping of %s, got %r" % (", ".join(cls.FIELDS), mapping))
+        unknown = sorted(set(mapping.keys()) - set(cls.FIELDS))
+        if unknown:
+            raise ValueError("mpc.grad has unknown keys %s (known: %s)" % (unknown, ", ".join(cls.FIELDS)))
+        return cls(**{k: mapping[k] for k in mapping.keys()})
+
+    def row_count(self, rollouts):
+        """G for R = rollouts."""
+        r = int(rollouts)
+        if r < 2 or r > _capi.MAX_SAMPLES:
+            raise ValueError("the gradient stage needs 2..%d rollouts, got %d" % (_capi.MAX_SAMPLES, r))
+        g = max(1, r // 8) if self.rows is None else self.rows
+        if g > r // 2:
+            raise ValueError("grad.rows=%d exceeds half the %d rollouts (%d): the refined rows replace the worst ones and "
+                             "must not reach the best" % (g, r, r // 2))
+        return g
+
+    def __repr__(self):
+        return "GradSettings(%s)" % ", ".join("%s=%r" % (f, getattr(self, f)) for f in self.FIELDS)
+
+
+def grad_from_config(config, rollouts=None, horizon=None):
+    """The GradSettings of a config's optional `mpc.grad` mapping, checked against mpc.rollouts and mpc.time_horizon;
+    None when the key is absent."""
+    mpc = config.get("mpc") if hasattr(config, "get") else None
+    grad = GradSettings.from_config(mpc.get("grad") if mpc is not None and hasattr(mpc, "get") else None)
+    if grad is not None:
+        _grad_check(grad, int(mpc.rollouts) if rollouts is None else rollouts,
+                    int(mpc.time_horizon) if horizon is None else horizon)
+    return grad
+
+
+def _grad_check(grad, rollouts, horizon):
+    if not isinstance(grad, GradSettings):
+        raise TypeError("grad must be an evaluation.GradSettings, got %r" % (grad,))
+    grad.row_count(rollouts)
+    if int(horizon) > CEM_MAX_HORIZON:
+        raise ValueError("the gradient stage takes a horizon of at most %d, got %d" % (CEM_MAX_HORIZON, int(horizon)))
 
 
 def cem_normal_floats(batch, rollouts, horizon, iterations, seq_length=None):
@@ -595,8 +757,46 @@ def _uniform_actions(cem, noise, seq, nz):
     torch.minimum(seq, high, out=seq)                           # low + (high - low) * u can round past high
 
 
+def _grad_stage(models, grad, grad_io, state, goal, b, r, seq, pred, out_err, out_choice, out_act):
+    """The gradient stage of one planning step (GradSettings; include/ndp.h): score the population `seq` [steps,B,R,4]
+    whose last predictions are `pred`, gather its G best rows, refine them by J x (open-loop rollout that keeps every
+    pass's activations, ndp_plan_goal_grad, the backward chain of ndp_fm_input_grads, ndp_plan_grad_step), and let the last
+    step write them over the G worst rows of `seq`, in place.  grad_io: a dict whose curve [J,B,G], src and dst [B,G] are
+    written, and which receives "rows" [steps,B,G,4], the last iteration's gradient.  Every buffer of the stage is
+    allocated here; nothing synchronises with the host."""
+    dev, steps, g = models.device, int(seq.shape[0]), grad.row_count(r)
+    models.score_select(pred, b, r, goal, seq[0], None, None, out_err, out_choice, out_act, None)
+    seq_g = torch.empty(steps, b, g, 4, dtype=torch.float32, device=dev)
+    m, v, rows = torch.empty_like(seq_g), torch.empty_like(seq_g), torch.empty_like(seq_g)
+    models.grad_gather(out_err, seq, grad_io["src"], grad_io["dst"], seq_g, m, v)
+    start = _broadcast(state, torch.empty(b * g, 3, 128, 128, dtype=torch.float32, device=dev))     # once: no pass writes it
+    err_g = torch.empty(b, g, dtype=torch.float32, device=dev)
+    for j in range(grad.iterations):
+        cur = start
+        for ts in range(steps):
+            cur = models.forward_keep(cur, seq_g[ts], ts)
+        models.goal_grad(cur, goal, g, err_g, cur)             # in place: cur is d err / d (the last predictions)
+        for ts in range(steps - 1, -1, -1):
+            d_state = torch.empty_like(cur) if ts > 0 else None
+            models.input_grads(cur, ts, d_state, rows[ts])
+            cur = d_state
+        last = j == grad.iterations - 1
+        models.grad_step(rows, seq_g, m, v, err_g, j + 1, grad, grad_io["curve"][j], grad_io["dst"] if last else None,
+                         seq if last else None)
+    grad_io["rows"] = rows
+
+
+def _grad_buffers(grad, lead, b, r, dev):
+    """The stage's results, `lead` the leading dimensions (mpc_plan: one set per planning step): curve [.., J,B,G], src
+    and dst [.., B,G] (-1 where the stage does not run)."""
+    g = grad.row_count(r)
+    return {"curve": torch.empty(*lead, grad.iterations, b, g, dtype=torch.float32, device=dev),
+            "src": torch.full((*lead, b, g), -1, dtype=torch.int32, device=dev),
+            "dst": torch.full((*lead, b, g), -1, dtype=torch.int32, device=dev)}
+
+
 def _plan_once(models, cem, state, goal, goal_code, b, r, steps, noise, cem_io, rep, forced, out_err, out_choice, out_act,
-               pred_out, prior=None):
+               pred_out, prior=None, grad=None, grad_io=None):
     """One planning step from `state` [B,3,128,128], for mpc_plan and plan_step alike.  Population 0 is the generator's
     closed-loop rollouts (_rollout_generator), or with cem.proposal "uniform" a uniform draw replayed open loop; then
     `cem.iterations` x (ndp_eval_score_select, ndp_plan_cem_update, _rollout_open) -- none when `cem` is None --; then the
@@ -608,7 +808,10 @@ def _plan_once(models, cem, state, goal, goal_code, b, r, steps, noise, cem_io, 
     one ndp_plan_warm shifts it into this step's mean / std and draws W = cem.warm_count(R) rows per horizon step from it,
     which replace rows R - W .. R - 1 of population 0; the first update then smooths against the shifted fit (smooth = 1,
     first = 1).  The step's normals are then [steps,B,W,4] ahead of the iterations' blocks.  cem.weighting "mppi" or a
-    prior send every update through ndp_plan_update; otherwise the step is ndp_plan_cem_update's, bit for bit."""
+    prior send every update through ndp_plan_update; otherwise the step is ndp_plan_cem_update's, bit for bit.
+    grad: None, or a GradSettings with grad_io (_grad_buffers): with iterations > 0, _grad_stage runs between the rounds
+    and the last selection, which then scores one more open-loop rollout of the population; mean and std are not touched by
+    it, and curve keeps its I + 1 entries (the last is the final population's)."""
     dev, br = models.device, b * r
     seq = torch.empty(steps, b, r, 4, dtype=torch.float32, device=dev)
     mean = std = warm = None
@@ -646,6 +849,9 @@ def _plan_once(models, cem, state, goal, goal_code, b, r, steps, noise, cem_io, 
             models.cem_update(out_err, seq, normal[it * per:(it + 1) * per], cem, it == 0, mean, std, nxt, best)
         seq = nxt
         pred, pred0 = _rollout_open(models, state, seq, rep)
+    if grad is not None and grad.iterations > 0:
+        _grad_stage(models, grad, grad_io, state, goal, b, r, seq, pred, out_err, out_choice, out_act)
+        pred, pred0 = _rollout_open(models, state, seq, rep)
     models.score_select(pred, b, r, goal, seq[0], pred0 if pred_out is not None else None, forced, out_err, out_choice,
                         out_act, pred_out)
     if cem is not None:
@@ -664,7 +870,7 @@ def mpc_noise_floats(batch, seq_length, rollouts, horizon, noise_dim):
 
 
 def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=None, seed=0, on_step=None, cem=None,
-             normal=None):
+             normal=None, grad=None):
     """mpc_eval.py:112-184 for B trajectories at once, rows [B][R].
 
     frames [B,T,3,128,128] float or [B,T,128,128,3] bytes, actions [B,T,4].  noise: None (device draws of
@@ -685,12 +891,19 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     Th, cem, seq_length=T) floats; with cem.warm_start every planning step but the first has [steps,B,W,4] ahead of its
     iterations, and starts from the fit of the step before it, _plan_once's `prior`).  Added results: best_curve
     [T-1,I+1,B] the chosen row's error per population, best_err [T-1,B] the least of them, cem_mean / cem_std [B,steps,4]
-    the last planning step's fit (zeros with 0 iterations)."""
+    the last planning step's fit (zeros with 0 iterations).
+
+    grad: None, or a GradSettings: every planning step refines its G best rows by gradient descent before it chooses
+    (_grad_stage), with or without `cem`; with 0 iterations every result above has the bits of the call without `grad`.
+    Added results: grad_curve [T-1,J,B,G] the refined rows' errors before each update, grad_src and grad_dst [T-1,B,G] the
+    rows they came from and the rows they replaced (-1 with 0 iterations)."""
     r, th = int(rollouts), int(horizon)
     if r < 1 or th < 1:
         raise ValueError("rollouts and horizon must be >= 1, got %d, %d" % (r, th))
     if cem is not None:
         _cem_check(cem, r, th)
+    if grad is not None:
+        _grad_check(grad, r, th)
     imgs, b, t = _frames(models, frames)
     t1, nz, br = t - 1, models.noise_dim, b * r
     if t1 < 1:
@@ -724,8 +937,10 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
         normal = _cem_normal(models, normal, plan_normal_floats(b, r, th, cem, seq_length=t), seed)
         curve = torch.empty(t1, cem.iterations + 1, b, dtype=torch.float32, device=dev)
         best = torch.empty(t1, b, dtype=torch.float32, device=dev)
+    if grad is not None:
+        grad_all = _grad_buffers(grad, (t1,), b, r, dev)
     off = n_off = 0
-    prior = None
+    prior = grad_io = None
     for image_num in range(t1):
         if on_step is not None:
             on_step(image_num)
@@ -737,10 +952,12 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
                 n_normal += steps * b * cem.warm_count(r) * 4
             cem_io = normal[n_off:n_off + n_normal], curve[image_num], best[image_num]
             n_off += n_normal
+        if grad is not None:
+            grad_io = {k: x[image_num] for k, x in grad_all.items()}
         nxt = torch.empty(b, 3, 128, 128, dtype=torch.float32, device=dev)
         _, cem_mean, cem_std = _plan_once(models, cem, state, goal, goal_code, b, r, steps, noise[off:off + n_noise], cem_io,
                                           rep, None if forced is None else forced[image_num], out_err[image_num],
-                                          out_choice[image_num], out_act[image_num], nxt, prior)
+                                          out_choice[image_num], out_act[image_num], nxt, prior, grad, grad_io)
         if cem is not None and cem.warm_start:
             prior = cem_mean, cem_std                                      # shifted by one action at the next step
         off += n_noise
@@ -754,6 +971,8 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
            "image_error_sum": image_error_sum, "action_error": action_error}
     if cem is not None:
         res.update(best_curve=curve, best_err=best, cem_mean=cem_mean, cem_std=cem_std)
+    if grad is not None:
+        res.update(grad_curve=grad_all["curve"], grad_src=grad_all["src"], grad_dst=grad_all["dst"])
     return res
 
 
@@ -764,7 +983,7 @@ def plan_step_noise_floats(batch, rollouts, horizon, noise_dim):
 
 
 def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, seed=0, choice=None, cem=None, normal=None,
-              prior=None):
+              prior=None, grad=None):
     """One planning step of MPC_gym_eval.py:183-225 for B environments at once, rows [B][R]: from the observed `state`
     [B,3,128,128], R rollouts of Th steps through encoder, generator and forward model, scored against the goal image.
 
@@ -786,12 +1005,19 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
 
     prior: None, or with cem.warm_start (anything else: ValueError) the pair (cem_mean, cem_std) [B,steps_prev,4],
     steps_prev >= Th, that the previous call returned: the step starts from that fit shifted by one action (_plan_once),
-    and `normal` is then [Th,B,W,4] ahead of the iterations (plan_normal_floats(B, R, Th, cem, prior=True) floats)."""
+    and `normal` is then [Th,B,W,4] ahead of the iterations (plan_normal_floats(B, R, Th, cem, prior=True) floats).
+
+    grad: None, or a GradSettings: the gradient stage before the choice (_grad_stage), with or without `cem`.  The dict
+    that follows the four values (the fifth value also without `cem`) then carries grad_curve [J,B,G], grad_src and
+    grad_dst [B,G] and, with J > 0, grad_rows [Th,B,G,4], the last iteration's gradient; with 0 iterations the four have the
+    bits of the call without `grad`."""
     r, th = int(rollouts), int(horizon)
     if r < 1 or th < 1:
         raise ValueError("rollouts and horizon must be >= 1, got %d, %d" % (r, th))
     if cem is not None:
         _cem_check(cem, r, th)
+    if grad is not None:
+        _grad_check(grad, r, th)
     if state.dim() != 4 or tuple(state.shape[1:]) != (3, 128, 128) or tuple(goal.shape) != tuple(state.shape):
         raise _capi.NdpError("state and goal must both be [B,3,128,128], got %s and %s"
                              % (tuple(state.shape), tuple(goal.shape)))
@@ -829,11 +1055,17 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
         cem_io = _cem_normal(models, normal, plan_normal_floats(b, r, th, cem, prior=prior is not None), seed), curve, best
     # the full horizon (MPC_gym_eval.py:188); nobody reads the chosen rollout's prediction (the environment gives the
     # next state): no pred_out
+    grad_io = None if grad is None else _grad_buffers(grad, (), b, r, dev)
     seq, mean, std = _plan_once(models, cem, state.contiguous(), goal.contiguous(), goal_code, b, r, th, noise, cem_io, rep,
-                                forced, err, pick, action, None, prior)
-    if cem is None:
+                                forced, err, pick, action, None, prior, grad, grad_io)
+    if cem is None and grad is None:
         return action, pick, err, seq[0]
-    return action, pick, err, seq[0], {"best_curve": curve, "best_err": best, "cem_mean": mean, "cem_std": std}
+    info = {} if cem is None else {"best_curve": curve, "best_err": best, "cem_mean": mean, "cem_std": std}
+    if grad is not None:
+        info.update(grad_curve=grad_io["curve"], grad_src=grad_io["src"], grad_dst=grad_io["dst"])
+        if "rows" in grad_io:
+            info["grad_rows"] = grad_io["rows"]
+    return action, pick, err, seq[0], info
 
 
 class MpcController:
@@ -849,7 +1081,7 @@ class MpcController:
     back, because the environment needs them.  `info`: state_u8 [B,128,128,3] (what MPC_gym_eval.get_state resizes to),
     state [B,3,128,128], rollout_errors [B,R], choice [B], actions0 [B,R,4], all on the device."""
 
-    def __init__(self, models, rollouts, horizon, frame_shape=None, seed=0, cem=None, normal=None):
+    def __init__(self, models, rollouts, horizon, frame_shape=None, seed=0, cem=None, normal=None, grad=None):
         from .resize import LanczosResizer
         self.models, self.rollouts, self.horizon = models, int(rollouts), int(horizon)
         if self.rollouts < 1 or self.horizon < 1:
@@ -862,6 +1094,11 @@ class MpcController:
         # With cem.warm_start every plan() after the first since reset() starts from the fit of the one before it
         # (plan_step's `prior`), and its piece of the stream has [Th,B,W,4] ahead of the iterations
         self.cem, self.normal = cem, normal
+        # grad: a GradSettings turns plan_step's gradient stage on for every plan(); `info` then also carries grad_curve,
+        # grad_src, grad_dst and grad_rows
+        if grad is not None:
+            _grad_check(grad, self.rollouts, self.horizon)
+        self.grad = grad
         self._prior, self._normal_off = None, 0
         self.resizer = LanczosResizer(models.device)
         self.frame_shape = None                               # None: the first frame tells
@@ -925,7 +1162,7 @@ class MpcController:
             self._normal_off += per
         action, pick, err, act0, *extra = plan_step(self.models, state, self.goal, self.goal_code, self.rollouts, self.horizon,
                                                     noise=noise, seed=self.seed + self.steps, choice=choice, cem=self.cem,
-                                                    normal=normal, prior=self._prior)
+                                                    normal=normal, prior=self._prior, grad=self.grad)
         extra = extra[0] if extra else {}                     # with `cem`: best_curve, best_err, cem_mean, cem_std
         if self.cem is not None and self.cem.warm_start:
             self._prior = extra["cem_mean"], extra["cem_std"]

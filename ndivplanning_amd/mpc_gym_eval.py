@@ -153,6 +153,7 @@ def fetch_push_control_evaluation(args, image_encoder, fwd_model_autoencoder, ge
     shapes = E.noise_piece_shapes("mpc_gym", bs, t, k, nz, r, th)
     per_step = E.plan_step_noise_floats(1, r, th, nz)
     cem = E.cem_from_config(config, r, th)                # the optional `mpc.cem` mapping (absent: the planner as it was)
+    grad = E.grad_from_config(config, r, th)              # the optional `mpc.grad` mapping (absent: no gradient stage)
     fut_idx = torch.arange(1, t, dtype=torch.int32, device=dev)
     action_error_sum = torch.zeros(1, dtype=torch.float32, device=dev)
     image_error_sum = None
@@ -169,7 +170,7 @@ def fetch_push_control_evaluation(args, image_encoder, fwd_model_autoencoder, ge
         state = imgs[0:1]                                                         # frame 0 of the dataset (:180-181)
         for image_num in range(t1):
             if ctrl is None:
-                ctrl = E.MpcController(models, r, th, seed=seed, cem=cem)         # the first frame tells the camera's size
+                ctrl = E.MpcController(models, r, th, seed=seed, cem=cem, grad=grad)   # the first frame tells the camera's size
             if image_num == 0:
                 ctrl.reset(imgs[t1:t1 + 1])                                       # the goal, encoded once per trajectory
                 ctrl.seed = seed + i * t1                                         # (read only for `cem`'s normal draws)

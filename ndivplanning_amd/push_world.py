@@ -452,12 +452,13 @@ def generate(n, out_dir, steps=15, seed=0, epsilon=0.2, start="simplified", batc
 
 
 # ---------------------------------------------------------------------------------------------------- closed-loop MPC
-def closed_loop_mpc(models, world, goal_frames, steps, rollouts, horizon, cem=None, seed=0, threshold=SUCCESS_THRESHOLD):
+def closed_loop_mpc(models, world, goal_frames, steps, rollouts, horizon, cem=None, seed=0, threshold=SUCCESS_THRESHOLD,
+                    grad=None):
     """MPC on the world's n live environments from its current state: MpcController.reset(goal_frames), then per step
     ctrl.act(world.render()) -> world.step(actions).  goal_frames: uint8 [n,S,S,3].  Returns {"distance" [n],
-    "success" [n] bool, "actions" [steps,n,4]} on the host."""
+    "success" [n] bool, "actions" [steps,n,4]} on the host.  cem, grad: the controller's CemSettings / GradSettings."""
     from .evaluation import MpcController
-    ctrl = MpcController(models, rollouts, horizon, frame_shape=(world.size, world.size), seed=seed, cem=cem)
+    ctrl = MpcController(models, rollouts, horizon, frame_shape=(world.size, world.size), seed=seed, cem=cem, grad=grad)
     goal = torch.as_tensor(goal_frames)
     if goal.dtype != torch.uint8 or tuple(goal.shape) != (world.n, world.size, world.size, 3):
         raise ValueError("goal_frames must be uint8 %s, got %s %s"
@@ -475,7 +476,7 @@ def closed_loop_mpc(models, world, goal_frames, steps, rollouts, horizon, cem=No
 
 
 def evaluate_mpc(models, n, steps, rollouts, horizon, cem=None, seed=0, start="simplified", frame_size=128,
-                 threshold=SUCCESS_THRESHOLD):
+                 threshold=SUCCESS_THRESHOLD, grad=None):
     """Three policies from the same n seeded starts: the expert (the ceiling), uniform random actions (the floor) and
     MPC towards the expert's last frame -- what frame T-1 of a generated dataset is, and what the reference uses as the
     goal image.  Returns {policy: {"distance": mean final block-goal distance, "success": rate}} and "mpc_actions"."""
@@ -495,7 +496,8 @@ def evaluate_mpc(models, n, steps, rollouts, horizon, cem=None, seed=0, start="s
         world.step(torch.rand(world.n, 4, generator=gen) * 2.0 - 1.0, render=False)
     result["random"] = report()
     world.reset(render=False)
-    run = closed_loop_mpc(models, world, goal_frames, steps, rollouts, horizon, cem=cem, seed=seed, threshold=threshold)
+    run = closed_loop_mpc(models, world, goal_frames, steps, rollouts, horizon, cem=cem, seed=seed, threshold=threshold,
+                          grad=grad)
     result["mpc"] = report()
     result["mpc_actions"] = run["actions"]
     return result
@@ -503,7 +505,7 @@ def evaluate_mpc(models, n, steps, rollouts, horizon, cem=None, seed=0, start="s
 
 # -------------------------------------------------------------------------------------------------------- command line
 def _mpc_main(argv):
-    """`mpc`: the model paths and the mpc.* / mpc.cem keys of the configuration, as mpc_eval reads them."""
+    """`mpc`: the model paths and the mpc.* / mpc.cem / mpc.grad keys of the configuration, as mpc_eval reads them."""
     from argparse import ArgumentParser
 
     from . import evaluation as E
@@ -526,7 +528,7 @@ def _mpc_main(argv):
     r, th = int(config.mpc.rollouts), int(config.mpc.time_horizon)
     result = evaluate_mpc(models, namespace.envs, namespace.steps, r, th, cem=E.cem_from_config(config, r, th),
                           seed=int(config.random_seed), start=namespace.start,
-                          threshold=float(config.evaluation.threshold))
+                          threshold=float(config.evaluation.threshold), grad=E.grad_from_config(config, r, th))
     for policy in ("expert", "random", "mpc"):
         print("%-6s mean goal distance %.4f  success rate %.3f" % (policy, result[policy]["distance"],
                                                                    result[policy]["success"]))
