@@ -225,6 +225,15 @@ int64_t ndp_step_workspace_floats(const ndp_step_config *cfg);
  * -1: bad config or index. */
 #define NDP_STEP_TENSORS 12
 int64_t ndp_step_workspace_offset(const ndp_step_config *cfg, int tensor);
+/* For tests, host arithmetic only: the block -> (job, chunk) map of a step's weight-gradient launch
+ * (which: 0 = D, 1 = G; first: as run_g_forward), by the function the kernel itself calls.
+ * pairs[2 b], pairs[2 b + 1] for block b < min(grid, capacity): the job and row chunk; (-2, -2): an
+ * NDiv block.  table[32]: the chunk count of every job of the launch's table (0 past its end; a
+ * block whose chunk is not below its job's count returns at once), then in table[28..31] njobs,
+ * nwide, wide_chunks, nchunks of the launch.  slab_area[2]: float offset and length of the slabs
+ * the launch writes, inside the workspace.  Returns the launch's grid, -1 for a bad argument. */
+int64_t ndp_step_wgrad_blocks(const ndp_step_config *cfg, int which, int first, int32_t *pairs,
+                              int64_t capacity, int32_t *table, int64_t *slab_area);
 
 /* codes [flat,256], actions [flat,4] (ground truth), noise [flat,K,nz].
  * run_g_forward: 1 on the first D step of an iteration, 0 on repeats

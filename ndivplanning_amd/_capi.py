@@ -82,6 +82,7 @@ SIGNATURES = {
                               c_float, c_float, c_float, c_float, c_void_p]),
     "ndp_step_workspace_floats": (c_int64, [POINTER(StepConfig)]),
     "ndp_step_workspace_offset": (c_int64, [POINTER(StepConfig), c_int]),
+    "ndp_step_wgrad_blocks": (c_int64, [POINTER(StepConfig), c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "ndp_step_d_grads": (c_int, [POINTER(StepConfig), POINTER(StepBuffers), c_void_p, c_void_p, c_void_p,
                                  c_int, c_void_p]),
     "ndp_step_g_grads": (c_int, [POINTER(StepConfig), POINTER(StepBuffers), c_void_p, c_void_p, c_void_p,

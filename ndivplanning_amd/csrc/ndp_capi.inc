@@ -1014,6 +1014,31 @@ int64_t ndp_step_workspace_offset(const ndp_step_config* cfg, int tensor) {
   return at[tensor];
 }
 
+int64_t ndp_step_wgrad_blocks(const ndp_step_config* cfg, int which, int first, int32_t* pairs, int64_t capacity,
+                              int32_t* table, int64_t* slab_area) {
+  if (!step_config_ok(cfg) || which < 0 || which > 1 || !pairs || !table || !slab_area || capacity < 0) return -1;
+  const StepPlan p = step_plan(cfg, first != 0);
+  // host arithmetic only: the operands are addresses that nothing here reads
+  alignas(16) static float origin[4];
+  float* ws = origin;
+  const int K = cfg->num_sample, nz = cfg->noise_dim;
+  WgradArgs w;
+  if (which) build_g_jobs(w, nz, ws, p.gw, ws, p.acts, origin, CODE, K, origin, nz, p.m, ws + p.g_seg);
+  else build_d_jobs(w, ws, p.dw, origin, CODE, K, p.m, p.mpad, first ? ws + p.d_seg : nullptr, p.rpad);
+  const int64_t grid = which ? p.wgrad_g_grid : p.wgrad_d_grid;
+  const int slots = w.nwide * w.wide_chunks + 8 * ((w.nchunks + 7) / 8) * w.njobs;   // as wgrad_body
+  for (int j = 0; j < kMaxJobs; ++j) table[j] = j < w.njobs + w.nwide ? w.job[j].nchunks : 0;
+  table[kMaxJobs] = w.njobs; table[kMaxJobs + 1] = w.nwide; table[kMaxJobs + 2] = w.wide_chunks; table[kMaxJobs + 3] = w.nchunks;
+  slab_area[0] = which ? p.gw.slabs : p.dw.slabs;
+  slab_area[1] = (which ? p.gw.plan.slabs : p.dw.plan.slabs) * (which ? p.gw.slab_stride : p.dw.slab_stride);
+  for (int64_t b = 0; b < grid && b < capacity; ++b) {
+    int job = -2, chunk = -2;
+    if (b < slots) wgrad_slot(w.njobs, w.nwide, w.wide_chunks, (int)b, job, chunk);   // as wgrad_fetch_args
+    pairs[2 * b] = job; pairs[2 * b + 1] = chunk;
+  }
+  return grid;
+}
+
 int ndp_step_d_grads(const ndp_step_config* c, const ndp_step_buffers* b, const float* codes, const float* actions,
                      float* noise, int run_g_forward, void* stream) {
   int rc = check_step("ndp_step_d_grads", c, b, codes, actions, noise);

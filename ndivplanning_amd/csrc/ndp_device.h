@@ -123,6 +123,45 @@ __device__ __forceinline__ T load_kernargs() {
   return out;
 }
 
+// The line prefetch of load_kernargs alone, for a kernel that copies only a part of its arguments: one dword of each
+// 64-byte line of the first BYTES bytes of the kernarg segment (up to 8 lines), one wait.  Returns the segment's address
+// behind an empty asm: what is read through it comes after the prefetch and hits the scalar cache.
+template <size_t BYTES>
+__device__ __forceinline__ uint64_t touch_kernargs() {
+  typedef const __attribute__((address_space(4))) void* kptr_t;
+  kptr_t kp = (kptr_t)__builtin_amdgcn_kernarg_segment_ptr();
+  static_assert(BYTES >= 4 && BYTES <= 512, "touch_kernargs: 1..8 lines");
+  constexpr int LAST = (((int)BYTES - 4) / 64) * 64;
+  constexpr int O1 = 64 < LAST ? 64 : LAST, O2 = 128 < LAST ? 128 : LAST, O3 = 192 < LAST ? 192 : LAST,
+                O4 = 256 < LAST ? 256 : LAST, O5 = 320 < LAST ? 320 : LAST, O6 = 384 < LAST ? 384 : LAST,
+                O7 = 448 < LAST ? 448 : LAST;
+  uint32_t t0, t1, t2, t3, t4, t5, t6, t7;
+  asm volatile(
+      "s_load_dword %0, %8, 0x0\n\ts_load_dword %1, %8, %9\n\ts_load_dword %2, %8, %10\n\t"
+      "s_load_dword %3, %8, %11\n\ts_load_dword %4, %8, %12\n\ts_load_dword %5, %8, %13\n\t"
+      "s_load_dword %6, %8, %14\n\ts_load_dword %7, %8, %15\n\ts_waitcnt lgkmcnt(0)"
+      : "=&s"(t0), "=&s"(t1), "=&s"(t2), "=&s"(t3), "=&s"(t4), "=&s"(t5), "=&s"(t6), "=&s"(t7)
+      : "s"(kp), "i"(O1), "i"(O2), "i"(O3), "i"(O4), "i"(O5), "i"(O6), "i"(O7)
+      : "memory");
+  uint64_t v = (uint64_t)kp;
+  asm volatile("" : "+s"(v) : "s"(t0 | t1 | t2 | t3 | t4 | t5 | t6 | t7));
+  return v;
+}
+
+// A T at address `at` of the kernarg segment (4-byte aligned; `at` from touch_kernargs or another empty asm), read
+// dword by dword: hipcc merges these into wide SCALAR loads.  A __builtin_memcpy from a byte pointer has alignment 1
+// and becomes vector loads -- a round trip to L2 that the scalar-cache prefetch does nothing for.
+template <class T>
+__device__ __forceinline__ T read_kernargs(uint64_t at) {
+  static_assert(sizeof(T) % 4 == 0 && alignof(T) >= 4, "read_kernargs: whole dwords");
+  const __attribute__((address_space(4))) uint32_t* src = (const __attribute__((address_space(4))) uint32_t*)at;
+  T out;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(&out);
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / 4); ++i) dst[i] = src[i];
+  return out;
+}
+
 template <int WALIGN>
 __device__ __forceinline__ f32x4 ldg4(const float* p) {
 #ifdef NDP_EXP_NOLOAD     // diagnostic ablation: no weight traffic

@@ -1298,6 +1298,22 @@ struct WgradArgs : WgradHead {
   int wide_begin, wide_end;             // host side only: the parameter range the WIDE job writes
 };
 
+// Block -> (job, chunk) of a launch, for the blocks in front of its NDiv blocks: the WIDE jobs' chunks first (the longest),
+// then the 64 x 64 slots dealt round-robin over the 8 XCDs, chunk % 8 == block % 8 (see wgrad_body).  A slot whose chunk
+// is not below its job's own count has nothing to do.  Host and device: ndp_step_wgrad_blocks enumerates the same map.
+__host__ __device__ __forceinline__ void wgrad_slot(int njobs, int nwide, int wide_chunks, int block, int& job, int& chunk) {
+  const int wide_blocks = nwide * wide_chunks;
+  if (block < wide_blocks) {
+    job = njobs + block / wide_chunks;
+    chunk = block % wide_chunks;
+  } else {
+    const int b = block - wide_blocks;
+    const int idx = b >> 3;
+    job = idx % njobs;
+    chunk = (b & 7) + 8 * (idx / njobs);
+  }
+}
+
 #ifdef NDP_STAMPS
 #define NDP_WSTAMP(i) do { if (threadIdx.x == 0) { wst[2 * (i)] = clock64(); wst[2 * (i) + 1] = wall_clock64(); } } while (0)
 #else
@@ -1577,17 +1593,8 @@ __device__ __forceinline__ void wgrad_fetch_args(WgradHead& a, WgradJob& jb, int
     asm volatile("s_load_dword %0, %5, 0x0\n\ts_load_dword %1, %5, 0x40\n\ts_load_dword %2, %5, 0x80\n\t"
                  "s_load_dword %3, %5, 0x4\n\ts_load_dword %4, %5, 0x8\n\ts_waitcnt lgkmcnt(0)"
                  : "=&s"(h0), "=&s"(h1), "=&s"(h2), "=&s"(hw0), "=&s"(hw1) : "s"(kp) : "memory");
-    const int njobs = (int)h0;                        // WgradHead::njobs, nwide, wide_chunks are the first three words
-    const int wide_blocks = (int)hw0 * (int)hw1;
-    if ((int)blockIdx.x < wide_blocks) {
-      job_id = njobs + (int)blockIdx.x / (int)hw1;
-      chunk = (int)blockIdx.x % (int)hw1;
-    } else {
-      const int b = (int)blockIdx.x - wide_blocks;
-      const int idx = b >> 3;
-      job_id = idx % njobs;
-      chunk = (b & 7) + 8 * (idx / njobs);
-    }
+    // WgradHead::njobs, nwide, wide_chunks are the first three words
+    wgrad_slot((int)h0, (int)hw0, (int)hw1, (int)blockIdx.x, job_id, chunk);
     const uint32_t joff = (uint32_t)(offsetof(WgradArgs, job) + (size_t)job_id * sizeof(WgradJob));
     uint32_t j0, j1;
     asm volatile("s_load_dword %0, %2, %3\n\ts_load_dword %1, %2, %4\n\ts_waitcnt lgkmcnt(0)"
@@ -1746,32 +1753,51 @@ __device__ __forceinline__ float p2p_sum(const P2PArgs& x, float g, int64_t p, b
   return s;
 }
 
-struct ReduceArgs {
-  const float* slabs; int nchunks; int64_t slab_stride; int64_t n;
-  // parameter ranges (whole layers) whose weight-gradient jobs wrote fewer slabs than nchunks
-  int nregions; int reg_begin[4], reg_end[4], reg_slabs[4];
-  P2PArgs p2p;
-  float* grad;                         // [n] or null
+// What every thread of k_reduce_adam needs: the first 136 bytes of its arguments, copied to scalar registers at entry.
+struct ReduceHot {
+  const float* slabs; int64_t slab_stride; int64_t n;
   float *params, *exp_avg, *exp_avg_sq;   // Adam (params null -> no update)
   const int32_t* step;                 // Adam state word (already advanced for this step)
-  float lr, beta1, beta2, eps;
-  LossTerm loss[3]; int nloss;
+  float* grad;                         // [n] or null
+  // parameter ranges (whole layers) whose weight-gradient jobs wrote fewer slabs than nchunks
+  int nchunks, nregions; int reg_begin[4], reg_end[4], reg_slabs[4];
+  float beta1, beta2, eps, lr;
+};
+struct ReduceArgs : ReduceHot {
+  // read where they are used: by the last block, behind the Adam arithmetic, by the exchanging instantiation
+  int nloss; LossTerm loss[3];
   float* losses; float* loss_sums;
   PackSpec pack;                       // lane-ordered copies to refresh with the new parameters
+  P2PArgs p2p;
 };
 
 __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v,
                                             float step_size, float bc2_sqrt, float b1, float b2, float eps) {
-  m = m + (g - m) * (1.f - b1);                 // exp_avg.lerp_(grad, 1 - beta1)
-  v = v * b2 + (1.f - b2) * g * g;              // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
+  // (the fused multiply-adds are written out: left to hipcc, which products it contracts depends on how the kernel
+  // around them is vectorised, and the update must give the same bits in every kernel that applies it)
+  m = __builtin_fmaf(g - m, 1.f - b1, m);                  // exp_avg.lerp_(grad, 1 - beta1)
+  v = __builtin_fmaf(v, b2, (1.f - b2) * g * g);           // exp_avg_sq.mul_(b2).addcmul_(g, g, 1 - b2)
   const float denom = sqrtf(v) / bc2_sqrt + eps;
-  p = p - step_size * (m / denom);              // param.addcdiv_(exp_avg, denom, -step_size)
+  p = __builtin_fmaf(-step_size, m / denom, p);            // param.addcdiv_(exp_avg, denom, -step_size)
 }
 
+// the loss fields of ReduceArgs, as they lie in it
+struct ReduceLossArgs { int nloss; LossTerm loss[3]; float* losses; float* loss_sums; };
+static_assert(offsetof(ReduceArgs, loss_sums) + sizeof(float*) - offsetof(ReduceArgs, nloss) == sizeof(ReduceLossArgs) &&
+              offsetof(ReduceArgs, loss) - offsetof(ReduceArgs, nloss) == offsetof(ReduceLossArgs, loss) &&
+              offsetof(ReduceArgs, losses) - offsetof(ReduceArgs, nloss) == offsetof(ReduceLossArgs, losses), "ReduceArgs: loss fields");
+
 template <bool P2P>
-__global__ __launch_bounds__(kThreads) void k_reduce_adam(ReduceArgs a) {
-  // (load_kernargs was tried here too: rocprofv3 averages 6.14 / 5.23 us against 5.51 / 5.45 us plain for the G / D
-  // launch -- every thread of 330 short-lived workgroups copying the struct costs more than the scalar misses do)
+__global__ __launch_bounds__(kThreads) void k_reduce_adam(ReduceArgs a_segment) {
+  // The kernel's whole body is one memory round trip, and hipcc reads a by-value argument where it is first used, each
+  // new cache line of the ~490-byte struct a scalar-cache miss of its own in front of that round trip.  So: one dword of
+  // every line is requested at entry (touch_kernargs: independent loads, one wait), the hot head is copied to scalar
+  // registers, and the cold parts are read where they are used -- pack behind the Adam arithmetic, the loss terms in the
+  // last block -- which then hit the scalar cache.
+  // (load_kernargs of the WHOLE struct was tried here: rocprofv3 averages 6.14 / 5.23 us against 5.51 / 5.45 us plain for
+  // the G / D launch -- every wave of 330 short-lived workgroups copying 490 bytes costs more than the misses do)
+  const uint64_t kv = touch_kernargs<P2P ? sizeof(ReduceArgs) : offsetof(ReduceArgs, p2p)>();
+  const ReduceHot a = read_kernargs<ReduceHot>(kv);
   __shared__ float sh[8];
   const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   const bool live = p < a.n;
@@ -1803,29 +1829,35 @@ __global__ __launch_bounds__(kThreads) void k_reduce_adam(ReduceArgs a) {
       for (int u = 0; u < NB; ++u) g += t[u];
     }
   }
-  if constexpr (P2P) g = p2p_sum(a.p2p, g, p, live, (uint32_t)a.step[0]);     // sum over ranks
+  if constexpr (P2P) g = p2p_sum(a_segment.p2p, g, p, live, (uint32_t)a.step[0]);     // sum over ranks
   if (live && a.grad != nullptr) a.grad[p] = g;
   if (upd) {
     adam_update(pv, g, m, v, step_size, bc2_sqrt, a.beta1, a.beta2, a.eps);
     a.params[p] = pv;
     a.exp_avg[p] = m;
     a.exp_avg_sq[p] = v;
-    if (a.pack.packed != nullptr) pack_store(a.pack, (int)p, pv);
+    uint64_t kp = kv;
+    asm volatile("" : "+s"(kp) : "v"(pv));            // behind the arithmetic
+    const PackSpec pack = read_kernargs<PackSpec>(kp + offsetof(ReduceArgs, pack));
+    if (pack.packed != nullptr) pack_store(pack, (int)p, pv);
   }
   // the loss scalars are the LAST block's job: the launch has one block more than the parameters need, so
   // this runs beside the parameter blocks instead of after one of them
   if (blockIdx.x == gridDim.x - 1) {
+    uint64_t kl = kv;
+    asm volatile("" : "+s"(kl));                      // inside the branch
+    const ReduceLossArgs c = read_kernargs<ReduceLossArgs>(kl + offsetof(ReduceArgs, nloss));
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
-      if (t >= a.nloss) break;
-      const LossTerm lt = a.loss[t];
+      if (t >= c.nloss) break;
+      const LossTerm lt = c.loss[t];
       float s = 0.f;
       for (int i = threadIdx.x; i < lt.count; i += kThreads) s += lt.partials[i];
       s = block_sum(s, sh + 4);
       if (threadIdx.x == 0) {
         s *= lt.scale;
-        a.losses[lt.slot] = s;
-        if (a.loss_sums != nullptr) a.loss_sums[lt.slot] += s;
+        c.losses[lt.slot] = s;
+        if (c.loss_sums != nullptr) c.loss_sums[lt.slot] += s;
       }
     }
   }
