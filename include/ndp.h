@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define NDP_VERSION 135          /* 0.3.2: ndp_fm_* (forward / next-frame model), ndp_fm_backward, ndp_fm_side_stream */
+#define NDP_VERSION 136          /* 0.3.2: ndp_fm_* (forward / next-frame model), ndp_fm_backward, ndp_fm_side_stream */
 
 #define NDP_OK            0
 #define NDP_E_ARG         1      /* bad argument (shape, alignment, null) */
@@ -414,16 +414,24 @@ int ndp_fm_train_grads_u8(const float *params, float *running_stats, const uint8
 int ndp_fm_side_stream(int on);
 /* Cross-rank BatchNorm statistics for a data-parallel driver.  The per-channel sums a BatchNorm needs are accumulated
  * by the kernel that produces its input as 64-bit fixed-point integers (csrc/ndp_forward_model.inc, "epilogue
- * statistics").  With a function set here, every ndp_fm_forward(training) / ndp_fm_train_grads / ndp_fm_backward call
- * invokes fn(acc, words, stream, ctx) on the calling thread between the launch that fills an accumulator and the launch
- * that reads it; fn must enqueue, on `stream`, an in-place SUM over the ranks of the `words` int64 values at `acc` (device
- * memory inside the workspace) -- an RCCL all-reduce of ncclInt64.  Integer sums are exact and order-free: `world` ranks
- * with B / world images each then normalise, and update the running statistics, exactly as one process with B images
- * does (the reference trains on one device: train_forward_model.py:62); the BatchNorm weight / bias gradients stay each
- * rank's own share, for the gradient all-reduce to add up.  20 small collectives per iteration.  fn == NULL: off (per-rank
- * statistics, what torch's DistributedDataParallel does without SyncBatchNorm).  Process-wide. */
+ * statistics").  A *_train_grads_dp call given such a function invokes fn(acc, words, stream, ctx) on the calling
+ * thread between the launch that fills an accumulator and the launch that reads it; fn must enqueue, on `stream`, an
+ * in-place SUM over the ranks of the `words` int64 values at `acc` (device memory inside the workspace) -- an RCCL
+ * all-reduce of ncclInt64.  Integer sums are exact and order-free: `world` ranks with B / world images each then
+ * normalise, and update the running statistics, exactly as one process with B images does (the reference trains on one
+ * device: train_forward_model.py:62); the BatchNorm weight / bias gradients stay each rank's own share, for the gradient
+ * all-reduce to add up.  fn == NULL: off (per-rank statistics, what torch's DistributedDataParallel does without
+ * SyncBatchNorm).  The function travels with the call: the library keeps no pointer to it once the call has returned. */
 typedef void (*ndp_fm_stat_sync_fn)(void *acc, int64_t words, void *stream, void *ctx);
-int ndp_fm_set_stat_sync(ndp_fm_stat_sync_fn fn, void *ctx, int world);
+/* Data parallel: ndp_fm_train_grads (frames_u8 == 0: float frames) or ndp_fm_train_grads_u8 (frames_u8 != 0) for one
+ * rank's share of a global batch -- the same launches, the same bits -- with the 10 BatchNorms' statistics summed over
+ * `world` ranks through stat_sync (10 forward + 10 backward calls: 20 small collectives per iteration).  stat_sync ==
+ * NULL or world == 1: this rank's statistics only (1 <= world <= 4096, else NDP_E_ARG and nothing launched).  No other
+ * ndp_fm_* entry point sums statistics over ranks: ndp_fm_forward / ndp_fm_backward(_inputs) take no function. */
+int ndp_fm_train_grads_dp(const float *params, float *running_stats, const void *frames_cur, const void *frames_fut,
+                          int frames_u8, const float *actions, int64_t n_images, float *grad, float *loss,
+                          float *loss_sum, float *resid_out, float *workspace, void *stream,
+                          ndp_fm_stat_sync_fn stat_sync, void *stat_ctx, int world);
 
 /* Gradient buckets for a data-parallel driver (the reference trains on one device: train_forward_model.py:62; the
  * north star asks for the all-reduce of the gradients "overlapped with backward").  ndp_fm_grad_buckets writes the 7
@@ -431,7 +439,7 @@ int ndp_fm_set_stat_sync(ndp_fm_stat_sync_fn fn, void *ctx, int world);
  * gradients come last layer first -- and returns 7.  Every ndp_fm_train_grads / ndp_fm_backward call records one event
  * per bucket where its last byte is written; ndp_fm_bucket_wait(b, stream) makes `stream` (the caller's communication
  * stream) wait for bucket b of the most recent such call on the current device, so that its all-reduce runs beside the
- * rest of the backward pass.  The buckets cover the whole vector exactly once. */
+ * rest of the backward pass (NDP_E_ARG before the first one).  The buckets cover the whole vector exactly once. */
 int ndp_fm_grad_buckets(int64_t *offsets, int64_t *counts, int capacity);
 int ndp_fm_bucket_wait(int bucket, void *stream);
 int ndp_fm_backward(const float *params, const float *d_resid, int64_t n_images, float *grad,
@@ -516,7 +524,7 @@ int ndp_ae_apply_adam(float *params, const float *grad, float *exp_avg, float *e
                       float *workspace, void *stream);
 /* Data parallel: ndp_ae_train_grads for one rank's share of a global batch, with
  *   - cross-rank BatchNorm statistics through the function given with THIS call (ndp_fm_stat_sync_fn: same contract as
- *     ndp_fm_set_stat_sync's, which this call never uses): the 8 BatchNorms call stat_sync(acc, words, stream, stat_ctx)
+ *     ndp_fm_train_grads_dp's): the 8 BatchNorms call stat_sync(acc, words, stream, stat_ctx)
  *     between the launch that fills an accumulator and the launch that reads it, 8 forward + 8 backward calls; the
  *     running statistics and dx come from the sums over the ranks, d gamma / d beta from this rank's own.
  *     stat_sync == NULL or world == 1: this rank's statistics only (1 <= world <= 4096);

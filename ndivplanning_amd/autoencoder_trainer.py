@@ -14,9 +14,8 @@ Data parallel (one rank's share of a global batch), as ForwardModelTrainer: `red
 between the two library calls, or `bucket_reduce` (dp.BucketedMeanAllReduce over ndp_ae_grad_buckets /
 ndp_ae_bucket_wait) does it per gradient bucket beside the rest of the backward pass; `sync_batchnorm_world` > 1 sums
 the BatchNorm statistics over the ranks (`stat_group`: their process group) through a callback passed with every
-ndp_ae_train_grads_dp call, so that W ranks with B / W images each train the step of one process with B images."""
-import ctypes
-
+ndp_ae_train_grads_dp call (FlatTrainer owns it), so that W ranks with B / W images each train the step of one process
+with B images."""
 import torch
 
 from . import _capi
@@ -36,19 +35,10 @@ class AutoencoderTrainer(FlatTrainer):
         dev = self.device
         if self.batch < 1 or self.lib.ndp_ae_workspace_floats(self.batch) <= 0:
             raise _capi.NdpError("AutoencoderTrainer: unsupported batch of %d images" % self.batch)
-        if int(sync_batchnorm_world) < 1:
-            raise ValueError("sync_batchnorm_world must be >= 1, got %r" % (sync_batchnorm_world,))
-        self.sync_world = int(sync_batchnorm_world)
-        self._allocate(IA.pack_autoencoder(encoder, decoder, dev), lr, betas, eps)
+        self._allocate(IA.pack_autoencoder(encoder, decoder, dev), lr, betas, eps, sync_batchnorm_world, stat_group)
         self.recon = torch.zeros(self.batch, 3, 128, 128, dtype=torch.float32, device=dev) if keep_reconstruction else None
         self.forwards = 0                                                    # training-mode forwards (num_batches_tracked)
         self._batches0 = int(encoder.conv1_bn.num_batches_tracked.item())
-        # cross-rank statistics: the callback and the ctypes thunk the library calls, alive until close()
-        self.stat_sync, self._stat_cb = None, None
-        if self.sync_world > 1:
-            from . import dp
-            self.stat_sync = dp.StatAllReduce(self.workspace, group=stat_group)
-            self._stat_cb = _capi.STAT_SYNC_FN(self.stat_sync)
         self._pack()
 
     def grads(self, images):
@@ -65,15 +55,11 @@ class AutoencoderTrainer(FlatTrainer):
                                                         p(self.loss), p(self.loss_sum), recon, p(self.workspace),
                                                         _capi.stream_ptr(self.device)), "ndp_ae_train_grads")
             else:
-                if self.sync_world > 1 and self._stat_cb is None:
-                    raise _capi.NdpError("AutoencoderTrainer: closed (its cross-rank statistics callback is released)")
-                fn = ctypes.cast(self._stat_cb, ctypes.c_void_p) if self._stat_cb is not None else None
                 _capi.check(self.lib.ndp_ae_train_grads_dp(p(self.params), p(self.stats), p(images), n, p(self.grad),
                                                            p(self.loss), p(self.loss_sum), recon, p(self.workspace),
-                                                           _capi.stream_ptr(self.device), fn, None, self.sync_world),
+                                                           _capi.stream_ptr(self.device), *self._stat_args()),
                             "ndp_ae_train_grads_dp")
-        if self.stat_sync is not None:
-            self.stat_sync.check()
+        self._stat_check()
         self.forwards += 1
         return self.loss
 
@@ -82,10 +68,6 @@ class AutoencoderTrainer(FlatTrainer):
         the mean over its own images)."""
         self.grads(images)
         return self._reduce_and_apply()
-
-    def close(self):
-        """Release the cross-rank statistics callback (if any); a closed data-parallel trainer refuses grads()."""
-        self.stat_sync, self._stat_cb = None, None
 
     def load_from_modules(self):
         """Take parameters and running statistics from the modules again (after they were changed from outside)."""

@@ -431,7 +431,7 @@ static int ae_forward_loss(hipStream_t st, const float* params, float* running, 
   fm_attrs();
   const FmWs& ws = aw.fm;
   const FmMaps m = ae_maps(aw);
-  const FmRun r = {st, kAeNet, m, ws, n, params, running, nullptr, sync};   // (sync: the caller's, never ndp_fm_set_stat_sync's)
+  const FmRun r = {st, kAeNet, m, ws, n, params, running, nullptr, sync};
   int rc;
   {
     // conv1's columns, and every statistics accumulator of the step zeroed (k_fm_image_cols without actions)
@@ -770,15 +770,7 @@ int ndp_ae_grad_buckets(int64_t* offsets, int64_t* counts, int capacity, int* n_
 }
 
 int ndp_ae_bucket_wait(int bucket, void* stream) {
-  using namespace ndp;
-  NDP_CHECK_ARG(bucket >= 0 && bucket < kAeBuckets, "ndp_ae_bucket_wait: bucket out of range");
-  int dev = -1;
-  NDP_CHECK_ARG(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices, "ndp_ae_bucket_wait: no current device");
-  FmBucketEvents& be = g_ae_buckets.dev[dev];
-  NDP_CHECK_ARG(be.recorded.load(), "ndp_ae_bucket_wait: no ndp_ae_train_grads_dp call has recorded the events on this device");
-  if (hipStreamWaitEvent((hipStream_t)stream, be.ev[bucket], 0) != hipSuccess)
-    return fail(NDP_E_LAUNCH, "ndp_ae_bucket_wait: hipStreamWaitEvent failed");
-  return NDP_OK;
+  return ndp::fm_bucket_wait(ndp::g_ae_buckets, ndp::kAeNet, bucket, stream, "ndp_ae_bucket_wait");
 }
 
 int ndp_ae_apply_adam(float* params, const float* grad, float* exp_avg, float* exp_avg_sq, int32_t* step_count, float lr,

@@ -1144,7 +1144,7 @@ __global__ __launch_bounds__(kThreads) void k_fm_bn_eval_stats(const float* runn
 //           the stored mean (the reference's value is rounding noise of its own); no further pass over the map.
 struct FmStatFin {
   const long long* acc; int replicas, what, P;       // acc == null: nothing to do (eval mode: mean / invstd are given)
-  const long long* acc_local;                        // cross-rank statistics (ndp_fm_set_stat_sync): acc holds the sums over ALL
+  const long long* acc_local;                        // cross-rank statistics (ndp_fm_stat_sync_fn): acc holds the sums over ALL
                                                      // ranks (P counts their pixels), acc_local this rank's -- what 2 writes
                                                      // d beta / d gamma / the bias gradient from the LOCAL sums (the gradient
                                                      // all-reduce adds the ranks' up), dx uses the global ones; null: acc
@@ -2385,16 +2385,15 @@ static void fm_ep_fill(FmStatEp& ep, const FmEpReq& rq, const FmWs& ws) {
   ep.acc = ws.stat_acc + fm_stat_offset_words(rq.slot);
   ep.x = rq.x.p; ep.x_ld = rq.x.ld; ep.y = rq.y.p; ep.y_ld = rq.y.ld; ep.mean = rq.mean; ep.invstd = rq.invstd;
 }
-// Cross-rank BatchNorm statistics (ndp_fm_set_stat_sync): between the launch that fills a BatchNorm's accumulator and the
+// Cross-rank BatchNorm statistics (ndp_fm_stat_sync_fn): between the launch that fills a BatchNorm's accumulator and the
 // launch that consumes it, the caller's function sums the accumulator over the ranks on the launch stream -- 64-bit
 // integers, so the sum is exact and the same on every rank in any order: W ranks with B / W images each then normalise
 // exactly as one process with B images does (SyncBatchNorm's semantics; the reference trains on one device).  The
 // backward sums are copied first: d beta / d gamma are written from this rank's own sums (the gradient all-reduce adds
 // the ranks' up), dx is computed with the global ones.
-// The descriptor travels with the call (FmBnAt::sync): the ndp_fm_* entry points pass the process-wide g_fm_sync, the
-// autoencoder's data-parallel entry point its own per-call one (ndp_autoencoder.inc); null: this rank's sums only.
+// The descriptor travels with the call (FmBnAt::sync): ndp_fm_train_grads_dp and ndp_ae_train_grads_dp build one on
+// their stack from their arguments, every other entry point passes null: this rank's sums only.
 struct FmStatSync { ndp_fm_stat_sync_fn fn; void* ctx; int world; };
-static FmStatSync g_fm_sync = {nullptr, nullptr, 1};
 static bool fm_sync_on(const FmStatSync* s) { return s != nullptr && s->fn != nullptr && s->world > 1; }
 static int fm_stat_sync(hipStream_t st, const FmWs& ws, int slot, const FmStatSync* sync) {
   if (!fm_sync_on(sync)) return NDP_OK;
@@ -2596,7 +2595,7 @@ static FmEpReq fm_ep_bias(int mode, int slot, FmView y) {
 }
 
 // Where BatchNorm b's tensors live in a network's flat vectors.  sync: where the statistics are summed over the ranks
-// (fm_stat_sync; null: this rank's own) -- the forward model's process-wide hook, the autoencoder's per-call one.
+// (fm_stat_sync; null: this rank's own) -- the function a *_train_grads_dp call was given.
 struct FmBnAt {
   const float* gamma; const float* beta; float* running_mean; float* running_var;
   float* d_gamma; float* d_beta; float* d_conv_bias;     // backward outputs (d_conv_bias: the bias of the layer in front)
@@ -2935,10 +2934,11 @@ static int fm_adam_pack(hipStream_t st, const FmNet& net, float* params, const f
 
 // forward pass up to the tanh output y2 (workspace); training: batch statistics (+ running update when running != null)
 static int fm_forward(hipStream_t st, const float* params, float* running, const void* cur, bool u8, const float* actions,
-                      int64_t n, int training, const FmWs& ws, bool clear_backward_too = false, const FmLossArgs* with_loss = nullptr) {
+                      int64_t n, int training, const FmWs& ws, const FmStatSync* sync, bool clear_backward_too = false,
+                      const FmLossArgs* with_loss = nullptr) {
   fm_attrs();
   const FmMaps m = fm_maps(ws);
-  const FmRun r = {st, kFmNet, m, ws, n, params, running, nullptr, &g_fm_sync};
+  const FmRun r = {st, kFmNet, m, ws, n, params, running, nullptr, sync};
   const int64_t npix = n * 16384;
   // (the refinement stage's 16-channel maps are stored unpadded, kFmR1LD, and y2 as 3 + 1 channels written by k_fm_r2_fwd)
   {
@@ -3046,8 +3046,8 @@ static void fm_bucket_range(const FmNet& net, int b, int64_t* offset, int64_t* c
     *count = fm_param_offset(net, net.bucket_end[b], false) - *offset;
   }
 }
-// One event per bucket, per device and network, created on first use.  `recorded`: set once a call has recorded all of
-// them (the autoencoder's ndp_ae_bucket_wait refuses before; the forward model does not look at it).
+// One event per bucket, per device and network, created on first use.  `recorded`: set once a pass has recorded all of
+// them (fm_bucket_wait refuses before).
 constexpr int kFmMaxBuckets = 8;
 struct FmBucketEvents { hipEvent_t ev[kFmMaxBuckets]; bool ok; std::atomic<bool> recorded; };
 struct FmBucketEventSet { FmBucketEvents dev[kMaxDevices]; std::once_flag once[kMaxDevices]; };
@@ -3063,6 +3063,18 @@ static FmBucketEvents* fm_bucket_events(FmBucketEventSet& set, const FmNet& net)
     for (int i = 0; i < n; ++i) be->ok = be->ok && hipEventCreateWithFlags(&be->ev[i], hipEventDisableTiming) == hipSuccess;
   });
   return be->ok ? be : nullptr;
+}
+// the body of ndp_fm_bucket_wait / ndp_ae_bucket_wait: `stream` waits for bucket `bucket` of the most recent pass on the
+// current device; `who`: the entry point, for its error strings
+static int fm_bucket_wait(FmBucketEventSet& set, const FmNet& net, int bucket, void* stream, const char* who) {
+  NDP_CHECK_ARG(bucket >= 0 && bucket < net.buckets, "%s: bucket out of range", who);
+  int dev = -1;
+  NDP_CHECK_ARG(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices, "%s: no current device", who);
+  FmBucketEvents& be = set.dev[dev];
+  NDP_CHECK_ARG(be.recorded.load(), "%s: no pass has recorded the bucket events on this device", who);
+  if (hipStreamWaitEvent((hipStream_t)stream, be.ev[bucket], 0) != hipSuccess)
+    return fail(NDP_E_LAUNCH, "%s: hipStreamWaitEvent failed", who);
+  return NDP_OK;
 }
 
 // conv1's data gradient (d_cur) and the action columns of dz (d_actions), either may be null: one launch behind the
@@ -3086,8 +3098,8 @@ static int fm_conv1_dgrad(const FmRun& r, bool ident, const float* d_out, float*
 // d_cur / d_actions (ndp_fm_backward_inputs, either may be null): the gradient with respect to the image through the
 // network alone and to the actions, one more launch on `st` behind the chain's last BatchNorm backward; `grad` and the
 // launches that produce it are the same with and without them.
-static int fm_backward(hipStream_t st, const float* params, int64_t n, float* grad, const FmWs& ws, bool cleared = false,
-                       float* d_cur = nullptr, float* d_actions = nullptr) {
+static int fm_backward(hipStream_t st, const float* params, int64_t n, float* grad, const FmWs& ws, const FmStatSync* sync,
+                       bool cleared = false, float* d_cur = nullptr, float* d_actions = nullptr) {
   FmSide* side = fm_side();
   hipStream_t sw = side ? side->stream : st;                        // where the weight gradients go
   FmBucketEvents* buckets = fm_bucket_events(g_fm_buckets, kFmNet);
@@ -3099,7 +3111,7 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
     }
   };
   const FmMaps m = fm_maps(ws);
-  const FmRun r = {st, kFmNet, m, ws, n, params, nullptr, grad, &g_fm_sync};
+  const FmRun r = {st, kFmNet, m, ws, n, params, nullptr, grad, sync};
   const int64_t npix = n * 16384;
   int rc;
   FmSlabPlan plan = fm_plan_new();
@@ -3195,6 +3207,7 @@ static int fm_backward(hipStream_t st, const float* params, int64_t n, float* gr
   if (buckets) {
     hipEventRecord(buckets->ev[5], st);
     hipEventRecord(buckets->ev[6], st);
+    buckets->recorded.store(true);
   }
   return NDP_OK;
 }
@@ -3330,7 +3343,7 @@ static int fm_forward_any(const float* params, float* running_stats, const void*
   hipStream_t st = (hipStream_t)stream;
   const FmWs ws = fm_ws(workspace, n_images);
   fm_eval_forget(workspace);
-  int rc = fm_forward(st, params, running_stats, state_cur, u8, actions, n_images, training, ws);
+  int rc = fm_forward(st, params, running_stats, state_cur, u8, actions, n_images, training, ws, nullptr);
   if (rc) return rc;
   if (!training) {
     rc = fm_loss(st, state_cur, nullptr, u8, n_images, 0, out, nullptr, nullptr, nullptr, ws);
@@ -3357,7 +3370,7 @@ int ndp_fm_forward_u8(const float* params, float* running_stats, const uint8_t* 
 
 static int fm_train_grads_any(const float* params, float* running_stats, const void* state_cur, const void* state_fut, bool u8,
                               const float* actions, int64_t n_images, float* grad, float* loss, float* loss_sum,
-                              float* resid_out, float* workspace, void* stream, const char* who) {
+                              float* resid_out, float* workspace, void* stream, const ndp::FmStatSync* sync, const char* who) {
   using namespace ndp;
   NDP_CHECK_ARG(params && state_cur && state_fut && actions && grad && loss && workspace && n_images >= 1, "%s: bad arguments", who);
   NDP_CHECK_ARG(n_images <= 8192, "%s: more than 8192 images per call", who);
@@ -3368,30 +3381,31 @@ static int fm_train_grads_any(const float* params, float* running_stats, const v
   const FmWs ws = fm_ws(workspace, n_images);
   const FmLossArgs la = fm_loss_args(state_cur, state_fut, u8, n_images, 1, resid_out, ws);
   fm_eval_forget(workspace);
-  int rc = fm_forward(st, params, running_stats, state_cur, u8, actions, n_images, 1, ws, true, &la);
+  int rc = fm_forward(st, params, running_stats, state_cur, u8, actions, n_images, 1, ws, sync, true, &la);
   if (rc) return rc;
   rc = fm_loss(st, state_cur, state_fut, u8, n_images, 1, resid_out, loss, loss_sum, grad, ws, true);
   if (rc) return rc;
-  return fm_backward(st, params, n_images, grad, ws, true);
+  return fm_backward(st, params, n_images, grad, ws, sync, true);
 }
 int ndp_fm_train_grads(const float* params, float* running_stats, const float* state_cur, const float* state_fut,
                        const float* actions, int64_t n_images, float* grad, float* loss, float* loss_sum, float* resid_out,
                        float* workspace, void* stream) {
   return fm_train_grads_any(params, running_stats, state_cur, state_fut, false, actions, n_images, grad, loss, loss_sum, resid_out,
-                            workspace, stream, "ndp_fm_train_grads");
+                            workspace, stream, nullptr, "ndp_fm_train_grads");
 }
 int ndp_fm_train_grads_u8(const float* params, float* running_stats, const uint8_t* frames_cur, const uint8_t* frames_fut,
                           const float* actions, int64_t n_images, float* grad, float* loss, float* loss_sum, float* resid_out,
                           float* workspace, void* stream) {
   return fm_train_grads_any(params, running_stats, frames_cur, frames_fut, true, actions, n_images, grad, loss, loss_sum, resid_out,
-                            workspace, stream, "ndp_fm_train_grads_u8");
+                            workspace, stream, nullptr, "ndp_fm_train_grads_u8");
 }
-
-int ndp_fm_set_stat_sync(ndp_fm_stat_sync_fn fn, void* ctx, int world) {
-  using namespace ndp;
-  NDP_CHECK_ARG(world >= 1 && world <= 4096, "ndp_fm_set_stat_sync: bad world size");
-  g_fm_sync.fn = fn; g_fm_sync.ctx = ctx; g_fm_sync.world = fn ? world : 1;
-  return NDP_OK;
+int ndp_fm_train_grads_dp(const float* params, float* running_stats, const void* frames_cur, const void* frames_fut, int frames_u8,
+                          const float* actions, int64_t n_images, float* grad, float* loss, float* loss_sum, float* resid_out,
+                          float* workspace, void* stream, ndp_fm_stat_sync_fn stat_sync, void* stat_ctx, int world) {
+  NDP_CHECK_ARG(world >= 1 && world <= 4096, "ndp_fm_train_grads_dp: bad world size");
+  const ndp::FmStatSync sync = {stat_sync, stat_ctx, world};
+  return fm_train_grads_any(params, running_stats, frames_cur, frames_fut, frames_u8 != 0, actions, n_images, grad, loss, loss_sum,
+                            resid_out, workspace, stream, ndp::fm_sync_on(&sync) ? &sync : nullptr, "ndp_fm_train_grads_dp");
 }
 
 int ndp_fm_grad_buckets(int64_t* offsets, int64_t* counts, int capacity) {
@@ -3402,13 +3416,7 @@ int ndp_fm_grad_buckets(int64_t* offsets, int64_t* counts, int capacity) {
 }
 
 int ndp_fm_bucket_wait(int bucket, void* stream) {
-  using namespace ndp;
-  NDP_CHECK_ARG(bucket >= 0 && bucket < kFmBuckets, "ndp_fm_bucket_wait: bucket out of range");
-  FmBucketEvents* be = fm_bucket_events(g_fm_buckets, kFmNet);
-  if (!be) return fail(NDP_E_LAUNCH, "ndp_fm_bucket_wait: could not create the bucket events");
-  if (hipStreamWaitEvent((hipStream_t)stream, be->ev[bucket], 0) != hipSuccess)
-    return fail(NDP_E_LAUNCH, "ndp_fm_bucket_wait: hipStreamWaitEvent failed");
-  return NDP_OK;
+  return ndp::fm_bucket_wait(ndp::g_fm_buckets, ndp::kFmNet, bucket, stream, "ndp_fm_bucket_wait");
 }
 
 int ndp_fm_side_stream(int on) {
@@ -3427,7 +3435,7 @@ int ndp_fm_backward(const float* params, const float* d_resid, int64_t n_images,
   fm_eval_forget(workspace);
   int rc = fm_loss(st, d_resid, nullptr, false, n_images, 3, nullptr, nullptr, nullptr, grad, ws);
   if (rc) return rc;
-  return fm_backward(st, params, n_images, grad, ws);
+  return fm_backward(st, params, n_images, grad, ws, nullptr);
 }
 
 int ndp_fm_backward_inputs(const float* params, const float* d_resid, int64_t n_images, float* grad, float* d_state_cur,
@@ -3441,7 +3449,7 @@ int ndp_fm_backward_inputs(const float* params, const float* d_resid, int64_t n_
   fm_eval_forget(workspace);
   int rc = fm_loss(st, d_resid, nullptr, false, n_images, 3, nullptr, nullptr, nullptr, grad, ws);
   if (rc) return rc;
-  return fm_backward(st, params, n_images, grad, ws, false, d_state_cur, d_actions);
+  return fm_backward(st, params, n_images, grad, ws, nullptr, false, d_state_cur, d_actions);
 }
 
 static int fm_rollout_link_args(ndp::fm_rollout::LinkArgs& a, const void* target, int target_u8, int64_t stride, int64_t n_images,

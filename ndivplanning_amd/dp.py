@@ -149,6 +149,8 @@ class StatAllReduce:
     """The body of a cross-rank statistics callback (include/ndp.h, ndp_fm_stat_sync_fn): called as
     fn(acc, words, stream, ctx) through a ctypes thunk (_capi.STAT_SYNC_FN(instance)), it all-reduces (SUM, int64: exact,
     order-free) the `words` accumulator values at `acc` -- inside `workspace`, the trainer's workspace tensor -- in place.
+    FlatTrainer passes the thunk with every ndp_fm_train_grads_dp / ndp_ae_train_grads_dp call: W ranks with B / W images
+    each then train the single-process step on B images (20 / 16 small collectives per iteration, on the critical path).
     Counts its calls; an exception inside a callback is kept and re-raised by `check()`."""
 
     def __init__(self, workspace, group=None):
@@ -172,32 +174,6 @@ class StatAllReduce:
         if self.error is not None:
             err, self.error = self.error, None
             raise RuntimeError("cross-rank BatchNorm statistics: %r" % (err,))
-
-
-class CrossRankBatchNorm(StatAllReduce):
-    """Forward-model BatchNorm statistics over ALL ranks' images (include/ndp.h, ndp_fm_set_stat_sync): the library calls
-    back between the launch that fills a BatchNorm's fixed-point accumulator and the launch that reads it, and this
-    all-reduces (SUM, int64: exact, order-free) the accumulator in place on the launch stream.  W ranks with B / W images
-    each then train exactly the single-process step on B images (up to fp32 summation order inside a tile): what the
-    reference's `batch_size` means.  20 small collectives per iteration, on the critical path.
-
-    `workspace`: the trainer's workspace tensor (the accumulators live inside it).  Process-wide while installed;
-    `close()` (or a new instance) removes it.  An exception inside a callback is kept and re-raised by `check()`."""
-
-    def __init__(self, workspace, world, group=None):
-        from . import _capi
-        super().__init__(workspace, group)
-        self._capi, self.lib = _capi, _capi.load()
-        self.world = int(world)
-        self._cb = _capi.STAT_SYNC_FN(self)                    # keep the thunk alive as long as it is installed
-        import ctypes
-        _capi.check(self.lib.ndp_fm_set_stat_sync(ctypes.cast(self._cb, ctypes.c_void_p), None, self.world),
-                    "ndp_fm_set_stat_sync")
-
-    def close(self):
-        if self._cb is not None:
-            self.lib.ndp_fm_set_stat_sync(None, None, 1)
-            self._cb = None
 
 
 def run_step(backend, reduce_fn, discrim_steps=1):

@@ -1,6 +1,9 @@
 """What ForwardModelTrainer (forward_trainer.py) and AutoencoderTrainer (autoencoder_trainer.py) share: one flat parameter
 vector that the kernels read, its gradient, Adam moments and running BatchNorm statistics on one GPU, the checks of what
-a step is given, and the reduce-then-apply tail of a step."""
+a step is given, the cross-rank BatchNorm statistics of a data-parallel driver (`sync_batchnorm_world` > 1: a callback
+passed with every *_train_grads_dp call, never installed anywhere), and the reduce-then-apply tail of a step."""
+import ctypes
+
 import torch
 
 from . import _capi
@@ -24,8 +27,12 @@ class FlatTrainer:
             raise ValueError("give either reduce_fn (one collective) or bucket_reduce (per-bucket, overlapped)")
         self.reduce_fn, self.bucket_reduce = reduce_fn, bucket_reduce
 
-    def _allocate(self, packed, lr, betas, eps):
-        """Buffers of a trainer on self.device for at most self.batch images; packed: (params, running_stats)."""
+    def _allocate(self, packed, lr, betas, eps, sync_batchnorm_world=1, stat_group=None):
+        """Buffers of a trainer on self.device for at most self.batch images; packed: (params, running_stats).
+        sync_batchnorm_world > 1: BatchNorm statistics summed over that many ranks (`stat_group`: their process group)."""
+        self.sync_world = int(sync_batchnorm_world)
+        if self.sync_world < 1:
+            raise ValueError("sync_batchnorm_world must be >= 1, got %r" % (sync_batchnorm_world,))
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         f32 = dict(dtype=torch.float32, device=self.device)
         self.params, self.stats = packed
@@ -36,6 +43,27 @@ class FlatTrainer:
         self.loss_sum = torch.zeros(1, **f32)
         self.workspace = torch.empty(getattr(self.lib, self._WORKSPACE_FN)(self.batch), **f32)
         self.steps = 0                                                               # Adam steps
+        # cross-rank statistics: the callback and the ctypes thunk the library calls, alive until close()
+        self.stat_sync, self._stat_cb = None, None
+        if self.sync_world > 1:
+            from . import dp
+            self.stat_sync = dp.StatAllReduce(self.workspace, group=stat_group)
+            self._stat_cb = _capi.STAT_SYNC_FN(self.stat_sync)
+
+    def _stat_args(self):
+        """(stat_sync, stat_ctx, world): the last three arguments of this trainer's *_train_grads_dp call."""
+        if self.sync_world > 1 and self._stat_cb is None:
+            raise _capi.NdpError("%s: closed (its cross-rank statistics callback is released)" % type(self).__name__)
+        return ctypes.cast(self._stat_cb, ctypes.c_void_p) if self._stat_cb is not None else None, None, self.sync_world
+
+    def _stat_check(self):
+        """After a pass: re-raise what a statistics callback raised inside it."""
+        if self.stat_sync is not None:
+            self.stat_sync.check()
+
+    def close(self):
+        """Release the cross-rank statistics callback (if any); a closed data-parallel trainer refuses grads()."""
+        self.stat_sync, self._stat_cb = None, None
 
     def _pack(self, workspace=None):
         """The second weight order the kernels read, rebuilt from .params in the head of a workspace (.workspace)."""

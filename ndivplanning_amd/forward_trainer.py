@@ -1,6 +1,6 @@
 """One iteration of the reference's forward-model training loop (train_forward_model.py:98-112) as gfx950 kernels:
 
-    state_fut_resid_hat = forward_autoencoder(state_cur, action)      ->  ndp_fm_train_grads   (forward, training-mode
+    state_fut_resid_hat = forward_autoencoder(state_cur, action)      ->  ndp_fm_train_grads_dp (forward, training-mode
     loss = mse(state_fut_resid_hat, state_fut - state_cur)                BatchNorm, MSE, backward: every gradient)
     optimizer.zero_grad(); loss.backward()
     optimizer.step()                                                   ->  ndp_fm_apply_adam
@@ -12,6 +12,9 @@ library calls -- is where a data-parallel driver all-reduces the gradient (SURVE
 the loss is a mean over the local batch, so the driver averages).  `bucket_reduce` (dp.BucketedMeanAllReduce) does the
 same per gradient bucket on a communication stream, each bucket as soon as the backward pass has completed it
 (ndp_fm_grad_buckets / ndp_fm_bucket_wait): the all-reduce runs beside the rest of the backward pass.
+`sync_batchnorm_world` > 1 sums the BatchNorm statistics over the ranks (`stat_group`: their process group) through a
+callback passed with every ndp_fm_train_grads_dp call (FlatTrainer), so that W ranks with B / W images each train the
+step of one process with B images; `close()` releases the callback.
 
 `rollout_steps=H` > 1 adds `grads_rollout` / `step_rollout`: the model is unrolled H steps on its
 own predictions over a window of H + 1 frames and trained on the mean of the H step losses through every path
@@ -29,23 +32,18 @@ class ForwardModelTrainer(FlatTrainer):
 
     def __init__(self, model: FE.ForwardAutoencoder, batch: int, lr: float = 2e-4, betas=(0.5, 0.999), eps: float = 1e-8,
                  reduce_fn=None, keep_residual: bool = False, bucket_reduce=None, sync_batchnorm_world: int = 1,
-                 rollout_steps: int = 1):
+                 rollout_steps: int = 1, stat_group=None):
         self.rollout_steps = int(rollout_steps)
         if self.rollout_steps < 1:
             raise ValueError("rollout_steps must be >= 1, got %r" % (rollout_steps,))
         if self.rollout_steps > 1 and (bucket_reduce is not None or int(sync_batchnorm_world) > 1):
-            # the bucket events are those of the most recent backward pass and the statistics hook is process-wide: both
-            # assume one pass per iteration
+            # the bucket events are those of the most recent backward pass (one pass per iteration), and the entry points
+            # a rollout is made of (ndp_fm_forward, ndp_fm_backward_inputs) take no statistics function
             raise ValueError("rollout_steps > 1 works with reduce_fn only: not with bucket_reduce or cross-rank BatchNorm")
         self.model = model
         self._place([model], "the model on a", batch, reduce_fn, bucket_reduce)
-        self._allocate(FE.pack_module(model, self.device), lr, betas, eps)
+        self._allocate(FE.pack_module(model, self.device), lr, betas, eps, sync_batchnorm_world, stat_group)
         self.resid = torch.zeros(self.batch, 3, 128, 128, dtype=torch.float32, device=self.device) if keep_residual else None
-        # BatchNorm statistics over all ranks' images (dp.CrossRankBatchNorm): W ranks x B / W images = one process x B
-        self.stat_sync = None
-        if int(sync_batchnorm_world) > 1:
-            from . import dp
-            self.stat_sync = dp.CrossRankBatchNorm(self.workspace, int(sync_batchnorm_world))
         self._pack()
         self._workspaces = [self.workspace]                          # pass k of a rollout keeps its activations in [k]
         self._extra_stale = False                                    # the extra workspaces' second weight order is behind
@@ -91,14 +89,12 @@ class ForwardModelTrainer(FlatTrainer):
         self._check(state_fut, shape, "state_fut", torch.uint8 if u8 else torch.float32)
         self._check(actions, (n, 4), "actions")
         p = _capi.ptr
-        fn, name = ((self.lib.ndp_fm_train_grads_u8, "ndp_fm_train_grads_u8") if u8
-                    else (self.lib.ndp_fm_train_grads, "ndp_fm_train_grads"))
         with torch.cuda.device(self.device):
-            _capi.check(fn(p(self.params), p(self.stats), p(state_cur), p(state_fut), p(actions), n,
-                           p(self.grad), p(self.loss), p(self.loss_sum), p(self.resid) if self.resid is not None else None,
-                           p(self.workspace), _capi.stream_ptr(self.device)), name)
-        if self.stat_sync is not None:
-            self.stat_sync.check()
+            _capi.check(self.lib.ndp_fm_train_grads_dp(
+                p(self.params), p(self.stats), p(state_cur), p(state_fut), int(u8), p(actions), n, p(self.grad), p(self.loss),
+                p(self.loss_sum), p(self.resid) if self.resid is not None else None, p(self.workspace),
+                _capi.stream_ptr(self.device), *self._stat_args()), "ndp_fm_train_grads_dp")
+        self._stat_check()
         return self.loss
 
     def step(self, state_cur, state_fut, actions):
@@ -163,12 +159,6 @@ class ForwardModelTrainer(FlatTrainer):
             return self.step(frames[:, 0].contiguous(), frames[:, 1].contiguous(), actions[:, 0].contiguous())
         self.grads_rollout(frames, actions)
         return self._reduce_and_apply()
-
-    def close(self):
-        """Remove the process-wide cross-rank statistics hook this trainer installed (if any)."""
-        if self.stat_sync is not None:
-            self.stat_sync.close()
-            self.stat_sync = None
 
     # intermediate maps of the last grads() call (tests, inspection): name -> (workspace tensor index, side, channels kept)
     _MAPS = {"feat1": (1, 64, 128, 64, 128), "up5": (1, 64, 128, 0, 64), "feat2": (2, 32, 256, 128, 256), "up4": (2, 32, 256, 0, 128),

@@ -135,6 +135,49 @@ def test_mean_all_reduce_of_the_forward_model_recipe(tmp_path):
     assert a["bounds"] == (0, 4) and b["bounds"] == (4, 8)
 
 
+def _stat_worker(rank, world, port):
+    sys.path.insert(0, ROOT)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    torch.set_num_threads(1)
+    from ndivplanning_amd import _capi, dp
+    dp.init_process_group(None)
+    ws = torch.arange(1, 65, dtype=torch.float32)                          # the "workspace": 64 floats, none of them zero
+    base = torch.tensor([1, -7, 2 ** 40 + 5, 2 ** 60, -2 ** 59, 12345], dtype=torch.int64)
+    ws[8:20].view(torch.int64).copy_(base * (rank + 1))                    # six int64 accumulators at byte offset 32
+    stat = dp.StatAllReduce(ws)
+    thunk = _capi.STAT_SYNC_FN(stat)                                       # what the library is given: fn(acc, words, stream, ctx)
+    at = ws.data_ptr()
+    assert at % 8 == 0
+    thunk(at + 32, 6, None, None)
+    stat.check()
+    assert stat.calls == 1 and torch.equal(ws[8:20].view(torch.int64), base * 3)          # exact beyond 2^53
+    thunk(at + 32, 3, None, None)                                          # the first three words again: 3 + 3
+    stat.check()
+    assert stat.calls == 2
+    assert torch.equal(ws[8:20].view(torch.int64), torch.cat([base[:3] * 6, base[3:] * 3]))
+    assert torch.equal(ws[:8], torch.arange(1, 9, dtype=torch.float32)) and torch.equal(ws[20:], torch.arange(21, 65, dtype=torch.float32))
+    before = ws.clone()
+    # an accumulator in front of, behind or running over the end of the workspace, and one that is not 8-byte aligned: kept
+    # for check(), nothing reduced (a sum over the two ranks would change every value here: none is zero)
+    for acc, words in ((at - 8, 1), (at + 256, 1), (at + 256 - 40, 6), (at + 36, 4)):
+        thunk(acc, words, None, None)
+        with pytest.raises(RuntimeError, match="cross-rank BatchNorm statistics"):
+            stat.check()
+        stat.check()                                                       # raised once, then cleared
+        assert stat.calls == 2 and torch.equal(ws.view(torch.int32), before.view(torch.int32))    # (bits: some are NaNs)
+    thunk(at + 32, 6, None, None)                                          # still usable, and the ranks are still in step
+    stat.check()
+    assert stat.calls == 3 and torch.equal(ws[8:20].view(torch.int64), torch.cat([base[:3] * 12, base[3:] * 6]))
+    dist.destroy_process_group()
+
+
+def test_stat_all_reduce_through_its_thunk_sums_int64_in_place_and_refuses_foreign_pointers():
+    """dp.StatAllReduce as the library calls it (a _capi.STAT_SYNC_FN thunk: acc pointer, word count, stream, ctx) on a CPU
+    workspace with two gloo ranks: the int64 sum is exact and in place, `calls` counts the reductions, and an accumulator
+    outside the workspace or misaligned raises from check() without any collective.  Needs neither the library nor a GPU."""
+    mp.spawn(_stat_worker, args=(2, _free_port()), nprocs=2, join=True)
+
+
 def _lockstep_worker(rank, world, port, out_dir):
     sys.path.insert(0, ROOT)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))

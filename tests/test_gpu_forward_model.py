@@ -501,7 +501,7 @@ def _syncbn_rank(rank, world, port, out_dir):
 
 
 def test_cross_rank_batchnorm_gives_the_global_batch_gradient(tmp_path):
-    """ndp_fm_set_stat_sync / dp.CrossRankBatchNorm at the gradient level: two ranks with 2 images each -- every BatchNorm's
+    """ndp_fm_train_grads_dp / dp.StatAllReduce at the gradient level: two ranks with 2 images each -- every BatchNorm's
     fixed-point accumulator all-reduced as int64 between the kernel that fills it and the kernel that reads it (10 forward
     + 10 backward callbacks per rank), d beta / d gamma from each rank's own sums, dx from the global ones -- then the mean
     of the two flat gradients, against ONE process on the 4 images: same loss, same running statistics, every gradient
@@ -559,6 +559,97 @@ def test_gradient_buckets_cover_the_flat_vector_in_completion_order():
     torch.cuda.synchronize(DEV)
     want = [tr.grad[o:o + c].double().abs().sum().item() for o, c in buckets]
     assert [s_.item() for s_ in sums] == want and all(w > 0 for w in want)
+
+
+def test_train_grads_dp_without_a_function_is_train_grads_bit_for_bit():
+    """ndp_fm_train_grads_dp(stat_sync=NULL, world=1) against ndp_fm_train_grads (float frames) and ndp_fm_train_grads_u8
+    (byte frames, frames_u8=1): the same launches, so the same bits in grad, loss, running statistics and residual.  A world
+    size outside 1..4096 is NDP_E_ARG and launches nothing."""
+    from ndivplanning_amd import _capi
+    lib, p = _capi.load(), _capi.ptr
+    tr, _ = _hip_trainer(5, 2, keep_residual=True)
+    frames, actions = _inputs(11, 2)
+    act = actions[:, 0].contiguous().to(DEV)
+    f32 = [frames[:, i].contiguous().to(DEV) for i in (0, 1)]
+    u8 = [((f.permute(0, 2, 3, 1) + 1.0) * 127.5).round().clamp(0, 255).to(torch.uint8).contiguous() for f in f32]
+    stats0 = tr.stats.clone()
+
+    def run(name, cur, fut, *dp):
+        tr.stats.copy_(stats0)
+        for t in (tr.grad, tr.loss, tr.resid):
+            t.zero_()
+        flag = [int(cur.dtype == torch.uint8)] if dp else []
+        with torch.cuda.device(DEV):
+            rc = getattr(lib, name)(p(tr.params), p(tr.stats), p(cur), p(fut), *flag, p(act), 2, p(tr.grad), p(tr.loss), None,
+                                    p(tr.resid), p(tr.workspace), _capi.stream_ptr(DEV), *dp)
+        torch.cuda.synchronize(DEV)
+        return rc, [t.clone() for t in (tr.grad, tr.loss, tr.stats, tr.resid)]
+    for name, (cur, fut) in (("ndp_fm_train_grads", f32), ("ndp_fm_train_grads_u8", u8)):
+        rc, want = run(name, cur, fut)
+        assert rc == 0 and float(want[0].abs().sum()) > 0 and not torch.equal(want[2], stats0)
+        rc, got = run("ndp_fm_train_grads_dp", cur, fut, None, None, 1)
+        assert rc == 0
+        for g, w, what in zip(got, want, ("grad", "loss", "running_stats", "resid_out")):
+            assert torch.equal(g, w), (name, what)
+    for world in (0, 4097):
+        rc, got = run("ndp_fm_train_grads_dp", f32[0], f32[1], None, None, world)
+        assert rc == 1 and b"ndp_fm_train_grads_dp" in lib.ndp_last_error()              # NDP_E_ARG
+        assert not got[0].any() and not got[1].any() and not got[3].any() and torch.equal(got[2], stats0)
+
+
+def _isolation_child(rank, port):
+    import gc
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1",
+                      NDP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import torch.distributed as dist
+    from ndivplanning_amd import _capi, dp
+    from ndivplanning_amd.models import forward_encoder as FE
+    lib = _capi.load()
+    with torch.cuda.device(DEV):
+        assert lib.ndp_fm_bucket_wait(0, _capi.stream_ptr(DEV)) == 1                     # NDP_E_ARG: no pass yet
+    assert b"ndp_fm_bucket_wait" in lib.ndp_last_error()
+    dp.init_process_group(DEV, force=True)
+    frames, actions = _inputs(7, 2)
+    cur, fut, act = (t.contiguous().to(DEV) for t in (frames[:, 0], frames[:, 1], actions[:, 0]))
+    B, state = _hip_trainer(3, 2)
+    B.grads(cur, fut, act)
+    g0, loss0 = B.grad.clone(), B.loss.clone()
+    A, _ = _hip_trainer(3, 2, sync_batchnorm_world=2)
+    A.grads(cur, fut, act)
+    stat = A.stat_sync
+    assert stat.calls == 20
+    B.grads(cur, fut, act)                                     # another trainer in the process: never through A's function
+    assert torch.equal(B.grad, g0) and torch.equal(B.loss, loss0) and stat.calls == 20
+    model = FE.ForwardAutoencoder()                            # the module's autograd path (ndp_fm_forward / ndp_fm_backward)
+    model.load_state_dict(state)
+    model = model.to(DEV).train()
+    torch.nn.functional.mse_loss(model(cur, act), fut - cur).backward()
+    assert model.encoder.conv1.weight.grad is not None and stat.calls == 20
+    A.close()
+    with pytest.raises(_capi.NdpError):
+        A.grads(cur, fut, act)
+    del A, stat
+    gc.collect()
+    B.grads(cur, fut, act)                                     # nothing dangles behind a trainer that is gone
+    assert torch.equal(B.grad, g0)
+    torch.cuda.synchronize(DEV)
+    dist.destroy_process_group()
+
+
+def test_cross_rank_statistics_stay_with_the_trainer_that_asked_for_them():
+    """The statistics function travels with ndp_fm_train_grads_dp calls of ONE trainer: a plain trainer and the module's
+    autograd path in the same process never call it, a closed trainer refuses, and after the trainer is collected the
+    library holds no pointer to it.  ndp_fm_bucket_wait before any backward pass has nothing to wait for.  One child
+    process with a one-rank gloo group."""
+    import socket
+    import torch.multiprocessing as mp
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    mp.spawn(_isolation_child, args=(port,), nprocs=1, join=True)
 
 
 def test_the_reference_loop_unchanged_module_forward_loss_backward_torch_adam():
