@@ -456,6 +456,33 @@ int ndp_fm_apply_adam(float *params, const float *grad, float *exp_avg, float *e
 int ndp_fm_input_grads(const float *params, const float *d_out, int64_t n_images,
                        float *d_state_cur, float *d_actions, float *workspace, void *stream);
 
+/* The eval-mode pass with a choice of operand precision (the planner's passes: it ranks sampled rollouts by a pixel MSE
+ * and tolerates operand rounding; training and every other entry point stay fp32).
+ *   NDP_FM_FP32  the launches and the bits of ndp_fm_forward / ndp_fm_forward_u8 (training == 0); lp_weights may be NULL.
+ *   NDP_FM_BF16  changes exactly this: layers 1..4 and 7..11 (conv2..conv5, deconv2..deconv6: the stride-2 layers, 99 % of
+ *                the multiplications) compute  out = act(bias + sum bf16(x) * bf16(w))  where bf16(.) rounds fp32 to bf16
+ *                to nearest even (NaN stays NaN, overflow goes to +-Inf), a product of two bf16 values is exact in fp32,
+ *                and the sum is accumulated in fp32 (the accumulator of v_mfma_f32_16x16x32_bf16; K-split partial sums and
+ *                their reduction stay fp32).  Bias, activation, BatchNorm with the running statistics, the skip
+ *                concatenations and every stored map stay fp32 -- the workspace layout is unchanged -- and conv1, conv6,
+ *                deconv1 and the refinement stage keep their fp32 kernels.  The activations are rounded where a kernel
+ *                stages them; the weights are rounded ONCE: ndp_fm_pack_params_lp writes, into a caller-owned buffer of
+ *                ndp_fm_lp_weight_bytes() bytes (16-byte aligned), the bf16 copy of the weight order each of the nine
+ *                layers' forward launch reads (a convolution's first, a transposed convolution's second), one launch.
+ *                It reads `params` and the second weight order in the workspace head, so it follows ndp_fm_pack_params
+ *                / ndp_fm_apply_adam on the same stream whenever the parameters change.
+ * Exactly one of state_cur (float [n,3,128,128]) and frames_u8 (bytes [n][128][128][3]) is given.  Any other precision,
+ * NDP_FM_BF16 without lp_weights, both or neither image pointer: NDP_E_ARG, nothing launched.  A bf16 pass leaves no
+ * activations that ndp_fm_input_grads may consume: after it that call returns NDP_E_UNSUPPORTED and launches nothing.
+ * Two passes on the same inputs give the same bits (fixed-order sums, as everywhere). */
+#define NDP_FM_FP32 0
+#define NDP_FM_BF16 1
+int64_t ndp_fm_lp_weight_bytes(void);
+int ndp_fm_pack_params_lp(const float *params, const float *workspace, void *lp_weights, void *stream);
+int ndp_fm_forward_lp(const float *params, const float *running_stats, const float *state_cur,
+                      const uint8_t *frames_u8, const float *actions, int64_t n_images, int precision,
+                      const void *lp_weights, float *out, float *workspace, void *stream);
+
 /* ndp_fm_backward with the gradient of the TRAINING-mode pass with respect to its inputs as well: the same precondition
  * (a training-mode ndp_fm_forward on this workspace came first), the same launches and bit for bit the same `grad`, plus
  * d_state_cur [n,3,128,128] (or NULL) = d loss / d state_cur through the network alone -- the training-mode output is

@@ -125,6 +125,10 @@ SIGNATURES = {
     "ndp_fm_bucket_wait": (c_int, [c_int, c_void_p]),
     "ndp_fm_backward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "ndp_fm_input_grads": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ndp_fm_lp_weight_bytes": (c_int64, []),
+    "ndp_fm_pack_params_lp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ndp_fm_forward_lp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
     "ndp_fm_apply_adam": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                                   c_void_p, c_void_p]),
     "ndp_fm_backward_inputs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -11,6 +11,26 @@ from . import _capi
 from . import jpeg as jpeg_frames
 
 OUTPUTS = ("float", "bytes")
+FM_PRECISIONS = ("fp32", "bf16")    # NDP_FM_FP32, NDP_FM_BF16 (include/ndp.h): the operand precision of an eval-mode pass
+
+
+def fm_precision_code(name):
+    """'fp32' / 'bf16' -> NDP_FM_FP32 / NDP_FM_BF16; anything else is a ValueError that lists the two names."""
+    if not isinstance(name, str) or name not in FM_PRECISIONS:
+        raise ValueError("fm_precision must be 'fp32' or 'bf16', got %r" % (name,))
+    return FM_PRECISIONS.index(name)
+
+
+def fm_precision_of(config):
+    """The forward model's operand precision for an evaluation script: --fm-precision (a top-level key, as every command
+    line argument becomes one), else the config's `evaluation.fm_precision`, else 'fp32'.  Checked."""
+    name = config.get("fm_precision") if hasattr(config, "get") else None
+    if name is None:
+        ev = config.get("evaluation") if hasattr(config, "get") else None
+        name = ev.get("fm_precision") if ev is not None and hasattr(ev, "get") else None
+    name = "fp32" if name is None else name
+    fm_precision_code(name)
+    return name
 
 
 def _check_out(out):

@@ -16,6 +16,8 @@
 //               1 / 2 / 2 / 4 taps; the 4x4 <-> 1x1 layers are sixteen one-tap classes;
 //   k_fm_wgrad  dW[j][tap][k] = sum over pixels m  dense[m][j] . gathered[pixel(m) + tap][k]
 //               -- every weight gradient (rows = the reduction, both operands read along channels, as k_wgrad).
+// (The eval-mode pass can run its nine stride-2 layers with bf16 operands instead -- k_fm_gemm_bf16, k_fm_deconv32_bf16,
+// ndp_fm_forward_lp with NDP_FM_BF16 -- which changes nothing of what follows: every stored map stays fp32.)
 // Activations are NHWC with an explicit pixel stride, so that cat([up, skip]) is never copied: the decoder's BatchNorm
 // + ReLU writes the lower channels of the next layer's input map, the encoder's writes the upper ones; their gradients
 // come back the same way (the encoder's data gradients accumulate onto the skip halves).  Channel counts that are not
@@ -75,6 +77,11 @@ static const FmLabels kFmLabels[kFmLayers] = {
     FM_LABELS("conv1"), FM_LABELS("conv2"), FM_LABELS("conv3"), FM_LABELS("conv4"), FM_LABELS("conv5"), FM_LABELS("conv6"),
     FM_LABELS("deconv1"), FM_LABELS("deconv2"), FM_LABELS("deconv3"), FM_LABELS("deconv4"), FM_LABELS("deconv5"),
     FM_LABELS("deconv6"), FM_LABELS("refine1"), FM_LABELS("refine2")};
+#define FM_LP_LABEL(name) "k_fm_gemm_bf16[" name "]"
+static const char* const kFmLpLabel[kFmLayers] = {                      // forward launches with bf16 operands (fm_lp_layer)
+    nullptr, FM_LP_LABEL("conv2"), FM_LP_LABEL("conv3"), FM_LP_LABEL("conv4"), FM_LP_LABEL("conv5"), nullptr, nullptr,
+    FM_LP_LABEL("deconv2"), FM_LP_LABEL("deconv3"), FM_LP_LABEL("deconv4"), FM_LP_LABEL("deconv5"), FM_LP_LABEL("deconv6"),
+    nullptr, nullptr};
 // Gradient buckets for a data-parallel driver (SURVEY.md section 8e / 8f-4: "RCCL all-reduce ... overlapped with backward"):
 // ranges of the flat gradient in the order in which the backward pass completes them.  The weight gradients are produced
 // last layer first, so the range of layers 9..13 is final while the data-gradient chain is still at deconv3; one event per
@@ -140,6 +147,16 @@ static int64_t fm_p2_floats(const FmNet& net, int l) {
 static int64_t fm_p2_offset(const FmNet& net, int l) {
   int64_t o = 0;
   for (int i = 0; i < l; ++i) o += fm_p2_floats(net, i);
+  return o;
+}
+// The layers that precision NDP_FM_BF16 runs with bf16 operands: the stride-2 3x3 convolutions behind the first and the
+// stride-2 4x4 transposed convolutions (kFm: 1..4 and 7..11, 99 % of the multiplications).  The bf16 weight buffer holds,
+// layer after layer, the weight order each one's forward launch reads (a convolution P1, a transposed convolution P2),
+// element for element: fm_w_floats values of 2 bytes each.
+static bool fm_lp_layer(const FmNet& net, int l) { return net.layer[l].p2 == FM_P2_CONV_S2 || net.layer[l].p2 == FM_P2_DECONV_S2; }
+static int64_t fm_lp_offset(const FmNet& net, int l) {
+  int64_t o = 0;
+  for (int i = 0; i < l; ++i) o += fm_lp_layer(net, i) ? fm_w_floats(net, i) : 0;
   return o;
 }
 
@@ -516,6 +533,210 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
   fm_stat_publish(a.ep, cls * a.mtiles + m_tile, n_tile * BN, BN, sums);
 }
 
+// ------------------------------------------------------------------------------------------ k_fm_gemm_bf16
+// k_fm_gemm with bf16 MFMA operands (precision NDP_FM_BF16 of the eval-mode pass; the definition is in include/ndp.h):
+// out = act(bias + sum bf16(x) . bf16(w)), the products exact and the sum in fp32 in the accumulator of
+// v_mfma_f32_16x16x32_bf16.  Same FmGemmArgs (a.w carries the address of the layer's bf16 weights, rounded once by
+// k_fm_pack_lp), same tiles, XCD order, K split and K steps of 32, same epilogue (only modes 0 and 1 and no statistics are
+// ever asked of it: the eval-mode pass has none).  What differs is the operand path:
+//   A tile  the gathered fp32 activations are rounded to nearest even where they are staged (v_cvt_pk_bf16_f32: NaN stays
+//           NaN, overflow goes to +-Inf), 8 bytes per 4 values into a bf16 LDS tile;
+//   B tile  8 bytes per 4 values from the bf16 copy, stored as they come;
+//   read    one 16-byte LDS read per lane and 32-wide K step: lane l = 16 q + c holds k = 8 q .. 8 q + 7 of row c, for both
+//           operands; the weights go in as the A operand and the pixels as B, so that, as in k_fm_gemm, a lane ends up
+//           with output pixel c and the four columns 4 q .. 4 q + 3 (the C/D layout does not depend on the operand type).
+// LDS row stride: 48 bf16 = 96 bytes for 64 bytes of data.  A ds_read_b128 is served in four groups of 16 lanes, each
+// 8 rows at one q and the other 8 rows at q + 1 (lanes {0-3, 12-15, 20-27}, ...), over 16 slots of 16 bytes (256 bytes of
+// banks).  With a row stride of s slots a lane's slot is (s * row + q) mod 16: s = 4 (unpadded) puts 4 rows on a slot;
+// an odd s (80 bytes) spreads the 16 rows over all 16 slots, so the 8 reads at q + 1 must land on slots of the other 8:
+// 2-way for 3 of them; s = 6 sends any 8 consecutive rows to the 8 even slots and the rows at q + 1 to the odd ones:
+// conflict-free, which s = 2 (smaller than a row) is the only smaller stride to do.  (Measured: no conflict cycle from the
+// reads; the 8-byte staging stores, two consecutive rows per 16-lane group and banked modulo 128 bytes, are 2-way: DESIGN 5s.)
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+constexpr int kFmLpLD = 48;
+template <int BN> constexpr int fm_gemm_bf16_lds_bytes() { return 2 * (kFmBM + BN) * kFmLpLD * 2; }
+__device__ __forceinline__ uint32_t fm_bf16_pair(float lo, float hi) {
+  const bf16x2 v = {(__bf16)lo, (__bf16)hi};                           // fptrunc: round to nearest even (v_cvt_pk_bf16_f32)
+  return __builtin_bit_cast(uint32_t, v);
+}
+
+template <int BN>
+__global__ __launch_bounds__(kThreads, 2) void k_fm_gemm_bf16(FmGemmArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t smem_lp[];
+  constexpr int BM = kFmBM, BK = kFmBK, LD = kFmLpLD;
+  constexpr int TI = BN == 128 ? 4 : 2, TJ = BN == 128 ? 4 : 2;
+  int n_tile, m_tile;                                                  // (k_fm_gemm's order)
+  if (a.mtiles >= 8) {
+    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
+    n_tile = jb % a.ntiles;
+    m_tile = (jb / a.ntiles) * 8 + xcd;
+    if (m_tile >= a.mtiles) return;
+  } else {
+    n_tile = blockIdx.x % a.ntiles;
+    m_tile = blockIdx.x / a.ntiles;
+  }
+  const int split = blockIdx.y, cls = blockIdx.z;
+  const FmClass kc = fm_class(a, cls);
+  const int ksteps = kc.KH * kc.KW * a.C / BK;
+  const int sbeg = split * a.steps_per_split;
+  const int send = sbeg + a.steps_per_split < ksteps ? sbeg + a.steps_per_split : ksteps;
+  const int K = kc.KH * kc.KW * a.C;
+  const uint16_t* wcls = reinterpret_cast<const uint16_t*>(a.w) + kc.w_off;
+
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int c = lane & 15, q = lane >> 4;
+  const int row0 = BN == 128 ? (wave >> 1) * 64 : wave * 32, col0 = BN == 128 ? (wave & 1) * 64 : 0;
+
+  constexpr int QPR = BK / 4, RPP = kThreads / QPR, NUA = BM / RPP, NUB = BN / RPP;
+  const int r0 = t / QPR, kq = t % QPR;
+  const float* a_img[NUA];
+  int a_y0[NUA], a_x0[NUA];
+#pragma unroll
+  for (int u = 0; u < NUA; ++u) {
+    int m = m_tile * BM + r0 + RPP * u;
+    const bool valid = m < a.M;
+    m = valid ? m : a.M - 1;
+    const int img = m / (a.GH * a.GW), rem = m - img * (a.GH * a.GW);
+    const int y = rem / a.GW, x = rem - y * a.GW;
+    a_img[u] = a.src + (size_t)img * a.SH * a.SW * a.src_ld + 4 * kq;
+    a_y0[u] = valid ? y * a.ss - kc.pad_y : -(1 << 20);               // rows past M: every tap out of bounds -> zeros
+    a_x0[u] = x * a.ss - kc.pad_x;
+  }
+  const uint16_t* b_row[NUB];
+  bool b_ok[NUB];
+#pragma unroll
+  for (int u = 0; u < NUB; ++u) {
+    const int n = n_tile * BN + r0 + RPP * u;
+    b_ok[u] = n < a.N;
+    b_row[u] = wcls + (size_t)(b_ok[u] ? n : a.N - 1) * K + 4 * kq;
+  }
+  f32x4 ra[NUA];
+  u32x2 rb[NUB];
+  bool ra_ok[NUA];
+  auto fetch = [&](int step) {
+    const int k0 = step * BK;
+    const int tap = k0 / a.C, ci0 = k0 - tap * a.C;                    // uniform: one tap, 32 consecutive channels
+    const int kh = tap / kc.KW, kw = tap - kh * kc.KW;
+#pragma unroll
+    for (int u = 0; u < NUA; ++u) {
+      const int yy = a_y0[u] + kh, xx = a_x0[u] + kw;
+      const bool ok = (unsigned)yy < (unsigned)a.SH && (unsigned)xx < (unsigned)a.SW;
+      ra[u] = ldg4<4>(a_img[u] + (ok ? (size_t)(yy * a.SW + xx) * a.src_ld + ci0 : 0));
+      ra_ok[u] = ok;
+    }
+#pragma unroll
+    for (int u = 0; u < NUB; ++u) rb[u] = *reinterpret_cast<const u32x2*>(b_row[u] + k0);
+    pin_vmem();
+  };
+  auto stage = [&](int buf) {
+    uint16_t* As = smem_lp + buf * (BM + BN) * LD;
+    uint16_t* Bs = As + BM * LD;
+#pragma unroll
+    for (int u = 0; u < NUA; ++u) {
+      const u32x2 v = {fm_bf16_pair(ra[u][0], ra[u][1]), fm_bf16_pair(ra[u][2], ra[u][3])};
+      *reinterpret_cast<u32x2*>(As + (r0 + RPP * u) * LD + 4 * kq) = ra_ok[u] ? v : u32x2{0u, 0u};
+    }
+#pragma unroll
+    for (int u = 0; u < NUB; ++u)
+      *reinterpret_cast<u32x2*>(Bs + (r0 + RPP * u) * LD + 4 * kq) = b_ok[u] ? rb[u] : u32x2{0u, 0u};
+  };
+
+  f32x4 acc[TI][TJ];
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int jn = 0; jn < TJ; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  if (sbeg < send) {
+    fetch(sbeg);
+    stage(0);
+  }
+  __syncthreads();
+  int buf = 0;
+  for (int step = sbeg; step < send; ++step) {
+    const bool more = step + 1 < send;
+    if (more) fetch(step + 1);
+    const uint16_t* As = smem_lp + buf * (BM + BN) * LD + (row0 + c) * LD + 8 * q;
+    const uint16_t* Bs = smem_lp + buf * (BM + BN) * LD + BM * LD + (col0 + c) * LD + 8 * q;
+    bf16x8 af[TI], bf[TJ];
+#pragma unroll
+    for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const bf16x8*>(As + i * 16 * LD);
+#pragma unroll
+    for (int jn = 0; jn < TJ; ++jn) bf[jn] = *reinterpret_cast<const bf16x8*>(Bs + jn * 16 * LD);
+#pragma unroll
+    for (int i = 0; i < TI; ++i)
+#pragma unroll
+      for (int jn = 0; jn < TJ; ++jn)
+        acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[jn], af[i], acc[i][jn], 0, 0, 0);   // transposed tiles
+    pin_vmem();
+    if (more) stage(buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // k_fm_gemm's epilogue without the statistics: a lane holds output pixel c and the columns 4q .. 4q+3 of each tile
+  const bool fin = a.nsplit == 1;
+  f32x4 bias4[TJ];
+  int colj[TJ];
+#pragma unroll
+  for (int jn = 0; jn < TJ; ++jn) {
+    bias4[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+    colj[jn] = n_tile * BN + col0 + jn * 16 + 4 * q;
+    if (fin && a.bias != nullptr && colj[jn] < a.N) bias4[jn] = *reinterpret_cast<const f32x4*>(a.bias + colj[jn]);
+  }
+#pragma unroll
+  for (int i = 0; i < TI; ++i) {
+    const int m = m_tile * BM + row0 + i * 16 + c;
+    if (m >= a.M) continue;
+    const size_t pix = fm_out_pixel_index(a, kc, m);
+    float* orow = fin ? a.out + pix * a.out_ld : a.part + ((size_t)(cls * a.nsplit + split) * a.M + m) * a.N;
+    f32x4 prev[TJ];
+#pragma unroll
+    for (int jn = 0; jn < TJ; ++jn) {
+      prev[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (fin && a.accumulate && colj[jn] < a.N) prev[jn] = *reinterpret_cast<const f32x4*>(orow + colj[jn]);
+    }
+#pragma unroll
+    for (int jn = 0; jn < TJ; ++jn) {
+      const int col = colj[jn];
+      if (col >= a.N) {                                                // N is a multiple of 4
+        if (fin && col < a.zero_to) *reinterpret_cast<f32x4*>(orow + col) = f32x4{0.f, 0.f, 0.f, 0.f};
+        continue;
+      }
+      f32x4 v = acc[i][jn];
+      if (fin) {
+        v += bias4[jn];
+        v = f32x4{fm_act(v[0], a.act), fm_act(v[1], a.act), fm_act(v[2], a.act), fm_act(v[3], a.act)};
+        v += prev[jn];
+      }
+      *reinterpret_cast<f32x4*>(orow + col) = v;
+    }
+  }
+}
+
+// fp32 -> bf16 copies of the weights k_fm_gemm_bf16 reads, one launch for all of a network's segments: 4,096 values per
+// workgroup, 16 bytes in and 8 bytes out per thread and pass.
+constexpr int kFmLpMaxSegs = 12;
+struct FmPackLpArgs {
+  const float* src[kFmLpMaxSegs]; int64_t dst_off[kFmLpMaxSegs], count[kFmLpMaxSegs];
+  int block_begin[kFmLpMaxSegs + 1]; int nseg;
+  uint16_t* dst;
+};
+__global__ __launch_bounds__(kThreads) void k_fm_pack_lp(FmPackLpArgs a) {
+  int s = 0;
+  while (s + 1 < a.nseg && (int)blockIdx.x >= a.block_begin[s + 1]) ++s;
+  const int64_t base = (int64_t)((int)blockIdx.x - a.block_begin[s]) * 4096;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int64_t i = base + (int64_t)(it * kThreads + (int)threadIdx.x) * 4;
+    if (i >= a.count[s]) return;                                       // (counts are multiples of 4)
+    const f32x4 v = ldg4<4>(a.src[s] + i);
+    *reinterpret_cast<u32x2*>(a.dst + a.dst_off[s] + i) = u32x2{fm_bf16_pair(v[0], v[1]), fm_bf16_pair(v[2], v[3])};
+  }
+}
+
 // deconv6 (128 -> 32 channels at 128 x 128; deconv5, 64 channels, as two halves when it has the tiles): the FOUR parity
 // classes of a row tile in one workgroup.  As four mode-1
 // launches' worth of 128 x 32 tiles the layer staged every source pixel once per (class, tap) pair -- 16 operand tiles per
@@ -707,6 +928,142 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
   }
   __syncthreads();
   fm_stat_publish(a.ep, m_tile, co0, 32, sums);
+}
+
+// k_fm_deconv32 with bf16 MFMA operands (precision NDP_FM_BF16: deconv6, and deconv5 where fm_geom chooses this form): the
+// same walk over the nine taps, tiles, weight order and output placement; the operand path is k_fm_gemm_bf16's (the source
+// tile rounded where it is staged, 8 bytes per 4 values from the bf16 weights in a.w, one 16-byte LDS read per lane and
+// 32-wide K step, row stride kFmLpLD).  Bias only: no activation and no statistics, which the eval-mode pass never asks of
+// these layers.  Measured against mode 1 of k_fm_gemm_bf16 (16 operand tiles per 32 channels instead of 9): DESIGN.md 5s.
+constexpr int fm_deconv32_bf16_lds_bytes() { return 2 * (kFmBM + 128) * kFmLpLD * 2; }
+__global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32_bf16(FmDcArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t smem_lp[];
+  constexpr int BM = kFmBM, BK = kFmBK, LD = kFmLpLD, NB = 128;         // NB: 4 classes x 32 output channels
+  int m_tile;
+  if (a.mtiles >= 8) {
+    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
+    m_tile = jb * 8 + xcd;
+    if (m_tile >= a.mtiles) return;
+  } else {
+    m_tile = blockIdx.x;
+  }
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int c = lane & 15, q = lane >> 4;
+  const int row0 = wave * 32;
+  constexpr int QPR = BK / 4, RPP = kThreads / QPR, NUA = BM / RPP;
+  const int r0 = t / QPR, kq = t % QPR;
+  const float* a_img[NUA];
+  int a_y[NUA], a_x[NUA];
+#pragma unroll
+  for (int u = 0; u < NUA; ++u) {
+    int m = m_tile * BM + r0 + RPP * u;
+    const bool valid = m < a.M;
+    m = valid ? m : a.M - 1;
+    const int img = m / (a.SH * a.SW), rem = m - img * (a.SH * a.SW);
+    const int y = rem / a.SW, x = rem - y * a.SW;
+    a_img[u] = a.src + (size_t)img * a.SH * a.SW * a.src_ld + 4 * kq;
+    a_y[u] = valid ? y : -(1 << 20);
+    a_x[u] = x;
+  }
+  const uint16_t* b_cls[4];                                            // B rows: pass u = class u, row r0 = output channel
+  const int co0 = blockIdx.y * 32;
+#pragma unroll
+  for (int u = 0; u < 4; ++u) b_cls[u] = reinterpret_cast<const uint16_t*>(a.w) + ((size_t)u * a.N + co0 + r0) * 4 * a.C + 4 * kq;
+  const int chunks = a.C / BK, nsteps = 9 * chunks;
+  f32x4 ra[NUA];
+  u32x2 rb[4];
+  bool ra_ok[NUA];
+  auto fetch = [&](int step) {
+    const int tap = step / chunks, ci0 = (step - tap * chunks) * BK;
+    const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
+#pragma unroll
+    for (int u = 0; u < NUA; ++u) {
+      const int yy = a_y[u] + dy, xx = a_x[u] + dx;
+      const bool ok = (unsigned)yy < (unsigned)a.SH && (unsigned)xx < (unsigned)a.SW;
+      ra[u] = ldg4<4>(a_img[u] + (ok ? (size_t)(yy * a.SW + xx) * a.src_ld + ci0 : 0));
+      ra_ok[u] = ok;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
+      if ((unsigned)khp < 2u && (unsigned)kwp < 2u)                     // (uniform)
+        rb[u] = *reinterpret_cast<const u32x2*>(b_cls[u] + (size_t)(khp * 2 + kwp) * a.C + ci0);
+    }
+    pin_vmem();
+  };
+  auto stage = [&](int buf, int step) {
+    const int tap = step / chunks;
+    const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
+    uint16_t* As = smem_lp + buf * (BM + NB) * LD;
+    uint16_t* Bs = As + BM * LD;
+#pragma unroll
+    for (int u = 0; u < NUA; ++u) {
+      const u32x2 v = {fm_bf16_pair(ra[u][0], ra[u][1]), fm_bf16_pair(ra[u][2], ra[u][3])};
+      *reinterpret_cast<u32x2*>(As + (r0 + RPP * u) * LD + 4 * kq) = ra_ok[u] ? v : u32x2{0u, 0u};
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
+      if ((unsigned)khp < 2u && (unsigned)kwp < 2u) *reinterpret_cast<u32x2*>(Bs + (u * 32 + r0) * LD + 4 * kq) = rb[u];
+    }
+  };
+  f32x4 acc[2][8];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int jn = 0; jn < 8; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  fetch(0);
+  stage(0, 0);
+  __syncthreads();
+  int buf = 0;
+  for (int step = 0; step < nsteps; ++step) {
+    const bool more = step + 1 < nsteps;
+    if (more) fetch(step + 1);
+    const int tap = step / chunks;
+    const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
+    const uint16_t* As = smem_lp + buf * (BM + NB) * LD + (row0 + c) * LD + 8 * q;
+    const uint16_t* Bs = smem_lp + buf * (BM + NB) * LD + BM * LD + c * LD + 8 * q;
+    bf16x8 af[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const bf16x8*>(As + i * 16 * LD);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
+      if ((unsigned)khp >= 2u || (unsigned)kwp >= 2u) continue;       // (uniform: this tap is not one of class u's)
+      bf16x8 bf[2];
+#pragma unroll
+      for (int jn = 0; jn < 2; ++jn) bf[jn] = *reinterpret_cast<const bf16x8*>(Bs + (u * 32 + jn * 16) * LD);
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int jn = 0; jn < 2; ++jn)
+          acc[i][u * 2 + jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[jn], af[i], acc[i][u * 2 + jn], 0, 0, 0);
+    }
+    pin_vmem();
+    if (more) stage(buf ^ 1, step + 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // a lane holds row (grid position) c of a tile and output channels 4q .. 4q + 3 of each 16-column tile
+  f32x4 bias4[2];
+#pragma unroll
+  for (int jn = 0; jn < 2; ++jn) bias4[jn] = *reinterpret_cast<const f32x4*>(a.bias + co0 + jn * 16 + 4 * q);
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int m = m_tile * BM + row0 + i * 16 + c;
+    if (m >= a.M) continue;
+    const int img = m / (a.SH * a.SW), rem = m - img * (a.SH * a.SW);
+    const int y = rem / a.SW, x = rem - y * a.SW;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const size_t pix = ((size_t)img * 2 * a.SH + 2 * y + (u >> 1)) * 2 * a.SW + 2 * x + (u & 1);
+      float* orow = a.out + pix * a.out_ld + co0;
+#pragma unroll
+      for (int jn = 0; jn < 2; ++jn) *reinterpret_cast<f32x4*>(orow + jn * 16 + 4 * q) = acc[i][u * 2 + jn] + bias4[jn];
+    }
+  }
 }
 
 // The 4x4 <-> 1x1 layers (deconv1 forward, conv6's data gradient: mode 3, sixteen one-tap classes) at a handful of rows:
@@ -2365,6 +2722,9 @@ static void fm_attrs() {
   std::call_once(device_once(g_fm_attr_once), [] {
     allow_lds(k_fm_gemm<128>, fm_gemm_lds_floats<128>() * 4);
     allow_lds(k_fm_gemm<32>, fm_gemm_lds_floats<32>() * 4);
+    allow_lds(k_fm_gemm_bf16<128>, fm_gemm_bf16_lds_bytes<128>());
+    allow_lds(k_fm_gemm_bf16<32>, fm_gemm_bf16_lds_bytes<32>());
+    allow_lds(k_fm_deconv32_bf16, fm_deconv32_bf16_lds_bytes());
     allow_lds(k_fm_deconv32<false>, fm_deconv32_lds_floats() * 4);
     allow_lds(k_fm_deconv32<true>, fm_deconv32_lds_floats() * 4);
     allow_lds((k_fm_wgrad<64, 64>), (fm_wgrad_lds_floats<64, 64>() * 4));
@@ -2424,9 +2784,12 @@ constexpr int kFmSplitTarget = 256;
 
 // out = act(bias + gather-GEMM) [+ out]; see k_fm_gemm for the modes.  GH = grid of rows per image (square maps).
 // rq: statistics of the finished output, from this launch's epilogue or -- with a K split -- from the split sums'.
+// lp: `w` is the address of the layer's bf16 weights and the launch is k_fm_gemm_bf16 (modes 0 and 1, no statistics).
 static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int SH, int ss, const float* w, const float* bias,
                    FmView out, int OH, int GH, int64_t n, int C, int N, int KH, int pad, int act, int accumulate,
-                   const FmWs& ws, const FmEpReq* rq = nullptr) {
+                   const FmWs& ws, const FmEpReq* rq = nullptr, bool lp = false) {
+  if (lp && (mode > 1 || (rq != nullptr && rq->mode != 0)))
+    return fail(NDP_E_UNSUPPORTED, "forward model: %s has no bf16 launch of this kind", label);
   FmGemmArgs a;
   memset(&a, 0, sizeof(a));
   a.src = src.p; a.w = w; a.bias = bias; a.out = out.p; a.part = ws.part;
@@ -2478,7 +2841,9 @@ static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int 
   const dim3 grid((unsigned)gx, (unsigned)a.nsplit, (unsigned)(a.cls_units > 0 ? 1 : ncls));
   {
     KTimer kt(label, st);
-    if (bn == 128) hipLaunchKernelGGL(k_fm_gemm<128>, grid, dim3(kThreads), fm_gemm_lds_floats<128>() * 4, st, a);
+    if (lp && bn == 128) hipLaunchKernelGGL(k_fm_gemm_bf16<128>, grid, dim3(kThreads), fm_gemm_bf16_lds_bytes<128>(), st, a);
+    else if (lp) hipLaunchKernelGGL(k_fm_gemm_bf16<32>, grid, dim3(kThreads), fm_gemm_bf16_lds_bytes<32>(), st, a);
+    else if (bn == 128) hipLaunchKernelGGL(k_fm_gemm<128>, grid, dim3(kThreads), fm_gemm_lds_floats<128>() * 4, st, a);
     else hipLaunchKernelGGL(k_fm_gemm<32>, grid, dim3(kThreads), fm_gemm_lds_floats<32>() * 4, st, a);
   }
   rc = check_launch("k_fm_gemm");
@@ -2672,7 +3037,8 @@ static int fm_bn_bwd_at(hipStream_t st, int b, FmView raw, FmView y, FmView dy, 
 
 // deconv6's forward pass, the four parity classes per workgroup (k_fm_deconv32)
 static int fm_deconv32(hipStream_t st, const char* label, FmView src, int SH, const float* w, const float* bias, FmView out,
-                       int64_t n, int C, int N, const FmEpReq& rq, const FmWs& ws, bool relu = false) {
+                       int64_t n, int C, int N, const FmEpReq& rq, const FmWs& ws, bool relu = false, bool lp = false) {
+  if (lp && (relu || rq.mode != 0)) return fail(NDP_E_UNSUPPORTED, "forward model: %s has no bf16 launch of this kind", label);
   FmDcArgs a;
   memset(&a, 0, sizeof(a));
   a.src = src.p; a.src_ld = src.ld; a.SH = a.SW = SH; a.w = w; a.bias = bias; a.out = out.p; a.out_ld = out.ld;
@@ -2682,7 +3048,8 @@ static int fm_deconv32(hipStream_t st, const char* label, FmView src, int SH, co
   const unsigned gx = a.mtiles >= 8 ? 8u * (unsigned)((a.mtiles + 7) / 8) : (unsigned)a.mtiles;
   KTimer kt(label, st);
   const dim3 grid(gx, (unsigned)(N / 32));
-  if (relu) hipLaunchKernelGGL(k_fm_deconv32<true>, grid, dim3(kThreads), fm_deconv32_lds_floats() * 4, st, a);
+  if (lp) hipLaunchKernelGGL(k_fm_deconv32_bf16, grid, dim3(kThreads), fm_deconv32_bf16_lds_bytes(), st, a);   // (w: bf16 weights)
+  else if (relu) hipLaunchKernelGGL(k_fm_deconv32<true>, grid, dim3(kThreads), fm_deconv32_lds_floats() * 4, st, a);
   else hipLaunchKernelGGL(k_fm_deconv32<false>, grid, dim3(kThreads), fm_deconv32_lds_floats() * 4, st, a);
   return check_launch(label);
 }
@@ -2800,6 +3167,7 @@ static FmMaps fm_maps(const FmWs& ws) {
 struct FmRun {
   hipStream_t st; const FmNet& net; const FmMaps& m; const FmWs& ws; int64_t n;
   const float* params; float* running; float* grad; const FmStatSync* sync;
+  const uint16_t* lp;                        // the bf16 weights (fm_lp_offset), or null: every layer in fp32
 };
 static const float* fm_w1(const FmRun& r, int l) { return r.params + fm_param_offset(r.net, l, false); }
 static const float* fm_w2(const FmRun& r, int l) { return r.ws.p2 + fm_p2_offset(r.net, l); }
@@ -2813,6 +3181,16 @@ static int fm_no_launch(const FmRun& r, int l, int dir) {
 static int fm_layer_fwd(const FmRun& r, int l, int act, const FmEpReq& rq) {
   const FmGeom g = fm_geom(r.net, l, FM_FWD, r.n);
   if (g.mode < 0) return fm_no_launch(r, l, FM_FWD);
+  if (r.lp != nullptr && fm_lp_layer(r.net, l)) {
+    // bf16 operands: the same geometry and kernel choice, the bf16 copy of the weight order the launch reads
+    FmView lsrc, lout;
+    fm_layer_views(r.net, r.m, l, FM_FWD, &lsrc, &lout);
+    const float* lw = reinterpret_cast<const float*>(r.lp + fm_lp_offset(r.net, l));
+    if (g.deconv32 && act == 0)
+      return fm_deconv32(r.st, kFmLpLabel[l], lsrc, g.SH, lw, fm_bias(r, l), lout, r.n, g.C, g.N, rq, r.ws, false, true);
+    return fm_gemm(r.st, kFmLpLabel[l], g.mode, lsrc, g.SH, g.ss, lw, fm_bias(r, l), lout, g.OH, g.GH, r.n, g.C, g.N, g.KH, g.pad,
+                   act, 0, r.ws, &rq, true);
+  }
   const float* w = g.p2 ? fm_w2(r, l) : fm_w1(r, l);
   const char* label = r.net.label[l].of[FM_FWD];
   FmView src, out;
@@ -2891,6 +3269,24 @@ static int fm_pack(hipStream_t st, const FmNet& net, const float* params, const 
   return check_launch("k_fm_pack");
 }
 
+// the bf16 weights of the fm_lp_layer layers from P1 (params) / P2 (the workspace head, packed before), one launch
+static int fm_pack_lp(hipStream_t st, const FmNet& net, const float* params, const FmWs& ws, uint16_t* lp) {
+  FmPackLpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.dst = lp;
+  for (int l = 0; l < net.layers; ++l) {
+    if (!fm_lp_layer(net, l)) continue;
+    if (a.nseg == kFmLpMaxSegs) return fail(NDP_E_UNSUPPORTED, "forward model: more than %d bf16 layers", kFmLpMaxSegs);
+    const int i = a.nseg++;
+    a.src[i] = net.layer[l].kind == FM_CONV ? params + fm_param_offset(net, l, false) : ws.p2 + fm_p2_offset(net, l);
+    a.dst_off[i] = fm_lp_offset(net, l); a.count[i] = fm_w_floats(net, l);
+    a.block_begin[i + 1] = a.block_begin[i] + (int)((a.count[i] + 4095) / 4096);
+  }
+  KTimer kt("k_fm_pack_lp", st);
+  hipLaunchKernelGGL(k_fm_pack_lp, dim3((unsigned)a.block_begin[a.nseg]), dim3(kThreads), 0, st, a);
+  return check_launch("k_fm_pack_lp");
+}
+
 // Adam over the flat parameter buffer + the P2 rebuild, one launch (k_fm_adam_pack); `step` was advanced by the caller.
 // Tiles: the transposing layers.  Plain elements: everything between and after their weights -- among them the refinement
 // layers' weights (FM_P2_REFINE: at most the kernel's two) and conv1's (FM_P2_COLUMNS), which store their P2 position too.
@@ -2935,10 +3331,10 @@ static int fm_adam_pack(hipStream_t st, const FmNet& net, float* params, const f
 // forward pass up to the tanh output y2 (workspace); training: batch statistics (+ running update when running != null)
 static int fm_forward(hipStream_t st, const float* params, float* running, const void* cur, bool u8, const float* actions,
                       int64_t n, int training, const FmWs& ws, const FmStatSync* sync, bool clear_backward_too = false,
-                      const FmLossArgs* with_loss = nullptr) {
+                      const FmLossArgs* with_loss = nullptr, const uint16_t* lp = nullptr) {
   fm_attrs();
   const FmMaps m = fm_maps(ws);
-  const FmRun r = {st, kFmNet, m, ws, n, params, running, nullptr, sync};
+  const FmRun r = {st, kFmNet, m, ws, n, params, running, nullptr, sync, lp};
   const int64_t npix = n * 16384;
   // (the refinement stage's 16-channel maps are stored unpadded, kFmR1LD, and y2 as 3 + 1 channels written by k_fm_r2_fwd)
   {
@@ -3333,7 +3729,8 @@ int ndp_fm_pack_params(const float* params, float* workspace, void* stream) {
 }
 
 static int fm_forward_any(const float* params, float* running_stats, const void* state_cur, bool u8, const float* actions,
-                          int64_t n_images, int training, float* out, float* workspace, void* stream, const char* who) {
+                          int64_t n_images, int training, float* out, float* workspace, void* stream, const char* who,
+                          const uint16_t* lp = nullptr) {
   using namespace ndp;
   NDP_CHECK_ARG(params && state_cur && actions && out && workspace && n_images >= 1, "%s: bad arguments", who);
   NDP_CHECK_ARG(training || running_stats, "%s: eval mode needs the running statistics", who);
@@ -3343,11 +3740,11 @@ static int fm_forward_any(const float* params, float* running_stats, const void*
   hipStream_t st = (hipStream_t)stream;
   const FmWs ws = fm_ws(workspace, n_images);
   fm_eval_forget(workspace);
-  int rc = fm_forward(st, params, running_stats, state_cur, u8, actions, n_images, training, ws, nullptr);
+  int rc = fm_forward(st, params, running_stats, state_cur, u8, actions, n_images, training, ws, nullptr, false, nullptr, lp);
   if (rc) return rc;
   if (!training) {
     rc = fm_loss(st, state_cur, nullptr, u8, n_images, 0, out, nullptr, nullptr, nullptr, ws);
-    if (rc == NDP_OK) fm_eval_mark(workspace, n_images);     // ndp_fm_input_grads may follow
+    if (rc == NDP_OK && lp == nullptr) fm_eval_mark(workspace, n_images);     // ndp_fm_input_grads may follow (fp32 passes only)
     return rc;
   }
   // training mode returns the residual (forward_encoder.py:111-112): y2 -> NCHW
@@ -3366,6 +3763,29 @@ int ndp_fm_forward_u8(const float* params, float* running_stats, const uint8_t* 
                       int training, float* out, float* workspace, void* stream) {
   return fm_forward_any(params, running_stats, frames_cur, true, actions, n_images, training, out, workspace, stream,
                         "ndp_fm_forward_u8");
+}
+
+int64_t ndp_fm_lp_weight_bytes(void) { return 2 * ndp::fm_lp_offset(ndp::kFmNet, ndp::kFmNet.layers); }
+int ndp_fm_pack_params_lp(const float* params, const float* workspace, void* lp_weights, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(params && workspace && lp_weights && aligned16(params) && aligned16(workspace) && aligned16(lp_weights),
+                "ndp_fm_pack_params_lp: bad arguments");
+  return fm_pack_lp((hipStream_t)stream, kFmNet, params, fm_ws(const_cast<float*>(workspace), 1), (uint16_t*)lp_weights);
+}
+int ndp_fm_forward_lp(const float* params, const float* running_stats, const float* state_cur, const uint8_t* frames_u8,
+                      const float* actions, int64_t n_images, int precision, const void* lp_weights, float* out, float* workspace,
+                      void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(precision == NDP_FM_FP32 || precision == NDP_FM_BF16, "ndp_fm_forward_lp: precision %d is neither NDP_FM_FP32 nor "
+                "NDP_FM_BF16", precision);
+  NDP_CHECK_ARG((state_cur != nullptr) != (frames_u8 != nullptr), "ndp_fm_forward_lp: exactly one of state_cur and frames_u8");
+  NDP_CHECK_ARG(running_stats, "ndp_fm_forward_lp: eval mode needs the running statistics");
+  NDP_CHECK_ARG(precision == NDP_FM_FP32 || (lp_weights && aligned16(lp_weights)),
+                "ndp_fm_forward_lp: NDP_FM_BF16 needs the 16-byte aligned bf16 weights of ndp_fm_pack_params_lp");
+  const bool u8 = frames_u8 != nullptr;
+  return fm_forward_any(params, const_cast<float*>(running_stats), u8 ? (const void*)frames_u8 : (const void*)state_cur, u8, actions,
+                        n_images, 0, out, workspace, stream, "ndp_fm_forward_lp",
+                        precision == NDP_FM_BF16 ? (const uint16_t*)lp_weights : nullptr);
 }
 
 static int fm_train_grads_any(const float* params, float* running_stats, const void* state_cur, const void* state_fut, bool u8,

@@ -36,7 +36,8 @@ refined by gradient descent on the planner's score and replace the worst ones.  
 import torch
 
 from . import _capi, jpeg
-from ._eval_io import config_cli, device_of, load_eval_models  # noqa: F401 (device_of: the scripts read it from here)
+from ._eval_io import (FM_PRECISIONS, config_cli, device_of, fm_precision_code, fm_precision_of,  # noqa: F401 (device_of,
+                       load_eval_models)                                                        # fm_precision_of: for the scripts)
 from .models.forward_encoder import pack_module
 from .models.image_autoencoder import pack_encoder_params
 
@@ -51,7 +52,11 @@ def _ptr(t):
 class EvalModels:
     """The three trained modules, packed once for the kernels (eval mode: BatchNorm with running statistics)."""
 
-    def __init__(self, image_encoder, fwd_model_autoencoder, generator, device=None):
+    def __init__(self, image_encoder, fwd_model_autoencoder, generator, device=None, fm_precision="fp32"):
+        """fm_precision: 'fp32', or 'bf16' -- `forward` (every pass of the planner's rollouts) runs the nine stride-2 layers
+        with bf16 operands and fp32 accumulation (NDP_FM_BF16, include/ndp.h); forward_keep / input_grads stay fp32."""
+        self._fm_precision_code = fm_precision_code(fm_precision)
+        self.fm_precision = fm_precision
         if device is None:
             device = next(fwd_model_autoencoder.parameters()).device
         device = torch.device(device)
@@ -75,6 +80,7 @@ class EvalModels:
             self.g_params = generator.flat_parameters().detach().to(device).clone()
         self._enc_ws = None
         self._fm_ws, self._fm_n = None, 0
+        self._fm_lp = None               # the bf16 weights (ndp_fm_pack_params_lp), rebuilt with every ndp_fm_pack_params
         self._mse_ws = None
 
     # ------------------------------------------------------------------ one launch (or a few) each
@@ -115,10 +121,16 @@ class EvalModels:
             with _capi.on_device(self.device):
                 _capi.check(self.lib.ndp_fm_pack_params(_ptr(self.fm_params), _ptr(self._fm_ws), self._stream()),
                             "ndp_fm_pack_params")
+                if self._fm_precision_code:
+                    if self._fm_lp is None:
+                        self._fm_lp = torch.empty(self.lib.ndp_fm_lp_weight_bytes(), dtype=torch.uint8, device=self.device)
+                    _capi.check(self.lib.ndp_fm_pack_params_lp(_ptr(self.fm_params), _ptr(self._fm_ws), _ptr(self._fm_lp),
+                                                               self._stream()), "ndp_fm_pack_params_lp")
         out = torch.empty(n, 3, 128, 128, dtype=torch.float32, device=self.device)
         with _capi.on_device(self.device):
-            _capi.check(self.lib.ndp_fm_forward(_ptr(self.fm_params), _ptr(self.fm_stats), _ptr(state), _ptr(actions), n, 0,
-                                                _ptr(out), _ptr(self._fm_ws), self._stream()), "ndp_fm_forward")
+            _capi.check(self.lib.ndp_fm_forward_lp(_ptr(self.fm_params), _ptr(self.fm_stats), _ptr(state), None, _ptr(actions), n,
+                                                   self._fm_precision_code, _ptr(self._fm_lp), _ptr(out), _ptr(self._fm_ws),
+                                                   self._stream()), "ndp_fm_forward_lp")
         return out
 
     def g_input(self, state_code, state_rep, goal_code, goal_rep, rows):
@@ -642,12 +654,17 @@ def grad_from_config(config, rollouts=None, horizon=None):
     return grad
 
 
-def _grad_check(grad, rollouts, horizon):
+def _grad_check(grad, rollouts, horizon, models=None):
     if not isinstance(grad, GradSettings):
         raise TypeError("grad must be an evaluation.GradSettings, got %r" % (grad,))
     grad.row_count(rollouts)
     if int(horizon) > CEM_MAX_HORIZON:
         raise ValueError("the gradient stage takes a horizon of at most %d, got %d" % (CEM_MAX_HORIZON, int(horizon)))
+    if models is not None and getattr(models, "fm_precision", "fp32") != "fp32":
+        # the gradient stage runs in fp32 (forward_keep / input_grads): its rows would be ranked against bf16 ones
+        raise ValueError("grad=%r with an EvalModels of fm_precision=%r: the gradient stage is fp32 only and mixed-precision "
+                         "ranking is not offered; plan with fm_precision='fp32' or without grad"
+                         % (grad, models.fm_precision))
 
 
 def cem_normal_floats(batch, rollouts, horizon, iterations, seq_length=None):
@@ -903,7 +920,7 @@ def mpc_plan(models, frames, actions, rollouts, horizon, noise=None, choices=Non
     if cem is not None:
         _cem_check(cem, r, th)
     if grad is not None:
-        _grad_check(grad, r, th)
+        _grad_check(grad, r, th, models)
     imgs, b, t = _frames(models, frames)
     t1, nz, br = t - 1, models.noise_dim, b * r
     if t1 < 1:
@@ -1017,7 +1034,7 @@ def plan_step(models, state, goal, goal_code, rollouts, horizon, noise=None, see
     if cem is not None:
         _cem_check(cem, r, th)
     if grad is not None:
-        _grad_check(grad, r, th)
+        _grad_check(grad, r, th, models)
     if state.dim() != 4 or tuple(state.shape[1:]) != (3, 128, 128) or tuple(goal.shape) != tuple(state.shape):
         raise _capi.NdpError("state and goal must both be [B,3,128,128], got %s and %s"
                              % (tuple(state.shape), tuple(goal.shape)))
@@ -1097,7 +1114,7 @@ class MpcController:
         # grad: a GradSettings turns plan_step's gradient stage on for every plan(); `info` then also carries grad_curve,
         # grad_src, grad_dst and grad_rows
         if grad is not None:
-            _grad_check(grad, self.rollouts, self.horizon)
+            _grad_check(grad, self.rollouts, self.horizon, models)
         self.grad = grad
         self._prior, self._normal_off = None, 0
         self.resizer = LanczosResizer(models.device)
@@ -1318,6 +1335,8 @@ def script_main(fetch, argv=None, add_arguments=None, prepare=None):
     from .utils.cli_arguments.common_arguments import add_common_arguments
     parser = ArgumentParser(description="Interact with your training script")
     parser = add_common_arguments(parser)
+    parser.add_argument("--fm-precision", choices=FM_PRECISIONS, default=None,
+                        help="operand precision of the forward model's passes (default: evaluation.fm_precision, else fp32)")
     if add_arguments is not None:
         add_arguments(parser)
     _, config, wrapped = config_cli(parser, argv, "evaluation", prepare)

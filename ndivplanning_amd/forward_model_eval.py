@@ -25,7 +25,8 @@ import torch
 from . import _capi
 from . import image_quality as IQ
 from . import jpeg as jpeg_frames
-from ._eval_io import _check_out, _require_eval, _require_gpu, _to_bytes, fp64_mean, load_module, trajectory_batches
+from ._eval_io import (FM_PRECISIONS, _check_out, _require_eval, _require_gpu, _to_bytes, fm_precision_code, fp64_mean,
+                       load_module, trajectory_batches)
 from .utils.trajectory_loader import open_dataset
 
 IMAGE = (3, 128, 128)
@@ -83,7 +84,39 @@ def score(pred, target=None, target_idx=None, base=None, base_idx=None, errors=T
     return pred_err, base_err, pred_u8
 
 
-def _forward(fwd_model, state, actions):
+def _forward_bf16(fwd_model, state, actions):
+    """One eval-mode pass with bf16 operands (NDP_FM_BF16, include/ndp.h) on the module's packed parameters: a workspace
+    and the bf16 weights of their own beside the module's cache, rebuilt when the cache is (a parameter changed)."""
+    lib = _capi.load()
+    dev, n = state.device, int(state.shape[0])
+    cache = fwd_model._cache_for(dev)
+    lp = cache.get("lp")
+    if lp is None or lp["n"] < n:
+        lp = cache["lp"] = {"ws": torch.empty(lib.ndp_fm_workspace_floats(n), dtype=torch.float32, device=dev), "n": n,
+                            "weights": torch.empty(lib.ndp_fm_lp_weight_bytes(), dtype=torch.uint8, device=dev),
+                            "packed": False}
+    u8 = state.dtype == torch.uint8
+    if u8 and tuple(state.shape[1:]) != (128, 128, 3):
+        raise _capi.NdpError("byte frames must be [n,128,128,3], got %s" % (tuple(state.shape),))
+    x = state.detach().contiguous() if u8 else state.detach().contiguous().float()
+    a = actions.detach().contiguous().float()
+    out = torch.empty(n, 3, 128, 128, dtype=torch.float32, device=dev)
+    with _capi.on_device(x):
+        st = _capi.stream_ptr(dev)
+        if not lp["packed"]:
+            _capi.check(lib.ndp_fm_pack_params(_capi.ptr(cache["params"]), _capi.ptr(lp["ws"]), st), "ndp_fm_pack_params")
+            _capi.check(lib.ndp_fm_pack_params_lp(_capi.ptr(cache["params"]), _capi.ptr(lp["ws"]), _capi.ptr(lp["weights"]), st),
+                        "ndp_fm_pack_params_lp")
+            lp["packed"] = True
+        _capi.check(lib.ndp_fm_forward_lp(_capi.ptr(cache["params"]), _capi.ptr(cache["stats"]), None if u8 else _capi.ptr(x),
+                                          _capi.ptr(x) if u8 else None, _capi.ptr(a), n, 1, _capi.ptr(lp["weights"]),
+                                          _capi.ptr(out), _capi.ptr(lp["ws"]), st), "ndp_fm_forward_lp")
+    return out
+
+
+def _forward(fwd_model, state, actions, precision="fp32"):
+    if precision == "bf16":
+        return _forward_bf16(fwd_model, state, actions)
     with torch.no_grad():
         return fwd_model(state, actions.detach().float())
 
@@ -96,18 +129,19 @@ def _quality(pred, base, target, base_idx=None, target_idx=None):
     return ssim, psnr, base_ssim, base_psnr
 
 
-def predict(fwd_model, state, actions, target=None, out="float", quality=False):
+def predict(fwd_model, state, actions, target=None, out="float", quality=False, precision="fp32"):
     """(next_state, per-image MSE [n], persistence MSE [n], mean MSE [1]) of one eval-mode step from `state`, float32
     [n,3,128,128] in [-1,1] or byte frames uint8 [n,128,128,3] (normalised as the loader does, as the kernels read them).
     next_state: float32 NCHW (out="float") or the reference's bytes HWC (out="bytes": below 0 / above 255 saturate).  The
     errors are against `target` (float or byte frames); the persistence MSE is that of `state` itself against the target.
     Without a target the three error results are None.  quality=True: four more results follow, SSIM and PSNR per image of
     the prediction and of `state` itself against the target (ssim, psnr, persistence_ssim, persistence_psnr [n]; None
-    without a target)."""
+    without a target).  precision: 'fp32', or 'bf16' -- the pass with bf16 operands (NDP_FM_BF16, include/ndp.h)."""
     _check_out(out)
+    fm_precision_code(precision)
     _require_eval(fwd_model=fwd_model)
     _require_gpu(state, "state")
-    pred = _forward(fwd_model, state, actions)
+    pred = _forward(fwd_model, state, actions, precision)
     if target is None:
         return ((score(pred, out_bytes=True)[2] if out == "bytes" else pred), None, None, None) + ((None,) * 4 if quality else ())
     err, base_err, pred_u8 = score(pred, target, base=state, out_bytes=out == "bytes")
@@ -115,13 +149,14 @@ def predict(fwd_model, state, actions, target=None, out="float", quality=False):
     return ((pred_u8 if out == "bytes" else pred), err, base_err, fp64_mean(err)) + extra
 
 
-def rollout(fwd_model, state0, actions, targets=None, out="float", quality=False):
+def rollout(fwd_model, state0, actions, targets=None, out="float", quality=False, precision="fp32"):
     """H eval-mode steps from state0 [B,...] (float NCHW or byte frames) with actions [B,H,4], every step on the model's
     own fp32 prediction of the step before, as `mpc_plan` does (bytes are never fed back).  Returns (predictions
     [B,H,3,128,128] float32 or [B,H,128,128,3] bytes, err [B,H], persistence [B,H]); targets [B,H,...] float or byte
     frames, None: the two errors are None.  persistence[b,h] is the error of state0[b] against target h.  quality=True:
-    (ssim, psnr, persistence_ssim, persistence_psnr), [B,H] each, follow (None without targets)."""
+    (ssim, psnr, persistence_ssim, persistence_psnr), [B,H] each, follow (None without targets).  precision: as predict's."""
     _check_out(out)
+    fm_precision_code(precision)
     _require_eval(fwd_model=fwd_model)
     _require_gpu(state0, "state0")
     _require_gpu(actions, "actions")
@@ -137,7 +172,7 @@ def rollout(fwd_model, state0, actions, targets=None, out="float", quality=False
     preds, errs, bases, state = [], [], [], state0
     quals = [[], [], [], []]
     for h in range(steps):
-        state = _forward(fwd_model, state, actions[:, h].contiguous())
+        state = _forward(fwd_model, state, actions[:, h].contiguous(), precision)
         want_bytes = out == "bytes"
         if flat_targets is not None:
             err, base_err, pred_u8 = score(state, flat_targets, rows + h, base=state0, out_bytes=want_bytes)
@@ -185,7 +220,7 @@ def _maps(sched, T, b, device):
 QUALITY_KEYS = ("ssim", "psnr", "persistence_ssim", "persistence_psnr")
 
 
-def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=0, quality=False):
+def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=0, quality=False, precision="fp32"):
     """The multi-step prediction error over `dataset` (PushDataset / SyntheticPushDataset: images, byte frames or JPEG
     streams, which `jpeg.JpegDecoder` decodes on the device), from EVERY start frame: pass h of a batch of B trajectories
     runs the B * (T - h) starts still alive (rollout_schedule) in ONE forward call, on their own predictions of pass
@@ -202,7 +237,8 @@ def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=
         `errors`' order: two ndp_image_quality launches per pass, the predictions against `frames` through the target
         rows, then `frames` through the start rows against the same targets.  Every other key holds the same bits.
     The means are taken in fp64 over the fp32 per-prediction values; a PSNR mean skips no value (an infinite value gives an
-    infinite mean)."""
+    infinite mean).  precision: 'fp32', or 'bf16' -- every pass with bf16 operands (NDP_FM_BF16, include/ndp.h)."""
+    fm_precision_code(precision)
     _require_eval(fwd_model=fwd_model)
     if len(dataset) == 0 or int(batch_size) < 1:
         raise ValueError("evaluate needs a non-empty dataset and batch_size >= 1 (dataset: %d trajectories, batch_size %r)"
@@ -237,7 +273,7 @@ def evaluate(fwd_model, dataset, horizon=None, batch_size=16, device=None, keep=
                 state = frames.index_select(0, start_rows.long())
             else:                                                     # the survivors' own predictions: drop each last start
                 state = state.view(b, alive + 1, *IMAGE)[:, :alive].reshape(b * alive, *IMAGE)
-            state = _forward(fwd_model, state, flat_actions.index_select(0, action_rows.long()))
+            state = _forward(fwd_model, state, flat_actions.index_select(0, action_rows.long()), precision)
             err, base_err, pred_u8 = score(state, frames, target_rows, base=frames, base_idx=start_rows, out_bytes=want > 0)
             errs[h - 1].append(err)
             bases[h - 1].append(base_err)
@@ -319,6 +355,8 @@ def make_parser():
     parser.add_argument("--num-save", type=int, default=8)
     parser.add_argument("--quality", action="store_true",
                         help="also print SSIM and PSNR per horizon, of the model and of the persistence baseline")
+    parser.add_argument("--fm-precision", choices=FM_PRECISIONS, default="fp32",
+                        help="operand precision of the forward model's passes: fp32, or bf16 operands with fp32 accumulation")
     return parser
 
 
@@ -329,7 +367,7 @@ def main(argv=None, log=print):
     dataset = make_dataset(args.data, seq_length=args.seq_length, raw_jpeg=args.raw_jpeg)
     keep = args.num_save if args.save_dir else 0
     result = evaluate(model, dataset, horizon=args.horizon, batch_size=args.batch_size, device=device, keep=keep,
-                      quality=args.quality)
+                      quality=args.quality, precision=args.fm_precision)
     one_step = float(result["one_step_mse"].item())
     log("val_pred_loss:", one_step, "trajectories:", len(dataset))
     rows = zip(result["horizon_mse"].tolist(), result["persistence_mse"].tolist(), result["counts"].tolist())
