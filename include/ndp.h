@@ -483,6 +483,37 @@ int ndp_fm_forward_lp(const float *params, const float *running_stats, const flo
                       const uint8_t *frames_u8, const float *actions, int64_t n_images, int precision,
                       const void *lp_weights, float *out, float *workspace, void *stream);
 
+/* The image encoder's pass with the same choice (the planner encodes every predicted frame once per horizon step).
+ *   NDP_ENC_FP32  the launches and the bits of ndp_encoder_forward / ndp_encoder_forward_u8; lp_weights may be NULL.
+ *   NDP_ENC_BF16  differs in exactly these points:
+ *     - conv2..conv6 compute  out = act(bias + sum bf16(x) * bf16(w))  with w the packed fp32 weight (BatchNorm folded
+ *       in), bf16(.) fp32 -> bf16 to nearest even (NaN stays NaN, overflow goes to +-Inf), products exact in fp32, the sum
+ *       in fp32 (the accumulator of v_mfma_f32_16x16x32_bf16), the bias fp32, ReLU applied in fp32;
+ *     - conv1 keeps its fp32 arithmetic on the image and on its fp32 weights;
+ *     - the maps behind conv1..conv5 are STORED as bf16: the rounding of the next layer's operand, done once by the
+ *       producer (each map is read by the next convolution only).  K-split partial sums and the codes stay fp32;
+ *     - a ReLU passes a NaN on (the fp32 pass's maximum with zero drops it), so a NaN pixel gives that image NaN codes;
+ *     - the weights are rounded ONCE: ndp_encoder_pack_params_lp writes the bf16 copy of conv2..conv6's packed weights,
+ *       in the same [Cout][KH][KW][Cin] order, back to back, into a caller-owned buffer of ndp_encoder_lp_weight_bytes()
+ *       bytes (2 * 8,364,032; 16-byte aligned), one launch; it follows every change of packed_params.
+ * Workspace: ndp_encoder_workspace_floats(n) serves both precisions.  A bf16 pass of c <= 512 images lays out the five
+ * maps, consecutive, as bf16, NHWC ([c][64][64][64], [c][32][32][128], [c][16][16][256], [c][8][8][512], [c][4][4][1024]),
+ * then the fp32 partial sums; ndp_encoder_lp_act_offset(layer 0..4, n_images) (host only) is a map's offset in bf16
+ * elements for c = min(n_images, 512), -1 for any other layer or n_images < 1.  Passes reuse the workspace, so after a
+ * call the maps are those of the last pass.
+ * Exactly one of images (float [n,3,128,128]) and frames_hwc (bytes [n][128][128][3]) is given.  An unknown precision,
+ * NDP_ENC_BF16 without lp_weights, both or neither image pointer, a buffer that is not 16-byte aligned (packed_params, images,
+ * lp_weights, codes, workspace; frames_hwc may have any alignment, as in ndp_encoder_forward_u8), n_images < 1: NDP_E_ARG,
+ * nothing launched.  Two passes on the same inputs give the same bits; byte frames and the floats built from them too. */
+#define NDP_ENC_FP32 0
+#define NDP_ENC_BF16 1
+int64_t ndp_encoder_lp_weight_bytes(void);
+int64_t ndp_encoder_lp_act_offset(int layer, int64_t n_images);
+int ndp_encoder_pack_params_lp(const float *packed_params, void *lp_weights, void *stream);
+int ndp_encoder_forward_lp(const float *packed_params, const float *images, const uint8_t *frames_hwc,
+                           int64_t n_images, int precision, const void *lp_weights, float *codes,
+                           float *workspace, void *stream);
+
 /* ndp_fm_backward with the gradient of the TRAINING-mode pass with respect to its inputs as well: the same precondition
  * (a training-mode ndp_fm_forward on this workspace came first), the same launches and bit for bit the same `grad`, plus
  * d_state_cur [n,3,128,128] (or NULL) = d loss / d state_cur through the network alone -- the training-mode output is

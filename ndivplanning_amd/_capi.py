@@ -106,6 +106,10 @@ SIGNATURES = {
     "ndp_encoder_workspace_floats": (c_int64, [c_int64]),
     "ndp_encoder_forward": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "ndp_encoder_forward_u8": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "ndp_encoder_lp_weight_bytes": (c_int64, []),
+    "ndp_encoder_lp_act_offset": (c_int64, [c_int, c_int64]),
+    "ndp_encoder_pack_params_lp": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "ndp_encoder_forward_lp": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ndp_fm_param_floats": (c_int64, []),
     "ndp_fm_stat_floats": (c_int64, []),
     "ndp_fm_workspace_floats": (c_int64, [c_int64]),

@@ -21,7 +21,8 @@ def fetch(kind, image_encoder, fwd_model_autoencoder, generator, dataset, config
     generator.eval()
     seed, k, nz, bs, r, th = E.eval_settings(kind, config, dataset, generator)
     gpu_id = E.device_of(config)
-    models = E.EvalModels(image_encoder, fwd_model_autoencoder, generator, gpu_id, fm_precision=E.fm_precision_of(config))
+    models = E.EvalModels(image_encoder, fwd_model_autoencoder, generator, gpu_id, fm_precision=E.fm_precision_of(config),
+                          enc_precision=E.enc_precision_of(config))
     t1 = int(dataset.seq_length) - 1
     torch.manual_seed(seed)
     np.random.seed(seed)

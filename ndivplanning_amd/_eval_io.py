@@ -33,6 +33,28 @@ def fm_precision_of(config):
     return name
 
 
+ENC_PRECISIONS = ("fp32", "bf16")   # NDP_ENC_FP32, NDP_ENC_BF16 (include/ndp.h): the image encoder's pass in EvalModels.encode
+
+
+def enc_precision_code(name):
+    """'fp32' / 'bf16' -> NDP_ENC_FP32 / NDP_ENC_BF16; anything else is a ValueError that lists the two names."""
+    if not isinstance(name, str) or name not in ENC_PRECISIONS:
+        raise ValueError("enc_precision must be 'fp32' or 'bf16', got %r" % (name,))
+    return ENC_PRECISIONS.index(name)
+
+
+def enc_precision_of(config):
+    """The image encoder's precision for an evaluation script: --enc-precision (a top-level key), else the config's
+    `evaluation.enc_precision`, else 'fp32'.  Checked."""
+    name = config.get("enc_precision") if hasattr(config, "get") else None
+    if name is None:
+        ev = config.get("evaluation") if hasattr(config, "get") else None
+        name = ev.get("enc_precision") if ev is not None and hasattr(ev, "get") else None
+    name = "fp32" if name is None else name
+    enc_precision_code(name)
+    return name
+
+
 def _check_out(out):
     if out not in OUTPUTS:
         raise ValueError("out must be 'float' or 'bytes', got %r" % (out,))

@@ -27,6 +27,14 @@ namespace ndp {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+// bf16 MFMA operands (k_fm_gemm_bf16, k_fm_deconv32_bf16, k_conv_gemm_bf16): 8 values per lane and 32-wide K step
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ uint32_t fm_bf16_pair(float lo, float hi) {
+  const bf16x2 v = {(__bf16)lo, (__bf16)hi};                           // fptrunc: round to nearest even (v_cvt_pk_bf16_f32)
+  return __builtin_bit_cast(uint32_t, v);
+}
 
 constexpr int kThreads = 256;
 constexpr int kWaves = 4;
@@ -175,6 +183,27 @@ __device__ __forceinline__ f32x4 ldg4(const float* p) {
     f32x2 hi = *reinterpret_cast<const f32x2*>(p + 2);
     f32x4 r = {lo[0], lo[1], hi[0], hi[1]};
     return r;
+  }
+}
+
+// fp32 -> bf16 copies of weight tensors (k_fm_pack_lp, k_enc_pack_lp), one launch for all of a network's segments: 4,096
+// values per workgroup, 16 bytes in and 8 bytes out per thread and pass.
+constexpr int kPackLpMaxSegs = 12;
+struct PackLpArgs {
+  const float* src[kPackLpMaxSegs]; int64_t dst_off[kPackLpMaxSegs], count[kPackLpMaxSegs];
+  int block_begin[kPackLpMaxSegs + 1]; int nseg;
+  uint16_t* dst;
+};
+__device__ __forceinline__ void pack_lp_body(const PackLpArgs& a) {
+  int s = 0;
+  while (s + 1 < a.nseg && (int)blockIdx.x >= a.block_begin[s + 1]) ++s;
+  const int64_t base = (int64_t)((int)blockIdx.x - a.block_begin[s]) * 4096;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int64_t i = base + (int64_t)(it * kThreads + (int)threadIdx.x) * 4;
+    if (i >= a.count[s]) return;                                       // (counts are multiples of 4)
+    const f32x4 v = ldg4<4>(a.src[s] + i);
+    *reinterpret_cast<u32x2*>(a.dst + a.dst_off[s] + i) = u32x2{fm_bf16_pair(v[0], v[1]), fm_bf16_pair(v[2], v[3])};
   }
 }
 

@@ -12,6 +12,10 @@
 // (double-buffered, next step's global loads in flight during the 128 MFMAs per wave of the current one);
 // the 4 waves own 64 x 64 quadrants; lane (c, q) reads 4 consecutive k of "its" row with one ds_read_b128 and
 // MFMA step s pairs element s of the A and the B vector (a permutation of the k order, as in ndp_device.h).
+//
+// Precision NDP_ENC_BF16 (ndp_encoder_forward_lp; the definition is in include/ndp.h): the same six launches with conv1
+// storing its map as bf16 and conv2..6 through k_conv_gemm_bf16 -- bf16 maps and bf16 weights straight into the bf16 MFMA,
+// fp32 accumulation, fp32 partial sums and codes.
 
 namespace ndp {
 
@@ -162,11 +166,150 @@ __global__ __launch_bounds__(kThreads, (kEncBK >= 32 ? 2 : 3)) void k_conv_gemm(
   }
 }
 
+// ------------------------------------------------------------------------------------------ k_conv_gemm_bf16
+// k_conv_gemm with bf16 MFMA operands (precision NDP_ENC_BF16; the definition is in include/ndp.h):
+// out = act(bias + sum bf16(x) . bf16(w)), products exact, the sum in fp32 in the accumulator of v_mfma_f32_16x16x32_bf16.
+// Same ConvGemmArgs -- a.in is the bf16 map its producer stored (the rounding of this layer's operand, done once), a.w the
+// layer's bf16 weights (k_enc_pack_lp) -- same 128 x 128 tile, XCD order, K split and epilogue.  The operand path:
+//   load   both operands come as bf16 and go to LDS as they come: a 32-wide K chunk of an im2col row (one tap, 32
+//          consecutive channels) is 64 contiguous bytes, 16 bytes per thread and load; a padding tap is zeroed where it
+//          is written to LDS;
+//   LDS    row stride 48 values = 96 bytes, the conflict-free stride of k_fm_gemm_bf16 (any 8 consecutive rows on the 8
+//          even 16-byte slots, the rows at q + 1 on the odd ones);
+//   read   k_fm_gemm_bf16's fragments: one 16-byte read per operand tile and 32-wide K step, lane l = 16 q + c holds row c,
+//          k = 8 q .. 8 q + 7; the weights are the A operand, so a lane ends with output pixel c and channels 4 q .. 4 q + 3.
+// OUT_LP: the finished map is stored as bf16 (conv2..conv5; 8 bytes per lane and tile); conv6 stores fp32 codes.  Partial
+// sums of a split layer are fp32 either way.
+// ReLU of the bf16 pass: a NaN stays a NaN, as the definition's torch.relu has it (fmaxf(NaN, 0) is 0: the fp32 pass,
+// whose bits are pinned, drops a NaN at its first ReLU)
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+
+constexpr int kEncLpBK = 32, kEncLpLD = 48;             // (a K step of 64 was measured and lost at small n: DESIGN 5t)
+constexpr int conv_gemm_bf16_lds_bytes() { return 2 * (kEncBM + kEncBN) * kEncLpLD * 2; }
+
+template <bool OUT_LP>
+__global__ __launch_bounds__(kThreads, 2) void k_conv_gemm_bf16(ConvGemmArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t smem_enc_lp[];
+  constexpr int BM = kEncBM, BN = kEncBN, BK = kEncLpBK, LD = kEncLpLD;
+  int n_tile, m_tile;                                                  // (k_conv_gemm's order)
+  if (a.mtiles >= 8) {
+    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    n_tile = j % a.ntiles;
+    m_tile = (j / a.ntiles) * 8 + xcd;
+    if (m_tile >= a.mtiles) return;
+  } else {
+    n_tile = blockIdx.x % a.ntiles;
+    m_tile = blockIdx.x / a.ntiles;
+  }
+  const int split = blockIdx.y;
+  const int kbeg = split * a.k_per_split;
+  const int kend = kbeg + a.k_per_split < a.K ? kbeg + a.k_per_split : a.K;
+
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int c = lane & 15, q = lane >> 4;
+  const int wm = wave >> 1, wn = wave & 1;
+
+  // global -> LDS assignment: NU rows (r0 + RPP u) x one 8-value quad (16 bytes, kq) of each operand per thread and step
+  constexpr int QPR = BK / 8, RPP = kThreads / QPR, NU = BM / RPP;
+  const int r0 = t / QPR, kq = t % QPR;
+  const uint16_t* in_lp = reinterpret_cast<const uint16_t*>(a.in);
+  const uint16_t* w_lp = reinterpret_cast<const uint16_t*>(a.w);
+  const uint16_t* a_img[NU];
+  int a_ih0[NU], a_iw0[NU], a_base[NU];
+  const uint16_t* b_row[NU];
+#pragma unroll
+  for (int u = 0; u < NU; ++u) {
+    int m = m_tile * BM + r0 + RPP * u;
+    const bool valid = m < a.M;
+    m = valid ? m : a.M - 1;
+    const int n = m / (a.OH * a.OW), rem = m - n * (a.OH * a.OW);
+    const int oh = rem / a.OW, ow = rem - oh * a.OW;
+    a_img[u] = in_lp + (size_t)n * a.H * a.W * a.Cin + 8 * kq;
+    a_ih0[u] = valid ? oh * a.stride - a.pad : -(1 << 20);       // rows past M: every tap out of bounds -> zeros
+    a_iw0[u] = ow * a.stride - a.pad;
+    a_base[u] = ((oh * a.stride - a.pad) * a.W + a_iw0[u]) * a.Cin;
+    b_row[u] = w_lp + (size_t)(n_tile * BN + r0 + RPP * u) * a.K + 8 * kq;
+  }
+  u32x4 ra[NU], rb[NU];
+  bool ra_ok[NU];
+  auto fetch = [&](int k0) {
+    const int tap = k0 / a.Cin, ci0 = k0 - tap * a.Cin;          // uniform: one tap, BK consecutive channels
+    const int kh = tap / a.KW, kw = tap - kh * a.KW;
+    const int tapoff = (kh * a.W + kw) * a.Cin + ci0;            // uniform
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const bool ok = (unsigned)(a_ih0[u] + kh) < (unsigned)a.H && (unsigned)(a_iw0[u] + kw) < (unsigned)a.W;
+      ra[u] = *reinterpret_cast<const u32x4*>(a_img[u] + (ok ? a_base[u] + tapoff : 0));   // always a valid address
+      ra_ok[u] = ok;
+      rb[u] = *reinterpret_cast<const u32x4*>(b_row[u] + k0);
+    }
+    pin_vmem();
+  };
+  auto stage = [&](int buf) {
+    uint16_t* As = smem_enc_lp + buf * (BM + BN) * LD;
+    uint16_t* Bs = As + BM * LD;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      *reinterpret_cast<u32x4*>(As + (r0 + RPP * u) * LD + 8 * kq) = ra_ok[u] ? ra[u] : u32x4{0u, 0u, 0u, 0u};
+      *reinterpret_cast<u32x4*>(Bs + (r0 + RPP * u) * LD + 8 * kq) = rb[u];
+    }
+  };
+
+  f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int jn = 0; jn < 4; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  fetch(kbeg);
+  stage(0);
+  __syncthreads();
+  int buf = 0;
+  for (int k0 = kbeg; k0 < kend; k0 += BK) {
+    const bool more = k0 + BK < kend;
+    if (more) fetch(k0 + BK);                                    // in flight during this step's MFMAs
+    const uint16_t* As = smem_enc_lp + buf * (BM + BN) * LD + (wm * 64 + c) * LD + 8 * q;
+    const uint16_t* Bs = smem_enc_lp + buf * (BM + BN) * LD + BM * LD + (wn * 64 + c) * LD + 8 * q;
+    bf16x8 af[4], bf[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      af[i] = *reinterpret_cast<const bf16x8*>(As + i * 16 * LD);
+      bf[i] = *reinterpret_cast<const bf16x8*>(Bs + i * 16 * LD);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int jn = 0; jn < 4; ++jn)
+        acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[jn], af[i], acc[i][jn], 0, 0, 0);   // transposed tiles
+    pin_vmem();
+    if (more) stage(buf ^ 1);
+    __syncthreads();
+    buf ^= 1;
+  }
+
+  // k_conv_gemm's epilogue: a lane holds output row (pixel) c and the channels 4q .. 4q+3 of each tile
+  const bool fin = a.nsplit == 1;
+  float* out = a.out + (fin ? 0 : (size_t)split * a.M * a.Cout);
+#pragma unroll
+  for (int jn = 0; jn < 4; ++jn) {
+    const int col = n_tile * BN + wn * 64 + jn * 16 + 4 * q;
+    const f32x4 bv = fin ? *reinterpret_cast<const f32x4*>(a.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m_tile * BM + wm * 64 + i * 16 + c;
+      if (m < a.M) {
+        f32x4 v = acc[i][jn] + bv;
+        if (a.relu && fin) v = f32x4{relu_keep_nan(v[0]), relu_keep_nan(v[1]), relu_keep_nan(v[2]), relu_keep_nan(v[3])};
+        const size_t at = (size_t)m * a.Cout + col;
+        if (OUT_LP && fin) *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(out) + at) = u32x2{fm_bf16_pair(v[0], v[1]), fm_bf16_pair(v[2], v[3])};
+        else *reinterpret_cast<f32x4*>(out + at) = v;
+      }
+    }
+  }
+}
+
 // out[m][co] = act(bias[co] + sum_s part[s][m][co])  (fixed order: bitwise reproducible)
-__global__ __launch_bounds__(kThreads) void k_splitk_reduce(const float* part, int nsplit, int64_t mc, const float* bias,
-                                                            int cout, int relu, float* out) {
-  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= mc) return;
+__device__ __forceinline__ float splitk_sum(const float* part, int nsplit, int64_t mc, const float* bias, int cout, int64_t i) {
   float s = bias[i % cout];
   int sp = 0;
   for (; sp + 8 <= nsplit; sp += 8) {      // 8 loads in flight, summed in split order
@@ -177,8 +320,26 @@ __global__ __launch_bounds__(kThreads) void k_splitk_reduce(const float* part, i
     for (int u = 0; u < 8; ++u) s += v[u];
   }
   for (; sp < nsplit; ++sp) s += part[(size_t)sp * mc + i];
+  return s;
+}
+__global__ __launch_bounds__(kThreads) void k_splitk_reduce(const float* part, int nsplit, int64_t mc, const float* bias,
+                                                            int cout, int relu, float* out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= mc) return;
+  const float s = splitk_sum(part, nsplit, mc, bias, cout, i);
   out[i] = relu ? fmaxf(s, 0.f) : s;
 }
+// ... the finished map stored as bf16 (the split layers of a NDP_ENC_BF16 pass; conv6's codes keep the fp32 one)
+__global__ __launch_bounds__(kThreads) void k_splitk_reduce_bf16(const float* part, int nsplit, int64_t mc, const float* bias,
+                                                                 int cout, int relu, __bf16* out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= mc) return;
+  const float s = splitk_sum(part, nsplit, mc, bias, cout, i);
+  out[i] = (__bf16)(relu ? relu_keep_nan(s) : s);
+}
+
+// the weights of conv2..conv6 as bf16, one launch (pack_lp_body, ndp_device.h: k_fm_pack_lp's body)
+__global__ __launch_bounds__(kThreads) void k_enc_pack_lp(PackLpArgs a) { pack_lp_body(a); }
 
 // conv1: 3 -> 64 channels, 3x3 stride 2 pad 1, 128x128 -> 64x64, BatchNorm folded, ReLU; reads the reference's NCHW
 // images, writes NHWC.  K = 27 (padded to 32 with zero weights) is a single 32-wide K step of the matrix pipe:
@@ -200,7 +361,9 @@ __device__ __forceinline__ void u8_norm_table(float* lut) {
 }
 
 // U8 = false: img is the reference's float tensor [n][3][128][128]; true: byte frames [n][128][128][3]
-template <bool U8>
+// LP (precision NDP_ENC_BF16): the same fp32 arithmetic, the map stored as bf16 -- a.out is then a bf16 map, and a lane's
+// 4 consecutive channels are one 8-byte store
+template <bool U8, bool LP = false>
 __global__ __launch_bounds__(kThreads) void k_enc_conv1(Conv1Args a) {
   __shared__ __attribute__((aligned(16))) float As[128 * kC1LD];     // [pixel][k]
   __shared__ __attribute__((aligned(16))) float Ws[64 * kC1LD];      // [co][k], k = ci*9 + kh*3 + kw, 27..31 zero
@@ -316,8 +479,14 @@ __global__ __launch_bounds__(kThreads) void k_enc_conv1(Conv1Args a) {
       for (int i = 0; i < 2; ++i) {
         const int p = wave * 32 + i * 16 + c;
         const f32x4 v = acc[i][jn] + bv[jn];
-        float* dst = a.out + (((size_t)n * 64 + oh0 + (p >> 6)) * 64 + (p & 63)) * 64 + col;
-        *reinterpret_cast<f32x4*>(dst) = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+        if (LP) {
+          uint16_t* dst = reinterpret_cast<uint16_t*>(a.out) + (((size_t)n * 64 + oh0 + (p >> 6)) * 64 + (p & 63)) * 64 + col;
+          *reinterpret_cast<u32x2*>(dst) =
+              u32x2{fm_bf16_pair(relu_keep_nan(v[0]), relu_keep_nan(v[1])), fm_bf16_pair(relu_keep_nan(v[2]), relu_keep_nan(v[3]))};
+        } else {
+          float* dst = a.out + (((size_t)n * 64 + oh0 + (p >> 6)) * 64 + (p & 63)) * 64 + col;
+          *reinterpret_cast<f32x4*>(dst) = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+        }
       }
     }
     if (pair + 1 < kC1Pairs) stage();                                // (row 0 of In: overwritten, every later pair has ih >= 0)
@@ -351,11 +520,13 @@ static int64_t enc_ws_floats(int64_t n) {
 
 // K split of layer l for n images: the deep layers have few output tiles when n is small (conv5: 8 per 8 images);
 // the smallest divisor d of K / 32 that gives >= 512 workgroups (2 per CU), with tiles * d <= kEncPartBlocks
-static int enc_split(int l, int64_t n) {
+// (bk: the K step of the kernel that runs the layer -- k_conv_gemm's kEncBK is a build option, NDP_ENC_BK, and may differ
+// from k_conv_gemm_bf16's 32: a split must be whole steps of the kernel it is for)
+static int enc_split(int l, int64_t n, int bk = kEncBK) {
   const EncLayer& L = kEnc[l];
   const int64_t m = n * L.hout * L.hout;
   const int64_t tiles = ((m + kEncBM - 1) / kEncBM) * (L.cout / kEncBN);
-  const int steps = L.ksz * L.ksz * L.cin / kEncBK;
+  const int steps = L.ksz * L.ksz * L.cin / bk;
   int best = 1;
   for (int d = 1; d <= steps && d <= 128; ++d) {
     if (steps % d != 0 || tiles * d > kEncPartBlocks) continue;
@@ -367,21 +538,31 @@ static int enc_split(int l, int64_t n) {
 
 static std::once_flag g_enc_attr_once[kMaxDevices];
 
-static int launch_conv_gemm(int l, const float* in, const float* params, float* out, int64_t n, float* part, hipStream_t st) {
-  const int nsplit = enc_split(l, n);
-  float* final_out = out;
-  if (nsplit > 1) out = part;
-  std::call_once(device_once(g_enc_attr_once), [] { allow_lds(k_conv_gemm, conv_gemm_lds_floats() * 4); });
+// layer l of n images as a GEMM launch: the geometry, the bias, the K split (the operands and the output: the caller's)
+static ConvGemmArgs conv_gemm_args(int l, const float* params, int64_t n, int nsplit) {
   const EncLayer& L = kEnc[l];
   ConvGemmArgs a;
-  a.in = in; a.w = params + enc_param_offset(l, false); a.bias = params + enc_param_offset(l, true); a.out = out;
+  a.in = nullptr; a.w = nullptr; a.bias = params + enc_param_offset(l, true); a.out = nullptr;
   a.H = a.W = L.hin; a.Cin = L.cin; a.OH = a.OW = L.hout; a.Cout = L.cout;
   a.KW = L.ksz; a.stride = L.stride; a.pad = L.pad;
   a.M = (int)(n * L.hout * L.hout); a.K = L.ksz * L.ksz * L.cin;
   a.relu = l < 5 ? 1 : 0;
   a.nsplit = nsplit; a.k_per_split = a.K / nsplit;
   a.mtiles = (a.M + kEncBM - 1) / kEncBM; a.ntiles = L.cout / kEncBN;
-  const dim3 grid((unsigned)(a.mtiles >= 8 ? 8 * ((a.mtiles + 7) / 8) * a.ntiles : a.mtiles * a.ntiles), (unsigned)nsplit);
+  return a;
+}
+static dim3 conv_gemm_grid(const ConvGemmArgs& a) {
+  return dim3((unsigned)(a.mtiles >= 8 ? 8 * ((a.mtiles + 7) / 8) * a.ntiles : a.mtiles * a.ntiles), (unsigned)a.nsplit);
+}
+
+static int launch_conv_gemm(int l, const float* in, const float* params, float* out, int64_t n, float* part, hipStream_t st) {
+  const int nsplit = enc_split(l, n);
+  float* final_out = out;
+  if (nsplit > 1) out = part;
+  std::call_once(device_once(g_enc_attr_once), [] { allow_lds(k_conv_gemm, conv_gemm_lds_floats() * 4); });
+  ConvGemmArgs a = conv_gemm_args(l, params, n, nsplit);
+  a.in = in; a.w = params + enc_param_offset(l, false); a.out = out;
+  const dim3 grid = conv_gemm_grid(a);
   KTimer kt(l == 5 ? "k_conv_gemm[6]" : (l == 1 ? "k_conv_gemm[2]" : (l == 2 ? "k_conv_gemm[3]" : (l == 3 ? "k_conv_gemm[4]" : "k_conv_gemm[5]"))), st);
   hipLaunchKernelGGL(k_conv_gemm, grid, dim3(kThreads), conv_gemm_lds_floats() * 4, st, a);
   int rc = check_launch("k_conv_gemm");
@@ -393,6 +574,67 @@ static int launch_conv_gemm(int l, const float* in, const float* params, float* 
   return check_launch("k_splitk_reduce");
 }
 
+// ---- precision NDP_ENC_BF16
+static std::once_flag g_enc_lp_attr_once[kMaxDevices];
+static const char* const kEncLpLabel[6] = {"k_enc_conv1_bf16", "k_conv_gemm_bf16[2]", "k_conv_gemm_bf16[3]", "k_conv_gemm_bf16[4]",
+                                           "k_conv_gemm_bf16[5]", "k_conv_gemm_bf16[6]"};
+static int64_t enc_lp_w_offset(int l) {        // conv l + 1's bf16 weights (l = 1..5; 6: the end), in bf16 elements
+  int64_t o = 0;
+  for (int i = 1; i < l; ++i) o += enc_w_floats(i);
+  return o;
+}
+static int64_t enc_lp_act_offset(int l, int64_t n) {   // map l (0..4; 5: the end) of a pass of n images, in bf16 elements
+  int64_t o = 0;
+  for (int i = 0; i < l; ++i) o += n * enc_act_floats(i);
+  return o;
+}
+
+// layer l = 1..5 with bf16 operands: `in` the bf16 map of layer l - 1, `out` a bf16 map (l < 5) or the fp32 codes (l == 5)
+static int launch_conv_gemm_bf16(int l, const uint16_t* in, const float* params, const uint16_t* lp, void* out, int64_t n,
+                                 float* part, hipStream_t st) {
+  const int nsplit = enc_split(l, n, kEncLpBK);
+  std::call_once(device_once(g_enc_lp_attr_once), [] {
+    allow_lds(k_conv_gemm_bf16<true>, conv_gemm_bf16_lds_bytes());
+    allow_lds(k_conv_gemm_bf16<false>, conv_gemm_bf16_lds_bytes());
+  });
+  ConvGemmArgs a = conv_gemm_args(l, params, n, nsplit);
+  a.in = reinterpret_cast<const float*>(in); a.w = reinterpret_cast<const float*>(lp + enc_lp_w_offset(l));
+  a.out = nsplit > 1 ? part : static_cast<float*>(out);
+  {
+    KTimer kt(kEncLpLabel[l], st);
+    if (l < 5) hipLaunchKernelGGL(k_conv_gemm_bf16<true>, conv_gemm_grid(a), dim3(kThreads), conv_gemm_bf16_lds_bytes(), st, a);
+    else hipLaunchKernelGGL(k_conv_gemm_bf16<false>, conv_gemm_grid(a), dim3(kThreads), conv_gemm_bf16_lds_bytes(), st, a);
+  }
+  int rc = check_launch("k_conv_gemm_bf16");
+  if (rc || nsplit == 1) return rc;
+  const int64_t mc = (int64_t)a.M * a.Cout;
+  if (l < 5) {
+    KTimer kt2("k_splitk_reduce_bf16", st);
+    hipLaunchKernelGGL(k_splitk_reduce_bf16, dim3((unsigned)((mc + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                       part, nsplit, mc, a.bias, a.Cout, a.relu, static_cast<__bf16*>(out));
+    return check_launch("k_splitk_reduce_bf16");
+  }
+  KTimer kt2("k_splitk_reduce", st);
+  hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((mc + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                     part, nsplit, mc, a.bias, a.Cout, a.relu, static_cast<float*>(out));
+  return check_launch("k_splitk_reduce");
+}
+
+static int enc_pack_lp(const float* params, uint16_t* lp, hipStream_t st) {
+  PackLpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.dst = lp;
+  for (int l = 1; l < 6; ++l) {
+    const int i = a.nseg++;
+    a.src[i] = params + enc_param_offset(l, false);
+    a.dst_off[i] = enc_lp_w_offset(l); a.count[i] = enc_w_floats(l);
+    a.block_begin[i + 1] = a.block_begin[i] + (int)((a.count[i] + 4095) / 4096);
+  }
+  KTimer kt("k_enc_pack_lp", st);
+  hipLaunchKernelGGL(k_enc_pack_lp, dim3((unsigned)a.block_begin[a.nseg]), dim3(kThreads), 0, st, a);
+  return check_launch("k_enc_pack_lp");
+}
+
 }  // namespace ndp
 
 extern "C" {
@@ -401,12 +643,36 @@ int64_t ndp_encoder_param_floats(void) { return ndp::enc_param_offset(6, false);
 
 int64_t ndp_encoder_workspace_floats(int64_t n_images) { return n_images < 1 ? 0 : ndp::enc_ws_floats(n_images); }
 
+// lp: the bf16 weights of ndp_encoder_pack_params_lp -> a NDP_ENC_BF16 pass (bf16 maps at the head of the workspace, the
+// fp32 partial sums behind them); null: the fp32 pass
 static int encoder_forward_any(const float* packed_params, const void* images, bool u8, int64_t n_images, float* codes,
-                               float* workspace, void* stream) {
+                               float* workspace, void* stream, const uint16_t* lp = nullptr) {
   using namespace ndp;
   hipStream_t st = (hipStream_t)stream;
   for (int64_t n0 = 0; n0 < n_images; n0 += kEncChunk) {
     const int64_t n = n_images - n0 < kEncChunk ? n_images - n0 : kEncChunk;
+    if (lp != nullptr) {
+      uint16_t* maps = reinterpret_cast<uint16_t*>(workspace);
+      float* part = reinterpret_cast<float*>(maps + enc_lp_act_offset(5, n));
+      const size_t first = (size_t)n0 * 3 * 128 * 128;
+      Conv1Args c1{u8 ? (const void*)(static_cast<const unsigned char*>(images) + first)
+                      : (const void*)(static_cast<const float*>(images) + first),
+                   packed_params + enc_param_offset(0, false), packed_params + enc_param_offset(0, true),
+                   reinterpret_cast<float*>(maps), n};
+      {
+        KTimer kt(kEncLpLabel[0], st);
+        if (u8) hipLaunchKernelGGL((k_enc_conv1<true, true>), dim3((unsigned)(n * kC1Groups)), dim3(kThreads), 0, st, c1);
+        else hipLaunchKernelGGL((k_enc_conv1<false, true>), dim3((unsigned)(n * kC1Groups)), dim3(kThreads), 0, st, c1);
+      }
+      int rc = check_launch("k_enc_conv1_bf16");
+      if (rc) return rc;
+      for (int l = 1; l < 6; ++l) {
+        void* out = l < 5 ? (void*)(maps + enc_lp_act_offset(l, n)) : (void*)(codes + n0 * 128);
+        rc = launch_conv_gemm_bf16(l, maps + enc_lp_act_offset(l - 1, n), packed_params, lp, out, n, part, st);
+        if (rc) return rc;
+      }
+      continue;
+    }
     float* act[5];
     float* p = workspace;
     for (int l = 0; l < 5; ++l) { act[l] = p; p += n * enc_act_floats(l); }
@@ -446,6 +712,36 @@ int ndp_encoder_forward_u8(const float* packed_params, const uint8_t* frames_hwc
   NDP_CHECK_ARG(aligned16(packed_params) && aligned16(codes) && aligned16(workspace),
                 "ndp_encoder_forward_u8: buffers must be 16-byte aligned");
   return encoder_forward_any(packed_params, frames_hwc, true, n_images, codes, workspace, stream);
+}
+
+int64_t ndp_encoder_lp_weight_bytes(void) { return 2 * ndp::enc_lp_w_offset(6); }
+
+int64_t ndp_encoder_lp_act_offset(int layer, int64_t n_images) {
+  if (layer < 0 || layer > 4 || n_images < 1) return -1;
+  return ndp::enc_lp_act_offset(layer, n_images < ndp::kEncChunk ? n_images : ndp::kEncChunk);
+}
+
+int ndp_encoder_pack_params_lp(const float* packed_params, void* lp_weights, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(packed_params && lp_weights, "ndp_encoder_pack_params_lp: bad arguments");
+  NDP_CHECK_ARG(aligned16(packed_params) && aligned16(lp_weights), "ndp_encoder_pack_params_lp: buffers must be 16-byte aligned");
+  return enc_pack_lp(packed_params, static_cast<uint16_t*>(lp_weights), (hipStream_t)stream);
+}
+
+int ndp_encoder_forward_lp(const float* packed_params, const float* images, const uint8_t* frames_hwc, int64_t n_images,
+                           int precision, const void* lp_weights, float* codes, float* workspace, void* stream) {
+  using namespace ndp;
+  NDP_CHECK_ARG(precision == NDP_ENC_FP32 || precision == NDP_ENC_BF16, "ndp_encoder_forward_lp: precision %d is neither "
+                "NDP_ENC_FP32 nor NDP_ENC_BF16", precision);
+  NDP_CHECK_ARG((images != nullptr) != (frames_hwc != nullptr), "ndp_encoder_forward_lp: exactly one of images and frames_hwc");
+  NDP_CHECK_ARG(packed_params && codes && workspace && n_images >= 1, "ndp_encoder_forward_lp: bad arguments");
+  NDP_CHECK_ARG(aligned16(packed_params) && aligned16(codes) && aligned16(workspace) && (images == nullptr || aligned16(images)),
+                "ndp_encoder_forward_lp: buffers must be 16-byte aligned");
+  NDP_CHECK_ARG(precision == NDP_ENC_FP32 || (lp_weights != nullptr && aligned16(lp_weights)),
+                "ndp_encoder_forward_lp: NDP_ENC_BF16 needs the 16-byte aligned bf16 weights of ndp_encoder_pack_params_lp");
+  const bool u8 = frames_hwc != nullptr;
+  return encoder_forward_any(packed_params, u8 ? (const void*)frames_hwc : (const void*)images, u8, n_images, codes, workspace,
+                             stream, precision == NDP_ENC_BF16 ? static_cast<const uint16_t*>(lp_weights) : nullptr);
 }
 
 }  // extern "C"

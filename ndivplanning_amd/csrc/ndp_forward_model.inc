@@ -552,15 +552,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
 // 2-way for 3 of them; s = 6 sends any 8 consecutive rows to the 8 even slots and the rows at q + 1 to the odd ones:
 // conflict-free, which s = 2 (smaller than a row) is the only smaller stride to do.  (Measured: no conflict cycle from the
 // reads; the 8-byte staging stores, two consecutive rows per 16-lane group and banked modulo 128 bytes, are 2-way: DESIGN 5s.)
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+// (bf16x2, bf16x8, u32x2 and fm_bf16_pair: ndp_device.h, shared with k_conv_gemm_bf16 of ndp_encoder.inc)
 constexpr int kFmLpLD = 48;
 template <int BN> constexpr int fm_gemm_bf16_lds_bytes() { return 2 * (kFmBM + BN) * kFmLpLD * 2; }
-__device__ __forceinline__ uint32_t fm_bf16_pair(float lo, float hi) {
-  const bf16x2 v = {(__bf16)lo, (__bf16)hi};                           // fptrunc: round to nearest even (v_cvt_pk_bf16_f32)
-  return __builtin_bit_cast(uint32_t, v);
-}
 
 template <int BN>
 __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm_bf16(FmGemmArgs a) {
@@ -716,26 +710,9 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm_bf16(FmGemmArgs a) {
   }
 }
 
-// fp32 -> bf16 copies of the weights k_fm_gemm_bf16 reads, one launch for all of a network's segments: 4,096 values per
-// workgroup, 16 bytes in and 8 bytes out per thread and pass.
-constexpr int kFmLpMaxSegs = 12;
-struct FmPackLpArgs {
-  const float* src[kFmLpMaxSegs]; int64_t dst_off[kFmLpMaxSegs], count[kFmLpMaxSegs];
-  int block_begin[kFmLpMaxSegs + 1]; int nseg;
-  uint16_t* dst;
-};
-__global__ __launch_bounds__(kThreads) void k_fm_pack_lp(FmPackLpArgs a) {
-  int s = 0;
-  while (s + 1 < a.nseg && (int)blockIdx.x >= a.block_begin[s + 1]) ++s;
-  const int64_t base = (int64_t)((int)blockIdx.x - a.block_begin[s]) * 4096;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int64_t i = base + (int64_t)(it * kThreads + (int)threadIdx.x) * 4;
-    if (i >= a.count[s]) return;                                       // (counts are multiples of 4)
-    const f32x4 v = ldg4<4>(a.src[s] + i);
-    *reinterpret_cast<u32x2*>(a.dst + a.dst_off[s] + i) = u32x2{fm_bf16_pair(v[0], v[1]), fm_bf16_pair(v[2], v[3])};
-  }
-}
+// fp32 -> bf16 copies of the weights k_fm_gemm_bf16 reads, one launch for all of a network's segments (pack_lp_body,
+// ndp_device.h: the encoder's k_enc_pack_lp runs the same body)
+__global__ __launch_bounds__(kThreads) void k_fm_pack_lp(PackLpArgs a) { pack_lp_body(a); }
 
 // deconv6 (128 -> 32 channels at 128 x 128; deconv5, 64 channels, as two halves when it has the tiles): the FOUR parity
 // classes of a row tile in one workgroup.  As four mode-1
@@ -3271,12 +3248,12 @@ static int fm_pack(hipStream_t st, const FmNet& net, const float* params, const 
 
 // the bf16 weights of the fm_lp_layer layers from P1 (params) / P2 (the workspace head, packed before), one launch
 static int fm_pack_lp(hipStream_t st, const FmNet& net, const float* params, const FmWs& ws, uint16_t* lp) {
-  FmPackLpArgs a;
+  PackLpArgs a;
   memset(&a, 0, sizeof(a));
   a.dst = lp;
   for (int l = 0; l < net.layers; ++l) {
     if (!fm_lp_layer(net, l)) continue;
-    if (a.nseg == kFmLpMaxSegs) return fail(NDP_E_UNSUPPORTED, "forward model: more than %d bf16 layers", kFmLpMaxSegs);
+    if (a.nseg == kPackLpMaxSegs) return fail(NDP_E_UNSUPPORTED, "forward model: more than %d bf16 layers", kPackLpMaxSegs);
     const int i = a.nseg++;
     a.src[i] = net.layer[l].kind == FM_CONV ? params + fm_param_offset(net, l, false) : ws.p2 + fm_p2_offset(net, l);
     a.dst_off[i] = fm_lp_offset(net, l); a.count[i] = fm_w_floats(net, l);

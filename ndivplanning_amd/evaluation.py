@@ -2,8 +2,8 @@
 (control_evaluation.py: open loop, complete_eval.py: closed loop, mpc_eval.py: model-predictive control).
 
 `EvalModels` packs the image encoder, the forward model and the generator once into the flat vectors their kernels read
-(the modules' own pack helpers) and calls the kernels directly: `ndp_encoder_forward`, `ndp_g_forward`, `ndp_fm_forward`
-(eval mode), and the evaluation glue of csrc/ndp_eval.inc (`ndp_eval_*`: pair MSEs, rollout selection, the generator's
+(the modules' own pack helpers) and calls the kernels directly: `ndp_encoder_forward_lp`, `ndp_g_forward`, `ndp_fm_forward_lp`
+(eval mode, in the precisions `enc_precision` / `fm_precision` name; 'fp32' is `ndp_encoder_forward` / `ndp_fm_forward`), and the evaluation glue of csrc/ndp_eval.inc (`ndp_eval_*`: pair MSEs, rollout selection, the generator's
 code input, byte-frame normalisation).  Every result is a device tensor.  `mpc_plan` on frames and actions that are
 already on the device makes no host synchronisation until its results are read; inputs on the host are uploaded with
 ordinary (blocking) copies, and open_loop / closed_loop upload small index tensors at every step.
@@ -36,8 +36,8 @@ refined by gradient descent on the planner's score and replace the worst ones.  
 import torch
 
 from . import _capi, jpeg
-from ._eval_io import (FM_PRECISIONS, config_cli, device_of, fm_precision_code, fm_precision_of,  # noqa: F401 (device_of,
-                       load_eval_models)                                                        # fm_precision_of: for the scripts)
+from ._eval_io import (ENC_PRECISIONS, FM_PRECISIONS, config_cli, device_of, enc_precision_code,  # noqa: F401 (device_of,
+                       enc_precision_of, fm_precision_code, fm_precision_of, load_eval_models)   # *_precision_of: for the scripts)
 from .models.forward_encoder import pack_module
 from .models.image_autoencoder import pack_encoder_params
 
@@ -52,11 +52,16 @@ def _ptr(t):
 class EvalModels:
     """The three trained modules, packed once for the kernels (eval mode: BatchNorm with running statistics)."""
 
-    def __init__(self, image_encoder, fwd_model_autoencoder, generator, device=None, fm_precision="fp32"):
+    def __init__(self, image_encoder, fwd_model_autoencoder, generator, device=None, fm_precision="fp32", enc_precision="fp32"):
         """fm_precision: 'fp32', or 'bf16' -- `forward` (every pass of the planner's rollouts) runs the nine stride-2 layers
-        with bf16 operands and fp32 accumulation (NDP_FM_BF16, include/ndp.h); forward_keep / input_grads stay fp32."""
+        with bf16 operands and fp32 accumulation (NDP_FM_BF16, include/ndp.h); forward_keep / input_grads stay fp32.
+        enc_precision: 'fp32', or 'bf16' -- `encode` (the state codes and the goal code alike) runs conv2..conv6 with bf16
+        operands and bf16 maps (NDP_ENC_BF16, include/ndp.h); the weights are rounded once, here.  The two combine freely,
+        and with cem= and grad= (the gradient stage never passes through the encoder)."""
         self._fm_precision_code = fm_precision_code(fm_precision)
         self.fm_precision = fm_precision
+        self._enc_precision_code = enc_precision_code(enc_precision)
+        self.enc_precision = enc_precision
         if device is None:
             device = next(fwd_model_autoencoder.parameters()).device
         device = torch.device(device)
@@ -79,6 +84,12 @@ class EvalModels:
         with torch.no_grad():
             self.g_params = generator.flat_parameters().detach().to(device).clone()
         self._enc_ws = None
+        self._enc_lp = None              # the bf16 weights of conv2..conv6 (ndp_encoder_pack_params_lp)
+        if self._enc_precision_code:
+            self._enc_lp = torch.empty(self.lib.ndp_encoder_lp_weight_bytes(), dtype=torch.uint8, device=device)
+            with _capi.on_device(device):
+                _capi.check(self.lib.ndp_encoder_pack_params_lp(_ptr(self.enc_params), _ptr(self._enc_lp), self._stream()),
+                            "ndp_encoder_pack_params_lp")
         self._fm_ws, self._fm_n = None, 0
         self._fm_lp = None               # the bf16 weights (ndp_fm_pack_params_lp), rebuilt with every ndp_fm_pack_params
         self._mse_ws = None
@@ -95,8 +106,9 @@ class EvalModels:
             self._enc_ws = torch.empty(need, dtype=torch.float32, device=self.device)
         codes = torch.empty(n, 128, dtype=torch.float32, device=self.device)
         with _capi.on_device(self.device):
-            _capi.check(self.lib.ndp_encoder_forward(_ptr(self.enc_params), _ptr(images), n, _ptr(codes), _ptr(self._enc_ws),
-                                                     self._stream()), "ndp_encoder_forward")
+            _capi.check(self.lib.ndp_encoder_forward_lp(_ptr(self.enc_params), _ptr(images), None, n, self._enc_precision_code,
+                                                        _ptr(self._enc_lp), _ptr(codes), _ptr(self._enc_ws), self._stream()),
+                        "ndp_encoder_forward_lp")
         return codes
 
     def generate(self, code, noise, code_rep=1, out=None):
@@ -1337,6 +1349,8 @@ def script_main(fetch, argv=None, add_arguments=None, prepare=None):
     parser = add_common_arguments(parser)
     parser.add_argument("--fm-precision", choices=FM_PRECISIONS, default=None,
                         help="operand precision of the forward model's passes (default: evaluation.fm_precision, else fp32)")
+    parser.add_argument("--enc-precision", choices=ENC_PRECISIONS, default=None,
+                        help="precision of the image encoder's passes (default: evaluation.enc_precision, else fp32)")
     if add_arguments is not None:
         add_arguments(parser)
     _, config, wrapped = config_cli(parser, argv, "evaluation", prepare)

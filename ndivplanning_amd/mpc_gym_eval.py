@@ -146,7 +146,7 @@ def fetch_push_control_evaluation(args, image_encoder, fwd_model_autoencoder, ge
     seed, k, nz, bs, r, th, t = _settings(config, dataset, generator)
     t1 = t - 1
     models = E.EvalModels(image_encoder, fwd_model_autoencoder, generator, E.device_of(config),
-                          fm_precision=E.fm_precision_of(config))
+                          fm_precision=E.fm_precision_of(config), enc_precision=E.enc_precision_of(config))
     dev = models.device
     torch.manual_seed(seed)
     np.random.seed(seed)

@@ -517,6 +517,8 @@ def _mpc_main(argv):
     parser.add_argument("--start", default="simplified")
     parser.add_argument("--fm-precision", choices=E.FM_PRECISIONS, default=None,
                         help="operand precision of the forward model's passes (default: evaluation.fm_precision, else fp32)")
+    parser.add_argument("--enc-precision", choices=E.ENC_PRECISIONS, default=None,
+                        help="precision of the image encoder's passes (default: evaluation.enc_precision, else fp32)")
 
     def check(ns):
         _check_n(ns.envs)
@@ -526,7 +528,8 @@ def _mpc_main(argv):
     image_encoder, generator, fwd_model_autoencoder, gpu_id = load_eval_models(config)
     for module in (image_encoder, generator, fwd_model_autoencoder):
         module.eval()
-    models = E.EvalModels(image_encoder, fwd_model_autoencoder, generator, gpu_id, fm_precision=E.fm_precision_of(config))
+    models = E.EvalModels(image_encoder, fwd_model_autoencoder, generator, gpu_id, fm_precision=E.fm_precision_of(config),
+                          enc_precision=E.enc_precision_of(config))
     r, th = int(config.mpc.rollouts), int(config.mpc.time_horizon)
     result = evaluate_mpc(models, namespace.envs, namespace.steps, r, th, cem=E.cem_from_config(config, r, th),
                           seed=int(config.random_seed), start=namespace.start,
