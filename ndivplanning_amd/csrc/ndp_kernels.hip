@@ -1265,7 +1265,7 @@ struct WgradJob {
   int lda, ldb;
   int a_cols, b_cols;
   int b_rowmod, b_rowdiv, b_rowmax;
-  int b_vec;           // B rows 16-byte aligned
+  int b_vec;           // B rows 16-byte aligned (host side; wgrad_loop reads B the same way whatever it says)
   int dst_off, dst_ld; // slab[dst_off + j*dst_ld + k]
   int bias_off;        // slab[bias_off + j] = sum_rows dY[row][j], or -1
   int kind;
@@ -1320,6 +1320,140 @@ __host__ __device__ __forceinline__ void wgrad_slot(int njobs, int nwide, int wi
 #define NDP_WSTAMP(i) do { } while (0)
 #endif
 
+// B-row map of a job, chosen once per workgroup (wgrad_block): row -> B row
+//   WB_PLAIN    min(row, b_rowmax)                         fc2.. and the skinny jobs; G's fc1 codes with code_rep == 1
+//   WB_DIV      min((row mod b_rowmod) / b_rowdiv, b_rowmax)   codes broadcast over the K samples and both passes; D's
+//               fc1 codes outside the fused step always (b_rowmod = the pass' rows), with b_rowdiv == 1 too
+//   WB_SEG      segment-sum entry -> code row (WgradJob::seg)
+//   WB_SEGWRAP  the same with plain rows from seg_wrap on
+enum { WB_PLAIN = 0, WB_DIV = 1, WB_SEG = 2, WB_SEGWRAP = 3 };
+
+// The rows of a chunk into a wave's accumulators and bias sums, for one B-row map.
+template <int MT, int NT, int KIND, int BMAP>
+__device__ __forceinline__ void wgrad_loop(const WgradJob& jb, int rbeg, int rend, int row_last,
+                                           f32x4 (&acc)[MT][NT], float (&bs)[MT]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int c = lane & 15, q = lane >> 4;
+  // Main loop.  A wave takes rows rbeg + 16 t + 4 wave + q of step t (nsteps steps).  Operands go through a register
+  // ring of PF steps: slot p holds step t (t % PF == p); once that step's MFMAs are ISSUED the slot's own registers are
+  // the destination of the loads of step t + PF, so a load has (PF - 1) * 16 MFMAs to land and the old and the new
+  // value of a slot are never live together (no second register set, no copy on the back-edge).  The fences keep
+  // hipcc from hoisting a refill above the MFMAs that still read the slot; ahead of step t it waits for slot t % PF
+  // alone, with a counted vmcnt that leaves the PF - 1 younger steps' loads in flight, across the back-edge too.
+  // Every load is UNconditional (rows past the end are clamped to a valid row and simply never consumed; narrow
+  // operands are loaded from a clamped column and zeroed by a select): a branch around a load makes hipcc fall back
+  // to s_waitcnt vmcnt(0) inside the loop.  Nothing uniform per workgroup is decided in here: the B-row map is a
+  // template parameter, and B rows are read as four floats of 4-byte alignment whatever WgradJob::b_vec says -- one
+  // global_load_dwordx4 either way (the fc1 codes of a caller with ld_code % 4 != 0 are the only unaligned operand).
+  // The plain maps step a clamped pointer (one 64-bit add and a min per step).
+  constexpr int PF = kWgradPrefetch;
+  constexpr bool SEG = BMAP == WB_SEG || BMAP == WB_SEGWRAP;
+  const float b_inv = 1.0f / (float)(SEG ? jb.seg_k : jb.b_rowdiv);
+  const float s_inv = 1.0f / (float)(SEG ? jb.seg_s : 1);
+  const int nsteps = rend > rbeg ? (rend - rbeg) >> 4 : 0;
+  const int row_first = rbeg + 4 * wave + q;
+  const int ca = KIND == WG_SKINNY_A ? (c < jb.a_cols ? c : jb.a_cols - 1) : 4 * c;
+  const int cb = KIND == WG_SKINNY_B ? (c < jb.b_cols ? c : jb.b_cols - 1) : 4 * c;
+  const bool a_on = KIND != WG_SKINNY_A || c < jb.a_cols;
+  const bool b_on = KIND != WG_SKINNY_B || c < jb.b_cols;
+  f32x4 ra[PF], rb[PF];
+  // the next step's operand addresses; rows only grow, so min(row, last) is min(pointer, pointer of the last row)
+  const int b_last = row_last < jb.b_rowmax ? row_last : jb.b_rowmax;
+  const float* pa = jb.A + (size_t)(row_first < row_last ? row_first : row_last) * jb.lda + ca;
+  const float* const pa_last = jb.A + (size_t)row_last * jb.lda + ca;
+  const size_t a_step = (size_t)16 * jb.lda, b_step = (size_t)16 * jb.ldb;
+  const float* pb = jb.B + (size_t)(row_first < b_last ? row_first : b_last) * jb.ldb + cb;    // WB_PLAIN
+  const float* const pb_last = jb.B + (size_t)b_last * jb.ldb + cb;
+  int nrow = row_first;                                                                        // the other maps
+  auto b_row = [&](int r) -> int {
+    int row = r < row_last ? r : row_last;
+    // the codes are broadcast over the K samples and both passes: rows wrap at most once and divide through a float
+    // reciprocal + fix-up (rows < 2^24): an integer division costs ~40 VALU issues per step and un-hides the MFMAs
+    int brow;
+    if (SEG) {
+      // entry -> (tile, s) -> code row (16*tile)/K + s; exact divisions by reciprocal + fix-up
+      // (as a mask the compiler cannot see through: as a select hipcc turns it into a branch around the divisions,
+      // which splits the step's block and leaves the arithmetic behind the MFMAs instead of between them)
+      int ident = BMAP == WB_SEGWRAP && row >= jb.seg_wrap ? -1 : 0;
+      if (BMAP == WB_SEGWRAP) asm("" : "+v"(ident));
+      const int e = row & ~ident;
+      int tile = (int)((float)e * s_inv);
+      tile = tile * jb.seg_s > e ? tile - 1 : tile;
+      tile = (tile + 1) * jb.seg_s <= e ? tile + 1 : tile;
+      const int x = 16 * tile;
+      int f0 = (int)((float)x * b_inv);
+      f0 = f0 * jb.seg_k > x ? f0 - 1 : f0;
+      f0 = (f0 + 1) * jb.seg_k <= x ? f0 + 1 : f0;
+      brow = ((row - jb.seg_wrap) & ident) | ((f0 + (e - tile * jb.seg_s)) & ~ident);
+    } else {
+      const int x = row >= jb.b_rowmod ? row - jb.b_rowmod : row;
+      int qd = (int)((float)x * b_inv);
+      qd = qd * jb.b_rowdiv > x ? qd - 1 : qd;
+      qd = (qd + 1) * jb.b_rowdiv <= x ? qd + 1 : qd;
+      brow = qd;
+    }
+    return brow < jb.b_rowmax ? brow : jb.b_rowmax;
+  };
+  if (BMAP != WB_PLAIN) pb = jb.B + (size_t)b_row(nrow) * jb.ldb + cb;
+  auto advance = [&]() {                         // VALU only: hipcc places it between the MFMAs of the step that follows
+    const float* na = pa + a_step;
+    pa = (uintptr_t)na < (uintptr_t)pa_last ? na : pa_last;
+    if (BMAP == WB_PLAIN) {
+      const float* nb = pb + b_step;
+      pb = (uintptr_t)nb < (uintptr_t)pb_last ? nb : pb_last;
+    } else {
+      nrow += 16;
+      pb = jb.B + (size_t)b_row(nrow) * jb.ldb + cb;
+    }
+  };
+  auto load_a = [&]() -> f32x4 {
+    if (KIND == WG_SKINNY_A) return f32x4{*pa, 0.f, 0.f, 0.f};     // (zeroed where it is consumed: the select would wait)
+    return *reinterpret_cast<const f32x4*>(pa);
+  };
+  auto load_b = [&]() -> f32x4 {
+    if (KIND == WG_SKINNY_B) return f32x4{*pb, 0.f, 0.f, 0.f};
+    return f32x4{pb[0], pb[1], pb[2], pb[3]};
+  };
+  auto mma_step = [&](f32x4 va, f32x4 vb) {
+    if (KIND == WG_SKINNY_A) va[0] = a_on ? va[0] : 0.f;
+    if (KIND == WG_SKINNY_B) vb[0] = b_on ? vb[0] : 0.f;
+#pragma unroll
+    for (int u = 0; u < MT; ++u) {
+      bs[u] += va[u];
+#pragma unroll
+      for (int v = 0; v < NT; ++v) acc[u][v] = mfma16(va[u], vb[v], acc[u][v]);
+      // the bias sum is taken HERE: left to itself hipcc gathers the adds of a whole pass behind its last step, which
+      // keeps every slot's old value live across its refill (a second register set and a copy again)
+      asm volatile("" : "+v"(bs[u]));
+    }
+  };
+#pragma unroll
+  for (int p = 0; p < PF; ++p) {
+    ra[p] = load_a();
+    rb[p] = load_b();
+    advance();
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  int t = 0;
+  for (; t + PF <= nsteps; t += PF) {
+#pragma unroll
+    for (int p = 0; p < PF; ++p) {
+      mma_step(ra[p], rb[p]);
+      __builtin_amdgcn_sched_barrier(0);         // the refill stays behind the MFMAs that read the slot ...
+      ra[p] = load_a();
+      rb[p] = load_b();
+      __builtin_amdgcn_sched_barrier(0);         // ... and ahead of the next step's
+      advance();
+    }
+  }
+  const int rem = nsteps - t;                    // < PF; slots 0..rem-1 hold those steps
+#pragma unroll
+  for (int p = 0; p < PF; ++p)
+    if (p < rem) mma_step(ra[p], rb[p]);
+}
+
+// One epilogue per job kind; the main loop is chosen beside it, once per workgroup, among what build_jobs can produce:
+// every B-row map for the full jobs, the plain map for the skinny ones.
 template <int MT, int NT, int KIND, bool WT>
 __device__ __forceinline__ void wgrad_block(const WgradJob& jb, int rbeg, int rend, int row_last,
                                             float* slab, float* smem, unsigned long long* wst) {
@@ -1333,100 +1467,17 @@ __device__ __forceinline__ void wgrad_block(const WgradJob& jb, int rbeg, int re
 #pragma unroll
     for (int v = 0; v < NT; ++v) acc[u][v] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
-  // Main loop.  A wave takes rows rbeg + 16 t + 4 wave + q of step t (nsteps steps).  Operands
-  // go through a register ring of PF steps: slot p is consumed by step t (t % PF == p) and
-  // refilled at once with step t + PF, so every load is issued PF*16 MFMAs before its use.
-  // Every load is UNconditional (rows past the end are clamped to a valid row and simply never
-  // consumed; narrow operands are loaded from a clamped column and zeroed by a select): a
-  // branch around a load makes hipcc fall back to s_waitcnt vmcnt(0) inside the loop.
-  constexpr int PF = kWgradPrefetch;
-  const bool seg_b = jb.seg != 0;
-  const bool plain_b = !seg_b && jb.b_rowdiv == 1 && jb.b_rowmod == 0x7fffffff;         // uniform per workgroup
-  const float b_inv = 1.0f / (float)(seg_b ? jb.seg_k : jb.b_rowdiv);
-  const float s_inv = 1.0f / (float)(seg_b ? jb.seg_s : 1);
-  const int nsteps = rend > rbeg ? (rend - rbeg) >> 4 : 0;
-  const int row_first = rbeg + 4 * wave + q;
-  const int ca = KIND == WG_SKINNY_A ? (c < jb.a_cols ? c : jb.a_cols - 1) : 4 * c;
-  const int cb = KIND == WG_SKINNY_B ? (c < jb.b_cols ? c : jb.b_cols - 1) : 4 * c;
-  const bool a_on = KIND != WG_SKINNY_A || c < jb.a_cols;
-  const bool b_on = KIND != WG_SKINNY_B || c < jb.b_cols;
-  f32x4 ra[PF], rb[PF];
-  auto load_a = [&](int t) -> f32x4 {
-    int row = row_first + 16 * t;
-    row = row < row_last ? row : row_last;
-    const float* p = jb.A + (size_t)row * jb.lda + ca;
-    if (KIND == WG_SKINNY_A) {
-      const float v = *p;
-      return f32x4{a_on ? v : 0.f, 0.f, 0.f, 0.f};
-    }
-    return *reinterpret_cast<const f32x4*>(p);
-  };
-  auto load_b = [&](int t) -> f32x4 {
-    int row = row_first + 16 * t;
-    row = row < row_last ? row : row_last;
-    // B row: min(((row mod b_rowmod) / b_rowdiv), b_rowmax).  Most jobs read B by the plain row;
-    // the others (codes, broadcast over the K samples and both passes) wrap at most once and
-    // divide through a float reciprocal + fix-up (rows < 2^24): an integer division costs ~40
-    // VALU issues per step and un-hides the MFMAs.
-    int brow = row;
-    if (seg_b) {
-      // entry -> (tile, s) -> code row (16*tile)/K + s; exact divisions by reciprocal + fix-up
-      const bool ident = jb.seg_wrap != 0 && row >= jb.seg_wrap;
-      const int e = ident ? 0 : row;
-      int tile = (int)((float)e * s_inv);
-      tile = tile * jb.seg_s > e ? tile - 1 : tile;
-      tile = (tile + 1) * jb.seg_s <= e ? tile + 1 : tile;
-      const int x = 16 * tile;
-      int f0 = (int)((float)x * b_inv);
-      f0 = f0 * jb.seg_k > x ? f0 - 1 : f0;
-      f0 = (f0 + 1) * jb.seg_k <= x ? f0 + 1 : f0;
-      brow = ident ? row - jb.seg_wrap : f0 + (e - tile * jb.seg_s);
-    } else if (!plain_b) {
-      const int x = row >= jb.b_rowmod ? row - jb.b_rowmod : row;
-      int qd = (int)((float)x * b_inv);
-      qd = qd * jb.b_rowdiv > x ? qd - 1 : qd;
-      qd = (qd + 1) * jb.b_rowdiv <= x ? qd + 1 : qd;
-      brow = qd;
-    }
-    brow = brow < jb.b_rowmax ? brow : jb.b_rowmax;
-    const float* p = jb.B + (size_t)brow * jb.ldb + cb;
-    if (KIND == WG_SKINNY_B) {
-      const float v = *p;
-      return f32x4{b_on ? v : 0.f, 0.f, 0.f, 0.f};
-    }
-    if (jb.b_vec) return *reinterpret_cast<const f32x4*>(p);
-    return f32x4{p[0], p[1], p[2], p[3]};
-  };
-  auto mma_step = [&](const f32x4& va, const f32x4& vb) {
-#pragma unroll
-    for (int u = 0; u < MT; ++u) {
-      bs[u] += va[u];
-#pragma unroll
-      for (int v = 0; v < NT; ++v) acc[u][v] = mfma16(va[u], vb[v], acc[u][v]);
-    }
-  };
   NDP_WSTAMP(1);
-#pragma unroll
-  for (int p = 0; p < PF; ++p) {
-    ra[p] = load_a(p);
-    rb[p] = load_b(p);
-  }
-  pin_vmem();
-  int t = 0;
-  for (; t + PF <= nsteps; t += PF) {
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-      const f32x4 va = ra[p], vb = rb[p];
-      ra[p] = load_a(t + p + PF);
-      rb[p] = load_b(t + p + PF);
-      pin_vmem();
-      mma_step(va, vb);
-    }
-  }
-  const int rem = nsteps - t;                    // < PF; slots 0..rem-1 hold those steps
-#pragma unroll
-  for (int p = 0; p < PF; ++p)
-    if (p < rem) mma_step(ra[p], rb[p]);
+#define NDP_WGRAD_LOOP(BMAP) wgrad_loop<MT, NT, KIND, BMAP>(jb, rbeg, rend, row_last, acc, bs)
+  if (KIND == WG_FULL) {
+    const int bmap = jb.seg != 0 ? (jb.seg_wrap != 0 ? WB_SEGWRAP : WB_SEG)
+                                 : (jb.b_rowdiv == 1 && jb.b_rowmod == 0x7fffffff ? WB_PLAIN : WB_DIV);
+    if (bmap == WB_PLAIN) NDP_WGRAD_LOOP(WB_PLAIN);
+    else if (bmap == WB_DIV) NDP_WGRAD_LOOP(WB_DIV);
+    else if (bmap == WB_SEG) NDP_WGRAD_LOOP(WB_SEG);
+    else NDP_WGRAD_LOOP(WB_SEGWRAP);
+  } else NDP_WGRAD_LOOP(WB_PLAIN);
+#undef NDP_WGRAD_LOOP
   NDP_WSTAMP(2);
   // ---- cross-wave reduction through LDS: tile image [JR][KC] per wave
   constexpr int JR = KIND == WG_SKINNY_A ? 16 : 64;

@@ -7,11 +7,13 @@ sys.path.insert(0, ROOT)
 import numpy as np, torch
 from ndivplanning_amd import _build, _capi
 
-lib_path = os.path.join(_build.LIB_DIR, "libndp_hip_stamps.so")
-extra = os.environ.get("NDP_CXXFLAGS", "").split()
-cmd = ["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-DNDP_STAMPS"] + extra + [
-       "-Wno-unused-value", "-Wno-pass-failed", os.path.join(_build.CSRC, "ndp_kernels.hip"), "-o", lib_path]
-subprocess.check_call(cmd)
+# NDP_STAMPS_LIB: use this -DNDP_STAMPS library instead of compiling one (e.g. another commit's, to compare)
+lib_path = os.environ.get("NDP_STAMPS_LIB") or os.path.join(_build.LIB_DIR, "libndp_hip_stamps.so")
+if not os.environ.get("NDP_STAMPS_LIB"):
+    extra = os.environ.get("NDP_CXXFLAGS", "").split()
+    cmd = ["hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-DNDP_STAMPS"] + extra + [
+           "-Wno-unused-value", "-Wno-pass-failed", os.path.join(_build.CSRC, "ndp_kernels.hip"), "-o", lib_path]
+    subprocess.check_call(cmd)
 _build.LIB_PATH = lib_path
 lib = _capi.load()
 raw = ctypes.CDLL(lib_path)
