@@ -44,6 +44,8 @@ class ForwardModelTrainer(FlatTrainer):
         self._place([model], "the model on a", batch, reduce_fn, bucket_reduce)
         self._allocate(FE.pack_module(model, self.device), lr, betas, eps, sync_batchnorm_world, stat_group)
         self.resid = torch.zeros(self.batch, 3, 128, 128, dtype=torch.float32, device=self.device) if keep_residual else None
+        self.forwards = 0                                            # training-mode forwards (num_batches_tracked)
+        self._batches0 = int(model.encoder.conv1_bn.num_batches_tracked.item())
         self._pack()
         self._workspaces = [self.workspace]                          # pass k of a rollout keeps its activations in [k]
         self._extra_stale = False                                    # the extra workspaces' second weight order is behind
@@ -95,6 +97,7 @@ class ForwardModelTrainer(FlatTrainer):
                 p(self.loss_sum), p(self.resid) if self.resid is not None else None, p(self.workspace),
                 _capi.stream_ptr(self.device), *self._stat_args()), "ndp_fm_train_grads_dp")
         self._stat_check()
+        self.forwards += 1
         return self.loss
 
     def step(self, state_cur, state_fut, actions):
@@ -151,6 +154,7 @@ class ForwardModelTrainer(FlatTrainer):
                                                p(self._locals[k - 1]), st), "ndp_fm_rollout_chain")
             c(lib.ndp_fm_grad_sum(p(self._step_grads), self._grad_stride, H, self.params.numel(), p(self.grad), st),
               "ndp_fm_grad_sum")
+        self.forwards += H                                           # every pass of the window moved the statistics
         return self.loss
 
     def step_rollout(self, frames, actions):
@@ -176,11 +180,15 @@ class ForwardModelTrainer(FlatTrainer):
     def load_from_module(self):
         """Take parameters and running statistics from the module again (after they were changed from outside)."""
         self.params, self.stats = FE.pack_module(self.model, self.device)
+        self._batches0 = int(self.model.encoder.conv1_bn.num_batches_tracked.item())
+        self.forwards = 0
         self._pack()
         self._extra_stale = True
 
     def sync_to_module(self):
-        FE.unpack_into_module(self.model, self.params, self.stats, batches_tracked=self.steps)
+        """num_batches_tracked counts training-mode forwards as torch's BatchNorm does (a window of H passes counts H, a
+        grads() without apply() counts), on top of what the module held when it was packed; .steps counts Adam steps."""
+        FE.unpack_into_module(self.model, self.params, self.stats, batches_tracked=self._batches0 + self.forwards)
         return self.model
 
     def _unpack(self, vec):

@@ -43,9 +43,12 @@ def main():
     # compared as tightly as the first
     for name, seed, data_seed, n in (("forward_model_case", 5, 6, 2), ("forward_model_case_sharp", 210, 1210, 1)):
         one_case(name, seed, data_seed, n)
+    # "forward_model_case_trained": the same two iterations from a state in which no bias, BatchNorm weight / bias,
+    # running statistic or batch counter has the value weight_init leaves (tests/trained_state.py: trained_like(state, seed))
+    one_case("forward_model_case_trained", 7, 8, 2, trained=True)
 
 
-def one_case(case_name, seed, data_seed, n):
+def one_case(case_name, seed, data_seed, n, trained=False):
     mpl = _stub("matplotlib")
     mpl.pyplot = _stub("matplotlib.pyplot")
     _stub("imageio")
@@ -60,6 +63,10 @@ def one_case(case_name, seed, data_seed, n):
     model = ForwardAutoencoder()
     model.decoder.weight_init(mean=0.0, std=0.02)                   # train_forward_model.py:69-70
     model.encoder.weight_init(mean=0.0, std=0.02)
+    if trained:
+        sys.path.insert(0, os.path.dirname(HERE))
+        from trained_state import trained_like
+        model.load_state_dict(trained_like(model.state_dict(), seed))
     model.train()
     mse = torch.nn.MSELoss()
     opt = torch.optim.Adam([{"params": model.decoder.parameters()}, {"params": model.encoder.parameters()}], lr=lr,
@@ -68,6 +75,8 @@ def one_case(case_name, seed, data_seed, n):
     frames = torch.rand(n, 3, 3, 128, 128, generator=gen) * 2.0 - 1.0          # [n, 3 frames, 3, 128, 128]
     actions = torch.rand(n, 3, 4, generator=gen) * 2.0 - 1.0
     rec = {"meta": np.array([seed, data_seed, n]), "lr": np.array(lr)}
+    if trained:
+        rec["trained"] = np.array(1)
     w64 = torch.cat([v.double().reshape(-1) for v in model.state_dict().values() if v.dtype.is_floating_point])
     rec["state_checksum"] = np.array([w64.sum().item(), w64.abs().sum().item(), float(w64.numel())])
     names = [k for k, _ in list(model.decoder.named_parameters(prefix="decoder")) + list(model.encoder.named_parameters(prefix="encoder"))]
@@ -87,6 +96,9 @@ def one_case(case_name, seed, data_seed, n):
     rec["names"] = np.array(names)
     sd = model.state_dict()
     rec["running_sums"] = np.stack([sums(sd[k]) for k in sd if "running_" in k])
+    if trained:                                                     # a BatchNorm in use and one that is never applied
+        rec["batches_tracked"] = np.array([int(sd["decoder.deconv3_bn.num_batches_tracked"]),
+                                           int(sd["encoder.conv4_bn.num_batches_tracked"])])
     path = os.path.join(HERE, case_name + ".npz")
     np.savez_compressed(path, **rec)
     print("wrote", path, os.path.getsize(path), "bytes; losses", rec["s0.loss"], rec["s1.loss"])

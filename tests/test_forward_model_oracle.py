@@ -23,12 +23,15 @@ def _inputs(data_seed, n):
 import pytest
 
 
-@pytest.mark.parametrize("case", ["forward_model_case", "forward_model_case_sharp"])
+@pytest.mark.parametrize("case", ["forward_model_case", "forward_model_case_sharp", "forward_model_case_trained"])
 def test_two_training_iterations_match_the_reference(case):
     g = load_golden(case)
     seed, data_seed, n = (int(v) for v in g["meta"])
     torch.set_num_threads(1)
     state = FO.init_forward_model_state(seed)
+    if "trained" in g:                                   # the same two iterations from a mid-training state
+        from trained_state import trained_like
+        state = trained_like(state, seed)
     w64 = torch.cat([v.double().reshape(-1) for v in _ref_order(state).values() if v.dtype.is_floating_point])
     # the fixture stores seeds, not 33 M weights: the RNG stream must have produced the same initial state
     np.testing.assert_allclose(np.array([w64.sum().item(), w64.abs().sum().item(), float(w64.numel())]),
@@ -56,6 +59,10 @@ def test_two_training_iterations_match_the_reference(case):
             assert abs(got[1] - wantp[1]) <= 1e-5 * max(wantp[1], 1e-12) + 1e-7, (name, it)
     running = np.stack([_sums(state[k]) for k in _ref_order(state) if "running_" in k])
     np.testing.assert_allclose(running, g["running_sums"], rtol=1e-5, atol=1e-7)
+    if "batches_tracked" in g:                           # a BatchNorm in use counts its two forwards; conv4_bn is never applied
+        assert [int(v) for v in g["batches_tracked"]] == [9, 7]
+        assert int(state["decoder.deconv3_bn.num_batches_tracked"]) == 9
+        assert int(state["encoder.conv4_bn.num_batches_tracked"]) == 7
 
 
 def test_eval_mode_adds_the_residual_and_uses_running_statistics():

@@ -18,12 +18,19 @@ DEV = "cuda:0"
 pytestmark = pytest.mark.gpu
 
 
-def _models(seed):
+def _models(seed, trained=False):
+    """trained: from a mid-training state (tests/trained_state.py) -- non-zero biases (deconv6's, which no BatchNorm
+    follows, among them: the k_ae_out_fwd_loss / k_ae_out_dgrad epilogues), BatchNorm weight / bias / running statistics
+    off 1 / 0 / 0 / 1, batch counters at 7."""
     from ndivplanning_amd.models.image_autoencoder import Decoder, Encoder
     torch.manual_seed(seed)
     enc, dec = Encoder(), Decoder()
     dec.weight_init(0.0, 0.02)
     enc.weight_init(0.0, 0.02)
+    if trained:
+        from trained_state import trained_like
+        enc.load_state_dict(trained_like(enc.state_dict(), seed))
+        dec.load_state_dict(trained_like(dec.state_dict(), seed + 1))
     return enc, dec
 
 
@@ -84,21 +91,24 @@ def _check(name, hip, f32, f64, floor):
     err = (hip - f64).abs().max().item()
     ref_err = (f32 - f64).abs().max().item()
     scale = f64.abs().max().item()
+    print("%s: |hip - fp64| %.3e, |fp32 - fp64| %.3e, scale %.3e" % (name, err, ref_err, scale))
     assert err <= 8 * ref_err + floor * max(scale, 1e-30), "%s: |hip - fp64| %.3e, |fp32 - fp64| %.3e, scale %.3e" % (
         name, err, ref_err, scale)
 
 
-@pytest.mark.parametrize("n", [1, 3, 16, 65, 240])
-def test_step_matches_fp64_elementwise(n):
+@pytest.mark.parametrize("n,trained", [pytest.param(n, False, id=str(n)) for n in (1, 3, 16, 65, 240)]
+                         + [pytest.param(n, True, id="trained-%d" % n) for n in (1, 3, 16)])
+def test_step_matches_fp64_elementwise(n, trained):
     torch.set_num_threads(16)
     x = _images(n, 100 + n)
-    tr, lh, gh, ph = _hip_step(*_models(7), x)
-    l64, g64, p64 = _cpu_step(*_models(7), x, torch.float64, tr.masks)
-    l32, g32, p32 = _cpu_step(*_models(7), x, torch.float32, tr.masks)
+    tracked = 7 if trained else 0                                      # the batch counters before the step
+    tr, lh, gh, ph = _hip_step(*_models(7, trained), x)
+    l64, g64, p64 = _cpu_step(*_models(7, trained), x, torch.float64, tr.masks)
+    l32, g32, p32 = _cpu_step(*_models(7, trained), x, torch.float32, tr.masks)
     assert abs(lh - l64) <= 8 * abs(l32 - l64) + 2e-6 * l64
     recon = tr.recon.cpu().double()
     with torch.no_grad():
-        enc, dec = _models(7)
+        enc, dec = _models(7, trained)
         want = dec.double().train()(enc.double().train()._forward_torch(x.double()))
     assert (recon - want).abs().max().item() <= 1e-4
     assert set(gh) == set(g64)
@@ -112,7 +122,7 @@ def test_step_matches_fp64_elementwise(n):
     lr = 2e-4
     for k in p64:
         if k.endswith("num_batches_tracked"):
-            assert ph[k].item() == p64[k].item() == (0 if k.startswith(("encoder.conv4_bn", "encoder.conv5_bn")) else 1), k
+            assert ph[k].item() == p64[k].item() == tracked + (0 if k.startswith(("encoder.conv4_bn", "encoder.conv5_bn")) else 1), k
         elif k.startswith(("encoder.conv4_bn", "encoder.conv5_bn")):
             assert torch.equal(ph[k], p64[k]), k                       # never applied: untouched
         elif k in NOISE_BIASES or k.endswith("running_mean"):

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import rollout_common as C
+import trained_state as TS
 from oracle import forward_model_oracle as FO
 
 pytestmark = pytest.mark.gpu
@@ -30,10 +31,14 @@ def _check(mine, ref32, ref64, what):
     assert err_mine <= max(2e-5, 2.0 * err_ref), (what, err_mine, err_ref)
 
 
-def _trainer(seed, n, **kw):
+def _trainer(seed, n, trained=False, **kw):
+    """trained: from a mid-training state (tests/trained_state.py): non-zero biases, BatchNorm weight / bias / running
+    statistics off 1 / 0 / 0 / 1, batch counters at 7."""
     from ndivplanning_amd.forward_trainer import ForwardModelTrainer
     from ndivplanning_amd.models import forward_encoder as FE
     state = FO.init_forward_model_state(seed)
+    if trained:
+        state = TS.trained_like(state, seed)
     model = FE.ForwardAutoencoder()
     model.load_state_dict(state)
     model = model.to(DEV).train()
@@ -71,14 +76,18 @@ def _check_grads(tr, want, exact, what):
         _check(mine, ref, exact["grads"][name], "%s %s" % (what, name))
 
 
-def _check_window(tr, state, floats, actions, n, H, what):
+def _check_window(tr, state, floats, actions, n, H, what, guard=False):
     """The trainer's last grads_rollout on (floats, actions) against the fp32 and fp64 oracles started from `state`;
-    returns the fp64 oracle's state (its running statistics moved H times)."""
+    returns the fp64 oracle's state (its running statistics moved H times).  guard (a trained-like state): the window
+    stays off the cancellation regime of E[x^2] - mean^2 at every BatchNorm site of every pass."""
     masks = _masks(tr, n, H)
     state32 = {k: v.detach().clone() for k, v in state.items()}
     state64 = _to64(state)
     want = C.rollout_grads(state32, floats, actions, masks)
-    exact = C.rollout_grads(state64, floats.double(), actions.double(), masks)
+    with TS.record_mean2_over_var(FO) as seen:
+        exact = C.rollout_grads(state64, floats.double(), actions.double(), masks)
+    if guard:
+        TS.assert_guard(seen, 10 * H)
     _check(tr.loss.cpu()[0], want["loss"], exact["loss"], what + " L")
     _check(tr.rollout_losses.cpu(), torch.stack(want["losses"]), torch.stack(exact["losses"]), what + " rollout_losses")
     assert abs(float(tr.rollout_losses.double().mean()) - float(tr.loss)) <= 1e-6 * float(tr.loss)
@@ -86,14 +95,15 @@ def _check_window(tr, state, floats, actions, n, H, what):
     return state64
 
 
-@pytest.mark.parametrize("n", [1, 3])
-def test_backward_inputs_gives_backwards_gradient_and_the_input_gradients(n):
+@pytest.mark.parametrize("n,trained", [pytest.param(1, False, id="1"), pytest.param(3, False, id="3"),
+                                       pytest.param(3, True, id="trained-3")])
+def test_backward_inputs_gives_backwards_gradient_and_the_input_gradients(n, trained):
     """ndp_fm_backward_inputs: `grad` bit-identical to ndp_fm_backward's on a second identical forward pass; d_state_cur (the
     data gradient of conv1 alone: no identity term) and d_actions against the oracle's autograd of the training-mode pass;
     either output alone."""
     from ndivplanning_amd import _capi
     torch.set_num_threads(8)
-    tr, state = _trainer(50 + n, n)
+    tr, state = _trainer(50 + n, n, trained)
     lib, p = tr.lib, _capi.ptr
     gen = torch.Generator().manual_seed(60 + n)
     cur = torch.rand(n, 3, 128, 128, generator=gen) * 2.0 - 1.0
@@ -136,15 +146,16 @@ def test_backward_inputs_gives_backwards_gradient_and_the_input_gradients(n):
     assert torch.equal(backward_inputs(only_cur, None), grad_a) and torch.equal(only_cur, d_cur)
 
 
-@pytest.mark.parametrize("n,H", [(2, 2), (3, 3)])
-def test_rollout_gradients_losses_and_statistics_match_the_oracle(n, H):
+@pytest.mark.parametrize("n,H,trained", [pytest.param(2, 2, False, id="2-2"), pytest.param(3, 3, False, id="3-3"),
+                                         pytest.param(2, 2, True, id="trained-2-2")])
+def test_rollout_gradients_losses_and_statistics_match_the_oracle(n, H, trained):
     """grads_rollout from float and from byte frames (the same bits): L, rollout_losses, every parameter gradient and the
     running statistics after the window against the oracle.  n = 3 is odd and below every tile; H = 3 has a middle pass
     with both an upstream and a downstream gradient."""
     torch.set_num_threads(8)
     frames8, floats, actions = _byte_window(70 + n, n, H + 1)       # a longer trajectory tensor: the window is a slice of it
-    tr, state = _trainer(80 + n, n, rollout_steps=H)
-    tr8, _ = _trainer(80 + n, n, rollout_steps=H)
+    tr, state = _trainer(80 + n, n, trained, rollout_steps=H)
+    tr8, _ = _trainer(80 + n, n, trained, rollout_steps=H)
     fl_d, f8_d, act_d = floats.to(DEV), frames8.to(DEV), actions.to(DEV)
     stats0 = tr8.stats.clone()
     # (slices along the time axis, as train() passes them: only the image stride differs)
@@ -152,11 +163,15 @@ def test_rollout_gradients_losses_and_statistics_match_the_oracle(n, H):
     tr8.grads_rollout(f8_d[:, 1:H + 2], act_d[:, 1:H + 1])
     assert torch.equal(tr.grad, tr8.grad) and torch.equal(tr.loss, tr8.loss) and torch.equal(tr.rollout_losses, tr8.rollout_losses)
     assert torch.equal(tr.stats, tr8.stats) and torch.equal(tr.loss_sum, tr.loss)
-    state64 = _check_window(tr, state, floats[:, 1:H + 2], actions[:, 1:H + 1], n, H, "n=%d, H=%d" % (n, H))
+    state64 = _check_window(tr, state, floats[:, 1:H + 2], actions[:, 1:H + 1], n, H, "n=%d, H=%d" % (n, H), guard=trained)
     sd = tr.sync_to_module().state_dict()
     for k, v in sd.items():                                          # the statistics moved H times, in order
         if "running_" in k:
             np.testing.assert_allclose(v.cpu().numpy(), state64[k].numpy(), rtol=1e-3, atol=1e-6, err_msg=k)
+        elif k.endswith("num_batches_tracked"):                      # a window of H passes counts H, as torch's BatchNorm does
+            unused = k.startswith(("encoder.conv4_bn", "encoder.conv5_bn"))
+            assert int(v) == int(state64[k]) == (7 if trained else 0) + (0 if unused else H), k
+    assert tr.steps == 0                                             # (Adam steps: none yet)
     # the contiguous window gives the same bits as the slice
     tr8.stats.copy_(stats0)
     tr8.grads_rollout(fl_d[:, 1:H + 2].contiguous(), act_d[:, 1:H + 1].contiguous())

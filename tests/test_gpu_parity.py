@@ -699,7 +699,7 @@ def test_adam_kernel_matches_oracle():
     ref = {"w": p.clone()}
     opt = O.AdamState(ref, 2e-4)
     pd_, m, v = p.to(DEV), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)
-    step = torch.zeros(1, dtype=torch.int32, device=DEV)
+    step = torch.zeros(4, dtype=torch.int32, device=DEV)          # the Adam state word is int32[4] (include/ndp.h)
     for t in range(5):
         gr = torch.randn(n, generator=gen) * (10.0 ** -t)
         opt.apply(ref, {"w": gr})
@@ -707,7 +707,7 @@ def test_adam_kernel_matches_oracle():
         _capi.check(lib.ndp_adam_step(_capi.ptr(pd_), _capi.ptr(grd), _capi.ptr(m), _capi.ptr(v), n, _capi.ptr(step),
                                       2e-4, 0.5, 0.999, 1e-8, _capi.stream_ptr()), "adam")
         _close(pd_, ref["w"], 2e-6, "params after %d Adam steps" % (t + 1))
-    assert int(step.item()) == 5
+    assert int(step[0].item()) == 5
 
 
 def test_device_noise_is_uniform_and_counter_based():
