@@ -28,7 +28,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-// bf16 MFMA operands (k_fm_gemm_bf16, k_fm_deconv32_bf16, k_conv_gemm_bf16): 8 values per lane and 32-wide K step
+// bf16 MFMA operands (the bf16 operand paths below): 8 values per lane and 32-wide K step
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ uint32_t fm_bf16_pair(float lo, float hi) {
@@ -186,15 +186,15 @@ __device__ __forceinline__ f32x4 ldg4(const float* p) {
   }
 }
 
-// fp32 -> bf16 copies of weight tensors (k_fm_pack_lp, k_enc_pack_lp), one launch for all of a network's segments: 4,096
-// values per workgroup, 16 bytes in and 8 bytes out per thread and pass.
+// fp32 -> bf16 copies of weight tensors (k_pack_lp, timed as k_fm_pack_lp and k_enc_pack_lp), one launch for all of a
+// network's segments: 4,096 values per workgroup, 16 bytes in and 8 bytes out per thread and pass.
 constexpr int kPackLpMaxSegs = 12;
 struct PackLpArgs {
   const float* src[kPackLpMaxSegs]; int64_t dst_off[kPackLpMaxSegs], count[kPackLpMaxSegs];
   int block_begin[kPackLpMaxSegs + 1]; int nseg;
   uint16_t* dst;
 };
-__device__ __forceinline__ void pack_lp_body(const PackLpArgs& a) {
+__global__ __launch_bounds__(kThreads) void k_pack_lp(PackLpArgs a) {
   int s = 0;
   while (s + 1 < a.nseg && (int)blockIdx.x >= a.block_begin[s + 1]) ++s;
   const int64_t base = (int64_t)((int)blockIdx.x - a.block_begin[s]) * 4096;
@@ -206,6 +206,100 @@ __device__ __forceinline__ void pack_lp_body(const PackLpArgs& a) {
     *reinterpret_cast<u32x2*>(a.dst + a.dst_off[s] + i) = u32x2{fm_bf16_pair(v[0], v[1]), fm_bf16_pair(v[2], v[3])};
   }
 }
+
+// ---------------------------------------------------------------------------------- operand paths of the LDS-staged GEMMs
+// k_fm_gemm, k_fm_deconv32 (ndp_forward_model.inc) and k_conv_gemm (ndp_encoder.inc) each write their tile order, gather,
+// fetch / stage / compute pipeline and epilogue once, as templates over an OperandPath: how a 32-wide K step of the two
+// operands gets from global memory into the MFMAs.  A path is a Stage for each operand (global -> registers -> LDS) and one
+// Mma (LDS tile -> fragments -> MFMAs).  Either way the weights go in as the MFMA's A operand and the pixels as B
+// (transposed tiles), so a lane (c, q) ends up with output pixel c and the four columns 4 q .. 4 q + 3 of each 16 x 16 tile:
+// the C/D layout does not depend on the operand type, and neither does an epilogue.
+//
+// Stage: `elem` the operand's element in global memory, `reg` what a thread holds per row and K step (V values), `quad`
+// what it writes to the tile for them, `lds` the tile's element.  staged(r) is the quad as it goes to LDS; staged(r, ok)
+// zeroes a padding tap (ok = false) -- there and not at the load, so that nothing consumes a load before the step's MFMAs
+// (hipcc would wait for it at once).  The kernel stores what staged() returns: `*(quad*)at = staged(..)` evaluates the
+// quad before the address, the order the register allocation of these loops was measured with.
+struct StageF32 {                       // fp32, stored as it comes: 16 bytes per thread
+  using elem = float; using reg = f32x4; using quad = f32x4; using lds = float;
+  static constexpr int V = 4;
+  static __device__ __forceinline__ reg load(const elem* p) { return ldg4<4>(p); }
+  static __device__ __forceinline__ quad staged(const reg& r) { return r; }
+  static __device__ __forceinline__ quad staged(const reg& r, bool ok) { return ok ? r : quad{0.f, 0.f, 0.f, 0.f}; }
+};
+struct StageRoundBf16 {                 // fp32, rounded to nearest even where it is staged (v_cvt_pk_bf16_f32: NaN stays NaN,
+  using elem = float; using reg = f32x4; using quad = u32x2; using lds = uint16_t;    // overflow goes to +-Inf): 16 bytes in,
+  static constexpr int V = 4;                                                         // 8 bytes to LDS
+  static __device__ __forceinline__ reg load(const elem* p) { return ldg4<4>(p); }
+  static __device__ __forceinline__ quad staged(const reg& r, bool ok) {
+    const quad v = {fm_bf16_pair(r[0], r[1]), fm_bf16_pair(r[2], r[3])};
+    return ok ? v : quad{0u, 0u};
+  }
+};
+template <class REG>                    // bf16 (a k_pack_lp copy of the weights, or a map its producer stored as bf16), stored as
+struct StageBf16 {                      // it comes: u32x2 = 4 values, u32x4 = 8 values per thread
+  using elem = uint16_t; using reg = REG; using quad = REG; using lds = uint16_t;
+  static constexpr int V = sizeof(REG) / 2;
+  static __device__ __forceinline__ reg load(const elem* p) { return *reinterpret_cast<const reg*>(p); }
+  static __device__ __forceinline__ quad staged(const reg& r) { return r; }
+  static __device__ __forceinline__ quad staged(const reg& r, bool ok) { return ok ? r : quad{}; }
+};
+
+// Mma: tiles() the workgroup's dynamic LDS as the tile's elements (the kernels name it at each use: the array itself, not a
+// pointer kept in a variable), LD the row stride (elements), KQ the lane's k offset per q in its row, `frag` what a lane (c, q)
+// holds of one 16-row tile and K step, read in PARTS LDS reads of 16 bytes; mma(a, b, acc, ks), ks = 0 .. KSUB-1 in order,
+// are the MFMAs of the step on one pair of fragments.
+//   fp32  two f32x4 at 4 q and 4 q + 16; 4 x 2 mfma16, MFMA s of a half pairing element s of both vectors (a permutation
+//         of the k order, as in layer_fwd below).  Row stride: 40 floats in the forward model (36 costs 8 LDS cycles per
+//         ds_read_b128 of an MFMA operand, 40 the ideal 4), 36 in the encoder.
+//   bf16  one bf16x8 at 8 q (k = 8 q .. 8 q + 7 of row c, both operands); one v_mfma_f32_16x16x32_bf16: products exact, the
+//         sum in fp32 in the accumulator.  Row stride 48 bf16 = 96 bytes for 64 bytes of data.  A ds_read_b128 is served in
+//         four groups of 16 lanes, each 8 rows at one q and the other 8 rows at q + 1 (lanes {0-3, 12-15, 20-27}, ...), over
+//         16 slots of 16 bytes (256 bytes of banks).  With a row stride of s slots a lane's slot is (s * row + q) mod 16:
+//         s = 4 (unpadded) puts 4 rows on a slot; an odd s (80 bytes) spreads the 16 rows over all 16 slots, so the 8 reads
+//         at q + 1 must land on slots of the other 8: 2-way for 3 of them; s = 6 sends any 8 consecutive rows to the 8 even
+//         slots and the rows at q + 1 to the odd ones: conflict-free, which s = 2 (smaller than a row) is the only smaller
+//         stride to do.  (Measured: no conflict cycle from the reads; the 8-byte staging stores of the forward model's
+//         path, two consecutive rows per 16-lane group and banked modulo 128 bytes, are 2-way: DESIGN 5s.)
+template <int LD_>
+struct MmaF32 {
+  using lds = float;
+  static constexpr int LD = LD_, KQ = 4, PARTS = 2, KSUB = 8;
+  struct frag { f32x4 h[2]; };
+  static __device__ __forceinline__ lds* tiles() { extern __shared__ __attribute__((aligned(16))) float smem[]; return smem; }
+  static __device__ __forceinline__ void read(frag& f, const lds* row, int part) {
+    f.h[part] = *reinterpret_cast<const f32x4*>(row + 16 * part);
+  }
+  static __device__ __forceinline__ f32x4 mma(const frag& a, const frag& b, f32x4 acc, int ks) {
+    return mfma16(a.h[ks >> 2][ks & 3], b.h[ks >> 2][ks & 3], acc);
+  }
+};
+struct MmaBf16 {
+  using lds = uint16_t;
+  static constexpr int LD = 48, KQ = 8, PARTS = 1, KSUB = 1;
+  typedef bf16x8 frag;
+  static __device__ __forceinline__ lds* tiles() { extern __shared__ __attribute__((aligned(16))) uint16_t smem_lp[]; return smem_lp; }
+  static __device__ __forceinline__ void read(frag& f, const lds* row, int) { f = *reinterpret_cast<const frag*>(row); }
+  static __device__ __forceinline__ f32x4 mma(const frag& a, const frag& b, f32x4 acc, int) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
+  }
+};
+
+template <class A_, class B_, class MMA>        // A: the gathered pixels, B: the weights
+struct OperandPath {
+  using A = A_; using B = B_; using Mma = MMA; using lds = typename MMA::lds;
+  static_assert(A::V == B::V && sizeof(typename A::lds) == sizeof(lds) && sizeof(typename B::lds) == sizeof(lds), "one tile layout");
+  static constexpr int V = A::V;
+  // bf16 operands.  The pipelines do not ask; the few deliberate differences of a kernel's bf16 instantiation outside the
+  // operand path (each kernel lists its own) do.
+  static constexpr bool kLp = sizeof(lds) == 2;
+  // dynamic LDS of a kernel that double-buffers `rows` tile rows (both operands together)
+  static constexpr int lds_bytes(int rows) { return 2 * rows * MMA::LD * (int)sizeof(lds); }
+};
+// The three paths that are launched:
+template <int LD> using PathF32 = OperandPath<StageF32, StageF32, MmaF32<LD>>;      // fp32 -> fp32: every fp32 instantiation
+using PathFmBf16 = OperandPath<StageRoundBf16, StageBf16<u32x2>, MmaBf16>;          // fp32 maps rounded at staging, bf16 weights
+using PathEncBf16 = OperandPath<StageBf16<u32x4>, StageBf16<u32x4>, MmaBf16>;       // bf16 maps and bf16 weights
 
 // ----------------------------------------------------------------------------------
 // Y[R x OUT] = act( X[R x IN] . Wm^T  (+ Xt[R x tail_n] . Wt^T)  + bias )

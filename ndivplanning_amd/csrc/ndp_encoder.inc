@@ -14,22 +14,24 @@
 // MFMA step s pairs element s of the A and the B vector (a permutation of the k order, as in ndp_device.h).
 //
 // Precision NDP_ENC_BF16 (ndp_encoder_forward_lp; the definition is in include/ndp.h): the same six launches with conv1
-// storing its map as bf16 and conv2..6 through k_conv_gemm_bf16 -- bf16 maps and bf16 weights straight into the bf16 MFMA,
-// fp32 accumulation, fp32 partial sums and codes.
+// storing its map as bf16 and conv2..6 through k_conv_gemm's bf16 operand path (EncBf16; the paths are described in
+// ndp_device.h) -- bf16 maps and bf16 weights straight into the bf16 MFMA, fp32 accumulation, fp32 partial sums and codes:
+// out = act(bias + sum bf16(x) . bf16(w)), where the bf16 map is what its producer stored (the rounding of this layer's
+// operand, done once) and the weights are the k_pack_lp copy.  A 32-wide K chunk of an im2col row is then 64 contiguous
+// bytes, 16 bytes per thread and load.
 
 namespace ndp {
 
-#ifndef NDP_ENC_BK
-#define NDP_ENC_BK 32
-#endif
-constexpr int kEncBM = 128, kEncBN = 128, kEncBK = NDP_ENC_BK, kEncLD = kEncBK + 4;
-constexpr int conv_gemm_lds_floats() { return 2 * (kEncBM + kEncBN) * kEncLD; }
+// (a K step of 64 was measured for the bf16 path and lost at small n: DESIGN 5t)
+constexpr int kEncBM = 128, kEncBN = 128, kEncBK = 32, kEncLD = kEncBK + 4;
+using EncF32 = PathF32<kEncLD>;
+using EncBf16 = PathEncBf16;
 
 struct ConvGemmArgs {
-  const float* in;        // NHWC [n][H][W][Cin]
-  const float* w;         // [Cout][K], k = (kh*KW + kw)*Cin + ci  (BatchNorm folded in)
+  const void* in;         // NHWC [n][H][W][Cin], P::A::elem of the launched path P
+  const void* w;          // [Cout][K], k = (kh*KW + kw)*Cin + ci  (BatchNorm folded in), P::B::elem
   const float* bias;      // [Cout] (BatchNorm folded in); ignored when nsplit > 1
-  float* out;             // NHWC [M][Cout]; nsplit > 1: partial sums [split][M][Cout]
+  void* out;              // NHWC [M][Cout], bf16 with OUT_LP, else fp32; nsplit > 1: fp32 partial sums [split][M][Cout]
   int H, W, Cin, OH, OW, Cout;
   int KW, stride, pad;
   int M, K;
@@ -38,9 +40,18 @@ struct ConvGemmArgs {
   int mtiles, ntiles;
 };
 
-__global__ __launch_bounds__(kThreads, (kEncBK >= 32 ? 2 : 3)) void k_conv_gemm(ConvGemmArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int BM = kEncBM, BN = kEncBN, BK = kEncBK, LD = kEncLD;
+// ReLU of the bf16 pass: a NaN stays a NaN, as the definition's torch.relu has it (fmaxf(NaN, 0) is 0: the fp32 pass,
+// whose bits are pinned, drops a NaN at its first ReLU)
+__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
+
+// The bf16 instantiations differ from the fp32 one outside the operand path, deliberately, in this: their ReLU keeps a NaN
+// (relu_keep_nan; the fp32 one is fmaxf), and with OUT_LP the finished map is stored as bf16 (conv2..conv5; 8 bytes per lane
+// and tile) -- conv6 stores fp32 codes, and the partial sums of a split layer are fp32 either way.
+template <class P, bool OUT_LP>
+__global__ __launch_bounds__(kThreads, 2) void k_conv_gemm(ConvGemmArgs a) {
+  using SA = typename P::A; using SB = typename P::B; using Mma = typename P::Mma;
+  static_assert(P::kLp || !OUT_LP, "k_conv_gemm: bf16 maps come from the bf16 pass");
+  constexpr int BM = kEncBM, BN = kEncBN, BK = kEncBK, LD = Mma::LD, V = P::V;
   // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs; the ntiles column tiles of one row tile
   // read the same im2col rows, so they run on the same XCD (one fetch into that L2)
   // (with fewer than 8 row tiles -- a handful of images -- plain order: the padded scheme would put every workgroup that
@@ -63,12 +74,12 @@ __global__ __launch_bounds__(kThreads, (kEncBK >= 32 ? 2 : 3)) void k_conv_gemm(
   const int c = lane & 15, q = lane >> 4;
   const int wm = wave >> 1, wn = wave & 1;
 
-  // global -> LDS assignment: 4 rows (r0 + 32 u) x one 4-float quad (kq) of each operand per thread and step
-  constexpr int QPR = BK / 4, RPP = kThreads / QPR, NU = BM / RPP;   // quads per row, rows per pass, passes
+  // global -> LDS assignment: NU rows (r0 + RPP u) x one quad of V values (kq) of each operand per thread and step
+  constexpr int QPR = BK / V, RPP = kThreads / QPR, NU = BM / RPP;   // quads per row, rows per pass, passes
   const int r0 = t / QPR, kq = t % QPR;
-  const float* a_img[NU];
+  const typename SA::elem* a_img[NU];
   int a_ih0[NU], a_iw0[NU], a_base[NU];
-  const float* b_row[NU];
+  const typename SB::elem* b_row[NU];
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     int m = m_tile * BM + r0 + RPP * u;
@@ -76,15 +87,15 @@ __global__ __launch_bounds__(kThreads, (kEncBK >= 32 ? 2 : 3)) void k_conv_gemm(
     m = valid ? m : a.M - 1;
     const int n = m / (a.OH * a.OW), rem = m - n * (a.OH * a.OW);
     const int oh = rem / a.OW, ow = rem - oh * a.OW;
-    a_img[u] = a.in + (size_t)n * a.H * a.W * a.Cin + 4 * kq;
+    a_img[u] = static_cast<const typename SA::elem*>(a.in) + (size_t)n * a.H * a.W * a.Cin + V * kq;
     a_ih0[u] = valid ? oh * a.stride - a.pad : -(1 << 20);       // rows past M: every tap out of bounds -> zeros
     a_iw0[u] = ow * a.stride - a.pad;
     a_base[u] = ((oh * a.stride - a.pad) * a.W + a_iw0[u]) * a.Cin;   // + tap offset = element offset in the image
-    b_row[u] = a.w + (size_t)(n_tile * BN + r0 + RPP * u) * a.K + 4 * kq;
+    b_row[u] = static_cast<const typename SB::elem*>(a.w) + (size_t)(n_tile * BN + r0 + RPP * u) * a.K + V * kq;
   }
-  f32x4 ra[NU], rb[NU];
-  bool ra_ok[NU];          // padding taps: the loaded value is replaced by zero when it is WRITTEN to LDS, so that
-                          // nothing consumes a load before the step's MFMAs (hipcc would wait for it at once)
+  typename SA::reg ra[NU];
+  typename SB::reg rb[NU];
+  bool ra_ok[NU];          // padding taps: zeroed where the quad is written to LDS (the Stages of ndp_device.h)
   auto fetch = [&](int k0) {
     const int tap = k0 / a.Cin, ci0 = k0 - tap * a.Cin;          // uniform: one tap, 32 consecutive channels
     const int kh = tap / a.KW, kw = tap - kh * a.KW;
@@ -92,19 +103,19 @@ __global__ __launch_bounds__(kThreads, (kEncBK >= 32 ? 2 : 3)) void k_conv_gemm(
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
       const bool ok = (unsigned)(a_ih0[u] + kh) < (unsigned)a.H && (unsigned)(a_iw0[u] + kw) < (unsigned)a.W;
-      ra[u] = ldg4<4>(a_img[u] + (ok ? a_base[u] + tapoff : 0));   // unconditional load from a valid address
+      ra[u] = SA::load(a_img[u] + (ok ? a_base[u] + tapoff : 0));   // unconditional load from a valid address
       ra_ok[u] = ok;
-      rb[u] = ldg4<4>(b_row[u] + k0);
+      rb[u] = SB::load(b_row[u] + k0);
     }
     pin_vmem();
   };
   auto stage = [&](int buf) {
-    float* As = smem + buf * (BM + BN) * LD;
-    float* Bs = As + BM * LD;
+    typename P::lds* As = Mma::tiles() + buf * (BM + BN) * LD;
+    typename P::lds* Bs = As + BM * LD;
 #pragma unroll
     for (int u = 0; u < NU; ++u) {
-      *reinterpret_cast<f32x4*>(As + (r0 + RPP * u) * LD + 4 * kq) = ra_ok[u] ? ra[u] : f32x4{0.f, 0.f, 0.f, 0.f};
-      *reinterpret_cast<f32x4*>(Bs + (r0 + RPP * u) * LD + 4 * kq) = rb[u];
+      *reinterpret_cast<typename SA::quad*>(As + (r0 + RPP * u) * LD + V * kq) = SA::staged(ra[u], ra_ok[u]);
+      *reinterpret_cast<typename SB::quad*>(Bs + (r0 + RPP * u) * LD + V * kq) = SB::staged(rb[u]);
     }
   };
 
@@ -121,25 +132,22 @@ __global__ __launch_bounds__(kThreads, (kEncBK >= 32 ? 2 : 3)) void k_conv_gemm(
   for (int k0 = kbeg; k0 < kend; k0 += BK) {
     const bool more = k0 + BK < kend;
     if (more) fetch(k0 + BK);                                    // in flight during this step's 128 MFMAs
-    const float* As = smem + buf * (BM + BN) * LD + (wm * 64 + c) * LD + 4 * q;
-    const float* Bs = smem + buf * (BM + BN) * LD + BM * LD + (wn * 64 + c) * LD + 4 * q;
-    constexpr int NH = BK / 16;
-    f32x4 af[NH][4], bf[NH][4];                                    // all 16-wide parts of the step up front
+    const typename P::lds* As = Mma::tiles() + buf * (BM + BN) * LD + (wm * 64 + c) * LD + Mma::KQ * q;
+    const typename P::lds* Bs = Mma::tiles() + buf * (BM + BN) * LD + BM * LD + (wn * 64 + c) * LD + Mma::KQ * q;
+    typename Mma::frag af[4], bf[4];                               // all parts of the step up front
 #pragma unroll
-    for (int h = 0; h < NH; ++h)
+    for (int h = 0; h < Mma::PARTS; ++h)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        af[h][i] = *reinterpret_cast<const f32x4*>(As + i * 16 * LD + 16 * h);
-        bf[h][i] = *reinterpret_cast<const f32x4*>(Bs + i * 16 * LD + 16 * h);
+        Mma::read(af[i], As + i * 16 * LD, h);
+        Mma::read(bf[i], Bs + i * 16 * LD, h);
       }
 #pragma unroll
-    for (int h = 0; h < NH; ++h)
+    for (int ks = 0; ks < Mma::KSUB; ++ks)
 #pragma unroll
-      for (int s = 0; s < 4; ++s)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-          for (int jn = 0; jn < 4; ++jn) acc[i][jn] = mfma16(bf[h][jn][s], af[h][i][s], acc[i][jn]);   // C^T tile: see epilogue
+        for (int jn = 0; jn < 4; ++jn) acc[i][jn] = Mma::mma(bf[jn], af[i], acc[i][jn], ks);   // C^T tile: see epilogue
     pin_vmem();
     if (more) stage(buf ^ 1);
     __syncthreads();
@@ -148,7 +156,7 @@ __global__ __launch_bounds__(kThreads, (kEncBK >= 32 ? 2 : 3)) void k_conv_gemm(
 
   // epilogue: the MFMAs computed the TRANSPOSED 16 x 16 tiles (weights as the A operand), so a lane holds output
   // row (pixel) c and 4 consecutive channels 4q..4q+3 of each tile: one 16-byte store per tile
-  float* out = a.out + (a.nsplit > 1 ? (size_t)split * a.M * a.Cout : 0);
+  float* out = static_cast<float*>(a.out) + (a.nsplit > 1 ? (size_t)split * a.M * a.Cout : 0);
   const bool fin = a.nsplit == 1;
 #pragma unroll
   for (int jn = 0; jn < 4; ++jn) {
@@ -159,149 +167,12 @@ __global__ __launch_bounds__(kThreads, (kEncBK >= 32 ? 2 : 3)) void k_conv_gemm(
       const int m = m_tile * BM + wm * 64 + i * 16 + c;
       if (m < a.M) {
         f32x4 v = acc[i][jn] + bv;
-        if (a.relu && fin) v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
-        *reinterpret_cast<f32x4*>(out + (size_t)m * a.Cout + col) = v;
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------ k_conv_gemm_bf16
-// k_conv_gemm with bf16 MFMA operands (precision NDP_ENC_BF16; the definition is in include/ndp.h):
-// out = act(bias + sum bf16(x) . bf16(w)), products exact, the sum in fp32 in the accumulator of v_mfma_f32_16x16x32_bf16.
-// Same ConvGemmArgs -- a.in is the bf16 map its producer stored (the rounding of this layer's operand, done once), a.w the
-// layer's bf16 weights (k_enc_pack_lp) -- same 128 x 128 tile, XCD order, K split and epilogue.  The operand path:
-//   load   both operands come as bf16 and go to LDS as they come: a 32-wide K chunk of an im2col row (one tap, 32
-//          consecutive channels) is 64 contiguous bytes, 16 bytes per thread and load; a padding tap is zeroed where it
-//          is written to LDS;
-//   LDS    row stride 48 values = 96 bytes, the conflict-free stride of k_fm_gemm_bf16 (any 8 consecutive rows on the 8
-//          even 16-byte slots, the rows at q + 1 on the odd ones);
-//   read   k_fm_gemm_bf16's fragments: one 16-byte read per operand tile and 32-wide K step, lane l = 16 q + c holds row c,
-//          k = 8 q .. 8 q + 7; the weights are the A operand, so a lane ends with output pixel c and channels 4 q .. 4 q + 3.
-// OUT_LP: the finished map is stored as bf16 (conv2..conv5; 8 bytes per lane and tile); conv6 stores fp32 codes.  Partial
-// sums of a split layer are fp32 either way.
-// ReLU of the bf16 pass: a NaN stays a NaN, as the definition's torch.relu has it (fmaxf(NaN, 0) is 0: the fp32 pass,
-// whose bits are pinned, drops a NaN at its first ReLU)
-__device__ __forceinline__ float relu_keep_nan(float v) { return v < 0.f ? 0.f : v; }
-
-constexpr int kEncLpBK = 32, kEncLpLD = 48;             // (a K step of 64 was measured and lost at small n: DESIGN 5t)
-constexpr int conv_gemm_bf16_lds_bytes() { return 2 * (kEncBM + kEncBN) * kEncLpLD * 2; }
-
-template <bool OUT_LP>
-__global__ __launch_bounds__(kThreads, 2) void k_conv_gemm_bf16(ConvGemmArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t smem_enc_lp[];
-  constexpr int BM = kEncBM, BN = kEncBN, BK = kEncLpBK, LD = kEncLpLD;
-  int n_tile, m_tile;                                                  // (k_conv_gemm's order)
-  if (a.mtiles >= 8) {
-    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-    n_tile = j % a.ntiles;
-    m_tile = (j / a.ntiles) * 8 + xcd;
-    if (m_tile >= a.mtiles) return;
-  } else {
-    n_tile = blockIdx.x % a.ntiles;
-    m_tile = blockIdx.x / a.ntiles;
-  }
-  const int split = blockIdx.y;
-  const int kbeg = split * a.k_per_split;
-  const int kend = kbeg + a.k_per_split < a.K ? kbeg + a.k_per_split : a.K;
-
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int c = lane & 15, q = lane >> 4;
-  const int wm = wave >> 1, wn = wave & 1;
-
-  // global -> LDS assignment: NU rows (r0 + RPP u) x one 8-value quad (16 bytes, kq) of each operand per thread and step
-  constexpr int QPR = BK / 8, RPP = kThreads / QPR, NU = BM / RPP;
-  const int r0 = t / QPR, kq = t % QPR;
-  const uint16_t* in_lp = reinterpret_cast<const uint16_t*>(a.in);
-  const uint16_t* w_lp = reinterpret_cast<const uint16_t*>(a.w);
-  const uint16_t* a_img[NU];
-  int a_ih0[NU], a_iw0[NU], a_base[NU];
-  const uint16_t* b_row[NU];
-#pragma unroll
-  for (int u = 0; u < NU; ++u) {
-    int m = m_tile * BM + r0 + RPP * u;
-    const bool valid = m < a.M;
-    m = valid ? m : a.M - 1;
-    const int n = m / (a.OH * a.OW), rem = m - n * (a.OH * a.OW);
-    const int oh = rem / a.OW, ow = rem - oh * a.OW;
-    a_img[u] = in_lp + (size_t)n * a.H * a.W * a.Cin + 8 * kq;
-    a_ih0[u] = valid ? oh * a.stride - a.pad : -(1 << 20);       // rows past M: every tap out of bounds -> zeros
-    a_iw0[u] = ow * a.stride - a.pad;
-    a_base[u] = ((oh * a.stride - a.pad) * a.W + a_iw0[u]) * a.Cin;
-    b_row[u] = w_lp + (size_t)(n_tile * BN + r0 + RPP * u) * a.K + 8 * kq;
-  }
-  u32x4 ra[NU], rb[NU];
-  bool ra_ok[NU];
-  auto fetch = [&](int k0) {
-    const int tap = k0 / a.Cin, ci0 = k0 - tap * a.Cin;          // uniform: one tap, BK consecutive channels
-    const int kh = tap / a.KW, kw = tap - kh * a.KW;
-    const int tapoff = (kh * a.W + kw) * a.Cin + ci0;            // uniform
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      const bool ok = (unsigned)(a_ih0[u] + kh) < (unsigned)a.H && (unsigned)(a_iw0[u] + kw) < (unsigned)a.W;
-      ra[u] = *reinterpret_cast<const u32x4*>(a_img[u] + (ok ? a_base[u] + tapoff : 0));   // always a valid address
-      ra_ok[u] = ok;
-      rb[u] = *reinterpret_cast<const u32x4*>(b_row[u] + k0);
-    }
-    pin_vmem();
-  };
-  auto stage = [&](int buf) {
-    uint16_t* As = smem_enc_lp + buf * (BM + BN) * LD;
-    uint16_t* Bs = As + BM * LD;
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-      *reinterpret_cast<u32x4*>(As + (r0 + RPP * u) * LD + 8 * kq) = ra_ok[u] ? ra[u] : u32x4{0u, 0u, 0u, 0u};
-      *reinterpret_cast<u32x4*>(Bs + (r0 + RPP * u) * LD + 8 * kq) = rb[u];
-    }
-  };
-
-  f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int jn = 0; jn < 4; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  fetch(kbeg);
-  stage(0);
-  __syncthreads();
-  int buf = 0;
-  for (int k0 = kbeg; k0 < kend; k0 += BK) {
-    const bool more = k0 + BK < kend;
-    if (more) fetch(k0 + BK);                                    // in flight during this step's MFMAs
-    const uint16_t* As = smem_enc_lp + buf * (BM + BN) * LD + (wm * 64 + c) * LD + 8 * q;
-    const uint16_t* Bs = smem_enc_lp + buf * (BM + BN) * LD + BM * LD + (wn * 64 + c) * LD + 8 * q;
-    bf16x8 af[4], bf[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      af[i] = *reinterpret_cast<const bf16x8*>(As + i * 16 * LD);
-      bf[i] = *reinterpret_cast<const bf16x8*>(Bs + i * 16 * LD);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int jn = 0; jn < 4; ++jn)
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[jn], af[i], acc[i][jn], 0, 0, 0);   // transposed tiles
-    pin_vmem();
-    if (more) stage(buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-
-  // k_conv_gemm's epilogue: a lane holds output row (pixel) c and the channels 4q .. 4q+3 of each tile
-  const bool fin = a.nsplit == 1;
-  float* out = a.out + (fin ? 0 : (size_t)split * a.M * a.Cout);
-#pragma unroll
-  for (int jn = 0; jn < 4; ++jn) {
-    const int col = n_tile * BN + wn * 64 + jn * 16 + 4 * q;
-    const f32x4 bv = fin ? *reinterpret_cast<const f32x4*>(a.bias + col) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m_tile * BM + wm * 64 + i * 16 + c;
-      if (m < a.M) {
-        f32x4 v = acc[i][jn] + bv;
-        if (a.relu && fin) v = f32x4{relu_keep_nan(v[0]), relu_keep_nan(v[1]), relu_keep_nan(v[2]), relu_keep_nan(v[3])};
+        if (a.relu && fin) {
+          if constexpr (P::kLp) v = f32x4{relu_keep_nan(v[0]), relu_keep_nan(v[1]), relu_keep_nan(v[2]), relu_keep_nan(v[3])};
+          else v = f32x4{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f), fmaxf(v[2], 0.f), fmaxf(v[3], 0.f)};
+        }
         const size_t at = (size_t)m * a.Cout + col;
-        if (OUT_LP && fin) *reinterpret_cast<u32x2*>(reinterpret_cast<uint16_t*>(out) + at) = u32x2{fm_bf16_pair(v[0], v[1]), fm_bf16_pair(v[2], v[3])};
+        if (OUT_LP && fin) *reinterpret_cast<u32x2*>(static_cast<uint16_t*>(a.out) + at) = u32x2{fm_bf16_pair(v[0], v[1]), fm_bf16_pair(v[2], v[3])};
         else *reinterpret_cast<f32x4*>(out + at) = v;
       }
     }
@@ -322,24 +193,17 @@ __device__ __forceinline__ float splitk_sum(const float* part, int nsplit, int64
   for (; sp < nsplit; ++sp) s += part[(size_t)sp * mc + i];
   return s;
 }
+// OUT = float: conv6's codes, and every split layer of the fp32 pass; OUT = __bf16: the finished map of a split layer of a
+// NDP_ENC_BF16 pass.  Each output type keeps its ReLU (see relu_keep_nan).
+template <class OUT>
 __global__ __launch_bounds__(kThreads) void k_splitk_reduce(const float* part, int nsplit, int64_t mc, const float* bias,
-                                                            int cout, int relu, float* out) {
+                                                            int cout, int relu, OUT* out) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= mc) return;
   const float s = splitk_sum(part, nsplit, mc, bias, cout, i);
-  out[i] = relu ? fmaxf(s, 0.f) : s;
+  if constexpr (sizeof(OUT) == sizeof(float)) out[i] = relu ? fmaxf(s, 0.f) : s;
+  else out[i] = (OUT)(relu ? relu_keep_nan(s) : s);
 }
-// ... the finished map stored as bf16 (the split layers of a NDP_ENC_BF16 pass; conv6's codes keep the fp32 one)
-__global__ __launch_bounds__(kThreads) void k_splitk_reduce_bf16(const float* part, int nsplit, int64_t mc, const float* bias,
-                                                                 int cout, int relu, __bf16* out) {
-  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= mc) return;
-  const float s = splitk_sum(part, nsplit, mc, bias, cout, i);
-  out[i] = (__bf16)(relu ? relu_keep_nan(s) : s);
-}
-
-// the weights of conv2..conv6 as bf16, one launch (pack_lp_body, ndp_device.h: k_fm_pack_lp's body)
-__global__ __launch_bounds__(kThreads) void k_enc_pack_lp(PackLpArgs a) { pack_lp_body(a); }
 
 // conv1: 3 -> 64 channels, 3x3 stride 2 pad 1, 128x128 -> 64x64, BatchNorm folded, ReLU; reads the reference's NCHW
 // images, writes NHWC.  K = 27 (padded to 32 with zero weights) is a single 32-wide K step of the matrix pipe:
@@ -520,13 +384,12 @@ static int64_t enc_ws_floats(int64_t n) {
 
 // K split of layer l for n images: the deep layers have few output tiles when n is small (conv5: 8 per 8 images);
 // the smallest divisor d of K / 32 that gives >= 512 workgroups (2 per CU), with tiles * d <= kEncPartBlocks
-// (bk: the K step of the kernel that runs the layer -- k_conv_gemm's kEncBK is a build option, NDP_ENC_BK, and may differ
-// from k_conv_gemm_bf16's 32: a split must be whole steps of the kernel it is for)
-static int enc_split(int l, int64_t n, int bk = kEncBK) {
+// (a split is whole K steps of k_conv_gemm: 32 in both precisions)
+static int enc_split(int l, int64_t n) {
   const EncLayer& L = kEnc[l];
   const int64_t m = n * L.hout * L.hout;
   const int64_t tiles = ((m + kEncBM - 1) / kEncBM) * (L.cout / kEncBN);
-  const int steps = L.ksz * L.ksz * L.cin / bk;
+  const int steps = L.ksz * L.ksz * L.cin / kEncBK;
   int best = 1;
   for (int d = 1; d <= steps && d <= 128; ++d) {
     if (steps % d != 0 || tiles * d > kEncPartBlocks) continue;
@@ -555,27 +418,7 @@ static dim3 conv_gemm_grid(const ConvGemmArgs& a) {
   return dim3((unsigned)(a.mtiles >= 8 ? 8 * ((a.mtiles + 7) / 8) * a.ntiles : a.mtiles * a.ntiles), (unsigned)a.nsplit);
 }
 
-static int launch_conv_gemm(int l, const float* in, const float* params, float* out, int64_t n, float* part, hipStream_t st) {
-  const int nsplit = enc_split(l, n);
-  float* final_out = out;
-  if (nsplit > 1) out = part;
-  std::call_once(device_once(g_enc_attr_once), [] { allow_lds(k_conv_gemm, conv_gemm_lds_floats() * 4); });
-  ConvGemmArgs a = conv_gemm_args(l, params, n, nsplit);
-  a.in = in; a.w = params + enc_param_offset(l, false); a.out = out;
-  const dim3 grid = conv_gemm_grid(a);
-  KTimer kt(l == 5 ? "k_conv_gemm[6]" : (l == 1 ? "k_conv_gemm[2]" : (l == 2 ? "k_conv_gemm[3]" : (l == 3 ? "k_conv_gemm[4]" : "k_conv_gemm[5]"))), st);
-  hipLaunchKernelGGL(k_conv_gemm, grid, dim3(kThreads), conv_gemm_lds_floats() * 4, st, a);
-  int rc = check_launch("k_conv_gemm");
-  if (rc || nsplit == 1) return rc;
-  const int64_t mc = (int64_t)a.M * a.Cout;
-  KTimer kt2("k_splitk_reduce", st);
-  hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((mc + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                     part, nsplit, mc, a.bias, a.Cout, a.relu, final_out);
-  return check_launch("k_splitk_reduce");
-}
-
 // ---- precision NDP_ENC_BF16
-static std::once_flag g_enc_lp_attr_once[kMaxDevices];
 static const char* const kEncLpLabel[6] = {"k_enc_conv1_bf16", "k_conv_gemm_bf16[2]", "k_conv_gemm_bf16[3]", "k_conv_gemm_bf16[4]",
                                            "k_conv_gemm_bf16[5]", "k_conv_gemm_bf16[6]"};
 static int64_t enc_lp_w_offset(int l) {        // conv l + 1's bf16 weights (l = 1..5; 6: the end), in bf16 elements
@@ -589,35 +432,40 @@ static int64_t enc_lp_act_offset(int l, int64_t n) {   // map l (0..4; 5: the en
   return o;
 }
 
-// layer l = 1..5 with bf16 operands: `in` the bf16 map of layer l - 1, `out` a bf16 map (l < 5) or the fp32 codes (l == 5)
-static int launch_conv_gemm_bf16(int l, const uint16_t* in, const float* params, const uint16_t* lp, void* out, int64_t n,
-                                 float* part, hipStream_t st) {
-  const int nsplit = enc_split(l, n, kEncLpBK);
-  std::call_once(device_once(g_enc_lp_attr_once), [] {
-    allow_lds(k_conv_gemm_bf16<true>, conv_gemm_bf16_lds_bytes());
-    allow_lds(k_conv_gemm_bf16<false>, conv_gemm_bf16_lds_bytes());
+// layer l = 1..5: split, launch, reduce.  lp == null, the fp32 pass: `in` and `out` are fp32 maps (l == 5: the codes) and the
+// weights come from `params`.  lp != null, NDP_ENC_BF16: `in` is the bf16 map of layer l - 1, the weights are lp's, `out` is
+// a bf16 map (l < 5) or the fp32 codes (l == 5).  Partial sums of a split layer are fp32 in `part` either way.
+static int launch_conv_gemm(int l, const void* in, const float* params, const uint16_t* lp, void* out, int64_t n, float* part,
+                            hipStream_t st) {
+  static const char* const kEncLabel[6] = {"k_enc_conv1", "k_conv_gemm[2]", "k_conv_gemm[3]", "k_conv_gemm[4]", "k_conv_gemm[5]",
+                                           "k_conv_gemm[6]"};
+  const int nsplit = enc_split(l, n);
+  const bool out_lp = lp != nullptr && l < 5;
+  std::call_once(device_once(g_enc_attr_once), [] {
+    allow_lds((k_conv_gemm<EncF32, false>), EncF32::lds_bytes(kEncBM + kEncBN));
+    allow_lds((k_conv_gemm<EncBf16, true>), EncBf16::lds_bytes(kEncBM + kEncBN));
+    allow_lds((k_conv_gemm<EncBf16, false>), EncBf16::lds_bytes(kEncBM + kEncBN));
   });
   ConvGemmArgs a = conv_gemm_args(l, params, n, nsplit);
-  a.in = reinterpret_cast<const float*>(in); a.w = reinterpret_cast<const float*>(lp + enc_lp_w_offset(l));
-  a.out = nsplit > 1 ? part : static_cast<float*>(out);
+  a.in = in; a.out = nsplit > 1 ? part : out;
+  if (lp != nullptr) a.w = lp + enc_lp_w_offset(l);
+  else a.w = params + enc_param_offset(l, false);
+  const dim3 grid = conv_gemm_grid(a);
   {
-    KTimer kt(kEncLpLabel[l], st);
-    if (l < 5) hipLaunchKernelGGL(k_conv_gemm_bf16<true>, conv_gemm_grid(a), dim3(kThreads), conv_gemm_bf16_lds_bytes(), st, a);
-    else hipLaunchKernelGGL(k_conv_gemm_bf16<false>, conv_gemm_grid(a), dim3(kThreads), conv_gemm_bf16_lds_bytes(), st, a);
+    KTimer kt(lp != nullptr ? kEncLpLabel[l] : kEncLabel[l], st);
+    if (lp == nullptr) hipLaunchKernelGGL((k_conv_gemm<EncF32, false>), grid, dim3(kThreads), EncF32::lds_bytes(kEncBM + kEncBN), st, a);
+    else if (out_lp) hipLaunchKernelGGL((k_conv_gemm<EncBf16, true>), grid, dim3(kThreads), EncBf16::lds_bytes(kEncBM + kEncBN), st, a);
+    else hipLaunchKernelGGL((k_conv_gemm<EncBf16, false>), grid, dim3(kThreads), EncBf16::lds_bytes(kEncBM + kEncBN), st, a);
   }
-  int rc = check_launch("k_conv_gemm_bf16");
+  int rc = check_launch(lp != nullptr ? "k_conv_gemm_bf16" : "k_conv_gemm");
   if (rc || nsplit == 1) return rc;
   const int64_t mc = (int64_t)a.M * a.Cout;
-  if (l < 5) {
-    KTimer kt2("k_splitk_reduce_bf16", st);
-    hipLaunchKernelGGL(k_splitk_reduce_bf16, dim3((unsigned)((mc + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                       part, nsplit, mc, a.bias, a.Cout, a.relu, static_cast<__bf16*>(out));
-    return check_launch("k_splitk_reduce_bf16");
-  }
-  KTimer kt2("k_splitk_reduce", st);
-  hipLaunchKernelGGL(k_splitk_reduce, dim3((unsigned)((mc + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
-                     part, nsplit, mc, a.bias, a.Cout, a.relu, static_cast<float*>(out));
-  return check_launch("k_splitk_reduce");
+  const dim3 rgrid((unsigned)((mc + kThreads - 1) / kThreads));
+  const char* rlabel = out_lp ? "k_splitk_reduce_bf16" : "k_splitk_reduce";
+  KTimer kt2(rlabel, st);
+  if (out_lp) hipLaunchKernelGGL(k_splitk_reduce<__bf16>, rgrid, dim3(kThreads), 0, st, part, nsplit, mc, a.bias, a.Cout, a.relu, static_cast<__bf16*>(out));
+  else hipLaunchKernelGGL(k_splitk_reduce<float>, rgrid, dim3(kThreads), 0, st, part, nsplit, mc, a.bias, a.Cout, a.relu, static_cast<float*>(out));
+  return check_launch(rlabel);
 }
 
 static int enc_pack_lp(const float* params, uint16_t* lp, hipStream_t st) {
@@ -631,7 +479,7 @@ static int enc_pack_lp(const float* params, uint16_t* lp, hipStream_t st) {
     a.block_begin[i + 1] = a.block_begin[i] + (int)((a.count[i] + 4095) / 4096);
   }
   KTimer kt("k_enc_pack_lp", st);
-  hipLaunchKernelGGL(k_enc_pack_lp, dim3((unsigned)a.block_begin[a.nseg]), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(k_pack_lp, dim3((unsigned)a.block_begin[a.nseg]), dim3(kThreads), 0, st, a);
   return check_launch("k_enc_pack_lp");
 }
 
@@ -668,7 +516,7 @@ static int encoder_forward_any(const float* packed_params, const void* images, b
       if (rc) return rc;
       for (int l = 1; l < 6; ++l) {
         void* out = l < 5 ? (void*)(maps + enc_lp_act_offset(l, n)) : (void*)(codes + n0 * 128);
-        rc = launch_conv_gemm_bf16(l, maps + enc_lp_act_offset(l - 1, n), packed_params, lp, out, n, part, st);
+        rc = launch_conv_gemm(l, maps + enc_lp_act_offset(l - 1, n), packed_params, lp, out, n, part, st);
         if (rc) return rc;
       }
       continue;
@@ -689,7 +537,7 @@ static int encoder_forward_any(const float* packed_params, const void* images, b
       if (rc) return rc;
     }
     for (int l = 1; l < 6; ++l) {
-      int rc = launch_conv_gemm(l, act[l - 1], packed_params, l < 5 ? act[l] : codes + n0 * 128, n, part, st);
+      int rc = launch_conv_gemm(l, act[l - 1], packed_params, nullptr, l < 5 ? act[l] : codes + n0 * 128, n, part, st);
       if (rc) return rc;
     }
   }

@@ -16,8 +16,8 @@
 //               1 / 2 / 2 / 4 taps; the 4x4 <-> 1x1 layers are sixteen one-tap classes;
 //   k_fm_wgrad  dW[j][tap][k] = sum over pixels m  dense[m][j] . gathered[pixel(m) + tap][k]
 //               -- every weight gradient (rows = the reduction, both operands read along channels, as k_wgrad).
-// (The eval-mode pass can run its nine stride-2 layers with bf16 operands instead -- k_fm_gemm_bf16, k_fm_deconv32_bf16,
-// ndp_fm_forward_lp with NDP_FM_BF16 -- which changes nothing of what follows: every stored map stays fp32.)
+// (The eval-mode pass can run its nine stride-2 layers with bf16 operands instead -- the FmBf16 instantiations of k_fm_gemm and
+// k_fm_deconv32, ndp_fm_forward_lp with NDP_FM_BF16 -- which changes nothing of what follows: every stored map stays fp32.)
 // Activations are NHWC with an explicit pixel stride, so that cat([up, skip]) is never copied: the decoder's BatchNorm
 // + ReLU writes the lower channels of the next layer's input map, the encoder's writes the upper ones; their gradients
 // come back the same way (the encoder's data gradients accumulate onto the skip halves).  Channel counts that are not
@@ -223,14 +223,17 @@ __device__ __forceinline__ void fm_stat_publish(const FmStatEp& a, int row, int 
 // mode 2  4 classes (py, px) of the data gradient of a stride-2 3x3 convolution: (1 + py) x (1 + px) taps, source pixel
 //         (y + kh, x + kw), output pixel (2y + py, 2x + px)
 // mode 3  16 classes = the pixels of a 4x4 map, one tap at the source's single pixel, output pixel (cls / 4, cls % 4)
-#ifndef NDP_FM_LD
-#define NDP_FM_LD 40     // LDS row stride (floats): 36 costs 8 LDS cycles per ds_read_b128 of an MFMA operand, 40 the ideal 4
-#endif
-constexpr int kFmBM = 128, kFmBK = 32, kFmLD = NDP_FM_LD;
-template <int BN> constexpr int fm_gemm_lds_floats() { return 2 * (kFmBM + BN) * kFmLD; }
+//
+// Operand paths (ndp_device.h): FmF32, and FmBf16 for precision NDP_FM_BF16 of the eval-mode pass (the definition is in
+// include/ndp.h): out = act(bias + sum bf16(x) . bf16(w)) -- `w` is then the layer's bf16 weights, rounded once by k_pack_lp,
+// the gathered fp32 activations are rounded where they are staged.
+constexpr int kFmBM = 128, kFmBK = 32;
+constexpr int kFmLD = 40;      // LDS row stride (floats): 36 costs 8 LDS cycles per ds_read_b128 of an MFMA operand, 40 the ideal 4
+using FmF32 = PathF32<kFmLD>;
+using FmBf16 = PathFmBf16;
 
 struct FmGemmArgs {
-  const float* src; const float* w; const float* bias; float* out; float* part;
+  const float* src; const void* w; const float* bias; float* out; float* part;    // w: P::B::elem of the launched path P
   int src_ld, SH, SW, ss;
   int out_ld, OH, OW;
   int GH, GW, M, C, N;                // rows m = (image*GH + y)*GW + x; C gathered channels (multiple of 32); N columns
@@ -315,10 +318,15 @@ __device__ __forceinline__ void fm_stat_terms(const FmStatEp& ep, size_t pix, in
   fm_stat_terms(ep.mode, v, y, x, mu, is, s1, s2);
 }
 
-template <int BN>
+// The bf16 instantiation differs from the fp32 ones outside the operand path, deliberately, in this: it has no statistics
+// epilogue (FmStatEp: the eval-mode pass never asks for one) and neither cls_units nor the mode-2 class order (modes 0
+// and 1 only) -- left out at compile time; fm_gemm refuses such a launch.
+template <int BN, class P = FmF32>
 __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int BM = kFmBM, BK = kFmBK, LD = kFmLD;
+  using SA = typename P::A; using SB = typename P::B; using Mma = typename P::Mma;
+  extern __shared__ __attribute__((aligned(16))) float smem[];       // the statistics' scratch (the tiles: Mma::tiles())
+  constexpr bool LP = P::kLp;
+  constexpr int BM = kFmBM, BK = kFmBK, LD = Mma::LD, V = P::V;
   constexpr int TI = BN == 128 ? 4 : 2, TJ = BN == 128 ? 4 : 2;     // 16 x 16 tiles per wave: rows x columns
   // 8 or more row tiles: the column tiles of one row tile share an XCD (k_conv_gemm).  Fewer (the deep layers at small
   // batches): plain order -- the padded scheme would leave every workgroup that has work on XCD 0 (measured: deconv2 at 8
@@ -335,26 +343,29 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
   }
   // mode 2 (data gradient of a stride-2 3x3 convolution): the parity classes have 1 / 2 / 2 / 4 taps -- the grid is
   // dispatched z-major, so the 4-tap class goes first and the 1-tap class fills the tail
-  int split = blockIdx.y, cls = a.mode == 2 ? 3 - (int)blockIdx.z : (int)blockIdx.z;
-  if (a.cls_units > 0) {
-    const int u = blockIdx.y, s = a.cls_units;
-    cls = u < s ? 0 : (u < 3 * s ? 1 : (u < 5 * s ? 2 : 3));
-    split = u - fm_unit_first(cls, s);
+  int split = blockIdx.y, cls = blockIdx.z;
+  if constexpr (!LP) {
+    if (a.mode == 2) cls = 3 - (int)blockIdx.z;
+    if (a.cls_units > 0) {
+      const int u = blockIdx.y, s = a.cls_units;
+      cls = u < s ? 0 : (u < 3 * s ? 1 : (u < 5 * s ? 2 : 3));
+      split = u - fm_unit_first(cls, s);
+    }
   }
   const FmClass kc = fm_class(a, cls);
   const int ksteps = kc.KH * kc.KW * a.C / BK;
   const int sbeg = split * a.steps_per_split;
   const int send = sbeg + a.steps_per_split < ksteps ? sbeg + a.steps_per_split : ksteps;
   const int K = kc.KH * kc.KW * a.C;
-  const float* wcls = a.w + kc.w_off;
+  const typename SB::elem* wcls = static_cast<const typename SB::elem*>(a.w) + kc.w_off;
 
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int c = lane & 15, q = lane >> 4;
   const int row0 = BN == 128 ? (wave >> 1) * 64 : wave * 32, col0 = BN == 128 ? (wave & 1) * 64 : 0;
 
-  constexpr int QPR = BK / 4, RPP = kThreads / QPR, NUA = BM / RPP, NUB = BN / RPP;
+  constexpr int QPR = BK / V, RPP = kThreads / QPR, NUA = BM / RPP, NUB = BN / RPP;
   const int r0 = t / QPR, kq = t % QPR;
-  const float* a_img[NUA];
+  const typename SA::elem* a_img[NUA];
   int a_y0[NUA], a_x0[NUA];
 #pragma unroll
   for (int u = 0; u < NUA; ++u) {
@@ -363,19 +374,20 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
     m = valid ? m : a.M - 1;
     const int img = m / (a.GH * a.GW), rem = m - img * (a.GH * a.GW);
     const int y = rem / a.GW, x = rem - y * a.GW;
-    a_img[u] = a.src + (size_t)img * a.SH * a.SW * a.src_ld + 4 * kq;
+    a_img[u] = a.src + (size_t)img * a.SH * a.SW * a.src_ld + V * kq;
     a_y0[u] = valid ? y * a.ss - kc.pad_y : -(1 << 20);             // rows past M: every tap out of bounds -> zeros
     a_x0[u] = x * a.ss - kc.pad_x;
   }
-  const float* b_row[NUB];
+  const typename SB::elem* b_row[NUB];
   bool b_ok[NUB];
 #pragma unroll
   for (int u = 0; u < NUB; ++u) {
     const int n = n_tile * BN + r0 + RPP * u;
     b_ok[u] = n < a.N;
-    b_row[u] = wcls + (size_t)(b_ok[u] ? n : a.N - 1) * K + 4 * kq;
+    b_row[u] = wcls + (size_t)(b_ok[u] ? n : a.N - 1) * K + V * kq;
   }
-  f32x4 ra[NUA], rb[NUB];
+  typename SA::reg ra[NUA];
+  typename SB::reg rb[NUB];
   bool ra_ok[NUA];
   auto fetch = [&](int step) {
     const int k0 = step * BK;
@@ -385,22 +397,20 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
     for (int u = 0; u < NUA; ++u) {
       const int yy = a_y0[u] + kh, xx = a_x0[u] + kw;
       const bool ok = (unsigned)yy < (unsigned)a.SH && (unsigned)xx < (unsigned)a.SW;
-      ra[u] = ldg4<4>(a_img[u] + (ok ? (size_t)(yy * a.SW + xx) * a.src_ld + ci0 : 0));
+      ra[u] = SA::load(a_img[u] + (ok ? (size_t)(yy * a.SW + xx) * a.src_ld + ci0 : 0));
       ra_ok[u] = ok;
     }
 #pragma unroll
-    for (int u = 0; u < NUB; ++u) rb[u] = ldg4<4>(b_row[u] + k0);
+    for (int u = 0; u < NUB; ++u) rb[u] = SB::load(b_row[u] + k0);
     pin_vmem();
   };
   auto stage = [&](int buf) {
-    float* As = smem + buf * (BM + BN) * LD;
-    float* Bs = As + BM * LD;
+    typename P::lds* As = Mma::tiles() + buf * (BM + BN) * LD;
+    typename P::lds* Bs = As + BM * LD;
 #pragma unroll
-    for (int u = 0; u < NUA; ++u)
-      *reinterpret_cast<f32x4*>(As + (r0 + RPP * u) * LD + 4 * kq) = ra_ok[u] ? ra[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < NUA; ++u) *reinterpret_cast<typename SA::quad*>(As + (r0 + RPP * u) * LD + V * kq) = SA::staged(ra[u], ra_ok[u]);
 #pragma unroll
-    for (int u = 0; u < NUB; ++u)
-      *reinterpret_cast<f32x4*>(Bs + (r0 + RPP * u) * LD + 4 * kq) = b_ok[u] ? rb[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < NUB; ++u) *reinterpret_cast<typename SB::quad*>(Bs + (r0 + RPP * u) * LD + V * kq) = SB::staged(rb[u], b_ok[u]);
   };
 
   f32x4 acc[TI][TJ];
@@ -418,25 +428,22 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
   for (int step = sbeg; step < send; ++step) {
     const bool more = step + 1 < send;
     if (more) fetch(step + 1);
-    const float* As = smem + buf * (BM + BN) * LD + (row0 + c) * LD + 4 * q;
-    const float* Bs = smem + buf * (BM + BN) * LD + BM * LD + (col0 + c) * LD + 4 * q;
-    constexpr int NH = BK / 16;
-    f32x4 af[NH][TI], bf[NH][TJ];
+    const typename P::lds* As = Mma::tiles() + buf * (BM + BN) * LD + (row0 + c) * LD + Mma::KQ * q;
+    const typename P::lds* Bs = Mma::tiles() + buf * (BM + BN) * LD + BM * LD + (col0 + c) * LD + Mma::KQ * q;
+    typename Mma::frag af[TI], bf[TJ];
 #pragma unroll
-    for (int h = 0; h < NH; ++h) {
+    for (int h = 0; h < Mma::PARTS; ++h) {
 #pragma unroll
-      for (int i = 0; i < TI; ++i) af[h][i] = *reinterpret_cast<const f32x4*>(As + i * 16 * LD + 16 * h);
+      for (int i = 0; i < TI; ++i) Mma::read(af[i], As + i * 16 * LD, h);
 #pragma unroll
-      for (int jn = 0; jn < TJ; ++jn) bf[h][jn] = *reinterpret_cast<const f32x4*>(Bs + jn * 16 * LD + 16 * h);
+      for (int jn = 0; jn < TJ; ++jn) Mma::read(bf[jn], Bs + jn * 16 * LD, h);
     }
 #pragma unroll
-    for (int h = 0; h < NH; ++h)
+    for (int ks = 0; ks < Mma::KSUB; ++ks)
 #pragma unroll
-      for (int s = 0; s < 4; ++s)
+      for (int i = 0; i < TI; ++i)
 #pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-          for (int jn = 0; jn < TJ; ++jn) acc[i][jn] = mfma16(bf[h][jn][s], af[h][i][s], acc[i][jn]);   // transposed tiles
+        for (int jn = 0; jn < TJ; ++jn) acc[i][jn] = Mma::mma(bf[jn], af[i], acc[i][jn], ks);   // transposed tiles
     pin_vmem();
     if (more) stage(buf ^ 1);
     __syncthreads();
@@ -445,7 +452,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
 
   // a lane holds output row (pixel) c and the 4 consecutive columns 4q .. 4q+3 of each tile
   const bool fin = a.nsplit == 1;
-  const bool stat = fin && a.ep.mode != 0 && n_tile * BN < a.ep.cols;
+  const bool stat = !LP && fin && a.ep.mode != 0 && n_tile * BN < a.ep.cols;
   const bool need_y = stat && (a.ep.mode == 2 || a.ep.mode == 3), need_x = stat && a.ep.mode == 2;
   f32x4 cs1[TJ], cs2[TJ], bias4[TJ], mu4[TJ], is4[TJ];
   int colj[TJ];
@@ -465,7 +472,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
     if (m >= a.M) continue;
     const size_t pix = fm_out_pixel_index(a, kc, m);
     float* orow = fin ? a.out + pix * a.out_ld
-                      : a.part + ((size_t)(a.cls_units > 0 ? (int)blockIdx.y : cls * a.nsplit + split) * a.M + m) * a.N;
+                      : a.part + ((size_t)(!LP && a.cls_units > 0 ? (int)blockIdx.y : cls * a.nsplit + split) * a.M + m) * a.N;
     // every load of this row tile before its first store (the compiler cannot move a load above a store that may alias it:
     // issued one by one between the stores, each would expose its own latency)
     f32x4 prev[TJ], yv[TJ], xv[TJ];
@@ -533,187 +540,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_gemm(FmGemmArgs a) {
   fm_stat_publish(a.ep, cls * a.mtiles + m_tile, n_tile * BN, BN, sums);
 }
 
-// ------------------------------------------------------------------------------------------ k_fm_gemm_bf16
-// k_fm_gemm with bf16 MFMA operands (precision NDP_FM_BF16 of the eval-mode pass; the definition is in include/ndp.h):
-// out = act(bias + sum bf16(x) . bf16(w)), the products exact and the sum in fp32 in the accumulator of
-// v_mfma_f32_16x16x32_bf16.  Same FmGemmArgs (a.w carries the address of the layer's bf16 weights, rounded once by
-// k_fm_pack_lp), same tiles, XCD order, K split and K steps of 32, same epilogue (only modes 0 and 1 and no statistics are
-// ever asked of it: the eval-mode pass has none).  What differs is the operand path:
-//   A tile  the gathered fp32 activations are rounded to nearest even where they are staged (v_cvt_pk_bf16_f32: NaN stays
-//           NaN, overflow goes to +-Inf), 8 bytes per 4 values into a bf16 LDS tile;
-//   B tile  8 bytes per 4 values from the bf16 copy, stored as they come;
-//   read    one 16-byte LDS read per lane and 32-wide K step: lane l = 16 q + c holds k = 8 q .. 8 q + 7 of row c, for both
-//           operands; the weights go in as the A operand and the pixels as B, so that, as in k_fm_gemm, a lane ends up
-//           with output pixel c and the four columns 4 q .. 4 q + 3 (the C/D layout does not depend on the operand type).
-// LDS row stride: 48 bf16 = 96 bytes for 64 bytes of data.  A ds_read_b128 is served in four groups of 16 lanes, each
-// 8 rows at one q and the other 8 rows at q + 1 (lanes {0-3, 12-15, 20-27}, ...), over 16 slots of 16 bytes (256 bytes of
-// banks).  With a row stride of s slots a lane's slot is (s * row + q) mod 16: s = 4 (unpadded) puts 4 rows on a slot;
-// an odd s (80 bytes) spreads the 16 rows over all 16 slots, so the 8 reads at q + 1 must land on slots of the other 8:
-// 2-way for 3 of them; s = 6 sends any 8 consecutive rows to the 8 even slots and the rows at q + 1 to the odd ones:
-// conflict-free, which s = 2 (smaller than a row) is the only smaller stride to do.  (Measured: no conflict cycle from the
-// reads; the 8-byte staging stores, two consecutive rows per 16-lane group and banked modulo 128 bytes, are 2-way: DESIGN 5s.)
-// (bf16x2, bf16x8, u32x2 and fm_bf16_pair: ndp_device.h, shared with k_conv_gemm_bf16 of ndp_encoder.inc)
-constexpr int kFmLpLD = 48;
-template <int BN> constexpr int fm_gemm_bf16_lds_bytes() { return 2 * (kFmBM + BN) * kFmLpLD * 2; }
-
-template <int BN>
-__global__ __launch_bounds__(kThreads, 2) void k_fm_gemm_bf16(FmGemmArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t smem_lp[];
-  constexpr int BM = kFmBM, BK = kFmBK, LD = kFmLpLD;
-  constexpr int TI = BN == 128 ? 4 : 2, TJ = BN == 128 ? 4 : 2;
-  int n_tile, m_tile;                                                  // (k_fm_gemm's order)
-  if (a.mtiles >= 8) {
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    n_tile = jb % a.ntiles;
-    m_tile = (jb / a.ntiles) * 8 + xcd;
-    if (m_tile >= a.mtiles) return;
-  } else {
-    n_tile = blockIdx.x % a.ntiles;
-    m_tile = blockIdx.x / a.ntiles;
-  }
-  const int split = blockIdx.y, cls = blockIdx.z;
-  const FmClass kc = fm_class(a, cls);
-  const int ksteps = kc.KH * kc.KW * a.C / BK;
-  const int sbeg = split * a.steps_per_split;
-  const int send = sbeg + a.steps_per_split < ksteps ? sbeg + a.steps_per_split : ksteps;
-  const int K = kc.KH * kc.KW * a.C;
-  const uint16_t* wcls = reinterpret_cast<const uint16_t*>(a.w) + kc.w_off;
-
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int c = lane & 15, q = lane >> 4;
-  const int row0 = BN == 128 ? (wave >> 1) * 64 : wave * 32, col0 = BN == 128 ? (wave & 1) * 64 : 0;
-
-  constexpr int QPR = BK / 4, RPP = kThreads / QPR, NUA = BM / RPP, NUB = BN / RPP;
-  const int r0 = t / QPR, kq = t % QPR;
-  const float* a_img[NUA];
-  int a_y0[NUA], a_x0[NUA];
-#pragma unroll
-  for (int u = 0; u < NUA; ++u) {
-    int m = m_tile * BM + r0 + RPP * u;
-    const bool valid = m < a.M;
-    m = valid ? m : a.M - 1;
-    const int img = m / (a.GH * a.GW), rem = m - img * (a.GH * a.GW);
-    const int y = rem / a.GW, x = rem - y * a.GW;
-    a_img[u] = a.src + (size_t)img * a.SH * a.SW * a.src_ld + 4 * kq;
-    a_y0[u] = valid ? y * a.ss - kc.pad_y : -(1 << 20);               // rows past M: every tap out of bounds -> zeros
-    a_x0[u] = x * a.ss - kc.pad_x;
-  }
-  const uint16_t* b_row[NUB];
-  bool b_ok[NUB];
-#pragma unroll
-  for (int u = 0; u < NUB; ++u) {
-    const int n = n_tile * BN + r0 + RPP * u;
-    b_ok[u] = n < a.N;
-    b_row[u] = wcls + (size_t)(b_ok[u] ? n : a.N - 1) * K + 4 * kq;
-  }
-  f32x4 ra[NUA];
-  u32x2 rb[NUB];
-  bool ra_ok[NUA];
-  auto fetch = [&](int step) {
-    const int k0 = step * BK;
-    const int tap = k0 / a.C, ci0 = k0 - tap * a.C;                    // uniform: one tap, 32 consecutive channels
-    const int kh = tap / kc.KW, kw = tap - kh * kc.KW;
-#pragma unroll
-    for (int u = 0; u < NUA; ++u) {
-      const int yy = a_y0[u] + kh, xx = a_x0[u] + kw;
-      const bool ok = (unsigned)yy < (unsigned)a.SH && (unsigned)xx < (unsigned)a.SW;
-      ra[u] = ldg4<4>(a_img[u] + (ok ? (size_t)(yy * a.SW + xx) * a.src_ld + ci0 : 0));
-      ra_ok[u] = ok;
-    }
-#pragma unroll
-    for (int u = 0; u < NUB; ++u) rb[u] = *reinterpret_cast<const u32x2*>(b_row[u] + k0);
-    pin_vmem();
-  };
-  auto stage = [&](int buf) {
-    uint16_t* As = smem_lp + buf * (BM + BN) * LD;
-    uint16_t* Bs = As + BM * LD;
-#pragma unroll
-    for (int u = 0; u < NUA; ++u) {
-      const u32x2 v = {fm_bf16_pair(ra[u][0], ra[u][1]), fm_bf16_pair(ra[u][2], ra[u][3])};
-      *reinterpret_cast<u32x2*>(As + (r0 + RPP * u) * LD + 4 * kq) = ra_ok[u] ? v : u32x2{0u, 0u};
-    }
-#pragma unroll
-    for (int u = 0; u < NUB; ++u)
-      *reinterpret_cast<u32x2*>(Bs + (r0 + RPP * u) * LD + 4 * kq) = b_ok[u] ? rb[u] : u32x2{0u, 0u};
-  };
-
-  f32x4 acc[TI][TJ];
-#pragma unroll
-  for (int i = 0; i < TI; ++i)
-#pragma unroll
-    for (int jn = 0; jn < TJ; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if (sbeg < send) {
-    fetch(sbeg);
-    stage(0);
-  }
-  __syncthreads();
-  int buf = 0;
-  for (int step = sbeg; step < send; ++step) {
-    const bool more = step + 1 < send;
-    if (more) fetch(step + 1);
-    const uint16_t* As = smem_lp + buf * (BM + BN) * LD + (row0 + c) * LD + 8 * q;
-    const uint16_t* Bs = smem_lp + buf * (BM + BN) * LD + BM * LD + (col0 + c) * LD + 8 * q;
-    bf16x8 af[TI], bf[TJ];
-#pragma unroll
-    for (int i = 0; i < TI; ++i) af[i] = *reinterpret_cast<const bf16x8*>(As + i * 16 * LD);
-#pragma unroll
-    for (int jn = 0; jn < TJ; ++jn) bf[jn] = *reinterpret_cast<const bf16x8*>(Bs + jn * 16 * LD);
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-      for (int jn = 0; jn < TJ; ++jn)
-        acc[i][jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[jn], af[i], acc[i][jn], 0, 0, 0);   // transposed tiles
-    pin_vmem();
-    if (more) stage(buf ^ 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-
-  // k_fm_gemm's epilogue without the statistics: a lane holds output pixel c and the columns 4q .. 4q+3 of each tile
-  const bool fin = a.nsplit == 1;
-  f32x4 bias4[TJ];
-  int colj[TJ];
-#pragma unroll
-  for (int jn = 0; jn < TJ; ++jn) {
-    bias4[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-    colj[jn] = n_tile * BN + col0 + jn * 16 + 4 * q;
-    if (fin && a.bias != nullptr && colj[jn] < a.N) bias4[jn] = *reinterpret_cast<const f32x4*>(a.bias + colj[jn]);
-  }
-#pragma unroll
-  for (int i = 0; i < TI; ++i) {
-    const int m = m_tile * BM + row0 + i * 16 + c;
-    if (m >= a.M) continue;
-    const size_t pix = fm_out_pixel_index(a, kc, m);
-    float* orow = fin ? a.out + pix * a.out_ld : a.part + ((size_t)(cls * a.nsplit + split) * a.M + m) * a.N;
-    f32x4 prev[TJ];
-#pragma unroll
-    for (int jn = 0; jn < TJ; ++jn) {
-      prev[jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (fin && a.accumulate && colj[jn] < a.N) prev[jn] = *reinterpret_cast<const f32x4*>(orow + colj[jn]);
-    }
-#pragma unroll
-    for (int jn = 0; jn < TJ; ++jn) {
-      const int col = colj[jn];
-      if (col >= a.N) {                                                // N is a multiple of 4
-        if (fin && col < a.zero_to) *reinterpret_cast<f32x4*>(orow + col) = f32x4{0.f, 0.f, 0.f, 0.f};
-        continue;
-      }
-      f32x4 v = acc[i][jn];
-      if (fin) {
-        v += bias4[jn];
-        v = f32x4{fm_act(v[0], a.act), fm_act(v[1], a.act), fm_act(v[2], a.act), fm_act(v[3], a.act)};
-        v += prev[jn];
-      }
-      *reinterpret_cast<f32x4*>(orow + col) = v;
-    }
-  }
-}
-
-// fp32 -> bf16 copies of the weights k_fm_gemm_bf16 reads, one launch for all of a network's segments (pack_lp_body,
-// ndp_device.h: the encoder's k_enc_pack_lp runs the same body)
-__global__ __launch_bounds__(kThreads) void k_fm_pack_lp(PackLpArgs a) { pack_lp_body(a); }
-
 // deconv6 (128 -> 32 channels at 128 x 128; deconv5, 64 channels, as two halves when it has the tiles): the FOUR parity
 // classes of a row tile in one workgroup.  As four mode-1
 // launches' worth of 128 x 32 tiles the layer staged every source pixel once per (class, tap) pair -- 16 operand tiles per
@@ -725,16 +551,21 @@ __global__ __launch_bounds__(kThreads) void k_fm_pack_lp(PackLpArgs a) { pack_lp
 // kw' = dx - px + 1 when both are 0 or 1.  Statistics (mode 1) over the 32 output channels, all classes together.
 // RELU: the stored output is max(v, 0) (the eval-mode decoder of ndp_autoencoder.inc, BatchNorm folded into w and bias: no
 // statistics there); the training paths' instantiation, RELU = false, is the kernel as it was.
+// The bf16 instantiation (precision NDP_FM_BF16: deconv6, and deconv5 where fm_geom chooses this form; measured against
+// mode 1 of k_fm_gemm's, 16 operand tiles per 32 channels instead of 9: DESIGN.md 5s) differs outside the operand path,
+// deliberately, in this: bias only -- no ReLU and no statistics, which the eval-mode pass never asks of these layers;
+// fm_deconv32 refuses such a launch.
 struct FmDcArgs {
-  const float* src; const float* w; const float* bias; float* out;
+  const float* src; const void* w; const float* bias; float* out;      // w: P::B::elem of the launched path P
   int src_ld, SH, SW, out_ld, M, C, N, mtiles;        // N output channels: blockIdx.y = which 32 of them
   FmStatEp ep;
 };
-constexpr int fm_deconv32_lds_floats() { return 2 * (kFmBM + 128) * kFmLD; }
-template <bool RELU>
+template <bool RELU, class P = FmF32>
 __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  constexpr int BM = kFmBM, BK = kFmBK, LD = kFmLD, NB = 128;           // NB: 4 classes x 32 output channels
+  using SA = typename P::A; using SB = typename P::B; using Mma = typename P::Mma;
+  static_assert(!(P::kLp && RELU), "k_fm_deconv32: the bf16 instantiation has no ReLU");
+  extern __shared__ __attribute__((aligned(16))) float smem[];       // the statistics' scratch (the tiles: Mma::tiles())
+  constexpr int BM = kFmBM, BK = kFmBK, LD = Mma::LD, V = P::V, NB = 128;   // NB: 4 classes x 32 output channels
   int m_tile;
   if (a.mtiles >= 8) {
     const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
@@ -746,9 +577,10 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int c = lane & 15, q = lane >> 4;
   const int row0 = wave * 32;
-  constexpr int QPR = BK / 4, RPP = kThreads / QPR, NUA = BM / RPP;      // 8 float4 per row, 32 rows per pass, 4 passes
+  constexpr int QPR = BK / V, RPP = kThreads / QPR, NUA = BM / RPP;      // 8 quads per row, 32 rows per pass, 4 passes
+  static_assert(RPP == 32, "k_fm_deconv32: a pass of B rows is one class's 32 output channels");
   const int r0 = t / QPR, kq = t % QPR;
-  const float* a_img[NUA];
+  const typename SA::elem* a_img[NUA];
   int a_y[NUA], a_x[NUA];
 #pragma unroll
   for (int u = 0; u < NUA; ++u) {
@@ -757,17 +589,18 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
     m = valid ? m : a.M - 1;
     const int img = m / (a.SH * a.SW), rem = m - img * (a.SH * a.SW);
     const int y = rem / a.SW, x = rem - y * a.SW;
-    a_img[u] = a.src + (size_t)img * a.SH * a.SW * a.src_ld + 4 * kq;
+    a_img[u] = a.src + (size_t)img * a.SH * a.SW * a.src_ld + V * kq;
     a_y[u] = valid ? y : -(1 << 20);
     a_x[u] = x;
   }
   // B rows: pass u = class u, row r0 = output channel
-  const float* b_cls[4];
+  const typename SB::elem* b_cls[4];
   const int co0 = blockIdx.y * 32;
 #pragma unroll
-  for (int u = 0; u < 4; ++u) b_cls[u] = a.w + ((size_t)u * a.N + co0 + r0) * 4 * a.C + 4 * kq;
+  for (int u = 0; u < 4; ++u) b_cls[u] = static_cast<const typename SB::elem*>(a.w) + ((size_t)u * a.N + co0 + r0) * 4 * a.C + V * kq;
   const int chunks = a.C / BK, nsteps = 9 * chunks;
-  f32x4 ra[NUA], rb[4];
+  typename SA::reg ra[NUA];
+  typename SB::reg rb[4];
   bool ra_ok[NUA];
   auto fetch = [&](int step) {
     const int tap = step / chunks, ci0 = (step - tap * chunks) * BK;
@@ -776,28 +609,27 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
     for (int u = 0; u < NUA; ++u) {
       const int yy = a_y[u] + dy, xx = a_x[u] + dx;
       const bool ok = (unsigned)yy < (unsigned)a.SH && (unsigned)xx < (unsigned)a.SW;
-      ra[u] = ldg4<4>(a_img[u] + (ok ? (size_t)(yy * a.SW + xx) * a.src_ld + ci0 : 0));
+      ra[u] = SA::load(a_img[u] + (ok ? (size_t)(yy * a.SW + xx) * a.src_ld + ci0 : 0));
       ra_ok[u] = ok;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
-      if ((unsigned)khp < 2u && (unsigned)kwp < 2u) rb[u] = ldg4<4>(b_cls[u] + (size_t)(khp * 2 + kwp) * a.C + ci0);   // (uniform)
+      if ((unsigned)khp < 2u && (unsigned)kwp < 2u) rb[u] = SB::load(b_cls[u] + (size_t)(khp * 2 + kwp) * a.C + ci0);   // (uniform)
     }
     pin_vmem();
   };
   auto stage = [&](int buf, int step) {
     const int tap = step / chunks;
     const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
-    float* As = smem + buf * (BM + NB) * LD;
-    float* Bs = As + BM * LD;
+    typename P::lds* As = Mma::tiles() + buf * (BM + NB) * LD;
+    typename P::lds* Bs = As + BM * LD;
 #pragma unroll
-    for (int u = 0; u < NUA; ++u)
-      *reinterpret_cast<f32x4*>(As + (r0 + RPP * u) * LD + 4 * kq) = ra_ok[u] ? ra[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int u = 0; u < NUA; ++u) *reinterpret_cast<typename SA::quad*>(As + (r0 + RPP * u) * LD + V * kq) = SA::staged(ra[u], ra_ok[u]);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
-      if ((unsigned)khp < 2u && (unsigned)kwp < 2u) *reinterpret_cast<f32x4*>(Bs + (u * 32 + r0) * LD + 4 * kq) = rb[u];
+      if ((unsigned)khp < 2u && (unsigned)kwp < 2u) *reinterpret_cast<typename SB::quad*>(Bs + (u * 32 + r0) * LD + V * kq) = SB::staged(rb[u]);
     }
   };
   f32x4 acc[2][8];
@@ -815,30 +647,28 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
     if (more) fetch(step + 1);
     const int tap = step / chunks;
     const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
-    const float* As = smem + buf * (BM + NB) * LD + (row0 + c) * LD + 4 * q;
-    const float* Bs = smem + buf * (BM + NB) * LD + BM * LD + c * LD + 4 * q;
-    f32x4 af[2][2];
+    const typename P::lds* As = Mma::tiles() + buf * (BM + NB) * LD + (row0 + c) * LD + Mma::KQ * q;
+    const typename P::lds* Bs = Mma::tiles() + buf * (BM + NB) * LD + BM * LD + c * LD + Mma::KQ * q;
+    typename Mma::frag af[2];
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < Mma::PARTS; ++h)
 #pragma unroll
-      for (int i = 0; i < 2; ++i) af[h][i] = *reinterpret_cast<const f32x4*>(As + i * 16 * LD + 16 * h);
+      for (int i = 0; i < 2; ++i) Mma::read(af[i], As + i * 16 * LD, h);
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
       if ((unsigned)khp >= 2u || (unsigned)kwp >= 2u) continue;       // (uniform: this tap is not one of class u's)
-      f32x4 bf[2][2];
+      typename Mma::frag bf[2];
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+      for (int h = 0; h < Mma::PARTS; ++h)
 #pragma unroll
-        for (int jn = 0; jn < 2; ++jn) bf[h][jn] = *reinterpret_cast<const f32x4*>(Bs + (u * 32 + jn * 16) * LD + 16 * h);
+        for (int jn = 0; jn < 2; ++jn) Mma::read(bf[jn], Bs + (u * 32 + jn * 16) * LD, h);
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
+      for (int ks = 0; ks < Mma::KSUB; ++ks)
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int jn = 0; jn < 2; ++jn) acc[i][u * 2 + jn] = mfma16(bf[h][jn][e], af[h][i][e], acc[i][u * 2 + jn]);
+          for (int jn = 0; jn < 2; ++jn) acc[i][u * 2 + jn] = Mma::mma(bf[jn], af[i], acc[i][u * 2 + jn], ks);
     }
     pin_vmem();
     if (more) stage(buf ^ 1, step + 1);
@@ -847,7 +677,7 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
   }
 
   // a lane holds row (grid position) c of a tile and output channels 4q .. 4q + 3 of each 16-column tile
-  const bool stat = a.ep.mode != 0;
+  const bool stat = !P::kLp && a.ep.mode != 0;
   f32x4 cs1[2], cs2[2], bias4[2];
 #pragma unroll
   for (int jn = 0; jn < 2; ++jn) {
@@ -907,142 +737,6 @@ __global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32(FmDcArgs a) {
   fm_stat_publish(a.ep, m_tile, co0, 32, sums);
 }
 
-// k_fm_deconv32 with bf16 MFMA operands (precision NDP_FM_BF16: deconv6, and deconv5 where fm_geom chooses this form): the
-// same walk over the nine taps, tiles, weight order and output placement; the operand path is k_fm_gemm_bf16's (the source
-// tile rounded where it is staged, 8 bytes per 4 values from the bf16 weights in a.w, one 16-byte LDS read per lane and
-// 32-wide K step, row stride kFmLpLD).  Bias only: no activation and no statistics, which the eval-mode pass never asks of
-// these layers.  Measured against mode 1 of k_fm_gemm_bf16 (16 operand tiles per 32 channels instead of 9): DESIGN.md 5s.
-constexpr int fm_deconv32_bf16_lds_bytes() { return 2 * (kFmBM + 128) * kFmLpLD * 2; }
-__global__ __launch_bounds__(kThreads, 2) void k_fm_deconv32_bf16(FmDcArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t smem_lp[];
-  constexpr int BM = kFmBM, BK = kFmBK, LD = kFmLpLD, NB = 128;         // NB: 4 classes x 32 output channels
-  int m_tile;
-  if (a.mtiles >= 8) {
-    const int xcd = blockIdx.x & 7, jb = blockIdx.x >> 3;
-    m_tile = jb * 8 + xcd;
-    if (m_tile >= a.mtiles) return;
-  } else {
-    m_tile = blockIdx.x;
-  }
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int c = lane & 15, q = lane >> 4;
-  const int row0 = wave * 32;
-  constexpr int QPR = BK / 4, RPP = kThreads / QPR, NUA = BM / RPP;
-  const int r0 = t / QPR, kq = t % QPR;
-  const float* a_img[NUA];
-  int a_y[NUA], a_x[NUA];
-#pragma unroll
-  for (int u = 0; u < NUA; ++u) {
-    int m = m_tile * BM + r0 + RPP * u;
-    const bool valid = m < a.M;
-    m = valid ? m : a.M - 1;
-    const int img = m / (a.SH * a.SW), rem = m - img * (a.SH * a.SW);
-    const int y = rem / a.SW, x = rem - y * a.SW;
-    a_img[u] = a.src + (size_t)img * a.SH * a.SW * a.src_ld + 4 * kq;
-    a_y[u] = valid ? y : -(1 << 20);
-    a_x[u] = x;
-  }
-  const uint16_t* b_cls[4];                                            // B rows: pass u = class u, row r0 = output channel
-  const int co0 = blockIdx.y * 32;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) b_cls[u] = reinterpret_cast<const uint16_t*>(a.w) + ((size_t)u * a.N + co0 + r0) * 4 * a.C + 4 * kq;
-  const int chunks = a.C / BK, nsteps = 9 * chunks;
-  f32x4 ra[NUA];
-  u32x2 rb[4];
-  bool ra_ok[NUA];
-  auto fetch = [&](int step) {
-    const int tap = step / chunks, ci0 = (step - tap * chunks) * BK;
-    const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
-#pragma unroll
-    for (int u = 0; u < NUA; ++u) {
-      const int yy = a_y[u] + dy, xx = a_x[u] + dx;
-      const bool ok = (unsigned)yy < (unsigned)a.SH && (unsigned)xx < (unsigned)a.SW;
-      ra[u] = ldg4<4>(a_img[u] + (ok ? (size_t)(yy * a.SW + xx) * a.src_ld + ci0 : 0));
-      ra_ok[u] = ok;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
-      if ((unsigned)khp < 2u && (unsigned)kwp < 2u)                     // (uniform)
-        rb[u] = *reinterpret_cast<const u32x2*>(b_cls[u] + (size_t)(khp * 2 + kwp) * a.C + ci0);
-    }
-    pin_vmem();
-  };
-  auto stage = [&](int buf, int step) {
-    const int tap = step / chunks;
-    const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
-    uint16_t* As = smem_lp + buf * (BM + NB) * LD;
-    uint16_t* Bs = As + BM * LD;
-#pragma unroll
-    for (int u = 0; u < NUA; ++u) {
-      const u32x2 v = {fm_bf16_pair(ra[u][0], ra[u][1]), fm_bf16_pair(ra[u][2], ra[u][3])};
-      *reinterpret_cast<u32x2*>(As + (r0 + RPP * u) * LD + 4 * kq) = ra_ok[u] ? v : u32x2{0u, 0u};
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
-      if ((unsigned)khp < 2u && (unsigned)kwp < 2u) *reinterpret_cast<u32x2*>(Bs + (u * 32 + r0) * LD + 4 * kq) = rb[u];
-    }
-  };
-  f32x4 acc[2][8];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int jn = 0; jn < 8; ++jn) acc[i][jn] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  fetch(0);
-  stage(0, 0);
-  __syncthreads();
-  int buf = 0;
-  for (int step = 0; step < nsteps; ++step) {
-    const bool more = step + 1 < nsteps;
-    if (more) fetch(step + 1);
-    const int tap = step / chunks;
-    const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
-    const uint16_t* As = smem_lp + buf * (BM + NB) * LD + (row0 + c) * LD + 8 * q;
-    const uint16_t* Bs = smem_lp + buf * (BM + NB) * LD + BM * LD + c * LD + 8 * q;
-    bf16x8 af[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) af[i] = *reinterpret_cast<const bf16x8*>(As + i * 16 * LD);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int khp = dy - (u >> 1) + 1, kwp = dx - (u & 1) + 1;
-      if ((unsigned)khp >= 2u || (unsigned)kwp >= 2u) continue;       // (uniform: this tap is not one of class u's)
-      bf16x8 bf[2];
-#pragma unroll
-      for (int jn = 0; jn < 2; ++jn) bf[jn] = *reinterpret_cast<const bf16x8*>(Bs + (u * 32 + jn * 16) * LD);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int jn = 0; jn < 2; ++jn)
-          acc[i][u * 2 + jn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bf[jn], af[i], acc[i][u * 2 + jn], 0, 0, 0);
-    }
-    pin_vmem();
-    if (more) stage(buf ^ 1, step + 1);
-    __syncthreads();
-    buf ^= 1;
-  }
-
-  // a lane holds row (grid position) c of a tile and output channels 4q .. 4q + 3 of each 16-column tile
-  f32x4 bias4[2];
-#pragma unroll
-  for (int jn = 0; jn < 2; ++jn) bias4[jn] = *reinterpret_cast<const f32x4*>(a.bias + co0 + jn * 16 + 4 * q);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    const int m = m_tile * BM + row0 + i * 16 + c;
-    if (m >= a.M) continue;
-    const int img = m / (a.SH * a.SW), rem = m - img * (a.SH * a.SW);
-    const int y = rem / a.SW, x = rem - y * a.SW;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const size_t pix = ((size_t)img * 2 * a.SH + 2 * y + (u >> 1)) * 2 * a.SW + 2 * x + (u & 1);
-      float* orow = a.out + pix * a.out_ld + co0;
-#pragma unroll
-      for (int jn = 0; jn < 2; ++jn) *reinterpret_cast<f32x4*>(orow + jn * 16 + 4 * q) = acc[i][u * 2 + jn] + bias4[jn];
-    }
-  }
-}
-
 // The 4x4 <-> 1x1 layers (deconv1 forward, conv6's data gradient: mode 3, sixteen one-tap classes) at a handful of rows:
 // the rows are the IMAGES, so at 8 images a 128-row tile is 94 % padding, and each of the 128 (class, column tile)
 // workgroups staged 80 KB of weights through LDS for five K steps: 24-25 us for 2 M MACs per image.  Here a WAVE owns one
@@ -1060,7 +754,7 @@ __global__ __launch_bounds__(kThreads) void k_fm_rows_cls(FmGemmArgs a) {
   const FmClass kc = fm_class(a, cls);
   const int nk = a.C / 16;                                             // k groups of 16 (C is a multiple of 32)
   f32x4 wf[kFmRowsMaxC / 16];
-  const float* wrow = a.w + kc.w_off + (size_t)(n0 + c) * a.C + 4 * q;
+  const float* wrow = static_cast<const float*>(a.w) + kc.w_off + (size_t)(n0 + c) * a.C + 4 * q;
 #pragma unroll
   for (int t = 0; t < kFmRowsMaxC / 16; ++t) wf[t] = t < nk ? *reinterpret_cast<const f32x4*>(wrow + 16 * t) : f32x4{0.f, 0.f, 0.f, 0.f};
   const int col = n0 + 4 * q;
@@ -2697,13 +2391,13 @@ struct FmView { float* p; int ld; };
 static std::once_flag g_fm_attr_once[kMaxDevices];
 static void fm_attrs() {
   std::call_once(device_once(g_fm_attr_once), [] {
-    allow_lds(k_fm_gemm<128>, fm_gemm_lds_floats<128>() * 4);
-    allow_lds(k_fm_gemm<32>, fm_gemm_lds_floats<32>() * 4);
-    allow_lds(k_fm_gemm_bf16<128>, fm_gemm_bf16_lds_bytes<128>());
-    allow_lds(k_fm_gemm_bf16<32>, fm_gemm_bf16_lds_bytes<32>());
-    allow_lds(k_fm_deconv32_bf16, fm_deconv32_bf16_lds_bytes());
-    allow_lds(k_fm_deconv32<false>, fm_deconv32_lds_floats() * 4);
-    allow_lds(k_fm_deconv32<true>, fm_deconv32_lds_floats() * 4);
+    allow_lds((k_fm_gemm<128, FmF32>), FmF32::lds_bytes(kFmBM + 128));
+    allow_lds((k_fm_gemm<32, FmF32>), FmF32::lds_bytes(kFmBM + 32));
+    allow_lds((k_fm_gemm<128, FmBf16>), FmBf16::lds_bytes(kFmBM + 128));
+    allow_lds((k_fm_gemm<32, FmBf16>), FmBf16::lds_bytes(kFmBM + 32));
+    allow_lds((k_fm_deconv32<false, FmF32>), FmF32::lds_bytes(kFmBM + 128));
+    allow_lds((k_fm_deconv32<true, FmF32>), FmF32::lds_bytes(kFmBM + 128));      // (the eval-mode decoder of ndp_autoencoder.inc)
+    allow_lds((k_fm_deconv32<false, FmBf16>), FmBf16::lds_bytes(kFmBM + 128));
     allow_lds((k_fm_wgrad<64, 64>), (fm_wgrad_lds_floats<64, 64>() * 4));
     allow_lds((k_fm_wgrad<32, 64>), (fm_wgrad_lds_floats<32, 64>() * 4));
     allow_lds((k_fm_wgrad<32, 16>), (fm_wgrad_lds_floats<32, 16>() * 4));
@@ -2761,8 +2455,9 @@ constexpr int kFmSplitTarget = 256;
 
 // out = act(bias + gather-GEMM) [+ out]; see k_fm_gemm for the modes.  GH = grid of rows per image (square maps).
 // rq: statistics of the finished output, from this launch's epilogue or -- with a K split -- from the split sums'.
-// lp: `w` is the address of the layer's bf16 weights and the launch is k_fm_gemm_bf16 (modes 0 and 1, no statistics).
-static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int SH, int ss, const float* w, const float* bias,
+// lp: `w` is the address of the layer's bf16 weights and the launch is k_fm_gemm's bf16 instantiation (modes 0 and 1, no
+// statistics); otherwise `w` is fp32.
+static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int SH, int ss, const void* w, const float* bias,
                    FmView out, int OH, int GH, int64_t n, int C, int N, int KH, int pad, int act, int accumulate,
                    const FmWs& ws, const FmEpReq* rq = nullptr, bool lp = false) {
   if (lp && (mode > 1 || (rq != nullptr && rq->mode != 0)))
@@ -2818,10 +2513,13 @@ static int fm_gemm(hipStream_t st, const char* label, int mode, FmView src, int 
   const dim3 grid((unsigned)gx, (unsigned)a.nsplit, (unsigned)(a.cls_units > 0 ? 1 : ncls));
   {
     KTimer kt(label, st);
-    if (lp && bn == 128) hipLaunchKernelGGL(k_fm_gemm_bf16<128>, grid, dim3(kThreads), fm_gemm_bf16_lds_bytes<128>(), st, a);
-    else if (lp) hipLaunchKernelGGL(k_fm_gemm_bf16<32>, grid, dim3(kThreads), fm_gemm_bf16_lds_bytes<32>(), st, a);
-    else if (bn == 128) hipLaunchKernelGGL(k_fm_gemm<128>, grid, dim3(kThreads), fm_gemm_lds_floats<128>() * 4, st, a);
-    else hipLaunchKernelGGL(k_fm_gemm<32>, grid, dim3(kThreads), fm_gemm_lds_floats<32>() * 4, st, a);
+    auto launch = [&](auto path) {
+      using P = decltype(path);
+      if (bn == 128) hipLaunchKernelGGL((k_fm_gemm<128, P>), grid, dim3(kThreads), P::lds_bytes(kFmBM + 128), st, a);
+      else hipLaunchKernelGGL((k_fm_gemm<32, P>), grid, dim3(kThreads), P::lds_bytes(kFmBM + 32), st, a);
+    };
+    if (lp) launch(FmBf16{});
+    else launch(FmF32{});
   }
   rc = check_launch("k_fm_gemm");
   if (rc || a.nsplit == 1) return rc;
@@ -3013,7 +2711,7 @@ static int fm_bn_bwd_at(hipStream_t st, int b, FmView raw, FmView y, FmView dy, 
 }
 
 // deconv6's forward pass, the four parity classes per workgroup (k_fm_deconv32)
-static int fm_deconv32(hipStream_t st, const char* label, FmView src, int SH, const float* w, const float* bias, FmView out,
+static int fm_deconv32(hipStream_t st, const char* label, FmView src, int SH, const void* w, const float* bias, FmView out,
                        int64_t n, int C, int N, const FmEpReq& rq, const FmWs& ws, bool relu = false, bool lp = false) {
   if (lp && (relu || rq.mode != 0)) return fail(NDP_E_UNSUPPORTED, "forward model: %s has no bf16 launch of this kind", label);
   FmDcArgs a;
@@ -3025,9 +2723,9 @@ static int fm_deconv32(hipStream_t st, const char* label, FmView src, int SH, co
   const unsigned gx = a.mtiles >= 8 ? 8u * (unsigned)((a.mtiles + 7) / 8) : (unsigned)a.mtiles;
   KTimer kt(label, st);
   const dim3 grid(gx, (unsigned)(N / 32));
-  if (lp) hipLaunchKernelGGL(k_fm_deconv32_bf16, grid, dim3(kThreads), fm_deconv32_bf16_lds_bytes(), st, a);   // (w: bf16 weights)
-  else if (relu) hipLaunchKernelGGL(k_fm_deconv32<true>, grid, dim3(kThreads), fm_deconv32_lds_floats() * 4, st, a);
-  else hipLaunchKernelGGL(k_fm_deconv32<false>, grid, dim3(kThreads), fm_deconv32_lds_floats() * 4, st, a);
+  if (lp) hipLaunchKernelGGL((k_fm_deconv32<false, FmBf16>), grid, dim3(kThreads), FmBf16::lds_bytes(kFmBM + 128), st, a);
+  else if (relu) hipLaunchKernelGGL((k_fm_deconv32<true, FmF32>), grid, dim3(kThreads), FmF32::lds_bytes(kFmBM + 128), st, a);
+  else hipLaunchKernelGGL((k_fm_deconv32<false, FmF32>), grid, dim3(kThreads), FmF32::lds_bytes(kFmBM + 128), st, a);
   return check_launch(label);
 }
 
@@ -3162,7 +2860,7 @@ static int fm_layer_fwd(const FmRun& r, int l, int act, const FmEpReq& rq) {
     // bf16 operands: the same geometry and kernel choice, the bf16 copy of the weight order the launch reads
     FmView lsrc, lout;
     fm_layer_views(r.net, r.m, l, FM_FWD, &lsrc, &lout);
-    const float* lw = reinterpret_cast<const float*>(r.lp + fm_lp_offset(r.net, l));
+    const uint16_t* lw = r.lp + fm_lp_offset(r.net, l);
     if (g.deconv32 && act == 0)
       return fm_deconv32(r.st, kFmLpLabel[l], lsrc, g.SH, lw, fm_bias(r, l), lout, r.n, g.C, g.N, rq, r.ws, false, true);
     return fm_gemm(r.st, kFmLpLabel[l], g.mode, lsrc, g.SH, g.ss, lw, fm_bias(r, l), lout, g.OH, g.GH, r.n, g.C, g.N, g.KH, g.pad,
@@ -3260,7 +2958,7 @@ static int fm_pack_lp(hipStream_t st, const FmNet& net, const float* params, con
     a.block_begin[i + 1] = a.block_begin[i] + (int)((a.count[i] + 4095) / 4096);
   }
   KTimer kt("k_fm_pack_lp", st);
-  hipLaunchKernelGGL(k_fm_pack_lp, dim3((unsigned)a.block_begin[a.nseg]), dim3(kThreads), 0, st, a);
+  hipLaunchKernelGGL(k_pack_lp, dim3((unsigned)a.block_begin[a.nseg]), dim3(kThreads), 0, st, a);
   return check_launch("k_fm_pack_lp");
 }
 

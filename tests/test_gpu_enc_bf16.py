@@ -1,5 +1,5 @@
 """GPU: the image encoder's pass with bf16 MFMA operands and bf16 maps (ndp_encoder_forward_lp with NDP_ENC_BF16,
-ndp_encoder_pack_params_lp; k_conv_gemm_bf16, k_enc_conv1<., true>, k_splitk_reduce_bf16 in csrc/ndp_encoder.inc) held to
+ndp_encoder_pack_params_lp; k_conv_gemm's bf16 path, k_enc_conv1<., true>, k_splitk_reduce<__bf16> in csrc/ndp_encoder.inc) held to
 its definition in include/ndp.h, on EO.init_encoder_state(11, bn_seed=12) and EO.synthetic_images at
 
   n = 1    every deep layer is K-split; conv5 is a 16-row partial tile

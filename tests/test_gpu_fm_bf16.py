@@ -1,8 +1,8 @@
 """GPU: the eval-mode forward model with bf16 MFMA operands (ndp_fm_forward_lp with NDP_FM_BF16, ndp_fm_pack_params_lp;
-k_fm_gemm_bf16 in csrc/ndp_forward_model.inc) held to its definition in include/ndp.h, on the golden model of
+k_fm_gemm's bf16 path in csrc/ndp_forward_model.inc) held to its definition in include/ndp.h, on the golden model of
 tests/golden/fm_eval_case.npz at n = 1, 3 and 9 images (the K-split path with a partial 128-row tile; odd row counts; conv5
 crossing a tile boundary with 144 rows; conv2 with 8 and more row tiles, the XCD order, at every n) and at n = 16, where
-deconv5 changes from mode 1 of k_fm_gemm_bf16 to k_fm_deconv32_bf16 (deconv6 takes it at every n), float and byte frames.
+deconv5 changes from mode 1 of k_fm_gemm to k_fm_deconv32, both on the bf16 path (deconv6 takes it at every n), float and byte frames.
 
 Bounds.  Layer by layer, so that nothing compounds: each of the nine layers' stored output against the fp64 convolution of
 the ROUNDED device input and the rounded weights -- bf16 products are exact in fp32, only the order of the fp32 sum can
